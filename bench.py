@@ -6,9 +6,14 @@ LocalDeformableBundleAdjustment solve, optimize(5) (reference g2o_optimization.c
 to HBM once, outside the timed region; each timed step is {reset estimates (device-to-device), optimize(5)}.
 
 N = 1: BASELINE.json configs[1] (C2: 5k map points x 20 keyframes, pinhole), every point a deformation-graph node
-(parity mode).  The line also carries `value_exact_trials` (every LM trial solved to 1e-10, as
-g2o does; `value` uses the early-rejection heuristic of nrs_options), the rooflines of the two dominant kernels
-(HIP events on the context's stream), the tracked-fps half of the metric and the CPU baseline (C++ restatement).
+(parity mode).  A plain run sets up, warms up, times --steps steps and prints the line.  With --full
+the line also carries `value_exact_trials` (every LM trial solved to 1e-10, as g2o does; `value` uses the early-rejection
+heuristic of nrs_options), the rooflines of the two dominant kernels (HIP events on the context's stream), the
+tracked-fps half of the metric, the other legs and the CPU baseline (C++ restatement).
+
+--dump-outputs DIR: after the timed steps, the keyframe poses and map points of the last step (what nrs_dba_download
+hands a caller) go to DIR/poses_qt.npy and DIR/landmarks_xyz.npy, float64.  The inputs are seeded: the same arguments
+give the same inputs in every run.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): `value` comes from ONE window -- BASELINE.json
 configs[3] (C4: 50k points x 200 keyframes) -- sharded over the N ranks by keyframes, in this process: RCCL
@@ -420,10 +425,23 @@ def timed_steps(ctx, steps, warmup, barrier):
     return dict(dt=time.perf_counter() - t0, lm_iters=lm_iters, trials=trials, inner=inner)
 
 
-def run_sharded(dist, rank, world, local_rank, steps, warmup, barrier, window, dev):
+def download_outputs(ctx):
+    """what the timed path hands its caller after the last step: keyframe poses [q | t] and map points, float64"""
+    pq, xyz = ctx.dba_download()
+    return dict(poses_qt=pq, landmarks_xyz=xyz)
+
+
+def dump_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
+def run_sharded(dist, rank, world, local_rank, steps, warmup, barrier, window, dev, download=False):
     """ONE window over all ranks, in this process.  The RCCL unique id is made by rank 0's library and broadcast
     with torch.distributed; every rank uploads the same window and owns a contiguous keyframe range of it
-    (nrs_shard_plan); reset / optimize are collective.  Returns this rank's timing."""
+    (nrs_shard_plan); reset / optimize are collective.  Returns this rank's timing (and, with `download`, the window's
+    outputs after the last step: every rank takes part in the download)."""
     import torch
     import nrs
     p, e, cam, qt = window
@@ -443,20 +461,22 @@ def run_sharded(dist, rank, world, local_rank, steps, warmup, barrier, window, d
     ctx.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
     t_up = time.perf_counter() - t_up
     res = timed_steps(ctx, steps, warmup, barrier)
+    if download:
+        res["outputs"] = download_outputs(ctx)
     kb = nrs.shard_plan(len(qt), p["lm_kf"], world)
     res.update(upload_s=t_up, keyframes_of_rank=[int(kb[rank]), int(kb[rank + 1])], rccl_world=ctx.comm_rank()[1])
     ctx.close()
     return res
 
 
-def sharded_section(dist, rank, world, local_rank, steps, warmup, barrier, window, dev):
+def sharded_section(dist, rank, world, local_rank, steps, warmup, barrier, window, dev, download=False):
     """run_sharded + agreement: returns (result, None) on every rank, or (None, error text) on every rank.  Failures
     that every rank sees (no device, librccl missing, a window that cannot be split) come back as errors; a rank that
     dies inside a collective is the watchdog's business (main)."""
     import torch
     err, res = None, None
     try:
-        res = run_sharded(dist, rank, world, local_rank, steps, warmup, barrier, window, dev)
+        res = run_sharded(dist, rank, world, local_rank, steps, warmup, barrier, window, dev, download)
     except Exception as ex:
         err = "rank %d: %r" % (rank, ex)
     ok = torch.tensor([0.0 if err else 1.0], dtype=torch.float64, device=dev)
@@ -852,11 +872,16 @@ def main():
     ap.add_argument("--sharded-workload", default="C4", help="N > 1: the ONE window that is sharded over the ranks")
     ap.add_argument("--sharded-points", type=int, default=0, help="override the sharded window's map points (tests)")
     ap.add_argument("--sharded-kf", type=int, default=0, help="override the sharded window's keyframes (tests)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-regime", action="store_true", help="skip the bounded C4 leg (operator + lineariser in the HBM regime)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary legs: exact trials, rooflines, one-shot cost, tracked fps, "
+                    "graph / triangulation / Shi-Tomasi / skinned legs, CPU baselines (N > 1: rank 0 alone on the sharded window)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the poses and map points of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-hbm-regime", action="store_true", help="--full: skip the bounded C4 leg (operator + lineariser in the HBM regime)")
     ap.add_argument("--no-sharded", action="store_true", help="N > 1: independent windows only")
     ap.add_argument("--sharded-timeout", type=float, default=900.0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -881,6 +906,7 @@ def main():
     ctx = nrs.Context(device=local_rank)          # fails loudly without a HIP device
     ctx.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
     r = timed_steps(ctx, args.steps, args.warmup, barrier)
+    outputs = download_outputs(ctx) if args.dump_outputs else None
     dev = "cuda" if dist is not None else None
     dt, lm_iters_all = reduce_over_ranks(dist, r["dt"], r["lm_iters"], dev)
     arith = "fp64 state / normal equations / PCG, fp32 projection and projection Jacobian (as the reference)"
@@ -910,7 +936,7 @@ def main():
         with open(nrs.LIB_PATH, "rb") as fh:
             out["build"] = {"library": os.path.relpath(nrs.LIB_PATH, ROOT), "sha256_16": hashlib.sha256(fh.read()).hexdigest()[:16],
                             "last_build": bm or "no record: the library travelled prebuilt with the snapshot"}
-    if not multi and rank == 0:
+    if args.full and not multi and rank == 0:
         # ---- the same steps with every LM trial solved to pcg_rtol (g2o's behaviour; `value` rejects hopeless trials early)
         xctx = nrs.Context(device=local_rank, exact_trials=1)
         xctx.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
@@ -1010,11 +1036,12 @@ def main():
         sn, sk, _, smodel = S.CONFIGS[args.sharded_workload]
         sn, sk = args.sharded_points or sn, args.sharded_kf or sk
         win = make_window(args.sharded_workload, 0, sn, sk)          # the same window on every rank
-        res, err = sharded_section(dist, rank, world, local_rank, args.steps, args.warmup, barrier, win, "cuda")
+        res, err = sharded_section(dist, rank, world, local_rank, args.steps, args.warmup, barrier, win, "cuda", bool(args.dump_outputs))
         if res is not None:
             sdt, _ = reduce_over_ranks(dist, res["dt"], 0.0, "cuda")
+            outputs = res.pop("outputs", None)
             single = None
-            if rank == 0 and world > 1:
+            if args.full and rank == 0 and world > 1:
                 # rank 0 alone on the same window (the other ranks wait at the barrier below)
                 c1 = nrs.Context(device=local_rank)
                 pw, ew, camw, qtw = win
@@ -1042,6 +1069,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         flush_c_stdio()                      # RCCL's start-up banner sits in the C stdio buffer: the JSON line comes last
         print(json.dumps(out), flush=True)
 

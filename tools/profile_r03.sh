@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-3 profiling recipe (run on the GPU box through gpurun from the repo root):
-#   1) rocprofv3 --kernel-trace --stats of the default bench command            -> per-kernel durations (C2)
+#   1) rocprofv3 --kernel-trace --stats of the bench command with --full            -> per-kernel durations (C2)
 #   2) separate --pmc passes (FETCH_SIZE / WRITE_SIZE cannot share a pass; SQ set on its own) on C2 and on C4
 #      (C4 = the HBM regime: ~14 GB resident, far beyond the 256 MB Infinity Cache)
 #   3) kernel-trace of one C4 optimize(1) for the full-launch durations the C4 roofline lines use
@@ -11,7 +11,7 @@ R=$PWD
 OUT=$R/gpurun_out/r03
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o bench -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-hbm-regime > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
+timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o bench -- python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-hbm-regime > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 for W in C2 C4; do
   timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/pmc_fetch_$W -o p -- python $R/tools/c4_probe.py $W 2 > $OUT/pmc_fetch_$W.log 2>&1
   timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $OUT/pmc_write_$W -o p -- python $R/tools/c4_probe.py $W 2 > $OUT/pmc_write_$W.log 2>&1
@@ -22,7 +22,7 @@ timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_M
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES -f csv -d $OUT/pmc_insts_C4 -o p -- python $R/tools/c4_probe.py C4 1 > $OUT/pmc_insts_C4.log 2>&1
 NRS_NO_PLAIN=1 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES -f csv -d $OUT/pmc_insts_C4_generic -o p -- python $R/tools/c4_probe.py C4 1 > $OUT/pmc_insts_C4_generic.log 2>&1
 cd $R
-timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 200 python tools/lin_probe.py C2 C3 C4 2>&1 | grep workload > $OUT/lin_probe.jsonl
 find $OUT -name "*.csv" -size +20M -delete
 ls -R $OUT | head -60
