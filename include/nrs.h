@@ -100,7 +100,8 @@ typedef struct {
                                  458 node copies x 20 keyframes; the PCG wins beyond), block-Jacobi PCG else;
                                  1: always the factorisation (if its K x (3 nodes + 6)^2 x 8 bytes fit 6 GB);
                                  2: always block-Jacobi PCG (hundreds of iterations per trial).  Same LM iterates either
-                                 way.  Plain (every point a node) and sharded windows use the block-Jacobi PCG.
+                                 way.  Plain (every point a node) and sharded windows use the block-Jacobi PCG: on a context
+                                 with a communicator an embedded window always solves by block-Jacobi PCG, whatever this says.
                                  (Sits where the 40-byte layout had padding: values outside 0..2 are read as 0.) */
 } nrs_options;
 void nrs_options_init(nrs_options* opt);
@@ -217,8 +218,12 @@ int nrs_dba_solve(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* pos
  *                                 (sk_xyz = X0, their positions at the start); then nrs_dba_reset / optimize / download as before
  *   nrs_dba_download_skinned      the skinned points at the current estimate (n_skin x 3, fp64)
  *   nrs_dba_solve_embedded        one shot: upload, optimize(iters), download (poses_qt, lm_xyz, sk_xyz in/out)
- * One GPU (no communicator); the linear solve is the PCG with the observations' blocks applied as hyper-edges
- * (csrc/nrs_engine_skin.hpp). */
+ *   nrs_dba_skin_stats            out[0] skinned observations held on this context (sharded: those of its own keyframes), [1] their
+ *                                 padded slots, [2] device bytes of the skin buffer they occupy (not part of nrs_dba_stats' [4]);
+ *                                 NRS_ERR_STATE when no skinned observations are resident
+ * The linear solve is the PCG with the observations' blocks applied as hyper-edges (csrc/nrs_engine_skin.hpp), or the keyframe-block
+ * factorisation as its preconditioner (nrs_options.embedded_solver).  With a communicator the window is sharded like a plain one (the
+ * multi-GPU block below). */
 int nrs_dba_build_edges_embedded(int32_t n_kf, const int32_t* kf_rowptr, const int32_t* kf_pt, int32_t n_points, const uint8_t* is_node,
                                  const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w, const float* nbr_d0, const int32_t* nbr_status,
                                  int32_t* n_lm, int32_t* lm_obs, int32_t* n_spring, int32_t* sp_ij, float* sp_d0,
@@ -231,6 +236,7 @@ int nrs_dba_upload_embedded(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, c
                             int32_t n_skin, const int32_t* sk_kf, const float* sk_uv, const float* sk_xyz,
                             const int32_t* sk_node, const double* sk_omega, float scale);
 int nrs_dba_download_skinned(nrs_ctx* ctx, double* sk_xyz /* n_skin x 3, fp64 */);
+int nrs_dba_skin_stats(nrs_ctx* ctx, int64_t out[3]);
 int nrs_dba_solve_embedded(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* poses_qt,
                            int32_t n_lm, float* lm_xyz, const int32_t* lm_kf, const float* lm_uv,
                            int32_t n_spring, const int32_t* sp_ij, const float* sp_d0,
@@ -346,6 +352,11 @@ int nrs_shi_buffers(nrs_ctx* ctx, float* scores, int16_t* xgrad, int16_t* ygrad)
  *     doubles (dot products, pose rows of the operator).
  * nrs_dba_reset / optimize / download / residuals are collective: every rank calls them in the same
  * order; they return the same trace and, after download, the same complete result on every rank.
+ * Embedded windows (nrs_dba_upload_embedded) shard the same way and exchange nothing new: the keyframe ranges are those of
+ * nrs_shard_plan on the node copies' lm_kf, a rank holds the skinned observations of its own keyframes only (they reach node copies
+ * of their own keyframe, so no halo row), and their pose blocks, chi2, max diagonal and PCG shares travel in the packets above.
+ * The solve is the block-Jacobi PCG (nrs_options.embedded_solver).  nrs_dba_download_skinned and nrs_dba_solve_embedded are
+ * collective as well: every rank returns the same bits.
  * RCCL is bound at run time (dlopen): librccl must be loadable only if nrs_comm_init_rccl is used.   */
 #define NRS_COMM_ID_BYTES 128
 int nrs_comm_unique_id(uint8_t* id, int32_t capacity /* >= NRS_COMM_ID_BYTES */);      /* rank 0; broadcast by the caller */

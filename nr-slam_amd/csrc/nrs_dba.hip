@@ -69,7 +69,6 @@ static int dba_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const dou
     s.shard = true;                     // with a communicator on the context: one window over its ranks (include/nrs.h)
     std::vector<double> sk_X0;
     if (sk.n > 0) {                     // embedded window (N2b): observations of points without a vertex
-        if (c->comm) return c->fail(NRS_ERR_STATE, "embedded BA windows are not sharded over a communicator");
         sk_X0.resize(3 * (size_t)sk.n);
         for (size_t i = 0; i < sk_X0.size(); ++i) sk_X0[i] = (double)sk.xyz[i];
         s.n_skin = sk.n; s.sk_uv = sk.uv; s.sk_X0 = sk_X0.data(); s.sk_node = sk.node; s.sk_om = sk.omega; s.sk_pose = sk.kf;
@@ -112,6 +111,13 @@ extern "C" int nrs_dba_download_skinned(nrs_ctx* c, double* sk_xyz) {
     if (!c->dba) return c->fail(NRS_ERR_STATE, "no BA problem uploaded");
     if (!sk_xyz) return c->fail(NRS_ERR_INVALID, "null output");
     return engine_skin_positions(c, c->dba, sk_xyz);
+}
+
+extern "C" int nrs_dba_skin_stats(nrs_ctx* c, int64_t out[3]) {
+    if (!c || !out) return NRS_ERR_INVALID;
+    if (!c->dba) return c->fail(NRS_ERR_STATE, "no BA problem uploaded");
+    if (engine_skin_stats(c->dba, out) != NRS_OK) return c->fail(NRS_ERR_STATE, "no skinned observations on this window");
+    return NRS_OK;
 }
 
 extern "C" int nrs_dba_stats(nrs_ctx* c, int64_t stats[5]) {

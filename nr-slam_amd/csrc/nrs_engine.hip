@@ -344,8 +344,8 @@ static int evaluate(nrs_ctx* c, Engine* e, int which, bool reproj_done = false) 
     if (d.sk_n > 0) hipLaunchKernelGGL((k_skin<LIN>), dim3(d.sk_nblk), b, 0, c->stream, d, d.pose[which], d.xl[which]);   // embedded mode: the skinned observations
     if (LIN && d.sk_pcg) {                                         // embedded BA window: their blocks join D / b_l / H_pp / b_p (the PCG path reads those)
         if (d.D_op) NRS_HIP(c, hipMemcpyAsync(d.D_op, d.D, sizeof(double) * 6 * (size_t)d.n_rows, hipMemcpyDeviceToDevice, c->stream));   // (gather path: the operator's copy)
-        hipLaunchKernelGGL(k_skin_rows, dim3((d.sk_nrl + SK_RPB - 1) / SK_RPB), b, 0, c->stream, d);
-        hipLaunchKernelGGL(k_skin_pose, dim3((27 * d.K + BLK - 1) / BLK), b, 0, c->stream, d);
+        if (d.sk_nrl > 0) hipLaunchKernelGGL(k_skin_rows, dim3((d.sk_nrl + SK_RPB - 1) / SK_RPB), b, 0, c->stream, d);   // (a rank may hold none)
+        hipLaunchKernelGGL(k_skin_pose, dim3((27 * d.sh_nk + BLK - 1) / BLK), b, 0, c->stream, d);   // (own poses)
     }
     if (LIN && e->nd && e->nd->on) {                               // the direct solver's explicit blocks of this linearisation
         const NdVals& nv = e->nd->slot->vals;
@@ -623,7 +623,12 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
                 db.sh_t0b[cls] = d.sh_t0[cls] + d.sh_nt[cls] - d.sh_back[cls];
                 db.sh_ntb[cls] = d.sh_back[cls];
             }
-            launch_spmv(c, di, lam, it, tol2);
+            // embedded window: the skinned observations reach rows of their own keyframe only -- k_skin_op goes with the interior tiles
+            skin_op_done = launch_spmv(c, di, lam, it, tol2, d.sk_pcg != 0);
+            if (d.sk_pcg && !skin_op_done) {
+                hipLaunchKernelGGL(k_skin_op, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, it);
+                skin_op_done = true;
+            }
             NRS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_halo, 0));
             launch_spmv(c, db, lam, it, tol2);
         } else {
@@ -634,9 +639,10 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
         }
         if (d.sk_pcg) {                                            // embedded BA window: H u of the skinned observations' blocks (nrs_engine_skin.hpp)
             if (!skin_op_done) hipLaunchKernelGGL(k_skin_op, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, it);
-            // the row pass: inside k_pcg_update<true> (for the rows it updates) unless the update is the generic kernel's
-            skin_rows_fused = !d.sh_on && !d.hier && !d.ecd && !c->env("NRS_SKIN_ROWS_OWN_LAUNCH");
-            if (!skin_rows_fused) hipLaunchKernelGGL(k_skin_op_rows, dim3(d.n_rows / SK_RPB), dim3(BLK), 0, c->stream, d);
+            // the row pass: inside k_pcg_update<true> (for the rows it updates) unless the update is the generic kernel's (a sharded
+            // window reduces hierarchically, k_reduce_partials + all-reduce, and still takes the fused form: the update reads red)
+            skin_rows_fused = (d.sh_on || !d.hier) && !d.ecd && !c->env("NRS_SKIN_ROWS_OWN_LAUNCH");
+            if (!skin_rows_fused) hipLaunchKernelGGL(k_skin_op_rows, dim3(d.sh_nvb * BLK / SK_RPB), dim3(BLK), 0, c->stream, d);
         }
         if (d.sh_on) {
             // this rank's dot products and pose sums (other ranks' slots are zero), then the sum over the
@@ -648,7 +654,7 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
         } else if (d.hier) hipLaunchKernelGGL(k_reduce_partials, dim3(1 + d.K), dim3(BLK), 0, c->stream, d);
         {
             Timer t(c, &c->prof.vec_ms, &c->prof.vec_launches);
-            if (skin_rows_fused) hipLaunchKernelGGL(k_pcg_update<true>, dim3(d.n_rows / SK_RPB + n_poseblk), dim3(BLK), 0, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
+            if (skin_rows_fused) hipLaunchKernelGGL(k_pcg_update<true>, dim3(d.sh_nvb * BLK / SK_RPB + n_poseblk), dim3(BLK), 0, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
             else hipLaunchKernelGGL(k_pcg_update<false>, dim3((((d.sh_nvb + 1) / 2 + 7) / 8) * 8 + n_poseblk), dim3(BLK), 0, c->stream,
                                     d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
         }

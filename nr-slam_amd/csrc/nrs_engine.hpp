@@ -74,7 +74,8 @@ int engine_pack_hash(nrs_ctx* c, Engine* e, uint64_t* out /*24*/);
 // embedded mode: levels of the skinned observations (1 = level 0) / their chi2 = r^T Omega r at the current estimate
 int engine_skin_set_active(nrs_ctx* c, Engine* e, const uint8_t* active);
 int engine_skin_chi2(nrs_ctx* c, Engine* e, double* chi /*n_skin*/);
-int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz /*n_skin x 3*/);   // embedded BA windows: the skinned points at the current estimate
+int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz /*n_skin x 3*/);   // embedded BA windows: the skinned points at the current estimate (collective when sharded)
+int engine_skin_stats(const Engine* e, int64_t out[3]);            // skinned observations held here, their padded slots, skin-buffer bytes; NRS_ERR_STATE: none resident
 // OPT:927-1137's edge construction on the device (index for index what nrs_dba_build_edges returns); arrays live in ctx scratch
 int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
                               const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out);

@@ -985,6 +985,10 @@ __global__ __launch_bounds__(BLK) void k_finalize_pack(Dev P) {
     }
     if (LIN)
         for (int k = P.sh_k0 + tid; k < P.sh_k0 + P.sh_nk; k += BLK) md = fmax(md, P.red_loc[3 + k]);
+    if (P.sk_n > 0) {                                              // embedded window: the rank's skinned observations (its own keyframes') and their diagonal
+        for (int b = tid; b < P.sk_nblk; b += BLK) chi += P.sk_part[(size_t)b * 32 + 27];
+        if (LIN && tid == 0) md = fmax(md, *P.sk_maxdiag);
+    }
     double c = wave_sum(chi);
     sc = wave_sum(sc);
 #pragma unroll

@@ -544,10 +544,10 @@ __global__ __launch_bounds__(BLK) void k_pcg_update(Dev P, double lam, int it, d
     const double sc_gamma0 = P.scal[SC_GAMMA0];
     const double sc_slot0 = P.scal[(it & 1) ? SC_SLOT1 : SC_SLOT0], sc_slot1 = P.scal[((it & 1) ? SC_SLOT1 : SC_SLOT0) + 1];
     const int n_vec2 = (n_vecblk + 1) >> 1;
-    const int n_vec8 = SKR ? P.n_rows / SK_RPB : ((n_vec2 + 7) >> 3) << 3;          // (row workgroups of this launch)
+    const int n_vec8 = SKR ? n_vecblk * BLK / SK_RPB : ((n_vec2 + 7) >> 3) << 3;   // (row workgroups of this launch)
     const bool row_wg = (int)blockIdx.x < n_vec8;
     const int pair = (row_wg && !SKR) ? P.sh_vb0 * (BLK / 2) + xcd_tile(blockIdx.x, n_vec2) * BLK + tid : 0;
-    const int sk_r = (int)blockIdx.x * SK_RPB + tid / SK_RL, sk_t = tid % SK_RL;   // SKR: this lane's row and its place in the row's group
+    const int sk_r = P.sh_vb0 * BLK + (int)blockIdx.x * SK_RPB + tid / SK_RL, sk_t = tid % SK_RL;   // SKR: this lane's row (own rows) and its place in the row's group
     const bool has_rows = SKR ? row_wg && sk_t == 0 : row_wg && 2 * pair < (P.sh_vb0 + n_vecblk) * BLK;
     const size_t o = SKR ? 3 * (size_t)sk_r : 6 * (size_t)pair;
     double uu[6], pp[6], ww[6], ss[6], rr[6], xx[6], Di[12];

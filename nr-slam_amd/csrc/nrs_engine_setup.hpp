@@ -1136,29 +1136,37 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         // solver when it takes the frame (k_nd_values folds them into its blocks) and by the same PCG form when it does not.
         // Slots: observations grouped by pose (caller order inside a pose: K = 1 keeps the caller's order), every pose's padded to BLK;
         // per node row the list of the observations that reach it, in slot order.
+        // A rank of a sharded window (communicator) holds the observations of its OWN keyframes [sh_k0, sh_k0 + sh_nk) only: they reach
+        // node copies of their own keyframe (checked below), so everything they read or write is rank-local and no halo row is needed;
+        // their pose blocks and chi2 join the all-reduced packets once (k_finalize_pack).  Observations held elsewhere: sk_slot = -1.
         const bool ba_form = s.sk_pose != nullptr;
-        if (d.fused || d.sh_on || !s.sk_uv || !s.sk_X0 || !s.sk_node || !s.sk_om) return c->fail(NRS_ERR_INVALID, "skinned observations: two-kernel PCG path, one GPU");
+        if (d.fused || (d.sh_on && !ba_form) || !s.sk_uv || !s.sk_X0 || !s.sk_node || !s.sk_om) return c->fail(NRS_ERR_INVALID, "skinned observations: two-kernel PCG path");
         if (!ba_form && !(arena == &c->arena_trk && s.K == 1)) return c->fail(NRS_ERR_INVALID, "skinned observations without a pose index: single-frame tracking engines only");
         const size_t n_in = (size_t)s.n_skin;
         std::vector<int> pose0;
         if (!ba_form) pose0.assign(n_in, 0);
         const int* sk_pose = ba_form ? s.sk_pose : pose0.data();
+        const int own_k0 = d.sh_k0, own_k1 = d.sh_k0 + d.sh_nk;    // (the whole window on one GPU)
+        auto held = [&](size_t i) { return sk_pose[i] >= own_k0 && sk_pose[i] < own_k1; };
         std::vector<int> cnt(s.K + 1, 0), pose_blk(s.K + 1, 0);
         for (size_t i = 0; i < n_in; ++i) {
             if (sk_pose[i] < 0 || sk_pose[i] >= s.K) return c->fail(NRS_ERR_INVALID, "skinned observation: pose index out of range");
-            cnt[sk_pose[i] + 1]++;
+            if (held(i)) cnt[sk_pose[i] + 1]++;
         }
         for (int k = 0; k < s.K; ++k) pose_blk[k + 1] = pose_blk[k] + (cnt[k + 1] + BLK - 1) / BLK;
+        if (d.sh_on && pose_blk[s.K] == 0)                         // (a rank whose keyframes have none: one empty block of its first pose, so that every launch has a grid)
+            for (int k = own_k0; k < s.K; ++k) pose_blk[k + 1]++;
         const size_t nblk = (size_t)pose_blk[s.K], n = nblk * BLK;
         std::vector<int> next(s.K), blk_pose(nblk);
         for (int k = 0; k < s.K; ++k) { next[k] = pose_blk[k] * BLK; for (int b2 = pose_blk[k]; b2 < pose_blk[k + 1]; ++b2) blk_pose[b2] = k; }
-        e->sk_slot.resize(n_in);
+        e->sk_slot.assign(n_in, -1);
         std::vector<float> uv(2 * n, 0.f);
         std::vector<double> X0(3 * n, 0.0), om(SK_MAX * n, 0.0);
         std::vector<int> rows(SK_MAX * n, -1);
         std::vector<uint8_t> act(n, 0);
         std::vector<int> rl_cnt(d.n_rows + 1, 0);
         for (size_t i = 0; i < n_in; ++i) {
+            if (!held(i)) continue;
             const size_t sl = (size_t)next[sk_pose[i]]++;
             e->sk_slot[i] = (int)sl;
             uv[2 * sl] = s.sk_uv[2 * i]; uv[2 * sl + 1] = s.sk_uv[2 * i + 1];
@@ -1178,6 +1186,13 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         for (int r = 0; r < d.n_rows; ++r)
             if (rl_cnt[r + 1] > 0) { row_list[r] = (int)rl_row.size(); rl_row.push_back(r); rl_ptr.push_back(rl_ptr.back() + rl_cnt[r + 1]); }
         const size_t n_ent = (size_t)rl_ptr.back(), nrl = rl_row.size();
+        if (d.sh_on) {                                             // a rank's per-row arrays may be row-limited (biased pointers, ArenaPlan::get_rows):
+            const int own_lo = d.sh_g0 * ROW_ALIGN, own_hi = (d.sh_g0 + d.sh_ng) * ROW_ALIGN;   // no launch may reach a row it does not own
+            for (size_t q = 0; q < rows.size(); ++q)
+                if (rows[q] >= 0 && (rows[q] < own_lo || rows[q] >= own_hi)) return c->fail(NRS_ERR_INVALID, "skinned observation: node row %d outside the rank's rows [%d, %d)", rows[q], own_lo, own_hi);
+            for (size_t l = 0; l < nrl; ++l)
+                if (rl_row[l] < own_lo || rl_row[l] >= own_hi) return c->fail(NRS_ERR_INVALID, "skinned observations: row list %d outside the rank's rows [%d, %d)", rl_row[l], own_lo, own_hi);
+        }
         std::vector<int> rl_obs(n_ent + 1), fill(rl_ptr.begin(), rl_ptr.end() - 1);
         std::vector<double> rl_om(n_ent + 1);
         for (size_t sl = 0; sl < n; ++sl)
@@ -1196,6 +1211,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
                      spec_stride = al(8 * 32 * nblk) + al(8 * n), total = o_spec + (size_t)e->n_spec * spec_stride;   // (shadow sets of sk_part / sk_chi: speculative trials)
         DevBuf& buf = arena == &c->arena_trk ? c->nd_skin : c->dba_skin;
         NRS_TRY(c->ensure(buf, total));
+        e->sk_bytes = total;
         char* sb = buf.as<char>();
         auto up = [&](size_t off, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(sb + off, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
         NRS_HIP(c, up(o_uv, uv.data(), 8 * n)); NRS_HIP(c, up(o_X0, X0.data(), 24 * n)); NRS_HIP(c, up(o_row, rows.data(), 4 * SK_MAX * n));
@@ -1293,32 +1309,51 @@ namespace nrs {
 int engine_skin_set_active(nrs_ctx* c, Engine* e, const uint8_t* active) {
     if (e->d.sk_n <= 0) return NRS_OK;
     std::vector<uint8_t> act((size_t)e->d.sk_n, 0);                // (slots are pose-grouped and padded: padding stays inactive)
-    for (size_t i = 0; i < e->sk_slot.size(); ++i) act[e->sk_slot[i]] = active[i];
+    for (size_t i = 0; i < e->sk_slot.size(); ++i) if (e->sk_slot[i] >= 0) act[e->sk_slot[i]] = active[i];
     NRS_HIP(c, hipMemcpyAsync(const_cast<uint8_t*>(e->d.sk_active), act.data(), act.size(), hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     return NRS_OK;
 }
 // embedded BA window: the skinned points at the current estimate, X0 + sum_k om_k (x_{n_k} - x_start_{n_k}), summed over k in order
-// (caller order of the observations; host arithmetic on the downloaded rows -- the same expression k_skin evaluates)
+// (caller order of the observations; host arithmetic on the downloaded rows -- the same expression k_skin evaluates).
+// Sharded: COLLECTIVE -- a rank evaluates the observations it holds from its own rows (the only rows they reach), zeros elsewhere, and
+// the n_skin x 3 block is summed over the ranks through transient scratch: every rank returns the same bits.
 int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz) {
     const Dev& d = e->d;
     if (!d.sk_pcg) return c->fail(NRS_ERR_STATE, "no skinned observations on this window");
-    const size_t nr = 3 * (size_t)d.n_rows, n = e->sk_slot.size();
+    const size_t r0 = (size_t)d.sh_vb0 * BLK, nr = 3 * (size_t)d.sh_nvb * BLK, n = e->sk_slot.size();   // (own rows: all of them on one GPU)
     std::vector<double> cur(nr), ini(nr);
-    NRS_HIP(c, hipMemcpyAsync(cur.data(), d.xl[e->cur], 8 * nr, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(ini.data(), d.xl_init, 8 * nr, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(cur.data(), d.xl[e->cur] + 3 * r0, 8 * nr, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(ini.data(), d.xl_init + 3 * r0, 8 * nr, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; ++i) {
         double x[3] = {e->sk_X0[3 * i], e->sk_X0[3 * i + 1], e->sk_X0[3 * i + 2]};
+        if (e->sk_slot[i] < 0) { xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = 0.0; continue; }   // (held by another rank)
         for (int k = 0; k < SK_MAX; ++k) {
             const int v = e->sk_vert[SK_MAX * i + k];
             if (v < 0) continue;
-            const size_t r = 3 * (size_t)e->vrow[v];
+            const size_t r = 3 * ((size_t)e->vrow[v] - r0);
             const double om = e->sk_om[SK_MAX * i + k];
             for (int a = 0; a < 3; ++a) x[a] += om * (cur[r + a] - ini[r + a]);
         }
         xyz[3 * i] = x[0]; xyz[3 * i + 1] = x[1]; xyz[3 * i + 2] = x[2];
     }
+    if (!d.sh_on || n == 0) return NRS_OK;
+    const size_t m = 3 * n;
+    NRS_TRY(c->ensure(c->gather_ws, 2 * sizeof(double) * m));
+    double* in = c->gather_ws.as<double>();
+    NRS_HIP(c, hipMemcpyAsync(in, xyz, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+    NRS_TRY(c->comm->allreduce(c, in, in + m, m));
+    NRS_HIP(c, hipMemcpyAsync(xyz, in + m, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    c->release(c->gather_ws);
+    return NRS_OK;
+}
+int engine_skin_stats(const Engine* e, int64_t out[3]) {
+    if (e->d.sk_n <= 0) return NRS_ERR_STATE;
+    int64_t held = 0;
+    for (int s : e->sk_slot) held += s >= 0;
+    out[0] = held; out[1] = e->d.sk_n; out[2] = (int64_t)e->sk_bytes;
     return NRS_OK;
 }
 int engine_skin_chi2(nrs_ctx* c, Engine* e, double* chi) {
@@ -1330,7 +1365,7 @@ int engine_skin_chi2(nrs_ctx* c, Engine* e, double* chi) {
         std::vector<double> h((size_t)d.sk_n);
         NRS_HIP(c, hipMemcpyAsync(h.data(), d.sk_chi, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < e->sk_slot.size(); ++i) chi[i] = h[e->sk_slot[i]];
+        for (size_t i = 0; i < e->sk_slot.size(); ++i) chi[i] = e->sk_slot[i] >= 0 ? h[e->sk_slot[i]] : 0.0;
     }
     return NRS_OK;
 }

@@ -152,10 +152,12 @@ __global__ __launch_bounds__(BLK) void k_skin_rows(Dev P) {
     }
 }
 
+// (27 sh_nk threads from pose sh_k0: the poses this engine owns -- every pose on one GPU.  A rank of a sharded window leaves the other
+// poses alone: their H_pp still hold the last all-reduced values, which must neither be added to nor enter the max diagonal.)
 __global__ __launch_bounds__(BLK) void k_skin_pose(Dev P) {
     const int i = blockIdx.x * BLK + threadIdx.x;
-    if (i >= 27 * P.K) return;
-    const int k = i / 27, cc = i % 27;
+    if (i >= 27 * P.sh_nk) return;
+    const int k = P.sh_k0 + i / 27, cc = i % 27;
     double s = 0;
     for (int b = P.sk_pose_blk[k]; b < P.sk_pose_blk[k + 1]; ++b) s += P.sk_part[(size_t)b * 32 + cc];
     if (cc < 21) {
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(BLK, 4) void k_spmv_f_skin(Dev P, double lam, int c
 // The row pass in a launch of its own (large windows on the hierarchical reduction, NRS_SKIN_ROWS_OWN_LAUNCH=1): w_row += sum om g_o.
 // Otherwise k_pcg_update<true> does it for the rows it is about to update.  The rows' shares of the dot products are k_skin_op's.
 __global__ __launch_bounds__(BLK) void k_skin_op_rows(Dev P) {
-    const int tid = threadIdx.x, r = blockIdx.x * SK_RPB + tid / SK_RL, t = tid % SK_RL;     // (n_rows is a multiple of BLK)
+    const int tid = threadIdx.x, r = P.sh_vb0 * BLK + blockIdx.x * SK_RPB + tid / SK_RL, t = tid % SK_RL;   // (the own rows, sh_nvb * BLK / SK_RPB workgroups)
     const int done = P.flags[0], q0 = P.sk_row_q[2 * (size_t)r], q1 = P.sk_row_q[2 * (size_t)r + 1];
     const uint8_t rf = P.rflag[r];
     const double w0 = P.wv[3 * (size_t)r], w1 = P.wv[3 * (size_t)r + 1], w2 = P.wv[3 * (size_t)r + 2];

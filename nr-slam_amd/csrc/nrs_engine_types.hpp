@@ -253,7 +253,8 @@ struct Engine {
     std::vector<uint32_t> h_d_om;
     std::vector<uint8_t> h_rflag, h_pose_fixed;
     std::vector<float> h_uv;         // observations by row, kept by a rank that holds its own rows only (residual taps)
-    std::vector<int> sk_slot;        // embedded BA windows: observation (caller order) -> slot (pose-grouped, padded)
+    std::vector<int> sk_slot;        // embedded BA windows: observation (caller order) -> slot (pose-grouped, padded); -1: held by another rank
+    size_t sk_bytes = 0;             // bytes of the context's skin buffer this engine's observations occupy
     std::vector<int> sk_vert;        // embedded mode: the skinned observations' node vertices (n_skin x 11, -1 pads) and weights
     std::vector<double> sk_om, sk_X0;
     unsigned long long serial = 0;   // identifies this engine to the context's tap buffer (nrs_ctx::tap)

@@ -30,7 +30,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_local_group_create", "nrs_local_group_destroy", "nrs_comm_init_local",
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
            "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_triangulate_batch", "nrs_track_deform_solve_rg",
-           "nrs_skin_select_nodes", "nrs_dba_stats"]
+           "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats"]
 
 
 class NrsError(RuntimeError):
@@ -520,6 +520,12 @@ class Context:
         st = (C.c_int64 * 5)()
         self._chk(self.lib.nrs_dba_stats(self.h, st))
         return dict(rows=st[0], packed_rows=st[1], spring_slots=st[2], damper_slots=st[3], device_bytes=st[4])
+
+    def dba_skin_stats(self):
+        """skinned observations of the resident embedded window on this rank (include/nrs.h nrs_dba_skin_stats)"""
+        st = (C.c_int64 * 3)()
+        self._chk(self.lib.nrs_dba_skin_stats(self.h, st))
+        return [st[0], st[1], st[2]]
 
     # ---- N2: skinned mode
     def skin_select_nodes(self, pos, n_nodes, eligible=None):
