@@ -100,9 +100,18 @@ typedef struct {
                                  458 node copies x 20 keyframes; the PCG wins beyond), block-Jacobi PCG else;
                                  1: always the factorisation (if its K x (3 nodes + 6)^2 x 8 bytes fit 6 GB);
                                  2: always block-Jacobi PCG (hundreds of iterations per trial).  Same LM iterates either
-                                 way.  Plain (every point a node) and sharded windows use the block-Jacobi PCG: on a context
-                                 with a communicator an embedded window always solves by block-Jacobi PCG, whatever this says.
+                                 way.  Plain windows (every point a node) use the block-Jacobi PCG.  On a context with a
+                                 communicator an embedded window solves by block-Jacobi PCG whatever this says, unless
+                                 sharded_kft = 1.
                                  (Sits where the 40-byte layout had padding: values outside 0..2 are read as 0.) */
+    int32_t sharded_kft;      /* embedded BA windows on a context with a communicator:
+                                 0 (default): block-Jacobi PCG, whatever embedded_solver says;
+                                 1: embedded_solver decides as on one GPU.  The keyframe-block factorisation is then sharded:
+                                 a rank holds and inverts the blocks of its own keyframes, and the elimination chains are
+                                 handed from rank to rank (one Schur-update operand per crossing in the factorisation, one
+                                 vector per crossing in the solve).  The factor and M^-1 x are bit-identical to one GPU's.
+                                 If any rank cannot hold its share, every rank falls back to the PCG.  Values other than
+                                 0 / 1 are read as 0. */
 } nrs_options;
 void nrs_options_init(nrs_options* opt);
 
@@ -277,7 +286,12 @@ int nrs_dba_gradient(nrs_ctx* ctx, double* b /* 6 n_kf + 3 n_lm */, double* diag
  *   what 1  out_d = the assembled diagonal block of keyframe k (ld x ld: its free node copies in row order, then its pose)
  *   what 2  out_d = the coupling of keyframes k and k + 1 as a dense ld x ld matrix (rows: k)
  *   what 3  out_d = M^-1 in_d, both in solver order (6 per pose, then 3 per node copy): the factorisation applied as the PCG applies it
- *   what 4  out_i = per node copy its (keyframe, compact index) pair, -1: fixed */
+ *   what 4  out_i = per node copy its (keyframe, compact index) pair, -1: fixed
+ *   what 5  out_i[0..6) = this rank's share: {first own keyframe, own keyframes, middle keyframe, rank that holds it,
+ *           factor bytes held >> 10 (KiB), hand-overs per factorisation}; one GPU: {0, K, m, 0, bytes >> 10, 0}
+ * On a communicator (nrs_options.sharded_kft = 1) what 0 reports as on one GPU, what 1 / 2 answer for the rank's own keyframes only
+ * (NRS_ERR_INVALID on the other ranks); what 1 / 2 / 3 linearise and assemble, so every rank calls them together (the same lam and
+ * k); what 3 returns the complete M^-1 in_d on every rank, the same bits everywhere. */
 int nrs_debug_kft(nrs_ctx* ctx, double lam, int32_t what, int32_t k, const double* in_d, double* out_d, int32_t* out_i);
 
 /* Parity tap of the problem construction (edge lists -> row layout, sliced-ELL incidence streams, halo lists, chi2 edge lists;

@@ -90,6 +90,12 @@ struct RcclComm : Comm {
         NRS_NCCL(c, api->GroupEnd());
         return NRS_OK;
     }
+    int handover(nrs_ctx* c, const double* send, double* recv, size_t n, int from, int to) override {
+        if (from == to || n == 0) return NRS_OK;
+        if (rank == from) NRS_NCCL(c, api->Send(send, n, ncclDouble, to, comm, c->stream));
+        else if (rank == to) NRS_NCCL(c, api->Recv(recv, n, ncclDouble, from, comm, c->stream));
+        return NRS_OK;
+    }
 };
 
 // ------------------------------------------------------------------------------------- local (threads, one GPU)
@@ -183,6 +189,18 @@ struct LocalComm : Comm {
         if (rank < world - 1) NRS_LOCAL(c, g, hip_rc(c, hipMemcpyAsync(v + h.hi_recv, g->slot[rank + 1] + h.hi_recv, sizeof(double) * h.hi_recv_n, hipMemcpyDeviceToDevice, st), "halo copy"));
         NRS_LOCAL(c, g, hip_rc(c, hipStreamSynchronize(st), "hipStreamSynchronize"));
         NRS_LOCAL_BARRIER(c, g);
+        return NRS_OK;
+    }
+    int handover(nrs_ctx* c, const double* send, double* recv, size_t n, int from, int to) override {
+        if (world == 1 || from == to || n == 0) return NRS_OK;
+        g->slot[rank] = rank == from ? send : nullptr;
+        NRS_LOCAL(c, g, hip_rc(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize"));   // (the sender's operand is complete)
+        NRS_LOCAL_BARRIER(c, g);
+        if (rank == to) {
+            NRS_LOCAL(c, g, hip_rc(c, hipMemcpyAsync(recv, g->slot[from], sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream), "hand-over copy"));
+            NRS_LOCAL(c, g, hip_rc(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize"));
+        }
+        NRS_LOCAL_BARRIER(c, g);                                   // (the sender may overwrite its operand)
         return NRS_OK;
     }
 };

@@ -25,12 +25,16 @@ struct ShiState;     // nrs_shi.hip
 // context's stream.  Two primitives are all the engine needs:
 //   allreduce : element-wise sum of n doubles over the ranks, the same bits on every rank
 //   exchange  : boundary rows of a replicated-layout row vector with rank-1 / rank+1 (offsets in doubles)
+// and one for the sharded keyframe-block factorisation (nrs_engine_kft.hpp):
+//   handover  : one point-to-point move: rank `from` sends n doubles, rank `to` receives them.  COLLECTIVE in the sense that every
+//               rank calls it at the same point of the schedule with the same (from, to, n); the others move nothing
 struct HaloPlan { size_t lo_send = 0, lo_send_n = 0, hi_send = 0, hi_send_n = 0, lo_recv = 0, lo_recv_n = 0, hi_recv = 0, hi_recv_n = 0; };
 struct Comm {
     int rank = 0, world = 1;
     virtual ~Comm() {}
     virtual int allreduce(nrs_ctx* c, const double* send, double* recv, size_t n) = 0;
     virtual int exchange(nrs_ctx* c, double* vec, const HaloPlan& h, hipStream_t stream) = 0;   // ordered on `stream`
+    virtual int handover(nrs_ctx* c, const double* send, double* recv, size_t n, int from, int to) = 0;   // ordered on the context's stream
 };
 struct Arena { char* base = nullptr; size_t cap = 0, off = 0; };
 

@@ -79,6 +79,7 @@ static int dba_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const dou
     // rank-local work) returns without a collective; from there on a failure may be one rank's alone (err_local) and the ranks
     // agree on the outcome before the first collective of the solve.
     if (rc == NRS_OK || c->err_local) rc = comm_agree(c, rc);
+    if (rc == NRS_OK) rc = engine_kft_agree(c, c->dba);           // (every rank got here: the set-up succeeded everywhere)
     if (rc != NRS_OK) dba_free(c);
     return rc;
 }
@@ -304,7 +305,7 @@ extern "C" int nrs_dba_gradient(nrs_ctx* c, double* b, double* diag) {
 extern "C" int nrs_debug_kft(nrs_ctx* c, double lam, int32_t what, int32_t k, const double* in_d, double* out_d, int32_t* out_i) {
     if (!c) return NRS_ERR_INVALID;
     if (!c->dba) return c->fail(NRS_ERR_STATE, "no BA problem uploaded");
-    if ((what == 0 || what == 4) ? !out_i : !out_d) return c->fail(NRS_ERR_INVALID, "null output");
+    if ((what == 0 || what == 4 || what == 5) ? !out_i : !out_d) return c->fail(NRS_ERR_INVALID, "null output");
     if (what == 3 && !in_d) return c->fail(NRS_ERR_INVALID, "null input");
     return engine_kft_debug(c, c->dba, lam, what, k, in_d, out_d, out_i);
 }

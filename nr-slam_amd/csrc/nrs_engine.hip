@@ -45,6 +45,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <new>
 #include <system_error>
 #include <thread>
@@ -659,7 +660,7 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
                                     d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
         }
         if (kft_lazy) {
-            hipLaunchKernelGGL(k_kft_rnorm, dim3(1), dim3(1024), 0, c->stream, e->kft->d, d, d.rv, (it & 1) ? d.rp : d.rp2, tol2, pub_seq);
+            NRS_TRY(kft_rtest(c, e, e->kft, d.rv, (it & 1) ? d.rp : d.rp2, tol2, pub_seq));
             e->kft->apply_pending = true;
         } else if (kft_on)                                         // u = M^-1 r over the keyframe chains (the update left the block-Jacobi u: overwritten)
             NRS_TRY(kft_apply(c, e->kft, d.rv, (it & 1) ? d.rp : d.rp2, d.uv3, (it & 1) ? d.up : d.up2, d.flags));

@@ -55,7 +55,12 @@ struct KftDev {
     const int* cl_ptr[2];            // K x (nfm + 1)
     const int* cl_from[2]; const int* cl_tp[2];
     double* cl_val[2];               // the lists' values (tp_val[cl_tp[.]], refreshed per linearisation: the solve's loops read them in place)
+    // sharded window (nrs_options.sharded_kft): the keyframes [k_lo, k_hi) of this rank, their first row; A is biased by k_lo blocks,
+    // z / xs by max(0, k_lo - 1) vectors (the neighbours' hand-over slots).  One GPU: [0, K), row 0.
+    int k_lo, k_hi, row0;
+    const double* bd_val;            // damper values of the couplings across rank boundaries (all-reduced per factorisation; src flag KFT_BD)
 };
+constexpr uint32_t KFT_BD = 0x40000000u;   // te_src: the value is bd_val[index] (pe_src: type 3)
 
 struct KftHost {
     bool on = false;
@@ -64,11 +69,30 @@ struct KftHost {
     int factorisations = 0;
     bool apply_pending = false;      // the PCG's iteration 0 ended with the residual test (k_kft_rnorm): u = M^-1 r is enqueued when the solve goes on
     std::vector<int> kf_nb;          // per keyframe: 64-blocks that hold unknowns (ceil((3 nodes + 6) / 64))
+    // sharded (world > 1): every rank walks the one-GPU schedule and runs the steps of its own keyframes; a chain that crosses a rank
+    // boundary hands its Schur-update operand (factorisation) or its vector (solve) to the neighbour
+    bool sh = false;
+    int rows_own = 0;                // rows of the own keyframes (from row F.row0)
+    std::vector<int> kf_nf;          // K: free node copies per keyframe (host copy)
+    std::vector<int> kb;             // world + 1: keyframe ranges of the ranks (shard_plan)
+    int r_m = 0, handovers = 0;      // the rank that holds the middle keyframe; hand-overs per factorisation
+    size_t factor_bytes = 0;         // the blocks held (own keyframes) and the two Schur-update operands
+    int n_bd = 0;
+    const int* bd_slot = nullptr;    // n_bd: this rank's d_s slot of a boundary damper's value, -1: held by another rank
+    double* bd_buf = nullptr;        // 2 x n_bd: this rank's shares, their sum (= KftDev::bd_val)
+    double* pose_ws = nullptr;       // 2 x 6 K: the pose part of u = M^-1 r, own keyframes' entries and their sum over the ranks
+    double* rn = nullptr;            // 4: the residual test's two partial sums and their sum over the ranks
+    int owner(int k) const {
+        if (!sh) return 0;
+        int r = 0;
+        while (k >= kb[r + 1]) ++r;
+        return r;
+    }
 };
 
 // ------------------------------------------------------------------------------------------------------------------ assembly
 __global__ __launch_bounds__(256) void k_kft_clear(KftDev F) {
-    const int k = blockIdx.y;
+    const int k = F.k_lo + blockIdx.y;
     const size_t idx = 2 * ((size_t)blockIdx.x * 256 + threadIdx.x), n2 = (size_t)F.ld * F.ld;
     if (idx >= n2) return;
     const int i = (int)(idx / F.ld), j = (int)(idx % F.ld), nk = 3 * F.kf_nf[k] + F.kf_np[k];
@@ -81,7 +105,7 @@ __global__ __launch_bounds__(256) void k_kft_clear(KftDev F) {
 // node diagonal blocks (D + lambda: every edge's share, the skinned observations' included) and the pose-node blocks: the node copy's own
 // reprojection edge (factored form, as row_factored) + sum om B_o over the observations that reach the row (SK_RL lanes a row)
 __global__ __launch_bounds__(BLK) void k_kft_diag(Dev P, KftDev F, double lam) {
-    const int tid = threadIdx.x, r = blockIdx.x * SK_RPB + tid / SK_RL, t = tid % SK_RL;
+    const int tid = threadIdx.x, r = F.row0 + blockIdx.x * SK_RPB + tid / SK_RL, t = tid % SK_RL;
     const int ci = F.row_ci[r], k = P.grp_pose[r / ROW_ALIGN];
     const int nf = F.kf_nf[k], np = F.kf_np[k];
     double acc[18];
@@ -141,8 +165,8 @@ __global__ __launch_bounds__(BLK) void k_kft_diag(Dev P, KftDev F, double lam) {
 
 __global__ __launch_bounds__(256) void k_kft_pose(Dev P, KftDev F, double lam) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 36 * F.K) return;
-    const int k = i / 36, p = (i % 36) / 6, q = i % 6;
+    if (i >= 36 * (F.k_hi - F.k_lo)) return;
+    const int k = F.k_lo + i / 36, p = (i % 36) / 6, q = i % 6;
     if (!F.kf_np[k]) return;
     const int lo = p < q ? p : q, hi = p < q ? q : p;
     const int pk = lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo);       // packed upper index (as k_pcg_update)
@@ -173,8 +197,8 @@ __global__ __launch_bounds__(256) void k_kft_pairs(Dev P, KftDev F) {
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int cc = 0; cc < 3; ++cc) b[3 * a + cc] -= qc * v[a] * v[cc];
-        } else if (type == 1) {                                    // damper, the two vertices of one keyframe: - s I
-            const double s = P.d_s[idx];
+        } else if (type == 1 || type == 3) {                       // damper, the two vertices of one keyframe: - s I (3: value held by another rank)
+            const double s = type == 1 ? P.d_s[idx] : F.bd_val[idx];
             b[0] -= s; b[4] -= s; b[8] -= s;
         } else {                                                   // skinned observation: om_hi om_lo J_l^T w J_l
             const double w = F.pe_w[q];
@@ -205,7 +229,7 @@ __global__ __launch_bounds__(256) void k_kft_tvals(Dev P, KftDev F) {
     double t = 0;
     for (int q = F.tp_ptr[i]; q < F.tp_ptr[i + 1]; ++q) {
         const uint32_t src = F.te_src[q];
-        const double s = P.d_s[src & 0x7FFFFFFFu];
+        const double s = (src & KFT_BD) ? F.bd_val[src & (KFT_BD - 1)] : P.d_s[src & 0x7FFFFFFFu];
         t += (src >> 31) ? -s : s;
     }
     F.tp_val[i] = t;
@@ -216,6 +240,13 @@ __global__ __launch_bounds__(256) void k_kft_clvals(KftDev F) {
     if (i >= F.n_tp) return;
     F.cl_val[0][i] = F.tp_val[F.cl_tp[0][i]];
     F.cl_val[1][i] = F.tp_val[F.cl_tp[1][i]];
+}
+
+// sharded: this rank's shares of the boundary dampers' values (the others' slots are zero), summed over the ranks into bd_val
+__global__ __launch_bounds__(256) void k_kft_bd_gather(Dev P, const int* __restrict__ slot, double* __restrict__ out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = slot[i] >= 0 ? P.d_s[slot[i]] : 0.0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the sweep
@@ -867,7 +898,7 @@ __global__ __launch_bounds__(256) void k_kft_gemv(KftDev F, int mode, int k0, in
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-static int kft_invert(nrs_ctx* c, const KftHost& H, int kf0, int kf1, int* flags) {
+static int kft_invert(nrs_ctx* c, const KftHost& H, int kf0, int kf1, int* flags, int nbu) {   // nbu: of the one-GPU pair (a rank may run one chain of it)
     const KftDev& F = H.d;
     if (c->env("NRS_KFT_TWO_LAUNCHES")) {                           // (A/B: the panel and the trailing update of a step as launches of their own)
         for (int j = 0; j < F.nb; ++j) {
@@ -876,7 +907,6 @@ static int kft_invert(nrs_ctx* c, const KftHost& H, int kf0, int kf1, int* flags
         }
         return NRS_OK;
     }
-    const int nbu = std::max(kf0 >= 0 ? H.kf_nb[kf0] : 1, kf1 >= 0 ? H.kf_nb[kf1] : 1);
     for (int j = 0; j <= nbu; ++j)
         if (c->env("NRS_KFT_SCALAR_SWEEP")) hipLaunchKernelGGL(k_kft_step<false>, dim3(2 * (nbu + nbu * nbu)), dim3(256), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
         else if (c->env("NRS_KFT_FOUR_WAVES")) hipLaunchKernelGGL(k_kft_step<true>, dim3(2 * (nbu + nbu * nbu)), dim3(256), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
@@ -884,32 +914,61 @@ static int kft_invert(nrs_ctx* c, const KftHost& H, int kf0, int kf1, int* flags
     return NRS_OK;
 }
 
-// assembly of every A_k and T_k at the current linearisation (after evaluate<true>), then the two elimination chains
-static int kft_factor(nrs_ctx* c, Engine* e, KftHost* H, double lam) {
+// assembly of the (own) A_k and the T_k at the current linearisation (after evaluate<true>).  Sharded: the damper values of the couplings
+// across rank boundaries are first summed over the ranks (each is linearised by the rank that holds its slot).
+static int kft_assemble(nrs_ctx* c, Engine* e, KftHost* H, double lam) {
     const Dev& d = e->d;
     const KftDev& F = H->d;
     const size_t n2 = (size_t)F.ld * F.ld;
-    hipLaunchKernelGGL(k_kft_clear, dim3((unsigned)((n2 / 2 + 255) / 256), F.K), dim3(256), 0, c->stream, F);
-    hipLaunchKernelGGL(k_kft_diag, dim3(d.n_rows / SK_RPB), dim3(BLK), 0, c->stream, d, F, lam);
-    hipLaunchKernelGGL(k_kft_pose, dim3((36 * F.K + 255) / 256), dim3(256), 0, c->stream, d, F, lam);
+    if (H->n_bd > 0) {
+        hipLaunchKernelGGL(k_kft_bd_gather, dim3((H->n_bd + 255) / 256), dim3(256), 0, c->stream, d, H->bd_slot, H->bd_buf, H->n_bd);
+        NRS_TRY(c->comm->allreduce(c, H->bd_buf, H->bd_buf + H->n_bd, (size_t)H->n_bd));
+    }
+    const int nk = F.k_hi - F.k_lo;
+    hipLaunchKernelGGL(k_kft_clear, dim3((unsigned)((n2 / 2 + 255) / 256), nk), dim3(256), 0, c->stream, F);
+    hipLaunchKernelGGL(k_kft_diag, dim3((unsigned)(H->rows_own / SK_RPB)), dim3(BLK), 0, c->stream, d, F, lam);
+    hipLaunchKernelGGL(k_kft_pose, dim3((36 * nk + 255) / 256), dim3(256), 0, c->stream, d, F, lam);
     if (F.n_pp) hipLaunchKernelGGL(k_kft_pairs, dim3((unsigned)(((size_t)F.n_pp * KFT_PL + 255) / 256)), dim3(256), 0, c->stream, d, F);
     if (F.n_tp) {
         hipLaunchKernelGGL(k_kft_tvals, dim3((F.n_tp + 255) / 256), dim3(256), 0, c->stream, d, F);
         hipLaunchKernelGGL(k_kft_clvals, dim3((F.n_tp + 255) / 256), dim3(256), 0, c->stream, F);
     }
+    return NRS_OK;
+}
+
+// the two elimination chains
+static int kft_factor(nrs_ctx* c, Engine* e, KftHost* H, double lam) {
+    const Dev& d = e->d;
+    const KftDev& F = H->d;
+    const size_t n2 = (size_t)F.ld * F.ld;
+    NRS_TRY(kft_assemble(c, e, H, lam));
+    // the one-GPU schedule, step by step: a rank runs the steps of its own keyframes, and where a chain crosses into the next rank's
+    // range the Schur-update operand (G_f C^T of the last keyframe, k_kft_gct) moves there and k_kft_tgt runs on the receiver
     const int len0 = F.m, len1 = F.K - 1 - F.m;
+    auto own = [&](int k) { return k >= F.k_lo && k < F.k_hi; };
     for (int s = 0; s < std::max(len0, len1); ++s) {
-        const int k0 = s < len0 ? s : -1, k1 = s < len1 ? F.K - 1 - s : -1;
-        NRS_TRY(kft_invert(c, *H, k0, k1, d.flags));
+        const int g0 = s < len0 ? s : -1, g1 = s < len1 ? F.K - 1 - s : -1;
+        const int k0 = g0 >= 0 && own(g0) ? g0 : -1, k1 = g1 >= 0 && own(g1) ? g1 : -1;
+        const int nbu = std::max(g0 >= 0 ? H->kf_nb[g0] : 1, g1 >= 0 ? H->kf_nb[g1] : 1);
         const dim3 g((F.ld + 255) / 256, F.nfm, 2), g2((F.ld + KFT_TC - 1) / KFT_TC, 2);
         const size_t shy = sizeof(double) * KFT_TC * F.ld;
-        hipLaunchKernelGGL(k_kft_gct, g, dim3(256), 0, c->stream, F, k0, k1);
-        if (k0 >= 0 && k1 >= 0 && k0 + 1 == k1 - 1) {              // both chains reach the middle keyframe: one after the other (fixed order)
-            hipLaunchKernelGGL(k_kft_tgt, g2, dim3(KFT_TGT_NT), shy, c->stream, F, k0, -1);
-            hipLaunchKernelGGL(k_kft_tgt, g2, dim3(KFT_TGT_NT), shy, c->stream, F, -1, k1);
-        } else hipLaunchKernelGGL(k_kft_tgt, g2, dim3(KFT_TGT_NT), shy, c->stream, F, k0, k1);
+        if (k0 >= 0 || k1 >= 0) {
+            NRS_TRY(kft_invert(c, *H, k0, k1, d.flags, nbu));
+            hipLaunchKernelGGL(k_kft_gct, g, dim3(256), 0, c->stream, F, k0, k1);
+        }
+        if (H->sh) {
+            if (g0 >= 0 && H->owner(g0) != H->owner(g0 + 1))
+                NRS_TRY(c->comm->handover(c, F.YT, F.YT, 3 * (size_t)H->kf_nf[g0 + 1] * F.ld, H->owner(g0), H->owner(g0 + 1)));
+            if (g1 >= 0 && H->owner(g1) != H->owner(g1 - 1))
+                NRS_TRY(c->comm->handover(c, F.YT + n2, F.YT + n2, 3 * (size_t)H->kf_nf[g1 - 1] * F.ld, H->owner(g1), H->owner(g1 - 1)));
+        }
+        const int t0 = g0 >= 0 && own(g0 + 1) ? g0 : -1, t1 = g1 >= 0 && own(g1 - 1) ? g1 : -1;
+        if (t0 >= 0 && t1 >= 0 && t0 + 1 == t1 - 1) {              // both chains reach the middle keyframe: one after the other (fixed order)
+            hipLaunchKernelGGL(k_kft_tgt, g2, dim3(KFT_TGT_NT), shy, c->stream, F, t0, -1);
+            hipLaunchKernelGGL(k_kft_tgt, g2, dim3(KFT_TGT_NT), shy, c->stream, F, -1, t1);
+        } else if (t0 >= 0 || t1 >= 0) hipLaunchKernelGGL(k_kft_tgt, g2, dim3(KFT_TGT_NT), shy, c->stream, F, t0, t1);
     }
-    NRS_TRY(kft_invert(c, *H, F.m, -1, d.flags));
+    if (own(F.m)) NRS_TRY(kft_invert(c, *H, F.m, -1, d.flags, H->kf_nb[F.m]));
     NRS_HIP(c, hipGetLastError());
     H->factorisations++;
     return NRS_OK;
@@ -921,13 +980,15 @@ static int kft_factor(nrs_ctx* c, Engine* e, KftHost* H, double lam) {
 // small.  This kernel tests the step's residual on its own first, |r| <= rtol |b| over the factorisation's unknowns (fixed-order sums, one
 // workgroup): when it holds the solve is marked converged -- with the iterate the PCG would have returned an iteration later -- and the
 // second pass is never enqueued; when it does not, the PCG carries on as before (pcg_enqueue_batch, nrs_engine.hip).
-__global__ __launch_bounds__(1024) void k_kft_rnorm(KftDev F, Dev P, const double* __restrict__ rv, const double* __restrict__ rp, double tol2, int pub_seq) {
+// Sharded (part != nullptr): the sums over the own keyframes go to part[0..2); k_kft_rtest takes the test on their sum over the ranks.
+__global__ __launch_bounds__(1024) void k_kft_rnorm(KftDev F, Dev P, const double* __restrict__ rv, const double* __restrict__ rp, double tol2, int pub_seq,
+                                                    double* part = nullptr) {
     __shared__ double lds[2 * 16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     double sr = 0, sb = 0;
     const bool live = P.flags[0] == 0;
     if (live)
-        for (int k = 0; k < F.K; ++k) {
+        for (int k = F.k_lo; k < F.k_hi; ++k) {
             const int nf = F.kf_nf[k], np = F.kf_np[k];
             for (int jx = tid; jx < 3 * nf + np; jx += 1024) {
                 double r, b;
@@ -945,6 +1006,7 @@ __global__ __launch_bounds__(1024) void k_kft_rnorm(KftDev F, Dev P, const doubl
     if (tid == 0) {
         sr = 0; sb = 0;
         for (int q = 0; q < 16; ++q) { sr += lds[2 * q]; sb += lds[2 * q + 1]; }
+        if (part) { part[0] = sr; part[1] = sb; return; }
         if (live && sr <= tol2 * sb) {                             // (a NaN fails the test: the PCG's own checks see it)
             __threadfence();
             P.flags[0] = 1;
@@ -953,19 +1015,78 @@ __global__ __launch_bounds__(1024) void k_kft_rnorm(KftDev F, Dev P, const doubl
     }
 }
 
+__global__ void k_kft_rtest(Dev P, const double* __restrict__ sum, double tol2, int pub_seq) {
+    if (threadIdx.x != 0) return;
+    if (P.flags[0] == 0 && sum[0] <= tol2 * sum[1]) {
+        __threadfence();
+        P.flags[0] = 1;
+    }
+    if (pub_seq != 0) publish_flags(P, pub_seq);
+}
+
+// the residual test of the first step (k_kft_rnorm): sharded, its two sums over the ranks (every rank takes the same decision)
+static int kft_rtest(nrs_ctx* c, Engine* e, KftHost* H, const double* rv, const double* rp, double tol2, int pub_seq) {
+    const Dev& d = e->d;
+    if (!H->sh) {
+        hipLaunchKernelGGL(k_kft_rnorm, dim3(1), dim3(1024), 0, c->stream, H->d, d, rv, rp, tol2, pub_seq, nullptr);
+        return NRS_OK;
+    }
+    hipLaunchKernelGGL(k_kft_rnorm, dim3(1), dim3(1024), 0, c->stream, H->d, d, rv, rp, tol2, 0, H->rn);
+    NRS_TRY(c->comm->allreduce(c, H->rn, H->rn + 2, 2));
+    hipLaunchKernelGGL(k_kft_rtest, dim3(1), dim3(64), 0, c->stream, d, H->rn + 2, tol2, pub_seq);
+    return NRS_OK;
+}
+
+__global__ __launch_bounds__(256) void k_kft_pose_share(KftDev F, const double* __restrict__ up, double* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 6 * F.K) return;
+    const int k = i / 6;
+    out[i] = (k >= F.k_lo && k < F.k_hi) ? up[i] : 0.0;
+}
+
+// u = M^-1 r over the keyframe chains.  Sharded: the one-GPU stage order; a rank runs the stages of its own keyframes, and where a chain
+// crosses a rank boundary the vector its next stage reads (z forward, xs backward) moves to the neighbour.  u lands on the own rows (the
+// operator's boundary exchange carries it on); the pose part is summed over the ranks (every rank holds every pose).
 static int kft_apply(nrs_ctx* c, KftHost* H, const double* rv, const double* rp, double* uv, double* up, const int* flags) {
     const KftDev& F = H->d;
     const int len0 = F.m, len1 = F.K - 1 - F.m, ns = std::max(len0, len1);
     const dim3 b(256);
     const size_t shm = sizeof(double) * F.ld;
-    auto stage = [&](int mode, int k0, int k1) {
+    auto own = [&](int k) { return k >= F.k_lo && k < F.k_hi; };
+    auto stage = [&](int mode, int g0, int g1) {
+        const int k0 = g0 >= 0 && own(g0) ? g0 : -1, k1 = g1 >= 0 && own(g1) ? g1 : -1;
+        if (k0 < 0 && k1 < 0) return;
         const int nch = k1 >= 0 ? 2 : 1;
         hipLaunchKernelGGL(k_kft_vec, dim3((F.ld + 255) / 256, nch), b, 0, c->stream, F, mode, k0, k1, rv, rp, flags);
         hipLaunchKernelGGL(k_kft_gemv, dim3(F.ld / 16, nch), b, shm, c->stream, F, mode, k0, k1, uv, up, flags);
     };
-    for (int s = 0; s < ns; ++s) stage(0, s < len0 ? s : -1, s < len1 ? F.K - 1 - s : -1);
+    auto move = [&](double* v, int k, int to) -> int {            // the vector of keyframe k to the rank that holds keyframe `to`
+        const int a = H->owner(k), bb = H->owner(to);
+        if (a == bb) return NRS_OK;
+        return c->comm->handover(c, v + (size_t)k * F.ld, v + (size_t)k * F.ld, (size_t)F.ld, a, bb);
+    };
+    for (int s = 0; s < ns; ++s) {
+        const int g0 = s < len0 ? s : -1, g1 = s < len1 ? F.K - 1 - s : -1;
+        stage(0, g0, g1);
+        if (H->sh) {
+            if (g0 >= 0) NRS_TRY(move(F.z, g0, g0 + 1));
+            if (g1 >= 0) NRS_TRY(move(F.z, g1, g1 - 1));
+        }
+    }
     stage(1, F.m, -1);
-    for (int s = ns - 1; s >= 0; --s) stage(2, s < len0 ? s : -1, s < len1 ? F.K - 1 - s : -1);
+    for (int s = ns - 1; s >= 0; --s) {
+        const int g0 = s < len0 ? s : -1, g1 = s < len1 ? F.K - 1 - s : -1;
+        if (H->sh) {
+            if (g0 >= 0) NRS_TRY(move(F.xs, g0 + 1, g0));
+            if (g1 >= 0) NRS_TRY(move(F.xs, g1 - 1, g1));
+        }
+        stage(2, g0, g1);
+    }
+    if (H->sh) {
+        hipLaunchKernelGGL(k_kft_pose_share, dim3((6 * F.K + 255) / 256), dim3(256), 0, c->stream, F, up, H->pose_ws);
+        NRS_TRY(c->comm->allreduce(c, H->pose_ws, H->pose_ws + 6 * (size_t)F.K, 6 * (size_t)F.K));
+        NRS_HIP(c, hipMemcpyAsync(up, H->pose_ws + 6 * (size_t)F.K, sizeof(double) * 6 * (size_t)F.K, hipMemcpyDeviceToDevice, c->stream));
+    }
     return NRS_OK;
 }
 

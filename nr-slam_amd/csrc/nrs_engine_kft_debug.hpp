@@ -9,6 +9,9 @@ namespace nrs {
 //   what 2: the coupling T_k as a dense ld x ld matrix (rows: keyframe k, columns: keyframe k + 1)       (out_d)
 //   what 3: u = M^-1 r for r given in solver order (6 K pose entries, then 3 per vertex); u in the same order (in_d -> out_d)
 //   what 4: per vertex its (keyframe, compact node) pair, -1 for a fixed vertex                          (out_i, 2 M ints)
+//   what 5: this rank's share {first own keyframe, own keyframes, m, rank of m, factor KiB held, hand-overs per factorisation}  (out_i, 6)
+// Sharded (a communicator): what 1 / 2 / 3 linearise and assemble, so every rank calls them together; what 1 / 2 return the block of an
+// own keyframe (NRS_ERR_INVALID on the other ranks), what 3 returns the complete u on every rank.
 int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const double* in_d, double* out_d, int32_t* out_i) {
     Dev& d = e->d;
     KftHost* H = e->kft;
@@ -23,6 +26,11 @@ int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const d
     if (!H || !H->on) return c->fail(NRS_ERR_STATE, "no keyframe-block factorisation on this window");
     const KftDev& F = H->d;
     const size_t n2 = (size_t)F.ld * F.ld;
+    if (what == 5) {
+        out_i[0] = F.k_lo; out_i[1] = F.k_hi - F.k_lo; out_i[2] = F.m; out_i[3] = H->r_m;
+        out_i[4] = (int32_t)(H->factor_bytes >> 10); out_i[5] = H->handovers;
+        return NRS_OK;
+    }
     if (what == 4) {
         std::vector<int> rc((size_t)d.n_rows);
         NRS_HIP(c, hipMemcpy(rc.data(), F.row_ci, 4 * rc.size(), hipMemcpyDeviceToHost));
@@ -34,13 +42,9 @@ int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const d
     NRS_TRY(evaluate<true>(c, e, e->cur));
     NRS_TRY(read_scalars(c, e));
     if (what == 1 || what == 2) {
-        if (k < 0 || k >= F.K) return c->fail(NRS_ERR_INVALID, "keyframe out of range");
-        hipLaunchKernelGGL(k_kft_clear, dim3((unsigned)((n2 / 2 + 255) / 256), F.K), dim3(256), 0, c->stream, F);
-        hipLaunchKernelGGL(k_kft_diag, dim3(d.n_rows / SK_RPB), dim3(BLK), 0, c->stream, d, F, lam);
-        hipLaunchKernelGGL(k_kft_pose, dim3((36 * F.K + 255) / 256), dim3(256), 0, c->stream, d, F, lam);
-        if (F.n_pp) hipLaunchKernelGGL(k_kft_pairs, dim3((unsigned)(((size_t)F.n_pp * KFT_PL + 255) / 256)), dim3(256), 0, c->stream, d, F);
-        if (F.n_tp) hipLaunchKernelGGL(k_kft_tvals, dim3((F.n_tp + 255) / 256), dim3(256), 0, c->stream, d, F);
+        NRS_TRY(kft_assemble(c, e, H, lam));
         NRS_HIP(c, hipStreamSynchronize(c->stream));
+        if (k < F.k_lo || k >= F.k_hi) return c->fail(NRS_ERR_INVALID, "keyframe out of range (or not held by this rank)");
         if (what == 1) { NRS_HIP(c, hipMemcpy(out_d, F.A + (size_t)k * n2, 8 * n2, hipMemcpyDeviceToHost)); return NRS_OK; }
         std::vector<int> ptr((size_t)F.K * (F.nfm + 1)), from((size_t)F.n_tp + 1), tp((size_t)F.n_tp + 1);
         std::vector<double> tv((size_t)F.n_tp + 1);
@@ -59,18 +63,44 @@ int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const d
         NRS_TRY(kft_factor(c, e, H, lam));
         std::vector<double> rv(3 * (size_t)d.n_rows, 0.0);
         for (int v = 0; v < d.M; ++v) for (int a = 0; a < 3; ++a) rv[3 * (size_t)e->vrow[v] + a] = in_d[6 * (size_t)d.K + 3 * (size_t)v + a];
-        NRS_HIP(c, hipMemcpyAsync(d.rv, rv.data(), 8 * rv.size(), hipMemcpyHostToDevice, c->stream));
+        const size_t o = 3 * (size_t)d.row_lo, nr = 3 * (size_t)(d.row_hi - d.row_lo);   // (the rows this engine holds: all of them on one GPU)
+        NRS_HIP(c, hipMemcpyAsync(d.rv + o, rv.data() + o, 8 * nr, hipMemcpyHostToDevice, c->stream));
         NRS_HIP(c, hipMemcpyAsync(d.rp, in_d, 8 * 6 * (size_t)d.K, hipMemcpyHostToDevice, c->stream));
-        NRS_HIP(c, hipMemsetAsync(d.uv3, 0, 8 * 3 * (size_t)d.n_rows, c->stream));
+        NRS_HIP(c, hipMemsetAsync(d.uv3 + o, 0, 8 * nr, c->stream));
         NRS_HIP(c, hipMemsetAsync(d.up, 0, 8 * 6 * (size_t)d.K, c->stream));
         NRS_TRY(kft_apply(c, H, d.rv, d.rp, d.uv3, d.up, d.flags));
         NRS_HIP(c, hipGetLastError());
-        NRS_HIP(c, hipMemcpyAsync(rv.data(), d.uv3, 8 * rv.size(), hipMemcpyDeviceToHost, c->stream));
+        NRS_HIP(c, hipMemcpyAsync(rv.data() + o, d.uv3 + o, 8 * nr, hipMemcpyDeviceToHost, c->stream));
         NRS_HIP(c, hipMemcpyAsync(out_d, d.up, 8 * 6 * (size_t)d.K, hipMemcpyDeviceToHost, c->stream));
         int fl[8];
         NRS_HIP(c, hipMemcpyAsync(fl, d.flags, sizeof(fl), hipMemcpyDeviceToHost, c->stream));
         NRS_HIP(c, hipStreamSynchronize(c->stream));
         for (int v = 0; v < d.M; ++v) for (int a = 0; a < 3; ++a) out_d[6 * (size_t)d.K + 3 * (size_t)v + a] = rv[3 * (size_t)e->vrow[v] + a];
+        if (H->sh) {                                               // the complete u on every rank: own node copies here, the poses from rank 0, summed
+            const int r_lo = F.row0, r_hi = F.row0 + H->rows_own;
+            const size_t n = 6 * (size_t)d.K + 3 * (size_t)d.M;
+            if (c->comm->rank != 0) std::fill(out_d, out_d + 6 * (size_t)d.K, 0.0);
+            for (int v = 0; v < d.M; ++v)
+                if (e->vrow[v] < r_lo || e->vrow[v] >= r_hi) for (int a = 0; a < 3; ++a) out_d[6 * (size_t)d.K + 3 * (size_t)v + a] = 0.0;
+            NRS_TRY(c->ensure(c->gather_ws, 2 * sizeof(double) * n));
+            double* g = c->gather_ws.as<double>();
+            NRS_HIP(c, hipMemcpyAsync(g, out_d, 8 * n, hipMemcpyHostToDevice, c->stream));
+            NRS_TRY(c->comm->allreduce(c, g, g + n, n));
+            NRS_HIP(c, hipMemcpyAsync(out_d, g + n, 8 * n, hipMemcpyDeviceToHost, c->stream));
+            NRS_HIP(c, hipStreamSynchronize(c->stream));
+            c->release(c->gather_ws);
+            int bad = fl[2], any = 0;                              // (a pivot failure on any rank fails every rank)
+            NRS_TRY(c->ensure(c->gather_ws, 2 * sizeof(double)));
+            double fv = bad ? 1.0 : 0.0, fs = 0.0;
+            g = c->gather_ws.as<double>();
+            NRS_HIP(c, hipMemcpyAsync(g, &fv, 8, hipMemcpyHostToDevice, c->stream));
+            NRS_TRY(c->comm->allreduce(c, g, g + 1, 1));
+            NRS_HIP(c, hipMemcpyAsync(&fs, g + 1, 8, hipMemcpyDeviceToHost, c->stream));
+            NRS_HIP(c, hipStreamSynchronize(c->stream));
+            c->release(c->gather_ws);
+            any = fs != 0.0;
+            fl[2] = any;
+        }
         if (fl[2]) return c->fail(NRS_ERR_NUMERIC, "keyframe-block factorisation: a pivot that is not positive");
         return NRS_OK;
     }

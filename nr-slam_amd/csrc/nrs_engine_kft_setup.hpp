@@ -30,6 +30,21 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
     if (nf_max >= 4096 || nf_max < 1) return NRS_OK;
     const int ld = ((3 * nf_max + 6 + KFT_B - 1) / KFT_B) * KFT_B, nb = ld / KFT_B, nfm = ld / 3;
     const size_t n2 = (size_t)ld * ld;
+    // k_kft_tgt stages KFT_TC rows of ld doubles in LDS, k_kft_step its panels: beyond the device's LDS (ld > 5120 on gfx950) the
+    // launches would fail on every trial -- the block-Jacobi PCG instead
+    const size_t lds_cap = std::max(c->prop.sharedMemPerBlock, c->prop.sharedMemPerBlockOptin);
+    if (sizeof(double) * KFT_TC * (size_t)ld > lds_cap || KFT_STEP_LDS > lds_cap || KFT_PANEL_LDS > lds_cap) return NRS_OK;
+    // Sharded (nrs_options.sharded_kft, world > 1): the decisions above and below are taken on the complete window, which every rank
+    // uploads; a rank holds the blocks of its own keyframes [k_lo, k_hi), the couplings that touch them and the hand-over slots
+    const bool sh = d.sh_on && d.sh_world > 1;
+    const int k_lo = d.sh_k0, k_hi = d.sh_k0 + d.sh_nk, nk = k_hi - k_lo;   // (the whole window on one GPU)
+    const int zlo = std::max(0, k_lo - 1), zhi = std::min(K, k_hi + 1);
+    const int own_lo = pose_grp_ptr[k_lo] * ROW_ALIGN, own_hi = pose_grp_ptr[k_hi] * ROW_ALIGN;
+    auto own = [&](int k) { return k >= k_lo && k < k_hi; };
+    std::vector<int> kb(d.sh_world + 1, 0);
+    if (sh) shard_plan(K, pose_grp_ptr.data(), d.sh_world, kb.data());
+    else kb[1] = K;
+    auto owner = [&](int k) { int r = 0; while (k >= kb[r + 1]) ++r; return r; };
     if (c->opt.embedded_solver == 0) {
         // automatic choice by a cost model of the two solvers, fitted on tools/kft_probe.py runs (10 .. 40 keyframes, 100 .. 650 nodes per keyframe,
         // profiles/r06_kft_crossover.txt): the factorisation is ceil(K / 2) dependent inversions of nb + 1 launches, (16.5 + 0.72 nb) us a launch
@@ -43,7 +58,8 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
         const double kft_ms = ((K + 1) / 2) * (nb + 1.0) * launch_us * 1e-3 + 0.05 * K, pcg_ms = (14.0 + 0.016 * std::max(0, nf_max - 500)) * std::pow(K / 20.0, 0.45);
         if (kft_ms > pcg_ms) return NRS_OK;
     }
-    if ((size_t)K * n2 * sizeof(double) > ((size_t)6 << 30)) return NRS_OK;       // (the factor would not be worth its memory: the PCG stays block-Jacobi)
+    // (the factor would not be worth its memory: the PCG stays block-Jacobi.  Sharded: judged on the rank's own blocks, and agreed below)
+    bool fits = (size_t)nk * n2 * sizeof(double) <= ((size_t)6 << 30);
     std::vector<int> kf_row((size_t)K * nfm, -1);
     for (int k = 0; k < K; ++k)
         for (int r = pose_grp_ptr[k] * ROW_ALIGN; r < pose_grp_ptr[k + 1] * ROW_ALIGN; ++r)
@@ -66,27 +82,60 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
     }
     std::vector<KftEnt> te;
     te.reserve(4 * (size_t)s.n_dm);
+    // A damper's value is read from the slot of its first free vertex (one GPU: every slot is linearised).  Sharded, that slot is
+    // linearised by the rank whose rows hold the vertex only: a damper whose vertices lie on two ranks is a boundary damper, and its value
+    // reaches the other rank through bd_val (all-reduced per factorisation, kft_assemble) -- the same bits as the slot's.
+    std::vector<int> bd_slot;
     for (int q = 0; q < s.n_dm; ++q) {
         const int* v = s.dm_idx + 4 * (size_t)q;                   // (1c, 2c, 1n, 2n), -1: absent
-        int kk[4], cc[4], pos = -1;
+        int kk[4], cc[4], rs = -1;
         for (int r = 0; r < 4; ++r) {
             kk[r] = v[r] >= 0 ? vk(v[r]) : -1; cc[r] = v[r] >= 0 ? vc(v[r]) : -1;
-            if (pos < 0 && cc[r] >= 0) pos = e->dm_pos[4 * (size_t)q + r];
+            if (rs < 0 && cc[r] >= 0) rs = r;
         }
-        if (pos < 0) continue;
-        // J = (-w, +w, +w, -w) I on (1c, 2c, 1n, 2n): block (p, q) = sg_p sg_q s I
-        if (v[0] >= 0 && v[1] >= 0) { if (kk[0] != kk[1]) return NRS_OK; add_pair(kk[0], cc[0], cc[1], (1u << 30) | (uint32_t)pos, 0.0); }
-        if (v[2] >= 0 && v[3] >= 0) { if (kk[2] != kk[3]) return NRS_OK; add_pair(kk[2], cc[2], cc[3], (1u << 30) | (uint32_t)pos, 0.0); }
+        if (rs < 0) continue;
+        int pos = -1;
+        uint32_t pe_ref = 0, te_ref = 0;
+        {
+            int klo = K, khi = -1;
+            for (int r = 0; r < 4; ++r) if (v[r] >= 0) { klo = std::min(klo, kk[r]); khi = std::max(khi, kk[r]); }
+            const int row = e->vrow[v[rs]];
+            const bool held = row >= own_lo && row < own_hi;
+            if (sh && owner(klo) != owner(khi)) {
+                const int bd = (int)bd_slot.size();
+                bd_slot.push_back(held ? e->dm_pos[4 * (size_t)q + rs] : -1);
+                pe_ref = (3u << 30) | (uint32_t)bd; te_ref = KFT_BD | (uint32_t)bd; pos = 0;
+            } else if (held || !sh) {
+                pos = e->dm_pos[4 * (size_t)q + rs];
+                pe_ref = (1u << 30) | (uint32_t)pos; te_ref = (uint32_t)pos;
+            }
+        }
+        // the window-wide checks come before the sharded skip below: every rank takes the same decision on every damper
         static const int cur[2] = {0, 1}, nxt[2] = {2, 3};
+        if (v[0] >= 0 && v[1] >= 0 && kk[0] != kk[1]) return NRS_OK;
+        if (v[2] >= 0 && v[3] >= 0 && kk[2] != kk[3]) return NRS_OK;
+        for (int x = 0; x < 2; ++x)
+            for (int y = 0; y < 2; ++y) {
+                const int a = cur[x], b = nxt[y];
+                if (v[a] >= 0 && v[b] >= 0 && cc[a] >= 0 && cc[b] >= 0 && kk[b] != kk[a] + 1) return NRS_OK;   // (a damper that does not join consecutive keyframes)
+            }
+        if (pos < 0) continue;                                     // (sharded: a damper of other ranks' keyframes)
+        // J = (-w, +w, +w, -w) I on (1c, 2c, 1n, 2n): block (p, q) = sg_p sg_q s I
+        if (v[0] >= 0 && v[1] >= 0) add_pair(kk[0], cc[0], cc[1], pe_ref, 0.0);
+        if (v[2] >= 0 && v[3] >= 0) add_pair(kk[2], cc[2], cc[3], pe_ref, 0.0);
         for (int x = 0; x < 2; ++x)
             for (int y = 0; y < 2; ++y) {
                 const int a = cur[x], b = nxt[y];
                 if (v[a] < 0 || v[b] < 0 || cc[a] < 0 || cc[b] < 0) continue;
-                if (kk[b] != kk[a] + 1) return NRS_OK;             // (a damper that does not join consecutive keyframes)
+                if (!own(kk[a]) && !own(kk[b])) continue;          // (sharded: the couplings that touch an own keyframe)
                 const bool minus = (x == y);                       // (1c,1n), (2c,2n): - s ; (1c,2n), (2c,1n): + s
-                te.push_back(KftEnt{((uint64_t)kk[a] << 24) | ((uint64_t)cc[a] << 12) | (uint64_t)cc[b], (minus ? 0x80000000u : 0u) | (uint32_t)pos, 0.0});
+                te.push_back(KftEnt{((uint64_t)kk[a] << 24) | ((uint64_t)cc[a] << 12) | (uint64_t)cc[b], (minus ? 0x80000000u : 0u) | te_ref, 0.0});
             }
     }
+    // every check above is taken on the whole window, alike on every rank; what follows (memory, list sizes) is this rank's own.  Sharded,
+    // a rank that cannot hold its share leaves e->kft unset, and engine_kft_agree -- after the upload's agreement -- drops the
+    // factorisation on every rank (no collective here: a peer's set-up may have failed before this point)
+    e->kft_wanted = sh;
     mark("edge entries");
     // The skinned observations' pairs (55 per observation: 5 M at C2) are never materialised: per keyframe -- in parallel -- a counting pass
     // over (hi, lo) < nf^2, then a placing pass straight into the keyframe's sorted source / weight arrays.  Order inside a pair's list:
@@ -116,6 +165,7 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
             std::vector<int> cnt;
             std::vector<int> cn((size_t)SK_MAX);
             for (int k = (int)ka; k < (int)kb; ++k) {
+                if (!own(k)) continue;                             // (sharded: the own keyframes' blocks only)
                 const size_t nk = (size_t)kf_nf[k], nkey = nk * nk;
                 cnt.assign(nkey + 1, 0);
                 auto each_skin_pair = [&](auto&& fn) {
@@ -161,7 +211,7 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
     {
         size_t n_pairs = 0;
         for (int k = 0; k < K; ++k) { n_pairs += kl[k].pp_id.size(); ent_base[k + 1] = ent_base[k] + kl[k].pe_src.size(); }
-        if (ent_base[K] >= ((size_t)1 << 31)) return NRS_OK;
+        if (ent_base[K] >= ((size_t)1 << 31)) fits = false;
         pp_id.reserve(n_pairs); pp_ptr.reserve(n_pairs + 1);
         for (int k = 0; k < K; ++k) {
             pp_id.insert(pp_id.end(), kl[k].pp_id.begin(), kl[k].pp_id.end());
@@ -206,13 +256,20 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
     const size_t tile = (size_t)KFT_B * KFT_B;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t o_A = take(8 * (size_t)K * n2), o_YT = take(8 * 2 * n2), o_Bb = take(8 * 4 * nb * tile), o_Cb = take(8 * 4 * nb * tile), o_Pv = take(8 * 4 * tile),
-                 o_z = take(8 * (size_t)K * ld), o_xs = take(8 * (size_t)K * ld), o_vb = take(8 * 2 * (size_t)ld), o_nf = take(4 * (size_t)K), o_np = take(4 * (size_t)K), o_kr = take(4 * kf_row.size()),
+    const int n_bd = (int)bd_slot.size();
+    const size_t o_A = take(8 * (size_t)nk * n2), o_YT = take(8 * 2 * n2), o_Bb = take(8 * 4 * nb * tile), o_Cb = take(8 * 4 * nb * tile), o_Pv = take(8 * 4 * tile),
+                 o_z = take(8 * (size_t)(zhi - zlo) * ld), o_xs = take(8 * (size_t)(zhi - zlo) * ld), o_vb = take(8 * 2 * (size_t)ld), o_nf = take(4 * (size_t)K), o_np = take(4 * (size_t)K), o_kr = take(4 * kf_row.size()),
                  o_rc = take(4 * row_ci.size()), o_ppid = take(4 * (n_pp + 1)), o_ppp = take(4 * (n_pp + 1)), o_pes = take(4 * (pe_size + 1)), o_pew = take(8 * (pe_size + 1)),
                  o_tpp = take(4 * (n_tp + 1)), o_tes = take(4 * (te.size() + 1)), o_tpv = take(8 * (n_tp + 1)),
                  o_cp0 = take(4 * cl_ptr[0].size()), o_cp1 = take(4 * cl_ptr[1].size()), o_cf0 = take(4 * (n_tp + 1)), o_cf1 = take(4 * (n_tp + 1)),
-                 o_ct0 = take(4 * (n_tp + 1)), o_ct1 = take(4 * (n_tp + 1)), o_cv0 = take(8 * (n_tp + 1)), o_cv1 = take(8 * (n_tp + 1));
-    if (c->ensure(c->dba_kft, off) != NRS_OK) return NRS_OK;      // (no memory for the factor: block-Jacobi PCG)
+                 o_ct0 = take(4 * (n_tp + 1)), o_ct1 = take(4 * (n_tp + 1)), o_cv0 = take(8 * (n_tp + 1)), o_cv1 = take(8 * (n_tp + 1)),
+                 o_bds = take(4 * ((size_t)n_bd + 1)), o_bdb = take(8 * 2 * ((size_t)n_bd + 1)), o_pw = take(sh ? 8 * 12 * (size_t)K : 0), o_rn = take(8 * 4);
+    if (fits && c->ensure(c->dba_kft, off) != NRS_OK) {            // (no memory for the factor: block-Jacobi PCG, without a stale error behind)
+        (void)hipGetLastError();
+        c->err[0] = 0;
+        fits = false;
+    }
+    if (!fits) { c->release(c->dba_kft); return NRS_OK; }
     mark("device buffer");
     char* base = c->dba_kft.as<char>();
     auto up = [&](size_t o, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
@@ -223,17 +280,21 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
     NRS_HIP(c, up(o_cp0, cl_ptr[0].data(), 4 * cl_ptr[0].size())); NRS_HIP(c, up(o_cp1, cl_ptr[1].data(), 4 * cl_ptr[1].size()));
     NRS_HIP(c, up(o_cf0, cl_from[0].data(), 4 * n_tp)); NRS_HIP(c, up(o_cf1, cl_from[1].data(), 4 * n_tp));
     NRS_HIP(c, up(o_ct0, cl_tp[0].data(), 4 * n_tp)); NRS_HIP(c, up(o_ct1, cl_tp[1].data(), 4 * n_tp));
+    NRS_HIP(c, up(o_bds, bd_slot.data(), 4 * (size_t)n_bd));
     NRS_HIP(c, hipMemsetAsync(base + o_z, 0, o_nf - o_z, c->stream));     // (z and xs)
+    NRS_HIP(c, hipMemsetAsync(base + o_bdb, 0, o_rn + 8 * 4 - o_bdb, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     mark("uploads");
-    KftHost* H = new (std::nothrow) KftHost();
+    std::unique_ptr<KftHost> H(new (std::nothrow) KftHost());
     if (!H) return c->fail(NRS_ERR_ALLOC, "out of host memory");
     KftDev& F = H->d;
     memset(&F, 0, sizeof(F));
     F.K = K; F.ld = ld; F.nb = nb; F.m = K / 2; F.nfm = nfm;
-    F.A = reinterpret_cast<double*>(base + o_A); F.YT = reinterpret_cast<double*>(base + o_YT);
+    F.k_lo = k_lo; F.k_hi = k_hi; F.row0 = own_lo;
+    // (A, z and xs are addressed by the GLOBAL keyframe index: the pointers are biased by the first block / vector held)
+    F.A = reinterpret_cast<double*>(base + o_A) - (size_t)k_lo * n2; F.YT = reinterpret_cast<double*>(base + o_YT);
     F.Bb = reinterpret_cast<double*>(base + o_Bb); F.Cb = reinterpret_cast<double*>(base + o_Cb); F.Pv = reinterpret_cast<double*>(base + o_Pv);
-    F.z = reinterpret_cast<double*>(base + o_z); F.xs = reinterpret_cast<double*>(base + o_xs); F.vb = reinterpret_cast<double*>(base + o_vb);
+    F.z = reinterpret_cast<double*>(base + o_z) - (size_t)zlo * ld; F.xs = reinterpret_cast<double*>(base + o_xs) - (size_t)zlo * ld; F.vb = reinterpret_cast<double*>(base + o_vb);
     F.kf_nf = reinterpret_cast<const int*>(base + o_nf); F.kf_np = reinterpret_cast<const int*>(base + o_np);
     F.kf_row = reinterpret_cast<const int*>(base + o_kr); F.row_ci = reinterpret_cast<const int*>(base + o_rc);
     F.n_pp = (int)n_pp; F.pp_id = reinterpret_cast<const uint32_t*>(base + o_ppid); F.pp_ptr = reinterpret_cast<const int*>(base + o_ppp);
@@ -252,11 +313,44 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
         NRS_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_kft_step<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KFT_STEP_LDS));
         attr_done = true;
     }
+    F.bd_val = reinterpret_cast<const double*>(base + o_bdb) + n_bd;
     H->bytes = off;
+    H->factor_bytes = o_Bb - o_A;                                  // (what was carved for the blocks and the two operands)
     H->kf_nb.resize(K);
     for (int k = 0; k < K; ++k) H->kf_nb[k] = std::max(1, (3 * kf_nf[k] + kf_np[k] + KFT_B - 1) / KFT_B);
+    H->kf_nf = kf_nf;
+    H->rows_own = own_hi - own_lo;
+    H->sh = sh;
+    H->kb = kb;
+    H->r_m = owner(K / 2);
+    H->handovers = sh ? d.sh_world - 1 : 0;                        // (every rank boundary is crossed by one chain, once)
+    H->n_bd = n_bd;
+    H->bd_slot = reinterpret_cast<const int*>(base + o_bds);
+    H->bd_buf = reinterpret_cast<double*>(base + o_bdb);
+    H->pose_ws = sh ? reinterpret_cast<double*>(base + o_pw) : nullptr;
+    H->rn = reinterpret_cast<double*>(base + o_rn);
     H->on = true;
-    e->kft = H;
+    e->kft = H.release();
+    return NRS_OK;
+}
+
+// Sharded windows: the window-wide checks of kft_setup chose the factorisation alike on every rank (kft_wanted), but a rank may not
+// hold its share (memory, list sizes).  Called by every rank once the upload's own agreement has succeeded: one all-reduced flag, and
+// the factorisation stays on every rank or on none -- every rank then calls the same collectives in the solve.
+int engine_kft_agree(nrs_ctx* c, Engine* e) {
+    if (!e || !e->kft_wanted || !c->comm || c->comm->world == 1) return NRS_OK;
+    NRS_TRY(c->ensure(c->comm_flag, 2 * sizeof(double)));        // (already there: the upload's agreement used it)
+    double* d = c->comm_flag.as<double>();
+    double flag = e->kft && e->kft->on ? 0.0 : 1.0, sum = 0.0;
+    NRS_HIP(c, hipMemcpyAsync(d, &flag, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    NRS_TRY(c->comm->allreduce(c, d, d + 1, 1));
+    NRS_HIP(c, hipMemcpyAsync(&sum, d + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (sum != 0.0) {                                              // some rank cannot hold its share: block-Jacobi PCG everywhere
+        delete e->kft;
+        e->kft = nullptr;
+        c->release(c->dba_kft);
+    }
     return NRS_OK;
 }
 

@@ -1250,7 +1250,9 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     }
     d.sk_pcg = (d.sk_n > 0 && !(e->nd && e->nd->on)) ? 1 : 0;      // (on the direct solver k_nd_values folds the observations into its blocks)
     if (d.sk_pcg) d.ecd = 0;                                       // (k_pcg_update<true> owns 16 rows a workgroup: no r.u partials per 256 rows for the operator's early test -- one launch in hundreds)
-    if (d.sk_pcg && s.sk_pose && d.use_lds && !d.sh_on && !d.hier && c->opt.embedded_solver != 2) {   // embedded BA window: the keyframe-block factorisation as the PCG's preconditioner
+    // embedded BA window: the keyframe-block factorisation as the PCG's preconditioner.  On a communicator only with sharded_kft = 1 (a
+    // sharded window reduces hierarchically: the factorisation's u replaces the update's after the all-reduced scalars, as on one GPU)
+    if (d.sk_pcg && s.sk_pose && d.use_lds && (d.sh_on ? c->opt.sharded_kft == 1 : !d.hier) && c->opt.embedded_solver != 2) {
         NRS_TRY(kft_setup(c, e, s, pose_grp_ptr));
         mark("keyframe-block factorisation plan");
     }

@@ -230,6 +230,7 @@ struct Engine {
     Dev d;
     NdEngine* nd = nullptr;
     KftHost* kft = nullptr;
+    bool kft_wanted = false;         // sharded (world > 1): the window-wide checks chose the factorisation; whether every rank holds its share is agreed by engine_kft_agree
     Arena* arena = nullptr;
     int cur = 0;
     int n_spec = 0;                  // shadow sets carved for speculative trials (single-frame engines; 0: none)

@@ -457,6 +457,7 @@ extern "C" int nrs_create(nrs_ctx** out, const nrs_options* opt) {
     }
     if (c->opt.direct_solve < 0 || c->opt.direct_solve > 2) c->opt.direct_solve = 0;
     if (c->opt.embedded_solver < 0 || c->opt.embedded_solver > 2) c->opt.embedded_solver = 0;
+    if (c->opt.sharded_kft != 1) c->opt.sharded_kft = 0;
     if (c->opt.pcg_rtol <= 0) c->opt.pcg_rtol = 1e-10;
     c->dbg.load_environment();
     if (const char* e = c->env("NRS_PCG_RTOL")) { const double v = atof(e); if (v > 0) c->opt.pcg_rtol = v; }   // experiments only

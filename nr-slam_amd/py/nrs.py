@@ -68,7 +68,7 @@ def debug_clear():
 class Options(C.Structure):
     _fields_ = [("device", C.c_int32), ("struct_size", C.c_uint32), ("pcg_rtol", C.c_double), ("pcg_max_iters", C.c_int32),
                 ("pcg_batch", C.c_int32), ("profile", C.c_int32), ("exact_trials", C.c_int32), ("direct_solve", C.c_int32),
-                ("embedded_solver", C.c_int32)]
+                ("embedded_solver", C.c_int32), ("sharded_kft", C.c_int32)]
 
 
 class LmTrial(C.Structure):
@@ -334,9 +334,11 @@ class RGraph:
 
 
 class Context:
-    def __init__(self, device=-1, pcg_rtol=0.0, pcg_max_iters=0, pcg_batch=0, profile=0, exact_trials=0, direct_solve=0, embedded_solver=0):
+    def __init__(self, device=-1, pcg_rtol=0.0, pcg_max_iters=0, pcg_batch=0, profile=0, exact_trials=0, direct_solve=0, embedded_solver=0,
+                 sharded_kft=0):
         self.lib = load_library()
-        opt = Options(device, C.sizeof(Options), pcg_rtol, pcg_max_iters, pcg_batch, profile, exact_trials, direct_solve, embedded_solver)
+        opt = Options(device, C.sizeof(Options), pcg_rtol, pcg_max_iters, pcg_batch, profile, exact_trials, direct_solve, embedded_solver,
+                      sharded_kft)
         self.h = C.c_void_p()
         rc = self.lib.nrs_create(C.byref(self.h), C.byref(opt))
         if rc != OK:
@@ -774,6 +776,12 @@ class Context:
         u = np.zeros_like(r)
         self._chk(self.lib.nrs_debug_kft(self.h, C.c_double(lam), C.c_int32(3), C.c_int32(0), _p(r, C.c_double), _p(u, C.c_double), None))
         return u
+
+    def debug_kft_share(self):
+        """this rank's share of the keyframe-block factorisation: dict(k0, nk, m, r_m, kib, handovers) (one GPU: the whole window)"""
+        o = np.zeros(6, np.int32)
+        self._chk(self.lib.nrs_debug_kft(self.h, C.c_double(0.0), C.c_int32(5), C.c_int32(0), None, None, _p(o, C.c_int32)))
+        return dict(k0=int(o[0]), nk=int(o[1]), m=int(o[2]), r_m=int(o[3]), kib=int(o[4]), handovers=int(o[5]))
 
     def debug_kft_index(self):
         o = np.zeros((self._n_lm, 2), np.int32)
