@@ -440,6 +440,33 @@ static int direct_trial_enqueue(nrs_ctx* c, Engine* e, int set, double lam, int*
     return NRS_OK;
 }
 
+// The engine seen through shadow set `set` of a PCG BA window (nrs_engine_types.hpp SpecSet; set < 0: the engine itself): everything
+// an LM trial writes -- solve vectors, preconditioner inverses, partials, scalars, status words, trial state, host mirrors -- is the
+// set's, its launches go to the set's stream, its PCG launches become no-ops once the set's abort word holds abort_id.  The
+// linearisation and the current state are the engine's.  pcg_begin / pcg_enqueue_batch / pcg_advance / evaluate and the host waits
+// run unchanged on this view; the engine's own arrays, stream and mirrors come back when it goes.
+struct PcgSetView {
+    nrs_ctx* c; Engine* e; Dev saved; hipStream_t main; double* hs; int* hf; bool on;
+    PcgSetView(nrs_ctx* c_, Engine* e_, int set, int abort_id)
+        : c(c_), e(e_), saved(e_->d), main(c_->stream), hs(e_->h_scal), hf(e_->h_flags), on(set >= 0) {
+        if (!on) return;
+        const SpecSet& q = e->spec[set];
+        Dev& d = e->d;
+        d.xv = q.xv; d.rv = q.rv; d.uv3 = q.uv3; d.pv = q.pv; d.sv = q.sv; d.wv = q.wv; d.Dinv = q.Dinv; d.Hppinv = q.Hppinv;
+        d.xp = q.xp; d.rp = q.rp; d.rp2 = q.rp2; d.up = q.up; d.up2 = q.up2; d.pp = q.pp; d.sp = q.sp;
+        d.part_spmv = q.part_spmv; d.part_ru = q.part_ru; d.red = q.red; d.part_ec = q.part_ec;
+        d.part_apply = q.part_apply; d.part_rchi = q.part_rchi; d.part_reg = q.part_reg; d.scal = q.scal; d.flags = q.flags;
+        d.h_scal = q.h_scal; d.h_flags = q.h_flags;
+        d.pose[1 - e->cur] = q.pose; d.xl[1 - e->cur] = q.xl;
+        d.abort = q.abort; d.abort_id = abort_id;
+        e->h_scal = q.h_scal; e->h_flags = q.h_flags;
+        c->stream = c->spec_stream[set];
+    }
+    ~PcgSetView() { if (on) { e->d = saved; c->stream = main; e->h_scal = hs; e->h_flags = hf; } }
+    PcgSetView(const PcgSetView&) = delete;
+    PcgSetView& operator=(const PcgSetView&) = delete;
+};
+
 // (H + lam I) x = b by block-Jacobi PCG, resumable: pcg_begin, then pcg_advance until it reports
 // convergence; with stop_at_peek it also returns as soon as the 1e-4 milestone flag is up.
 constexpr double PEEK_RTOL = 1e-1;      // inner-solve accuracy at which a trial is first evaluated
@@ -704,14 +731,30 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
     const int n_spec = e->nd && e->nd->on && d.K == 1 && !d.sh_on && !d.ec_on && !c->opt.profile && !c->env("NRS_CHECK_EVAL") &&
                                e->nd->S().chain_from >= e->nd->S().plan.n_levels       // (the chained factorisation's workgroups wait for each other too: one such launch at a time)
                            ? std::min(e->n_spec, e->nd->S().n_alt) : 0;
-    struct Pending { int set; double lam; int seq; int solve_id; } pend[1 + SPEC_MAX];
+    // ... and BA windows on the two-kernel PCG (PcgSetView): a trial of the batch is its pcg_begin, its first PCG batch and its
+    // evaluation; the host then takes the trials in order through the usual peeks, further PCG batches going to the trial's own set.
+    // The first batch's size depends on the milestone the trials before it reached (first_batch): a trial whose size the host does
+    // not confirm when it gets to it is discarded with the rest of the batch and solved again on the engine's own arrays.
+    const int n_spec_pcg = e->spec_pcg && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && d.sk_n == 0 && !(e->kft && e->kft->on) &&
+                                   !c->opt.profile && !c->env("NRS_CHECK_EVAL")
+                               ? e->n_spec : 0;
+    struct Pending { int set; double lam; int seq; int solve_id; int first; int pit; } pend[1 + SPEC_MAX];
     int n_pend = 0, i_pend = 0;
     struct SpecDrain {                                             // an error return with trials in flight: nothing of theirs may outlive the engine the caller is about to drop
         nrs_ctx* c; int n; bool ok = false;
         ~SpecDrain() { if (!ok) for (int j = 0; j < n; ++j) if (c->spec_stream[j]) (void)hipStreamSynchronize(c->spec_stream[j]); }
-    } spec_drain{c, n_spec};
+    } spec_drain{c, std::max(n_spec, n_spec_pcg)};
+    // size of a PCG trial's first batch (trial q of an LM iteration): up to the first peek milestone the last trial needed, or the
+    // whole solve the last one needed where it was short
+    auto first_batch = [&](int q) -> int {
+        const bool expect_accept = q == 0 && e->first_trial_accepted && e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch;
+        if (!c->opt.exact_trials && !expect_accept) return e->pred_peek > 0 ? std::min(e->pred_peek, c->opt.pcg_batch) : std::max(1, c->opt.pcg_batch / 2);
+        if (e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch) return e->pred_iters + 1;
+        return 0;
+    };
     const int spec_first = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : 0;
     const bool spec_dbg = c->env("NRS_SPEC_DBG") != nullptr;       // (host clocks of a batch on stderr)
+    const int spec_first_pcg = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : n_spec_pcg;
     auto t_batch = std::chrono::steady_clock::now();
     auto join_batch = [&]() -> int {                              // the context's stream continues behind every shadow trial of the batch (they read the linearisation and the state)
         // trials of the batch nobody has asked for yet are not needed: their solves drain (the context's stream is idle here -- the
@@ -746,8 +789,62 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
             double temp = 0, scale = 0;
             bool ok = true;
             const bool direct = e->nd && e->nd->on;                  // nested-dissection Cholesky instead of PCG (nrs_engine_nd.hpp)
+            const double* hs = e->h_scal;                            // the mirrors this trial's results arrive in
+            const int* hf = e->h_flags;
+            int won = -1;                                          // the shadow set that holds this trial's state (-1: the engine's own)
+            int spec_seq = 0, spec_id = 0;
+            bool in_flight = false;                                // PCG window: this trial's first batch and evaluation went out with a batch
+            if (n_spec_pcg > 0) {
+                if (i_pend == n_pend) {                            // nothing in flight: inside a run of rejections, this trial and the ones after it
+                    n_pend = i_pend = 0;
+                    int nb = 1;
+                    if (qmax >= 1) nb = std::min(std::min(std::max(e->spec_run - qmax + 1, 2), 1 + n_spec_pcg), 10 - qmax);
+                    // the first trial of an iteration whose first trial was rejected last time goes out with followers (NRS_SPEC_FIRST=<n>
+                    // of them, default n_spec; 0: none) -- C2: the rejected run 852 -> 642 us of a step, 2.62 -> 2.48 ms per step
+                    if (qmax == 0 && spec_first_pcg > 0 && it < 32 && (e->spec_run_at >> it & 1u)) nb = std::min(1 + n_spec_pcg, 1 + spec_first_pcg);
+                    if (nb > 1) {
+                        NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
+                        double l = lam, n = ni;
+                        for (int j = 0; j < nb; ++j) {
+                            if (j > 0) { l *= n; n *= 2; if (!std::isfinite(l)) break; }
+                            Pending& p = pend[n_pend];
+                            // (followers of an iteration's first trial: the first batch the last run's later trials were confirmed with --
+                            // the milestone of a run's trials, not of the accepted trial before it that first_batch would go by)
+                            p.first = qmax == 0 && j > 0 && e->spec_follow_first > 0 ? e->spec_follow_first : first_batch(qmax + j);
+                            p.set = j - 1; p.lam = l; p.solve_id = ++e->spec_gen; p.pit = 0;
+                            PcgSetView v(c, e, p.set, p.solve_id);
+                            if (p.set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork, 0));
+                            NRS_TRY(pcg_begin(c, e, l, &p.pit));
+                            NRS_TRY(pcg_enqueue_batch(c, e, l, &p.pit, p.first));
+                            hipLaunchKernelGGL(k_apply, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, l, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
+                            NRS_TRY(evaluate<false>(c, e, trial, false));
+                            p.seq = c->seq;
+                            if (p.set >= 0) NRS_HIP(c, hipEventRecord(c->spec_join[p.set], c->stream));
+                            ++n_pend;
+                            if (spec_dbg) fprintf(stderr, "[spec] it %d trial %d: set %d first %d enqueued\n", it, qmax + j, p.set, p.first);
+                        }
+                        NRS_HIP(c, hipGetLastError());
+                    }
+                }
+                if (qmax > 0) e->spec_follow_first = first_batch(qmax);
+                if (i_pend < n_pend) {
+                    const Pending& pp = pend[i_pend++];
+                    if (pp.lam != lam) return c->fail(NRS_ERR_STATE, "speculative trial: damping %.17g does not match the sequence (%.17g)", pp.lam, lam);
+                    // (exact trials evaluate the converged solve only: where its batches end does not matter)
+                    if (!c->opt.exact_trials && pp.first != first_batch(qmax)) {
+                        if (spec_dbg) fprintf(stderr, "[spec] it %d trial %d: first batch %d, now %d: solved again\n", it, qmax, pp.first, first_batch(qmax));
+                        --i_pend;
+                        NRS_TRY(join_batch());
+                    } else {
+                        won = pp.set; pit = pp.pit; spec_seq = pp.seq; spec_id = pp.solve_id; in_flight = true;
+                    }
+                }
+            }
+            {
+            PcgSetView view(c, e, n_spec_pcg > 0 ? won : -1, spec_id);
+            if (won >= 0) { hs = e->h_scal; hf = e->h_flags; }
             // (a directly solved engine's flag words are cleared by the evaluation that published them: k_finalize, every trial and linearisation)
-            if (!direct) NRS_TRY(pcg_begin(c, e, lam, &pit));
+            if (!direct && !in_flight) NRS_TRY(pcg_begin(c, e, lam, &pit));
             auto eval_trial = [&]() -> int {
                 Timer t(c, &c->prof.update_ms, &c->prof.update_launches);
                 const bool one_pose = d.K == 1 && !d.sh_on;      // a2's engines: trial state and reprojection chi2 in one launch
@@ -774,9 +871,6 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
             // size is what the previous trial needed to reach the first milestone (the kernels record
             // it), so a trial that is going to be rejected costs a handful of iterations.
             int seen = 0;                                  // peek levels already evaluated
-            const double* hs = e->h_scal;                            // the mirrors this trial's results arrive in
-            const int* hf = e->h_flags;
-            int won = -1;                                          // the shadow set that holds this trial's state (-1: the engine's own)
             if (direct && n_spec > 0) {
                 if (i_pend == n_pend) {                            // nothing in flight: this trial and, inside a run of rejections, the ones that would follow it
                     n_pend = i_pend = 0;
@@ -813,14 +907,13 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
                 NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam));
                 NRS_TRY(eval_trial());
                 done = true;
+            } else if (in_flight) {                        // (enqueued with the batch: its publication is the one to wait for)
+                NRS_TRY(wait_published_at(c, hf, spec_seq, c->stream));
+                done = hf[0] != 0 || pit >= c->opt.pcg_max_iters;
             } else {
-                int first = 0;
                 // (after an iteration whose first trial was accepted, the next first trial usually is too:
                 // short solves then go out whole, without the intermediate look)
-                const bool expect_accept = qmax == 0 && e->first_trial_accepted && e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch;
-                if (peeking && !expect_accept) first = e->pred_peek > 0 ? std::min(e->pred_peek, c->opt.pcg_batch) : std::max(1, c->opt.pcg_batch / 2);
-                else if (e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch) first = e->pred_iters + 1;
-                NRS_TRY(pcg_enqueue_batch(c, e, lam, &pit, first));
+                NRS_TRY(pcg_enqueue_batch(c, e, lam, &pit, first_batch(qmax)));
                 NRS_TRY(eval_trial());
                 done = e->h_flags[0] != 0 || pit >= c->opt.pcg_max_iters;
             }
@@ -848,6 +941,7 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
                 NRS_TRY(pcg_advance(c, e, lam, peeking && seen < peek_levels ? seen + 1 : 0, &pit, &done));
                 NRS_TRY(eval_trial());
             }
+            }                                              // (the engine's own view again: the state may be swapped below)
             // (flags[2] == 2: a bounded wait of the direct solver ran out -- a synchronisation fault, not a matrix that is not positive
             // definite: the factor and the assembly areas hold partial data, so this is an error, never a rejected trial)
             if (hf[2] == 2) return c->fail(NRS_ERR_HIP, "direct solve: a wait for another workgroup's result timed out (LM iteration %d, trial %d, solve set %d)", it, qmax, won);
@@ -881,6 +975,10 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
                 }
                 NRS_TRY(join_batch());                 // (trials of the batch still in flight are discarded; the next linearisation waits for them)
                 if (n_spec > 0 && qmax > 0) c->spec_run = qmax;   // (a run of qmax rejections ended here)
+                if (n_spec_pcg > 0) {
+                    if (qmax > 0) e->spec_run = qmax;
+                    if (it < 32) e->spec_run_at = qmax > 0 ? e->spec_run_at | 1u << it : e->spec_run_at & ~(1u << it);
+                }
                 e->cur = trial;                        // discardTop: the trial state becomes current
             } else {
                 lam *= ni;

@@ -718,6 +718,8 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     {
         Dev tmpd = d;
         Engine te;
+        spec_pcg_sets(c, e, 0);                                    // shadow sets for speculative LM trials (carved with the arena)
+        te.n_spec = e->n_spec; te.spec_pcg = e->spec_pcg;
         carve(dry, tmpd, false, nnz_s, nnz_d, (size_t)n_slices, n_halo, &te);
     }
     if (dry.off > arena->cap) {
@@ -789,6 +791,7 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     }
     e->h_scal = c->pin_scal; e->h_flags = c->pin_flags;
     d.h_scal = c->pin_scal; d.h_flags = c->pin_flags;
+    if (e->n_spec > 0) NRS_TRY(spec_prepare(c, e));
     NRS_HIP(c, hipStreamSynchronize(st));                            // (host staging vectors die here; the overflow word is final)
     int h_fl2[2] = {0, 0};
     NRS_HIP(c, hipMemcpy(h_fl2, d_flag, sizeof(int) * 2, hipMemcpyDeviceToHost));

@@ -866,6 +866,7 @@ __global__ __launch_bounds__(BLK, OCC) void k_lin_plain(Dev P, const double* __r
 // =====================================================================================
 __global__ __launch_bounds__(BLK) void k_chi_edges(Dev P, const double* __restrict__ xl) {
     __shared__ double lds[4];
+    if (spec_aborted(P)) return;                                   // (a discarded speculative trial)
     // a fixed number of workgroups (<= 2048, so that the single-workgroup k_finalize has few partials to sum: on C4
     // 428k partials made it 760 us per trial), each over a contiguous range of edges in a fixed order
     const int tid = threadIdx.x, n = P.ec_nsp + P.ec_ndm;

@@ -49,6 +49,7 @@ __device__ inline bool inv6_spd(const double* Hu, double lam, double* Ainv /*36*
 
 __global__ __launch_bounds__(BLK) void k_trial_setup(Dev P, double lam) {
     __shared__ double lds_ru[4];
+    if (spec_aborted(P)) return;
     const int i = (P.sh_vb0 + blockIdx.x) * BLK + threadIdx.x;      // row (own range); poses below: every rank, all of them
     double ru[1] = {0};
     if (i < P.n_rows) {
@@ -234,7 +235,8 @@ __device__ __forceinline__ void spmv_f_body(const Dev& P, const double lam, cons
         if (lane == 0) lds[wave] = gsum;
     }
     const double gamma0 = P.scal[SC_GAMMA0];
-    const int done_flag = P.flags[0];                              // launches behind a converged solve are no-ops
+    // launches behind a converged solve are no-ops, and so are those of a discarded speculative trial
+    const int done_flag = P.flags[0] | (P.abort && *reinterpret_cast<const volatile int*>(P.abort) == P.abort_id);
     if (DF) {
         stage_rows_d(P, b, tid, P.uv3, lu, lgf, lgb);
         const int row0 = b * P.tile_rows, hb = P.halo_ptr[b], ns = P.halo_ns[b];
@@ -540,7 +542,7 @@ __global__ __launch_bounds__(BLK) void k_pcg_update(Dev P, double lam, int it, d
     const double* rp_in = (it & 1) ? P.rp2 : P.rp;   double* rp_out = (it & 1) ? P.rp : P.rp2;
     // Everything this launch reads is requested before the first dependent use (flag, scalars,
     // partials, the two rows of this thread): otherwise the launch is a chain of four round trips.
-    const int done_flag = P.flags[0];
+    const int done_flag = P.flags[0] | (P.abort && *reinterpret_cast<const volatile int*>(P.abort) == P.abort_id);   // (a discarded speculative trial: no-op)
     const double sc_gamma0 = P.scal[SC_GAMMA0];
     const double sc_slot0 = P.scal[(it & 1) ? SC_SLOT1 : SC_SLOT0], sc_slot1 = P.scal[((it & 1) ? SC_SLOT1 : SC_SLOT0) + 1];
     const int n_vec2 = (n_vecblk + 1) >> 1;
@@ -1297,6 +1299,7 @@ __global__ __launch_bounds__(BLK) void k_pcg_fused(Dev P, double lam, int it, do
 __global__ __launch_bounds__(BLK) void k_apply(Dev P, double lam, const Pose* __restrict__ pose_in,
                                                const double* __restrict__ xl_in, Pose* pose_out, double* xl_out) {
     __shared__ double lds[4];
+    if (spec_aborted(P)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = (P.sh_vb0 + blockIdx.x) * BLK + tid;             // row (own range); poses below: every rank, all of them
     double sc[1] = {0};

@@ -76,6 +76,18 @@ static int spec_sets(const nrs_ctx* c) {
     return 2;
 }
 
+// shadow sets of a BA window on the two-kernel PCG (speculative LM trials, nrs_engine_types.hpp): unsharded windows without skinned
+// observations (no keyframe-block factorisation either: that needs them), not profiling, up to NRS_SPEC_MAX_ROWS rows (default 2^18).
+// A set is 27 doubles a row (20 MB at C2's 92k rows).  Above the default the trials' launches fill the device on their own: C3 (455k
+// rows) takes 17.5 ms per step with sets against 17.0 without, so larger windows carve none.
+static void spec_pcg_sets(const nrs_ctx* c, Engine* e, int n_skin) {
+    const Dev& d = e->d;
+    const long max_rows = c->env("NRS_SPEC_MAX_ROWS") ? atol(c->env("NRS_SPEC_MAX_ROWS")) : (1L << 18);
+    const bool on = !e->nd && !d.fused && !d.coarse && !d.sh_on && n_skin == 0 && !c->opt.profile && (long)d.n_rows <= max_rows;
+    e->spec_pcg = on;
+    e->n_spec = on ? spec_sets(c) : 0;
+}
+
 static void carve(ArenaPlan& A, Dev& d, bool has_X0, size_t nnz_s, size_t nnz_d, size_t n_slices, size_t n_halo, Engine* e) {
     const size_t nr = (size_t)d.n_rows, K = (size_t)d.K;
     if (d.row_hi <= 0) { d.row_lo = 0; d.row_hi = d.n_rows; }     // (callers that never shard leave the range unset: every row)
@@ -163,6 +175,19 @@ static void carve(ArenaPlan& A, Dev& d, bool has_X0, size_t nnz_s, size_t nnz_d,
         q.part_apply = A.get<double>((size_t)d.n_vecblk); q.part_rchi = A.get<double>((size_t)d.n_groups); q.part_reg = A.get<double>(2 * (size_t)d.n_regblk);
         q.scal = A.get<double>(SC_N); q.flags = A.get<int>(8); q.abort = A.get<int>(1);
         q.sk_part = q.sk_chi = nullptr;
+        q.rv = q.uv3 = q.pv = q.sv = q.wv = q.Dinv = q.Hppinv = q.rp = q.rp2 = q.up = q.up2 = q.pp = q.sp = nullptr;
+        q.part_spmv = q.part_ru = q.red = q.part_ec = nullptr;
+        if (!e->spec_pcg) continue;
+        double** rows[] = {&q.rv, &q.uv3, &q.pv, &q.sv, &q.wv};
+        for (auto p : rows) *p = A.get_rows<double>(3);
+        q.Dinv = A.get_rows<double>(6);
+        q.Hppinv = A.get<double>(36 * K);
+        double** poses[] = {&q.rp, &q.rp2, &q.up, &q.up2, &q.pp, &q.sp};
+        for (auto p : poses) *p = A.get<double>(6 * K);
+        q.part_spmv = A.get<double>(NPART * (size_t)d.n_regblk);
+        q.part_ru = A.get<double>(d.ecd ? 2 * (size_t)d.n_vecblk : 1);
+        q.red = A.get<double>(4 + 6 * K);
+        q.part_ec = A.get<double>(d.ec_on ? std::max(1, d.ec_nblk) : 1);
     }
 }
 
@@ -952,7 +977,8 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     {
         Dev tmp = d;
         Engine te;
-        te.n_spec = e->n_spec;
+        if (!e->nd) spec_pcg_sets(c, e, s.n_skin);                 // (a2's engines chose theirs above)
+        te.n_spec = e->n_spec; te.spec_pcg = e->spec_pcg;
         carve(dry, tmp, s.X0 != nullptr, nnz_s, nnz_d, ss_ptr.size() - 1, halo_rows.size(), &te);
     }
     if (dry.off > arena->cap) {

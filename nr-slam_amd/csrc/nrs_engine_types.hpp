@@ -158,6 +158,9 @@ struct Dev {
     EcSpring* ec_sp; EcDamper* ec_dm; float* ec_w; double* part_ec;
     double* h_scal; int* h_flags;     // host-mapped mirrors, written by k_finalize / k_publish (no copy kernels)
     int* flags;                      // [0] pcg done, [1] pcg iterations, [2] nan flag
+    // speculative PCG trials (SpecSet): a trial on a shadow set is discarded once *abort == abort_id -- the set's queued PCG launches
+    // then return at once, as behind a converged solve (null: the engine's own trials, never discarded)
+    const int* abort; int abort_id;
     // shard window (multi-GPU): the layout is the whole problem on every rank, a rank
     // launches the row kernels over its own contiguous range of poses only.  Unsharded: the full ranges.
     int sh_on, sh_rank, sh_world;
@@ -214,14 +217,25 @@ enum { SC_CHI = 0, SC_MAXDIAG = 1, SC_SCALE = 2, SC_GAMMA0 = 3, SC_SLOT0 = 4, SC
 // vectors, trial state, partial sums, scalars, status words and their host mirrors (here) and the solver's factor storage, assembly
 // areas and unknowns (NdSolver).  The host then reads the results in order; the first accepted one becomes the state (pointer swap),
 // the rest are discarded.  Same trials, same arithmetic, same bits as one at a time.
+// BA windows on the two-kernel PCG (a3; Engine::spec_pcg) run their rejected trials the same way: a set then also holds everything a PCG
+// trial writes -- the row and pose vectors of the solve (with the pose ping-pong halves), the lambda-dependent block-Jacobi inverses
+// k_trial_setup writes, the operator's partials and sums -- while the linearisation (incidence factors, row records, D, H_pp, b) and the
+// current state stay shared and read-only.  The first PCG batch of a speculative trial is sized when it is enqueued; the host re-derives
+// that size when it reaches the trial and solves the trial again on the engine's own arrays if the two differ (engine_optimize).
+// Carved for unsharded windows without skinned observations up to 2^18 rows (spec_pcg_sets; DESIGN.md section 8: C2 2.78 -> 2.52 ms
+// per step, C3 slower with them).
 constexpr int SPEC_MAX = 3;          // shadow sets: up to 1 + SPEC_MAX trials in flight
 struct SpecSet {
     double *xv, *xp, *part_apply, *part_rchi, *part_reg, *scal;
     double *sk_part, *sk_chi;        // embedded mode (the context's skin buffer)
     int* flags;
-    int* abort;                      // id of the set's solve that is not needed any more (NdDev::abort)
+    int* abort;                      // id of the set's solve that is not needed any more (NdDev::abort, Dev::abort)
     Pose* pose; double* xl;          // the trial state (swapped with the engine's on acceptance)
     double* h_scal; int* h_flags;    // mapped host mirrors of its own (nrs_ctx::pin_spec_*)
+    // PCG trials (Engine::spec_pcg; null otherwise)
+    double *rv, *uv3, *pv, *sv, *wv, *Dinv, *Hppinv;
+    double *rp, *rp2, *up, *up2, *pp, *sp;
+    double *part_spmv, *part_ru, *red, *part_ec;
 };
 
 struct NdEngine;                     // nrs_engine_nd.hpp: the direct solver of a single-frame engine
@@ -233,7 +247,12 @@ struct Engine {
     bool kft_wanted = false;         // sharded (world > 1): the window-wide checks chose the factorisation; whether every rank holds its share is agreed by engine_kft_agree
     Arena* arena = nullptr;
     int cur = 0;
-    int n_spec = 0;                  // shadow sets carved for speculative trials (single-frame engines; 0: none)
+    int n_spec = 0;                  // shadow sets carved for speculative trials (single-frame engines, PCG BA windows; 0: none)
+    bool spec_pcg = false;           // the sets hold PCG trials (BA window on the two-kernel PCG)
+    int spec_run = 4;                // PCG windows: rejections of the last completed run of an LM iteration (sizes the next batch)
+    int spec_gen = 0;                // PCG windows: id of the last speculative trial enqueued (Dev::abort_id)
+    unsigned spec_run_at = 0;        // PCG windows: LM iterations (< 32) of the last optimize whose first trial was rejected (NRS_SPEC_FIRST)
+    int spec_follow_first = 0;       // PCG windows: first-batch size of the last trial after a rejection (NRS_SPEC_FIRST: its followers' guess)
     SpecSet spec[SPEC_MAX];
     int pred_iters = 0;              // inner iterations of the last fully solved LM trial (sizes later batches)
     int pack_rows = 0;               // rows whose incidence records this engine holds (sharded: the rank's keyframe range)
@@ -268,6 +287,12 @@ struct Engine {
 // =====================================================================================
 // device helpers
 // =====================================================================================
+// a discarded speculative PCG trial (Dev::abort): its set's words may change under a running launch, so a workgroup decides once
+// (P.abort is a kernel argument: the branch is uniform, and launches of the engine's own trials do not pay for the barrier)
+__device__ inline bool spec_aborted(const Dev& P) {
+    return P.abort && __syncthreads_or(*reinterpret_cast<const volatile int*>(P.abort) == P.abort_id);
+}
+
 __device__ inline int xcd_tile(int b, int nb) {
     const int nb8 = (nb + 7) >> 3;
     return (b & 7) * nb8 + (b >> 3);
