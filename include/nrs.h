@@ -266,6 +266,27 @@ int nrs_dba_solve_window(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, doub
                          int32_t iters, nrs_lm_trace* trace);
 int nrs_dba_window_edges(nrs_ctx* ctx, int32_t* n_spring, int32_t* sp_ij, float* sp_d0, int32_t* n_damper, int32_t* dm_idx, float* dm_w);
 
+/* The EMBEDDED window (N2b above) in one call: flattened keyframes as for nrs_dba_solve_window, obs_xyz / obs_uv per OBSERVATION
+ * (position in the concatenation kf_pt), the node flags and the ordered neighbour lists.  The lists nrs_dba_build_edges_embedded
+ * returns are built on the device (csrc/nrs_engine_embwin.hpp: index for index, the fp64 weights to the last bit), copied to the
+ * host and handed to the set-up nrs_dba_upload_embedded runs; then optimize(iters) and the download.  There is no size threshold.
+ * The host construction (nrs_dba_build_edges_embedded, the same lists) is taken with a communicator on the context, under
+ * NRS_HOST_PACK=1 and for a window whose neighbour lists are empty.  Arguments are checked as for nrs_dba_solve_window, and is_node
+ * must not be null; a NODE listed twice in one keyframe (which the reference cannot produce, frame.h:108-123, and on which a
+ * sequential and a parallel walk would differ) is NRS_ERR_INVALID as well.  After an error nothing is resident.
+ * On return the window is resident as after nrs_dba_upload_embedded (reset / optimize / download / download_skinned /
+ * nrs_debug_kft), and obs_xyz holds, cast to float: the optimised position of every node copy, the skinned position of every
+ * skinned observation; observations that reach no node copy are unchanged.
+ *   nrs_dba_window_edges_embedded  parity tap: the lists of the resident window (null arrays: the four counts only); *on_device = 1
+ *                                  when the device built them; NRS_ERR_STATE when the resident window was not made by this call */
+int nrs_dba_solve_window_embedded(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* poses_qt /* in/out */,
+                                  const int32_t* kf_rowptr, const int32_t* kf_pt, float* obs_xyz /* n_obs x 3, in/out */, const float* obs_uv,
+                                  int32_t n_points, const uint8_t* is_node, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
+                                  const float* nbr_d0, const int32_t* nbr_status, float scale, int32_t iters, nrs_lm_trace* trace);
+int nrs_dba_window_edges_embedded(nrs_ctx* ctx, int32_t* on_device, int32_t* n_lm, int32_t* lm_obs, int32_t* n_spring, int32_t* sp_ij,
+                                  float* sp_d0, int32_t* n_damper, int32_t* dm_idx, float* dm_w, int32_t* n_skin, int32_t* sk_obs,
+                                  int32_t* sk_node, double* sk_omega);
+
 /* Device-resident form of the same solve (used by bench.py so that the timed region starts with
  * the inputs already in HBM): upload once, then any number of {reset, optimize}. */
 int nrs_dba_upload(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, const double* poses_qt,

@@ -18,6 +18,7 @@ struct DevBuf {
 };
 
 struct Engine;       // nrs_engine.hip
+struct EmbWindow;    // nrs_engine.hpp: the lists of an embedded window built in one call
 struct KltState;     // nrs_klt.hip
 struct ShiState;     // nrs_shi.hip
 
@@ -84,6 +85,9 @@ struct nrs_ctx {
     nrs::DevBuf pack_ws, pack_ws2, pack_ws3, pack_ws4;   // device-side problem construction (nrs_engine_devpack.hpp): raw inputs + intermediates
     nrs::DevBuf dba_skin;            // ... and of the resident BA window (N2b)
     nrs::DevBuf dba_kft;             // embedded BA window: the keyframe-block factorisation (nrs_engine_kft.hpp)
+    nrs::EmbWindow* dba_embwin = nullptr;   // lists of the resident window when nrs_dba_solve_window_embedded made it (dropped by dba_free)
+    void* embwin_pin = nullptr;      // pinned host staging of the device-built lists (nrs_engine_embwin.hpp), kept for the context's lifetime
+    size_t embwin_pin_cap = 0;
     nrs::DevBuf nd_skin;             // embedded mode (nrs_engine_skin.hpp): the skinned observations of the tracking engine
     void* plan_worker = nullptr;     // nrs_engine_nd.hpp PlanWorker: the helper thread of the direct solver's symbolic phase (one for the context's lifetime)
     void* nd_cache = nullptr;        // direct solver of the tracking engines (nrs_engine_nd.hpp NdCache): the last few plans with their device arrays

@@ -1,6 +1,8 @@
 // a3: LocalDeformableBundleAdjustment C-ABI entry points (reference
 // modules/optimization/g2o_optimization.cc:880-1161) on top of the graph LM engine.
 #include <algorithm>
+#include <chrono>
+#include <memory>
 #include <vector>
 #include "nrs_engine.hpp"
 
@@ -9,6 +11,8 @@ namespace nrs {
 void dba_free(nrs_ctx* c) {
     if (c->dba) engine_destroy(c, c->dba);
     c->dba = nullptr;
+    delete c->dba_embwin;                                            // (the lists of a window nrs_dba_solve_window_embedded made)
+    c->dba_embwin = nullptr;
 }
 
 // constants of OPT:958-973 (float arithmetic, widened to double like g2o does)
@@ -204,9 +208,9 @@ extern "C" int nrs_dba_solve_embedded(nrs_ctx* c, const nrs_camera* cam, int32_t
 
 // LocalDeformableBundleAdjustment in ONE call, as mapping.cc:57 makes it: the edge construction of OPT:927-1137 on the device,
 // then the device-side problem construction and the solve.  Windows that do not qualify take nrs_dba_build_edges + nrs_dba_solve.
-static int window_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
-                         const float* lm_xyz, const float* lm_uv, int32_t n_points, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
-                         const float* nbr_d0, const int32_t* nbr_status, float scale, std::vector<int32_t>& lm_kf) {
+static int window_validate(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                           const float* lm_xyz, const float* lm_uv, int32_t n_points, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
+                           const float* nbr_d0, const int32_t* nbr_status, std::vector<int32_t>& lm_kf) {
     if (!cam || n_kf <= 0 || !poses_qt || !kf_rowptr || !kf_pt || !lm_xyz || !lm_uv || n_points <= 0 || !nbr_rowptr || !nbr_col || !nbr_w || !nbr_d0 || !nbr_status)
         return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window: bad argument");
     if (cam->model != NRS_CAM_PINHOLE && cam->model != NRS_CAM_KB8) return c->fail(NRS_ERR_INVALID, "unknown camera model %d", cam->model);
@@ -219,6 +223,14 @@ static int window_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const 
     for (int32_t i = 0; i < nbr_rowptr[n_points]; ++i) if (nbr_col[i] < 0 || nbr_col[i] >= n_points) return c->fail(NRS_ERR_INVALID, "neighbour index out of range");
     lm_kf.resize(n_lm);
     for (int k = 0; k < n_kf; ++k) for (int32_t i = kf_rowptr[k]; i < kf_rowptr[k + 1]; ++i) lm_kf[i] = k;
+    return NRS_OK;
+}
+
+static int window_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                         const float* lm_xyz, const float* lm_uv, int32_t n_points, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
+                         const float* nbr_d0, const int32_t* nbr_status, float scale, std::vector<int32_t>& lm_kf) {
+    NRS_TRY(window_validate(c, cam, n_kf, poses_qt, kf_rowptr, kf_pt, lm_xyz, lm_uv, n_points, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, lm_kf));
+    const int32_t n_lm = kf_rowptr[n_kf];
     dba_free(c);
     EngineSpec s;
     s.K = n_kf; s.M = n_lm;
@@ -286,6 +298,111 @@ extern "C" int nrs_dba_window_edges(nrs_ctx* c, int32_t* n_spring, int32_t* sp_i
     if (n_damper) *n_damper = nd;
     if (!sp_ij && !sp_d0 && !dm_idx && !dm_w) return NRS_OK;
     return engine_edges_to_host(c, c->dba, sp_ij, sp_d0, dm_idx, dm_w);
+}
+
+// ---- the EMBEDDED window in one call (include/nrs.h): the lists of nrs_dba_build_edges_embedded built on the device
+// (csrc/nrs_engine_embwin.hpp), handed to the set-up nrs_dba_upload_embedded runs, then optimize(iters) and the download.  A communicator
+// on the context, NRS_HOST_PACK=1 or empty neighbour lists take nrs_dba_build_edges_embedded instead: the same lists.
+static int embwin_build_host(nrs_ctx* c, int32_t n_kf, const int32_t* kf_rowptr, const int32_t* kf_pt, const int32_t* obs_kf, const float* obs_xyz, const float* obs_uv,
+                             int32_t n_points, const uint8_t* is_node, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w, const float* nbr_d0,
+                             const int32_t* nbr_status, EmbWindow* w) {
+    {                                                                // a node listed twice in one keyframe: refused here as on the device
+        std::vector<int32_t> seen(n_points, -1);
+        for (int32_t i = 0; i < kf_rowptr[n_kf]; ++i) {
+            if (!is_node[kf_pt[i]]) continue;
+            if (seen[kf_pt[i]] == obs_kf[i]) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_embedded: a map point is listed twice in one keyframe");
+            seen[kf_pt[i]] = obs_kf[i];
+        }
+    }
+    int32_t nl = 0, ns = 0, nd = 0, nk = 0;
+    int rc = nrs_dba_build_edges_embedded(n_kf, kf_rowptr, kf_pt, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, &nl, nullptr, &ns, nullptr, nullptr,
+                                          &nd, nullptr, nullptr, &nk, nullptr, nullptr, nullptr);
+    if (rc != NRS_OK) return c->fail(rc, "nrs_dba_build_edges_embedded failed");
+    w->on_device = 0; w->n_obs = kf_rowptr[n_kf]; w->n_lm = nl; w->n_sp = ns; w->n_dm = nd; w->n_skin = nk;
+    w->host.assign(embwin_bytes(nl, ns, nd, nk), 0);
+    embwin_bind(w, w->host.data());
+    rc = nrs_dba_build_edges_embedded(n_kf, kf_rowptr, kf_pt, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, &nl, w->lm_obs, &ns, w->sp_ij, w->sp_d0,
+                                      &nd, w->dm_idx, w->dm_w, &nk, w->sk_obs, w->sk_node, w->sk_omega);
+    if (rc != NRS_OK) return c->fail(rc, "nrs_dba_build_edges_embedded failed");
+    for (int32_t i = 0; i < nl; ++i) {
+        const size_t o = (size_t)w->lm_obs[i];
+        for (int a = 0; a < 3; ++a) w->lm_xyz[3 * (size_t)i + a] = obs_xyz[3 * o + a];
+        for (int a = 0; a < 2; ++a) w->lm_uv[2 * (size_t)i + a] = obs_uv[2 * o + a];
+        w->lm_kf[i] = obs_kf[o];
+    }
+    for (int32_t i = 0; i < nk; ++i) {
+        const size_t o = (size_t)w->sk_obs[i];
+        for (int a = 0; a < 3; ++a) w->sk_xyz[3 * (size_t)i + a] = obs_xyz[3 * o + a];
+        for (int a = 0; a < 2; ++a) w->sk_uv[2 * (size_t)i + a] = obs_uv[2 * o + a];
+        w->sk_kf[i] = obs_kf[o];
+    }
+    return NRS_OK;
+}
+
+extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                                             float* obs_xyz, const float* obs_uv, int32_t n_points, const uint8_t* is_node, const int32_t* nbr_rowptr,
+                                             const int32_t* nbr_col, const float* nbr_w, const float* nbr_d0, const int32_t* nbr_status, float scale, int32_t iters,
+                                             nrs_lm_trace* trace) {
+    if (!c) return NRS_ERR_INVALID;
+    dba_free(c);                                                     // whatever happens below, no earlier window stays resident
+    std::vector<int32_t> obs_kf;
+    NRS_TRY(window_validate(c, cam, n_kf, poses_qt, kf_rowptr, kf_pt, obs_xyz, obs_uv, n_points, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, obs_kf));
+    if (!is_node) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_embedded: bad argument");
+    const bool tm = c->env("NRS_TIMING") != nullptr;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto mark = [&](const char* what) {
+        if (!tm) return;
+        auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[nrs] embedded window %-14s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    };
+    std::unique_ptr<EmbWindow> w(new EmbWindow);
+    if (!c->comm && !c->env("NRS_HOST_PACK") && nbr_rowptr[n_points] > 0) {
+        bool duplicate = false;
+        NRS_TRY(engine_build_embedded_window_device(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0,
+                                                    nbr_status, w.get(), &duplicate));
+        if (duplicate) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_embedded: a map point is listed twice in one keyframe");
+    } else
+        NRS_TRY(embwin_build_host(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, w.get()));
+    mark("construction");
+    NRS_TRY(nrs_dba_upload_embedded(c, cam, n_kf, poses_qt, w->n_lm, w->lm_xyz, w->lm_kf, w->lm_uv, w->n_sp, w->sp_ij, w->sp_d0, w->n_dm, w->dm_idx, w->dm_w, w->n_skin,
+                                    w->sk_kf, w->sk_uv, w->sk_xyz, w->sk_node, w->sk_omega, scale));
+    c->dba_embwin = w.release();
+    const EmbWindow& r = *c->dba_embwin;
+    if (tm) (void)hipStreamSynchronize(c->stream);
+    mark("set-up");
+    NRS_TRY(nrs_dba_optimize(c, iters, trace));
+    std::vector<double> xyz((size_t)r.n_lm * 3), sk((size_t)r.n_skin * 3);
+    NRS_TRY(download(c, n_kf, poses_qt, xyz.data()));
+    if (r.n_skin > 0) NRS_TRY(engine_skin_positions(c, c->dba, sk.data()));
+    for (int32_t i = 0; i < r.n_lm; ++i)                             // OPT:1158 cast<float>, as nrs_dba_solve_embedded
+        for (int a = 0; a < 3; ++a) obs_xyz[3 * (size_t)r.lm_obs[i] + a] = (float)xyz[3 * (size_t)i + a];
+    for (int32_t i = 0; i < r.n_skin; ++i)
+        for (int a = 0; a < 3; ++a) obs_xyz[3 * (size_t)r.sk_obs[i] + a] = (float)sk[3 * (size_t)i + a];
+    mark("solve + download");
+    return NRS_OK;
+}
+
+// parity tap of the device list builder: the lists of the resident window nrs_dba_solve_window_embedded made
+extern "C" int nrs_dba_window_edges_embedded(nrs_ctx* c, int32_t* on_device, int32_t* n_lm, int32_t* lm_obs, int32_t* n_spring, int32_t* sp_ij, float* sp_d0,
+                                             int32_t* n_damper, int32_t* dm_idx, float* dm_w, int32_t* n_skin, int32_t* sk_obs, int32_t* sk_node, double* sk_omega) {
+    if (!c) return NRS_ERR_INVALID;
+    if (!c->dba || !c->dba_embwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_embedded");
+    const EmbWindow& r = *c->dba_embwin;
+    if (on_device) *on_device = r.on_device;
+    if (n_lm) *n_lm = r.n_lm;
+    if (n_spring) *n_spring = r.n_sp;
+    if (n_damper) *n_damper = r.n_dm;
+    if (n_skin) *n_skin = r.n_skin;
+    if (lm_obs) memcpy(lm_obs, r.lm_obs, sizeof(int32_t) * (size_t)r.n_lm);
+    if (sp_ij) memcpy(sp_ij, r.sp_ij, sizeof(int32_t) * 2 * (size_t)r.n_sp);
+    if (sp_d0) memcpy(sp_d0, r.sp_d0, sizeof(float) * (size_t)r.n_sp);
+    if (dm_idx) memcpy(dm_idx, r.dm_idx, sizeof(int32_t) * 4 * (size_t)r.n_dm);
+    if (dm_w) memcpy(dm_w, r.dm_w, sizeof(float) * (size_t)r.n_dm);
+    if (sk_obs) memcpy(sk_obs, r.sk_obs, sizeof(int32_t) * (size_t)r.n_skin);
+    if (sk_node) memcpy(sk_node, r.sk_node, sizeof(int32_t) * 11 * (size_t)r.n_skin);
+    if (sk_omega) memcpy(sk_omega, r.sk_omega, sizeof(double) * 11 * (size_t)r.n_skin);
+    return NRS_OK;
 }
 
 extern "C" int nrs_dba_residuals(nrs_ctx* c, double* r_reproj, double* r_spring, double* r_damper) {

@@ -61,6 +61,7 @@
 #include "nrs_engine_setup.hpp"
 #include "nrs_engine_kft_setup.hpp"
 #include "nrs_engine_devpack.hpp"
+#include "nrs_engine_embwin.hpp"
 
 namespace nrs {
 

@@ -79,6 +79,21 @@ int engine_skin_stats(const Engine* e, int64_t out[3]);            // skinned ob
 // OPT:927-1137's edge construction on the device (index for index what nrs_dba_build_edges returns); arrays live in ctx scratch
 int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
                               const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out);
+// embedded window in one call (nrs_engine_embwin.hpp): node copies, springs / dampers over node-copy indices, skinned observations and
+// the per-observation data gathered for both; the arrays sit in ONE blob laid out by embwin_layout (host: `host`, device-built: the
+// context's pinned staging)
+struct EmbWindow {
+    int on_device = 0, n_obs = 0, n_lm = 0, n_sp = 0, n_dm = 0, n_skin = 0;
+    int *lm_obs = nullptr, *sp_ij = nullptr, *dm_idx = nullptr, *sk_obs = nullptr, *sk_node = nullptr, *lm_kf = nullptr, *sk_kf = nullptr;
+    float *sp_d0 = nullptr, *dm_w = nullptr, *lm_xyz = nullptr, *lm_uv = nullptr, *sk_xyz = nullptr, *sk_uv = nullptr;
+    double* sk_omega = nullptr;
+    std::vector<char> host;
+};
+size_t embwin_bytes(int n_lm, int n_sp, int n_dm, int n_skin);
+void embwin_bind(EmbWindow* w, char* base);                       // the pointers of w for its counts, into a blob of embwin_bytes
+int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
+                                        int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
+                                        const int* nbr_status, EmbWindow* out, bool* duplicate);
 bool engine_device_pack_ok(nrs_ctx* c, const EngineSpec& s);      // would engine_create build this window on the device?
 int engine_edges_to_host(nrs_ctx* c, Engine* e, int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w);   // parity tap of the device edge builder    // checksums of the packed arrays (host- or device-built)       // solver order, caller vertex order
 // parity tap: (H + lam I) x = b for explicitly given blocks (one pose, M landmark rows, no regularisers) through

@@ -1,0 +1,273 @@
+// Device-side list construction of the EMBEDDED BA window (part of nrs_engine.hip; include/nrs.h nrs_dba_solve_window_embedded).
+//
+// The host form is nrs_dba_build_edges_embedded (csrc/nrs_host_build.cpp), whose output this reproduces index for index and bit
+// for bit, the fp64 skinning weights included.  It is the per-observation walk of k_win_edges (nrs_engine_devpack.hpp) with two
+// additions: the walks run between NODE copies only, and every observed point that is not a node is bound to the <= 11 node
+// copies its own walk accepts.
+//   numbering   a node copy is an observation whose map point has is_node set; node copies are numbered keyframe by keyframe in
+//               observation order: an exclusive scan of the flag over the concatenation kf_pt.  The n_kf x n_points table `cur`
+//               holds the node-copy index of (keyframe, map point) or -1; map points that are not nodes stay -1, so every walk
+//               passes over them exactly as over a point the keyframe does not observe
+//   walks       one thread per observation, count pass / exclusive scans / emit pass (as engine_build_edges_device).  A node copy
+//               emits its springs and its dampers with the next keyframe (stop rule and duplicate rule of k_win_edges: the pair is
+//               a duplicate iff the other node copy comes earlier in the keyframe and its own walk reaches this point; a duplicate
+//               still counts as a regulariser).  Any other observation accepts at most 11 node copies of its keyframe, widens their
+//               float weights to double, sums them in walk order and divides each by the sum; one that reaches no node copy emits
+//               nothing.  Skinned observations keep observation order (their slot: a scan of the per-observation count)
+//   gathers     lm_xyz / lm_uv / lm_kf of the node copies and sk_xyz / sk_uv / sk_kf of the skinned observations from the
+//               caller's per-observation arrays
+// DUPLICATE MAP POINTS.  The host walk and a parallel walk differ when a map point is listed twice in one keyframe: the host's table
+// changes while it walks the keyframe, this one is complete before any walk starts.  The reference cannot produce the case
+// (frame.h:108-123 maps id to index one to one), so it is detected here and reported (*duplicate = true; the entry point returns
+// NRS_ERR_INVALID before any solver launch): a node copy whose own index is not the one left in `cur` is such a duplicate.
+// The lists end up in pinned host memory of the context (one copy back), laid out by embwin_layout, and are handed to the set-up
+// nrs_dba_upload_embedded runs (nrs_engine_setup.hpp reads host arrays).  Plain C++ and vector stores only; the only atomic is the
+// atomicMax on `cur`, as in k_win_cur.
+#pragma once
+
+namespace nrs {
+
+// byte offsets of the 14 arrays of an EmbWindow in one blob (device scratch, pinned mirror and host storage share the layout)
+enum { EW_SK_OMEGA, EW_LM_OBS, EW_SP_IJ, EW_SP_D0, EW_DM_IDX, EW_DM_W, EW_SK_OBS, EW_SK_NODE, EW_LM_XYZ, EW_LM_UV, EW_LM_KF, EW_SK_XYZ, EW_SK_UV, EW_SK_KF, EW_N };
+static size_t embwin_layout(int n_lm, int n_sp, int n_dm, int n_skin, size_t off[EW_N]) {
+    const size_t bytes[EW_N] = {88 * (size_t)n_skin, 4 * (size_t)n_lm, 8 * (size_t)n_sp, 4 * (size_t)n_sp, 16 * (size_t)n_dm, 4 * (size_t)n_dm, 4 * (size_t)n_skin,
+                                44 * (size_t)n_skin, 12 * (size_t)n_lm, 8 * (size_t)n_lm, 4 * (size_t)n_lm, 12 * (size_t)n_skin, 8 * (size_t)n_skin, 4 * (size_t)n_skin};
+    size_t o = 0;
+    for (int i = 0; i < EW_N; ++i) { off[i] = o; o += ((bytes[i] + 255) / 256) * 256 + 256; }
+    return o;
+}
+size_t embwin_bytes(int n_lm, int n_sp, int n_dm, int n_skin) {
+    size_t off[EW_N];
+    return embwin_layout(n_lm, n_sp, n_dm, n_skin, off);
+}
+void embwin_bind(EmbWindow* w, char* base) {
+    size_t off[EW_N];
+    (void)embwin_layout(w->n_lm, w->n_sp, w->n_dm, w->n_skin, off);
+    w->sk_omega = reinterpret_cast<double*>(base + off[EW_SK_OMEGA]);
+    w->lm_obs = reinterpret_cast<int*>(base + off[EW_LM_OBS]); w->sp_ij = reinterpret_cast<int*>(base + off[EW_SP_IJ]);
+    w->sp_d0 = reinterpret_cast<float*>(base + off[EW_SP_D0]); w->dm_idx = reinterpret_cast<int*>(base + off[EW_DM_IDX]);
+    w->dm_w = reinterpret_cast<float*>(base + off[EW_DM_W]); w->sk_obs = reinterpret_cast<int*>(base + off[EW_SK_OBS]);
+    w->sk_node = reinterpret_cast<int*>(base + off[EW_SK_NODE]); w->lm_xyz = reinterpret_cast<float*>(base + off[EW_LM_XYZ]);
+    w->lm_uv = reinterpret_cast<float*>(base + off[EW_LM_UV]); w->lm_kf = reinterpret_cast<int*>(base + off[EW_LM_KF]);
+    w->sk_xyz = reinterpret_cast<float*>(base + off[EW_SK_XYZ]); w->sk_uv = reinterpret_cast<float*>(base + off[EW_SK_UV]);
+    w->sk_kf = reinterpret_cast<int*>(base + off[EW_SK_KF]);
+}
+
+__global__ void k_ew_flag(int n_obs, const int* __restrict__ kf_pt, const uint8_t* __restrict__ is_node, int* flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_obs) flag[i] = is_node[kf_pt[i]] ? 1 : 0;
+}
+// cur[(k, p)] <- node-copy index (flag scanned: lm_of), as k_win_cur
+__global__ void k_ew_cur(int n_obs, const int* __restrict__ obs_k, const int* __restrict__ kf_pt, const int* __restrict__ flag, const int* __restrict__ lm_of,
+                         int n_points, int* cur) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_obs && flag[i]) atomicMax(&cur[(size_t)obs_k[i] * n_points + kf_pt[i]], lm_of[i]);
+}
+// a node copy that is not the one `cur` kept: its map point is listed twice in the keyframe.  tot[0..4) <- the four counts.
+__global__ void k_ew_check(int n_obs, const int* __restrict__ obs_k, const int* __restrict__ kf_pt, const int* __restrict__ flag, const int* __restrict__ lm_of,
+                           int n_points, const int* __restrict__ cur, int* tot) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_obs && flag[i] && cur[(size_t)obs_k[i] * n_points + kf_pt[i]] != lm_of[i]) tot[4] = 1;
+}
+__global__ void k_ew_totals(int n_obs, const int* __restrict__ lm_of, const int* __restrict__ off_s, const int* __restrict__ off_d, const int* __restrict__ off_k, int* tot) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { tot[0] = lm_of[n_obs]; tot[1] = off_s[n_obs]; tot[2] = off_d[n_obs]; tot[3] = off_k[n_obs]; }
+}
+
+// One thread per observation i = (keyframe k, map point p); W.lm_k / W.kf_pt are per OBSERVATION here, W.cur the node-copy table.
+// EMIT = false: counts per observation; true: writes at the scanned offsets.
+template <bool EMIT>
+__global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, const int* __restrict__ lm_of, int* cnt_s, int* cnt_d, int* cnt_k,
+                          const int* __restrict__ off_s, const int* __restrict__ off_d, const int* __restrict__ off_k, int* lm_obs, int* sp_ij, float* sp_d0,
+                          int* dm_idx, float* dm_w, int* sk_obs, int* sk_node, double* sk_omega) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_obs) return;
+    const int k = W.lm_k[i], p = W.kf_pt[i];
+    const int* cur = W.cur + (size_t)k * W.n_points;
+    const int lo = W.nbr_rowptr[p], hi = W.nbr_rowptr[p + 1];
+    if (!flag[i]) {                                                  // a skinned observation: its walk accepts node copies
+        int n_reg = 0;
+        double tot = 0.0;
+        for (int e = lo; e < hi; ++e) {
+            if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
+            if (cur[W.nbr_col[e]] < 0) continue;
+            tot += (double)W.nbr_w[e];                               // (walk order, from 0.0: the host's sum)
+            ++n_reg;
+        }
+        if (!EMIT) { cnt_s[i] = 0; cnt_d[i] = 0; cnt_k[i] = n_reg > 0 ? 1 : 0; return; }
+        if (n_reg == 0) return;                                      // (no node copy within reach: the observation constrains nothing)
+        const size_t q = (size_t)off_k[i];
+        sk_obs[q] = i;
+        int j = 0;
+        for (int e = lo; e < hi && j < n_reg; ++e) {                 // the same walk again: its first n_reg accepted entries
+            const int o = W.nbr_col[e];
+            if (cur[o] < 0) continue;
+            sk_node[11 * q + j] = cur[o];
+            sk_omega[11 * q + j] = (double)W.nbr_w[e] / tot;
+            ++j;
+        }
+        for (; j < 11; ++j) { sk_node[11 * q + j] = -1; sk_omega[11 * q + j] = 0.0; }
+        return;
+    }
+    const int l = lm_of[i];
+    int ns = 0, nd = 0, n_reg = 0;
+    if (EMIT) lm_obs[l] = i;
+    for (int e = lo; e < hi; ++e) {                                  // springs between node copies (OPT:1033-1074)
+        if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
+        const int o = W.nbr_col[e];
+        if (cur[o] < 0) continue;
+        ++n_reg;
+        if (cur[o] < l && win_walk_reaches(W, k, o, p, false)) continue;        // inserted by o's walk already
+        if (EMIT) { const size_t q = (size_t)(off_s[i] + ns); sp_ij[2 * q] = l; sp_ij[2 * q + 1] = cur[o]; sp_d0[q] = W.nbr_d0[e]; }
+        ++ns;
+    }
+    if (k + 1 < W.n_kf) {                                            // dampers with the next keyframe (OPT:1076-1136)
+        const int* nxt = W.cur + (size_t)(k + 1) * W.n_points;
+        if (nxt[p] >= 0) {
+            n_reg = 0;
+            for (int e = lo; e < hi; ++e) {
+                if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
+                const int o = W.nbr_col[e];
+                if (cur[o] < 0 || nxt[o] < 0) continue;
+                ++n_reg;
+                if (cur[o] < l && win_walk_reaches(W, k, o, p, true)) continue;
+                if (EMIT) {
+                    const size_t q = (size_t)(off_d[i] + nd);
+                    dm_idx[4 * q] = l; dm_idx[4 * q + 1] = cur[o]; dm_idx[4 * q + 2] = nxt[p]; dm_idx[4 * q + 3] = nxt[o];
+                    dm_w[q] = W.nbr_w[e];
+                }
+                ++nd;
+            }
+        }
+    }
+    if (!EMIT) { cnt_s[i] = ns; cnt_d[i] = nd; cnt_k[i] = 0; }
+}
+
+// per-observation data of the node copies (n_a, obs_a) and of the skinned observations (n_b, obs_b)
+__global__ void k_ew_gather(int n_a, const int* __restrict__ obs_a, int n_b, const int* __restrict__ obs_b, const float* __restrict__ obs_xyz,
+                            const float* __restrict__ obs_uv, const int* __restrict__ obs_k, float* a_xyz, float* a_uv, int* a_kf, float* b_xyz, float* b_uv, int* b_kf) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_a) {
+        const size_t o = (size_t)obs_a[i];
+        for (int a = 0; a < 3; ++a) a_xyz[3 * (size_t)i + a] = obs_xyz[3 * o + a];
+        for (int a = 0; a < 2; ++a) a_uv[2 * (size_t)i + a] = obs_uv[2 * o + a];
+        a_kf[i] = obs_k[o];
+    }
+    if (i < n_b) {
+        const size_t o = (size_t)obs_b[i];
+        for (int a = 0; a < 3; ++a) b_xyz[3 * (size_t)i + a] = obs_xyz[3 * o + a];
+        for (int a = 0; a < 2; ++a) b_uv[2 * (size_t)i + a] = obs_uv[2 * o + a];
+        b_kf[i] = obs_k[o];
+    }
+}
+
+// Builds the lists of an embedded window on the device and copies them to the context's pinned staging (out's pointers: valid until
+// the next call).  The arguments are validated by the caller (indices in range, nnz > 0).
+int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
+                                        int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
+                                        const int* nbr_status, EmbWindow* out, bool* duplicate) {
+    *duplicate = false;
+    const int n_obs = kf_rowptr[n_kf], nnz = nbr_rowptr[n_points];
+    hipStream_t st = c->stream;
+    NRS_HIP(c, hipSetDevice(c->device));
+    const bool tm = c->env("NRS_TIMING") != nullptr;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto mark = [&](const char* what) {
+        if (!tm) return;
+        (void)hipStreamSynchronize(st);
+        auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[nrs] embedded lists %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    };
+    size_t tb = 0;
+    (void)rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st);
+    int *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_flag, *d_lm, *d_cs, *d_cd, *d_ck, *d_os, *d_od, *d_ok, *d_tot;
+    float *d_w, *d_d0, *d_xyz, *d_uv;
+    uint8_t* d_node;
+    void* tmp;
+    auto layout = [&](DpScratch& W) {
+        d_pt = W.get<int>(n_obs); d_k = W.get<int>(n_obs); d_node = W.get<uint8_t>(n_points);
+        d_nrp = W.get<int>(n_points + 1); d_col = W.get<int>(nnz); d_st = W.get<int>(nnz); d_w = W.get<float>(nnz); d_d0 = W.get<float>(nnz);
+        d_xyz = W.get<float>(3 * (size_t)n_obs); d_uv = W.get<float>(2 * (size_t)n_obs);
+        d_cur = W.get<int>((size_t)n_kf * n_points);
+        d_flag = W.get<int>((size_t)n_obs + 1); d_lm = W.get<int>((size_t)n_obs + 1);
+        d_cs = W.get<int>((size_t)n_obs + 1); d_cd = W.get<int>((size_t)n_obs + 1); d_ck = W.get<int>((size_t)n_obs + 1);
+        d_os = W.get<int>((size_t)n_obs + 1); d_od = W.get<int>((size_t)n_obs + 1); d_ok = W.get<int>((size_t)n_obs + 1);
+        d_tot = W.get<int>(8);
+        tmp = W.get<char>(tb + 256);
+    };
+    DpScratch dry{nullptr, 0, 0};
+    layout(dry);
+    NRS_TRY(c->ensure(c->pack_ws3, dry.off + 4096));
+    DpScratch W{c->pack_ws3.as<char>(), 0, c->pack_ws3.cap};
+    layout(W);
+    NRS_HIP(c, hipMemcpyAsync(d_pt, kf_pt, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_k, obs_kf, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_node, is_node, (size_t)n_points, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_nrp, nbr_rowptr, sizeof(int) * ((size_t)n_points + 1), hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_col, nbr_col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_st, nbr_status, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_w, nbr_w, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_d0, nbr_d0, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_xyz, obs_xyz, sizeof(float) * 3 * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_uv, obs_uv, sizeof(float) * 2 * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemsetAsync(d_cur, 0xFF, sizeof(int) * (size_t)n_kf * n_points, st));
+    NRS_HIP(c, hipMemsetAsync(d_flag + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(d_cs + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(d_cd + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(d_ck + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(d_tot, 0, sizeof(int) * 8, st));
+    mark("uploads");
+    const dim3 g((unsigned)((n_obs + 255) / 256)), b(256);
+    size_t t2;
+    // ---- node-copy numbering and the table
+    hipLaunchKernelGGL(k_ew_flag, g, b, 0, st, n_obs, d_pt, d_node, d_flag);
+    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_flag, d_lm, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(k_ew_cur, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur);
+    hipLaunchKernelGGL(k_ew_check, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur, d_tot);
+    // ---- count pass, scans
+    WinDev wd{n_kf, n_points, nullptr, d_pt, d_k, d_nrp, d_col, d_st, d_w, d_d0, d_cur};
+    hipLaunchKernelGGL((k_ew_walk<false>), g, b, 0, st, wd, n_obs, d_flag, d_lm, d_cs, d_cd, d_ck, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                       (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr);
+    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cd, d_od, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_ck, d_ok, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(k_ew_totals, dim3(1), dim3(64), 0, st, n_obs, d_lm, d_os, d_od, d_ok, d_tot);
+    NRS_HIP(c, hipGetLastError());
+    int tot[5] = {0, 0, 0, 0, 0};
+    NRS_HIP(c, hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    NRS_HIP(c, hipStreamSynchronize(st));
+    mark("count + scans");
+    if (tot[4]) { *duplicate = true; return NRS_OK; }
+    out->n_obs = n_obs; out->n_lm = tot[0]; out->n_sp = tot[1]; out->n_dm = tot[2]; out->n_skin = tot[3];
+    // ---- emit pass and gathers into one blob, one copy back
+    size_t off[EW_N];
+    const size_t bytes = embwin_layout(tot[0], tot[1], tot[2], tot[3], off);
+    NRS_TRY(c->ensure(c->pack_ws4, bytes + 4096));
+    if (bytes > c->embwin_pin_cap) {
+        if (c->embwin_pin) (void)hipHostFree(c->embwin_pin);
+        c->embwin_pin = nullptr; c->embwin_pin_cap = 0;
+        const size_t want = bytes + bytes / 4;
+        hipError_t he = hipHostMalloc(&c->embwin_pin, want, hipHostMallocDefault);
+        if (he != hipSuccess) return c->fail(NRS_ERR_ALLOC, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(he));
+        c->embwin_pin_cap = want;
+    }
+    EmbWindow dv = *out;
+    embwin_bind(&dv, c->pack_ws4.as<char>());
+    hipLaunchKernelGGL((k_ew_walk<true>), g, b, 0, st, wd, n_obs, d_flag, d_lm, (int*)nullptr, (int*)nullptr, (int*)nullptr, d_os, d_od, d_ok, dv.lm_obs, dv.sp_ij, dv.sp_d0,
+                       dv.dm_idx, dv.dm_w, dv.sk_obs, dv.sk_node, dv.sk_omega);
+    const int n_g = std::max(dv.n_lm, dv.n_skin);
+    if (n_g > 0)
+        hipLaunchKernelGGL(k_ew_gather, dim3((unsigned)((n_g + 255) / 256)), b, 0, st, dv.n_lm, dv.lm_obs, dv.n_skin, dv.sk_obs, d_xyz, d_uv, d_k, dv.lm_xyz, dv.lm_uv, dv.lm_kf,
+                           dv.sk_xyz, dv.sk_uv, dv.sk_kf);
+    NRS_HIP(c, hipGetLastError());
+    mark("emit + gathers");
+    NRS_HIP(c, hipMemcpyAsync(c->embwin_pin, c->pack_ws4.as<char>(), bytes, hipMemcpyDeviceToHost, st));
+    NRS_HIP(c, hipStreamSynchronize(st));
+    mark("copy back");
+    embwin_bind(out, static_cast<char*>(c->embwin_pin));
+    out->on_device = 1;
+    return NRS_OK;
+}
+
+}  // namespace nrs

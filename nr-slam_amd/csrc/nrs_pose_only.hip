@@ -493,6 +493,7 @@ extern "C" void nrs_destroy(nrs_ctx* c) {
     if (c->pin_flags) (void)hipHostFree(c->pin_flags);
     if (c->pin_spec_scal) (void)hipHostFree(c->pin_spec_scal);
     if (c->pin_spec_flags) (void)hipHostFree(c->pin_spec_flags);
+    if (c->embwin_pin) (void)hipHostFree(c->embwin_pin);
     for (int j = 0; j < 3; ++j) {
         if (c->spec_stream[j]) { (void)hipStreamSynchronize(c->spec_stream[j]); (void)hipStreamDestroy(c->spec_stream[j]); }
         if (c->spec_join[j]) (void)hipEventDestroy(c->spec_join[j]);

@@ -20,7 +20,7 @@ COMM_ID_BYTES = 128
 SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "nrs_device_name", "nrs_get_profile",
            "nrs_reset_profile", "nrs_stream", "nrs_pose_only_solve", "nrs_dba_build_edges",
            "nrs_dba_solve", "nrs_dba_upload", "nrs_dba_build_edges_embedded", "nrs_dba_upload_embedded", "nrs_dba_download_skinned", "nrs_dba_solve_embedded", "nrs_dba_reset", "nrs_dba_optimize",
-           "nrs_dba_download", "nrs_dba_residuals", "nrs_dba_gradient", "nrs_dba_pack_hash", "nrs_dba_solve_window", "nrs_dba_window_edges", "nrs_debug_pcg_solve", "nrs_debug_kft", "nrs_debug_set", "nrs_debug_nd_solve", "nrs_debug_nd_cache_stats", "nrs_track_deform_solve_embedded",
+           "nrs_dba_download", "nrs_dba_residuals", "nrs_dba_gradient", "nrs_dba_pack_hash", "nrs_dba_solve_window", "nrs_dba_window_edges", "nrs_dba_solve_window_embedded", "nrs_dba_window_edges_embedded", "nrs_debug_pcg_solve", "nrs_debug_kft", "nrs_debug_set", "nrs_debug_nd_solve", "nrs_debug_nd_cache_stats", "nrs_track_deform_solve_embedded",
            "nrs_graph_select_neighbours", "nrs_graph_update", "nrs_track_deform_solve",
            "nrs_klt_configure", "nrs_klt_clear", "nrs_klt_num_points", "nrs_klt_set_reference",
            "nrs_klt_track", "nrs_klt_get_template", "nrs_klt_insert_template", "nrs_klt_get_templates",
@@ -663,6 +663,44 @@ class Context:
             return None
         self._chk(rc)
         return dict(sp_ij=sp_ij, sp_d0=sp_d0, dm_idx=dm_idx, dm_w=dm_w)
+
+    def dba_solve_window_embedded(self, cam, poses_qt, kf_points, obs_xyz, obs_uv, is_node, graph, scale, iters=5, trace=None):
+        """The embedded window in one call (include/nrs.h nrs_dba_solve_window_embedded): the lists of dba_build_edges_embedded are built
+        on the device.  obs_xyz / obs_uv are per observation (position in the concatenation of kf_points).  Returns (poses_qt, obs_xyz):
+        node copies optimised, skinned observations at their skinned position, observations bound to nothing unchanged."""
+        n_kf = len(kf_points)
+        kf_rowptr = np.zeros(n_kf + 1, np.int32)
+        kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
+        kf_pt = _i32(np.concatenate(kf_points))
+        pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
+        xyz = np.array(obs_xyz, np.float32).reshape(-1, 3).copy()
+        uv = _f32(obs_uv).reshape(-1, 2)
+        node = None if is_node is None else np.ascontiguousarray(is_node, np.uint8)
+        rp, col, w, d0, st = (_i32(graph["rowptr"]), _i32(graph["col"]), _f32(graph["w"]), _f32(graph["d0"]), _i32(graph["status"]))
+        assert node is None or len(node) == len(rp) - 1
+        self._chk(self.lib.nrs_dba_solve_window_embedded(self.h, C.byref(cam), C.c_int32(n_kf), _p(pq, C.c_double), _p(kf_rowptr, C.c_int32), _p(kf_pt, C.c_int32),
+                                                         _p(xyz, C.c_float), _p(uv, C.c_float), C.c_int32(len(rp) - 1),
+                                                         None if node is None else _p(node, C.c_uint8), _p(rp, C.c_int32), _p(col, C.c_int32),
+                                                         _p(w, C.c_float), _p(d0, C.c_float), _p(st, C.c_int32), C.c_float(scale), C.c_int32(iters),
+                                                         C.byref(trace.c) if trace else None))
+        n = [C.c_int32(0) for _ in range(4)]
+        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, None, C.byref(n[0]), None, C.byref(n[1]), None, None, C.byref(n[2]), None, None, C.byref(n[3]), None, None, None))
+        self._n_kf, self._n_lm, self._n_sp, self._n_dm, self._n_skin = n_kf, n[0].value, n[1].value, n[2].value, n[3].value
+        return pq, xyz
+
+    def dba_window_edges_embedded(self):
+        """lists of the resident window dba_solve_window_embedded made: the keys of dba_build_edges_embedded plus on_device (1: built on
+        the device); NrsError NRS_ERR_STATE when the resident window was made by another call"""
+        dev, nl, ns, nd, nk = (C.c_int32(0) for _ in range(5))
+        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, C.byref(dev), C.byref(nl), None, C.byref(ns), None, None, C.byref(nd), None, None, C.byref(nk), None, None, None))
+        lm_obs = np.zeros(nl.value, np.int32)
+        sp_ij, sp_d0 = np.zeros((ns.value, 2), np.int32), np.zeros(ns.value, np.float32)
+        dm_idx, dm_w = np.zeros((nd.value, 4), np.int32), np.zeros(nd.value, np.float32)
+        sk_obs, sk_node, sk_omega = np.zeros(nk.value, np.int32), np.zeros((nk.value, 11), np.int32), np.zeros((nk.value, 11), np.float64)
+        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, C.byref(dev), C.byref(nl), _p(lm_obs, C.c_int32), C.byref(ns), _p(sp_ij, C.c_int32), _p(sp_d0, C.c_float),
+                                                         C.byref(nd), _p(dm_idx, C.c_int32), _p(dm_w, C.c_float), C.byref(nk), _p(sk_obs, C.c_int32),
+                                                         _p(sk_node, C.c_int32), _p(sk_omega, C.c_double)))
+        return dict(lm_obs=lm_obs, sp_ij=sp_ij, sp_d0=sp_d0, dm_idx=dm_idx, dm_w=dm_w, sk_obs=sk_obs, sk_node=sk_node, sk_omega=sk_omega, on_device=dev.value)
 
     def dba_upload(self, cam, poses_qt, lm_xyz, lm_kf, lm_uv, edges, scale):
         args = self._dba_args(cam, poses_qt, lm_xyz, lm_kf, lm_uv, edges, scale)
