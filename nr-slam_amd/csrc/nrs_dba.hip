@@ -249,18 +249,25 @@ static int window_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const 
     ba_constants(s, scale);
     s.delta_pos = 0.0; s.spring_form = 0; s.shard = true;
     s.n_sp = 1; s.n_dm = 1;                                          // (placeholders for the eligibility test: counts follow)
-    if (!c->comm && engine_device_pack_ok(c, s)) {
+    // On a communicator every rank builds the window's edge lists on its own device and hands them to the rank-local construction.
+    // Whatever happens from here on may happen on one rank alone, so every rank reaches exactly one agreement: here, or in the
+    // nrs_dba_upload of the host path (a rank whose window does not qualify takes that path on its own: the same bits).
+    if (engine_device_pack_ok(c, s)) {
         DevEdges de;
         NRS_HIP(c, hipSetDevice(c->device));
-        NRS_TRY(engine_build_edges_device(c, n_kf, kf_rowptr, kf_pt, lm_kf.data(), n_points, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, &de));
-        if (de.n_sp > 0 && de.n_dm > 0) {
+        int rc = engine_build_edges_device(c, n_kf, kf_rowptr, kf_pt, lm_kf.data(), n_points, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, &de);
+        if (rc != NRS_OK) { (void)comm_agree(c, rc); return rc; }
+        if (de.n_sp > 0 && de.n_dm > 0) {                            // (the same counts on every rank)
             s.n_sp = de.n_sp; s.sp_ij = de.sp_ij; s.sp_d0 = de.sp_d0;
             s.n_dm = de.n_dm; s.dm_idx = de.dm_idx; s.dm_w = de.dm_w;
             s.edges_on_device = true;
-            const int rc = engine_create(c, s, &c->arena_dba, &c->dba);
-            if (rc == NRS_OK) return NRS_OK;
+            rc = engine_create(c, s, &c->arena_dba, &c->dba);
+            if (rc != NRS_ERR_STATE) {                               // (NRS_ERR_STATE: the window's halos exceed the device path's limits)
+                if (rc == NRS_OK || c->err_local) rc = comm_agree(c, rc);
+                if (rc != NRS_OK) dba_free(c);
+                return rc;
+            }
             dba_free(c);
-            if (rc != NRS_ERR_STATE) return rc;                      // (NRS_ERR_STATE: the window's halos exceed the device path's limits)
         }
     }
     // host path: nrs_dba_build_edges, then the upload as nrs_dba_upload makes it

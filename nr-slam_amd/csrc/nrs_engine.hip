@@ -1140,13 +1140,15 @@ int engine_pack_hash(nrs_ctx* c, Engine* e, uint64_t* out) {
         out[12] = fnv(ed.data(), sizeof(EcDamper) * ed.size());
         ok = ok && dev(d.ec_w, sizeof(float) * (size_t)d.ec_ndm, &out[13]);
     }
-    ok = ok && dev(d.rflag, (size_t)d.n_rows, &out[14]) && dev(d.uv, sizeof(float) * 2 * (size_t)d.n_rows, &out[15]);
-    ok = ok && dev(d.xl_init, sizeof(double) * 3 * (size_t)d.n_rows, &out[16]) && dev(d.pose_init, sizeof(Pose) * (size_t)d.K, &out[17]);
+    // per-row arrays: the rows this engine holds (all of them, except on a row-limited rank of a sharded window: ArenaPlan::get_rows)
+    const size_t r0 = (size_t)d.row_lo, rn = (size_t)(d.row_hi - d.row_lo);
+    ok = ok && dev(d.rflag + r0, rn, &out[14]) && dev(d.uv + 2 * r0, sizeof(float) * 2 * rn, &out[15]);
+    ok = ok && dev(d.xl_init + 3 * r0, sizeof(double) * 3 * rn, &out[16]) && dev(d.pose_init, sizeof(Pose) * (size_t)d.K, &out[17]);
     ok = ok && dev(d.grp_pose, sizeof(int) * (size_t)d.n_groups, &out[18]) && dev(d.pose_grp_ptr, sizeof(int) * ((size_t)d.K + 1), &out[19]);
     const int sc[16] = {d.n_rows, d.T, d.ss_nnz, d.sd_nnz, d.max_halo, d.max_halo_s, d.n_tiles_cls[0], d.n_tiles_cls[1], d.cap_h[0], d.cap_h[1], d.cap_s[0], d.cap_s[1],
                         d.ec_nblk, d.lin_rb, d.hier + 2 * d.fused + 4 * d.ecd + 8 * d.use_lds, d.plain + 2 * d.tp_ok + 4 * d.h4};
-    if (d.plain) { uint64_t h = 0; ok = ok && dev(d.row_tp, sizeof(uint32_t) * (size_t)d.n_rows, &h); out[20] ^= h * 31; }
-    if (d.plain) { uint64_t h = 0; ok = ok && dev(d.row_cnt, sizeof(uint32_t) * (size_t)d.n_rows, &h); out[20] ^= h * 131; }
+    if (d.plain) { uint64_t h = 0; ok = ok && dev(d.row_tp + r0, sizeof(uint32_t) * rn, &h); out[20] ^= h * 31; }
+    if (d.plain) { uint64_t h = 0; ok = ok && dev(d.row_cnt + r0, sizeof(uint32_t) * rn, &h); out[20] ^= h * 131; }
     out[20] ^= fnv(sc, sizeof(sc));
     out[21] = e->dev_edges ? 1 : 0;                                  // (which path built it: not part of the comparison)
     if (d.fused) ok = ok && dev(d.tile_desc, sizeof(int) * 8 * nt, &out[22]) && dev(d.halo_fix, sizeof(int) * BLK * nt, &out[23]);

@@ -15,8 +15,18 @@
 // The host keeps what it needs to drive the solve: the vertex -> row map (download), the tile classes (from the halo sizes).
 // Conditions (otherwise engine_create takes the host path): a plain BA window (nothing fixed, no masks, offsets or unary
 // dampers, every damper with four vertices, springs without kernel) of >= 2 keyframes and >= 2048 padded rows -- the two-kernel
-// path (>= 32768 rows, T = 2) and the fused one (T = 8) alike -- no communicator, halos that fit the LDS budget, at most 2048 halo
-// rows per tile.  NRS_HOST_PACK=1 forces the host path, and so does every A/B switch that path honours (devpack_eligible).
+// path (>= 32768 rows, T = 2) and the fused one (T = 8) alike -- halos that fit the LDS budget, at most 2048 halo rows per tile.
+// NRS_HOST_PACK=1 forces the host path, and so does every A/B switch that path honours (devpack_eligible).
+//
+// On a communicator (a world of one included) every rank runs this construction for ITSELF, without a collective: the row layout
+// is the window's (integer sorts and one fp64 expression: the same vrow on every rank, O(window) work), everything behind it is
+// the rank's share -- the (row, edge) keys of rows in [pack_lo, pack_hi) only (k_dp_count_own / k_dp_keys_own compact them; the
+// sorts, k_dp_fill_s/d, both halo passes over the rank's own tiles and the chi2 edge lists see nothing else), rows of other ranks
+// keep empty lists.  A sharded window is always on the two-kernel PCG, so a window under 32768 rows is two-kernel with T = 8 here.
+// The shard fields (tile ranges per class, boundary tiles, the adjacent-keyframe check) come from the per-tile minimum / maximum
+// halo row that pass 0 leaves, BEFORE the arena is carved: a rank's per-row arrays hold its own keyframes and one ghost keyframe
+// either side only (ArenaPlan::get_rows), and every kernel here that writes one is bounded to [row_lo, row_hi).  A rank whose
+// window does not qualify after all takes the host path on its own: the two constructions give the same bits.
 #pragma once
 #include <rocprim/rocprim.hpp>
 
@@ -115,6 +125,54 @@ __global__ void k_dp_inc(int n_sp, const int* __restrict__ sp_ij, int n_dm, cons
     }
 }
 
+// ---- a rank of a sharded window: the incidences of rows in [lo, hi) only.  Counts first (the record-side scratch is sized from
+// them), then the keys, compacted: a workgroup reserves its share of the output with one atomic per list -- the order this leaves
+// is arbitrary and does not matter, the keys are distinct and the radix sorts that follow put them in (row, sequence) order.
+// tot / cur [0..4): spring incidences, damper incidences, springs counted here (first endpoint owned), dampers counted here
+__global__ __launch_bounds__(256) void k_dp_count_own(int n_sp, const int* __restrict__ sp_ij, int n_dm, const int* __restrict__ dm_idx, const int* __restrict__ vrow,
+                                                      int lo, int hi, int* cnt_s, int* cnt_d, int* tot) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int es = 0, ed = 0;
+    if (i < 2 * (int64_t)n_sp) {
+        const int r = vrow[sp_ij[i]];
+        if (r >= lo && r < hi) { atomicAdd(&cnt_s[r], 1); es = !(i & 1); }
+    }
+    if (i < 4 * (int64_t)n_dm) {
+        const int r = vrow[dm_idx[i]];
+        if (r >= lo && r < hi) { atomicAdd(&cnt_d[r], 1); ed = !(i & 3); }
+    }
+    const int ns = __syncthreads_count(es), nd = __syncthreads_count(ed);
+    if (threadIdx.x == 0) { if (ns) atomicAdd(&tot[2], ns); if (nd) atomicAdd(&tot[3], nd); }
+}
+__global__ __launch_bounds__(256) void k_dp_keys_own(int n_sp, const int* __restrict__ sp_ij, int n_dm, const int* __restrict__ dm_idx, const int* __restrict__ vrow,
+                                                     int lo, int hi, uint64_t* key_s, uint64_t* key_d, uint64_t* ek_s, uint64_t* ek_d, int* cur) {
+    __shared__ int n_loc[4], base[4];
+    const int tid = threadIdx.x;
+    if (tid < 4) n_loc[tid] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + tid;
+    int rs = -1, rd = -1, ps = 0, pd = 0, pes = -1, ped = -1;
+    if (i < 2 * (int64_t)n_sp) {
+        const int r = vrow[sp_ij[i]];
+        if (r >= lo && r < hi) { rs = r; ps = atomicAdd(&n_loc[0], 1); if (!(i & 1)) pes = atomicAdd(&n_loc[2], 1); }
+    }
+    if (i < 4 * (int64_t)n_dm) {
+        const int r = vrow[dm_idx[i]];
+        if (r >= lo && r < hi) { rd = r; pd = atomicAdd(&n_loc[1], 1); if (!(i & 3)) ped = atomicAdd(&n_loc[3], 1); }
+    }
+    __syncthreads();
+    if (tid < 4) base[tid] = n_loc[tid] ? atomicAdd(&cur[tid], n_loc[tid]) : 0;
+    __syncthreads();
+    if (rs >= 0) {
+        key_s[base[0] + ps] = ((uint64_t)(uint32_t)rs << 32) | (uint64_t)(uint32_t)i;
+        if (pes >= 0) ek_s[base[2] + pes] = ((uint64_t)(uint32_t)rs << 32) | (uint64_t)(uint32_t)(i >> 1);
+    }
+    if (rd >= 0) {
+        key_d[base[1] + pd] = ((uint64_t)(uint32_t)rd << 32) | (uint64_t)(uint32_t)i;
+        if (ped >= 0) ek_d[base[3] + ped] = ((uint64_t)(uint32_t)rd << 32) | (uint64_t)(uint32_t)(i >> 2);
+    }
+}
+
 // slice widths (x 64): a slice = 64 / T rows, T lanes per row
 __global__ void k_dp_widths(int n_slices, int T, const int* __restrict__ cnt_s, const int* __restrict__ cnt_d, int* ws, int* wd) {
     const int sl = blockIdx.x * blockDim.x + threadIdx.x;
@@ -162,20 +220,22 @@ __global__ void k_dp_fill_d(int64_t n, int T, const uint64_t* __restrict__ key, 
 
 // ---- halo of a tile: the rows its incidences reference outside its own 128 rows.  PASS 0 counts (hs, ns), PASS 1 writes
 // the lists and the final incidence headers.  LDS: open-addressing hash set (row, seen-by-a-spring flag), then a bitonic sort
-// of (damper-only << 31 | row).
+// of (damper-only << 31 | row).  The grid covers tiles [b0, b0 + gridDim.x): a rank of a sharded window runs its own tiles only
+// (the others have empty lists) and takes from pass 0 the smallest / largest halo row of every tile as well (hmin / hmax: the
+// shard fields are derived from them, nrs_engine_setup.hpp "shard window").
 template <int PASS>
-__global__ __launch_bounds__(256) void k_dp_halo(int tile_rows, int T, uint16_t* row_tp16, const int* __restrict__ ss_ptr, const int* __restrict__ sd_ptr, const int* __restrict__ S_other,
+__global__ __launch_bounds__(256) void k_dp_halo(int b0, int* hmin, int* hmax, int tile_rows, int T, uint16_t* row_tp16, const int* __restrict__ ss_ptr, const int* __restrict__ sd_ptr, const int* __restrict__ S_other,
                                                  const uint8_t* __restrict__ S_side, const int* __restrict__ D_o, const int8_t* __restrict__ D_role,
                                                  int* hs, int* hns, const int* __restrict__ halo_ptr, int* halo_rows, uint32_t* s_om, uint2* d_hdr,
                                                  int* overflow) {
     __shared__ uint32_t hk[DP_HASH];                                 // row + 1 (0 = empty)
     __shared__ uint32_t hf[DP_HASH];                                 // 1 = referenced by a spring
     __shared__ uint32_t keys[DP_HCAP];
-    __shared__ int cnt, cnt_s;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    __shared__ int cnt, cnt_s, row_mn, row_mx;
+    const int b = b0 + blockIdx.x, tid = threadIdx.x;
     const int row0 = b * tile_rows, row1 = row0 + tile_rows;
     for (int i = tid; i < DP_HASH; i += 256) { hk[i] = 0; hf[i] = 0; }
-    if (tid == 0) { cnt = 0; cnt_s = 0; }
+    if (tid == 0) { cnt = 0; cnt_s = 0; row_mn = 0x7FFFFFFF; row_mx = -1; }
     __syncthreads();
     const int s0 = ss_ptr[b * 4], s1 = ss_ptr[b * 4 + 4], d0 = sd_ptr[b * 4], d1 = sd_ptr[b * 4 + 4];
     auto insert = [&](int o, uint32_t spring) {
@@ -198,10 +258,12 @@ __global__ __launch_bounds__(256) void k_dp_halo(int tile_rows, int T, uint16_t*
             const int j = atomicAdd(&cnt, 1);
             if (hf[i]) atomicAdd(&cnt_s, 1);
             if (j < DP_HCAP) keys[j] = (hf[i] ? 0u : 0x80000000u) | (hk[i] - 1u);
+            if (PASS == 0 && hmin) { atomicMin(&row_mn, (int)(hk[i] - 1u)); atomicMax(&row_mx, (int)(hk[i] - 1u)); }
         }
     }
     __syncthreads();
     const int n = cnt, ns = cnt_s;
+    if (PASS == 0 && hmin && tid == 0) { hmin[b] = row_mn; hmax[b] = row_mx; }
     if (n > DP_HCAP) { if (tid == 0) atomicExch(overflow, 1); if (PASS == 0 && tid == 0) { hs[b] = n; hns[b] = ns; } return; }
     if (PASS == 0) { if (tid == 0) { hs[b] = n; hns[b] = ns; } return; }
     // bitonic sort of keys[0 .. 2048): spring part first (bit 31 clear), each part ascending by row; padding (0xFFFFFFFF) last
@@ -285,19 +347,20 @@ __global__ void k_dp_ecfill(int n_sp, const uint64_t* __restrict__ ks, const int
 }
 
 // per-row data from per-vertex data (padding rows: fixed, no observation, zeros)
-__global__ void k_dp_rowdata(int n_rows, const int* __restrict__ row_v, const double* __restrict__ xyz, const float* __restrict__ uv_in,
+// (rows [r0, r1): every row, or the rows a rank of a sharded window holds -- the arrays are addressed by the global row)
+__global__ void k_dp_rowdata(int r0, int r1, const int* __restrict__ row_v, const double* __restrict__ xyz, const float* __restrict__ uv_in,
                              uint8_t* rflag, float* uv, double* xl) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
+    const int r = r0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= r1) return;
     const int v = row_v[r];
     rflag[r] = v < 0 ? (uint8_t)RF_FIXED : (uint8_t)(RF_OBS | RF_REPROJ_ACTIVE);
     uv[2 * (size_t)r] = v < 0 ? 0.f : uv_in[2 * (size_t)v];
     uv[2 * (size_t)r + 1] = v < 0 ? 0.f : uv_in[2 * (size_t)v + 1];
     for (int a = 0; a < 3; ++a) xl[3 * (size_t)r + a] = v < 0 ? 0.0 : xyz[3 * (size_t)v + a];
 }
-__global__ void k_dp_rowcnt(int n_rows, const int* __restrict__ cnt_s, const int* __restrict__ cnt_d, uint32_t* out) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n_rows) out[r] = (uint32_t)cnt_s[r] | ((uint32_t)cnt_d[r] << 16);
+__global__ void k_dp_rowcnt(int r0, int r1, const int* __restrict__ cnt_s, const int* __restrict__ cnt_d, uint32_t* out) {
+    const int r = r0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < r1) out[r] = (uint32_t)cnt_s[r] | ((uint32_t)cnt_d[r] << 16);
 }
 __global__ void k_dp_rowv(int M, const int* __restrict__ vrow, int* row_v) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -456,9 +519,11 @@ int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const 
 
 static bool devpack_eligible(nrs_ctx* c, const EngineSpec& s, int n_pad_rows) {
     if (c->env("NRS_HOST_PACK") || c->env("NRS_NO_PLAIN") || c->env("NRS_NO_LDS") || c->env("NRS_DFORM") || c->env("NRS_NO_EDGE_CHI") || c->env("NRS_NO_FUSED") ||
-        c->env("NRS_SELL_T") || c->env("NRS_FUSED_MAX_ROWS") || c->env("NRS_TILE_CUT_PCT") || c->env("NRS_HIER") || c->env("NRS_NO_ECD"))
+        c->env("NRS_SELL_T") || c->env("NRS_FUSED_MAX_ROWS") || c->env("NRS_TILE_CUT_PCT") || c->env("NRS_HIER") || c->env("NRS_NO_ECD") || c->env("NRS_SHARD_PACK_ALL"))
         return false;                                                // (test / A-B switches are honoured by the host path)
-    if (c->comm || s.X0 || s.n_un || s.sp_active || s.dm_active || s.pose_fixed || s.force_gather || s.n_skin > 0) return false;
+    // a communicator: one window over its ranks, with a rank count the sharded path accepts (engine_create has refused the others)
+    if (c->comm && (!s.shard || c->comm->world > 8 || s.K < c->comm->world)) return false;
+    if (s.X0 || s.n_un || s.sp_active || s.dm_active || s.pose_fixed || s.force_gather || s.n_skin > 0) return false;
     if (s.K < 2 || n_pad_rows < 2048 || s.delta_pos > 0 || s.spring_form != 0 || s.n_dm <= 0 || s.n_sp <= 0) return false;   // (single-frame problems: a2, host)
     if (4 * (int64_t)s.n_dm >= 0xFFFFFFFFLL || (int64_t)n_pad_rows >= 0x7FFFFFFFLL) return false;
     return true;
@@ -494,7 +559,8 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
         if (!tm) return;
         (void)hipStreamSynchronize(c->stream);
         auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nrs] device pack %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        if (c->comm) fprintf(stderr, "[nrs] rank %d/%d device pack %-18s %.2f ms\n", c->comm->rank, c->comm->world, what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        else fprintf(stderr, "[nrs] device pack %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
     };
     for (int v = 0; v < s.M; ++v) if (s.rflag[v] != (RF_OBS | RF_REPROJ_ACTIVE)) return NRS_OK;
@@ -524,11 +590,19 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     d.n_vecblk = d.n_rows / BLK;
     const int n_rows = d.n_rows, n_slices = n_rows / (64 / T), n_tiles = d.n_regblk;
     const int64_t ni_s = 2 * (int64_t)n_sp, ni_d = 4 * (int64_t)n_dm;
+    // a rank of a sharded window packs the incidence records of its own keyframe range only (shard_plan, as engine_create)
+    const bool sh = c->comm != nullptr && s.shard;
+    const int Wn = sh ? c->comm->world : 1, rk = sh ? c->comm->rank : 0;
+    std::vector<int> kb(Wn + 1, 0);
+    kb[Wn] = K;
+    if (sh) shard_plan(K, pose_grp_ptr.data(), Wn, kb.data());
+    const int pack_lo = pose_grp_ptr[kb[rk]] * ROW_ALIGN, pack_hi = pose_grp_ptr[kb[rk + 1]] * ROW_ALIGN;
+    const int tb0 = pack_lo / d.tile_rows, tb1 = pack_hi / d.tile_rows;     // its tiles
     // ---- scratch: raw inputs + intermediates (sized from the inputs; the packed arrays themselves go into the arena later)
     size_t tmp_bytes = 0;
     {
         size_t b1 = 0, b2 = 0, b3 = 0, b4 = 0;
-        (void)rocprim::radix_sort_keys(nullptr, b1, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)std::max(ni_s, ni_d), 0, 64, c->stream);
+        if (!sh) (void)rocprim::radix_sort_keys(nullptr, b1, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)std::max(ni_s, ni_d), 0, 64, c->stream);   // (a rank: sized from its share, below)
         (void)rocprim::segmented_radix_sort_pairs(nullptr, b2, (uint64_t*)nullptr, (uint64_t*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)M, (unsigned)K,
                                                   (int*)nullptr, (int*)nullptr, 0, 64, c->stream);
         (void)rocprim::segmented_radix_sort_pairs(nullptr, b3, (uint32_t*)nullptr, (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n_rows,
@@ -539,7 +613,7 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     auto al = [](size_t b) { return ((b + 255) / 256) * 256 + 256; };
     double* r_x; int* r_kf; float* r_uv; int* r_sp; float* r_d0; int* r_dm; float* r_w;
     uint64_t *code_a, *code_b, *key_s, *key_s2, *key_d, *key_d2;
-    int *val_a, *val_b, *cs, *cd, *d_pose_ptr, *d_pgp, *tile_off, *vrow, *row_v, *tv_a, *tv_b, *cnt_s, *cnt_d, *rs_s, *rs_d, *ws, *wd, *d_ss, *d_sd, *hs, *hns, *d_flag;
+    int *val_a, *val_b, *cs, *cd, *d_pose_ptr, *d_pgp, *tile_off, *vrow, *row_v, *tv_a, *tv_b, *cnt_s, *cnt_d, *rs_s, *rs_d, *ws, *wd, *d_ss, *d_sd, *hs, *hns, *hmin, *hmax, *d_flag;
     uint32_t *tk_a, *tk_b;
     void* tmp;
     double* mm;
@@ -552,11 +626,11 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
         vrow = W.get<int>(M); row_v = W.get<int>(n_rows);
         tk_a = W.get<uint32_t>(n_rows); tk_b = W.get<uint32_t>(n_rows); tv_a = W.get<int>(n_rows); tv_b = W.get<int>(n_rows);
         cnt_s = W.get<int>((size_t)n_rows + 1); cnt_d = W.get<int>((size_t)n_rows + 1); rs_s = W.get<int>((size_t)n_rows + 1); rs_d = W.get<int>((size_t)n_rows + 1);
-        key_s = W.get<uint64_t>(ni_s); key_s2 = W.get<uint64_t>(ni_s); key_d = W.get<uint64_t>(ni_d); key_d2 = W.get<uint64_t>(ni_d);
+        if (!sh) { key_s = W.get<uint64_t>(ni_s); key_s2 = W.get<uint64_t>(ni_s); key_d = W.get<uint64_t>(ni_d); key_d2 = W.get<uint64_t>(ni_d); }   // (a rank: in the second scratch, sized from its share)
         ws = W.get<int>((size_t)n_slices + 1); wd = W.get<int>((size_t)n_slices + 1); d_ss = W.get<int>((size_t)n_slices + 1); d_sd = W.get<int>((size_t)n_slices + 1);
         tmp = W.get<char>(tmp_bytes);
         mm = W.get<double>(8);
-        hs = W.get<int>(n_tiles); hns = W.get<int>(n_tiles); d_flag = W.get<int>(16);
+        hs = W.get<int>(n_tiles); hns = W.get<int>(n_tiles); hmin = W.get<int>(n_tiles); hmax = W.get<int>(n_tiles); d_flag = W.get<int>(16);
     };
     {
         DpScratch dry{nullptr, 0, 0};
@@ -607,7 +681,9 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     // ---- incidence counts, slice widths, offsets
     NRS_HIP(c, hipMemsetAsync(cnt_s, 0, sizeof(int) * ((size_t)n_rows + 1), st));
     NRS_HIP(c, hipMemsetAsync(cnt_d, 0, sizeof(int) * ((size_t)n_rows + 1), st));
-    hipLaunchKernelGGL(k_dp_inc, nb(std::max(ni_s, ni_d)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, vrow, cnt_s, cnt_d, key_s, key_d);
+    NRS_HIP(c, hipMemsetAsync(d_flag, 0, sizeof(int) * 16, st));
+    if (sh) hipLaunchKernelGGL(k_dp_count_own, nb(std::max(ni_s, ni_d)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, vrow, pack_lo, pack_hi, cnt_s, cnt_d, d_flag + 4);
+    else hipLaunchKernelGGL(k_dp_inc, nb(std::max(ni_s, ni_d)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, vrow, cnt_s, cnt_d, key_s, key_d);
     hipLaunchKernelGGL(k_dp_widths, nb(n_slices), dim3(256), 0, st, n_slices, T, cnt_s, cnt_d, ws, wd);
     NRS_HIP(c, hipMemsetAsync(ws + n_slices, 0, sizeof(int), st));
     NRS_HIP(c, hipMemsetAsync(wd + n_slices, 0, sizeof(int), st));
@@ -618,45 +694,82 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     int h_nnz[2] = {0, 0};
     NRS_HIP(c, hipMemcpyAsync(&h_nnz[0], d_ss + n_slices, sizeof(int), hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipMemcpyAsync(&h_nnz[1], d_sd + n_slices, sizeof(int), hipMemcpyDeviceToHost, st));
-    // (the sorts run while the host waits for the two totals)
+    // (the sorts run while the host waits for the two totals; a rank sorts its own keys once it knows how many there are)
     const int row_bits = 32 - __builtin_clz((unsigned)std::max(1, n_rows - 1));
-    tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, key_s, key_s2, (size_t)ni_s, 0, 32 + row_bits, st));
-    tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, key_d, key_d2, (size_t)ni_d, 0, 32 + row_bits, st));
+    int h_own[4] = {(int)ni_s, (int)ni_d, n_sp, n_dm};              // incidences and counted edges held here: all of them on one GPU
+    if (sh) {
+        NRS_HIP(c, hipMemcpyAsync(&h_own[0], rs_s + n_rows, sizeof(int), hipMemcpyDeviceToHost, st));
+        NRS_HIP(c, hipMemcpyAsync(&h_own[1], rs_d + n_rows, sizeof(int), hipMemcpyDeviceToHost, st));
+        NRS_HIP(c, hipMemcpyAsync(&h_own[2], d_flag + 6, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+    } else {
+        tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, key_s, key_s2, (size_t)ni_s, 0, 32 + row_bits, st));
+        tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, key_d, key_d2, (size_t)ni_d, 0, 32 + row_bits, st));
+    }
     NRS_HIP(c, hipStreamSynchronize(st));
     const size_t nnz_s = (size_t)h_nnz[0], nnz_d = (size_t)h_nnz[1];
+    const int64_t own_s = h_own[0], own_d = h_own[1];
+    const int ec_nsp = h_own[2], ec_ndm = h_own[3];
     d.ss_nnz = (int)nnz_s; d.sd_nnz = (int)nnz_d;
-    mark("counts + sorts");
-    // ---- second scratch: sliced-ELL intermediates with GLOBAL neighbour rows
-    const size_t need2 = 2 * al(4 * nnz_s) + al(nnz_s) + al(12 * nnz_d) + al(4 * nnz_d) + al(nnz_d) + 2 * al(8 * (size_t)n_sp) + 2 * al(8 * (size_t)n_dm) + (1 << 16);
+    if (!sh) mark("counts + sorts");
+    // ---- second scratch: sliced-ELL intermediates with GLOBAL neighbour rows; on a rank also its keys and the sorts' temporary
+    // storage -- everything here is sized from what the rank holds
+    size_t tmp2_bytes = 0;
+    if (sh) {
+        (void)rocprim::radix_sort_keys(nullptr, tmp2_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)std::max<int64_t>(std::max(own_s, own_d), 1), 0, 64, c->stream);
+        tmp2_bytes += 1024;
+    }
+    const size_t need2 = 2 * al(4 * nnz_s) + al(nnz_s) + al(12 * nnz_d) + al(4 * nnz_d) + al(nnz_d) + 2 * al(8 * (size_t)ec_nsp) + 2 * al(8 * (size_t)ec_ndm) +
+                         (sh ? 2 * al(8 * (size_t)own_s) + 2 * al(8 * (size_t)own_d) + al(tmp2_bytes) : 0) + (1 << 16);
     NRS_TRY(c->ensure(c->pack_ws2, need2));
     DpScratch W2{c->pack_ws2.as<char>(), 0, c->pack_ws2.cap};
     int* S_other = W2.get<int>(nnz_s);
     uint8_t* S_side = W2.get<uint8_t>(nnz_s);
     int* D_o = W2.get<int>(3 * nnz_d);
     int8_t* D_role = W2.get<int8_t>(nnz_d);
-    uint64_t* ek_s = W2.get<uint64_t>(n_sp); uint64_t* ek_s2 = W2.get<uint64_t>(n_sp);
-    uint64_t* ek_d = W2.get<uint64_t>(n_dm); uint64_t* ek_d2 = W2.get<uint64_t>(n_dm);
+    uint64_t* ek_s = W2.get<uint64_t>(ec_nsp); uint64_t* ek_s2 = W2.get<uint64_t>(ec_nsp);
+    uint64_t* ek_d = W2.get<uint64_t>(ec_ndm); uint64_t* ek_d2 = W2.get<uint64_t>(ec_ndm);
     float* t_d0 = W2.get<float>(nnz_s);
     float* t_w = W2.get<float>(nnz_d);
+    void* tmp2 = nullptr;
+    if (sh) {
+        key_s = W2.get<uint64_t>(own_s); key_s2 = W2.get<uint64_t>(own_s); key_d = W2.get<uint64_t>(own_d); key_d2 = W2.get<uint64_t>(own_d);
+        tmp2 = W2.get<char>(tmp2_bytes);
+    }
     if (W2.off > W2.cap) return c->fail(NRS_ERR_ALLOC, "device pack: scratch under-sized");
+    if (sh) {
+        hipLaunchKernelGGL(k_dp_keys_own, nb(std::max(ni_s, ni_d)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, vrow, pack_lo, pack_hi, key_s, key_d, ek_s, ek_d, d_flag + 8);
+        size_t t2 = tmp2_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp2, t2, key_s, key_s2, (size_t)own_s, 0, 32 + row_bits, st));
+        t2 = tmp2_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp2, t2, key_d, key_d2, (size_t)own_d, 0, 32 + row_bits, st));
+        t2 = tmp2_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp2, t2, ek_s, ek_s2, (size_t)ec_nsp, 0, 32 + row_bits, st));
+        t2 = tmp2_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp2, t2, ek_d, ek_d2, (size_t)ec_ndm, 0, 32 + row_bits, st));
+        mark("counts + sorts");
+    }
     // ---- halo sizes (pass 0 needs S_other / D_o: fill them into scratch first; S_d0 / D_w go straight into the arena later,
     // so the fill kernels run twice as cheaply as once with a staging copy: here only the ids)
     NRS_HIP(c, hipMemsetAsync(S_other, 0xFF, sizeof(int) * nnz_s, st));
     NRS_HIP(c, hipMemsetAsync(S_side, 0, nnz_s, st));
     NRS_HIP(c, hipMemsetAsync(D_o, 0xFF, sizeof(int) * 3 * nnz_d, st));
     NRS_HIP(c, hipMemsetAsync(D_role, 0xFF, nnz_d, st));
-    NRS_HIP(c, hipMemsetAsync(d_flag, 0, sizeof(int) * 16, st));
     // (S_d0 / D_w are staged too: the arena is carved only once the halo sizes are known)
     NRS_HIP(c, hipMemsetAsync(t_d0, 0, sizeof(float) * nnz_s, st));
     NRS_HIP(c, hipMemsetAsync(t_w, 0, sizeof(float) * nnz_d, st));
-    hipLaunchKernelGGL(k_dp_fill_s, nb(ni_s), dim3(256), 0, st, ni_s, T, key_s2, rs_s, d_ss, r_sp, r_d0, vrow, S_other, t_d0, S_side);
-    hipLaunchKernelGGL(k_dp_fill_d, nb(ni_d), dim3(256), 0, st, ni_d, T, key_d2, rs_d, d_sd, r_dm, r_w, vrow, D_o, t_w, D_role);
-    hipLaunchKernelGGL((k_dp_halo<0>), dim3(n_tiles), dim3(256), 0, st, d.tile_rows, T, (uint16_t*)nullptr, d_ss, d_sd, S_other, S_side, D_o, D_role, hs, hns, (const int*)nullptr,
-                       (int*)nullptr, (uint32_t*)nullptr, (uint2*)nullptr, d_flag);
-    std::vector<int> h_hs(n_tiles), h_hns(n_tiles), h_vrow(M);
+    if (own_s) hipLaunchKernelGGL(k_dp_fill_s, nb(own_s), dim3(256), 0, st, own_s, T, key_s2, rs_s, d_ss, r_sp, r_d0, vrow, S_other, t_d0, S_side);
+    if (own_d) hipLaunchKernelGGL(k_dp_fill_d, nb(own_d), dim3(256), 0, st, own_d, T, key_d2, rs_d, d_sd, r_dm, r_w, vrow, D_o, t_w, D_role);
+    if (sh) {                                                        // (tiles of other ranks: empty lists)
+        NRS_HIP(c, hipMemsetAsync(hs, 0, sizeof(int) * n_tiles, st));
+        NRS_HIP(c, hipMemsetAsync(hns, 0, sizeof(int) * n_tiles, st));
+    }
+    hipLaunchKernelGGL((k_dp_halo<0>), dim3(tb1 - tb0), dim3(256), 0, st, tb0, sh ? hmin : (int*)nullptr, sh ? hmax : (int*)nullptr, d.tile_rows, T, (uint16_t*)nullptr, d_ss, d_sd,
+                       S_other, S_side, D_o, D_role, hs, hns, (const int*)nullptr, (int*)nullptr, (uint32_t*)nullptr, (uint2*)nullptr, d_flag);
+    std::vector<int> h_hs(n_tiles), h_hns(n_tiles), h_vrow(M), h_hmin, h_hmax;
     int h_flag = 0;
     NRS_HIP(c, hipMemcpyAsync(h_hs.data(), hs, sizeof(int) * n_tiles, hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipMemcpyAsync(h_hns.data(), hns, sizeof(int) * n_tiles, hipMemcpyDeviceToHost, st));
+    if (sh) {
+        h_hmin.resize(n_tiles); h_hmax.resize(n_tiles);
+        NRS_HIP(c, hipMemcpyAsync(h_hmin.data() + tb0, hmin + tb0, sizeof(int) * (tb1 - tb0), hipMemcpyDeviceToHost, st));
+        NRS_HIP(c, hipMemcpyAsync(h_hmax.data() + tb0, hmax + tb0, sizeof(int) * (tb1 - tb0), hipMemcpyDeviceToHost, st));
+    }
     NRS_HIP(c, hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipMemcpyAsync(h_vrow.data(), vrow, sizeof(int) * (size_t)M, hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipStreamSynchronize(st));
@@ -706,11 +819,52 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     d.sh_on = 0; d.sh_rank = 0; d.sh_world = 1; d.sh_lead = 1;
     d.sh_k0 = 0; d.sh_nk = K; d.sh_g0 = 0; d.sh_ng = d.n_groups; d.sh_vb0 = 0; d.sh_nvb = d.n_vecblk;
     for (int cls = 0; cls < 2; ++cls) { d.sh_t0[cls] = 0; d.sh_nt[cls] = d.n_tiles_cls[cls]; }
+    if (sh) {
+        // ---- shard window (engine_create "shard window": the same fields, the same refusals).  What the host reads off the halo
+        // lists -- a row beyond the adjacent keyframes, a row of another rank -- is decided by a tile's smallest and largest halo row
+        d.sh_on = 1; d.sh_rank = rk; d.sh_world = Wn; d.sh_lead = rk == 0;
+        d.sh_k0 = kb[rk]; d.sh_nk = kb[rk + 1] - kb[rk];
+        d.sh_g0 = pose_grp_ptr[kb[rk]]; d.sh_ng = pose_grp_ptr[kb[rk + 1]] - d.sh_g0;
+        d.sh_vb0 = d.sh_g0 * (ROW_ALIGN / BLK); d.sh_nvb = d.sh_ng * (ROW_ALIGN / BLK);
+        if ((int64_t)d.sh_nvb * BLK < K) return c->fail(NRS_ERR_INVALID, "sharded solve: shard smaller than the pose count");
+        for (int cls = 0; cls < 2; ++cls) {                       // tile_list is ascending inside a class
+            const int* tl = tile_list.data() + (cls ? d.n_tiles_cls[0] : 0);
+            const int n = d.n_tiles_cls[cls];
+            const int a = (int)(std::lower_bound(tl, tl + n, tb0) - tl), b2 = (int)(std::lower_bound(tl, tl + n, tb1) - tl);
+            d.sh_t0[cls] = a; d.sh_nt[cls] = b2 - a;
+        }
+        const int r_lo = (kb[rk] > 0 ? pose_grp_ptr[kb[rk] - 1] : d.sh_g0) * ROW_ALIGN;
+        const int r_hi = (kb[rk + 1] < K ? pose_grp_ptr[kb[rk + 1] + 1] : d.sh_g0 + d.sh_ng) * ROW_ALIGN;
+        for (int b = tb0; b < tb1; ++b)
+            if (h_hs[b] > 0 && (h_hmin[b] < r_lo || h_hmax[b] >= r_hi))
+                return c->fail(NRS_ERR_INVALID, "sharded solve: an edge of keyframe range [%d, %d) reaches beyond the adjacent keyframes", kb[rk], kb[rk + 1]);
+        // the per-row arrays hold [r_lo, r_hi) only (NRS_SHARD_FULL_VECTORS=1: every row): every launch below that writes one is bounded to it
+        if (Wn > 1 && !c->env("NRS_SHARD_FULL_VECTORS")) { d.row_lo = r_lo; d.row_hi = r_hi; }
+        auto foreign = [&](int b) { return h_hs[b] > 0 && (h_hmin[b] < pack_lo || h_hmax[b] >= pack_hi); };
+        for (int cls = 0; cls < 2; ++cls) {
+            const int* tl = tile_list.data() + (cls ? d.n_tiles_cls[0] : 0) + d.sh_t0[cls];
+            const int n = d.sh_nt[cls];
+            int first = n, last = -1;                              // first / last own tile of the class that is interior
+            for (int i = 0; i < n; ++i) if (!foreign(tl[i])) { first = i; break; }
+            for (int i = n - 1; i >= 0; --i) if (!foreign(tl[i])) { last = i; break; }
+            bool clean = last >= first;
+            for (int i = first; i <= last && clean; ++i) clean = !foreign(tl[i]);
+            if (!clean) { d.sh_front[cls] = n; d.sh_back[cls] = 0; continue; }
+            d.sh_front[cls] = first; d.sh_back[cls] = n - 1 - last;
+        }
+        HaloPlan& h = e->halo;
+        auto rows_of = [&](int k, size_t& off, size_t& n) { off = 3 * (size_t)pose_grp_ptr[k] * ROW_ALIGN; n = 3 * (size_t)(pose_grp_ptr[k + 1] - pose_grp_ptr[k]) * ROW_ALIGN; };
+        if (rk > 0) { rows_of(kb[rk], h.lo_send, h.lo_send_n); rows_of(kb[rk] - 1, h.lo_recv, h.lo_recv_n); }
+        if (rk < Wn - 1) { rows_of(kb[rk + 1] - 1, h.hi_send, h.hi_send_n); rows_of(kb[rk + 1], h.hi_recv, h.hi_recv_n); }
+        d.fused = 0; d.ecd = 0; d.hier = 1;                         // always the two-kernel PCG, reductions over the ranks
+    }
+    if (d.row_hi <= 0) { d.row_lo = 0; d.row_hi = n_rows; }         // (as carve: every row)
+    const int row_lo = d.row_lo, row_hi = d.row_hi;
     d.ec_on = 1; d.plain = 1;
     d.lin_rb = ROW_ALIGN / (64 / T);
-    d.ec_nsp = n_sp; d.ec_ndm = n_dm;
-    d.ec_nblk = std::min((n_sp + n_dm + BLK - 1) / BLK, 2048);
-    e->pack_rows = n_rows;
+    d.ec_nsp = ec_nsp; d.ec_ndm = ec_ndm;
+    d.ec_nblk = std::min((ec_nsp + ec_ndm + BLK - 1) / BLK, 2048);
+    e->pack_rows = pack_hi - pack_lo;
     if (tm) fprintf(stderr, "[nrs] device pack: tiles %d x %d rows, halo rows: max %d, mean %.1f, spring part max %d, classes %d (cap %d/%d) + %d (cap %d/%d)\n", n_tiles, d.tile_rows,
                     d.max_halo, (double)n_halo / n_tiles, d.max_halo_s, d.n_tiles_cls[0], d.cap_h[0], d.cap_s[0], d.n_tiles_cls[1], d.cap_h[1], d.cap_s[1]);
     // ---- arena
@@ -747,8 +901,8 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     std::vector<Pose> poses(s.poses, s.poses + K);
     NRS_HIP(c, hipMemcpyAsync(d.pose_init, poses.data(), sizeof(Pose) * K, hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemsetAsync(d.pose_fixed, 0, K, st));
-    NRS_HIP(c, hipMemsetAsync(d.row_tp, 0xFF, sizeof(uint32_t) * (size_t)n_rows, st));
-    hipLaunchKernelGGL((k_dp_halo<1>), dim3(n_tiles), dim3(256), 0, st, d.tile_rows, T, reinterpret_cast<uint16_t*>(d.row_tp), d.ss_ptr, d.sd_ptr, S_other, S_side, D_o, D_role, hs, hns, d.halo_ptr,
+    NRS_HIP(c, hipMemsetAsync(d.row_tp + row_lo, 0xFF, sizeof(uint32_t) * (size_t)(row_hi - row_lo), st));
+    hipLaunchKernelGGL((k_dp_halo<1>), dim3(tb1 - tb0), dim3(256), 0, st, tb0, (int*)nullptr, (int*)nullptr, d.tile_rows, T, reinterpret_cast<uint16_t*>(d.row_tp), d.ss_ptr, d.sd_ptr, S_other, S_side, D_o, D_role, hs, hns, d.halo_ptr,
                        d.halo_rows, d.s_om, d.d_hdr, d_flag);
     if (d.fused) {
         std::vector<int> tile_desc(8 * (size_t)n_tiles, 0);
@@ -764,12 +918,23 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
         NRS_HIP(c, hipStreamSynchronize(st));                        // (tile_desc dies here)
     } else if (d.use_lds)
         hipLaunchKernelGGL(k_dp_halofix, dim3(n_tiles), dim3(BLK), 0, st, n_tiles, d.halo_ptr, d.halo_rows, d.halo_fix, HALO_FIX, -1);
-    hipLaunchKernelGGL(k_dp_rowdata, nb(n_rows), dim3(256), 0, st, n_rows, row_v, r_x, r_uv, d.rflag, d.uv, d.xl_init);
-    hipLaunchKernelGGL(k_dp_rowcnt, nb(n_rows), dim3(256), 0, st, n_rows, cnt_s, cnt_d, d.row_cnt);
-    hipLaunchKernelGGL(k_dp_eckeys, nb(std::max(n_sp, n_dm)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, vrow, ek_s, ek_d);
-    tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, ek_s, ek_s2, (size_t)n_sp, 0, 32 + row_bits, st));
-    tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, ek_d, ek_d2, (size_t)n_dm, 0, 32 + row_bits, st));
-    hipLaunchKernelGGL(k_dp_ecfill, nb(std::max(n_sp, n_dm)), dim3(256), 0, st, n_sp, ek_s2, r_sp, r_d0, n_dm, ek_d2, r_dm, r_w, vrow, d.ec_sp, d.ec_dm, d.ec_w);
+    hipLaunchKernelGGL(k_dp_rowdata, nb(row_hi - row_lo), dim3(256), 0, st, row_lo, row_hi, row_v, r_x, r_uv, d.rflag, d.uv, d.xl_init);
+    hipLaunchKernelGGL(k_dp_rowcnt, nb(row_hi - row_lo), dim3(256), 0, st, row_lo, row_hi, cnt_s, cnt_d, d.row_cnt);
+    if (!sh) {                                                       // (a rank sorted the keys of the edges it counts with its incidence keys)
+        hipLaunchKernelGGL(k_dp_eckeys, nb(std::max(n_sp, n_dm)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, vrow, ek_s, ek_d);
+        tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, ek_s, ek_s2, (size_t)n_sp, 0, 32 + row_bits, st));
+        tb = tmp_bytes; NRS_HIP(c, rocprim::radix_sort_keys(tmp, tb, ek_d, ek_d2, (size_t)n_dm, 0, 32 + row_bits, st));
+    }
+    if (ec_nsp + ec_ndm > 0)
+        hipLaunchKernelGGL(k_dp_ecfill, nb(std::max(ec_nsp, ec_ndm)), dim3(256), 0, st, ec_nsp, ek_s2, r_sp, r_d0, ec_ndm, ek_d2, r_dm, r_w, vrow, d.ec_sp, d.ec_dm, d.ec_w);
+    if (sh) {                                                        // slots of other ranks' tiles are never written: zero for good (as engine_create)
+        NRS_HIP(c, hipMemsetAsync(d.part_lin, 0, sizeof(double) * 32 * (size_t)d.n_groups * (size_t)d.lin_rb, st));
+        NRS_HIP(c, hipMemsetAsync(d.part_rchi, 0, sizeof(double) * (size_t)d.n_groups, st));
+        NRS_HIP(c, hipMemsetAsync(d.part_reg, 0, sizeof(double) * 2 * (size_t)d.n_regblk, st));
+        NRS_HIP(c, hipMemsetAsync(d.part_spmv, 0, sizeof(double) * NPART * (size_t)d.n_regblk, st));
+        NRS_HIP(c, hipMemsetAsync(d.red, 0, sizeof(double) * (4 + 6 * (size_t)K), st));
+        NRS_HIP(c, hipMemsetAsync(d.red_loc, 0, sizeof(double) * (4 + 6 * (size_t)K), st));
+    }
     NRS_HIP(c, hipMemsetAsync(d.s_qc, 0, sizeof(double) * nnz_s, st));
     NRS_HIP(c, hipMemsetAsync(d.d_s, 0, sizeof(double) * nnz_d, st));
     NRS_HIP(c, hipMemsetAsync(d.part_apply, 0, sizeof(double) * (size_t)d.n_vecblk, st));
@@ -780,6 +945,10 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     e->vrow.swap(h_vrow);
     e->h_rflag.assign(n_rows, RF_FIXED);
     for (int v = 0; v < M; ++v) e->h_rflag[e->vrow[v]] = RF_OBS | RF_REPROJ_ACTIVE;
+    if (row_hi - row_lo < n_rows) {                                  // (a row-limited rank: the residual taps stage the observations of every row from here)
+        e->h_uv.assign(2 * (size_t)n_rows, 0.f);
+        for (int v = 0; v < M; ++v) { e->h_uv[2 * (size_t)e->vrow[v]] = s.uv[2 * (size_t)v]; e->h_uv[2 * (size_t)e->vrow[v] + 1] = s.uv[2 * (size_t)v + 1]; }
+    }
     e->h_pose_fixed.assign(K, 0);
     e->dev_edges = true;                                             // residual taps copy the raw edges from the pack scratch (device to device)
     e->raw_sp = r_sp; e->raw_d0 = r_d0; e->raw_dm = r_dm; e->raw_w = r_w;
