@@ -166,7 +166,8 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *   PCG / packing NRS_NO_LDS, NRS_NO_FUSED, NRS_FUSED_MAX_ROWS=<n>, NRS_NO_COARSE, NRS_COARSE_MIN_TILES=<n>, NRS_NO_ONE_XCD, NRS_NO_ECD, NRS_HIER,
  *                 NRS_NO_PLAIN, NRS_NO_H4, NRS_RC=<0..3>, NRS_NT=0|1, NRS_DFORM, NRS_NO_EDGE_CHI, NRS_SELL_T=<lanes>, NRS_NO_MORTON,
  *                 NRS_NO_TILE_SORT, NRS_ONE_CLASS, NRS_TILE_CUT_PCT=<p>, NRS_HOST_PACK, NRS_HOST_THREADS=<n>, NRS_HOST_THREADS_SMALL=<n>,
- *                 NRS_SKIN_OP_OWN_LAUNCH, NRS_SKIN_ROWS_OWN_LAUNCH, NRS_PCG_RTOL=<r> (experiments)
+ *                 NRS_SKIN_OP_OWN_LAUNCH, NRS_SKIN_ROWS_OWN_LAUNCH, NRS_PCG_RTOL=<r> (experiments), NRS_SHARD_EMBWIN_DEVICE (a rank of a
+ *                 communicator builds its share of nrs_dba_solve_window_embedded's lists on its device; off: the host builder)
  *   embedded BA   NRS_KFT_TWO_LAUNCHES (a sweep step of the keyframe-block factorisation as two launches), NRS_KFT_SCALAR_SWEEP (the pivot
  *                 block's sweep in the 4-pivot register form), NRS_KFT_FOUR_WAVES (panel workgroups without the four helper waves), NRS_KFT_NO_RESIDUAL_TEST (M^-1 applied again after the first PCG step
  *                 instead of the step's residual tested on its own)
@@ -271,14 +272,25 @@ int nrs_dba_window_edges(nrs_ctx* ctx, int32_t* n_spring, int32_t* sp_ij, float*
  * returns are built on the device (csrc/nrs_engine_embwin.hpp: index for index, the fp64 weights to the last bit), copied to the
  * host and handed to the set-up nrs_dba_upload_embedded runs; then optimize(iters) and the download.  There is no size threshold.
  * The host construction (nrs_dba_build_edges_embedded, the same lists) is taken with a communicator on the context, under
- * NRS_HOST_PACK=1 and for a window whose neighbour lists are empty.  Arguments are checked as for nrs_dba_solve_window, and is_node
+ * NRS_HOST_PACK=1 and for a window whose neighbour lists are empty.  A communicator takes the host builder BY DEFAULT; with
+ * NRS_SHARD_EMBWIN_DEVICE=1 on the context (nrs_debug_set; collective; at most 8 ranks, no more ranks than keyframes) every rank
+ * builds the lists on its own device over the same inputs and keeps the skinned observations of ITS keyframes only: node copies,
+ * springs, dampers and sk_obs whole, sk_node / sk_omega and the gathered per-observation data for the slice
+ * [sk_base, sk_base + sk_held) of the skinned list -- staging, host memory and set-up work of a rank follow its share (unmeasured on
+ * hardware).  The set-up adds no collective; a rank that does not qualify takes the host construction on its own, with the same
+ * bits in the solve.  Arguments are checked as for nrs_dba_solve_window, and is_node
  * must not be null; a NODE listed twice in one keyframe (which the reference cannot produce, frame.h:108-123, and on which a
  * sequential and a parallel walk would differ) is NRS_ERR_INVALID as well.  After an error nothing is resident.
  * On return the window is resident as after nrs_dba_upload_embedded (reset / optimize / download / download_skinned /
  * nrs_debug_kft), and obs_xyz holds, cast to float: the optimised position of every node copy, the skinned position of every
  * skinned observation; observations that reach no node copy are unchanged.
  *   nrs_dba_window_edges_embedded  parity tap: the lists of the resident window (null arrays: the four counts only); *on_device = 1
- *                                  when the device built them; NRS_ERR_STATE when the resident window was not made by this call */
+ *                                  when the device built them; NRS_ERR_STATE when the resident window was not made by this call.
+ *                                  On a rank of a communicator that built its share on the device the counts are the window's, sk_obs is
+ *                                  whole, and sk_node / sk_omega hold the rank's sk_held rows (the window's rows from sk_base on)
+ *   nrs_dba_window_slice_embedded  of the resident window: out[0] sk_base, [1] sk_held, [2] / [3] the rank's keyframes [k0, k1),
+ *                                  [4] bytes of the lists' staging, [5] bytes the five sliced skinned arrays take of it (padding
+ *                                  included); a whole window: 0, n_skin, 0, n_kf */
 int nrs_dba_solve_window_embedded(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* poses_qt /* in/out */,
                                   const int32_t* kf_rowptr, const int32_t* kf_pt, float* obs_xyz /* n_obs x 3, in/out */, const float* obs_uv,
                                   int32_t n_points, const uint8_t* is_node, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
@@ -286,6 +298,7 @@ int nrs_dba_solve_window_embedded(nrs_ctx* ctx, const nrs_camera* cam, int32_t n
 int nrs_dba_window_edges_embedded(nrs_ctx* ctx, int32_t* on_device, int32_t* n_lm, int32_t* lm_obs, int32_t* n_spring, int32_t* sp_ij,
                                   float* sp_d0, int32_t* n_damper, int32_t* dm_idx, float* dm_w, int32_t* n_skin, int32_t* sk_obs,
                                   int32_t* sk_node, double* sk_omega);
+int nrs_dba_window_slice_embedded(nrs_ctx* ctx, int64_t out[6]);
 
 /* Device-resident form of the same solve (used by bench.py so that the timed region starts with
  * the inputs already in HBM): upload once, then any number of {reset, optimize}. */
@@ -392,7 +405,9 @@ int nrs_shi_buffers(nrs_ctx* ctx, float* scores, int16_t* xgrad, int16_t* ygrad)
  * nrs_shard_plan on the node copies' lm_kf, a rank holds the skinned observations of its own keyframes only (they reach node copies
  * of their own keyframe, so no halo row), and their pose blocks, chi2, max diagonal and PCG shares travel in the packets above.
  * The solve is the block-Jacobi PCG (nrs_options.embedded_solver).  nrs_dba_download_skinned and nrs_dba_solve_embedded are
- * collective as well: every rank returns the same bits.
+ * collective as well: every rank returns the same bits (the skinned points are evaluated on the device, each rank its own, into a
+ * vector of the window's observations that is summed over the ranks where it stands).  nrs_dba_solve_window_embedded on a
+ * communicator builds each rank's share of the lists on its device under NRS_SHARD_EMBWIN_DEVICE=1 (above).
  * RCCL is bound at run time (dlopen): librccl must be loadable only if nrs_comm_init_rccl is used.   */
 #define NRS_COMM_ID_BYTES 128
 int nrs_comm_unique_id(uint8_t* id, int32_t capacity /* >= NRS_COMM_ID_BYTES */);      /* rank 0; broadcast by the caller */
@@ -407,6 +422,8 @@ int nrs_dba_stats(nrs_ctx* ctx, int64_t stats[5]);
 /* keyframe ranges: rank r owns keyframes kf_begin[r] .. kf_begin[r+1]-1 (balanced by padded landmark
  * rows, every rank at least one keyframe).  Host only, needs no device. */
 int nrs_shard_plan(int32_t n_kf, int32_t n_lm, const int32_t* lm_kf, int32_t world, int32_t* kf_begin /* world+1 */);
+/* the same ranges from the number of vertices of every keyframe (what a rank of nrs_dba_solve_window_embedded derives on its device) */
+int nrs_shard_plan_counts(int32_t n_kf, const int32_t* kf_vertices, int32_t world, int32_t* kf_begin /* world+1 */);
 /* Test harness: ranks are threads of one process, their contexts on the same GPU; rendezvous on the
  * host.  Runs the sharded arithmetic on a 1-GPU box. */
 int nrs_local_group_create(int32_t world /* <= 8 */, void** group);

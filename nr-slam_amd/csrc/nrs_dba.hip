@@ -32,7 +32,10 @@ void ba_constants(EngineSpec& s, float scale) {
 
 using namespace nrs;
 
-struct SkinIn { int32_t n = 0; const int32_t* kf = nullptr; const float* uv = nullptr; const float* xyz = nullptr; const int32_t* node = nullptr; const double* omega = nullptr; };
+struct SkinIn {
+    int32_t n = 0; const int32_t* kf = nullptr; const float* uv = nullptr; const float* xyz = nullptr; const int32_t* node = nullptr; const double* omega = nullptr;
+    int32_t total = 0, base = 0, k0 = 0, k1 = 0;                     // total > 0: a rank's slice of the window's list (EngineSpec sk_total / sk_base / sk_k0 / sk_k1)
+};
 
 static int dba_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt,
                       int32_t n_lm, const float* lm_xyz, const int32_t* lm_kf, const float* lm_uv,
@@ -72,9 +75,10 @@ static int dba_upload(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const dou
     s.spring_form = 0;                  // PositionRegularizer Jacobian as written (position_regularizer.cc:51-60)
     s.shard = true;                     // with a communicator on the context: one window over its ranks (include/nrs.h)
     std::vector<double> sk_X0;
-    if (sk.n > 0) {                     // embedded window (N2b): observations of points without a vertex
-        sk_X0.resize(3 * (size_t)sk.n);
-        for (size_t i = 0; i < sk_X0.size(); ++i) sk_X0[i] = (double)sk.xyz[i];
+    if (sk.n > 0 || sk.total > 0) {     // embedded window (N2b): observations of points without a vertex
+        sk_X0.resize(3 * (size_t)sk.n + 3);                          // (+ slack: an empty slice still needs a non-null array)
+        for (size_t i = 0; i < 3 * (size_t)sk.n; ++i) sk_X0[i] = (double)sk.xyz[i];
+        s.sk_total = sk.total; s.sk_base = sk.base; s.sk_k0 = sk.k0; s.sk_k1 = sk.k1;
         s.n_skin = sk.n; s.sk_uv = sk.uv; s.sk_X0 = sk_X0.data(); s.sk_node = sk.node; s.sk_om = sk.omega; s.sk_pose = sk.kf;
     }
     // rank-local checks and allocations can fail on one rank only: the ranks agree before the first collective
@@ -308,8 +312,13 @@ extern "C" int nrs_dba_window_edges(nrs_ctx* c, int32_t* n_spring, int32_t* sp_i
 }
 
 // ---- the EMBEDDED window in one call (include/nrs.h): the lists of nrs_dba_build_edges_embedded built on the device
-// (csrc/nrs_engine_embwin.hpp), handed to the set-up nrs_dba_upload_embedded runs, then optimize(iters) and the download.  A communicator
-// on the context, NRS_HOST_PACK=1 or empty neighbour lists take nrs_dba_build_edges_embedded instead: the same lists.
+// (csrc/nrs_engine_embwin.hpp), handed to the set-up nrs_dba_upload_embedded runs, then optimize(iters) and the download.
+// NRS_HOST_PACK=1 or empty neighbour lists take nrs_dba_build_edges_embedded instead: the same lists.  So does a communicator, unless
+// NRS_SHARD_EMBWIN_DEVICE=1 is set on the context (the host builder stays the default there: tests/test_gpu_embedded_window.py holds a
+// communicator to on_device = 0 and whole lists from the tap).  With the switch every rank
+// builds on its own device and keeps the skinned observations of its own keyframes only (a sliced list through the set-up); as in
+// window_upload, whatever happens after the validation may happen on one rank alone, so every rank reaches exactly ONE agreement: after
+// a failed device build, or in the upload (a rank that does not qualify takes the host builder on its own: the same bits).
 static int embwin_build_host(nrs_ctx* c, int32_t n_kf, const int32_t* kf_rowptr, const int32_t* kf_pt, const int32_t* obs_kf, const float* obs_xyz, const float* obs_uv,
                              int32_t n_points, const uint8_t* is_node, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w, const float* nbr_d0,
                              const int32_t* nbr_status, EmbWindow* w) {
@@ -326,7 +335,8 @@ static int embwin_build_host(nrs_ctx* c, int32_t n_kf, const int32_t* kf_rowptr,
                                           &nd, nullptr, nullptr, &nk, nullptr, nullptr, nullptr);
     if (rc != NRS_OK) return c->fail(rc, "nrs_dba_build_edges_embedded failed");
     w->on_device = 0; w->n_obs = kf_rowptr[n_kf]; w->n_lm = nl; w->n_sp = ns; w->n_dm = nd; w->n_skin = nk;
-    w->host.assign(embwin_bytes(nl, ns, nd, nk), 0);
+    w->sk_base = 0; w->sk_held = nk; w->k0 = 0; w->k1 = n_kf;
+    w->host.assign(embwin_bytes(nl, ns, nd, nk, nk), 0);
     embwin_bind(w, w->host.data());
     rc = nrs_dba_build_edges_embedded(n_kf, kf_rowptr, kf_pt, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, &nl, w->lm_obs, &ns, w->sp_ij, w->sp_d0,
                                       &nd, w->dm_idx, w->dm_w, &nk, w->sk_obs, w->sk_node, w->sk_omega);
@@ -364,16 +374,26 @@ extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, 
         t_prev = now;
     };
     std::unique_ptr<EmbWindow> w(new EmbWindow);
-    if (!c->comm && !c->env("NRS_HOST_PACK") && nbr_rowptr[n_points] > 0) {
+    // (more ranks than keyframes, more than 8 ranks: the set-up refuses those alike on every rank -- reached through the host builder)
+    const bool shard = c->comm && c->env("NRS_SHARD_EMBWIN_DEVICE") && c->comm->world <= 8 && n_kf >= c->comm->world;
+    if ((!c->comm || shard) && !c->env("NRS_HOST_PACK") && nbr_rowptr[n_points] > 0) {
         bool duplicate = false;
-        NRS_TRY(engine_build_embedded_window_device(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0,
-                                                    nbr_status, w.get(), &duplicate));
+        int rc = engine_build_embedded_window_device(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0,
+                                                     nbr_status, shard, w.get(), &duplicate);
+        if (rc != NRS_OK) { (void)comm_agree(c, rc); return rc; }
+        // (decided from identical inputs: the same refusal on every rank, before any agreement)
         if (duplicate) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_embedded: a map point is listed twice in one keyframe");
     } else
         NRS_TRY(embwin_build_host(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, w.get()));
     mark("construction");
-    NRS_TRY(nrs_dba_upload_embedded(c, cam, n_kf, poses_qt, w->n_lm, w->lm_xyz, w->lm_kf, w->lm_uv, w->n_sp, w->sp_ij, w->sp_d0, w->n_dm, w->dm_idx, w->dm_w, w->n_skin,
-                                    w->sk_kf, w->sk_uv, w->sk_xyz, w->sk_node, w->sk_omega, scale));
+    if (w->on_device && shard) {                                     // this rank's slice of the skinned list (valid by construction)
+        SkinIn sk;
+        sk.n = w->sk_held; sk.kf = w->sk_kf; sk.uv = w->sk_uv; sk.xyz = w->sk_xyz; sk.node = w->sk_node; sk.omega = w->sk_omega;
+        sk.total = w->n_skin; sk.base = w->sk_base; sk.k0 = w->k0; sk.k1 = w->k1;
+        NRS_TRY(dba_upload(c, cam, n_kf, poses_qt, w->n_lm, w->lm_xyz, w->lm_kf, w->lm_uv, w->n_sp, w->sp_ij, w->sp_d0, w->n_dm, w->dm_idx, w->dm_w, scale, sk));
+    } else
+        NRS_TRY(nrs_dba_upload_embedded(c, cam, n_kf, poses_qt, w->n_lm, w->lm_xyz, w->lm_kf, w->lm_uv, w->n_sp, w->sp_ij, w->sp_d0, w->n_dm, w->dm_idx, w->dm_w, w->n_skin,
+                                        w->sk_kf, w->sk_uv, w->sk_xyz, w->sk_node, w->sk_omega, scale));
     c->dba_embwin = w.release();
     const EmbWindow& r = *c->dba_embwin;
     if (tm) (void)hipStreamSynchronize(c->stream);
@@ -407,8 +427,23 @@ extern "C" int nrs_dba_window_edges_embedded(nrs_ctx* c, int32_t* on_device, int
     if (dm_idx) memcpy(dm_idx, r.dm_idx, sizeof(int32_t) * 4 * (size_t)r.n_dm);
     if (dm_w) memcpy(dm_w, r.dm_w, sizeof(float) * (size_t)r.n_dm);
     if (sk_obs) memcpy(sk_obs, r.sk_obs, sizeof(int32_t) * (size_t)r.n_skin);
-    if (sk_node) memcpy(sk_node, r.sk_node, sizeof(int32_t) * 11 * (size_t)r.n_skin);
-    if (sk_omega) memcpy(sk_omega, r.sk_omega, sizeof(double) * 11 * (size_t)r.n_skin);
+    if (sk_node) memcpy(sk_node, r.sk_node, sizeof(int32_t) * 11 * (size_t)r.sk_held);          // (a sliced rank: its rows, nrs_dba_window_slice_embedded)
+    if (sk_omega) memcpy(sk_omega, r.sk_omega, sizeof(double) * 11 * (size_t)r.sk_held);
+    return NRS_OK;
+}
+
+extern "C" int nrs_dba_window_slice_embedded(nrs_ctx* c, int64_t out[6]) {
+    if (!c || !out) return NRS_ERR_INVALID;
+    if (!c->dba || !c->dba_embwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_embedded");
+    const EmbWindow& r = *c->dba_embwin;
+    out[0] = r.sk_base; out[1] = r.sk_held; out[2] = r.k0; out[3] = r.k1; out[4] = (int64_t)r.bytes; out[5] = (int64_t)r.sk_bytes;
+    return NRS_OK;
+}
+
+extern "C" int nrs_shard_plan_counts(int32_t n_kf, const int32_t* kf_vertices, int32_t world, int32_t* kf_begin) {
+    if (n_kf <= 0 || !kf_vertices || world < 1 || world > n_kf || !kf_begin) return NRS_ERR_INVALID;
+    for (int k = 0; k < n_kf; ++k) if (kf_vertices[k] < 0) return NRS_ERR_INVALID;
+    for (int r = 0; r < world; ++r) { int k0, k1; embwin_own_range(n_kf, kf_vertices, world, r, &k0, &k1); kf_begin[r] = k0; kf_begin[r + 1] = k1; }
     return NRS_OK;
 }
 

@@ -51,6 +51,11 @@ struct EngineSpec {
     const double* sk_om = nullptr;        // n_skin x 11 normalised weights
     const int* sk_pose = nullptr;         // n_skin pose index of every observation (null: pose 0); BA windows (K >= 1, PCG path): the point sits at
                                           // X0 + sum_k om[k] (x[node[k]] - x_start[node[k]]) -- N2b, oracle/embedded_oracle.py dba_solve_embedded
+    // a SLICED skinned list (a rank of a sharded embedded window whose lists were built on its device): sk_total > 0 is the window's
+    // count, the n_skin entries given are the window's [sk_base, sk_base + n_skin) -- the observations of keyframes [sk_k0, sk_k1), which
+    // must be the rank's own range (n_skin = 0: none, the arrays still non-null).  sk_total = 0: the whole list, as ever
+    int sk_total = 0, sk_base = 0, sk_k0 = 0, sk_k1 = 0;
+    int sk_window() const { return sk_total > 0 ? sk_total : n_skin; }   // skinned observations of the WINDOW
     bool shard = false;                   // split the poses over the ranks of the context's communicator (BA windows only)
     bool force_gather = false;            // stored-block operator (k_spmv gather path) instead of the LDS-staged factored one
     bool edges_on_device = false;         // sp_ij / sp_d0 / dm_idx / dm_w are DEVICE pointers (engine_build_edges_device): plain BA windows only
@@ -74,26 +79,31 @@ int engine_pack_hash(nrs_ctx* c, Engine* e, uint64_t* out /*24*/);
 // embedded mode: levels of the skinned observations (1 = level 0) / their chi2 = r^T Omega r at the current estimate
 int engine_skin_set_active(nrs_ctx* c, Engine* e, const uint8_t* active);
 int engine_skin_chi2(nrs_ctx* c, Engine* e, double* chi /*n_skin*/);
-int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz /*n_skin x 3*/);   // embedded BA windows: the skinned points at the current estimate (collective when sharded)
+int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz /*window's n_skin x 3*/);   // embedded BA windows: the skinned points at the current estimate, k_skin_positions (collective when sharded)
 int engine_skin_stats(const Engine* e, int64_t out[3]);            // skinned observations held here, their padded slots, skin-buffer bytes; NRS_ERR_STATE: none resident
 // OPT:927-1137's edge construction on the device (index for index what nrs_dba_build_edges returns); arrays live in ctx scratch
 int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
                               const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out);
 // embedded window in one call (nrs_engine_embwin.hpp): node copies, springs / dampers over node-copy indices, skinned observations and
 // the per-observation data gathered for both; the arrays sit in ONE blob laid out by embwin_layout (host: `host`, device-built: the
-// context's pinned staging)
+// context's pinned staging).  A rank of a sharded window builds its share only: sk_obs whole (n_skin), the heavy skinned arrays (sk_node,
+// sk_omega, sk_xyz, sk_uv, sk_kf) hold the sk_held observations from sk_base on -- those of the rank's keyframes [k0, k1)
 struct EmbWindow {
     int on_device = 0, n_obs = 0, n_lm = 0, n_sp = 0, n_dm = 0, n_skin = 0;
+    int sk_base = 0, sk_held = 0, k0 = 0, k1 = 0;                 // (a whole window: 0, n_skin, 0, n_kf)
+    size_t bytes = 0, sk_bytes = 0;                               // the blob; the five sliced arrays' part of it
     int *lm_obs = nullptr, *sp_ij = nullptr, *dm_idx = nullptr, *sk_obs = nullptr, *sk_node = nullptr, *lm_kf = nullptr, *sk_kf = nullptr;
     float *sp_d0 = nullptr, *dm_w = nullptr, *lm_xyz = nullptr, *lm_uv = nullptr, *sk_xyz = nullptr, *sk_uv = nullptr;
     double* sk_omega = nullptr;
     std::vector<char> host;
 };
-size_t embwin_bytes(int n_lm, int n_sp, int n_dm, int n_skin);
-void embwin_bind(EmbWindow* w, char* base);                       // the pointers of w for its counts, into a blob of embwin_bytes
+size_t embwin_bytes(int n_lm, int n_sp, int n_dm, int n_skin, int sk_held);
+void embwin_bind(EmbWindow* w, char* base);                       // the pointers of w for its counts, into a blob of embwin_bytes; sets w->bytes / sk_bytes
+// the keyframes [k0, k1) of rank `rank` of `world` from the per-keyframe node-copy counts: the shard_plan call of the set-up
+void embwin_own_range(int n_kf, const int* kf_nodes, int world, int rank, int* k0, int* k1);
 int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
                                         int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
-                                        const int* nbr_status, EmbWindow* out, bool* duplicate);
+                                        const int* nbr_status, bool own_only, EmbWindow* out, bool* duplicate);   // own_only: the share of the context's rank
 bool engine_device_pack_ok(nrs_ctx* c, const EngineSpec& s);      // would engine_create build this window on the device?
 int engine_edges_to_host(nrs_ctx* c, Engine* e, int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w);   // parity tap of the device edge builder    // checksums of the packed arrays (host- or device-built)       // solver order, caller vertex order
 // parity tap: (H + lam I) x = b for explicitly given blocks (one pose, M landmark rows, no regularisers) through

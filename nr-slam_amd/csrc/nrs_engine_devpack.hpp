@@ -523,7 +523,7 @@ static bool devpack_eligible(nrs_ctx* c, const EngineSpec& s, int n_pad_rows) {
         return false;                                                // (test / A-B switches are honoured by the host path)
     // a communicator: one window over its ranks, with a rank count the sharded path accepts (engine_create has refused the others)
     if (c->comm && (!s.shard || c->comm->world > 8 || s.K < c->comm->world)) return false;
-    if (s.X0 || s.n_un || s.sp_active || s.dm_active || s.pose_fixed || s.force_gather || s.n_skin > 0) return false;
+    if (s.X0 || s.n_un || s.sp_active || s.dm_active || s.pose_fixed || s.force_gather || s.sk_window() > 0) return false;
     if (s.K < 2 || n_pad_rows < 2048 || s.delta_pos > 0 || s.spring_form != 0 || s.n_dm <= 0 || s.n_sp <= 0) return false;   // (single-frame problems: a2, host)
     if (4 * (int64_t)s.n_dm >= 0xFFFFFFFFLL || (int64_t)n_pad_rows >= 0x7FFFFFFFLL) return false;
     return true;

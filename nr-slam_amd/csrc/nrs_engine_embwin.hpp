@@ -20,6 +20,14 @@
 // changes while it walks the keyframe, this one is complete before any walk starts.  The reference cannot produce the case
 // (frame.h:108-123 maps id to index one to one), so it is detected here and reported (*duplicate = true; the entry point returns
 // NRS_ERR_INVALID before any solver launch): a node copy whose own index is not the one left in `cur` is such a duplicate.
+// SHARDED WINDOWS.  Every rank of a communicator runs this on its own device over identical inputs.  Numbering, `cur`, the duplicate
+// check, the count pass and the scans cover the whole window (cheap; every rank gets the same counts and the same slots); with the
+// totals come the node-copy and skinned-observation offsets at the keyframe boundaries (k_ew_kf_bounds), from which the rank takes its
+// keyframes [k0, k1) -- the set-up's own shard_plan call on the per-keyframe node-copy counts (embwin_own_range) -- and the slice
+// [sk_base, sk_base + sk_held) of the skinned list that belongs to them (observations are in keyframe order, so is the list).  Node
+// copies, springs, dampers and sk_obs (4 bytes an observation: the caller's scatter goes through it) are emitted whole; sk_node,
+// sk_omega, sk_xyz, sk_uv and sk_kf -- 156 of the 160 bytes of a skinned observation -- for the slice only, at slot - sk_base.  The blob,
+// its device scratch and the pinned staging are sized from sk_held.
 // The lists end up in pinned host memory of the context (one copy back), laid out by embwin_layout, and are handed to the set-up
 // nrs_dba_upload_embedded runs (nrs_engine_setup.hpp reads host arrays).  Plain C++ and vector stores only; the only atomic is the
 // atomicMax on `cur`, as in k_win_cur.
@@ -29,20 +37,32 @@ namespace nrs {
 
 // byte offsets of the 14 arrays of an EmbWindow in one blob (device scratch, pinned mirror and host storage share the layout)
 enum { EW_SK_OMEGA, EW_LM_OBS, EW_SP_IJ, EW_SP_D0, EW_DM_IDX, EW_DM_W, EW_SK_OBS, EW_SK_NODE, EW_LM_XYZ, EW_LM_UV, EW_LM_KF, EW_SK_XYZ, EW_SK_UV, EW_SK_KF, EW_N };
-static size_t embwin_layout(int n_lm, int n_sp, int n_dm, int n_skin, size_t off[EW_N]) {
-    const size_t bytes[EW_N] = {88 * (size_t)n_skin, 4 * (size_t)n_lm, 8 * (size_t)n_sp, 4 * (size_t)n_sp, 16 * (size_t)n_dm, 4 * (size_t)n_dm, 4 * (size_t)n_skin,
-                                44 * (size_t)n_skin, 12 * (size_t)n_lm, 8 * (size_t)n_lm, 4 * (size_t)n_lm, 12 * (size_t)n_skin, 8 * (size_t)n_skin, 4 * (size_t)n_skin};
-    size_t o = 0;
-    for (int i = 0; i < EW_N; ++i) { off[i] = o; o += ((bytes[i] + 255) / 256) * 256 + 256; }
+// (sk_obs has the window's n_skin entries, the other skinned arrays the sk_held entries of this blob: all of them, or a rank's slice)
+static size_t embwin_layout(int n_lm, int n_sp, int n_dm, int n_skin, int sk_held, size_t off[EW_N], size_t* sk_bytes = nullptr) {
+    const size_t bytes[EW_N] = {88 * (size_t)sk_held, 4 * (size_t)n_lm, 8 * (size_t)n_sp, 4 * (size_t)n_sp, 16 * (size_t)n_dm, 4 * (size_t)n_dm, 4 * (size_t)n_skin,
+                                44 * (size_t)sk_held, 12 * (size_t)n_lm, 8 * (size_t)n_lm, 4 * (size_t)n_lm, 12 * (size_t)sk_held, 8 * (size_t)sk_held, 4 * (size_t)sk_held};
+    size_t o = 0, sk = 0;
+    for (int i = 0; i < EW_N; ++i) {
+        const size_t b = ((bytes[i] + 255) / 256) * 256 + 256;
+        off[i] = o; o += b;
+        if (i == EW_SK_OMEGA || i == EW_SK_NODE || i == EW_SK_XYZ || i == EW_SK_UV || i == EW_SK_KF) sk += b;
+    }
+    if (sk_bytes) *sk_bytes = sk;
     return o;
 }
-size_t embwin_bytes(int n_lm, int n_sp, int n_dm, int n_skin) {
+size_t embwin_bytes(int n_lm, int n_sp, int n_dm, int n_skin, int sk_held) {
     size_t off[EW_N];
-    return embwin_layout(n_lm, n_sp, n_dm, n_skin, off);
+    return embwin_layout(n_lm, n_sp, n_dm, n_skin, sk_held, off);
+}
+void embwin_own_range(int n_kf, const int* kf_nodes, int world, int rank, int* k0, int* k1) {
+    std::vector<int> grp(n_kf + 1, 0), kb(world + 1, 0);
+    for (int k = 0; k < n_kf; ++k) grp[k + 1] = grp[k] + std::max(1, (kf_nodes[k] + ROW_ALIGN - 1) / ROW_ALIGN);   // (pose_grp_ptr of the set-up)
+    shard_plan(n_kf, grp.data(), world, kb.data());
+    *k0 = kb[rank]; *k1 = kb[rank + 1];
 }
 void embwin_bind(EmbWindow* w, char* base) {
     size_t off[EW_N];
-    (void)embwin_layout(w->n_lm, w->n_sp, w->n_dm, w->n_skin, off);
+    w->bytes = embwin_layout(w->n_lm, w->n_sp, w->n_dm, w->n_skin, w->sk_held, off, &w->sk_bytes);
     w->sk_omega = reinterpret_cast<double*>(base + off[EW_SK_OMEGA]);
     w->lm_obs = reinterpret_cast<int*>(base + off[EW_LM_OBS]); w->sp_ij = reinterpret_cast<int*>(base + off[EW_SP_IJ]);
     w->sp_d0 = reinterpret_cast<float*>(base + off[EW_SP_D0]); w->dm_idx = reinterpret_cast<int*>(base + off[EW_DM_IDX]);
@@ -73,12 +93,19 @@ __global__ void k_ew_totals(int n_obs, const int* __restrict__ lm_of, const int*
     if (blockIdx.x == 0 && threadIdx.x == 0) { tot[0] = lm_of[n_obs]; tot[1] = off_s[n_obs]; tot[2] = off_d[n_obs]; tot[3] = off_k[n_obs]; }
 }
 
+// lm_of / off_k at the keyframe boundaries: out[k] = node copies before keyframe k, out[n_kf + 1 + k] = skinned observations before it
+__global__ void k_ew_kf_bounds(int n_kf, const int* __restrict__ kf_rowptr, const int* __restrict__ lm_of, const int* __restrict__ off_k, int* out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k <= n_kf) { out[k] = lm_of[kf_rowptr[k]]; out[n_kf + 1 + k] = off_k[kf_rowptr[k]]; }
+}
+
 // One thread per observation i = (keyframe k, map point p); W.lm_k / W.kf_pt are per OBSERVATION here, W.cur the node-copy table.
-// EMIT = false: counts per observation; true: writes at the scanned offsets.
+// EMIT = false: counts per observation; true: writes at the scanned offsets.  Emitting, sk_node / sk_omega hold the skinned observations
+// of [i_lo, i_hi) only, from slot sk_lo on (a rank's keyframes; the whole window: 0, n_obs, 0); sk_obs is written for every one.
 template <bool EMIT>
 __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, const int* __restrict__ lm_of, int* cnt_s, int* cnt_d, int* cnt_k,
                           const int* __restrict__ off_s, const int* __restrict__ off_d, const int* __restrict__ off_k, int* lm_obs, int* sp_ij, float* sp_d0,
-                          int* dm_idx, float* dm_w, int* sk_obs, int* sk_node, double* sk_omega) {
+                          int* dm_idx, float* dm_w, int* sk_obs, int* sk_node, double* sk_omega, int i_lo, int i_hi, int sk_lo) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_obs) return;
@@ -86,6 +113,10 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
     const int* cur = W.cur + (size_t)k * W.n_points;
     const int lo = W.nbr_rowptr[p], hi = W.nbr_rowptr[p + 1];
     if (!flag[i]) {                                                  // a skinned observation: its walk accepts node copies
+        if (EMIT && (i < i_lo || i >= i_hi)) {                       // (another rank's: its place in sk_obs, which the count pass decided)
+            if (off_k[i + 1] != off_k[i]) sk_obs[off_k[i]] = i;
+            return;
+        }
         int n_reg = 0;
         double tot = 0.0;
         for (int e = lo; e < hi; ++e) {
@@ -96,8 +127,8 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
         }
         if (!EMIT) { cnt_s[i] = 0; cnt_d[i] = 0; cnt_k[i] = n_reg > 0 ? 1 : 0; return; }
         if (n_reg == 0) return;                                      // (no node copy within reach: the observation constrains nothing)
-        const size_t q = (size_t)off_k[i];
-        sk_obs[q] = i;
+        sk_obs[off_k[i]] = i;
+        const size_t q = (size_t)(off_k[i] - sk_lo);
         int j = 0;
         for (int e = lo; e < hi && j < n_reg; ++e) {                 // the same walk again: its first n_reg accepted entries
             const int o = W.nbr_col[e];
@@ -162,10 +193,10 @@ __global__ void k_ew_gather(int n_a, const int* __restrict__ obs_a, int n_b, con
 }
 
 // Builds the lists of an embedded window on the device and copies them to the context's pinned staging (out's pointers: valid until
-// the next call).  The arguments are validated by the caller (indices in range, nnz > 0).
+// the next call).  The arguments are validated by the caller (indices in range, nnz > 0; own_only: a communicator of at most n_kf ranks).
 int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
                                         int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
-                                        const int* nbr_status, EmbWindow* out, bool* duplicate) {
+                                        const int* nbr_status, bool own_only, EmbWindow* out, bool* duplicate) {
     *duplicate = false;
     const int n_obs = kf_rowptr[n_kf], nnz = nbr_rowptr[n_points];
     hipStream_t st = c->stream;
@@ -181,7 +212,7 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     };
     size_t tb = 0;
     (void)rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st);
-    int *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_flag, *d_lm, *d_cs, *d_cd, *d_ck, *d_os, *d_od, *d_ok, *d_tot;
+    int *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_flag, *d_lm, *d_cs, *d_cd, *d_ck, *d_os, *d_od, *d_ok, *d_tot, *d_krp, *d_kfb;
     float *d_w, *d_d0, *d_xyz, *d_uv;
     uint8_t* d_node;
     void* tmp;
@@ -194,6 +225,7 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
         d_cs = W.get<int>((size_t)n_obs + 1); d_cd = W.get<int>((size_t)n_obs + 1); d_ck = W.get<int>((size_t)n_obs + 1);
         d_os = W.get<int>((size_t)n_obs + 1); d_od = W.get<int>((size_t)n_obs + 1); d_ok = W.get<int>((size_t)n_obs + 1);
         d_tot = W.get<int>(8);
+        d_krp = W.get<int>((size_t)n_kf + 1); d_kfb = W.get<int>(2 * ((size_t)n_kf + 1));
         tmp = W.get<char>(tb + 256);
     };
     DpScratch dry{nullptr, 0, 0};
@@ -211,6 +243,7 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     NRS_HIP(c, hipMemcpyAsync(d_d0, nbr_d0, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemcpyAsync(d_xyz, obs_xyz, sizeof(float) * 3 * (size_t)n_obs, hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemcpyAsync(d_uv, obs_uv, sizeof(float) * 2 * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    if (own_only) NRS_HIP(c, hipMemcpyAsync(d_krp, kf_rowptr, sizeof(int) * ((size_t)n_kf + 1), hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemsetAsync(d_cur, 0xFF, sizeof(int) * (size_t)n_kf * n_points, st));
     NRS_HIP(c, hipMemsetAsync(d_flag + n_obs, 0, sizeof(int), st));
     NRS_HIP(c, hipMemsetAsync(d_cs + n_obs, 0, sizeof(int), st));
@@ -228,21 +261,33 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     // ---- count pass, scans
     WinDev wd{n_kf, n_points, nullptr, d_pt, d_k, d_nrp, d_col, d_st, d_w, d_d0, d_cur};
     hipLaunchKernelGGL((k_ew_walk<false>), g, b, 0, st, wd, n_obs, d_flag, d_lm, d_cs, d_cd, d_ck, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                       (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr);
+                       (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0, n_obs, 0);
     t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
     t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cd, d_od, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
     t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_ck, d_ok, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
     hipLaunchKernelGGL(k_ew_totals, dim3(1), dim3(64), 0, st, n_obs, d_lm, d_os, d_od, d_ok, d_tot);
+    if (own_only) hipLaunchKernelGGL(k_ew_kf_bounds, dim3((unsigned)((n_kf + 256) / 256)), b, 0, st, n_kf, d_krp, d_lm, d_ok, d_kfb);
     NRS_HIP(c, hipGetLastError());
     int tot[5] = {0, 0, 0, 0, 0};
+    std::vector<int> kfb(own_only ? 2 * ((size_t)n_kf + 1) : 0);
     NRS_HIP(c, hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    if (own_only) NRS_HIP(c, hipMemcpyAsync(kfb.data(), d_kfb, sizeof(int) * kfb.size(), hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipStreamSynchronize(st));
     mark("count + scans");
     if (tot[4]) { *duplicate = true; return NRS_OK; }
     out->n_obs = n_obs; out->n_lm = tot[0]; out->n_sp = tot[1]; out->n_dm = tot[2]; out->n_skin = tot[3];
+    out->sk_base = 0; out->sk_held = tot[3]; out->k0 = 0; out->k1 = n_kf;
+    if (own_only) {                                                  // this rank's keyframes and its slice of the skinned list
+        std::vector<int> kf_nodes(n_kf);
+        for (int k = 0; k < n_kf; ++k) kf_nodes[k] = kfb[k + 1] - kfb[k];
+        embwin_own_range(n_kf, kf_nodes.data(), c->comm->world, c->comm->rank, &out->k0, &out->k1);
+        out->sk_base = kfb[n_kf + 1 + out->k0]; out->sk_held = kfb[n_kf + 1 + out->k1] - out->sk_base;
+        if (out->k0 < 0 || out->k1 > n_kf || out->k0 >= out->k1 || out->sk_base < 0 || out->sk_held < 0 || out->sk_base + out->sk_held > tot[3])
+            return c->fail(NRS_ERR_STATE, "embedded lists: keyframe range [%d, %d) / slice [%d, +%d) of %d", out->k0, out->k1, out->sk_base, out->sk_held, tot[3]);
+    }
     // ---- emit pass and gathers into one blob, one copy back
     size_t off[EW_N];
-    const size_t bytes = embwin_layout(tot[0], tot[1], tot[2], tot[3], off);
+    const size_t bytes = embwin_layout(tot[0], tot[1], tot[2], tot[3], out->sk_held, off);
     NRS_TRY(c->ensure(c->pack_ws4, bytes + 4096));
     if (bytes > c->embwin_pin_cap) {
         if (c->embwin_pin) (void)hipHostFree(c->embwin_pin);
@@ -255,11 +300,11 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     EmbWindow dv = *out;
     embwin_bind(&dv, c->pack_ws4.as<char>());
     hipLaunchKernelGGL((k_ew_walk<true>), g, b, 0, st, wd, n_obs, d_flag, d_lm, (int*)nullptr, (int*)nullptr, (int*)nullptr, d_os, d_od, d_ok, dv.lm_obs, dv.sp_ij, dv.sp_d0,
-                       dv.dm_idx, dv.dm_w, dv.sk_obs, dv.sk_node, dv.sk_omega);
-    const int n_g = std::max(dv.n_lm, dv.n_skin);
+                       dv.dm_idx, dv.dm_w, dv.sk_obs, dv.sk_node, dv.sk_omega, kf_rowptr[dv.k0], kf_rowptr[dv.k1], dv.sk_base);
+    const int n_g = std::max(dv.n_lm, dv.sk_held);                   // (the gather of the skinned observations: the slice of sk_obs)
     if (n_g > 0)
-        hipLaunchKernelGGL(k_ew_gather, dim3((unsigned)((n_g + 255) / 256)), b, 0, st, dv.n_lm, dv.lm_obs, dv.n_skin, dv.sk_obs, d_xyz, d_uv, d_k, dv.lm_xyz, dv.lm_uv, dv.lm_kf,
-                           dv.sk_xyz, dv.sk_uv, dv.sk_kf);
+        hipLaunchKernelGGL(k_ew_gather, dim3((unsigned)((n_g + 255) / 256)), b, 0, st, dv.n_lm, dv.lm_obs, dv.sk_held, dv.sk_obs + dv.sk_base, d_xyz, d_uv, d_k, dv.lm_xyz,
+                           dv.lm_uv, dv.lm_kf, dv.sk_xyz, dv.sk_uv, dv.sk_kf);
     NRS_HIP(c, hipGetLastError());
     mark("emit + gathers");
     NRS_HIP(c, hipMemcpyAsync(c->embwin_pin, c->pack_ws4.as<char>(), bytes, hipMemcpyDeviceToHost, st));

@@ -401,7 +401,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     }
     if (s.edges_on_device) return c->fail(NRS_ERR_STATE, "device-built edge lists need the device-side construction, which this window does not qualify for");
     // a2's single-frame engines: the direct solver's symbolic phase needs the structure only and runs next to the packing below
-    if (s.n_skin > 0) {                                            // (checked HERE: the plan thread below indexes by these)
+    if (s.sk_window() > 0) {                                       // (checked HERE: the plan thread below indexes by these)
         if ((!(arena == &c->arena_trk && s.K == 1) && !s.sk_pose) || !s.sk_uv || !s.sk_X0 || !s.sk_node || !s.sk_om)
             return c->fail(NRS_ERR_INVALID, "skinned observations: single-frame tracking engines, or BA windows with a pose per observation");
         for (size_t q = 0; q < (size_t)SK_MAX * s.n_skin; ++q)
@@ -791,7 +791,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     // single-launch PCG iteration for problems that are bound by launch latency, not by traffic
     const int fused_max = c->env("NRS_FUSED_MAX_ROWS") ? atoi(c->env("NRS_FUSED_MAX_ROWS")) : 32768;
     d.fused = (d.use_lds && d.n_rows < fused_max && !c->env("NRS_NO_FUSED")) ? 1 : 0;
-    if (s.n_skin > 0) d.fused = 0;                                 // embedded mode: the skinned observations' operator kernels sit between the two launches of an iteration
+    if (s.sk_window() > 0) d.fused = 0;                            // embedded mode: the skinned observations' operator kernels sit between the two launches of an iteration
     d.hier = (d.n_regblk > 4096 || c->env("NRS_HIER")) ? 1 : 0;
     // (a profiling context times full operator launches only: no convergence-detecting early exits)
     d.ecd = (d.use_lds && !d.fused && !c->opt.profile && !c->env("NRS_NO_ECD")) ? 1 : 0;
@@ -977,7 +977,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     {
         Dev tmp = d;
         Engine te;
-        if (!e->nd) spec_pcg_sets(c, e, s.n_skin);                 // (a2's engines chose theirs above)
+        if (!e->nd) spec_pcg_sets(c, e, s.sk_window());            // (a2's engines chose theirs above)
         te.n_spec = e->n_spec; te.spec_pcg = e->spec_pcg;
         carve(dry, tmp, s.X0 != nullptr, nnz_s, nnz_d, ss_ptr.size() - 1, halo_rows.size(), &te);
     }
@@ -1156,7 +1156,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     engine_compact_headers(c, e);
     NRS_HIP(c, hipStreamSynchronize(c->stream));       // host staging vectors die here
     mark("pinned+sync");
-    if (s.n_skin > 0) {
+    if (s.sk_window() > 0) {
         // ---- embedded mode: the skinned observations (nrs_engine_skin.hpp; device arrays in a buffer of the context).  A BA window (N2b:
         // sk_pose given, K poses) solves by the PCG with the observations applied as hyper-edges; a single-frame engine (N2a) by the direct
         // solver when it takes the frame (k_nd_values folds them into its blocks) and by the same PCG form when it does not.
@@ -1165,10 +1165,17 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         // A rank of a sharded window (communicator) holds the observations of its OWN keyframes [sh_k0, sh_k0 + sh_nk) only: they reach
         // node copies of their own keyframe (checked below), so everything they read or write is rank-local and no halo row is needed;
         // their pose blocks and chi2 join the all-reduced packets once (k_finalize_pack).  Observations held elsewhere: sk_slot = -1.
+        // A SLICED list (s.sk_total > 0: the rank's share of a window whose lists were built on its device) holds nothing else: every entry
+        // must be the rank's own, and the keyframe range it was cut for must be the one this set-up arrived at.
         const bool ba_form = s.sk_pose != nullptr;
         if (d.fused || (d.sh_on && !ba_form) || !s.sk_uv || !s.sk_X0 || !s.sk_node || !s.sk_om) return c->fail(NRS_ERR_INVALID, "skinned observations: two-kernel PCG path");
         if (!ba_form && !(arena == &c->arena_trk && s.K == 1)) return c->fail(NRS_ERR_INVALID, "skinned observations without a pose index: single-frame tracking engines only");
         const size_t n_in = (size_t)s.n_skin;
+        const bool sliced = s.sk_total > 0;
+        if (sliced && (!ba_form || !d.sh_on || s.sk_base < 0 || s.n_skin < 0 || (int64_t)s.sk_base + s.n_skin > s.sk_total))
+            return c->fail(NRS_ERR_INVALID, "skinned observations: a sliced list needs a sharded BA window and a slice inside the window's list");
+        if (sliced && (s.sk_k0 != d.sh_k0 || s.sk_k1 != d.sh_k0 + d.sh_nk))
+            return c->fail(NRS_ERR_STATE, "skinned observations: the list was cut for keyframes [%d, %d), the rank owns [%d, %d)", s.sk_k0, s.sk_k1, d.sh_k0, d.sh_k0 + d.sh_nk);
         std::vector<int> pose0;
         if (!ba_form) pose0.assign(n_in, 0);
         const int* sk_pose = ba_form ? s.sk_pose : pose0.data();
@@ -1178,6 +1185,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         for (size_t i = 0; i < n_in; ++i) {
             if (sk_pose[i] < 0 || sk_pose[i] >= s.K) return c->fail(NRS_ERR_INVALID, "skinned observation: pose index out of range");
             if (held(i)) cnt[sk_pose[i] + 1]++;
+            else if (sliced) return c->fail(NRS_ERR_INVALID, "skinned observation: a sliced list holds an observation of keyframe %d, outside the rank's [%d, %d)", sk_pose[i], own_k0, own_k1);
         }
         for (int k = 0; k < s.K; ++k) pose_blk[k + 1] = pose_blk[k] + (cnt[k + 1] + BLK - 1) / BLK;
         if (d.sh_on && pose_blk[s.K] == 0)                         // (a rank whose keyframes have none: one empty block of its first pose, so that every launch has a grid)
@@ -1188,13 +1196,14 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         e->sk_slot.assign(n_in, -1);
         std::vector<float> uv(2 * n, 0.f);
         std::vector<double> X0(3 * n, 0.0), om(SK_MAX * n, 0.0);
-        std::vector<int> rows(SK_MAX * n, -1);
+        std::vector<int> rows(SK_MAX * n, -1), src(n, -1);
         std::vector<uint8_t> act(n, 0);
         std::vector<int> rl_cnt(d.n_rows + 1, 0);
         for (size_t i = 0; i < n_in; ++i) {
             if (!held(i)) continue;
             const size_t sl = (size_t)next[sk_pose[i]]++;
             e->sk_slot[i] = (int)sl;
+            src[sl] = (int)i;
             uv[2 * sl] = s.sk_uv[2 * i]; uv[2 * sl + 1] = s.sk_uv[2 * i + 1];
             for (int k = 0; k < 3; ++k) X0[3 * sl + k] = s.sk_X0[3 * i + k];
             act[sl] = 1;
@@ -1232,7 +1241,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         const size_t o_uv = 0, o_X0 = o_uv + al(8 * n), o_row = o_X0 + al(24 * n), o_om = o_row + al(4 * SK_MAX * n), o_act = o_om + al(8 * SK_MAX * n),
                      o_bp = o_act + al(n), o_pb = o_bp + al(4 * nblk), o_rr = o_pb + al(4 * (s.K + 1)), o_rp = o_rr + al(4 * (nrl + 1)), o_ro = o_rp + al(4 * (nrl + 1)),
                      o_rw = o_ro + al(4 * (n_ent + 1)), o_rec = o_rw + al(8 * (n_ent + 1)), o_part = o_rec + al(8 * 27 * n), o_chi = o_part + al(8 * 32 * nblk),
-                     o_md = o_chi + al(8 * n), o_g = o_md + 256, o_op = o_g + al(8 * 4 * n), o_rq = o_op + al(8 * 8 * nblk), o_recT = o_rq + al(8 * (size_t)d.n_rows),
+                     o_md = o_chi + al(8 * n), o_g = o_md + 256, o_op = o_g + al(8 * 4 * n), o_rq = o_op + al(8 * 8 * nblk), o_src = o_rq + al(8 * (size_t)d.n_rows), o_recT = o_src + al(4 * n),
                      o_dop = o_recT + al(8 * 24 * n), o_spec = o_dop + (d.use_lds ? 0 : al(8 * 6 * (size_t)d.n_rows)),
                      spec_stride = al(8 * 32 * nblk) + al(8 * n), total = o_spec + (size_t)e->n_spec * spec_stride;   // (shadow sets of sk_part / sk_chi: speculative trials)
         DevBuf& buf = arena == &c->arena_trk ? c->nd_skin : c->dba_skin;
@@ -1248,6 +1257,7 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         std::vector<int> row_q(2 * (size_t)d.n_rows, 0);           // per row: its list's range (k_pcg_update<true> / k_skin_op_rows go by rows)
         for (size_t l = 0; l < nrl; ++l) { row_q[2 * (size_t)rl_row[l]] = rl_ptr[l]; row_q[2 * (size_t)rl_row[l] + 1] = rl_ptr[l + 1]; }
         NRS_HIP(c, up(o_rq, row_q.data(), 8 * (size_t)d.n_rows));
+        NRS_HIP(c, up(o_src, src.data(), 4 * n));
         NRS_HIP(c, hipStreamSynchronize(c->stream));
         d.sk_n = (int)n; d.sk_nblk = (int)nblk; d.sk_pcg = 1;      // (a single-frame engine on the direct solver switches sk_pcg off below)
         d.sk_uv = reinterpret_cast<const float*>(sb + o_uv); d.sk_X0 = reinterpret_cast<const double*>(sb + o_X0);
@@ -1259,16 +1269,18 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
         d.sk_rec = reinterpret_cast<double*>(sb + o_rec); d.sk_part = reinterpret_cast<double*>(sb + o_part);
         d.sk_chi = reinterpret_cast<double*>(sb + o_chi); d.sk_maxdiag = reinterpret_cast<double*>(sb + o_md);
         d.sk_g = reinterpret_cast<double*>(sb + o_g); d.sk_opart = reinterpret_cast<double*>(sb + o_op); d.sk_row_q = reinterpret_cast<const int*>(sb + o_rq);
-        d.sk_recT = reinterpret_cast<double*>(sb + o_recT);
+        d.sk_recT = reinterpret_cast<double*>(sb + o_recT); d.sk_src = reinterpret_cast<const int*>(sb + o_src);
         d.D_op = d.use_lds ? nullptr : reinterpret_cast<double*>(sb + o_dop);
         for (int j = 0; j < e->n_spec; ++j) {
             e->spec[j].sk_part = reinterpret_cast<double*>(sb + o_spec + (size_t)j * spec_stride);
             e->spec[j].sk_chi = reinterpret_cast<double*>(sb + o_spec + (size_t)j * spec_stride + al(8 * 32 * nblk));
         }
         d.sk_base = ba_form ? d.xl_init : nullptr;                 // (tracking form: the rows ARE the deformations, X0 + sum om x)
-        e->sk_vert.assign(s.sk_node, s.sk_node + SK_MAX * n_in);
-        e->sk_om.assign(s.sk_om, s.sk_om + SK_MAX * n_in);
-        e->sk_X0.assign(s.sk_X0, s.sk_X0 + 3 * n_in);
+        e->sk_total = s.sk_window(); e->sk_base = sliced ? s.sk_base : 0;
+        if (!ba_form) {                                            // (the direct solver's plan reads them; a BA window's positions come from k_skin_positions)
+            e->sk_vert.assign(s.sk_node, s.sk_node + SK_MAX * n_in);
+            e->sk_om.assign(s.sk_om, s.sk_om + SK_MAX * n_in);
+        }
     }
     if (e->nd) {                                                   // direct solve when the frame is small enough to gain from it
         NRS_TRY(nd_engine_finish(c, e, e->nd, nd_prep));
@@ -1342,37 +1354,23 @@ int engine_skin_set_active(nrs_ctx* c, Engine* e, const uint8_t* active) {
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     return NRS_OK;
 }
-// embedded BA window: the skinned points at the current estimate, X0 + sum_k om_k (x_{n_k} - x_start_{n_k}), summed over k in order
-// (caller order of the observations; host arithmetic on the downloaded rows -- the same expression k_skin evaluates).
-// Sharded: COLLECTIVE -- a rank evaluates the observations it holds from its own rows (the only rows they reach), zeros elsewhere, and
-// the n_skin x 3 block is summed over the ranks through transient scratch: every rank returns the same bits.
+// embedded BA window: the skinned points at the current estimate, X0 + sum_k om_k (x_{n_k} - x_start_{n_k}), summed over k in order:
+// k_skin_positions (nrs_engine_skin.hpp), one thread per held slot, into a zeroed vector of the WINDOW's observations (caller order; a
+// sliced list starts at sk_base in it).  Sharded: COLLECTIVE -- a rank evaluates the observations it holds from its own rows (the only rows
+// they reach), zeros elsewhere, and the vector is summed over the ranks where it stands: every rank returns the same bits.
 int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz) {
     const Dev& d = e->d;
     if (!d.sk_pcg) return c->fail(NRS_ERR_STATE, "no skinned observations on this window");
-    const size_t r0 = (size_t)d.sh_vb0 * BLK, nr = 3 * (size_t)d.sh_nvb * BLK, n = e->sk_slot.size();   // (own rows: all of them on one GPU)
-    std::vector<double> cur(nr), ini(nr);
-    NRS_HIP(c, hipMemcpyAsync(cur.data(), d.xl[e->cur] + 3 * r0, 8 * nr, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(ini.data(), d.xl_init + 3 * r0, 8 * nr, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < n; ++i) {
-        double x[3] = {e->sk_X0[3 * i], e->sk_X0[3 * i + 1], e->sk_X0[3 * i + 2]};
-        if (e->sk_slot[i] < 0) { xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = 0.0; continue; }   // (held by another rank)
-        for (int k = 0; k < SK_MAX; ++k) {
-            const int v = e->sk_vert[SK_MAX * i + k];
-            if (v < 0) continue;
-            const size_t r = 3 * ((size_t)e->vrow[v] - r0);
-            const double om = e->sk_om[SK_MAX * i + k];
-            for (int a = 0; a < 3; ++a) x[a] += om * (cur[r + a] - ini[r + a]);
-        }
-        xyz[3 * i] = x[0]; xyz[3 * i + 1] = x[1]; xyz[3 * i + 2] = x[2];
-    }
-    if (!d.sh_on || n == 0) return NRS_OK;
-    const size_t m = 3 * n;
+    const size_t m = 3 * (size_t)e->sk_total;
+    if (m == 0) return NRS_OK;
     NRS_TRY(c->ensure(c->gather_ws, 2 * sizeof(double) * m));
     double* in = c->gather_ws.as<double>();
-    NRS_HIP(c, hipMemcpyAsync(in, xyz, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
-    NRS_TRY(c->comm->allreduce(c, in, in + m, m));
-    NRS_HIP(c, hipMemcpyAsync(xyz, in + m, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemsetAsync(in, 0, sizeof(double) * m, c->stream));
+    hipLaunchKernelGGL(k_skin_positions, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, d.xl[e->cur], e->sk_base, e->sk_total, in);
+    NRS_HIP(c, hipGetLastError());
+    const double* res = in;
+    if (d.sh_on) { NRS_TRY(c->comm->allreduce(c, in, in + m, m)); res = in + m; }
+    NRS_HIP(c, hipMemcpyAsync(xyz, res, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     c->release(c->gather_ws);
     return NRS_OK;

@@ -16,6 +16,30 @@
 namespace nrs {
 
 
+// Embedded BA windows: the skinned points at the estimate xl, one thread per slot: X0 + sum_k om_k (x_k - x_start_k) over the slot's node
+// rows, k = 0 .. 10 in order with the pads skipped and no contraction -- the expression, the order and the roundings of the host loop this
+// replaces.  Slot i holds observation sk_src[i] of the engine's list, which starts at `base` in the window's list of `total`; out is the
+// window's vector (zeroed by the caller: observations held by other ranks stay 0 for the sum over the ranks).
+__global__ __launch_bounds__(BLK) void k_skin_positions(Dev P, const double* __restrict__ xl, int base, int total, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= P.sk_n) return;
+    const int src = P.sk_src[i];
+    if (src < 0 || base + src >= total) return;                    // (padding)
+    double x[3] = {P.sk_X0[3 * (size_t)i], P.sk_X0[3 * (size_t)i + 1], P.sk_X0[3 * (size_t)i + 2]};
+    for (int k = 0; k < SK_MAX; ++k) {
+        const int row = P.sk_row[(size_t)k * P.sk_n + i];
+        if (row < 0) continue;
+        const double om = P.sk_om[(size_t)k * P.sk_n + i];
+        for (int a2 = 0; a2 < 3; ++a2) {
+            const double dx = P.sk_base ? xl[3 * (size_t)row + a2] - P.sk_base[3 * (size_t)row + a2] : xl[3 * (size_t)row + a2];
+            x[a2] += om * dx;
+        }
+    }
+    double* o = out + 3 * ((size_t)base + src);
+    o[0] = x[0]; o[1] = x[1]; o[2] = x[2];
+}
+
 template <bool LIN>
 __global__ __launch_bounds__(BLK) void k_skin(Dev P, const Pose* __restrict__ poses, const double* __restrict__ xl) {
     __shared__ double lds[4 * 28];

@@ -196,6 +196,7 @@ struct Dev {
     double* sk_g;                    // sk_n x 4: per observation A s + B^T u_p (3 values in a 32-byte slot) of the current PCG direction u
     double* sk_opart;                // sk_nblk x 8: sums over a block's observations of B s (6: the pose rows of H u), of (B^T u_p).s (the cross term u_l.(H_lp u_p)) and of g.s (their share of w.u)
     const int* sk_row_q;             // n_rows x 2: a row's range in sk_rl_obs / sk_rl_om (empty: no observation reaches it)
+    const int* sk_src;               // sk_n: a slot's observation, as an index into the list this engine was given (-1: padding) -- k_skin_positions
     double* D_op;                    // gather path (use_lds = 0) of an embedded problem: the rows' diagonal blocks as the lineariser left them, WITHOUT the observations'
                                      // share k_skin_rows adds to D for the preconditioner -- k_spmv applies these (k_skin_op / the row pass apply A_o whole); null: D
     double* pk; double* pk_loc;      // evaluation packet: [0] chi2 [1] scale [2..2+world) max diag per rank, then K x 27 (H_pp, b_p)
@@ -275,7 +276,8 @@ struct Engine {
     std::vector<float> h_uv;         // observations by row, kept by a rank that holds its own rows only (residual taps)
     std::vector<int> sk_slot;        // embedded BA windows: observation (caller order) -> slot (pose-grouped, padded); -1: held by another rank
     size_t sk_bytes = 0;             // bytes of the context's skin buffer this engine's observations occupy
-    std::vector<int> sk_vert;        // embedded mode: the skinned observations' node vertices (n_skin x 11, -1 pads) and weights
+    int sk_total = 0, sk_base = 0;   // embedded BA windows: the window's skinned observations; where this engine's list starts among them (a sliced list)
+    std::vector<int> sk_vert;        // single-frame embedded engines: the skinned observations' node vertices (n_skin x 11, -1 pads) and weights
     std::vector<double> sk_om, sk_X0;
     unsigned long long serial = 0;   // identifies this engine to the context's tap buffer (nrs_ctx::tap)
     // device-packed engines (nrs_engine_devpack.hpp) keep no host copies of the edges: the taps read the raw device copies

@@ -20,7 +20,7 @@ COMM_ID_BYTES = 128
 SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "nrs_device_name", "nrs_get_profile",
            "nrs_reset_profile", "nrs_stream", "nrs_pose_only_solve", "nrs_dba_build_edges",
            "nrs_dba_solve", "nrs_dba_upload", "nrs_dba_build_edges_embedded", "nrs_dba_upload_embedded", "nrs_dba_download_skinned", "nrs_dba_solve_embedded", "nrs_dba_reset", "nrs_dba_optimize",
-           "nrs_dba_download", "nrs_dba_residuals", "nrs_dba_gradient", "nrs_dba_pack_hash", "nrs_dba_solve_window", "nrs_dba_window_edges", "nrs_dba_solve_window_embedded", "nrs_dba_window_edges_embedded", "nrs_debug_pcg_solve", "nrs_debug_kft", "nrs_debug_set", "nrs_debug_nd_solve", "nrs_debug_nd_cache_stats", "nrs_track_deform_solve_embedded",
+           "nrs_dba_download", "nrs_dba_residuals", "nrs_dba_gradient", "nrs_dba_pack_hash", "nrs_dba_solve_window", "nrs_dba_window_edges", "nrs_dba_solve_window_embedded", "nrs_dba_window_edges_embedded", "nrs_dba_window_slice_embedded", "nrs_shard_plan_counts", "nrs_debug_pcg_solve", "nrs_debug_kft", "nrs_debug_set", "nrs_debug_nd_solve", "nrs_debug_nd_cache_stats", "nrs_track_deform_solve_embedded",
            "nrs_graph_select_neighbours", "nrs_graph_update", "nrs_track_deform_solve",
            "nrs_klt_configure", "nrs_klt_clear", "nrs_klt_num_points", "nrs_klt_set_reference",
            "nrs_klt_track", "nrs_klt_get_template", "nrs_klt_insert_template", "nrs_klt_get_templates",
@@ -139,6 +139,17 @@ def shard_plan(n_kf, lm_kf, world, lib=None):
     rc = lib.nrs_shard_plan(C.c_int32(n_kf), C.c_int32(len(lm_kf)), _p(lm_kf, C.c_int32), C.c_int32(world), _p(kb, C.c_int32))
     if rc != OK:
         raise NrsError(rc, "nrs_shard_plan")
+    return kb
+
+
+def shard_plan_counts(kf_vertices, world, lib=None):
+    """The same ranges from the number of vertices of every keyframe (include/nrs.h nrs_shard_plan_counts; host only)."""
+    lib = lib or load_library()
+    cnt = _i32(kf_vertices)
+    kb = np.zeros(world + 1, np.int32)
+    rc = lib.nrs_shard_plan_counts(C.c_int32(len(cnt)), _p(cnt, C.c_int32), C.c_int32(world), _p(kb, C.c_int32))
+    if rc != OK:
+        raise NrsError(rc, "nrs_shard_plan_counts")
     return kb
 
 
@@ -690,17 +701,28 @@ class Context:
 
     def dba_window_edges_embedded(self):
         """lists of the resident window dba_solve_window_embedded made: the keys of dba_build_edges_embedded plus on_device (1: built on
-        the device); NrsError NRS_ERR_STATE when the resident window was made by another call"""
+        the device); NrsError NRS_ERR_STATE when the resident window was made by another call.  On a rank of a communicator the counts
+        and sk_obs are the window's and sk_node / sk_omega the rank's rows [sk_base, sk_base + sk_held) (dba_window_slice_embedded);
+        sk_base / sk_held are in the dict as well"""
         dev, nl, ns, nd, nk = (C.c_int32(0) for _ in range(5))
+        sl = self.dba_window_slice_embedded()
         self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, C.byref(dev), C.byref(nl), None, C.byref(ns), None, None, C.byref(nd), None, None, C.byref(nk), None, None, None))
         lm_obs = np.zeros(nl.value, np.int32)
         sp_ij, sp_d0 = np.zeros((ns.value, 2), np.int32), np.zeros(ns.value, np.float32)
         dm_idx, dm_w = np.zeros((nd.value, 4), np.int32), np.zeros(nd.value, np.float32)
-        sk_obs, sk_node, sk_omega = np.zeros(nk.value, np.int32), np.zeros((nk.value, 11), np.int32), np.zeros((nk.value, 11), np.float64)
+        sk_obs, sk_node, sk_omega = np.zeros(nk.value, np.int32), np.zeros((sl["sk_held"], 11), np.int32), np.zeros((sl["sk_held"], 11), np.float64)
         self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, C.byref(dev), C.byref(nl), _p(lm_obs, C.c_int32), C.byref(ns), _p(sp_ij, C.c_int32), _p(sp_d0, C.c_float),
                                                          C.byref(nd), _p(dm_idx, C.c_int32), _p(dm_w, C.c_float), C.byref(nk), _p(sk_obs, C.c_int32),
                                                          _p(sk_node, C.c_int32), _p(sk_omega, C.c_double)))
-        return dict(lm_obs=lm_obs, sp_ij=sp_ij, sp_d0=sp_d0, dm_idx=dm_idx, dm_w=dm_w, sk_obs=sk_obs, sk_node=sk_node, sk_omega=sk_omega, on_device=dev.value)
+        return dict(lm_obs=lm_obs, sp_ij=sp_ij, sp_d0=sp_d0, dm_idx=dm_idx, dm_w=dm_w, sk_obs=sk_obs, sk_node=sk_node, sk_omega=sk_omega, on_device=dev.value,
+                    sk_base=sl["sk_base"], sk_held=sl["sk_held"])
+
+    def dba_window_slice_embedded(self):
+        """this rank's share of the resident window dba_solve_window_embedded made (include/nrs.h nrs_dba_window_slice_embedded):
+        dict(sk_base, sk_held, k0, k1, stage_bytes, sk_stage_bytes); a whole window: 0, n_skin, 0, n_kf"""
+        out = (C.c_int64 * 6)()
+        self._chk(self.lib.nrs_dba_window_slice_embedded(self.h, out))
+        return dict(zip(("sk_base", "sk_held", "k0", "k1", "stage_bytes", "sk_stage_bytes"), (int(v) for v in out)))
 
     def dba_upload(self, cam, poses_qt, lm_xyz, lm_kf, lm_uv, edges, scale):
         args = self._dba_args(cam, poses_qt, lm_xyz, lm_kf, lm_uv, edges, scale)
