@@ -615,6 +615,56 @@ int nrs_klt_insert_templates(nrs_ctx* ctx, int32_t count, const float* xy, const
 int nrs_klt_archive_templates(nrs_ctx* ctx, int32_t n, const int32_t* slots, const int32_t* keys);
 int nrs_klt_insert_archived(nrs_ctx* ctx, nrs_ctx* src, int32_t n, const int32_t* keys, const float* xy);
 
+/* ---- f5: the image front end -- System::ImageProcessing + Masker::GetAllMasks (modules/SLAM/system.cc:113-201) ------------
+ * What the reference does to every frame before the tracker is entered, on the device, with ONE upload of the frame:
+ *   grey    cv::cvtColor(RGB2GRAY) (system.cc:193): 8-bit fixed point (R*9798 + G*19235 + B*3735 + 2^14) >> 15, channel 0 = R
+ *   CLAHE   createCLAHE(3.0, Size(8,8))->apply (system.cc:198)
+ *   masks   one per configured filter (bright_filter.cc:24-39, border_filter.cc:24-39, predefined_filter.cc:27-39) and "Global":
+ *           their AND from 255, eroded by the 10x10 rectangle (masker.cc:94-115)
+ * The arithmetic is written down in DESIGN.md "f5"; the Gaussian of BrightFilter is this project's own definition (parity with
+ * OpenCV unpinned: no OpenCV in the build, none of its source in the reference tree).  The filters take the grey image only (the
+ * reference never hands them anything else, system.cc:122).
+ *
+ * A filter record mirrors one line of the reference's filters.txt (masker.cc:32-69):
+ *   NRS_FRONT_BRIGHT      p[0] = threshold                      ("BrightFilter th")
+ *   NRS_FRONT_BORDER      p[0..4] = rb, re, cb, ce, th          ("BorderFilter rb re cb ce th"; th is unused, as in the reference)
+ *   NRS_FRONT_PREDEFINED  mask / w / h / stride: the decoded mask image ("Predefined path": decoding stays with the caller); it is
+ *                         eroded once, here, by the 20x20 ellipse (PredefinedFilter's constructor) and kept on the device
+ * At most NRS_FRONT_MAX_FILTERS filters.  tiles_x x tiles_y: only the reference's 8 x 8 grid is built -- any other value is refused
+ * with NRS_ERR_INVALID.  Configuring drops the resident frame.  A context that was never configured processes with no filters,
+ * clip 3.0 and 8 x 8 tiles (the Global mask is then 255 everywhere). */
+#define NRS_FRONT_MAX_FILTERS 8
+enum { NRS_FRONT_BRIGHT = 0, NRS_FRONT_BORDER = 1, NRS_FRONT_PREDEFINED = 2 };
+enum { NRS_FRONT_IMAGE_GRAY = 0, NRS_FRONT_IMAGE_CLAHE = 1 };
+typedef struct {
+    int32_t kind;                /* NRS_FRONT_BRIGHT / BORDER / PREDEFINED                                              */
+    int32_t p[5];
+    const uint8_t* mask;         /* PREDEFINED only: w x h bytes on the host, row stride in bytes; read during the call  */
+    int32_t w, h, stride;
+} nrs_front_filter;
+int nrs_front_configure(nrs_ctx* ctx, int32_t n_filters, const nrs_front_filter* filters, float clahe_clip, int32_t tiles_x,
+                        int32_t tiles_y);
+/* System::ImageProcessing (system.cc:189-201) + Masker::GetAllMasks (masker.cc:94-115) of one frame.  img: 8 bit, 1, 3 or 4
+ * interleaved channels, row stride in bytes.  Every output pointer may be NULL; outputs are w x h bytes, rows packed.
+ * filter_masks_out (NULL, or one pointer per configured filter, each of them nullable) receives the filters' masks in
+ * configuration order: with global_out this is the GetAllMasks map.  Grey, CLAHE and Global stay resident in the context until
+ * the next call or configuration.  NRS_ERR_INVALID: empty image, channels not 1 / 3 / 4, a PREDEFINED mask of another size, a
+ * BorderFilter ROI (cb, rb, w-ce-cb, h-re-rb) that is empty or leaves the image. */
+int nrs_front_process(nrs_ctx* ctx, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t channels, uint8_t* gray_out,
+                      uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out);
+/* Resident hand-over: nrs_klt_set_reference (LK:47-168), nrs_klt_track (LK:170-596) and nrs_shi_extract (shi_tomasi.cc:38-54 +
+ * tracking.cc:118-134) on the frame the context already holds, so that a frame crosses the bus once.  The arguments are those of
+ * the host-pointer forms without the image / mask pointers and their strides; `image` selects NRS_FRONT_IMAGE_GRAY or
+ * NRS_FRONT_IMAGE_CLAHE; use_global_mask != 0 passes the resident Global mask where the host form takes a mask (the tracker's
+ * Track takes none).  The same internals run on the resident buffers: results are bit for bit those of the host-pointer forms
+ * fed the downloaded bytes (tests/test_gpu_front_resident.py).  NRS_ERR_STATE when no frame has been processed since the
+ * context was created or configured, or when w x h is not the resident frame's size. */
+int nrs_klt_set_reference_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int32_t use_global_mask, int32_t n, const float* xy);
+int nrs_klt_track_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int32_t n, float* xy, int32_t* status,
+                        int32_t use_initial_flow, float min_ssim, int32_t* n_good, float* ssim);
+int nrs_shi_extract_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int32_t use_global_mask, int32_t n_prev,
+                          const float* prev_xy, int32_t capacity, float* out_xy, int32_t* out_id, int32_t* n_out);
+
 /* ---- N2: the skinned mode ("5k points x 500 graph nodes") --------------------------------------------------------
  * The reference has no separate node set; its skinning is stage 2 of CameraPoseAndDeformationOptimization
  * (modules/optimization/g2o_optimization.cc:476-553, spatial_regularizer_fixed.cc:32-43): points of the frame that are not

@@ -21,6 +21,7 @@ struct Engine;       // nrs_engine.hip
 struct EmbWindow;    // nrs_engine.hpp: the lists of an embedded window built in one call
 struct KltState;     // nrs_klt.hip
 struct ShiState;     // nrs_shi.hip
+struct FrontState;   // nrs_front.hip
 
 // Exchange steps of a sharded solve (nrs_comm.hip): one process per GPU, every call is ordered on the
 // context's stream.  Two primitives are all the engine needs:
@@ -77,6 +78,7 @@ struct nrs_ctx {
     nrs::Arena arena_dba, arena_trk;
     nrs::KltState* klt = nullptr;
     nrs::ShiState* shi = nullptr;
+    nrs::FrontState* front = nullptr;   // image front end: configuration + the resident grey / CLAHE / Global mask of the last frame
     nrs::Comm* comm = nullptr;       // set by nrs_comm_init_*: BA problems uploaded afterwards are sharded over its ranks
     hipStream_t comm_stream = nullptr;   // boundary-row exchanges run here, next to the interior tiles on `stream`
     hipEvent_t ev_vec = nullptr, ev_halo = nullptr;
@@ -151,4 +153,10 @@ void comm_free(nrs_ctx* ctx);
 int comm_agree(nrs_ctx* ctx, int rc);    // collective: 0 if every rank passed 0, else an error on every rank
 void klt_free(nrs_ctx* ctx);
 void shi_free(nrs_ctx* ctx);
+void front_free(nrs_ctx* ctx);
+// nrs_front.hip, for the *_front entry points of the tracker and the extractor: the resident image (NRS_FRONT_IMAGE_*) and, when asked for,
+// the Global mask of the last nrs_front_process -- packed w x h bytes on the device; NRS_ERR_STATE when there is none or its size differs
+int front_resident(nrs_ctx* ctx, const char* who, int w, int h, int image, int use_global_mask, const uint8_t** img, const uint8_t** mask);
+// mask bytes under n device-side keypoints (x, y floats, truncated), downloaded to host_out
+int front_mask_at(nrs_ctx* ctx, const uint8_t* d_mask, int w, int h, const float* d_xy, int n, uint8_t* host_out);
 }

@@ -1,0 +1,427 @@
+// f5: the image front end -- what System::TrackImage does to a frame before the tracker is entered
+// (reference modules/SLAM/system.cc:113-201): cvtColor(RGB2GRAY), CLAHE(3.0, 8x8) and Masker::GetAllMasks
+// (modules/masking/masker.cc:94-115 with bright_filter.cc:24-39, border_filter.cc:24-39, predefined_filter.cc:27-39).
+//
+// One upload per frame; grey, CLAHE and the Global mask stay in the context for nrs_klt_*_front / nrs_shi_extract_front.
+// The arithmetic is DEFINED in DESIGN.md "f5" (OpenCV's conventions for the integer steps, the project's own definition of the
+// Gaussian) and restated on the CPU in tests/front_oracle.py; the kernels are held to that file byte for byte.
+//
+//   k_front_gray           8-bit fixed point (R*9798 + G*19235 + B*3735 + 2^14) >> 15, channel 0 = R
+//   k_front_clahe_lut      one workgroup per tile: LDS histogram (integer atomics), clip, redistribution, scan, LUT
+//   k_front_clahe_apply    bilinear blend of the four neighbouring LUTs, fp32, contraction off
+//   k_front_erode_ellipse  union of the element's row spans over a tile staged in LDS (the threshold of BrightFilter is
+//                          applied while the tile is loaded)
+//   k_front_rowmin/colmin  the rectangles, separably; the row pass reads its source through a functor: a plain image, the
+//                          BorderFilter's ROI-and-non-zero image, or the AND of all filter masks (the Global mask)
+//   k_front_gauss_h/v      11 taps each, float accumulators in tap order, one rounding at the end
+// Pixels outside the image never take part in a minimum (OpenCV's default border value of erode).
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+#include "nrs_ctx.hpp"
+
+namespace nrs {
+
+constexpr int FRONT_KMAX = 21;                 // largest structuring element (BorderFilter's 21x21)
+constexpr int FRONT_TX = 32, FRONT_TY = 8;     // output tile of the ellipse erosion
+
+struct EllSpans { int k; signed char lo[FRONT_KMAX], hi[FRONT_KMAX]; };     // element row i holds columns lo[i] <= j < hi[i]
+struct GaussW { float w[11]; };
+struct PlainSrc { const uint8_t* p; };
+struct BorderSrc { const uint8_t* gray; int x0, y0, x1, y1; };              // ROI [x0, x1) x [y0, y1)
+struct AndSrc { const uint8_t* p[NRS_FRONT_MAX_FILTERS]; int n; };
+
+struct FrontFilter {
+    int kind = 0;
+    int p[5] = {0, 0, 0, 0, 0};
+    int mw = 0, mh = 0;                        // PREDEFINED: size of the caller's mask
+};
+
+struct FrontState {
+    std::vector<FrontFilter> filters;
+    float clip = 3.f;
+    int tiles_x = 8, tiles_y = 8;
+    int w = 0, h = 0;
+    bool valid = false;                        // a frame has been processed under this configuration
+    DevBuf raw, gray, clahe, global, tmp_a, tmp_f, lut, at;
+    DevBuf fmask[NRS_FRONT_MAX_FILTERS];       // BRIGHT / BORDER: the last frame's mask; PREDEFINED: the eroded mask (made once)
+    EllSpans e11, e20;
+    GaussW gw;
+};
+
+__device__ __host__ inline int front_reflect101(int i, int n) {
+    if (n == 1) return 0;
+    const int p = 2 * (n - 1);
+    i %= p;
+    if (i < 0) i += p;
+    return i >= n ? p - i : i;
+}
+
+__global__ void k_front_gray(const uint8_t* __restrict__ src, int stride, int ch, int w, int h, uint8_t* __restrict__ dst) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* s = src + (size_t)y * stride + (size_t)x * ch;
+    int v = s[0];
+    if (ch > 1) v = (s[0] * 9798 + s[1] * 19235 + s[2] * 3735 + (1 << 14)) >> 15;
+    dst[(size_t)y * w + x] = (uint8_t)v;
+}
+
+__device__ inline uint8_t front_sat_rint(float v) {
+    const int i = __float2int_rn(v);           // round half to even
+    return (uint8_t)min(255, max(0, i));
+}
+
+// ---- CLAHE ------------------------------------------------------------------------------------------------------------------
+// grid = (tiles_x, tiles_y); the tile is cut from the image extended to (tw tiles_x) x (th tiles_y) by reflect-101
+__global__ __launch_bounds__(256) void k_front_clahe_lut(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int clip,
+                                                         uint8_t* __restrict__ lut) {
+#pragma clang fp contract(off)
+    __shared__ int hist[256];
+    __shared__ int s_excess;
+    const int tid = threadIdx.x;
+    hist[tid] = 0;
+    if (tid == 0) s_excess = 0;
+    __syncthreads();
+    const int area = tw * th;
+    for (int i = tid; i < area; i += 256) {
+        const int ly = i / tw, lx = i - ly * tw;
+        const int gx = front_reflect101(blockIdx.x * tw + lx, w), gy = front_reflect101(blockIdx.y * th + ly, h);
+        atomicAdd(&hist[gray[(size_t)gy * w + gx]], 1);
+    }
+    __syncthreads();
+    int v = hist[tid];
+    if (v > clip) { atomicAdd(&s_excess, v - clip); v = clip; }
+    __syncthreads();
+    const int excess = s_excess, batch = excess / 256;
+    int residual = excess - batch * 256;
+    v += batch;
+    if (residual > 0) {                        // one more for bins 0, step, 2 step, ... until the residual is used up
+        const int step = max(256 / residual, 1);
+        if (tid % step == 0 && tid / step < residual) v += 1;
+    }
+    hist[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {  // inclusive scan (integers: any order)
+        const int t = tid >= off ? hist[tid - off] : 0;
+        __syncthreads();
+        hist[tid] += t;
+        __syncthreads();
+    }
+    const float scale = 255.f / (float)area;
+    lut[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = front_sat_rint((float)hist[tid] * scale);
+}
+
+__global__ void k_front_clahe_apply(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int tiles_x, int tiles_y,
+                                    const uint8_t* __restrict__ lut, uint8_t* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const float inv_tw = 1.f / (float)tw, inv_th = 1.f / (float)th;
+    const float txf = (float)x * inv_tw - 0.5f, tyf = (float)y * inv_th - 0.5f;
+    int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
+    const float xa = txf - (float)tx1, ya = tyf - (float)ty1;     // before the indices are clamped
+    const float xa1 = 1.f - xa, ya1 = 1.f - ya;
+    const int tx2 = min(tx1 + 1, tiles_x - 1), ty2 = min(ty1 + 1, tiles_y - 1);
+    tx1 = max(tx1, 0); ty1 = max(ty1, 0);
+    const int v = gray[(size_t)y * w + x];
+    const float l11 = (float)lut[((size_t)ty1 * tiles_x + tx1) * 256 + v], l12 = (float)lut[((size_t)ty1 * tiles_x + tx2) * 256 + v];
+    const float l21 = (float)lut[((size_t)ty2 * tiles_x + tx1) * 256 + v], l22 = (float)lut[((size_t)ty2 * tiles_x + tx2) * 256 + v];
+    const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
+    dst[(size_t)y * w + x] = front_sat_rint(res);
+}
+
+// ---- morphology -------------------------------------------------------------------------------------------------------------
+// block (32, 8); THRESH: the source pixel is replaced by (v > th ? 0 : 255) while it is staged (BrightFilter)
+template <bool THRESH>
+__global__ __launch_bounds__(FRONT_TX * FRONT_TY) void k_front_erode_ellipse(const uint8_t* __restrict__ src, int w, int h, int th, EllSpans e,
+                                                                             uint8_t* __restrict__ dst) {
+    __shared__ uint8_t tile[(FRONT_TY + FRONT_KMAX - 1) * (FRONT_TX + FRONT_KMAX - 1)];
+    const int a = e.k / 2, tw = FRONT_TX + e.k - 1, thh = FRONT_TY + e.k - 1;
+    const int x0 = blockIdx.x * FRONT_TX - a, y0 = blockIdx.y * FRONT_TY - a;
+    const int tid = threadIdx.y * FRONT_TX + threadIdx.x;
+    for (int i = tid; i < tw * thh; i += FRONT_TX * FRONT_TY) {
+        const int ty = i / tw, tx = i - ty * tw, gx = x0 + tx, gy = y0 + ty;
+        int v = 255;
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            v = src[(size_t)gy * w + gx];
+            if (THRESH) v = v > th ? 0 : 255;
+        }
+        tile[i] = (uint8_t)v;
+    }
+    __syncthreads();
+    const int x = blockIdx.x * FRONT_TX + threadIdx.x, y = blockIdx.y * FRONT_TY + threadIdx.y;
+    if (x >= w || y >= h) return;
+    int m = 255;
+    for (int i = 0; i < e.k; ++i) {
+        const uint8_t* row = tile + (threadIdx.y + i) * tw + threadIdx.x;
+        for (int j = e.lo[i]; j < e.hi[i]; ++j) m = min(m, (int)row[j]);
+    }
+    dst[(size_t)y * w + x] = (uint8_t)m;
+}
+
+__device__ inline int front_load(const PlainSrc& s, int w, int x, int y) { return s.p[(size_t)y * w + x]; }
+__device__ inline int front_load(const BorderSrc& s, int w, int x, int y) {
+    return (x >= s.x0 && x < s.x1 && y >= s.y0 && y < s.y1 && s.gray[(size_t)y * w + x] != 0) ? 255 : 0;
+}
+__device__ inline int front_load(const AndSrc& s, int w, int x, int y) {
+    int v = 255;
+    for (int i = 0; i < s.n; ++i) v &= s.p[i][(size_t)y * w + x];
+    return v;
+}
+
+// the window of a k-wide rectangle covers x - k/2 .. x - k/2 + k - 1 (anchor k/2)
+template <class S>
+__global__ void k_front_rowmin(S s, int w, int h, int k, uint8_t* __restrict__ dst) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const int lo = max(x - k / 2, 0), hi = min(x - k / 2 + k - 1, w - 1);
+    int m = 255;
+    for (int xx = lo; xx <= hi; ++xx) m = min(m, front_load(s, w, xx, y));
+    dst[(size_t)y * w + x] = (uint8_t)m;
+}
+
+__global__ void k_front_colmin(const uint8_t* __restrict__ src, int w, int h, int k, uint8_t* __restrict__ dst) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const int lo = max(y - k / 2, 0), hi = min(y - k / 2 + k - 1, h - 1);
+    int m = 255;
+    for (int yy = lo; yy <= hi; ++yy) m = min(m, (int)src[(size_t)yy * w + x]);
+    dst[(size_t)y * w + x] = (uint8_t)m;
+}
+
+// ---- the Gaussian of BrightFilter (DESIGN.md "f5": defined here, OpenCV's fixed-point path is not reproduced) ---------------
+__global__ void k_front_gauss_h(const uint8_t* __restrict__ src, int w, int h, GaussW g, float* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* row = src + (size_t)y * w;
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 11; ++i) acc = acc + g.w[i] * (float)row[front_reflect101(x + i - 5, w)];
+    dst[(size_t)y * w + x] = acc;
+}
+
+__global__ void k_front_gauss_v(const float* __restrict__ src, int w, int h, GaussW g, uint8_t* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 11; ++i) acc = acc + g.w[i] * src[(size_t)front_reflect101(y + i - 5, h) * w + x];
+    dst[(size_t)y * w + x] = front_sat_rint(acc);
+}
+
+// mask value under each keypoint (Tracking::ExtractFeatures, tracking.cc:126: mask.at<uchar>(pt), coordinates truncated)
+__global__ void k_front_mask_at(const uint8_t* __restrict__ mask, int w, int h, const float* __restrict__ xy, int n, uint8_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)xy[2 * i], y = (int)xy[2 * i + 1];
+    out[i] = (x >= 0 && x < w && y >= 0 && y < h) ? mask[(size_t)y * w + x] : 0;
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+static void front_release(nrs_ctx* c, FrontState* f) {
+    DevBuf* bufs[] = {&f->raw, &f->gray, &f->clahe, &f->global, &f->tmp_a, &f->tmp_f, &f->lut, &f->at};
+    for (auto b : bufs) c->release(*b);
+    for (auto& b : f->fmask) c->release(b);
+    delete f;
+}
+
+void front_free(nrs_ctx* c) {
+    if (!c->front) return;
+    front_release(c, c->front);
+    c->front = nullptr;
+}
+
+// getStructuringElement(MORPH_ELLIPSE, Size(k, k)): r = c = k/2, row i spans [max(c-dx,0), min(c+dx+1,k)), dx = rint(c sqrt((r^2-dy^2)/r^2))
+static EllSpans ellipse_spans(int k) {
+    EllSpans e;
+    e.k = k;
+    const int r = k / 2, c = k / 2;
+    for (int i = 0; i < FRONT_KMAX; ++i) { e.lo[i] = 0; e.hi[i] = 0; }
+    for (int i = 0; i < k; ++i) {
+        const int dy = i - r;
+        if (std::abs(dy) > r) continue;
+        const int dx = (int)std::nearbyint((double)c * std::sqrt((double)(r * r - dy * dy) / (double)(r * r)));
+        e.lo[i] = (signed char)std::max(c - dx, 0);
+        e.hi[i] = (signed char)std::min(c + dx + 1, k);
+    }
+    return e;
+}
+
+// g_i = float(exp(-i^2/50)), their float sum from i = -5 upwards, w_i = g_i / sum in float
+static GaussW gauss_weights() {
+    GaussW g;
+    float s = 0.f;
+    for (int i = 0; i < 11; ++i) { g.w[i] = (float)std::exp(-(double)((i - 5) * (i - 5)) / 50.0); s = s + g.w[i]; }
+    for (int i = 0; i < 11; ++i) g.w[i] = g.w[i] / s;
+    return g;
+}
+
+static inline dim3 front_grid(int w, int h) { return dim3((w + 255) / 256, h); }
+static inline dim3 front_tiles(int w, int h) { return dim3((w + FRONT_TX - 1) / FRONT_TX, (h + FRONT_TY - 1) / FRONT_TY); }
+
+static FrontState* front_default(nrs_ctx* c) {
+    if (!c->front) {
+        FrontState* f = new (std::nothrow) FrontState();
+        if (!f) return nullptr;
+        f->e11 = ellipse_spans(11); f->e20 = ellipse_spans(20); f->gw = gauss_weights();
+        c->front = f;
+    }
+    return c->front;
+}
+
+int front_resident(nrs_ctx* c, const char* who, int w, int h, int image, int use_global_mask, const uint8_t** img, const uint8_t** mask) {
+    const FrontState* f = c->front;
+    if (!f || !f->valid) return c->fail(NRS_ERR_STATE, "%s: no frame has been processed (nrs_front_process)", who);
+    if (w != f->w || h != f->h) return c->fail(NRS_ERR_STATE, "%s: the resident frame is %d x %d, not %d x %d", who, f->w, f->h, w, h);
+    if (image != NRS_FRONT_IMAGE_GRAY && image != NRS_FRONT_IMAGE_CLAHE) return c->fail(NRS_ERR_INVALID, "%s: image selector must be GRAY or CLAHE", who);
+    *img = image == NRS_FRONT_IMAGE_GRAY ? f->gray.as<uint8_t>() : f->clahe.as<uint8_t>();
+    *mask = use_global_mask ? f->global.as<uint8_t>() : nullptr;
+    return NRS_OK;
+}
+
+int front_mask_at(nrs_ctx* c, const uint8_t* d_mask, int w, int h, const float* d_xy, int n, uint8_t* host_out) {
+    FrontState* f = c->front;
+    if (!f) return c->fail(NRS_ERR_STATE, "no front-end state");
+    if (n <= 0) return NRS_OK;
+    NRS_TRY(c->ensure(f->at, (size_t)n));
+    hipLaunchKernelGGL(k_front_mask_at, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_mask, w, h, d_xy, n, f->at.as<uint8_t>());
+    NRS_HIP(c, hipGetLastError());
+    NRS_HIP(c, hipMemcpyAsync(host_out, f->at.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    return NRS_OK;
+}
+
+}  // namespace nrs
+
+using namespace nrs;
+
+extern "C" int nrs_front_configure(nrs_ctx* c, int32_t n_filters, const nrs_front_filter* filters, float clahe_clip, int32_t tiles_x,
+                                   int32_t tiles_y) {
+    if (!c) return NRS_ERR_INVALID;
+    if (n_filters < 0 || n_filters > NRS_FRONT_MAX_FILTERS || (n_filters > 0 && !filters))
+        return c->fail(NRS_ERR_INVALID, "nrs_front_configure: 0..%d filters", NRS_FRONT_MAX_FILTERS);
+    if (tiles_x != 8 || tiles_y != 8) return c->fail(NRS_ERR_INVALID, "nrs_front_configure: only the reference's 8x8 CLAHE grid is built (SLAM/system.cc)");
+    if (!(clahe_clip > 0.f)) return c->fail(NRS_ERR_INVALID, "nrs_front_configure: clahe_clip must be positive");
+    for (int i = 0; i < n_filters; ++i) {
+        const nrs_front_filter& q = filters[i];
+        if (q.kind == NRS_FRONT_BORDER) {
+            if (q.p[0] < 0 || q.p[1] < 0 || q.p[2] < 0 || q.p[3] < 0) return c->fail(NRS_ERR_INVALID, "nrs_front_configure: filter %d: the ROI leaves the image", i);
+        } else if (q.kind == NRS_FRONT_PREDEFINED) {
+            if (!q.mask || q.w <= 0 || q.h <= 0 || q.stride < q.w) return c->fail(NRS_ERR_INVALID, "nrs_front_configure: filter %d: bad predefined mask", i);
+        } else if (q.kind != NRS_FRONT_BRIGHT) {
+            return c->fail(NRS_ERR_INVALID, "nrs_front_configure: filter %d: unknown kind %d", i, q.kind);
+        }
+    }
+    NRS_HIP(c, hipSetDevice(c->device));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    front_free(c);                                                 // a fresh Masker: nothing of the old configuration or its frame is kept
+    FrontState* f = front_default(c);
+    if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
+    f->clip = clahe_clip; f->tiles_x = tiles_x; f->tiles_y = tiles_y;
+    f->filters.resize((size_t)n_filters);
+    for (int i = 0; i < n_filters; ++i) {
+        const nrs_front_filter& q = filters[i];
+        FrontFilter& d = f->filters[i];
+        d.kind = q.kind;
+        for (int j = 0; j < 5; ++j) d.p[j] = q.p[j];
+        if (q.kind != NRS_FRONT_PREDEFINED) continue;
+        // PredefinedFilter's constructor: the mask eroded once by the 20x20 ellipse (predefined_filter.cc:27-34)
+        d.mw = q.w; d.mh = q.h;
+        const size_t n = (size_t)q.w * q.h;
+        int rc = c->ensure(f->tmp_a, n);
+        if (rc == NRS_OK) rc = c->ensure(f->fmask[i], n);
+        if (rc != NRS_OK) { front_free(c); return rc; }
+        hipError_t he = hipMemcpy2DAsync(f->tmp_a.p, (size_t)q.w, q.mask, (size_t)q.stride, (size_t)q.w, (size_t)q.h, hipMemcpyHostToDevice, c->stream);
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(k_front_erode_ellipse<false>, front_tiles(q.w, q.h), dim3(FRONT_TX, FRONT_TY), 0, c->stream, f->tmp_a.as<uint8_t>(), q.w, q.h, 0,
+                               f->e20, f->fmask[i].as<uint8_t>());
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+        if (he != hipSuccess) { front_free(c); return c->fail(NRS_ERR_HIP, "nrs_front_configure: predefined mask: %s", hipGetErrorString(he)); }
+    }
+    return NRS_OK;
+}
+
+extern "C" int nrs_front_process(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t channels, uint8_t* gray_out,
+                                 uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out) {
+    if (!c) return NRS_ERR_INVALID;
+    if (!img || w <= 0 || h <= 0) return c->fail(NRS_ERR_INVALID, "nrs_front_process: empty image");
+    if (channels != 1 && channels != 3 && channels != 4) return c->fail(NRS_ERR_INVALID, "nrs_front_process: %d channels (1, 3 or 4)", channels);
+    if ((int64_t)stride < (int64_t)w * channels) return c->fail(NRS_ERR_INVALID, "nrs_front_process: stride below the row length");
+    NRS_HIP(c, hipSetDevice(c->device));
+    FrontState* f = front_default(c);                              // (never configured: no filters, clip 3.0, 8x8)
+    if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
+    const int nf = (int)f->filters.size();
+    BorderSrc bsrc[NRS_FRONT_MAX_FILTERS];
+    for (int i = 0; i < nf; ++i) {
+        const FrontFilter& q = f->filters[i];
+        if (q.kind == NRS_FRONT_PREDEFINED && (q.mw != w || q.mh != h))
+            return c->fail(NRS_ERR_INVALID, "nrs_front_process: filter %d: the predefined mask is %d x %d, the image %d x %d", i, q.mw, q.mh, w, h);
+        if (q.kind == NRS_FRONT_BORDER) {                          // cv::Rect(cb, rb, w - ce - cb, h - re - rb)
+            const int rb = q.p[0], re = q.p[1], cb = q.p[2], ce = q.p[3];
+            const int64_t rw = (int64_t)w - ce - cb, rh = (int64_t)h - re - rb;
+            if (rw <= 0 || rh <= 0 || cb + rw > w || rb + rh > h)
+                return c->fail(NRS_ERR_INVALID, "nrs_front_process: filter %d: the ROI is empty or leaves the %d x %d image", i, w, h);
+            bsrc[i].x0 = cb; bsrc[i].y0 = rb; bsrc[i].x1 = cb + (int)rw; bsrc[i].y1 = rb + (int)rh;
+        }
+    }
+    f->valid = false;
+    const size_t n = (size_t)w * h, row = (size_t)w * channels;
+    NRS_TRY(c->ensure(f->raw, row * h));
+    NRS_TRY(c->ensure(f->gray, n));
+    NRS_TRY(c->ensure(f->clahe, n));
+    NRS_TRY(c->ensure(f->global, n));
+    NRS_TRY(c->ensure(f->tmp_a, n));
+    NRS_TRY(c->ensure(f->lut, (size_t)f->tiles_x * f->tiles_y * 256));
+    for (int i = 0; i < nf; ++i) {
+        if (f->filters[i].kind != NRS_FRONT_PREDEFINED) NRS_TRY(c->ensure(f->fmask[i], n));
+        if (f->filters[i].kind == NRS_FRONT_BRIGHT) NRS_TRY(c->ensure(f->tmp_f, sizeof(float) * n));
+    }
+    NRS_HIP(c, hipMemcpy2DAsync(f->raw.p, row, img, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
+    const dim3 blk(256), grid = front_grid(w, h);
+    uint8_t* gray = f->gray.as<uint8_t>();
+    uint8_t* tmp = f->tmp_a.as<uint8_t>();
+    hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, f->raw.as<uint8_t>(), (int)row, channels, w, h, gray);
+    // CLAHE (createCLAHE(clip, Size(8,8))->apply): tiles of the image extended to multiples of the grid
+    int pw = w, ph = h;
+    if (w % f->tiles_x != 0 || h % f->tiles_y != 0) { pw = w + f->tiles_x - w % f->tiles_x; ph = h + f->tiles_y - h % f->tiles_y; }
+    const int tw = pw / f->tiles_x, th = ph / f->tiles_y;
+    const int clip = std::max(1, (int)(f->clip * (float)(tw * th) / 256.f));
+    hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, gray, w, h, tw, th, clip, f->lut.as<uint8_t>());
+    hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, gray, w, h, tw, th, f->tiles_x, f->tiles_y, f->lut.as<uint8_t>(),
+                       f->clahe.as<uint8_t>());
+    AndSrc all;
+    all.n = nf;
+    for (int i = 0; i < NRS_FRONT_MAX_FILTERS; ++i) all.p[i] = nullptr;
+    for (int i = 0; i < nf; ++i) {
+        const FrontFilter& q = f->filters[i];
+        uint8_t* m = f->fmask[i].as<uint8_t>();
+        all.p[i] = m;
+        if (q.kind == NRS_FRONT_BRIGHT) {
+            hipLaunchKernelGGL(k_front_erode_ellipse<true>, front_tiles(w, h), dim3(FRONT_TX, FRONT_TY), 0, c->stream, gray, w, h, q.p[0], f->e11, tmp);
+            hipLaunchKernelGGL(k_front_gauss_h, grid, blk, 0, c->stream, tmp, w, h, f->gw, f->tmp_f.as<float>());
+            hipLaunchKernelGGL(k_front_gauss_v, grid, blk, 0, c->stream, f->tmp_f.as<float>(), w, h, f->gw, m);
+        } else if (q.kind == NRS_FRONT_BORDER) {
+            bsrc[i].gray = gray;
+            hipLaunchKernelGGL(k_front_rowmin<BorderSrc>, grid, blk, 0, c->stream, bsrc[i], w, h, 21, tmp);
+            hipLaunchKernelGGL(k_front_colmin, grid, blk, 0, c->stream, tmp, w, h, 21, m);
+        }
+    }
+    // Global: AND of all masks from 255, eroded by the 10x10 rectangle (masker.cc:98-110)
+    hipLaunchKernelGGL(k_front_rowmin<AndSrc>, grid, blk, 0, c->stream, all, w, h, 10, tmp);
+    hipLaunchKernelGGL(k_front_colmin, grid, blk, 0, c->stream, tmp, w, h, 10, f->global.as<uint8_t>());
+    NRS_HIP(c, hipGetLastError());
+    if (gray_out) NRS_HIP(c, hipMemcpyAsync(gray_out, f->gray.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (clahe_out) NRS_HIP(c, hipMemcpyAsync(clahe_out, f->clahe.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (global_out) NRS_HIP(c, hipMemcpyAsync(global_out, f->global.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (filter_masks_out)
+        for (int i = 0; i < nf; ++i)
+            if (filter_masks_out[i]) NRS_HIP(c, hipMemcpyAsync(filter_masks_out[i], f->fmask[i].p, n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    f->w = w; f->h = h; f->valid = true;
+    return NRS_OK;
+}

@@ -411,7 +411,8 @@ void klt_free(nrs_ctx* c) {
     c->klt = nullptr;
 }
 
-static int build_pyramid(nrs_ctx* c, KltState* k, const uint8_t* img, int w, int h, int stride) {
+// img: the caller's host image (uploaded into img_in), or -- on_device -- an image the context already holds (nrs_front_process)
+static int build_pyramid(nrs_ctx* c, KltState* k, const uint8_t* img, int w, int h, int stride, bool on_device = false) {
     // level sizes (buildOpticalFlowPyramid stops when the next level would not exceed winSize)
     int ws[KMAXL], hs[KMAXL], nl = 1;
     ws[0] = w; hs[0] = h;
@@ -428,7 +429,7 @@ static int build_pyramid(nrs_ctx* c, KltState* k, const uint8_t* img, int w, int
         off[l][1] = bytes; bytes += (px * sizeof(short2) + 255) / 256 * 256;
     }
     NRS_TRY(c->ensure(k->pyr_buf, bytes));
-    NRS_TRY(c->ensure(k->img_in, (size_t)stride * h));
+    if (!on_device) NRS_TRY(c->ensure(k->img_in, (size_t)stride * h));
     for (int l = 0; l < nl; ++l) {
         PyrLevel& L = k->pyr.L[l];
         L.w = ws[l]; L.h = hs[l]; L.stride = ws[l] + 2 * KPAD;
@@ -436,11 +437,12 @@ static int build_pyramid(nrs_ctx* c, KltState* k, const uint8_t* img, int w, int
         L.der = reinterpret_cast<short2*>(k->pyr_buf.as<char>() + off[l][1]);
     }
     k->pyr.n_levels = nl;
-    NRS_HIP(c, hipMemcpyAsync(k->img_in.p, img, (size_t)stride * h, hipMemcpyHostToDevice, c->stream));
+    if (!on_device) NRS_HIP(c, hipMemcpyAsync(k->img_in.p, img, (size_t)stride * h, hipMemcpyHostToDevice, c->stream));
+    const uint8_t* d_img = on_device ? img : k->img_in.as<uint8_t>();
     for (int l = 0; l < nl; ++l) {
         const PyrLevel& L = k->pyr.L[l];
         const dim3 b(256), g((L.stride + 255) / 256, L.h + 2 * KPAD);
-        if (l == 0) hipLaunchKernelGGL(k_pyr_copy, g, b, 0, c->stream, k->img_in.as<uint8_t>(), stride, L);
+        if (l == 0) hipLaunchKernelGGL(k_pyr_copy, g, b, 0, c->stream, d_img, stride, L);
         else hipLaunchKernelGGL(k_pyr_down, g, b, 0, c->stream, k->pyr.L[l - 1], L);
         hipLaunchKernelGGL(k_pyr_scharr, g, b, 0, c->stream, L);
     }
@@ -509,21 +511,21 @@ extern "C" int nrs_klt_clear(nrs_ctx* c) {
 
 extern "C" int nrs_klt_num_points(nrs_ctx* c) { return (c && c->klt) ? c->klt->n : 0; }
 
-extern "C" int nrs_klt_set_reference(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride,
-                                     const uint8_t* mask, int32_t n, const float* xy) {
-    if (!c) return NRS_ERR_INVALID;
-    if (!img || w <= KW || h <= KW || stride < w || n < 0 || (n > 0 && !xy)) return c->fail(NRS_ERR_INVALID, "nrs_klt_set_reference: bad argument");
+// SetReferenceImage on a host image / mask (uploaded) or on the resident ones of the front end (on_device)
+static int klt_set_reference_impl(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, const uint8_t* mask, bool on_device,
+                                  int32_t n, const float* xy) {
     NRS_HIP(c, hipSetDevice(c->device));
     KltState* k = klt(c);
     if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
-    NRS_TRY(build_pyramid(c, k, img, w, h, stride));
+    NRS_TRY(build_pyramid(c, k, img, w, h, stride, on_device));
     k->n = 0;
     NRS_TRY(reserve_points(c, k, n, false));
     k->n = n;
     if (n == 0) return NRS_OK;
     NRS_HIP(c, hipMemcpyAsync(k->prev.p, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     const uint8_t* dmask = nullptr;
-    if (mask) {
+    if (mask && on_device) dmask = mask;
+    else if (mask) {
         NRS_TRY(c->ensure(k->mask_in, (size_t)w * h));
         NRS_HIP(c, hipMemcpyAsync(k->mask_in.p, mask, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
         dmask = k->mask_in.as<uint8_t>();
@@ -536,16 +538,30 @@ extern "C" int nrs_klt_set_reference(nrs_ctx* c, const uint8_t* img, int32_t w, 
     return NRS_OK;
 }
 
-extern "C" int nrs_klt_track(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t n,
-                             float* xy, int32_t* status, int32_t use_initial_flow, float min_ssim, int32_t* n_good,
-                             float* ssim) {
+extern "C" int nrs_klt_set_reference(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride,
+                                     const uint8_t* mask, int32_t n, const float* xy) {
     if (!c) return NRS_ERR_INVALID;
+    if (!img || w <= KW || h <= KW || stride < w || n < 0 || (n > 0 && !xy)) return c->fail(NRS_ERR_INVALID, "nrs_klt_set_reference: bad argument");
+    return klt_set_reference_impl(c, img, w, h, stride, mask, false, n, xy);
+}
+
+extern "C" int nrs_klt_set_reference_front(nrs_ctx* c, int32_t w, int32_t h, int32_t image, int32_t use_global_mask, int32_t n, const float* xy) {
+    if (!c) return NRS_ERR_INVALID;
+    const uint8_t *img = nullptr, *mask = nullptr;
+    NRS_TRY(front_resident(c, "nrs_klt_set_reference_front", w, h, image, use_global_mask, &img, &mask));
+    if (w <= KW || h <= KW || n < 0 || (n > 0 && !xy)) return c->fail(NRS_ERR_INVALID, "nrs_klt_set_reference_front: bad argument");
+    return klt_set_reference_impl(c, img, w, h, w, mask, true, n, xy);
+}
+
+// Track on a host image (uploaded) or on a resident one of the front end (on_device)
+static int klt_track_impl(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, bool on_device, int32_t n,
+                          float* xy, int32_t* status, int32_t use_initial_flow, float min_ssim, int32_t* n_good, float* ssim) {
     KltState* k = c->klt;
     if (!k) return c->fail(NRS_ERR_STATE, "nrs_klt_track before nrs_klt_set_reference");
     if (!img || w <= KW || h <= KW || stride < w || n != k->n || (n > 0 && (!xy || !status)))
         return c->fail(NRS_ERR_INVALID, "nrs_klt_track: bad argument (n must equal the number of stored templates: %d)", k->n);
     NRS_HIP(c, hipSetDevice(c->device));
-    NRS_TRY(build_pyramid(c, k, img, w, h, stride));
+    NRS_TRY(build_pyramid(c, k, img, w, h, stride, on_device));
     if (n_good) *n_good = 0;
     if (n == 0) return NRS_OK;
     NRS_TRY(c->ensure(k->pts, sizeof(float) * 2 * n));
@@ -572,6 +588,21 @@ extern "C" int nrs_klt_track(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t 
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     if (n_good) *n_good = good;
     return NRS_OK;
+}
+
+extern "C" int nrs_klt_track(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t n,
+                             float* xy, int32_t* status, int32_t use_initial_flow, float min_ssim, int32_t* n_good,
+                             float* ssim) {
+    if (!c) return NRS_ERR_INVALID;
+    return klt_track_impl(c, img, w, h, stride, false, n, xy, status, use_initial_flow, min_ssim, n_good, ssim);
+}
+
+extern "C" int nrs_klt_track_front(nrs_ctx* c, int32_t w, int32_t h, int32_t image, int32_t n, float* xy, int32_t* status,
+                                   int32_t use_initial_flow, float min_ssim, int32_t* n_good, float* ssim) {
+    if (!c) return NRS_ERR_INVALID;
+    const uint8_t *img = nullptr, *mask = nullptr;
+    NRS_TRY(front_resident(c, "nrs_klt_track_front", w, h, image, 0, &img, &mask));
+    return klt_track_impl(c, img, w, h, w, true, n, xy, status, use_initial_flow, min_ssim, n_good, ssim);
 }
 
 extern "C" int nrs_klt_get_template(nrs_ctx* c, int32_t idx, float xy[2], int16_t* gray, int16_t* grad, float* mean,

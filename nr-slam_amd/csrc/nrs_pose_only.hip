@@ -488,6 +488,7 @@ extern "C" void nrs_destroy(nrs_ctx* c) {
     nrs::dba_free(c);
     nrs::klt_free(c);
     nrs::shi_free(c);
+    nrs::front_free(c);
     nrs::comm_free(c);
     if (c->pin_scal) (void)hipHostFree(c->pin_scal);
     if (c->pin_flags) (void)hipHostFree(c->pin_flags);

@@ -263,10 +263,11 @@ extern "C" int nrs_shi_configure(nrs_ctx* c, int32_t nms_window) {
     return NRS_OK;
 }
 
-extern "C" int nrs_shi_extract(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride,
-                               const uint8_t* mask, int32_t mask_stride, int32_t n_prev, const float* prev_xy,
-                               int32_t capacity, float* out_xy, int32_t* out_id, int32_t* n_out) {
-    if (!c) return NRS_ERR_INVALID;
+// Extract + the caller's mask filter.  on_device: img and mask are resident, packed w x h buffers of the front end -- the image is
+// read in place and the mask bytes under the new keypoints are fetched from the device (nrs_front.hip front_mask_at)
+static int shi_extract_impl(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, const uint8_t* mask, int32_t mask_stride,
+                            bool on_device, int32_t n_prev, const float* prev_xy, int32_t capacity, float* out_xy, int32_t* out_id,
+                            int32_t* n_out) {
     if (!img || !n_out || w < h || h < 5 || stride < w || n_prev < 0 || (n_prev > 0 && !prev_xy) || capacity < 0 ||
         (capacity > 0 && (!out_xy || !out_id)) || (mask && mask_stride < w))
         return c->fail(NRS_ERR_INVALID, "nrs_shi_extract: bad argument (width >= height >= 5 required)");
@@ -281,9 +282,9 @@ extern "C" int nrs_shi_extract(nrs_ctx* c, const uint8_t* img, int32_t w, int32_
         cells[i] = (int)(y * w + x);
     }
     if (s->w != w || s->h != h) NRS_TRY(shi_resize(c, s, w, h));
-    NRS_HIP(c, hipMemcpy2DAsync(s->img.p, (size_t)w, img, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
+    if (!on_device) NRS_HIP(c, hipMemcpy2DAsync(s->img.p, (size_t)w, img, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
     const dim3 blk(256), grid((w + 255) / 256, h);
-    const uint8_t* im = s->img.as<uint8_t>();
+    const uint8_t* im = on_device ? img : s->img.as<uint8_t>();
     int16_t* xg = s->xg.as<int16_t>();
     int16_t* yg = s->yg.as<int16_t>();
     float* sc = s->scores.as<float>();
@@ -316,14 +317,35 @@ extern "C" int nrs_shi_extract(nrs_ctx* c, const uint8_t* img, int32_t w, int32_
         NRS_HIP(c, hipStreamSynchronize(c->stream));
     }
     s->next_id += total;                                           // ids are consumed before the mask filter (tracking.cc:121-131)
+    std::vector<uint8_t> at;
+    if (mask && on_device && total > 0) {
+        at.resize((size_t)total);
+        NRS_TRY(front_mask_at(c, mask, w, h, s->out_xy.as<float>(), total, at.data()));
+    }
     int kept = 0;
     for (int i = 0; i < total; ++i) {
-        if (mask && !mask[(size_t)xy[2 * i + 1] * mask_stride + (size_t)xy[2 * i]]) continue;
+        if (mask && on_device) { if (!at[i]) continue; }
+        else if (mask && !mask[(size_t)xy[2 * i + 1] * mask_stride + (size_t)xy[2 * i]]) continue;
         if (kept < capacity) { out_xy[2 * kept] = xy[2 * i]; out_xy[2 * kept + 1] = xy[2 * i + 1]; out_id[kept] = ids[i]; }
         ++kept;
     }
     *n_out = kept;                                                 // > capacity: the output was truncated
     return NRS_OK;
+}
+
+extern "C" int nrs_shi_extract(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride,
+                               const uint8_t* mask, int32_t mask_stride, int32_t n_prev, const float* prev_xy,
+                               int32_t capacity, float* out_xy, int32_t* out_id, int32_t* n_out) {
+    if (!c) return NRS_ERR_INVALID;
+    return shi_extract_impl(c, img, w, h, stride, mask, mask_stride, false, n_prev, prev_xy, capacity, out_xy, out_id, n_out);
+}
+
+extern "C" int nrs_shi_extract_front(nrs_ctx* c, int32_t w, int32_t h, int32_t image, int32_t use_global_mask, int32_t n_prev,
+                                     const float* prev_xy, int32_t capacity, float* out_xy, int32_t* out_id, int32_t* n_out) {
+    if (!c) return NRS_ERR_INVALID;
+    const uint8_t *img = nullptr, *mask = nullptr;
+    NRS_TRY(front_resident(c, "nrs_shi_extract_front", w, h, image, use_global_mask, &img, &mask));
+    return shi_extract_impl(c, img, w, h, w, mask, w, true, n_prev, prev_xy, capacity, out_xy, out_id, n_out);
 }
 
 extern "C" int nrs_shi_buffers(nrs_ctx* c, float* scores, int16_t* xgrad, int16_t* ygrad) {

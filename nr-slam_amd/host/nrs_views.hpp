@@ -8,6 +8,10 @@
 // reference's own accessors.
 #pragma once
 #include <cstdint>
+#include <fstream>
+#include <functional>
+#include <map>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -350,6 +354,112 @@ private:
     Engine& e_;
     int cap_;
     nrs_rgraph* g_ = nullptr;
+};
+
+// Masker (modules/masking/masker.{h,cc}) + System::ImageProcessing (SLAM/system.cc:189-201) on the device front end (include/nrs.h f5).
+// loadFromTxt reads the reference's filters.txt (masker.cc:32-69): "BorderFilter rb re cb ce th", "BrightFilter th", "Predefined path";
+// other lines are skipped, as there.  Decoding the predefined image stays with the caller (cv::imread(path, IMREAD_GRAYSCALE) in a
+// drop-in): loadFromTxt hands every path to `decode`, which fills the bytes (rows packed) and the size.
+class Masker {
+public:
+    struct Filter {
+        int32_t kind = NRS_FRONT_BRIGHT;
+        int32_t p[5] = {0, 0, 0, 0, 0};
+        std::string name;                 // Filter::GetFilterName(): the key of the mask in GetAllMasks
+        std::string path;                 // Predefined: as written in the file
+        std::vector<uint8_t> mask;        // Predefined: w x h bytes
+        int32_t w = 0, h = 0;
+    };
+    using Decoder = std::function<bool(const std::string& path, std::vector<uint8_t>& bytes, int32_t& w, int32_t& h)>;
+    using Masks = std::map<std::string, std::vector<uint8_t>>;
+
+    // the three line forms, no device involved
+    static std::vector<Filter> ParseFilters(std::istream& in) {
+        std::vector<Filter> out;
+        std::string line;
+        while (std::getline(in, line)) {
+            std::istringstream ss(line);
+            std::string name;
+            ss >> name;
+            Filter f;
+            if (name == "BorderFilter") {
+                std::string v[5];
+                ss >> v[0] >> v[1] >> v[2] >> v[3] >> v[4];
+                f.kind = NRS_FRONT_BORDER; f.name = "BorderFilter";
+                for (int i = 0; i < 5; ++i) f.p[i] = std::stoi(v[i]);
+            } else if (name == "BrightFilter") {
+                std::string th;
+                ss >> th;
+                f.kind = NRS_FRONT_BRIGHT; f.name = "BrightFilter";
+                f.p[0] = std::stoi(th);
+            } else if (name == "Predefined") {
+                ss >> f.path;
+                f.kind = NRS_FRONT_PREDEFINED; f.name = "PredefinedFilter";
+            } else {
+                continue;
+            }
+            out.push_back(f);
+        }
+        return out;
+    }
+
+    explicit Masker(Engine& e, float clahe_clip = 3.0f) : e_(e), clip_(clahe_clip) {}
+
+    void loadFromTxt(const std::string& path, const Decoder& decode = nullptr) {
+        std::ifstream file(path);
+        if (!file.is_open()) return;                                   // (the reference loads nothing, silently)
+        for (Filter& f : ParseFilters(file)) {
+            if (f.kind == NRS_FRONT_PREDEFINED && (!decode || !decode(f.path, f.mask, f.w, f.h)))
+                throw std::runtime_error("Masker: cannot decode the predefined mask " + f.path);
+            filters_.push_back(std::move(f));
+        }
+        configured_ = false;
+    }
+    void addFilter(Filter f) { filters_.push_back(std::move(f)); configured_ = false; }
+    void deleteFilter(size_t idx) { filters_.erase(filters_.begin() + (long)idx); configured_ = false; }
+    const std::vector<Filter>& filters() const { return filters_; }
+
+    // System::ImageProcessing + Masker::GetAllMasks of one frame (SLAM/system.cc:113-122) in one upload: the masks by filter name plus
+    // "Global"; gray / clahe (nullable) receive im_gray and the processed image.  Afterwards the tracker's *_front calls run on the
+    // resident frame.
+    Masks ProcessFrame(const uint8_t* im, int32_t w, int32_t h, int32_t stride, int32_t channels, std::vector<uint8_t>* gray = nullptr,
+                       std::vector<uint8_t>* clahe = nullptr) {
+        configure();
+        const size_t n = (size_t)w * h;
+        std::vector<std::vector<uint8_t>> m(filters_.size(), std::vector<uint8_t>(n));
+        std::vector<uint8_t*> ptr;
+        for (auto& v : m) ptr.push_back(v.data());
+        std::vector<uint8_t> global(n);
+        if (gray) gray->resize(n);
+        if (clahe) clahe->resize(n);
+        e_.check_rc(nrs_front_process(e_.raw(), im, w, h, stride, channels, gray ? gray->data() : nullptr, clahe ? clahe->data() : nullptr,
+                                      global.data(), ptr.empty() ? nullptr : ptr.data()));
+        Masks all;
+        for (size_t i = 0; i < filters_.size(); ++i) all[filters_[i].name] = std::move(m[i]);   // (a later filter of the same name replaces the earlier one)
+        all["Global"] = std::move(global);
+        return all;
+    }
+    // absl::flat_hash_map<std::string, cv::Mat> GetAllMasks(const cv::Mat& im)   masker.cc:94-115 (im: the grey image)
+    Masks GetAllMasks(const uint8_t* im_gray, int32_t w, int32_t h, int32_t stride) { return ProcessFrame(im_gray, w, h, stride, 1); }
+
+private:
+    void configure() {
+        if (configured_) return;
+        std::vector<nrs_front_filter> rec(filters_.size());
+        for (size_t i = 0; i < filters_.size(); ++i) {
+            const Filter& f = filters_[i];
+            rec[i].kind = f.kind;
+            for (int j = 0; j < 5; ++j) rec[i].p[j] = f.p[j];
+            rec[i].mask = f.kind == NRS_FRONT_PREDEFINED ? f.mask.data() : nullptr;
+            rec[i].w = f.w; rec[i].h = f.h; rec[i].stride = f.w;
+        }
+        e_.check_rc(nrs_front_configure(e_.raw(), (int32_t)rec.size(), rec.empty() ? nullptr : rec.data(), clip_, 8, 8));
+        configured_ = true;
+    }
+    Engine& e_;
+    float clip_;
+    std::vector<Filter> filters_;
+    bool configured_ = false;
 };
 
 inline std::vector<int32_t> Engine::CameraPoseAndDeformationOptimization(const CameraView& cam, FrameView& f, MapView& m, RegularizationGraph& graph,

@@ -26,6 +26,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_klt_track", "nrs_klt_get_template", "nrs_klt_insert_template", "nrs_klt_get_templates",
            "nrs_klt_insert_templates", "nrs_klt_archive_templates", "nrs_klt_insert_archived",
            "nrs_shi_configure", "nrs_shi_extract", "nrs_shi_buffers",
+           "nrs_front_configure", "nrs_front_process", "nrs_klt_set_reference_front", "nrs_klt_track_front", "nrs_shi_extract_front",
            "nrs_comm_unique_id", "nrs_comm_init_rccl", "nrs_comm_rank", "nrs_shard_plan",
            "nrs_local_group_create", "nrs_local_group_destroy", "nrs_comm_init_local",
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
@@ -94,6 +95,16 @@ class Graph(C.Structure):
 class KltConfig(C.Structure):
     _fields_ = [("win_size", C.c_int32), ("max_level", C.c_int32), ("max_iters", C.c_int32),
                 ("epsilon", C.c_float), ("min_eig_threshold", C.c_float)]
+
+
+class FrontFilter(C.Structure):
+    """nrs_front_filter: kind, five ints, and for PREDEFINED a host mask with w, h, stride"""
+    _fields_ = [("kind", C.c_int32), ("p", C.c_int32 * 5), ("mask", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32),
+                ("stride", C.c_int32)]
+
+
+FRONT_BRIGHT, FRONT_BORDER, FRONT_PREDEFINED = 0, 1, 2
+FRONT_GRAY, FRONT_CLAHE = 0, 1
 
 
 class Profile(C.Structure):
@@ -400,6 +411,84 @@ class Context:
         yg = np.zeros((h, w), np.int16)
         self._chk(self.lib.nrs_shi_buffers(self.h, _p(sc, C.c_float), _p(xg, C.c_int16), _p(yg, C.c_int16)))
         return sc, xg, yg
+
+    # ---- f5: the image front end (grey, CLAHE, the Masker's masks) and the resident hand-over to the tracker / the extractor
+    def front_configure(self, filters=(), clahe_clip=3.0, tiles=(8, 8)):
+        """filters: ("bright", th) / ("border", rb, re, cb, ce[, th]) / ("predefined", mask h x w uint8), in the order of filters.txt"""
+        recs = (FrontFilter * max(len(filters), 1))()
+        keep = []
+        for r, f in zip(recs, filters):
+            kind = f[0].lower()
+            if kind == "bright":
+                r.kind, r.p[0] = FRONT_BRIGHT, int(f[1])
+            elif kind == "border":
+                r.kind = FRONT_BORDER
+                for j, v in enumerate(f[1:6]):
+                    r.p[j] = int(v)
+            elif kind == "predefined":
+                m = np.ascontiguousarray(f[1], np.uint8)
+                keep.append(m)
+                r.kind, r.mask, r.w, r.h, r.stride = FRONT_PREDEFINED, m.ctypes.data, m.shape[1], m.shape[0], m.strides[0]
+            else:
+                raise ValueError("unknown filter %r" % (f[0],))
+        self._chk(self.lib.nrs_front_configure(self.h, C.c_int32(len(filters)), recs if len(filters) else None, C.c_float(clahe_clip),
+                                               C.c_int32(tiles[0]), C.c_int32(tiles[1])))
+        self._front_n = len(filters)
+
+    def front_process(self, img, outputs=True, stride=None, width=None, channels=1):
+        """img: h x w (grey) or h x w x 3 / 4 uint8; rows may be padded (give `stride` in bytes, `width` in pixels and `channels`, img then being the raw
+        h x stride byte array).  outputs: True (everything), False (nothing is downloaded: the results stay resident) or the names wanted of
+        "gray", "clahe", "global", "masks".  -> dict of those"""
+        img = np.asarray(img, np.uint8)
+        if stride is None:
+            img = np.ascontiguousarray(img)
+            hh, ww = img.shape[:2]
+            ch = 1 if img.ndim == 2 else img.shape[2]
+            stride = img.strides[0] if hh else ww * ch
+        else:
+            hh, ww, ch = img.shape[0], int(width), int(channels)
+        nf = getattr(self, "_front_n", 0)
+        self._front_shape = (hh, ww)
+        want = ("gray", "clahe", "global", "masks") if outputs is True else tuple(outputs or ())
+        out = {k: np.zeros((hh, ww), np.uint8) for k in ("gray", "clahe", "global") if k in want}
+        ptrs = None
+        if "masks" in want:
+            out["masks"] = [np.zeros((hh, ww), np.uint8) for _ in range(nf)]
+            if nf:
+                ptrs = (C.c_void_p * nf)(*[m.ctypes.data for m in out["masks"]])
+        self._chk(self.lib.nrs_front_process(self.h, C.c_void_p(img.ctypes.data), C.c_int32(ww), C.c_int32(hh), C.c_int32(stride), C.c_int32(ch),
+                                             _p(out.get("gray"), C.c_uint8), _p(out.get("clahe"), C.c_uint8), _p(out.get("global"), C.c_uint8), ptrs))
+        return out
+
+    def klt_set_reference_front(self, xy, image=FRONT_GRAY, use_global_mask=True, shape=None):
+        hh, ww = shape or self._front_shape
+        xy = _f32(xy).reshape(-1, 2)
+        self._chk(self.lib.nrs_klt_set_reference_front(self.h, C.c_int32(ww), C.c_int32(hh), C.c_int32(image), C.c_int32(1 if use_global_mask else 0),
+                                                       C.c_int32(len(xy)), _p(xy, C.c_float)))
+
+    def klt_track_front(self, xy, status, image=FRONT_GRAY, initial_flow=True, min_ssim=0.7, shape=None):
+        hh, ww = shape or self._front_shape
+        xy = _f32(xy).reshape(-1, 2).copy()
+        st = _i32(status).copy()
+        good = C.c_int32(0)
+        ssim = np.full(len(xy), np.nan, np.float32)
+        self._chk(self.lib.nrs_klt_track_front(self.h, C.c_int32(ww), C.c_int32(hh), C.c_int32(image), C.c_int32(len(xy)), _p(xy, C.c_float),
+                                               _p(st, C.c_int32), C.c_int32(1 if initial_flow else 0), C.c_float(min_ssim), C.byref(good),
+                                               _p(ssim, C.c_float)))
+        return xy, st, good.value, ssim
+
+    def shi_extract_front(self, prev_xy=None, image=FRONT_GRAY, use_global_mask=True, capacity=65536, shape=None):
+        hh, ww = shape or self._front_shape
+        prev = None if prev_xy is None or len(prev_xy) == 0 else _f32(np.asarray(prev_xy).reshape(-1, 2))
+        xy = np.zeros((capacity, 2), np.float32)
+        ids = np.zeros(capacity, np.int32)
+        n = C.c_int32(0)
+        self._chk(self.lib.nrs_shi_extract_front(self.h, C.c_int32(ww), C.c_int32(hh), C.c_int32(image), C.c_int32(1 if use_global_mask else 0),
+                                                 C.c_int32(0 if prev is None else len(prev)), _p(prev, C.c_float), C.c_int32(capacity),
+                                                 _p(xy, C.c_float), _p(ids, C.c_int32), C.byref(n)))
+        self._shi_shape = (hh, ww)
+        k = min(n.value, capacity)
+        return xy[:k].copy(), ids[:k].copy(), n.value
 
     def comm_init_rccl(self, world, rank, uid):
         buf = (C.c_uint8 * len(uid)).from_buffer_copy(uid)

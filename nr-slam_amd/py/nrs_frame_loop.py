@@ -82,10 +82,15 @@ def project_f32(model, prm, p):
 class GpuBackend:
     """The product path: two nrs contexts (each owns one LucasKanadeTracker state)."""
 
-    def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0):
+    def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None):
         """n_nodes > 0: EMBEDDED-DEFORMATION mode (include/nrs.h nrs_track_deform_solve_embedded; needs the dense graph): n_nodes map points
         (farthest-point sampling on the initial map, nrs_skin_select_nodes) carry the deformation vertices for the whole sequence, every
-        other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call)"""
+        other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call)
+        front: None / False = the images handed to the loop are grey and go to the tracker as they are, without masks (as before).  True or a
+        list of filters (nrs.Context.front_configure) = the loop is handed the RAW frames of System::TrackImage (SLAM/system.cc:113-132): each
+        is uploaded once through nrs_front_process, LK and Shi-Tomasi run on the resident grey image (tracking.cc:92,353,367) and
+        SetReferenceImage / ExtractFeatures take the resident Global mask.  Only PointReuse's own tracker, a second context, still gets
+        the grey bytes from the host."""
         self.nrs = nrs
         self.dense, self.cap, self.rg = dense_graph or n_nodes > 0, cap_per_point, None
         self.n_nodes, self.node_flag = n_nodes, None
@@ -94,12 +99,31 @@ class GpuBackend:
         self.ctx_reuse = nrs.Context()
         self.klt_opts = klt_opts
         self.ctx.klt_configure(klt_opts["win"], klt_opts["max_level"], klt_opts["max_iters"], klt_opts["epsilon"], klt_opts["min_eig"])
+        self.front = bool(front) or isinstance(front, (list, tuple))
+        self._front_im, self._front_gray = None, None
+        if self.front:
+            self.ctx.front_configure(front if isinstance(front, (list, tuple)) else ())
+
+    # front mode: one nrs_front_process per frame.  The loop hands the SAME array to every step of a frame and starts each frame with
+    # klt_track, which therefore always processes; the later steps process only when they see another array
+    def _front_frame(self, im, force=False):
+        if force or im is not self._front_im:
+            self._front_gray = self.ctx.front_process(im, outputs=("gray",))["gray"]
+            self._front_im = im
+        return self._front_gray
 
     # main tracker
     def klt_set_reference(self, im, pts):
+        if self.front:
+            self._front_frame(im)
+            return self.ctx.klt_set_reference_front(pts, self.nrs.FRONT_GRAY, True)
         self.ctx.klt_set_reference(im, pts)
 
     def klt_track(self, im, pts, status, min_ssim):
+        if self.front:
+            self._front_frame(im, force=True)
+            xy, st, good, _ = self.ctx.klt_track_front(pts, status, self.nrs.FRONT_GRAY, initial_flow=True, min_ssim=min_ssim)
+            return xy, st
         xy, st, good, _ = self.ctx.klt_track(im, pts, status, initial_flow=True, min_ssim=min_ssim)
         return xy, st
 
@@ -125,6 +149,8 @@ class GpuBackend:
         self.ctx_reuse.klt_clear()
         self.ctx_reuse.klt_configure(o["win"], 1, o["max_iters"], o["epsilon"], o["min_eig"])
         self.ctx_reuse.klt_insert_archived(self.ctx, mps, pts)
+        if self.front:
+            im = self._front_frame(im)
         xy, st, good, _ = self.ctx_reuse.klt_track(im, pts, np.zeros(len(pts), np.int32), initial_flow=True, min_ssim=min_ssim)
         return xy, st
 
@@ -134,10 +160,16 @@ class GpuBackend:
         self.ctx_reuse.klt_clear()
         self.ctx_reuse.klt_configure(o["win"], 1, o["max_iters"], o["epsilon"], o["min_eig"])
         self.ctx_reuse.klt_insert_templates([dict(t, xy=np.asarray(p, F32)) for p, t in zip(pts, templates)])
+        if self.front:
+            im = self._front_frame(im)
         xy, st, good, _ = self.ctx_reuse.klt_track(im, pts, np.zeros(len(pts), np.int32), initial_flow=True, min_ssim=min_ssim)
         return xy, st
 
     def extract_features(self, im, held_xy, mask=None):
+        if self.front:
+            self._front_frame(im)
+            xy, ids, _ = self.ctx.shi_extract_front(held_xy, self.nrs.FRONT_GRAY, True)
+            return xy, ids
         xy, ids, _ = self.ctx.shi_extract(im, held_xy, mask)
         return xy, ids
 
