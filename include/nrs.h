@@ -680,6 +680,70 @@ int nrs_shi_extract_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int
 int nrs_skin_select_nodes(nrs_ctx* ctx, int32_t n_points, const float* pos /* n_points x 3 */, const uint8_t* eligible /* nullable */,
                           int32_t n_nodes, int32_t* node_ids);
 
+/* ---- f6: monocular map initialisation -- EssentialMatrixInitialization::Initialize (modules/tracking/essential_matrix_initialization.cc:47-410),
+ * the solve behind Tracking::MonocularMapInitialization (tracking.cc:136-214), in one call: the inputs are uploaded once, every stage runs
+ * on the device, the outputs come back in one download.  The arithmetic is written down in DESIGN.md "f6".
+ *   1 UnprojectTrackedFeatures (:83-103)   keypoints with status NRS_TRACKED become COMPACT indices in ascending order; rays are
+ *                                          Unproject(...).normalized() in fp32, pinhole and KB8
+ *   2 the sampler (:112-147)               8 clusters over the compact reference keypoints, one pick per cluster and hypothesis.  THIS PROJECT'S
+ *                                          DEFINITION (the reference: cv::kmeans + srand(4) / random_shuffle; parity unpinned): farthest-point seeds
+ *                                          (first = compact index 0, fp32 squared distances, ties to the lowest index), <= 10 Lloyd iterations
+ *                                          that stop when no centre moved more than 1 px, labels by fp32 squared distance (ties to the lowest
+ *                                          cluster), centres = fp64 sums rounded to fp32 (an empty cluster keeps its centre); hypothesis h takes
+ *                                          from cluster c the member of rank splitmix64(seed + (8 h + c + 1) * 0x9E3779B97F4A7C15) mod |c| in
+ *                                          ascending compact index (an empty cluster: that value mod the compact count, as a compact index)
+ *   3 ComputeE (:180-206)                  A (8 x 9) in fp32 as written; its right null vector and the 3 x 3 SVD in fp64 (Jacobi), each rounded
+ *                                          to fp32; Ef = -U diag(1,1,0) V^T.  The sign of E is free
+ *   4 ComputeScoreAndInliers (:236-256)    every hypothesis over the first n_matches compact rays, fp32 in a fixed order; acos is the fp64
+ *                                          function rounded to fp32.  Best = highest score, lowest h on ties (:154)
+ *   5 ReconstructCameras (:284-318)        DecomposeEssentialMatrix in fp64, rounded; the smaller rotation by trace; t = U.col(2) with its
+ *                                          component of the largest magnitude made positive (the reference: whatever sign Eigen's SVD returns),
+ *                                          then the `away` test over the inlier rays
+ *   6 ReconstructPoints (:320-410)         TriangulateMidPoint(ref, cur, I, T), parallax < 5 radians_per_pixel, depth and reprojection (5.991)
+ *                                          gates in the reference's order, the counters and the two verdict tests
+ * THE INDEXING QUIRK.  FindEssentialWithRANSAC fills the inlier flags by COMPACT index; ReconstructEnvironment / ReconstructPoints read
+ * inliers[idx], reference_keypoints_[idx] and current_keypoints_[idx] by KEYPOINT index over idx < n_matches (:266-267, :331-338).
+ * compact_indexing = 0 restates exactly that (with every keypoint TRACKED the two coincide); 1 reads keypoint compact_map[idx] instead.
+ * Not built: RefineSolution (never called in the reference) and the DBSCAN labels of FeatureTracksClustering (visualiser only). */
+typedef struct {
+    uint32_t struct_size;
+    int32_t  n_hypotheses;        /* 0 = the reference's count, ComputeMaxTries(0.8, 0.95) = 16 (:78-81,130-132); 1..4096              */
+    float    epipolar_threshold;  /* 0.005 rad (tracking.cc:66)                                                                       */
+    float    radians_per_pixel;   /* the caller's (tracking.cc:65); nrs_init_options_init sets 0.0025                                  */
+    int32_t  min_triangulated;    /* 100  (essential_matrix_initialization.cc:401)                                                    */
+    float    max_low_parallax;    /* 0.25 (:405)                                                                                      */
+    int32_t  compact_indexing;    /* 0 = index the inlier flags as the reference writes it (see above); 1 = through the compact map    */
+    uint64_t seed;                /* the sampler's; nrs_init_options_init sets 4 (srand(4), :112)                                      */
+} nrs_init_options;
+/* Caller-owned; struct_size must be set; every pointer may be NULL. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t  verdict;             /* 0 ok; 1 fewer than 8 matches (:51); 2 fewer than min_triangulated landmarks (:401); 3 low-parallax share
+                                     above max_low_parallax (:405)                                                                     */
+    int32_t  best_hypothesis, score;
+    int32_t  n_compact, n_hypotheses;   /* TRACKED keypoints; hypotheses run                                                           */
+    int32_t  counters[8];         /* ReconstructPoints: N (inliers visited), n_triangulated, n_parallax, n_depth_1, n_reprojection_error_1,
+                                     n_depth_2, n_reprojection_error_2, n_triangulation_error (always 0: TriangulateMidPoint never fails) */
+    float    E[9];                /* the best hypothesis, row-major                                                                     */
+    float    pose_qt[7];          /* camera_transform_world: qx qy qz qw tx ty tz, qw >= 0, |t| = 1                                     */
+    uint8_t* inlier;              /* n_matches, by compact index                                                                        */
+    float*   xyz;                 /* n x 3, by keypoint index; 0 where code != 0                                                        */
+    int32_t* code;                /* n: 0 triangulated; 1 not an inlier or not visited; 2 low parallax; 3 negative depth in camera 1;
+                                     4 reprojection in camera 1; 5 negative depth in camera 2; 6 reprojection in camera 2               */
+    float*   hyp_E;               /* parity taps: n_hypotheses x 9                                                                      */
+    int32_t* hyp_score;           /*              n_hypotheses                                                                          */
+    int32_t* samples_out;         /*              n_hypotheses x 8 compact indices                                                      */
+    int32_t* labels;              /*              n_compact (written by the library's sampler only)                                     */
+    float*   centres;             /*              8 x 2     (likewise)                                                                  */
+} nrs_init_result;
+void nrs_init_options_init(nrs_init_options* opt);
+/* ref_xy / cur_xy: n x 2 keypoints of the reference and the current image; status: n LandmarkStatus; n_matches: the tracker's count
+ * (<= the number of TRACKED keypoints); samples: NULL = the library's sampler, else n_hypotheses x 8 compact indices.  Returns an NRS_*
+ * code: a failed initialisation is a verdict, not an error.  NRS_ERR_INVALID: a wrong struct_size, n_hypotheses outside 0..4096,
+ * n_matches above the TRACKED count, a sample index outside the compact range. */
+int nrs_init_essential(nrs_ctx* ctx, const nrs_camera* cam, const nrs_init_options* opt, int32_t n, const float* ref_xy,
+                       const float* cur_xy, const int32_t* status, int32_t n_matches, const int32_t* samples, nrs_init_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@
 #include <cmath>
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
+#include "nrs_geom_f32.hpp"
 
 namespace nrs {
 
@@ -44,73 +45,6 @@ struct TriArgs {
     float* o_xyz;                // n_cand x 3
     double* o_dbg;               // n_cand x 4 or null: final chi2, LM iterations, trials, regulariser edges
 };
-
-// ---- Sophus SE3f in float (so3.hpp:388-395, se3.hpp:222-225), contraction off
-struct Se3f { float q[4], t[3]; };
-__device__ inline void crossf(const float* a, const float* b, float* o) {
-#pragma clang fp contract(off)
-    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ inline void so3_point(const float* q, const float* p, float* o) {
-#pragma clang fp contract(off)
-    float uv[3], c[3];
-    crossf(q, p, uv);
-    uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
-    crossf(q, uv, c);
-    o[0] = p[0] + q[3] * uv[0] + c[0]; o[1] = p[1] + q[3] * uv[1] + c[1]; o[2] = p[2] + q[3] * uv[2] + c[2];
-}
-__device__ inline void se3_point(const Se3f& T, const float* p, float* o) {
-#pragma clang fp contract(off)
-    so3_point(T.q, p, o);
-    o[0] = o[0] + T.t[0]; o[1] = o[1] + T.t[1]; o[2] = o[2] + T.t[2];
-}
-__device__ inline Se3f se3_inv(const Se3f& T) {
-#pragma clang fp contract(off)
-    Se3f r;
-    r.q[0] = -T.q[0]; r.q[1] = -T.q[1]; r.q[2] = -T.q[2]; r.q[3] = T.q[3];
-    const float nt[3] = {T.t[0] * -1.f, T.t[1] * -1.f, T.t[2] * -1.f};
-    so3_point(r.q, nt, r.t);
-    return r;
-}
-__device__ inline Se3f se3_mul(const Se3f& A, const Se3f& B) {
-#pragma clang fp contract(off)
-    Se3f r;
-    const float* a = A.q; const float* b = B.q;
-    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    float rt[3];
-    so3_point(A.q, B.t, rt);
-    r.t[0] = rt[0] + A.t[0]; r.t[1] = rt[1] + A.t[1]; r.t[2] = rt[2] + A.t[2];
-    return r;
-}
-__device__ inline float normf3(const float* v) {
-#pragma clang fp contract(off)
-    return sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-}
-
-// CameraModel::Unproject (pin_hole.cc:33-38, kannala_brandt_8.cc:53-85)
-__device__ inline void unproject_f32(const Cam& c, float u, float v, float* ray) {
-#pragma clang fp contract(off)
-    const float x = (u - c.p[2]) / c.p[0], y = (v - c.p[3]) / c.p[1];
-    if (c.model == 0) { ray[0] = x; ray[1] = y; ray[2] = 1.f; return; }
-    const float theta_d = sqrtf(x * x + y * y);
-    float th = 0.f;
-    if (theta_d > 1e-8f) {
-        float theta = theta_d;
-        for (int j = 0; j < 10; ++j) {
-            const float t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-            const float a = c.p[4] * t2, b = c.p[5] * t4, cc = c.p[6] * t6, d = c.p[7] * t8;
-            const float fix = (theta * (1.f + a + b + cc + d) - theta_d) / (1.f + 3.f * a + 5.f * b + 7.f * cc + 9.f * d);
-            theta = theta - fix;
-            if (fabsf(fix) < 1e-6f) break;
-        }
-        th = theta;
-    }
-    const float s = (float)sin((double)th), co = (float)cos((double)th);
-    ray[0] = s * x / theta_d; ray[1] = s * y / theta_d; ray[2] = co;
-}
 
 __device__ inline double wave_sum_all(double v) { return wave_sum(v); }
 __device__ inline double wave_max(double v) {
@@ -202,25 +136,8 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs A) {
         float nn = normf3(cr); cr[0] /= nn; cr[1] /= nn; cr[2] /= nn;
         nn = normf3(pr); pr[0] /= nn; pr[1] /= nn; pr[2] /= nn;
         const Se3f Tc = pose_of(first), Tp = pose_of(lastf);
-        // TriangulateMidPoint(previous_ray, current_ray, previous_T, current_T)  (geometry_toolbox.cc:45-79)
-        float f0[3] = {pr[0], pr[1], pr[2]}, f1[3] = {cr[0], cr[1], cr[2]};
-        nn = normf3(f0); f0[0] /= nn; f0[1] /= nn; f0[2] /= nn;
-        nn = normf3(f1); f1[0] /= nn; f1[1] /= nn; f1[2] /= nn;
-        const Se3f T10 = se3_mul(Tc, se3_inv(Tp));
-        const float x = T10.q[0], y = T10.q[1], z = T10.q[2], w = T10.q[3];
-        const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x,
-                    tyy = ty * y, tyz = tz * y, tzz = tz * z;
-        const float R[9] = {1.f - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.f - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1.f - (txx + tyy)};
-        float Rf0[3];
-        for (int i = 0; i < 3; ++i) Rf0[i] = (R[3 * i] * f0[0] + R[3 * i + 1] * f0[1]) + R[3 * i + 2] * f0[2];
-        float p[3], q[3], r[3];
-        crossf(Rf0, f1, p); crossf(Rf0, T10.t, q); crossf(f1, T10.t, r);
-        const float nq = normf3(q), nr = normf3(r), np_ = normf3(p);
-        const float s1 = nq / (nq + nr), s2 = nr / np_;
-        float x1[3];
-        for (int i = 0; i < 3; ++i) x1[i] = s1 * (T10.t[i] + s2 * (Rf0[i] + f1[i]));
         float X[3];
-        se3_point(se3_inv(Tc), x1, X);
+        triangulate_mid_point_f32(pr, cr, Tp, Tc, X);          // TriangulateMidPoint(previous_ray, current_ray, previous_T, current_T)
         float pc[3], u, v;
         se3_point(Tc, X, pc);
         project_f32(A.cam, pc[0], pc[1], pc[2], u, v);
@@ -232,9 +149,7 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs A) {
         if ((double)(ex * ex + ey * ey) > 5.991) { finish(TR_REPROJ2, 0, 0, 0); return; }
         const Se3f Tci = se3_inv(Tc), Tpi = se3_inv(Tp);
         const float n1[3] = {X[0] - Tci.t[0], X[1] - Tci.t[1], X[2] - Tci.t[2]}, n2[3] = {X[0] - Tpi.t[0], X[1] - Tpi.t[1], X[2] - Tpi.t[2]};
-        const float dot = (n1[0] * n2[0] + n1[1] * n2[1]) + n1[2] * n2[2];
-        const float cs = dot / (normf3(n1) * normf3(n2));
-        const float par = (float)acos((double)((1.f < cs) ? 1.f : cs));          // std::min(cs, 1.f): a NaN cosine stays NaN and passes the gate, as in the reference
+        const float par = rays_parallax_f32(n1, n2);
         if ((double)par < 0.0025 * 5.0) { finish(TR_PARALLAX, 0, 0, 0); return; }
     }
     // ================= depth seeds, vertices, world_transform_camera per vertex (lane v)

@@ -312,6 +312,60 @@ private:
     int levels_;
 };
 
+// EssentialMatrixInitialization (modules/tracking/essential_matrix_initialization.h): ChangeReference / Initialize on flat keypoint arrays.
+// Initialize returns the verdict of include/nrs.h (0 = absl::OkStatus; 1 "Not enough matches"; 2 / 3 "Not enough triangulated landmarks");
+// landmarks_code[i] == 0 where landmarks_position[i] holds a value (the reference's StatusOr), else the reason.
+class EssentialMatrixInitialization {
+public:
+    struct Options {                      // essential_matrix_initialization.h Options + what the reference hard-codes
+        float epipolar_threshold = 0.005f, radians_per_pixel = 0.0025f;
+        int n_hypotheses = 0;             // 0 = ComputeMaxTries(0.8, 0.95) = 16
+        int min_triangulated = 100;       // :401
+        float max_low_parallax = 0.25f;   // :405
+        bool compact_indexing = false;    // false = the inlier flags indexed as the reference writes it (include/nrs.h "the indexing quirk")
+        uint64_t seed = 4;
+    };
+    EssentialMatrixInitialization(Engine& e, const Options& options, const CameraView& calibration) : e_(e), options_(options), cam_(calibration) {}
+    // void ChangeReference(std::vector<cv::KeyPoint>& keypoints)
+    void ChangeReference(const std::vector<float>& keypoints_xy) { reference_keypoints_ = keypoints_xy; }
+    // absl::Status Initialize(const std::vector<cv::KeyPoint>&, const std::vector<LandmarkStatus>&, const int n_matches,
+    //                         Sophus::SE3f& camera_transform_world, std::vector<absl::StatusOr<Eigen::Vector3f>>& landmarks_position)
+    int Initialize(const std::vector<float>& current_keypoints_xy, const std::vector<int32_t>& keypoint_statuses, int n_matches,
+                   float camera_transform_world[7], std::vector<float>& landmarks_position, std::vector<int32_t>& landmarks_code) {
+        const size_t n = keypoint_statuses.size();
+        if (reference_keypoints_.size() != 2 * n || current_keypoints_xy.size() != 2 * n) throw std::runtime_error("EssentialMatrixInitialization: sizes differ");
+        nrs_init_options opt;
+        nrs_init_options_init(&opt);
+        opt.n_hypotheses = options_.n_hypotheses;
+        opt.epipolar_threshold = options_.epipolar_threshold;
+        opt.radians_per_pixel = options_.radians_per_pixel;
+        opt.min_triangulated = options_.min_triangulated;
+        opt.max_low_parallax = options_.max_low_parallax;
+        opt.compact_indexing = options_.compact_indexing ? 1 : 0;
+        opt.seed = options_.seed;
+        landmarks_position.assign(3 * n, 0.f);
+        landmarks_code.assign(n, 1);
+        nrs_init_result out{};
+        out.struct_size = (uint32_t)sizeof(out);
+        out.xyz = landmarks_position.data();
+        out.code = landmarks_code.data();
+        e_.check_rc(nrs_init_essential(e_.raw(), &cam_.cam, &opt, (int32_t)n, reference_keypoints_.data(), current_keypoints_xy.data(),
+                                       keypoint_statuses.data(), n_matches, nullptr, &out));
+        for (int i = 0; i < 7; ++i) camera_transform_world[i] = out.pose_qt[i];
+        last_ = out;
+        last_.xyz = nullptr; last_.code = nullptr;
+        return out.verdict;
+    }
+    const nrs_init_result& last() const { return last_; }   // score, counters, E of the last call (no arrays)
+
+private:
+    Engine& e_;
+    Options options_;
+    CameraView cam_;
+    std::vector<float> reference_keypoints_;
+    nrs_init_result last_{};
+};
+
 // RegularizationGraph (modules/map/regularization_graph.h:34-96) at the reference's all-pairs density, device resident.
 // Point "ids" are indices 0 .. capacity-1 (the shim keeps the MapPoint ID <-> index map, as it does for frames).
 class RegularizationGraph {

@@ -31,7 +31,8 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_local_group_create", "nrs_local_group_destroy", "nrs_comm_init_local",
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
            "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_triangulate_batch", "nrs_track_deform_solve_rg",
-           "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats"]
+           "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
+           "nrs_init_options_init", "nrs_init_essential"]
 
 
 class NrsError(RuntimeError):
@@ -105,6 +106,25 @@ class FrontFilter(C.Structure):
 
 FRONT_BRIGHT, FRONT_BORDER, FRONT_PREDEFINED = 0, 1, 2
 FRONT_GRAY, FRONT_CLAHE = 0, 1
+
+
+class InitOptions(C.Structure):
+    """nrs_init_options (f6)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_hypotheses", C.c_int32), ("epipolar_threshold", C.c_float), ("radians_per_pixel", C.c_float),
+                ("min_triangulated", C.c_int32), ("max_low_parallax", C.c_float), ("compact_indexing", C.c_int32), ("seed", C.c_uint64)]
+
+
+class InitResult(C.Structure):
+    """nrs_init_result (f6): scalars in the record, arrays through caller-owned pointers (each nullable)"""
+    _fields_ = [("struct_size", C.c_uint32), ("verdict", C.c_int32), ("best_hypothesis", C.c_int32), ("score", C.c_int32),
+                ("n_compact", C.c_int32), ("n_hypotheses", C.c_int32), ("counters", C.c_int32 * 8), ("E", C.c_float * 9),
+                ("pose_qt", C.c_float * 7), ("inlier", C.c_void_p), ("xyz", C.c_void_p), ("code", C.c_void_p), ("hyp_E", C.c_void_p),
+                ("hyp_score", C.c_void_p), ("samples_out", C.c_void_p), ("labels", C.c_void_p), ("centres", C.c_void_p)]
+
+
+INIT_OK, INIT_FEW_MATCHES, INIT_FEW_LANDMARKS, INIT_LOW_PARALLAX = 0, 1, 2, 3
+INIT_COUNTERS = ("N", "n_triangulated", "n_parallax", "n_depth_1", "n_reprojection_error_1", "n_depth_2", "n_reprojection_error_2",
+                 "n_triangulation_error")
 
 
 class Profile(C.Structure):
@@ -541,6 +561,51 @@ class Context:
                                                  _p(cand, C.c_int32), C.c_int32(min_track), _p(o_st, C.c_int32), _p(o_xyz, C.c_float),
                                                  _p(dbg, C.c_double)))
         return (o_st, o_xyz, dbg) if debug else (o_st, o_xyz)
+
+    # ---- f6
+    def init_essential(self, cam, ref_xy, cur_xy, status, n_matches, samples=None, taps=True, struct_size=None, **options):
+        """EssentialMatrixInitialization::Initialize in one call.  options: the fields of nrs_init_options (defaults from
+        nrs_init_options_init); samples: None or n_hypotheses x 8 compact indices.  Returns a dict: verdict, best_hypothesis, score,
+        n_compact, counters (dict), E[3,3], pose_q[4], pose_t[3], inlier[n_matches] (bool), xyz[n,3], code[n] and, with taps, hyp_E,
+        hyp_score, samples, labels, centres (the last two from the library's sampler only)."""
+        ref, cur, st = _f32(ref_xy).reshape(-1, 2), _f32(cur_xy).reshape(-1, 2), _i32(status)
+        n = len(st)
+        if len(ref) != n or len(cur) != n:
+            raise ValueError("init_essential: ref_xy, cur_xy and status differ in length")
+        opt = InitOptions()
+        self.lib.nrs_init_options_init(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(InitOptions._fields_) or k == "struct_size":
+                raise TypeError("init_essential: unknown option %r" % k)
+            setattr(opt, k, v)
+        if struct_size is not None:
+            opt.struct_size = struct_size
+        nh = opt.n_hypotheses if opt.n_hypotheses > 0 else 16
+        nc = int(np.sum(st == 1))
+        smp = None
+        if samples is not None:
+            smp = _i32(np.asarray(samples).reshape(-1))
+            if len(smp) != 8 * nh:
+                raise ValueError("init_essential: samples must be n_hypotheses x 8")
+        out = InitResult()
+        out.struct_size = C.sizeof(InitResult)
+        a = dict(inlier=np.zeros(max(n_matches, 0), np.uint8), xyz=np.zeros((n, 3), np.float32), code=np.zeros(n, np.int32))
+        if taps:
+            a.update(hyp_E=np.zeros((nh, 3, 3), np.float32), hyp_score=np.zeros(nh, np.int32), samples_out=np.zeros((nh, 8), np.int32),
+                     labels=np.zeros(nc, np.int32), centres=np.zeros((8, 2), np.float32))
+        for k, v in a.items():
+            setattr(out, k, v.ctypes.data if v.size else None)
+        self._chk(self.lib.nrs_init_essential(self.h, C.byref(cam), C.byref(opt), C.c_int32(n), _p(ref, C.c_float), _p(cur, C.c_float),
+                                              _p(st, C.c_int32), C.c_int32(n_matches), _p(smp, C.c_int32), C.byref(out)))
+        r = dict(verdict=out.verdict, best_hypothesis=out.best_hypothesis, score=out.score, n_compact=out.n_compact,
+                 n_hypotheses=out.n_hypotheses, counters=dict(zip(INIT_COUNTERS, list(out.counters))),
+                 E=np.array(list(out.E), np.float32).reshape(3, 3), pose_q=np.array(list(out.pose_qt)[:4], np.float32),
+                 pose_t=np.array(list(out.pose_qt)[4:], np.float32), inlier=a["inlier"].astype(bool), xyz=a["xyz"], code=a["code"])
+        if taps:
+            r.update(hyp_E=a["hyp_E"], hyp_score=a["hyp_score"], samples=a["samples_out"])
+            if samples is None:
+                r.update(labels=a["labels"], centres=a["centres"])
+        return r
 
     # ---- a19 / a20
     def graph_select_neighbours(self, g):

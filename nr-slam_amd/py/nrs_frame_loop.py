@@ -7,8 +7,8 @@ cadence (:336-392) -> SetLastFrame.  It only orchestrates: every numerical step 
 tracker, one for the two-level reuse tracker); the tests plug the oracle in behind the same calls.
 
 Keyframes extract new Shi-Tomasi features (tracking.cc:350-372): they enter the frame
-as TRACKED observations without a map point and are followed by LK from then on.  Not reproduced (out of
-the hot-path scope): map initialisation, the mapping thread (triangulation of those features,
+as TRACKED observations without a map point and are followed by LK from then on.  The map is started by `MonoInitializer` +
+`FrameLoop.from_initialization` (tracking.cc:136-214).  Not reproduced (out of the hot-path scope): the mapping thread (triangulation of those features,
 UpdateTriangulatedPoints, BA on keyframes), visualisation.
 
 Poses are Sophus::SE3f in the reference: unit quaternion + translation in float32, and so is the
@@ -177,6 +177,10 @@ class GpuBackend:
         q2, t2, _ = self.ctx.pose_only_solve(self.cam, uv, X, q, t)
         return q2, t2
 
+    # EssentialMatrixInitialization::Initialize (tracking.cc:161-165's call) on the device: include/nrs.h nrs_init_essential
+    def init_essential(self, ref_xy, cur_xy, status, n_matches, **options):
+        return self.ctx.init_essential(self.cam, ref_xy, cur_xy, status, n_matches, taps=False, **options)
+
     # dense_graph: the map's RegularizationGraph at the reference's density -- every pair of initial map points connected
     # (modules/map/map.cc:148-166) -- resident on the device; otherwise the caller's flat graph
     def make_graph(self, graph, X0):
@@ -211,6 +215,89 @@ class GpuBackend:
         self.ctx_reuse.close()
 
 
+class MonoInitializer:
+    """MonocularMapInitializer (modules/tracking/monocular_map_initializer.cc:52-307) on flat arrays over a backend: ProcessNewImage /
+    DataAssociation / ResetInitialization / AddFeatureTracks / RigidInitialization / InitializationRefinement.  A feature's id is its index in
+    the arrays of the current reference (they are never reordered between two resets), so a feature track is its first keypoint, its last one
+    and its length.  Not restated: FeatureTracksClustering (its DBSCAN labels reach the visualiser only).  n_tracks_in_image_ is taken as the
+    number of TRACKED statuses after the tracker's call -- what LucasKanadeTracker::Track returns.  max_features thins the extractor's list
+    evenly, mask is handed to the extractor's filter (ExtractFeatures, :135-153)."""
+    NO_DATA, RECENTLY_RESET, OK = 0, 1, 2
+
+    def __init__(self, backend, klt_min_ssim=0.5, min_tracks=100, max_images=30, max_features=None, **init_options):
+        self.b, self.min_ssim, self.min_tracks, self.max_images, self.max_features = backend, klt_min_ssim, min_tracks, max_images, max_features
+        self.init_options = init_options
+        self.state = self.NO_DATA
+        self.kp = self.ref_kp = np.zeros((0, 2), F32)
+        self.status = np.zeros(0, np.int32)
+        self.track_len = np.zeros(0, np.int32)
+        self.max_len, self.images, self.n_tracks = 0, 0, 0
+        self.log = []
+
+    def reset(self, im, mask=None):                              # ResetInitialization (:80-103)
+        xy, _ = self.b.extract_features(im, None, mask)
+        xy = np.asarray(xy, F32).reshape(-1, 2)
+        if self.max_features is not None and len(xy) > self.max_features:          # evenly over the extractor's (row-major) order
+            xy = xy[(np.arange(self.max_features) * len(xy)) // self.max_features]
+        self.kp, self.ref_kp = xy.copy(), xy.copy()
+        self.b.klt_set_reference(im, self.kp)
+        self.status = np.full(len(xy), TRACKED, np.int32)
+        self.track_len = np.zeros(len(xy), np.int32)
+        self.max_len, self.images = 0, 0
+        self.state = self.RECENTLY_RESET
+
+    def data_association(self, im, mask=None):                   # (:105-133)
+        if self.state == self.NO_DATA:
+            self.reset(im, mask)
+        else:
+            self.kp, self.status = self.b.klt_track(im, self.kp, self.status, self.min_ssim)
+            self.kp, self.status = np.asarray(self.kp, F32), np.asarray(self.status, np.int32)
+            self.n_tracks = int((self.status == TRACKED).sum())
+            if self.n_tracks < self.min_tracks:
+                self.reset(im, mask)
+            else:
+                self.images += 1
+                self.state = self.OK
+                if self.images > self.max_images:
+                    self.reset(im, mask)
+        self.track_len[self.status == TRACKED] += 1              # AddFeatureTracks (:155-166)
+        self.max_len += 1
+
+    def process_new_image(self, im, mask=None):
+        """ProcessNewImage (:52-78): None ("Just reset" / "Rigid Initialization failed") or the InitializationResults as a dict"""
+        self.data_association(im, mask)
+        entry = dict(reset=self.state == self.RECENTLY_RESET, n_features=len(self.kp), n_tracks=self.n_tracks, verdict=None)
+        self.log.append(entry)
+        if self.state == self.RECENTLY_RESET:
+            return None
+        entry.update(ref_xy=self.ref_kp.copy(), cur_xy=self.kp.copy(), status=self.status.copy())
+        r = self.b.init_essential(self.ref_kp, self.kp, self.status, self.n_tracks, **self.init_options)
+        entry["verdict"] = int(r["verdict"])
+        if r["verdict"] != 0:
+            return None
+        # InitializationRefinement + BuildInitializationResults (:235-307): triangulated landmarks whose track has the maximal length
+        keep = np.nonzero((np.asarray(r["code"]) == 0) & (self.track_len == self.max_len))[0]
+        xyz = np.asarray(r["xyz"], F32)[keep]
+        res = dict(index=keep, reference_keypoints=self.ref_kp[keep].copy(), current_keypoints=self.kp[keep].copy(),
+                   reference_landmark_positions=xyz.copy(), current_landmark_positions=xyz.copy(),
+                   pose_q=np.asarray(r["pose_q"], F32), pose_t=np.asarray(r["pose_t"], F32))
+        entry["n_map_points"] = len(keep)
+        return res
+
+
+def sigma_f32(data):
+    """Sigma (modules/utilities/statistics_toolbox.cc:25-50): fp32, sequential"""
+    acc = F32(0)
+    for v in data:
+        acc = F32(acc + F32(v))
+    mu = F32(acc / F32(len(data)))
+    acc = F32(0)
+    for v in data:
+        d = F32(F32(v) - mu)
+        acc = F32(acc + F32(d * d))
+    return F32(np.sqrt(F32(acc / F32(len(data)))))
+
+
 class FrameLoop:
     """State of Tracking + the slice of Map / Frame it touches, on flat arrays."""
 
@@ -243,6 +330,28 @@ class FrameLoop:
         else:
             self.templates = self.b.klt_get_templates(n)
         self.log = []
+
+    @classmethod
+    def from_initialization(cls, backend, project_f32, wh, result, im, stretch_th=1.1, **kw):
+        """The tail of Tracking::MonocularMapInitialization (tracking.cc:147-213) on a MonoInitializer result: scale = 3 / the nth_element
+        median of the landmark depths, Sigma of the depths, positions and the pose translation times scale, the all-pairs graph at
+        3 sigma scale (the backend keeps it: a dense-graph backend is required), klt_set_reference on the current image and the template
+        archive (both in __init__).  The loop starts at the current frame, every map point TRACKED_WITH_3D."""
+        if not getattr(backend, "dense", False):
+            raise ValueError("from_initialization needs a backend that keeps the all-pairs graph (dense_graph=True)")
+        X = np.asarray(result["current_landmark_positions"], F32)
+        depths = X[:, 2].astype(F32)
+        k = len(depths) // 2
+        scale = F32(F32(3) / np.partition(depths, k)[k])
+        sigma = sigma_f32(depths)
+        sigma_graph = F32(F32(sigma * scale) * F32(3))
+        Xs = (np.asarray(result["reference_landmark_positions"], F32) * scale).astype(F32)
+        t = (np.asarray(result["pose_t"], F32) * scale).astype(F32)
+        loop = cls(backend, project_f32, wh, scale, result["current_keypoints"], Xs, dict(sigma=float(sigma_graph), stretch_th=stretch_th),
+                   result["pose_q"], t, im, **kw)
+        loop.pos = (X * scale).astype(F32)
+        loop.init_sigma, loop.init_sigma_graph = sigma, sigma_graph
+        return loop
 
     # ---- tracking.cc:72-112 (tracked branch)
     def track_image(self, im):

@@ -588,3 +588,82 @@ def nd_block_system(n, seed=3, knn=11):
     last = np.zeros(N, np.uint8)
     last[n:] = 1
     return pos, last, pairs, Dn, Vp, rng.normal(0, 1, (N, 3))
+
+
+def make_init_pair(n=300, seed=1, model=PINHOLE, baseline=4.0, rot=(0.01, -0.02, 0.015), noise_px=0.3, outlier_frac=0.0, untracked_frac=0.0,
+                   relief=10.0):
+    """Two views of a RIGID surface for the monocular map initialisation (f6): the reference camera at the origin, the current one moved by
+    `baseline` mm (0: a pure rotation) and turned by the rotation vector `rot`.  Returns ref_xy / cur_xy (n x 2, fp32), status (n, 1 = TRACKED;
+    untracked points are interleaved and carry status 3 with their reference position as cur_xy), the true camera_transform_world (R, t with
+    |t| = baseline) and the points in the reference camera's frame.  Outliers keep status TRACKED and get a uniformly random cur_xy."""
+    rng = np.random.default_rng(seed)
+    prm = HAMLYN_PINHOLE if model == PINHOLE else ENDOMAPPER_KB8
+    if model == PINHOLE:
+        x, y = rng.uniform(-20, 20, n), rng.uniform(-15, 15, n)
+        z = 60 + relief * np.sin(x / 7) * np.cos(y / 6) + rng.uniform(-0.3 * relief, 0.3 * relief, n)      # (not a plane: the 8-point system needs relief)
+        X = np.stack([x, y, z], 1)
+    else:
+        ang, z = rng.uniform(0, 2 * np.pi, n), rng.uniform(12.0, 70.0, n)
+        rad = 15 + 1.5 * np.sin(3 * ang) * np.cos(z / 9)
+        X = np.stack([rad * np.cos(ang), rad * np.sin(ang), z], 1)
+    R = _small_rot(np.asarray(rot, np.float64))
+    d = np.array([1.0, 0.25, 0.1])
+    t = -baseline * d / np.linalg.norm(d)
+    ref = _project(model, prm.astype(np.float64), X)
+    cur = _project(model, prm.astype(np.float64), X @ R.T + t)
+    ref = ref + rng.normal(0, noise_px, ref.shape)
+    cur = cur + rng.normal(0, noise_px, cur.shape)
+    status = np.ones(n, np.int32)
+    out = rng.random(n) < outlier_frac
+    lo, hi = ref.min(0), ref.max(0)
+    cur[out] = rng.uniform(lo, hi, (int(out.sum()), 2))
+    un = np.zeros(n, bool)
+    if untracked_frac > 0:
+        step = max(2, int(round(1.0 / untracked_frac)))
+        un[step // 2::step] = True
+        status[un] = 3
+        cur[un] = ref[un]
+    return dict(model=model, prm=prm.copy(), ref_xy=ref.astype(F32), cur_xy=cur.astype(F32), status=status, n_matches=int((status == 1).sum()),
+                R=R, t=t, X=X, outlier=out, untracked=un)
+
+
+def make_init_sequence(n_points=500, n_frames=8, seed=3, wh=(320, 240), step=0.35, rot_step=(0.0006, -0.0009, 0.0004)):
+    """Rendered frames for the monocular map initialisation end to end (f6): a RIGID surface (the pinhole rest shape of surface_points)
+    seen by a camera that moves `step` mm per frame sideways and turns by rot_step per frame; frame 0 is the texture of
+    make_frame_sequence, the later frames are that texture warped by the dense flow interpolated from the projected point motions.
+    The calibration is the Hamlyn pinhole scaled to the image size.  Returns images, the calibration and the true poses and points."""
+    from scipy.interpolate import griddata
+    rng = np.random.default_rng(seed)
+    w, h = wh
+    prm = HAMLYN_PINHOLE.copy()
+    prm[:4] = prm[:4] * F32(w / 640.0)
+    X, _ = surface_points(n_points, rng, PINHOLE)
+    d = np.array([1.0, 0.3, 0.0])
+    poses_R, poses_t, uvt = [], [], []
+    for f in range(n_frames):
+        R = _small_rot(np.asarray(rot_step, np.float64) * f)
+        t = -R @ (step * f * d)
+        poses_R.append(R); poses_t.append(t)
+        uvt.append(_project(PINHOLE, prm.astype(np.float64), X @ R.T + t))
+    uv0 = uvt[0]
+    tex = _texture(h, w, rng)
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    images = []
+    for f in range(n_frames):
+        if f == 0:
+            sx, sy = xs, ys
+        else:
+            dd, pts = uv0 - uvt[f], uvt[f]
+            gx = griddata(pts, dd[:, 0], (xs, ys), method="linear")
+            gy = griddata(pts, dd[:, 1], (xs, ys), method="linear")
+            nx = griddata(pts, dd[:, 0], (xs, ys), method="nearest")
+            ny = griddata(pts, dd[:, 1], (xs, ys), method="nearest")
+            gx = np.where(np.isnan(gx), nx, gx); gy = np.where(np.isnan(gy), ny, gy)
+            sx, sy = xs + gx, ys + gy
+        sx2, sy2 = np.clip(sx + 32, 0, w + 62.0), np.clip(sy + 32, 0, h + 62.0)
+        x0, y0 = np.minimum(np.floor(sx2).astype(int), w + 62), np.minimum(np.floor(sy2).astype(int), h + 62)
+        fx, fy = sx2 - x0, sy2 - y0
+        v = (tex[y0, x0] * (1 - fx) + tex[y0, x0 + 1] * fx) * (1 - fy) + (tex[y0 + 1, x0] * (1 - fx) + tex[y0 + 1, x0 + 1] * fx) * fy
+        images.append(np.clip(np.rint(v), 0, 255).astype(np.uint8))
+    return dict(model=PINHOLE, prm=prm, wh=(w, h), images=images, R=poses_R, t=poses_t, X=X, uv_true=[u.astype(F32) for u in uvt],
+                radians_per_pixel=float(1.0 / prm[0]))
