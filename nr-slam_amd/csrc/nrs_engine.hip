@@ -58,6 +58,7 @@
 #include "nrs_engine_skin.hpp"
 #include "nrs_engine_nd.hpp"
 #include "nrs_engine_kft.hpp"
+#include "nrs_engine_plan.hpp"        // the decisions the host packer (setup) and the device packer (devpack) share, and the arena
 #include "nrs_engine_setup.hpp"
 #include "nrs_engine_kft_setup.hpp"
 #include "nrs_engine_devpack.hpp"

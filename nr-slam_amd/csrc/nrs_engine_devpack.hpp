@@ -34,7 +34,7 @@ namespace nrs {
 
 constexpr int DP_HCAP = 2048, DP_HASH = 4096;
 
-__device__ inline uint64_t dp_spread(uint64_t v) {                  // 21 bits -> every third bit (as engine_create)
+__device__ inline uint64_t dp_spread(uint64_t v) {                  // 21 bits -> every third bit (the host packer's `spread`)
     v &= 0x1fffff;
     v = (v | v << 32) & 0x1f00000000ffffULL;
     v = (v | v << 16) & 0x1f0000ff0000ffULL;
@@ -529,13 +529,7 @@ static bool devpack_eligible(nrs_ctx* c, const EngineSpec& s, int n_pad_rows) {
     return true;
 }
 
-bool engine_device_pack_ok(nrs_ctx* c, const EngineSpec& s) {
-    std::vector<int> cnt(s.K, 0);
-    for (int i = 0; i < s.M; ++i) cnt[s.lm_pose[i]]++;
-    int n_pad = 0;
-    for (int k = 0; k < s.K; ++k) n_pad += std::max(1, (cnt[k] + ROW_ALIGN - 1) / ROW_ALIGN) * ROW_ALIGN;
-    return devpack_eligible(c, s, n_pad);
-}
+bool engine_device_pack_ok(nrs_ctx* c, const EngineSpec& s) { return devpack_eligible(c, s, row_groups(s).n_pad_rows); }
 
 int engine_edges_to_host(nrs_ctx* c, Engine* e, int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w) {
     if (!e->dev_edges) return c->fail(NRS_ERR_STATE, "the resident problem keeps its edges on the host");
@@ -550,53 +544,24 @@ int engine_edges_to_host(nrs_ctx* c, Engine* e, int* sp_ij, float* sp_d0, int* d
 
 // Returns NRS_OK with *done = true when the engine was built here; *done = false (and NRS_OK) when the window turned out not to
 // qualify (a fixed vertex, an incomplete damper, a halo beyond the limits): the caller then runs the host path.
-static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine* e, bool* done) {
+static int engine_create_device(nrs_ctx* c, const EngineSpec& s, const RowGroups& g, Arena* arena, Engine* e, bool* done) {
     *done = false;
     Dev& d = e->d;
-    const bool tm = c->env("NRS_TIMING") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!tm) return;
-        (void)hipStreamSynchronize(c->stream);
-        auto now = std::chrono::steady_clock::now();
-        if (c->comm) fprintf(stderr, "[nrs] rank %d/%d device pack %-18s %.2f ms\n", c->comm->rank, c->comm->world, what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        else fprintf(stderr, "[nrs] device pack %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StageTimer mark{c, "device pack", true};
     for (int v = 0; v < s.M; ++v) if (s.rflag[v] != (RF_OBS | RF_REPROJ_ACTIVE)) return NRS_OK;
     if (!s.edges_on_device)                                        // an incomplete damper (-1: absent vertex, valid for engine_create): the device
         for (int64_t q = 0; q < 4 * (int64_t)s.n_dm; ++q)          // kernels index by these values, so such a window takes the host path
             if (s.dm_idx[q] < 0) return NRS_OK;
     const int K = s.K, M = s.M, n_sp = s.n_sp, n_dm = s.n_dm;
-    std::vector<int> pose_ptr(K + 1, 0), pose_grp_ptr(K + 1, 0), grp_pose;
-    for (int i = 0; i < M; ++i) pose_ptr[s.lm_pose[i] + 1]++;
-    for (int k = 0; k < K; ++k) pose_ptr[k + 1] += pose_ptr[k];
-    for (int k = 0; k < K; ++k) {
-        const int ng = std::max(1, (pose_ptr[k + 1] - pose_ptr[k] + ROW_ALIGN - 1) / ROW_ALIGN);
-        pose_grp_ptr[k + 1] = pose_grp_ptr[k] + ng;
-        for (int g = 0; g < ng; ++g) grp_pose.push_back(k);
-    }
-    memset(&d, 0, sizeof(d));
-    const int n_pad = pose_grp_ptr[K] * ROW_ALIGN;
-    const int T = n_pad >= 32768 ? 2 : 8;                          // lanes per row, as engine_create
-    d.T = T; d.K = K; d.M = M; d.n_sp = n_sp; d.n_dm = n_dm; d.n_un = 0;
-    d.cam = s.cam;
-    d.info_reproj = s.info_reproj; d.delta_reproj = s.delta_reproj; d.info_pos = s.info_pos; d.delta_pos = s.delta_pos;
-    d.info_spatial = s.info_spatial; d.delta_spatial = s.delta_spatial; d.k_spring = s.k_spring; d.spring_form = s.spring_form;
-    d.n_groups = pose_grp_ptr[K];
-    d.n_rows = d.n_groups * ROW_ALIGN;
-    d.tile_rows = BLK / T;
-    d.n_regblk = d.n_rows / d.tile_rows;
-    d.n_vecblk = d.n_rows / BLK;
+    const std::vector<int>&pose_ptr = g.pose_ptr, &pose_grp_ptr = g.pose_grp_ptr, &grp_pose = g.grp_pose;
+    const int T = lanes_per_row(c, g.n_pad_rows);
+    dev_init(d, s, g, T);
     const int n_rows = d.n_rows, n_slices = n_rows / (64 / T), n_tiles = d.n_regblk;
     const int64_t ni_s = 2 * (int64_t)n_sp, ni_d = 4 * (int64_t)n_dm;
-    // a rank of a sharded window packs the incidence records of its own keyframe range only (shard_plan, as engine_create)
+    // a rank of a sharded window packs the incidence records of its own keyframe range only
     const bool sh = c->comm != nullptr && s.shard;
-    const int Wn = sh ? c->comm->world : 1, rk = sh ? c->comm->rank : 0;
-    std::vector<int> kb(Wn + 1, 0);
-    kb[Wn] = K;
-    if (sh) shard_plan(K, pose_grp_ptr.data(), Wn, kb.data());
-    const int pack_lo = pose_grp_ptr[kb[rk]] * ROW_ALIGN, pack_hi = pose_grp_ptr[kb[rk + 1]] * ROW_ALIGN;
+    int pack_lo, pack_hi;
+    pack_range(c, s, g, pack_lo, pack_hi);
     const int tb0 = pack_lo / d.tile_rows, tb1 = pack_hi / d.tile_rows;     // its tiles
     // ---- scratch: raw inputs + intermediates (sized from the inputs; the packed arrays themselves go into the arena later)
     size_t tmp_bytes = 0;
@@ -775,118 +740,30 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     NRS_HIP(c, hipStreamSynchronize(st));
     mark("fill + halo sizes");
     if (h_flag) return NRS_OK;                                       // a halo beyond the kernel's limits: host path
-    // ---- halo_ptr, tile classes, LDS decision (host, O(tiles): as engine_create)
-    std::vector<int> halo_ptr(n_tiles + 1, 0), tile_list(n_tiles);
-    d.max_halo = 0; d.max_halo_s = 0;
-    for (int b = 0; b < n_tiles; ++b) {
-        halo_ptr[b + 1] = halo_ptr[b] + h_hs[b];
-        d.max_halo = std::max(d.max_halo, h_hs[b]);
-        d.max_halo_s = std::max(d.max_halo_s, h_hns[b]);
-    }
+    // ---- the decisions both packers share (nrs_engine_plan.hpp; host, O(tiles)): tile classes, LDS and path flags, the shard window
+    std::vector<int> halo_ptr(n_tiles + 1, 0);
+    for (int b = 0; b < n_tiles; ++b) halo_ptr[b + 1] = halo_ptr[b] + h_hs[b];
     const size_t n_halo = (size_t)halo_ptr[n_tiles];
-    {
-        std::vector<int> sorted = h_hs;
-        std::sort(sorted.begin(), sorted.end());
-        int cut = d.max_halo;
-        if (n_tiles >= 1024) {                                      // small problems are latency-bound: one launch
-            const int p97 = sorted[(size_t)(0.97 * (n_tiles - 1))];
-            const bool fits = sizeof(double) * 3 * (size_t)(2 * d.tile_rows + d.max_halo + d.max_halo_s + 2) <= 48 * 1024;
-            if (4 * d.max_halo > 5 * p97 && (n_tiles - (int)(0.97 * n_tiles) >= 1024 || !fits) && !c->env("NRS_ONE_CLASS")) cut = p97;
-        }
-        int n0 = 0;
-        for (int b = 0; b < n_tiles; ++b) if (h_hs[b] <= cut) tile_list[n0++] = b;
-        int n1 = n0;
-        for (int b = 0; b < n_tiles; ++b) if (h_hs[b] > cut) tile_list[n1++] = b;
-        d.n_tiles_cls[0] = n0; d.n_tiles_cls[1] = n_tiles - n0;
-        for (int b = 0; b < n_tiles; ++b) {
-            const int cls = h_hs[b] <= cut ? 0 : 1;
-            d.cap_h[cls] = std::max(d.cap_h[cls], h_hs[b]);
-            d.cap_s[cls] = std::max(d.cap_s[cls], h_hns[b]);
-        }
-    }
-    size_t lds_need = 0;
-    for (int cls = 0; cls < 2; ++cls) {
-        if (!d.n_tiles_cls[cls]) continue;
-        lds_need = std::max(lds_need, sizeof(double) * 3 * (size_t)(d.tile_rows + d.cap_h[cls]));
-        lds_need = std::max(lds_need, sizeof(double) * 3 * (size_t)(2 * d.tile_rows + d.cap_h[cls] + d.cap_s[cls] + 2));
-    }
-    if (lds_need > 64 * 1024 - 512 || d.tile_rows + d.max_halo >= 65535) return NRS_OK;     // gather fallback: host path
-    d.use_lds = 1; d.dform = 0; d.coarse = 0;
-    d.fused = d.n_rows < 32768 ? 1 : 0;                             // single-launch PCG iteration for latency-bound windows
-    d.hier = n_tiles > 4096 ? 1 : 0;
-    d.ecd = (!d.fused && !c->opt.profile) ? 1 : 0;
-    d.co_n = 3 * d.n_groups + 6;
-    d.sh_on = 0; d.sh_rank = 0; d.sh_world = 1; d.sh_lead = 1;
-    d.sh_k0 = 0; d.sh_nk = K; d.sh_g0 = 0; d.sh_ng = d.n_groups; d.sh_vb0 = 0; d.sh_nvb = d.n_vecblk;
-    for (int cls = 0; cls < 2; ++cls) { d.sh_t0[cls] = 0; d.sh_nt[cls] = d.n_tiles_cls[cls]; }
-    if (sh) {
-        // ---- shard window (engine_create "shard window": the same fields, the same refusals).  What the host reads off the halo
-        // lists -- a row beyond the adjacent keyframes, a row of another rank -- is decided by a tile's smallest and largest halo row
-        d.sh_on = 1; d.sh_rank = rk; d.sh_world = Wn; d.sh_lead = rk == 0;
-        d.sh_k0 = kb[rk]; d.sh_nk = kb[rk + 1] - kb[rk];
-        d.sh_g0 = pose_grp_ptr[kb[rk]]; d.sh_ng = pose_grp_ptr[kb[rk + 1]] - d.sh_g0;
-        d.sh_vb0 = d.sh_g0 * (ROW_ALIGN / BLK); d.sh_nvb = d.sh_ng * (ROW_ALIGN / BLK);
-        if ((int64_t)d.sh_nvb * BLK < K) return c->fail(NRS_ERR_INVALID, "sharded solve: shard smaller than the pose count");
-        for (int cls = 0; cls < 2; ++cls) {                       // tile_list is ascending inside a class
-            const int* tl = tile_list.data() + (cls ? d.n_tiles_cls[0] : 0);
-            const int n = d.n_tiles_cls[cls];
-            const int a = (int)(std::lower_bound(tl, tl + n, tb0) - tl), b2 = (int)(std::lower_bound(tl, tl + n, tb1) - tl);
-            d.sh_t0[cls] = a; d.sh_nt[cls] = b2 - a;
-        }
-        const int r_lo = (kb[rk] > 0 ? pose_grp_ptr[kb[rk] - 1] : d.sh_g0) * ROW_ALIGN;
-        const int r_hi = (kb[rk + 1] < K ? pose_grp_ptr[kb[rk + 1] + 1] : d.sh_g0 + d.sh_ng) * ROW_ALIGN;
-        for (int b = tb0; b < tb1; ++b)
-            if (h_hs[b] > 0 && (h_hmin[b] < r_lo || h_hmax[b] >= r_hi))
-                return c->fail(NRS_ERR_INVALID, "sharded solve: an edge of keyframe range [%d, %d) reaches beyond the adjacent keyframes", kb[rk], kb[rk + 1]);
-        // the per-row arrays hold [r_lo, r_hi) only (NRS_SHARD_FULL_VECTORS=1: every row): every launch below that writes one is bounded to it
-        if (Wn > 1 && !c->env("NRS_SHARD_FULL_VECTORS")) { d.row_lo = r_lo; d.row_hi = r_hi; }
-        auto foreign = [&](int b) { return h_hs[b] > 0 && (h_hmin[b] < pack_lo || h_hmax[b] >= pack_hi); };
-        for (int cls = 0; cls < 2; ++cls) {
-            const int* tl = tile_list.data() + (cls ? d.n_tiles_cls[0] : 0) + d.sh_t0[cls];
-            const int n = d.sh_nt[cls];
-            int first = n, last = -1;                              // first / last own tile of the class that is interior
-            for (int i = 0; i < n; ++i) if (!foreign(tl[i])) { first = i; break; }
-            for (int i = n - 1; i >= 0; --i) if (!foreign(tl[i])) { last = i; break; }
-            bool clean = last >= first;
-            for (int i = first; i <= last && clean; ++i) clean = !foreign(tl[i]);
-            if (!clean) { d.sh_front[cls] = n; d.sh_back[cls] = 0; continue; }
-            d.sh_front[cls] = first; d.sh_back[cls] = n - 1 - last;
-        }
-        HaloPlan& h = e->halo;
-        auto rows_of = [&](int k, size_t& off, size_t& n) { off = 3 * (size_t)pose_grp_ptr[k] * ROW_ALIGN; n = 3 * (size_t)(pose_grp_ptr[k + 1] - pose_grp_ptr[k]) * ROW_ALIGN; };
-        if (rk > 0) { rows_of(kb[rk], h.lo_send, h.lo_send_n); rows_of(kb[rk] - 1, h.lo_recv, h.lo_recv_n); }
-        if (rk < Wn - 1) { rows_of(kb[rk + 1] - 1, h.hi_send, h.hi_send_n); rows_of(kb[rk + 1], h.hi_recv, h.hi_recv_n); }
-        d.fused = 0; d.ecd = 0; d.hier = 1;                         // always the two-kernel PCG, reductions over the ranks
-    }
-    if (d.row_hi <= 0) { d.row_lo = 0; d.row_hi = n_rows; }         // (as carve: every row)
+    const std::vector<int> tile_list = tile_classes(c, d, h_hs, h_hns);
+    path_flags(c, d, s);
+    if (!d.use_lds) return NRS_OK;                                   // gather fallback: host path
+    // what the host reads off its halo lists -- a row beyond the adjacent keyframes, a row of another rank -- a tile's smallest and
+    // largest halo row decide (TileReach; the kernel leaves the two words of a tile without halo rows unwritten)
+    if (sh)
+        for (int b = tb0; b < tb1; ++b) if (!h_hs[b]) { h_hmin[b] = INT_MAX; h_hmax[b] = -1; }
+    NRS_TRY(shard_window(c, d, e->halo, s, g, tile_list, TileReach{h_hmin.data(), h_hmax.data(), h_hmin.data(), h_hmax.data()}));
+    if (d.row_hi <= 0) { d.row_lo = 0; d.row_hi = n_rows; }         // (unsharded: every row, as carve has it)
     const int row_lo = d.row_lo, row_hi = d.row_hi;
     d.ec_on = 1; d.plain = 1;
     d.lin_rb = ROW_ALIGN / (64 / T);
     d.ec_nsp = ec_nsp; d.ec_ndm = ec_ndm;
     d.ec_nblk = std::min((ec_nsp + ec_ndm + BLK - 1) / BLK, 2048);
     e->pack_rows = pack_hi - pack_lo;
-    if (tm) fprintf(stderr, "[nrs] device pack: tiles %d x %d rows, halo rows: max %d, mean %.1f, spring part max %d, classes %d (cap %d/%d) + %d (cap %d/%d)\n", n_tiles, d.tile_rows,
+    if (mark.on) fprintf(stderr, "[nrs] device pack: tiles %d x %d rows, halo rows: max %d, mean %.1f, spring part max %d, classes %d (cap %d/%d) + %d (cap %d/%d)\n", n_tiles, d.tile_rows,
                     d.max_halo, (double)n_halo / n_tiles, d.max_halo_s, d.n_tiles_cls[0], d.cap_h[0], d.cap_s[0], d.n_tiles_cls[1], d.cap_h[1], d.cap_s[1]);
     // ---- arena
-    ArenaPlan dry{arena, true};
-    {
-        Dev tmpd = d;
-        Engine te;
-        spec_pcg_sets(c, e, 0);                                    // shadow sets for speculative LM trials (carved with the arena)
-        te.n_spec = e->n_spec; te.spec_pcg = e->spec_pcg;
-        carve(dry, tmpd, false, nnz_s, nnz_d, (size_t)n_slices, n_halo, &te);
-    }
-    if (dry.off > arena->cap) {
-        arena_release(arena);
-        const size_t want = dry.off + dry.off / 8;
-        hipError_t he = hipMalloc((void**)&arena->base, want);
-        if (he != hipSuccess) return c->fail(NRS_ERR_ALLOC, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(he));
-        arena->cap = want;
-        if (c->env("NRS_POISON")) { (void)hipMemset(arena->base, 0xFF, want); (void)hipDeviceSynchronize(); }    // (debug: a read of memory nobody wrote shows up as NaN)
-    }
-    ArenaPlan real{arena, false};
-    carve(real, d, false, nnz_s, nnz_d, (size_t)n_slices, n_halo, e);
-    e->arena_bytes = real.off;
+    spec_pcg_sets(c, e, 0);                                          // shadow sets for speculative LM trials (carved with the arena)
+    NRS_TRY(arena_fit(c, arena, e, d, false, nnz_s, nnz_d, (size_t)n_slices, n_halo));
     mark("arena");
     // ---- final arrays
     NRS_HIP(c, hipMemcpyAsync(d.grp_pose, grp_pose.data(), sizeof(int) * grp_pose.size(), hipMemcpyHostToDevice, st));
@@ -905,14 +782,7 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     hipLaunchKernelGGL((k_dp_halo<1>), dim3(tb1 - tb0), dim3(256), 0, st, tb0, (int*)nullptr, (int*)nullptr, d.tile_rows, T, reinterpret_cast<uint16_t*>(d.row_tp), d.ss_ptr, d.sd_ptr, S_other, S_side, D_o, D_role, hs, hns, d.halo_ptr,
                        d.halo_rows, d.s_om, d.d_hdr, d_flag);
     if (d.fused) {
-        std::vector<int> tile_desc(8 * (size_t)n_tiles, 0);
-        const int rb = ROW_ALIGN / d.tile_rows;
-        for (int b = 0; b < n_tiles; ++b) {
-            const int kf = grp_pose[(size_t)b * d.tile_rows / ROW_ALIGN];
-            int* td = &tile_desc[8 * (size_t)b];
-            td[0] = kf; td[1] = pose_grp_ptr[kf] * rb; td[2] = pose_grp_ptr[kf + 1] * rb;
-            td[3] = halo_ptr[b]; td[4] = halo_ptr[b + 1] - halo_ptr[b];
-        }
+        const std::vector<int> tile_desc = tile_desc_build(d, g, halo_ptr);
         NRS_HIP(c, hipMemcpyAsync(d.tile_desc, tile_desc.data(), sizeof(int) * tile_desc.size(), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_dp_halofix, dim3(n_tiles), dim3(BLK), 0, st, n_tiles, d.halo_ptr, d.halo_rows, d.halo_fix, BLK, 0);
         NRS_HIP(c, hipStreamSynchronize(st));                        // (tile_desc dies here)
@@ -927,19 +797,7 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     }
     if (ec_nsp + ec_ndm > 0)
         hipLaunchKernelGGL(k_dp_ecfill, nb(std::max(ec_nsp, ec_ndm)), dim3(256), 0, st, ec_nsp, ek_s2, r_sp, r_d0, ec_ndm, ek_d2, r_dm, r_w, vrow, d.ec_sp, d.ec_dm, d.ec_w);
-    if (sh) {                                                        // slots of other ranks' tiles are never written: zero for good (as engine_create)
-        NRS_HIP(c, hipMemsetAsync(d.part_lin, 0, sizeof(double) * 32 * (size_t)d.n_groups * (size_t)d.lin_rb, st));
-        NRS_HIP(c, hipMemsetAsync(d.part_rchi, 0, sizeof(double) * (size_t)d.n_groups, st));
-        NRS_HIP(c, hipMemsetAsync(d.part_reg, 0, sizeof(double) * 2 * (size_t)d.n_regblk, st));
-        NRS_HIP(c, hipMemsetAsync(d.part_spmv, 0, sizeof(double) * NPART * (size_t)d.n_regblk, st));
-        NRS_HIP(c, hipMemsetAsync(d.red, 0, sizeof(double) * (4 + 6 * (size_t)K), st));
-        NRS_HIP(c, hipMemsetAsync(d.red_loc, 0, sizeof(double) * (4 + 6 * (size_t)K), st));
-    }
-    NRS_HIP(c, hipMemsetAsync(d.s_qc, 0, sizeof(double) * nnz_s, st));
-    NRS_HIP(c, hipMemsetAsync(d.d_s, 0, sizeof(double) * nnz_d, st));
-    NRS_HIP(c, hipMemsetAsync(d.part_apply, 0, sizeof(double) * (size_t)d.n_vecblk, st));
-    NRS_HIP(c, hipMemsetAsync(d.scal, 0, sizeof(double) * SC_N, st));
-    NRS_HIP(c, hipMemsetAsync(d.flags, 0, sizeof(int) * 8, st));
+    NRS_TRY(zero_work_arrays(c, d));
     NRS_HIP(c, hipGetLastError());
     // ---- host side of the engine
     e->vrow.swap(h_vrow);
@@ -953,13 +811,7 @@ static int engine_create_device(nrs_ctx* c, const EngineSpec& s, Arena* arena, E
     e->dev_edges = true;                                             // residual taps copy the raw edges from the pack scratch (device to device)
     e->raw_sp = r_sp; e->raw_d0 = r_d0; e->raw_dm = r_dm; e->raw_w = r_w;
     e->serial = ++c->engine_serial;
-    if (!c->pin_scal) NRS_HIP(c, hipHostMalloc((void**)&c->pin_scal, sizeof(double) * SC_N, hipHostMallocMapped | hipHostMallocCoherent));
-    if (!c->pin_flags) {
-        NRS_HIP(c, hipHostMalloc((void**)&c->pin_flags, sizeof(int) * 8, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(c->pin_flags, 0, sizeof(int) * 8);
-    }
-    e->h_scal = c->pin_scal; e->h_flags = c->pin_flags;
-    d.h_scal = c->pin_scal; d.h_flags = c->pin_flags;
+    NRS_TRY(pin_host_words(c, e));
     if (e->n_spec > 0) NRS_TRY(spec_prepare(c, e));
     NRS_HIP(c, hipStreamSynchronize(st));                            // (host staging vectors die here; the overflow word is final)
     int h_fl2[2] = {0, 0};

@@ -258,4 +258,134 @@ __global__ __launch_bounds__(BLK) void k_skin_op_rows(Dev P) {
     if (live && t == 0) { P.wv[3 * (size_t)r] = w0 + a[0]; P.wv[3 * (size_t)r + 1] = w1 + a[1]; P.wv[3 * (size_t)r + 2] = w2 + a[2]; }
 }
 
+// ---- embedded mode: set-up of the skinned observations of an engine whose rows are packed (engine_create; device arrays in a buffer of the
+// context).  A BA window (N2b: sk_pose given, K poses) solves by the PCG with the observations applied as hyper-edges; a single-frame
+// engine (N2a) by the direct solver when it takes the frame (k_nd_values folds them into its blocks) and by the same PCG form when it
+// does not.
+// Slots: observations grouped by pose (caller order inside a pose: K = 1 keeps the caller's order), every pose's padded to BLK;
+// per node row the list of the observations that reach it, in slot order.
+// A rank of a sharded window (communicator) holds the observations of its OWN keyframes [sh_k0, sh_k0 + sh_nk) only: they reach
+// node copies of their own keyframe (checked below), so everything they read or write is rank-local and no halo row is needed;
+// their pose blocks and chi2 join the all-reduced packets once (k_finalize_pack).  Observations held elsewhere: sk_slot = -1.
+// A SLICED list (s.sk_total > 0: the rank's share of a window whose lists were built on its device) holds nothing else: every entry
+// must be the rank's own, and the keyframe range it was cut for must be the one this set-up arrived at.
+static int skin_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, Arena* arena) {
+    Dev& d = e->d;
+    const bool ba_form = s.sk_pose != nullptr;
+    if (d.fused || (d.sh_on && !ba_form) || !s.sk_uv || !s.sk_X0 || !s.sk_node || !s.sk_om) return c->fail(NRS_ERR_INVALID, "skinned observations: two-kernel PCG path");
+    if (!ba_form && !(arena == &c->arena_trk && s.K == 1)) return c->fail(NRS_ERR_INVALID, "skinned observations without a pose index: single-frame tracking engines only");
+    const size_t n_in = (size_t)s.n_skin;
+    const bool sliced = s.sk_total > 0;
+    if (sliced && (!ba_form || !d.sh_on || s.sk_base < 0 || s.n_skin < 0 || (int64_t)s.sk_base + s.n_skin > s.sk_total))
+        return c->fail(NRS_ERR_INVALID, "skinned observations: a sliced list needs a sharded BA window and a slice inside the window's list");
+    if (sliced && (s.sk_k0 != d.sh_k0 || s.sk_k1 != d.sh_k0 + d.sh_nk))
+        return c->fail(NRS_ERR_STATE, "skinned observations: the list was cut for keyframes [%d, %d), the rank owns [%d, %d)", s.sk_k0, s.sk_k1, d.sh_k0, d.sh_k0 + d.sh_nk);
+    std::vector<int> pose0;
+    if (!ba_form) pose0.assign(n_in, 0);
+    const int* sk_pose = ba_form ? s.sk_pose : pose0.data();
+    const int own_k0 = d.sh_k0, own_k1 = d.sh_k0 + d.sh_nk;    // (the whole window on one GPU)
+    auto held = [&](size_t i) { return sk_pose[i] >= own_k0 && sk_pose[i] < own_k1; };
+    std::vector<int> cnt(s.K + 1, 0), pose_blk(s.K + 1, 0);
+    for (size_t i = 0; i < n_in; ++i) {
+        if (sk_pose[i] < 0 || sk_pose[i] >= s.K) return c->fail(NRS_ERR_INVALID, "skinned observation: pose index out of range");
+        if (held(i)) cnt[sk_pose[i] + 1]++;
+        else if (sliced) return c->fail(NRS_ERR_INVALID, "skinned observation: a sliced list holds an observation of keyframe %d, outside the rank's [%d, %d)", sk_pose[i], own_k0, own_k1);
+    }
+    for (int k = 0; k < s.K; ++k) pose_blk[k + 1] = pose_blk[k] + (cnt[k + 1] + BLK - 1) / BLK;
+    if (d.sh_on && pose_blk[s.K] == 0)                         // (a rank whose keyframes have none: one empty block of its first pose, so that every launch has a grid)
+        for (int k = own_k0; k < s.K; ++k) pose_blk[k + 1]++;
+    const size_t nblk = (size_t)pose_blk[s.K], n = nblk * BLK;
+    std::vector<int> next(s.K), blk_pose(nblk);
+    for (int k = 0; k < s.K; ++k) { next[k] = pose_blk[k] * BLK; for (int b2 = pose_blk[k]; b2 < pose_blk[k + 1]; ++b2) blk_pose[b2] = k; }
+    e->sk_slot.assign(n_in, -1);
+    std::vector<float> uv(2 * n, 0.f);
+    std::vector<double> X0(3 * n, 0.0), om(SK_MAX * n, 0.0);
+    std::vector<int> rows(SK_MAX * n, -1), src(n, -1);
+    std::vector<uint8_t> act(n, 0);
+    std::vector<int> rl_cnt(d.n_rows + 1, 0);
+    for (size_t i = 0; i < n_in; ++i) {
+        if (!held(i)) continue;
+        const size_t sl = (size_t)next[sk_pose[i]]++;
+        e->sk_slot[i] = (int)sl;
+        src[sl] = (int)i;
+        uv[2 * sl] = s.sk_uv[2 * i]; uv[2 * sl + 1] = s.sk_uv[2 * i + 1];
+        for (int k = 0; k < 3; ++k) X0[3 * sl + k] = s.sk_X0[3 * i + k];
+        act[sl] = 1;
+        for (int k = 0; k < SK_MAX; ++k) {
+            const int v = s.sk_node[SK_MAX * i + k];
+            if (v < 0) continue;
+            if (s.lm_pose[v] != sk_pose[i]) return c->fail(NRS_ERR_INVALID, "skinned observation: a node copy of another keyframe");
+            rows[(size_t)k * n + sl] = e->vrow[v];              // (11 x n, node-slot-major: the kernels read them coalesced)
+            om[(size_t)k * n + sl] = s.sk_om[SK_MAX * i + k];
+            rl_cnt[e->vrow[v] + 1]++;
+        }
+    }
+    // row lists (CSR over the rows that are reached), entries in slot order
+    std::vector<int> rl_row, rl_ptr(1, 0), row_list(d.n_rows, -1);
+    for (int r = 0; r < d.n_rows; ++r)
+        if (rl_cnt[r + 1] > 0) { row_list[r] = (int)rl_row.size(); rl_row.push_back(r); rl_ptr.push_back(rl_ptr.back() + rl_cnt[r + 1]); }
+    const size_t n_ent = (size_t)rl_ptr.back(), nrl = rl_row.size();
+    if (d.sh_on) {                                             // a rank's per-row arrays may be row-limited (biased pointers, ArenaPlan::get_rows):
+        const int own_lo = d.sh_g0 * ROW_ALIGN, own_hi = (d.sh_g0 + d.sh_ng) * ROW_ALIGN;   // no launch may reach a row it does not own
+        for (size_t q = 0; q < rows.size(); ++q)
+            if (rows[q] >= 0 && (rows[q] < own_lo || rows[q] >= own_hi)) return c->fail(NRS_ERR_INVALID, "skinned observation: node row %d outside the rank's rows [%d, %d)", rows[q], own_lo, own_hi);
+        for (size_t l = 0; l < nrl; ++l)
+            if (rl_row[l] < own_lo || rl_row[l] >= own_hi) return c->fail(NRS_ERR_INVALID, "skinned observations: row list %d outside the rank's rows [%d, %d)", rl_row[l], own_lo, own_hi);
+    }
+    std::vector<int> rl_obs(n_ent + 1), fill(rl_ptr.begin(), rl_ptr.end() - 1);
+    std::vector<double> rl_om(n_ent + 1);
+    for (size_t sl = 0; sl < n; ++sl)
+        for (int k = 0; k < SK_MAX; ++k) {
+            const int r = rows[(size_t)k * n + sl];
+            if (r < 0) continue;
+            const int q = fill[row_list[r]]++;
+            rl_obs[q] = (int)sl; rl_om[q] = om[(size_t)k * n + sl];
+        }
+    auto al = [](size_t b2) { return (b2 + 255) & ~(size_t)255; };
+    const size_t o_uv = 0, o_X0 = o_uv + al(8 * n), o_row = o_X0 + al(24 * n), o_om = o_row + al(4 * SK_MAX * n), o_act = o_om + al(8 * SK_MAX * n),
+                 o_bp = o_act + al(n), o_pb = o_bp + al(4 * nblk), o_rr = o_pb + al(4 * (s.K + 1)), o_rp = o_rr + al(4 * (nrl + 1)), o_ro = o_rp + al(4 * (nrl + 1)),
+                 o_rw = o_ro + al(4 * (n_ent + 1)), o_rec = o_rw + al(8 * (n_ent + 1)), o_part = o_rec + al(8 * 27 * n), o_chi = o_part + al(8 * 32 * nblk),
+                 o_md = o_chi + al(8 * n), o_g = o_md + 256, o_op = o_g + al(8 * 4 * n), o_rq = o_op + al(8 * 8 * nblk), o_src = o_rq + al(8 * (size_t)d.n_rows), o_recT = o_src + al(4 * n),
+                 o_dop = o_recT + al(8 * 24 * n), o_spec = o_dop + (d.use_lds ? 0 : al(8 * 6 * (size_t)d.n_rows)),
+                 spec_stride = al(8 * 32 * nblk) + al(8 * n), total = o_spec + (size_t)e->n_spec * spec_stride;   // (shadow sets of sk_part / sk_chi: speculative trials)
+    DevBuf& buf = arena == &c->arena_trk ? c->nd_skin : c->dba_skin;
+    NRS_TRY(c->ensure(buf, total));
+    e->sk_bytes = total;
+    char* sb = buf.as<char>();
+    auto up = [&](size_t off, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(sb + off, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+    NRS_HIP(c, up(o_uv, uv.data(), 8 * n)); NRS_HIP(c, up(o_X0, X0.data(), 24 * n)); NRS_HIP(c, up(o_row, rows.data(), 4 * SK_MAX * n));
+    NRS_HIP(c, up(o_om, om.data(), 8 * SK_MAX * n)); NRS_HIP(c, up(o_act, act.data(), n)); NRS_HIP(c, up(o_bp, blk_pose.data(), 4 * nblk));
+    NRS_HIP(c, up(o_pb, pose_blk.data(), 4 * (size_t)(s.K + 1))); NRS_HIP(c, up(o_rr, rl_row.data(), 4 * nrl)); NRS_HIP(c, up(o_rp, rl_ptr.data(), 4 * (nrl + 1)));
+    NRS_HIP(c, up(o_ro, rl_obs.data(), 4 * n_ent)); NRS_HIP(c, up(o_rw, rl_om.data(), 8 * n_ent));
+    NRS_HIP(c, hipMemsetAsync(sb + o_rec, 0, total - o_rec, c->stream));
+    std::vector<int> row_q(2 * (size_t)d.n_rows, 0);           // per row: its list's range (k_pcg_update<true> / k_skin_op_rows go by rows)
+    for (size_t l = 0; l < nrl; ++l) { row_q[2 * (size_t)rl_row[l]] = rl_ptr[l]; row_q[2 * (size_t)rl_row[l] + 1] = rl_ptr[l + 1]; }
+    NRS_HIP(c, up(o_rq, row_q.data(), 8 * (size_t)d.n_rows));
+    NRS_HIP(c, up(o_src, src.data(), 4 * n));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    d.sk_n = (int)n; d.sk_nblk = (int)nblk; d.sk_pcg = 1;      // (a single-frame engine on the direct solver switches sk_pcg off below)
+    d.sk_uv = reinterpret_cast<const float*>(sb + o_uv); d.sk_X0 = reinterpret_cast<const double*>(sb + o_X0);
+    d.sk_row = reinterpret_cast<const int*>(sb + o_row); d.sk_om = reinterpret_cast<const double*>(sb + o_om);
+    d.sk_active = reinterpret_cast<const uint8_t*>(sb + o_act);
+    d.sk_blk_pose = reinterpret_cast<const int*>(sb + o_bp); d.sk_pose_blk = reinterpret_cast<const int*>(sb + o_pb);
+    d.sk_nrl = (int)nrl; d.sk_rl_row = reinterpret_cast<const int*>(sb + o_rr); d.sk_rl_ptr = reinterpret_cast<const int*>(sb + o_rp);
+    d.sk_rl_obs = reinterpret_cast<const int*>(sb + o_ro); d.sk_rl_om = reinterpret_cast<const double*>(sb + o_rw);
+    d.sk_rec = reinterpret_cast<double*>(sb + o_rec); d.sk_part = reinterpret_cast<double*>(sb + o_part);
+    d.sk_chi = reinterpret_cast<double*>(sb + o_chi); d.sk_maxdiag = reinterpret_cast<double*>(sb + o_md);
+    d.sk_g = reinterpret_cast<double*>(sb + o_g); d.sk_opart = reinterpret_cast<double*>(sb + o_op); d.sk_row_q = reinterpret_cast<const int*>(sb + o_rq);
+    d.sk_recT = reinterpret_cast<double*>(sb + o_recT); d.sk_src = reinterpret_cast<const int*>(sb + o_src);
+    d.D_op = d.use_lds ? nullptr : reinterpret_cast<double*>(sb + o_dop);
+    for (int j = 0; j < e->n_spec; ++j) {
+        e->spec[j].sk_part = reinterpret_cast<double*>(sb + o_spec + (size_t)j * spec_stride);
+        e->spec[j].sk_chi = reinterpret_cast<double*>(sb + o_spec + (size_t)j * spec_stride + al(8 * 32 * nblk));
+    }
+    d.sk_base = ba_form ? d.xl_init : nullptr;                 // (tracking form: the rows ARE the deformations, X0 + sum om x)
+    e->sk_total = s.sk_window(); e->sk_base = sliced ? s.sk_base : 0;
+    if (!ba_form) {                                            // (the direct solver's plan reads them; a BA window's positions come from k_skin_positions)
+        e->sk_vert.assign(s.sk_node, s.sk_node + SK_MAX * n_in);
+        e->sk_om.assign(s.sk_om, s.sk_om + SK_MAX * n_in);
+    }
+    return NRS_OK;
+}
+
 }  // namespace nrs
