@@ -173,6 +173,7 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *                 instead of the step's residual tested on its own)
  *   sharding      NRS_SHARD_PACK_ALL, NRS_SHARD_FULL_VECTORS
  *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR
+ *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
  * (what each selects: README.md "Debug switches"; the A/B tests drive every launch form through nrs_debug_set). */
 int nrs_debug_set(nrs_ctx* ctx, const char* name /* "NRS_..." */, const char* value /* NULL: unset */);
 void nrs_destroy(nrs_ctx* ctx);
@@ -743,6 +744,57 @@ void nrs_init_options_init(nrs_init_options* opt);
  * n_matches above the TRACKED count, a sample index outside the compact range. */
 int nrs_init_essential(nrs_ctx* ctx, const nrs_camera* cam, const nrs_init_options* opt, int32_t n, const float* ref_xy,
                        const float* cur_xy, const int32_t* status, int32_t n_matches, const int32_t* samples, nrs_init_result* out);
+
+/* ---- f7: evaluation -- FrameEvaluator (modules/utilities/frame_evaluator.cc) and its two sources of ground truth, the stereo matchers
+ * (modules/stereo/) and a depth image.  Arithmetic and the stated departures: DESIGN.md 4 "Evaluation (f7)".  Per-point status: */
+typedef enum {
+    NRS_EVAL_OK = 0,
+    NRS_EVAL_OUT_OF_BOUNDS = 1,      /* either boundary test of the pattern matcher; the last column / row of a depth image             */
+    NRS_EVAL_SATURATED = 2,          /* template maximum above 250                                                                    */
+    NRS_EVAL_LOW_CORRELATION = 3,    /* best CCORR_NORMED below 0.99                                                                  */
+    NRS_EVAL_ZERO_DISPARITY = 4,     /* departure: the reference returns +-inf here and aborts later in the evaluator's CHECK          */
+    NRS_EVAL_BAD_DEPTH = 5,          /* interpolated depth not finite                                                                 */
+    NRS_EVAL_NOT_TRACKED = 6,        /* LK stereo: the tracker's status is not NRS_TRACKED                                            */
+    NRS_EVAL_ROW_DIFFERENCE = 7      /* LK stereo: |dy| > 2                                                                           */
+} nrs_eval_status;
+
+/* StereoPatternMatching::computeStereo3D for n keypoints (stereo_pattern_matching.cc:33-94): 15 x 15 template of the left image around
+ * (int)(x-7), (int)(y-7), TM_CCORR_NORMED against the search region (0, 0, w-3, 2*(int)((h-1)/2.f-2)) of the right image, first
+ * row-major maximum, rejected below 0.99.  Sums are exact integers, the score is fp64 (0 where a norm is 0).  cam supplies fx fy cx cy;
+ * bf is the matcher's baseline_.  xyz of a rejected point is NaN; score / match_xy (top-left corner of the best window) are NaN / -1
+ * for status 1 and 2.  Strides in bytes.  NRS_STEREO_NO_MFMA=1 (nrs_debug_set) selects the plain integer form of the correlation.
+ * NRS_ERR_INVALID: an image smaller than 32 x 32 (no search position left). */
+int nrs_stereo_match_pattern(nrs_ctx* ctx, const nrs_camera* cam, float bf, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h,
+                             int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, float* xyz, int32_t* status, double* score,
+                             int32_t* match_xy);
+
+/* The precomputed_depth_ branch of FrameEvaluator::ComputeGroundTruth (frame_evaluator.cc:265-278): Interpolate (geometry_toolbox.h:47-60)
+ * of an fp32 depth image (stride in floats) at the keypoint, times Unproject(keypoint) / its z.  Status 1 for x < 0, y < 0, x >= w-1 or
+ * y >= h-1 (departure: the reference reads past the image), 5 for a depth that is not finite; gt_xyz is NaN for both. */
+int nrs_eval_depth_ground_truth(nrs_ctx* ctx, const nrs_camera* cam, const float* depth, int32_t w, int32_t h, int32_t stride, int32_t n,
+                                const float* xy, float* gt_xyz, int32_t* gt_status);
+
+/* The loop of StereoLucasKanade::ComputeStereo3D (stereo_lucas_kanade.cc:50-72) on the tracker's output; the matcher itself is
+ * nrs_klt_set_reference(left) + nrs_klt_track(right, use_initial_flow = 1, min_ssim = 0.5) on a context kept for stereo.
+ * Host code, no context. */
+int nrs_stereo_from_tracks(const nrs_camera* cam, float bf, int32_t n, const float* left_xy, const float* right_xy,
+                           const int32_t* track_status, float* xyz, int32_t* status);
+
+/* ComputeReconstructionRMSE / ComputeRMSEWithScaleAlignment / ComputeRMSEWithoutScaleAlignment (frame_evaluator.cc:54-226) on the depths
+ * of the points with gt_ok != 0.  counts: valid, kept by the IQR gate, n_inliers.  inlier (nullable): n flags of the last iteration.
+ * Host code, no context.  NRS_ERR_INVALID with rmse = scale = NaN when n_inliers < 1 or no point is valid. */
+int nrs_eval_rmse(int32_t n, const float* est_z, const float* gt_z, const uint8_t* gt_ok, int32_t align_scales, int32_t precomputed_depth,
+                  float* rmse, float* scale, int32_t counts[3], uint8_t* inlier);
+
+/* EvaluateFrameReconstruction + SaveGroundTruthToFrame (frame_evaluator.cc:35-52, 291-305) for the n TRACKED_WITH_3D points of a frame:
+ * pose_qt = T_camera_world (xyzw, t) in float, world_xyz their positions, xy their keypoints.  Ground truth: a depth image (depth != NULL:
+ * nrs_eval_depth_ground_truth on ctx, precomputed_depth semantics) or gt_xyz / gt_status of a stereo matcher (ctx may be NULL then).
+ * The camera-frame depth is the z row of the SE3f action (host function se3f_act_z of csrc/nrs_eval_host.hpp, the arithmetic of se3f_act
+ * in py/nrs_frame_loop.py).  Outputs: nrs_eval_rmse's rmse / scale / counts, gt_world = T^-1 * (gt / scale) (n x 3, NaN without ground
+ * truth; nullable) and gt_status_out (n; nullable).  An nrs_eval_rmse failure is returned as is, with gt_status_out filled. */
+int nrs_eval_frame(nrs_ctx* ctx, const nrs_camera* cam, const float pose_qt[7], int32_t n, const float* world_xyz, const float* xy,
+                   const float* depth, int32_t w, int32_t h, int32_t stride, const float* gt_xyz, const int32_t* gt_status,
+                   float* rmse, float* scale, int32_t counts[3], float* gt_world, int32_t* gt_status_out);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,8 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
            "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_triangulate_batch", "nrs_track_deform_solve_rg",
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
-           "nrs_init_options_init", "nrs_init_essential"]
+           "nrs_init_options_init", "nrs_init_essential",
+           "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame"]
 
 
 class NrsError(RuntimeError):
@@ -182,6 +183,50 @@ def shard_plan_counts(kf_vertices, world, lib=None):
     if rc != OK:
         raise NrsError(rc, "nrs_shard_plan_counts")
     return kb
+
+
+# ---- f7: evaluation (include/nrs.h "f7: evaluation").  nrs_eval_status:
+EVAL_OK, EVAL_OUT_OF_BOUNDS, EVAL_SATURATED, EVAL_LOW_CORRELATION, EVAL_ZERO_DISPARITY, EVAL_BAD_DEPTH, EVAL_NOT_TRACKED, EVAL_ROW_DIFFERENCE = range(8)
+
+
+def eval_rmse(est_z, gt_z, gt_ok, align_scales=True, precomputed_depth=False, lib=None):
+    """nrs_eval_rmse (host only).  -> (rmse, scale, (valid, kept, n_inliers), inlier mask, rc); rc = -1 (NRS_ERR_INVALID) where no RMSE
+    exists (rmse and scale are NaN then)"""
+    lib = lib or load_library()
+    est, gt, ok = _f32(est_z), _f32(gt_z), np.ascontiguousarray(gt_ok, np.uint8)
+    n = len(est)
+    assert len(gt) == n and len(ok) == n
+    rmse, scale = C.c_float(0), C.c_float(0)
+    counts = (C.c_int32 * 3)()
+    inl = np.zeros(n, np.uint8)
+    rc = lib.nrs_eval_rmse(C.c_int32(n), _p(est, C.c_float), _p(gt, C.c_float), _p(ok, C.c_uint8), C.c_int32(1 if align_scales else 0),
+                           C.c_int32(1 if precomputed_depth else 0), C.byref(rmse), C.byref(scale), counts, _p(inl, C.c_uint8))
+    return np.float32(rmse.value), np.float32(scale.value), tuple(counts), inl.astype(bool), rc
+
+
+def stereo_from_tracks(cam, bf, left_xy, right_xy, track_status, lib=None):
+    """nrs_stereo_from_tracks (host only) -> (xyz [n,3], status [n])"""
+    lib = lib or load_library()
+    l, r, st = _f32(left_xy).reshape(-1, 2), _f32(right_xy).reshape(-1, 2), _i32(track_status)
+    n = len(l)
+    assert len(r) == n and len(st) == n
+    xyz, status = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+    rc = lib.nrs_stereo_from_tracks(C.byref(cam), C.c_float(bf), C.c_int32(n), _p(l, C.c_float), _p(r, C.c_float), _p(st, C.c_int32),
+                                    _p(xyz, C.c_float), _p(status, C.c_int32))
+    if rc != OK:
+        raise NrsError(rc, "nrs_stereo_from_tracks")
+    return xyz, status
+
+
+def stereo_lk(ctx_stereo, cam, bf, left, right, xy, min_ssim=0.5):
+    """StereoLucasKanade::ComputeStereo3D (stereo_lucas_kanade.cc:38-75): SetReferenceImage(left), Track(right, initial flow, min_ssim) and
+    the disparity step.  ctx_stereo is a context kept for stereo (configured with klt_configure): these calls replace its tracker's
+    reference, so it must not be the context that holds the tracking templates.  -> (xyz, status, right_xy, track_status)"""
+    xy = _f32(xy).reshape(-1, 2)
+    ctx_stereo.klt_set_reference(left, xy)
+    rxy, st, _, _ = ctx_stereo.klt_track(right, xy, np.full(len(xy), 1, np.int32), initial_flow=True, min_ssim=min_ssim)
+    xyz, status = stereo_from_tracks(cam, bf, xy, rxy, st, ctx_stereo.lib)
+    return xyz, status, rxy, st
 
 
 class LocalGroup:
@@ -606,6 +651,62 @@ class Context:
             if samples is None:
                 r.update(labels=a["labels"], centres=a["centres"])
         return r
+
+    # ---- f7: evaluation
+    def stereo_match_pattern(self, cam, bf, left, right, xy, stride_l=None, stride_r=None, width=None):
+        """nrs_stereo_match_pattern -> (xyz [n,3], status [n], score [n] fp64, match_xy [n,2]).  left / right: h x w uint8, or (with width)
+        h x stride arrays whose first `width` columns are the image"""
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        h = left.shape[0]
+        w = left.shape[1] if width is None else int(width)
+        xy = _f32(xy).reshape(-1, 2)
+        n = len(xy)
+        xyz, status = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        score, match = np.zeros(n, np.float64), np.zeros((n, 2), np.int32)
+        self._chk(self.lib.nrs_stereo_match_pattern(self.h, C.byref(cam), C.c_float(bf), _p(left, C.c_uint8), _p(right, C.c_uint8), C.c_int32(w),
+                                                    C.c_int32(h), C.c_int32(stride_l or left.strides[0]), C.c_int32(stride_r or right.strides[0]),
+                                                    C.c_int32(n), _p(xy, C.c_float), _p(xyz, C.c_float), _p(status, C.c_int32),
+                                                    _p(score, C.c_double), _p(match, C.c_int32)))
+        return xyz, status, score, match
+
+    def eval_depth_ground_truth(self, cam, depth, xy):
+        """nrs_eval_depth_ground_truth -> (gt_xyz [n,3], gt_status [n]); depth: h x w float32 (a row-strided view is passed as it is)"""
+        depth = np.asarray(depth, np.float32)
+        if depth.strides[1] != 4 or depth.strides[0] % 4:
+            depth = np.ascontiguousarray(depth)
+        h, w = depth.shape
+        xy = _f32(xy).reshape(-1, 2)
+        n = len(xy)
+        gt, st = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        self._chk(self.lib.nrs_eval_depth_ground_truth(self.h, C.byref(cam), C.c_void_p(depth.ctypes.data), C.c_int32(w), C.c_int32(h),
+                                                       C.c_int32(depth.strides[0] // 4), C.c_int32(n), _p(xy, C.c_float), _p(gt, C.c_float),
+                                                       _p(st, C.c_int32)))
+        return gt, st
+
+    def eval_frame(self, cam, pose_q, pose_t, world_xyz, xy, depth=None, gt_xyz=None, gt_status=None):
+        """nrs_eval_frame -> dict(rmse, scale, counts, gt_world [n,3], gt_status [n], rc): ground truth from a depth image, or from a
+        stereo matcher's gt_xyz / gt_status.  rc = -1 with rmse = scale = NaN when the frame has too few points with ground truth"""
+        qt = _f32(np.concatenate([np.asarray(pose_q, np.float32), np.asarray(pose_t, np.float32)]))
+        X, xy = _f32(world_xyz).reshape(-1, 3), _f32(xy).reshape(-1, 2)
+        n = len(X)
+        assert len(xy) == n
+        rmse, scale = C.c_float(0), C.c_float(0)
+        counts = (C.c_int32 * 3)()
+        gw, st = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        d, w, h, stride, g, gs = None, 0, 0, 0, None, None
+        if depth is not None:
+            d = np.ascontiguousarray(depth, np.float32)
+            h, w = d.shape
+            stride = w
+        else:
+            g, gs = _f32(gt_xyz).reshape(-1, 3), _i32(gt_status)
+            assert len(g) == n and len(gs) == n
+        rc = self.lib.nrs_eval_frame(self.h, C.byref(cam), _p(qt, C.c_float), C.c_int32(n), _p(X, C.c_float), _p(xy, C.c_float), _p(d, C.c_float),
+                                     C.c_int32(w), C.c_int32(h), C.c_int32(stride), _p(g, C.c_float), _p(gs, C.c_int32), C.byref(rmse),
+                                     C.byref(scale), counts, _p(gw, C.c_float), _p(st, C.c_int32))
+        if rc not in (OK, -1) or (rc == -1 and not np.isnan(rmse.value)):
+            self._chk(rc)
+        return dict(rmse=np.float32(rmse.value), scale=np.float32(scale.value), counts=tuple(counts), gt_world=gw, gt_status=st, rc=rc)
 
     # ---- a19 / a20
     def graph_select_neighbours(self, g):

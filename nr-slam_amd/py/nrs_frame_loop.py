@@ -208,9 +208,29 @@ class GpuBackend:
             return r
         return self.ctx.track_deform_solve(self.cam, graph, map_pos, f_map, f_status, f_uv, f_pos, q, t, scale, self.last_trace)
 
+    # ---- evaluation (include/nrs.h "f7: evaluation"): FrameEvaluator::EvaluateFrameReconstruction and its sources of ground truth
+    def eval_frame(self, q, t, X, kp, depth=None, gt_xyz=None, gt_status=None):
+        return self.ctx.eval_frame(self.cam, q, t, X, kp, depth=depth, gt_xyz=gt_xyz, gt_status=gt_status)
+
+    def stereo_pattern(self, left, right, kp, bf):
+        xyz, st, _, _ = self.ctx.stereo_match_pattern(self.cam, bf, left, right, kp)
+        return xyz, st
+
+    # the reference's LK stereo matcher owns its tracker (SLAM/system.cc:45-54): a third context, made on first use, so that the
+    # tracking templates of self.ctx are left alone
+    def stereo_lk(self, left, right, kp, bf, min_ssim=0.5):
+        if getattr(self, "ctx_stereo", None) is None:
+            o = self.klt_opts
+            self.ctx_stereo = self.nrs.Context()
+            self.ctx_stereo.klt_configure(o["win"], o["max_level"], o["max_iters"], o["epsilon"], o["min_eig"])
+        xyz, st, _, _ = self.nrs.stereo_lk(self.ctx_stereo, self.cam, bf, left, right, kp, min_ssim)
+        return xyz, st
+
     def close(self):
         if self.rg is not None:
             self.rg.close()
+        if getattr(self, "ctx_stereo", None) is not None:
+            self.ctx_stereo.close()
         self.ctx.close()
         self.ctx_reuse.close()
 
@@ -367,6 +387,31 @@ class FrameLoop:
                              kp_2d=self.kp[self.map_index < 0].copy(),
                              status_by_map=self._status_by_map(), pos_by_map=self._pos_by_map()))
         return n3d >= 10
+
+    # ---- FrameEvaluator::EvaluateFrameReconstruction (frame_evaluator.cc:35-52), called after track_image as System::TrackImageWithDepth
+    # does (SLAM/system.cc:162-187)
+    def evaluate(self, depth=None, right=None, matcher="pattern", left=None, bf=1.0):
+        """Scores the current frame: the TRACKED_WITH_3D slots against a depth image (fp32, h x w) or against a stereo matcher run on
+        (left, right) grey images -- matcher "pattern" (StereoPatternMatching) or "lk" (StereoLucasKanade); bf is the matcher's baseline_.
+        Appends dict(rmse, scale, counts, n, rc) to self.rmse and returns it (rmse NaN, rc -1: too few points with ground truth); the
+        world-frame ground truth of the evaluated slots is kept in self.ground_truth (slot indices in self.ground_truth_slots)."""
+        if not hasattr(self, "rmse"):
+            self.rmse = []
+        slots = np.nonzero(self.status == TRACKED_WITH_3D)[0]
+        kp, X = self.kp[slots], self.pos[slots]
+        if depth is not None:
+            r = self.b.eval_frame(self.pose[0], self.pose[1], X, kp, depth=depth)
+        else:
+            if right is None or left is None:
+                raise ValueError("evaluate: a depth image, or the left and right images of a stereo pair")
+            if matcher not in ("pattern", "lk"):
+                raise ValueError("evaluate: matcher %r" % (matcher,))
+            gt, st = (self.b.stereo_pattern if matcher == "pattern" else self.b.stereo_lk)(left, right, kp, bf)
+            r = self.b.eval_frame(self.pose[0], self.pose[1], X, kp, gt_xyz=gt, gt_status=st)
+        self.ground_truth, self.ground_truth_slots = r["gt_world"], slots
+        rec = dict(rmse=r["rmse"], scale=r["scale"], counts=r["counts"], n=len(slots), rc=r["rc"])
+        self.rmse.append(rec)
+        return rec
 
     def _status_by_map(self):
         s = np.full(len(self.map_pos), -1, np.int32)

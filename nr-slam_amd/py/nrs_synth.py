@@ -667,3 +667,89 @@ def make_init_sequence(n_points=500, n_frames=8, seed=3, wh=(320, 240), step=0.3
         images.append(np.clip(np.rint(v), 0, 255).astype(np.uint8))
     return dict(model=PINHOLE, prm=prm, wh=(w, h), images=images, R=poses_R, t=poses_t, X=X, uv_true=[u.astype(F32) for u in uvt],
                 radians_per_pixel=float(1.0 / prm[0]))
+
+
+# ---- f7: evaluation (include/nrs.h "f7: evaluation")
+def make_stereo_pair(wh, seed, disparities=(7, 0), n_keypoints=24, row_pad=0, repeat=True):
+    """A rectified pair for the stereo matchers: the left image is `_texture` (clipped to 250, so that nothing saturates by accident), the
+    right image is the same texture shifted by an integer disparity per horizontal band (len(disparities) bands of equal height): the
+    left pixel (x, y) of a band with disparity d is found at (x - d, y).  Keypoints sit on templates that lie inside one band; every
+    second one gets a fractional part.  Planted specials, all listed in the result: one keypoint whose template holds a 255 pixel
+    (saturated), one on integer coordinates in a band of disparity 0 (when there is one), one in each boundary band of
+    StereoPatternMatching::computeStereo3D, and (repeat) one whose right-image patch is copied to the top-left corner of the search
+    region, so that its best score is attained twice and the first row-major position, the copy, must win.
+    row_pad > 0: `left_rows` / `right_rows` are h x (w + row_pad) arrays whose pad columns hold 255, for callers that pass a row stride.
+    -> dict(left, right, xy, disparity (planted, -1 for boundary keypoints), kind (per keypoint: "ok", "saturated", "zero", "tie",
+    "boundary"), match (expected top-left corner of the best window, -1 for rejected ones), expect_status)"""
+    rng = np.random.default_rng(seed)
+    w, h = wh
+    dmax = int(max(disparities))
+    tex = np.clip(np.rint(_texture(h, w + dmax, rng, 0)), 0, 250).astype(np.uint8)
+    nb = len(disparities)
+    edges = [int(round(b * h / nb)) for b in range(nb + 1)]
+    left = tex[:, :w].copy()
+    right = np.zeros((h, w), np.uint8)
+    band_of = np.zeros(h, np.int32)
+    for b, d in enumerate(disparities):
+        right[edges[b]:edges[b + 1]] = tex[edges[b]:edges[b + 1], d:d + w]
+        band_of[edges[b]:edges[b + 1]] = b
+    cand = [(x, y) for y in range(7, h - 20) for x in range(27 + dmax, w - 20, 3)
+            if band_of[y - 7] == band_of[y + 7] and y % 2 == 0]
+    order = rng.permutation(len(cand))
+    cand = [cand[i] for i in order]
+    sat = cand[0]
+    cand = [c for c in cand[1:] if max(abs(c[0] - sat[0]), abs(c[1] - sat[1])) > 15]
+    xy, kind, disp = [(float(sat[0]), float(sat[1]))], ["saturated"], [int(disparities[band_of[sat[1]]])]
+    left[sat[1] + 2, sat[0] - 3] = 255
+    if 0 in disparities:
+        z = next(c for c in cand if disparities[band_of[c[1]]] == 0)
+        cand.remove(z)
+        xy.append((float(z[0]), float(z[1]))); kind.append("zero"); disp.append(0)
+    if repeat:
+        t = next(c for c in cand if disparities[band_of[c[1]]] > 0)
+        cand.remove(t)
+        d = int(disparities[band_of[t[1]]])
+        xy.append((float(t[0]), float(t[1]))); kind.append("tie"); disp.append(d)
+        right[0:15, 0:15] = right[t[1] - 7:t[1] + 8, t[0] - 7 - d:t[0] + 8 - d]
+    bounds = [(21.5, h / 2.0), (w - 19.5, h / 2.0), (w / 2.0, h - 19.5), (w / 2.0, 5.0), (-1.0, h / 2.0)]
+    n_reg = max(0, n_keypoints - len(xy) - len(bounds))
+    for k, c in enumerate(cand[:n_reg]):
+        fr = (0.0, 0.0) if k % 2 == 0 else (float(rng.choice([0.25, 0.5, 0.75])), float(rng.choice([0.0, 0.5])))
+        xy.append((c[0] + fr[0], c[1] + fr[1])); kind.append("ok"); disp.append(int(disparities[band_of[c[1]]]))
+    for b in bounds:
+        xy.append(b); kind.append("boundary"); disp.append(-1)
+    xy = np.array(xy, F32)
+    match = np.full((len(xy), 2), -1, np.int32)
+    for i, k in enumerate(kind):
+        if k in ("ok", "zero"):
+            match[i] = (int(xy[i, 0] - 7) - disp[i], int(xy[i, 1] - 7))
+        elif k == "tie":
+            match[i] = (0, 0)
+    # nrs_eval_status expected of each keypoint: 0 OK, 1 out of bounds, 2 saturated, 4 zero disparity (integer x in a band of disparity 0)
+    expect = np.array([dict(saturated=2, boundary=1, zero=4, tie=0).get(k, 4 if (disp[i] == 0 and xy[i, 0] == int(xy[i, 0])) else 0)
+                       for i, k in enumerate(kind)], np.int32)
+    out = dict(wh=(w, h), left=left, right=right, xy=xy, disparity=np.array(disp, np.int32), kind=kind, match=match, expect_status=expect)
+    if row_pad:
+        for name, im in (("left_rows", left), ("right_rows", right)):
+            full = np.full((h, w + row_pad), 255, np.uint8)
+            full[:, :w] = im
+            out[name] = full
+    return out
+
+
+def make_depth_image(sq, frame):
+    """The fp32 depth image of frame `frame` of a make_frame_sequence scene: the camera-frame z of the true surface points at their true
+    image positions, interpolated densely (linear inside their hull, nearest outside), in map units."""
+    from scipy.interpolate import griddata
+    w, h = sq["wh"]
+    q = np.asarray(sq["pose_q"][frame], np.float64)
+    x, y, z, s = q
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * s), 2 * (x * z + y * s)],
+                  [2 * (x * y + z * s), 1 - 2 * (x * x + z * z), 2 * (y * z - x * s)],
+                  [2 * (x * z - y * s), 2 * (y * z + x * s), 1 - 2 * (x * x + y * y)]])
+    zc = (np.asarray(sq["X_true"][frame], np.float64) @ R.T + np.asarray(sq["pose_t"][frame], np.float64))[:, 2]
+    uv = np.asarray(sq["uv_true"][frame], np.float64)
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    lin = griddata(uv, zc, (xs, ys), method="linear")
+    near = griddata(uv, zc, (xs, ys), method="nearest")
+    return np.where(np.isnan(lin), near, lin).astype(F32)
