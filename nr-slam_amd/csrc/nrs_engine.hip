@@ -63,221 +63,9 @@
 #include "nrs_engine_kft_setup.hpp"
 #include "nrs_engine_devpack.hpp"
 #include "nrs_engine_embwin.hpp"
+#include "nrs_engine_launch.hpp"      // kernel-variant dispatch (with_lanes, the launchers, Timer) and, through it, nrs_engine_probes.hpp
 
 namespace nrs {
-
-// HIP-event timing when profiling is on.  An event pair around ONE launch of a 20 us kernel reads 4-5 us high (the gaps
-// between the events and the kernel); the two kernels the roofline lines are about -- both idempotent: they read the state
-// and write factors / products -- are therefore launched PROFILE_REPS times back to back inside one pair and the time is
-// divided, which is also how the operator runs in the solve (launch after launch) and what the rocprofv3 trace shows.
-constexpr int PROFILE_REPS = 4;
-struct Timer {
-    nrs_ctx* c;
-    double* acc;
-    int64_t* cnt;
-    int reps;
-    Timer(nrs_ctx* c_, double* a, int64_t* n, int reps_ = 1) : c(c_), acc(a), cnt(n), reps(reps_) {
-        if (c->opt.profile) (void)hipEventRecord(c->ev0, c->stream);
-    }
-    ~Timer() {
-        if (c->opt.profile) {
-            (void)hipEventRecord(c->ev1, c->stream);
-            (void)hipEventSynchronize(c->ev1);
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-            *acc += ms / reps;
-            *cnt += 1;
-        }
-    }
-};
-
-template <bool LIN, bool LDS>
-static void launch_reg2(nrs_ctx* c, const Dev& d, const double* xl, size_t shm, int n, int cls) {
-    const dim3 g(((n + 7) / 8) * 8), b(BLK);
-    if constexpr (LIN && LDS) {
-        if (d.plain) {                                             // plain BA window: the specialised pass
-            const bool tp = d.tp_ok != 0;
-            switch (d.T) {
-                case 1: hipLaunchKernelGGL((k_lin_plain<1>), g, b, shm, c->stream, d, xl, cls); break;
-                case 4: hipLaunchKernelGGL((k_lin_plain<4>), g, b, shm, c->stream, d, xl, cls); break;
-                case 8:
-                    if (tp) hipLaunchKernelGGL((k_lin_plain<8, 4, -1, true>), g, b, shm, c->stream, d, xl, cls);
-                    else hipLaunchKernelGGL((k_lin_plain<8>), g, b, shm, c->stream, d, xl, cls);
-                    break;
-                case 16: hipLaunchKernelGGL((k_lin_plain<16>), g, b, shm, c->stream, d, xl, cls); break;
-                default:
-#ifdef NRS_DEBUG_PROBES
-                    if (d.cam.model == 0 && tp && c->env("NRS_LIN_EXP")) {     // timing experiments (wrong results): a piece of the pass removed
-                        switch (atoi(c->env("NRS_LIN_EXP"))) {
-                            case 1: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 1>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 2: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 2>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 3: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 3>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 4: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 4>), g, b, shm, c->stream, d, xl, cls); break;
-                            // round 5 (4-byte damper headers throughout; 6..9 compute right results): 5 half the damper slots,
-                            // 6 non-temporal streams, 7 two waves per SIMD with 8-slot batches, 8 the same with 10, 9 three waves with 6
-                            case 5: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 5, true>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 6: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 0, true, false, false, 4, true>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 7: hipLaunchKernelGGL((k_lin_plain<2, 2, 0, true, 0, true, false, false, 8>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 8: hipLaunchKernelGGL((k_lin_plain<2, 2, 0, true, 0, true, false, false, 10>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 9: hipLaunchKernelGGL((k_lin_plain<2, 3, 0, true, 0, true, false, false, 6>), g, b, shm, c->stream, d, xl, cls); break;
-                            case 10: hipLaunchKernelGGL((k_lin_plain<2, 2, 0, true, 0, true, false, false, 8, true>), g, b, shm, c->stream, d, xl, cls); break;
-                            default: hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 0, true>), g, b, shm, c->stream, d, xl, cls); break;
-                        }
-                        break;
-                    }
-#endif
-                    if (d.h4 && rc_of(d, cls)) {                             // the operator re-forms the factors: nothing stored per incidence
-#define NRS_LIN_RC(CAMV) switch (rc_of(d, cls)) { \
-    case 1: hipLaunchKernelGGL((k_lin_plain<2, 4, CAMV, true, 0, true, true, false>), g, b, shm, c->stream, d, xl, cls); break; \
-    case 2: hipLaunchKernelGGL((k_lin_plain<2, 4, CAMV, true, 0, true, false, true>), g, b, shm, c->stream, d, xl, cls); break; \
-    default: hipLaunchKernelGGL((k_lin_plain<2, 4, CAMV, true, 0, true, true, true>), g, b, shm, c->stream, d, xl, cls); break; }
-                        if (d.cam.model == 0) { NRS_LIN_RC(0) } else { NRS_LIN_RC(1) }
-#undef NRS_LIN_RC
-                    } else if (d.h4 && d.nt) {                      // (streams beyond the Infinity Cache: non-temporal accesses)
-                        if (d.cam.model == 0) hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 0, true, false, false, 4, true>), g, b, shm, c->stream, d, xl, cls);
-                        else hipLaunchKernelGGL((k_lin_plain<2, 4, 1, true, 0, true, false, false, 4, true>), g, b, shm, c->stream, d, xl, cls);
-                    } else if (d.h4) {                              // (implies tp)
-                        if (d.cam.model == 0) hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true, 0, true>), g, b, shm, c->stream, d, xl, cls);
-                        else hipLaunchKernelGGL((k_lin_plain<2, 4, 1, true, 0, true>), g, b, shm, c->stream, d, xl, cls);
-                    } else if (d.cam.model == 0) {
-                        if (tp) hipLaunchKernelGGL((k_lin_plain<2, 4, 0, true>), g, b, shm, c->stream, d, xl, cls);
-                        else hipLaunchKernelGGL((k_lin_plain<2, 4, 0, false>), g, b, shm, c->stream, d, xl, cls);
-                    } else {
-                        if (tp) hipLaunchKernelGGL((k_lin_plain<2, 4, 1, true>), g, b, shm, c->stream, d, xl, cls);
-                        else hipLaunchKernelGGL((k_lin_plain<2, 4, 1, false>), g, b, shm, c->stream, d, xl, cls);
-                    }
-                    break;
-            }
-            return;
-        }
-        if (d.dform) {                                             // temporal-difference dampers (two-kernel path: T = 2 unless overridden)
-            switch (d.T) {
-                case 1: hipLaunchKernelGGL((k_reg<1, true, true, true>), g, b, shm, c->stream, d, xl, cls); break;
-                case 4: hipLaunchKernelGGL((k_reg<4, true, true, true>), g, b, shm, c->stream, d, xl, cls); break;
-                case 8: hipLaunchKernelGGL((k_reg<8, true, true, true>), g, b, shm, c->stream, d, xl, cls); break;
-                case 16: hipLaunchKernelGGL((k_reg<16, true, true, true>), g, b, shm, c->stream, d, xl, cls); break;
-                default: hipLaunchKernelGGL((k_reg<2, true, true, true>), g, b, shm, c->stream, d, xl, cls); break;
-            }
-            return;
-        }
-    }
-    switch (d.T) {
-        case 1: hipLaunchKernelGGL((k_reg<1, LIN, LDS>), g, b, shm, c->stream, d, xl, cls); break;
-        case 4: hipLaunchKernelGGL((k_reg<4, LIN, LDS>), g, b, shm, c->stream, d, xl, cls); break;
-        case 8: hipLaunchKernelGGL((k_reg<8, LIN, LDS>), g, b, shm, c->stream, d, xl, cls); break;
-        case 16: hipLaunchKernelGGL((k_reg<16, LIN, LDS>), g, b, shm, c->stream, d, xl, cls); break;
-        default: hipLaunchKernelGGL((k_reg<2, LIN, LDS>), g, b, shm, c->stream, d, xl, cls); break;
-    }
-}
-
-template <bool LIN>
-static void launch_reg(nrs_ctx* c, const Dev& d, const double* xl) {
-    if (!d.use_lds) { launch_reg2<LIN, false>(c, d, xl, 0, d.n_regblk, 0); return; }
-    for (int cls = 0; cls < 2; ++cls) {
-        if (d.sh_nt[cls] == 0) continue;
-        size_t shm = (LIN && d.dform) ? sizeof(double) * 9 * (size_t)(d.tile_rows + d.cap_h[cls] + 1)
-                                      : sizeof(double) * 3 * (size_t)(d.tile_rows + d.cap_h[cls]) * (d.X0 ? 2 : 1);
-        if (LIN) shm = std::max(shm, sizeof(double) * 4 * 64 * 8);        // the pose-block product reuses the staging area: 4 KB per wave
-        launch_reg2<LIN, true>(c, d, xl, shm, d.sh_nt[cls], cls);        // (LIN: the linearisation point is d.lin_pose / xl)
-    }
-}
-
-template <bool LDS>
-static void launch_spmv2(nrs_ctx* c, const Dev& d, double lam, size_t shm, int it) {
-    const dim3 g(((d.n_regblk + 7) / 8) * 8), b(BLK);
-    switch (d.T) {
-        case 1: hipLaunchKernelGGL((k_spmv<1, LDS>), g, b, shm, c->stream, d, lam, it); break;
-        case 4: hipLaunchKernelGGL((k_spmv<4, LDS>), g, b, shm, c->stream, d, lam, it); break;
-        case 8: hipLaunchKernelGGL((k_spmv<8, LDS>), g, b, shm, c->stream, d, lam, it); break;
-        case 16: hipLaunchKernelGGL((k_spmv<16, LDS>), g, b, shm, c->stream, d, lam, it); break;
-        default: hipLaunchKernelGGL((k_spmv<2, LDS>), g, b, shm, c->stream, d, lam, it); break;
-    }
-}
-
-// with_skin_op (embedded BA window): k_skin_op's workgroups ride behind the operator's in the same launch (k_spmv_f_skin) where the
-// operator is the generic k_spmv_f<T, false>; returns whether they did (the caller launches k_skin_op on its own otherwise)
-static bool launch_spmv(nrs_ctx* c, const Dev& d0, double lam, int it, double tol2, bool with_skin_op = false) {
-    if (!d0.use_lds) { launch_spmv2<false>(c, d0, lam, 0, it); return false; }
-    bool merged = false;
-    Dev d = d0;
-#ifdef NRS_DEBUG_PROBES                                            // (phase clocks of one operator launch: make PROBES=1, then NRS_SPMV_DBG=1)
-    long long* dbg = nullptr;
-    static bool dbg_done = false;
-    if (d.h4 && it == 3 && !dbg_done && c->env("NRS_SPMV_DBG")) {  // phase clocks of one operator launch (100 MHz wall clock)
-        dbg_done = true;
-        const size_t ns = (size_t)d.n_rows / (64 / d.T);
-        if (hipMalloc((void**)&dbg, sizeof(long long) * 8 * ns) == hipSuccess) { (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 8 * ns, c->stream); d.dbg_clk = dbg; }
-    }
-    struct Dump {
-        nrs_ctx* c; long long* buf; size_t ns;
-        ~Dump() {
-            if (!buf) return;
-            (void)hipStreamSynchronize(c->stream);
-            std::vector<long long> h(8 * ns);
-            (void)hipMemcpy(h.data(), buf, sizeof(long long) * 8 * ns, hipMemcpyDeviceToHost);
-            (void)hipFree(buf);
-            double acc[5] = {0, 0, 0, 0, 0};
-            long long t_min = LLONG_MAX, t_max = 0;
-            size_t n = 0;
-            for (size_t i = 0; i < ns; ++i) {
-                const long long* q = &h[8 * i];
-                if (!q[0] || !q[5]) continue;
-                for (int k = 0; k < 5; ++k) acc[k] += (double)(q[k + 1] - q[k]);
-                t_min = std::min(t_min, q[0]); t_max = std::max(t_max, q[5]);
-                ++n;
-            }
-            if (n) fprintf(stderr, "[nrs] k_spmv_f phases (us per wave, mean over %zu waves): stage %.2f springs %.2f dampers %.2f row %.2f reduce %.2f | launch span %.1f us\n",
-                           n, acc[0] / n / 100.0, acc[1] / n / 100.0, acc[2] / n / 100.0, acc[3] / n / 100.0, acc[4] / n / 100.0, (double)(t_max - t_min) / 100.0);
-        }
-    } dump{c, dbg, dbg ? (size_t)d.n_rows / (64 / d.T) : 0};
-#endif
-    for (int cls = 0; cls < 2; ++cls) {
-        const int n = d.sh_nt[cls] + d.sh_ntb[cls];
-        if (n == 0) continue;
-        const dim3 g(((n + 7) / 8) * 8), b(BLK);
-        if (d.dform) {
-            const size_t shm = sizeof(double) * 3 * (3 * (size_t)(d.tile_rows + d.cap_h[cls] + 1) + d.tile_rows + d.cap_s[cls] + 1);
-            switch (d.T) {
-                case 1: hipLaunchKernelGGL((k_spmv_f<1, true>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-                case 4: hipLaunchKernelGGL((k_spmv_f<4, true>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-                case 8: hipLaunchKernelGGL((k_spmv_f<8, true>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-                case 16: hipLaunchKernelGGL((k_spmv_f<16, true>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-                default: hipLaunchKernelGGL((k_spmv_f<2, true>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-            }
-            continue;
-        }
-        const size_t shm = sizeof(double) * 3 * (size_t)(2 * d.tile_rows + d.cap_h[cls] + ((rc_of(d, cls) & 2) ? d.cap_h[cls] : d.cap_s[cls]) + 2);
-        const bool last_cls = cls == 1 || d.sh_nt[1] + d.sh_ntb[1] == 0;
-        if (with_skin_op && last_cls && !(d.T == 2 && d.plain && d.tp_ok) && !c->env("NRS_SKIN_OP_OWN_LAUNCH")) {
-            const dim3 g2(g.x + d.sk_nblk);
-            switch (d.T) {
-                case 1: hipLaunchKernelGGL((k_spmv_f_skin<1>), g2, b, shm, c->stream, d, lam, cls, it, tol2, (int)g.x); break;
-                case 2: hipLaunchKernelGGL((k_spmv_f_skin<2>), g2, b, shm, c->stream, d, lam, cls, it, tol2, (int)g.x); break;
-                case 4: hipLaunchKernelGGL((k_spmv_f_skin<4>), g2, b, shm, c->stream, d, lam, cls, it, tol2, (int)g.x); break;
-                case 16: hipLaunchKernelGGL((k_spmv_f_skin<16>), g2, b, shm, c->stream, d, lam, cls, it, tol2, (int)g.x); break;
-                default: hipLaunchKernelGGL((k_spmv_f_skin<8>), g2, b, shm, c->stream, d, lam, cls, it, tol2, (int)g.x); break;
-            }
-            merged = true;
-            continue;
-        }
-        switch (d.T) {
-            case 1: hipLaunchKernelGGL((k_spmv_f<1, false>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-            case 4: hipLaunchKernelGGL((k_spmv_f<4, false>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-            case 8: hipLaunchKernelGGL((k_spmv_f<8, false>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-            case 16: hipLaunchKernelGGL((k_spmv_f<16, false>), g, b, shm, c->stream, d, lam, cls, it, tol2); break;
-            default:
-                if (d.plain && d.tp_ok && d.h4 && rc_of(d, cls) == 1) hipLaunchKernelGGL((k_spmv_f<2, false, true, true, true, false>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                else if (d.plain && d.tp_ok && d.h4 && rc_of(d, cls) == 2) hipLaunchKernelGGL((k_spmv_f<2, false, true, true, false, true>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                else if (d.plain && d.tp_ok && d.h4 && rc_of(d, cls) == 3) hipLaunchKernelGGL((k_spmv_f<2, false, true, true, true, true>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                else if (d.plain && d.tp_ok && d.h4 && d.nt) hipLaunchKernelGGL((k_spmv_f<2, false, true, true, false, false, true>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                else if (d.plain && d.tp_ok && d.h4) hipLaunchKernelGGL((k_spmv_f<2, false, true, true>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                else if (d.plain && d.tp_ok) hipLaunchKernelGGL((k_spmv_f<2, false, true>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                else hipLaunchKernelGGL((k_spmv_f<2, false>), g, b, shm, c->stream, d, lam, cls, it, tol2);
-                break;
-        }
-    }
-    return merged;
-}
 
 // errors (+ linearisation) at a given state; leaves chi2 (and max diag) in scal[]
 template <bool LIN>
@@ -285,63 +73,24 @@ static int evaluate(nrs_ctx* c, Engine* e, int which, bool reproj_done = false) 
     if (LIN) { e->d.lin_pose = e->d.pose[which]; e->d.lin_xl = e->d.xl[which]; }   // the PCG kernels re-form factors from it
     const Dev& d = e->d;
     const dim3 gg(((d.sh_ng + 7) / 8) * 8), b(BLK);
-#ifdef NRS_DEBUG_PROBES                                            // (phase clocks of one lineariser launch: make PROBES=1, then NRS_LIN_DBG=1)
-    if (LIN && d.plain && c->env("NRS_LIN_DBG")) {
-        // phase clocks of one lineariser launch (100 MHz wall clock): where a wave's time goes
-        static bool done = false;
-        if (!done) {
-            done = true;
-            const size_t ns = (size_t)d.n_rows / (64 / d.T);
-            long long* buf = nullptr;
-            NRS_HIP(c, hipMalloc((void**)&buf, sizeof(long long) * 8 * ns));
-            NRS_HIP(c, hipMemsetAsync(buf, 0, sizeof(long long) * 8 * ns, c->stream));
-            Dev dd = d;
-            dd.dbg_clk = buf;
-            launch_reg<LIN>(c, dd, d.xl[which]);
-            NRS_HIP(c, hipStreamSynchronize(c->stream));
-            std::vector<long long> h(8 * ns);
-            NRS_HIP(c, hipMemcpy(h.data(), buf, sizeof(long long) * 8 * ns, hipMemcpyDeviceToHost));
-            (void)hipFree(buf);
-            double acc[5] = {0, 0, 0, 0, 0};
-            long long t_min = LLONG_MAX, t_max = 0;
-            size_t n = 0;
-            for (size_t i = 0; i < ns; ++i) {
-                const long long* q = &h[8 * i];
-                if (!q[0] || !q[5]) continue;
-                for (int k = 0; k < 5; ++k) acc[k] += (double)(q[k + 1] - q[k]);
-                t_min = std::min(t_min, q[0]); t_max = std::max(t_max, q[5]);
-                ++n;
-            }
-            fprintf(stderr, "[nrs] k_lin_plain phases (us per wave, mean over %zu waves): stage %.2f springs %.2f dampers %.2f reproj %.2f tail %.2f | launch span %.1f us\n",
-                    n, acc[0] / n / 100.0, acc[1] / n / 100.0, acc[2] / n / 100.0, acc[3] / n / 100.0, acc[4] / n / 100.0, (double)(t_max - t_min) / 100.0);
-        }
-    }
-#endif
+    NRS_PROBE(NRS_TRY(lin_clocks_once<LIN>(c, d, d.xl[which]));)
     if (LIN) {
         // LDS path: one fused pass (reprojection + springs + dampers per row); gather path: two
         const int reps = c->opt.profile ? PROFILE_REPS : 1;
         Timer t(c, &c->prof.linearize_ms, &c->prof.linearize_launches, reps);
         for (int r = 0; r < reps; ++r) {
             if (!d.use_lds) hipLaunchKernelGGL((k_reproj<LIN>), gg, b, 0, c->stream, d, d.pose[which], d.xl[which]);
-            launch_reg<LIN>(c, d, d.xl[which]);
+            NRS_TRY(launch_reg<LIN>(c, d, d.xl[which]));
         }
     } else {
         if (!reproj_done) hipLaunchKernelGGL((k_reproj<LIN>), gg, b, 0, c->stream, d, d.pose[which], d.xl[which]);
         if (d.ec_on) hipLaunchKernelGGL(k_chi_edges, dim3(std::max(1, d.ec_nblk)), b, 0, c->stream, d, d.xl[which]);
-        else launch_reg<LIN>(c, d, d.xl[which]);
+        else NRS_TRY(launch_reg<LIN>(c, d, d.xl[which]));
     }
     if (LIN) hipLaunchKernelGGL(k_pose_sums, dim3(d.sh_nk), b, 0, c->stream, d);
     if (LIN && d.coarse && !(e->nd && e->nd->on)) {                // (the coarse level is the PCG's: a directly solved engine never reads it -- 50 us per linearisation at 4.4k points)
-        const size_t rows = (size_t)(d.tile_rows + d.max_halo);
-        const size_t shm = sizeof(double) * 3 * rows + 3 * (rows + 8) + 16;
-        const dim3 g(d.n_regblk);
-        switch (d.T) {
-            case 1: hipLaunchKernelGGL((k_coarse_tile<1>), g, b, shm, c->stream, d); break;
-            case 2: hipLaunchKernelGGL((k_coarse_tile<2>), g, b, shm, c->stream, d); break;
-            case 4: hipLaunchKernelGGL((k_coarse_tile<4>), g, b, shm, c->stream, d); break;
-            case 16: hipLaunchKernelGGL((k_coarse_tile<16>), g, b, shm, c->stream, d); break;
-            default: hipLaunchKernelGGL((k_coarse_tile<8>), g, b, shm, c->stream, d); break;
-        }
+        const size_t rows = (size_t)(d.tile_rows + d.max_halo), shm = sizeof(double) * 3 * rows + 3 * (rows + 8) + 16;
+        NRS_TRY(with_lanes(c, d.T, [&](auto L) { hipLaunchKernelGGL((k_coarse_tile<decltype(L)::value>), dim3(d.n_regblk), b, shm, c->stream, d); }));
         hipLaunchKernelGGL(k_coarse_reduce, dim3(1), b, 0, c->stream, d);
     }
     if (d.sk_n > 0) hipLaunchKernelGGL((k_skin<LIN>), dim3(d.sk_nblk), b, 0, c->stream, d, d.pose[which], d.xl[which]);   // embedded mode: the skinned observations
@@ -369,32 +118,15 @@ static int evaluate(nrs_ctx* c, Engine* e, int which, bool reproj_done = false) 
     return NRS_OK;
 }
 
-// Wait for the publication numbered c->seq (k_finalize / k_publish: always the last kernel enqueued before
-// this).  The host polls the sequence word in mapped host memory; if it does not show up within ~2 s the
-// stream is synchronised instead, which also surfaces a device fault as an error.
-static int wait_published(nrs_ctx* c, Engine* e) {
-    volatile int* w = e->h_flags + 7;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spins = 0; *w != c->seq; ++spins) {
-        if (spins > 200000) std::this_thread::yield();             // long kernels (large windows): stop hogging the core
-        if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            NRS_HIP(c, hipStreamSynchronize(c->stream));
-            if (*w != c->seq) return c->fail(NRS_ERR_HIP, "device results were not published");
-            break;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return NRS_OK;
-}
-
-static int read_scalars(nrs_ctx* c, Engine* e) { return wait_published(c, e); }
-
-// the same wait on the mirrors of a shadow set (speculative trials): publication `seq` in flag block hf, enqueued on stream st
-static int wait_published_at(nrs_ctx* c, const int* hf, int seq, hipStream_t st) {
-    const volatile int* w = hf + 7;
+// Wait for publication `seq` in the flag block `flags` (mapped host memory: the engine's mirrors, or a shadow set's), enqueued on
+// stream st by k_finalize / k_publish / the last PCG launch of a batch -- always the last kernel enqueued there before this.  The
+// host polls the sequence word; if it does not show up within ~2 s the stream is synchronised instead, which also surfaces a device
+// fault as an error.
+static int wait_published(nrs_ctx* c, const int* flags, int seq, hipStream_t st) {
+    const volatile int* w = flags + 7;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t spins = 0; *w != seq; ++spins) {
-        if (spins > 200000) std::this_thread::yield();
+        if (spins > 200000) std::this_thread::yield();             // long kernels (large windows): stop hogging the core
         if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
             NRS_HIP(c, hipStreamSynchronize(st));
             if (*w != seq) return c->fail(NRS_ERR_HIP, "device results were not published");
@@ -514,44 +246,7 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
     }
     for (; it < stop; ++it) {
         const int pub = it + 1 == stop && !kft_lazy ? pub_seq : 0;     // (kft_lazy: k_kft_rnorm is the batch's last launch and publishes)
-#ifdef NRS_DEBUG_PROBES                                            // (phase clocks of one fused PCG launch: make PROBES=1, then NRS_PCG_DBG=1)
-        if (d.fused && it == 20 && d.coarse && c->env("NRS_PCG_DBG")) {   // phase clocks of one fused launch (100 MHz wall clock), once
-            static bool dbg_done = false;
-            if (!dbg_done) {
-                dbg_done = true;
-                long long* buf = nullptr;
-                const size_t nb8 = 8 * (size_t)d.n_regblk;
-                if (hipMalloc((void**)&buf, sizeof(long long) * nb8) == hipSuccess) {
-                    (void)hipMemsetAsync(buf, 0, sizeof(long long) * nb8, c->stream);
-                    Dev dd = d;
-                    dd.dbg_clk = buf;
-                    const dim3 g(((d.n_regblk + 7) / 8) * 8), bb(BLK);
-                    const size_t shm = sizeof(double) * (6 * (size_t)(d.tile_rows + d.max_halo) + 12 * (size_t)d.n_regblk + 16 * CO_MAX);
-                    // (an extra launch of the same iteration into the same half: idempotent -- it rewrites what the real one writes)
-                    (void)hipStreamSynchronize(c->stream);
-                    std::vector<long long> h(nb8);
-                    // the timed launch is the real one of this iteration
-                    hipLaunchKernelGGL((k_pcg_fused<8, true>), g, bb, shm, c->stream, dd, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                    (void)hipStreamSynchronize(c->stream);
-                    (void)hipMemcpy(h.data(), buf, sizeof(long long) * nb8, hipMemcpyDeviceToHost);
-                    (void)hipFree(buf);
-                    double acc[6] = {0, 0, 0, 0, 0, 0};
-                    long long t_min = LLONG_MAX, t_max = 0;
-                    int n = 0;
-                    for (int b2 = 0; b2 < d.n_regblk; ++b2) {
-                        const long long* q = &h[8 * (size_t)b2];
-                        if (!q[0] || !q[6]) continue;
-                        for (int k = 0; k < 6; ++k) acc[k] += (double)(q[k + 1] - q[k]);
-                        t_min = std::min(t_min, q[0]); t_max = std::max(t_max, q[6]);
-                        ++n;
-                    }
-                    if (n) fprintf(stderr, "[nrs] k_pcg_fused<8,true> phases (us per tile, mean over %d tiles): loads+pose %.2f coarse products %.2f scalars+corrections %.2f update+stage %.2f operator %.2f reduce+store %.2f | launch span %.1f us\n",
-                                   n, acc[0] / n / 100.0, acc[1] / n / 100.0, acc[2] / n / 100.0, acc[3] / n / 100.0, acc[4] / n / 100.0, acc[5] / n / 100.0, (double)(t_max - t_min) / 100.0);
-                    continue;
-                }
-            }
-        }
-#endif
+        NRS_PROBE(if (pcg_clocks_once(c, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub)) continue;)
         if (d.fused) {
             // frames of <= 32 tiles: every tile on a workgroup of ONE XCD (workgroups are dealt to the XCDs round-robin; the other seven
             // of every eight return at once) -- the vectors then stay in one L2 instead of being written through eight: 19.0 -> 18.0 us
@@ -563,77 +258,11 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
             const Dev& d = d1;
             const dim3 g(one_xcd ? 8 * d.n_regblk : ((d.n_regblk + 7) / 8) * 8), bb(BLK);
             const size_t shm = sizeof(double) * (6 * (size_t)(d.tile_rows + d.max_halo) + (d.coarse ? 12 * (size_t)d.n_regblk + 16 * CO_MAX : 0));
-            const bool check_fused = c->env("NRS_CHECK_FUSED") != nullptr;
-            if (check_fused && !d.coarse && d.T == 8) {
-                // debug: the same launch twice from the same state must leave the same bits in every array it writes
-                // (tools/flake_probe.py: run-to-run variation of the single-launch iteration)
-                struct Arr { void* p; size_t bytes; const char* name; };
-                const size_t nv = sizeof(double) * 3 * (size_t)d.n_rows, np6 = sizeof(double) * 6 * (size_t)d.K, npart = sizeof(double) * NPART * (size_t)d.n_regblk;
-                const Arr arr[] = {{d.rv, nv, "r0"}, {d.rv2, nv, "r1"}, {d.sv, nv, "s0"}, {d.sv2, nv, "s1"}, {d.wv, nv, "w0"}, {d.wv2, nv, "w1"}, {d.xv, nv, "x"},
-                                   {d.pv, nv, "p"}, {d.uv3, nv, "u"}, {d.rp, np6, "rp0"}, {d.rp2, np6, "rp1"}, {d.sp, np6, "sp0"}, {d.sp2, np6, "sp1"},
-                                   {d.up, np6, "up0"}, {d.up2, np6, "up1"}, {d.pp, np6, "pp"}, {d.xp, np6, "xp"}, {d.part_spmv, npart, "part0"},
-                                   {d.part_spmv2, npart, "part1"}, {d.scal, sizeof(double) * SC_N, "scal"}, {d.flags, sizeof(int) * 8, "flags"}};
-                size_t total = 0;
-                for (const Arr& a : arr) total += (a.bytes + 255) & ~(size_t)255;
-                static char* snap = nullptr; static size_t snap_cap = 0;
-                if (snap_cap < total) { if (snap) (void)hipFree(snap); NRS_HIP(c, hipMalloc((void**)&snap, total)); snap_cap = total; }
-                std::vector<char> h1(total), h2(total);
-                auto gather = [&](char* dst, hipMemcpyKind kind) -> int {
-                    size_t o = 0;
-                    for (const Arr& a : arr) { NRS_HIP(c, hipMemcpyAsync(dst + o, a.p, a.bytes, kind, c->stream)); o += (a.bytes + 255) & ~(size_t)255; }
-                    NRS_HIP(c, hipStreamSynchronize(c->stream));
-                    return NRS_OK;
-                };
-                NRS_TRY(gather(snap, hipMemcpyDeviceToDevice));
-                hipLaunchKernelGGL((k_pcg_fused<8, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                NRS_TRY(gather(h1.data(), hipMemcpyDeviceToHost));
-                { size_t o = 0; for (const Arr& a : arr) { NRS_HIP(c, hipMemcpyAsync(a.p, snap + o, a.bytes, hipMemcpyDeviceToDevice, c->stream)); o += (a.bytes + 255) & ~(size_t)255; } }
-                hipLaunchKernelGGL((k_pcg_fused<8, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                NRS_TRY(gather(h2.data(), hipMemcpyDeviceToHost));
-                size_t o = 0;
-                bool any = false;
-                for (const Arr& a : arr) {
-                    if (memcmp(h1.data() + o, h2.data() + o, a.bytes) != 0) {
-                        any = true;
-                        const size_t nel = a.bytes / 8;
-                        size_t ndiff = 0, first = 0, last = 0;
-                        for (size_t el = 0; el < nel; ++el)
-                            if (memcmp(h1.data() + o + 8 * el, h2.data() + o + 8 * el, 8) != 0) { if (!ndiff) first = el; last = el; ++ndiff; }
-                        double v1, v2; memcpy(&v1, h1.data() + o + 8 * first, 8); memcpy(&v2, h2.data() + o + 8 * first, 8);
-                        fprintf(stderr, "[nrs] fused launch it %d: array %s differs in %zu elements, first %zu (tile %zu) last %zu (tile %zu): %.6g / %.6g\n", it, a.name, ndiff, first,
-                                first / 3 / (size_t)d.tile_rows, last, last / 3 / (size_t)d.tile_rows, v1, v2);
-                    }
-                    o += (a.bytes + 255) & ~(size_t)255;
-                }
-                if (any) {
-                    const size_t o_fl = total - 256, o_sc = o_fl - ((sizeof(double) * SC_N + 255) & ~(size_t)255);
-                    const int* f1 = reinterpret_cast<const int*>(h1.data() + o_fl); const int* f2 = reinterpret_cast<const int*>(h2.data() + o_fl);
-                    const int* f0 = nullptr; (void)f0;
-                    fprintf(stderr, "[nrs]    flags after run 1: %d %d %d %d | run 2: %d %d %d %d ; scal gamma0 %.6g/%.6g slot0 %.6g %.6g / %.6g %.6g slot1 %.6g %.6g / %.6g %.6g\n", f1[0], f1[1], f1[2], f1[3], f2[0], f2[1], f2[2], f2[3],
-                            reinterpret_cast<const double*>(h1.data() + o_sc)[SC_GAMMA0], reinterpret_cast<const double*>(h2.data() + o_sc)[SC_GAMMA0],
-                            reinterpret_cast<const double*>(h1.data() + o_sc)[SC_SLOT0], reinterpret_cast<const double*>(h1.data() + o_sc)[SC_SLOT0 + 1],
-                            reinterpret_cast<const double*>(h2.data() + o_sc)[SC_SLOT0], reinterpret_cast<const double*>(h2.data() + o_sc)[SC_SLOT0 + 1],
-                            reinterpret_cast<const double*>(h1.data() + o_sc)[SC_SLOT1], reinterpret_cast<const double*>(h1.data() + o_sc)[SC_SLOT1 + 1],
-                            reinterpret_cast<const double*>(h2.data() + o_sc)[SC_SLOT1], reinterpret_cast<const double*>(h2.data() + o_sc)[SC_SLOT1 + 1]);
-                }
-            } else
-            switch (d.T) {
-                case 1: if (d.coarse) hipLaunchKernelGGL((k_pcg_fused<1, true>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        else hipLaunchKernelGGL((k_pcg_fused<1, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        break;
-                case 2: if (d.coarse) hipLaunchKernelGGL((k_pcg_fused<2, true>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        else hipLaunchKernelGGL((k_pcg_fused<2, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        break;
-                case 4: if (d.coarse) hipLaunchKernelGGL((k_pcg_fused<4, true>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        else hipLaunchKernelGGL((k_pcg_fused<4, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        break;
-                case 16: if (d.coarse) hipLaunchKernelGGL((k_pcg_fused<16, true>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        else hipLaunchKernelGGL((k_pcg_fused<16, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        break;
-                default: if (d.coarse) hipLaunchKernelGGL((k_pcg_fused<8, true>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        else hipLaunchKernelGGL((k_pcg_fused<8, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
-                        break;
-            }
+            if (c->env("NRS_CHECK_FUSED") && !d.coarse && d.T == 8) { NRS_TRY(check_fused_launch(c, d, g, shm, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub)); continue; }
+            NRS_TRY(with_lanes(c, d.T, [&](auto L) {
+                constexpr int T = decltype(L)::value;
+                hipLaunchKernelGGL((d.coarse ? k_pcg_fused<T, true> : k_pcg_fused<T, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
+            }));
             continue;
         }
         bool skin_op_done = false;                                 // (k_skin_op's workgroups went with the operator's launch)
@@ -654,18 +283,18 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
                 db.sh_ntb[cls] = d.sh_back[cls];
             }
             // embedded window: the skinned observations reach rows of their own keyframe only -- k_skin_op goes with the interior tiles
-            skin_op_done = launch_spmv(c, di, lam, it, tol2, d.sk_pcg != 0);
+            NRS_TRY(launch_spmv(c, di, lam, it, tol2, d.sk_pcg != 0, &skin_op_done));
             if (d.sk_pcg && !skin_op_done) {
                 hipLaunchKernelGGL(k_skin_op, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, it);
                 skin_op_done = true;
             }
             NRS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_halo, 0));
-            launch_spmv(c, db, lam, it, tol2);
+            NRS_TRY(launch_spmv(c, db, lam, it, tol2));
         } else {
             const int reps = c->opt.profile ? PROFILE_REPS : 1;    // (a profiling context has no convergence look-ahead: the launch is idempotent)
             Timer t(c, &c->prof.spmv_ms, &c->prof.spmv_launches, reps);
             if (d.hier && d.ecd) hipLaunchKernelGGL(k_reduce_ru, dim3(1), dim3(BLK), 0, c->stream, d, it);
-            for (int r = 0; r < reps; ++r) skin_op_done = launch_spmv(c, d, lam, it, tol2, d.sk_pcg != 0);
+            for (int r = 0; r < reps; ++r) NRS_TRY(launch_spmv(c, d, lam, it, tol2, d.sk_pcg != 0, &skin_op_done));
         }
         if (d.sk_pcg) {                                            // embedded BA window: H u of the skinned observations' blocks (nrs_engine_skin.hpp)
             if (!skin_op_done) hipLaunchKernelGGL(k_skin_op, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, it);
@@ -709,292 +338,351 @@ static int pcg_advance(nrs_ctx* c, Engine* e, double lam, int stop_level, int* i
         if (*it_io >= c->opt.pcg_max_iters) { *done = true; break; }
         NRS_TRY(pcg_enqueue_batch(c, e, lam, it_io, count, ++c->seq));      // its last launch publishes the flags
         NRS_HIP(c, hipGetLastError());
-        NRS_TRY(wait_published(c, e));
+        NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));
         if (e->h_flags[0] || *it_io >= c->opt.pcg_max_iters) { *done = true; break; }
         if (stop_level && e->h_flags[3] >= stop_level) { *done = false; break; }
     }
     return NRS_OK;
 }
 
-// g2o SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve on the resident problem.
+// size of a PCG trial's first batch (trial q of an LM iteration): up to the first peek milestone the last trial needed, or the
+// whole solve the last one needed where it was short
+static int first_batch(const nrs_ctx* c, const Engine* e, int q) {
+    const bool expect_accept = q == 0 && e->first_trial_accepted && e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch;
+    if (!c->opt.exact_trials && !expect_accept) return e->pred_peek > 0 ? std::min(e->pred_peek, c->opt.pcg_batch) : std::max(1, c->opt.pcg_batch / 2);
+    if (e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch) return e->pred_iters + 1;
+    return 0;
+}
+
+// What one engine_optimize call fixes before its first LM iteration: the switches read once per call, the shadow sets trials may use
+struct LmRun {
+    nrs_ctx* c; Engine* e;
+    bool peek_debug, check_chi, spec_dbg;                          // NRS_PEEK_DEBUG, NRS_CHECK_CHI, NRS_SPEC_DBG (host clocks of a batch on stderr)
+    int n_spec, n_spec_pcg;                                        // shadow sets for trials of a directly solved engine / of a PCG window (0: one trial at a time)
+    int spec_first, spec_first_pcg;                                // NRS_SPEC_FIRST=<n>: followers behind the first trial of an iteration
+};
+static LmRun lm_run(nrs_ctx* c, Engine* e) {
+    const Dev& d = e->d;
+    LmRun r{c, e};
+    r.peek_debug = c->env("NRS_PEEK_DEBUG") != nullptr;
+    r.check_chi = c->env("NRS_CHECK_CHI") != nullptr;
+    r.spec_dbg = c->env("NRS_SPEC_DBG") != nullptr;
+    // Speculative trials (directly solved single-pose engines; nrs_engine_types.hpp SpecSet): after a rejected trial the rest of the run
+    // goes out as a batch -- the trial g2o would try next on the engine's own arrays, the ones after it (lam x ni, then x 2 ni, ...) on
+    // the shadow sets -- and the results are read in order.  NRS_SPEC_TRIALS=0: one at a time (the same trials, the same bits).
+    r.n_spec = e->nd && e->nd->on && d.K == 1 && !d.sh_on && !d.ec_on && !c->opt.profile && !c->env("NRS_CHECK_EVAL") &&
+                       e->nd->S().chain_from >= e->nd->S().plan.n_levels       // (the chained factorisation's workgroups wait for each other too: one such launch at a time)
+                   ? std::min(e->n_spec, e->nd->S().n_alt) : 0;
+    // ... and BA windows on the two-kernel PCG (PcgSetView): a trial of the batch is its pcg_begin, its first PCG batch and its
+    // evaluation; the host then takes the trials in order through the usual peeks, further PCG batches going to the trial's own set.
+    // The first batch's size depends on the milestone the trials before it reached (first_batch): a trial whose size the host does
+    // not confirm when it gets to it is discarded with the rest of the batch and solved again on the engine's own arrays.
+    r.n_spec_pcg = e->spec_pcg && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && d.sk_n == 0 && !(e->kft && e->kft->on) &&
+                           !c->opt.profile && !c->env("NRS_CHECK_EVAL")
+                       ? e->n_spec : 0;
+    r.spec_first = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : 0;
+    r.spec_first_pcg = c->env("NRS_SPEC_FIRST") ? r.spec_first : r.n_spec_pcg;
+    return r;
+}
+
+// The LM trials in flight: the one g2o would try next (set -1: the engine's own arrays) and the ones that follow it if it is rejected
+// (shadow sets 0, 1, ...), enqueued together and taken in order.
+struct TrialBatch {
+    struct Pending { int set; double lam; int seq; int solve_id; int first; int pit; };
+    const LmRun r;
+    Pending pend[1 + SPEC_MAX];
+    int n_pend = 0, i_pend = 0;
+    bool ok = false;                                               // (set on the regular return)
+    std::chrono::steady_clock::time_point t_batch = std::chrono::steady_clock::now();
+    explicit TrialBatch(const LmRun& r_) : r(r_) {}
+    // an error return with trials in flight: nothing of theirs may outlive the engine the caller is about to drop
+    ~TrialBatch() {
+        if (!ok) for (int j = 0; j < std::max(r.n_spec, r.n_spec_pcg); ++j) if (r.c->spec_stream[j]) (void)hipStreamSynchronize(r.c->spec_stream[j]);
+    }
+    bool empty() const { return i_pend == n_pend; }
+    // the context's stream continues behind every shadow trial of the batch (they read the linearisation and the state)
+    int join() {
+        nrs_ctx* c = r.c;
+        // trials of the batch nobody has asked for yet are not needed: their solves drain (the context's stream is idle here -- the
+        // results before them have been read -- so the word is written at once)
+        for (int j = i_pend; j < n_pend && !c->env("NRS_SPEC_NO_ABORT"); ++j)
+            if (pend[j].set >= 0) NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.e->spec[pend[j].set].abort), pend[j].solve_id, 1, c->stream));
+        for (int j = 0; j < n_pend; ++j)
+            if (pend[j].set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_join[pend[j].set], 0));
+        n_pend = i_pend = 0;
+        return NRS_OK;
+    }
+    // the next result, which must be the trial at damping lam
+    int take(double lam, const Pending** out) {
+        const Pending& pp = pend[i_pend++];
+        if (pp.lam != lam) return r.c->fail(NRS_ERR_STATE, "speculative trial: damping %.17g does not match the sequence (%.17g)", pp.lam, lam);
+        *out = &pp;
+        return NRS_OK;
+    }
+    // PCG window, nothing in flight: inside a run of rejections, this trial and the ones after it (may leave the batch empty: the
+    // trial then goes out on its own)
+    int fill_pcg(int it, int qmax, double lam, double ni) {
+        nrs_ctx* c = r.c; Engine* e = r.e;
+        Dev& d = e->d;                                             // (seen through each trial's PcgSetView below)
+        const int trial = 1 - e->cur;
+        n_pend = i_pend = 0;
+        int nb = 1;
+        if (qmax >= 1) nb = std::min(std::min(std::max(e->spec_run - qmax + 1, 2), 1 + r.n_spec_pcg), 10 - qmax);
+        // the first trial of an iteration whose first trial was rejected last time goes out with followers (NRS_SPEC_FIRST=<n>
+        // of them, default n_spec; 0: none) -- C2: the rejected run 852 -> 642 us of a step, 2.62 -> 2.48 ms per step
+        if (qmax == 0 && r.spec_first_pcg > 0 && it < 32 && (e->spec_run_at >> it & 1u)) nb = std::min(1 + r.n_spec_pcg, 1 + r.spec_first_pcg);
+        if (nb <= 1) return NRS_OK;
+        NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
+        double l = lam, n = ni;
+        for (int j = 0; j < nb; ++j) {
+            if (j > 0) { l *= n; n *= 2; if (!std::isfinite(l)) break; }
+            Pending& p = pend[n_pend];
+            // (followers of an iteration's first trial: the first batch the last run's later trials were confirmed with --
+            // the milestone of a run's trials, not of the accepted trial before it that first_batch would go by)
+            p.first = qmax == 0 && j > 0 && e->spec_follow_first > 0 ? e->spec_follow_first : first_batch(c, e, qmax + j);
+            p.set = j - 1; p.lam = l; p.solve_id = ++e->spec_gen; p.pit = 0;
+            PcgSetView v(c, e, p.set, p.solve_id);
+            if (p.set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork, 0));
+            NRS_TRY(pcg_begin(c, e, l, &p.pit));
+            NRS_TRY(pcg_enqueue_batch(c, e, l, &p.pit, p.first));
+            hipLaunchKernelGGL(k_apply, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, l, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
+            NRS_TRY(evaluate<false>(c, e, trial, false));
+            p.seq = c->seq;
+            if (p.set >= 0) NRS_HIP(c, hipEventRecord(c->spec_join[p.set], c->stream));
+            ++n_pend;
+            if (r.spec_dbg) fprintf(stderr, "[spec] it %d trial %d: set %d first %d enqueued\n", it, qmax + j, p.set, p.first);
+        }
+        NRS_HIP(c, hipGetLastError());
+        return NRS_OK;
+    }
+    // directly solved engine, nothing in flight: this trial and, inside a run of rejections, the ones that would follow it
+    int fill_direct(int it, int qmax, double lam, double ni) {
+        nrs_ctx* c = r.c;
+        n_pend = i_pend = 0;
+        // how many: up to the trial that is expected to be accepted -- runs repeat their length from one LM iteration, round and
+        // frame to the next (c->spec_run: rejections of the last completed run) -- and two at a time beyond it; a trial of the
+        // batch that turns out not to be needed holds the next linearisation up until it has drained
+        int nb = 1;
+        if (qmax == 0 && r.spec_first > 0) nb = std::min(1 + r.n_spec, 1 + r.spec_first);   // (experiment: NRS_SPEC_FIRST=<n> further trials behind the first of an iteration)
+        if (qmax >= 1) nb = std::min(std::min(std::max(c->spec_run - qmax + 1, 2), 1 + r.n_spec), 10 - qmax);
+        if (const char* f = c->env("NRS_SPEC_FIXED")) { if (qmax >= 1) nb = std::min(std::min(std::max(1, atoi(f)), 1 + r.n_spec), 10 - qmax); }
+        if (nb > 1) NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
+        double l = lam, n = ni;
+        const auto tq0 = std::chrono::steady_clock::now();
+        for (int j = 0; j < nb; ++j) {
+            if (j > 0) { l *= n; n *= 2; if (!std::isfinite(l)) break; }
+            pend[n_pend].set = j - 1; pend[n_pend].lam = l;
+            NRS_TRY(direct_trial_enqueue(c, r.e, j - 1, l, &pend[n_pend].seq, &pend[n_pend].solve_id, nb > 1));
+            ++n_pend;
+            if (r.spec_dbg) fprintf(stderr, "[spec] it %d trial %d: set %d enqueued at +%.1f us\n", it, qmax, j - 1, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tq0).count());
+        }
+        NRS_HIP(c, hipGetLastError());
+        t_batch = tq0;
+        return NRS_OK;
+    }
+};
+
+// trial state, chi2 and scale of the solve so far, read back with one synchronisation (chi2, scale and the PCG flags)
+static int eval_trial(nrs_ctx* c, Engine* e, double lam) {
+    const Dev& d = e->d;
+    const int trial = 1 - e->cur;
+    Timer t(c, &c->prof.update_ms, &c->prof.update_launches);
+    const bool one_pose = d.K == 1 && !d.sh_on;                    // a2's engines: trial state and reprojection chi2 in one launch
+    if (one_pose)
+        hipLaunchKernelGGL(k_apply_reproj, dim3(((d.sh_ng + 7) / 8) * 8), dim3(BLK), 0, c->stream, d, lam, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
+    else
+        hipLaunchKernelGGL(k_apply, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, lam, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
+    if (d.sh_on) NRS_TRY(c->comm->exchange(c, d.xl[trial], e->halo, c->stream));   // the regularisers read the neighbours' boundary keyframes
+    NRS_TRY(evaluate<false>(c, e, trial, one_pose));
+    NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));
+    if (c->env("NRS_CHECK_EVAL")) {                                // (debug: the same evaluation again on the same state must give the same bits)
+        const double chi1 = e->h_scal[SC_CHI], sc1 = e->h_scal[SC_SCALE];
+        NRS_TRY(evaluate<false>(c, e, trial, false));
+        NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));
+        if (e->h_scal[SC_CHI] != chi1 || e->h_scal[SC_SCALE] != sc1)
+            fprintf(stderr, "[nrs] evaluation not reproducible: chi2 %.17g / %.17g, scale %.17g / %.17g\n", chi1, e->h_scal[SC_CHI], sc1, e->h_scal[SC_SCALE]);
+    }
+    return NRS_OK;
+}
+
+// One LM trial at damping lam -- g2o's solve + update + computeActiveErrors (optimization_algorithm_levenberg.cpp:98-119) -- from
+// pcg_begin, or the hand-over from the batch, to its final figures.
+struct LmTrial {
+    double chi_new = 0, scale = 0;                                 // chi2 at the trial state; the gain ratio's denominator (computeScale + 1e-3)
+    bool early = false;                                            // rejected at a peek: the solve was not finished
+    int status = 0, inner = 0, peek_it = 0, pit = 0;               // the solve's flags[2] (0: fine), flags[1] (iterations), flags[4] (iterations to the first milestone); enqueued
+    int set = -1;                                                  // the shadow set that holds the trial state (-1: the engine's own arrays)
+};
+static int run_trial(const LmRun& r, TrialBatch& tb, int it, int qmax, double lam, double ni, double chi, LmTrial* out) {
+    nrs_ctx* c = r.c; Engine* e = r.e;
+    int pit = 0, spec_seq = 0, spec_id = 0;
+    int won = -1;                                                  // the shadow set that holds this trial's state (-1: the engine's own)
+    bool done = false, early = false;
+    bool in_flight = false;                                        // PCG window: this trial's first batch and evaluation went out with a batch
+    double temp = 0, scale = 0;
+    const bool direct = e->nd && e->nd->on;                        // nested-dissection Cholesky instead of PCG (nrs_engine_nd.hpp)
+    const double *hs = e->h_scal; const int* hf = e->h_flags;      // the mirrors this trial's results arrive in
+    if (r.n_spec_pcg > 0) {
+        if (tb.empty()) NRS_TRY(tb.fill_pcg(it, qmax, lam, ni));
+        if (qmax > 0) e->spec_follow_first = first_batch(c, e, qmax);
+        if (!tb.empty()) {
+            const TrialBatch::Pending* pp = nullptr;
+            NRS_TRY(tb.take(lam, &pp));
+            // (exact trials evaluate the converged solve only: where its batches end does not matter)
+            if (!c->opt.exact_trials && pp->first != first_batch(c, e, qmax)) {
+                if (r.spec_dbg) fprintf(stderr, "[spec] it %d trial %d: first batch %d, now %d: solved again\n", it, qmax, pp->first, first_batch(c, e, qmax));
+                --tb.i_pend;
+                NRS_TRY(tb.join());
+            } else {
+                won = pp->set; pit = pp->pit; spec_seq = pp->seq; spec_id = pp->solve_id; in_flight = true;
+            }
+        }
+    }
+    {
+    PcgSetView view(c, e, r.n_spec_pcg > 0 ? won : -1, spec_id);
+    if (won >= 0) { hs = e->h_scal; hf = e->h_flags; }
+    // (a directly solved engine's flag words are cleared by the evaluation that published them: k_finalize, every trial and linearisation)
+    if (!direct && !in_flight) NRS_TRY(pcg_begin(c, e, lam, &pit));
+    const bool peeking = !c->opt.exact_trials;
+    // The first batch of PCG iterations and a speculative evaluation of its result go out together: most trials are decided by it
+    // (converged, or clearly rejected at a peek).  Its size is what the previous trial needed to reach the first milestone (the
+    // kernels record it), so a trial that is going to be rejected costs a handful of iterations.
+    int seen = 0;                                                  // peek levels already evaluated
+    if (direct && r.n_spec > 0) {
+        if (tb.empty()) NRS_TRY(tb.fill_direct(it, qmax, lam, ni));
+        const TrialBatch::Pending* pp = nullptr;
+        NRS_TRY(tb.take(lam, &pp));
+        won = pp->set;
+        if (won >= 0) { hs = e->spec[won].h_scal; hf = e->spec[won].h_flags; }
+        NRS_TRY(wait_published(c, hf, pp->seq, won >= 0 ? c->spec_stream[won] : c->stream));
+        if (r.spec_dbg) fprintf(stderr, "[spec] it %d trial %d: result of set %d at +%.1f us\n", it, qmax, won, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tb.t_batch).count());
+        done = true;
+    } else if (direct) {
+        // g2o's own sequence: factorise (H + lambda I), solve, evaluate (linear_solver_eigen.h:92-136); a pivot that is not
+        // positive raises flags[2] and the trial counts as failed below
+        NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam));
+        NRS_TRY(eval_trial(c, e, lam));
+        done = true;
+    } else if (in_flight) {                                        // (enqueued with the batch: its publication is the one to wait for)
+        NRS_TRY(wait_published(c, hf, spec_seq, c->stream));
+        done = hf[0] != 0 || pit >= c->opt.pcg_max_iters;
+    } else {
+        // (after an iteration whose first trial was accepted, the next first trial usually is too:
+        // short solves then go out whole, without the intermediate look)
+        NRS_TRY(pcg_enqueue_batch(c, e, lam, &pit, first_batch(c, e, qmax)));
+        NRS_TRY(eval_trial(c, e, lam));
+        done = e->h_flags[0] != 0 || pit >= c->opt.pcg_max_iters;
+    }
+    while (true) {
+        temp = hs[SC_CHI];
+        scale = hs[SC_SCALE] + 1e-3;
+        if (done) break;
+        const int lvl = hf[3];
+        if (peeking && lvl > seen) {
+            // peek: a trial that is clearly going to be rejected is not solved any further -- its step is discarded, so the iterate
+            // sequence is the reference's either way
+            const double rho_peek = (chi - temp) / scale;
+            // ... and only when the chi2 increase is well above the noise floor of the fp32 projection (relative 1e-7 per evaluation): near
+            // convergence the gain ratio of a tiny step is noise over the 1e-3 regulariser of its denominator, at any accuracy
+            early = hf[2] == 0 && std::isfinite(temp) && rho_peek < PEEK_RHO_LVL[lvl] && (temp - chi) > PEEK_MIN_REL_INCREASE * chi;
+            if (r.peek_debug) { fprintf(stderr, "[peek] it %d trial %d lvl %d pit %d rho %.4f relinc %.3e\n", it, qmax, lvl, pit, rho_peek, (temp - chi) / chi); early = false; }
+            if (early) break;
+            seen = lvl;
+            // the remaining looks exist only to reject: a gain ratio this far above every threshold cannot get there any more
+            // (estimates are within ~0.15), so the solve runs to convergence without further interruptions
+            if (rho_peek > 0.25 && !r.peek_debug) seen = PEEK_LEVELS;
+        }
+        NRS_TRY(pcg_advance(c, e, lam, peeking && seen < PEEK_LEVELS ? seen + 1 : 0, &pit, &done));
+        NRS_TRY(eval_trial(c, e, lam));
+    }
+    }                                                              // (the engine's own view again: the caller may swap the state)
+    // (flags[2] == 2: a bounded wait of the direct solver ran out -- a synchronisation fault, not a matrix that is not positive
+    // definite: the factor and the assembly areas hold partial data, so this is an error, never a rejected trial)
+    if (hf[2] == 2) return c->fail(NRS_ERR_HIP, "direct solve: a wait for another workgroup's result timed out (LM iteration %d, trial %d, solve set %d)", it, qmax, won);
+    out->chi_new = temp; out->scale = scale; out->early = early;
+    out->status = hf[2]; out->inner = hf[1]; out->peek_it = hf[4];
+    out->set = won; out->pit = pit;
+    return NRS_OK;
+}
+
+// g2o SparseOptimizer::optimize + OptimizationAlgorithmLevenberg::solve on the resident problem
+// (sparse_optimizer.cpp:203-285, optimization_algorithm_levenberg.cpp:57-174).
 // trace->count / iterations are accumulated (the drivers reset them once per entry point).
 int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* trace) {
     if (iters < 0) return c->fail(NRS_ERR_INVALID, "iters < 0");
     NRS_HIP(c, hipSetDevice(c->device));
     Dev& d = e->d;
+    const LmRun run = lm_run(c, e);
+    TrialBatch batch(run);
     double lam = -1, ni = 2;
-    const bool peek_debug = c->env("NRS_PEEK_DEBUG") != nullptr;
-    const bool check_chi = c->env("NRS_CHECK_CHI") != nullptr;
     double chi_carry = 0;
-    const int peek_levels = peek_debug ? 4 : PEEK_LEVELS;
-    // Speculative trials (directly solved single-pose engines; nrs_engine_types.hpp SpecSet): after a rejected trial the rest of the run
-    // goes out as a batch -- the trial g2o would try next on the engine's own arrays, the ones after it (lam x ni, then x 2 ni, ...) on
-    // the shadow sets -- and the results are read in order.  NRS_SPEC_TRIALS=0: one at a time (the same trials, the same bits).
-    const int n_spec = e->nd && e->nd->on && d.K == 1 && !d.sh_on && !d.ec_on && !c->opt.profile && !c->env("NRS_CHECK_EVAL") &&
-                               e->nd->S().chain_from >= e->nd->S().plan.n_levels       // (the chained factorisation's workgroups wait for each other too: one such launch at a time)
-                           ? std::min(e->n_spec, e->nd->S().n_alt) : 0;
-    // ... and BA windows on the two-kernel PCG (PcgSetView): a trial of the batch is its pcg_begin, its first PCG batch and its
-    // evaluation; the host then takes the trials in order through the usual peeks, further PCG batches going to the trial's own set.
-    // The first batch's size depends on the milestone the trials before it reached (first_batch): a trial whose size the host does
-    // not confirm when it gets to it is discarded with the rest of the batch and solved again on the engine's own arrays.
-    const int n_spec_pcg = e->spec_pcg && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && d.sk_n == 0 && !(e->kft && e->kft->on) &&
-                                   !c->opt.profile && !c->env("NRS_CHECK_EVAL")
-                               ? e->n_spec : 0;
-    struct Pending { int set; double lam; int seq; int solve_id; int first; int pit; } pend[1 + SPEC_MAX];
-    int n_pend = 0, i_pend = 0;
-    struct SpecDrain {                                             // an error return with trials in flight: nothing of theirs may outlive the engine the caller is about to drop
-        nrs_ctx* c; int n; bool ok = false;
-        ~SpecDrain() { if (!ok) for (int j = 0; j < n; ++j) if (c->spec_stream[j]) (void)hipStreamSynchronize(c->spec_stream[j]); }
-    } spec_drain{c, std::max(n_spec, n_spec_pcg)};
-    // size of a PCG trial's first batch (trial q of an LM iteration): up to the first peek milestone the last trial needed, or the
-    // whole solve the last one needed where it was short
-    auto first_batch = [&](int q) -> int {
-        const bool expect_accept = q == 0 && e->first_trial_accepted && e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch;
-        if (!c->opt.exact_trials && !expect_accept) return e->pred_peek > 0 ? std::min(e->pred_peek, c->opt.pcg_batch) : std::max(1, c->opt.pcg_batch / 2);
-        if (e->pred_iters > 0 && e->pred_iters + 1 <= 2 * c->opt.pcg_batch) return e->pred_iters + 1;
-        return 0;
-    };
-    const int spec_first = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : 0;
-    const bool spec_dbg = c->env("NRS_SPEC_DBG") != nullptr;       // (host clocks of a batch on stderr)
-    const int spec_first_pcg = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : n_spec_pcg;
-    auto t_batch = std::chrono::steady_clock::now();
-    auto join_batch = [&]() -> int {                              // the context's stream continues behind every shadow trial of the batch (they read the linearisation and the state)
-        // trials of the batch nobody has asked for yet are not needed: their solves drain (the context's stream is idle here -- the
-        // results before them have been read -- so the word is written at once)
-        for (int j = i_pend; j < n_pend && !c->env("NRS_SPEC_NO_ABORT"); ++j)
-            if (pend[j].set >= 0) NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->spec[pend[j].set].abort), pend[j].solve_id, 1, c->stream));
-        for (int j = 0; j < n_pend; ++j)
-            if (pend[j].set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_join[pend[j].set], 0));
-        n_pend = i_pend = 0;
-        return NRS_OK;
-    };
     for (int it = 0; it < iters; ++it) {
-        NRS_TRY(evaluate<true>(c, e, e->cur));
-        // computeActiveErrors at the start of an iteration re-derives the chi2 the last accepted trial
-        // already produced (same state, same summation order): after the first iteration the host
-        // does not wait for it, the linearisation and the first PCG batch go out back to back
+        NRS_TRY(evaluate<true>(c, e, e->cur));                     // buildSystem (levenberg.cpp:83)
+        // computeActiveErrors at the start of an iteration re-derives the chi2 the last accepted trial already produced (same state, same
+        // summation order): after the first iteration the host does not wait for it, the linearisation and the first PCG batch go out back to back
         double chi = chi_carry;
-        if (it == 0 || check_chi) {
-            NRS_TRY(read_scalars(c, e));
-            if (check_chi && it > 0 && e->h_scal[SC_CHI] != chi_carry)
+        if (it == 0 || run.check_chi) {
+            NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));
+            if (run.check_chi && it > 0 && e->h_scal[SC_CHI] != chi_carry)
                 fprintf(stderr, "[nrs] chi2 carried %.17g vs recomputed %.17g\n", chi_carry, e->h_scal[SC_CHI]);
             chi = e->h_scal[SC_CHI];
         }
-        if (it == 0) { lam = 1e-5 * e->h_scal[SC_MAXDIAG]; ni = 2; }
+        if (it == 0) { lam = 1e-5 * e->h_scal[SC_MAXDIAG]; ni = 2; }   // computeLambdaInit: tau * max diagonal (levenberg.cpp:89-91, 153-165)
         if (!std::isfinite(chi) || !std::isfinite(lam)) return c->fail(NRS_ERR_NUMERIC, "non-finite chi2/lambda at LM iteration %d", it);
         double rho = 0;
         int qmax = 0;
-        do {
-            int pit = 0;
-            bool done = false, early = false;
+        do {                                                       // levenberg.cpp:97-145
             const int trial = 1 - e->cur;
-            double temp = 0, scale = 0;
-            bool ok = true;
-            const bool direct = e->nd && e->nd->on;                  // nested-dissection Cholesky instead of PCG (nrs_engine_nd.hpp)
-            const double* hs = e->h_scal;                            // the mirrors this trial's results arrive in
-            const int* hf = e->h_flags;
-            int won = -1;                                          // the shadow set that holds this trial's state (-1: the engine's own)
-            int spec_seq = 0, spec_id = 0;
-            bool in_flight = false;                                // PCG window: this trial's first batch and evaluation went out with a batch
-            if (n_spec_pcg > 0) {
-                if (i_pend == n_pend) {                            // nothing in flight: inside a run of rejections, this trial and the ones after it
-                    n_pend = i_pend = 0;
-                    int nb = 1;
-                    if (qmax >= 1) nb = std::min(std::min(std::max(e->spec_run - qmax + 1, 2), 1 + n_spec_pcg), 10 - qmax);
-                    // the first trial of an iteration whose first trial was rejected last time goes out with followers (NRS_SPEC_FIRST=<n>
-                    // of them, default n_spec; 0: none) -- C2: the rejected run 852 -> 642 us of a step, 2.62 -> 2.48 ms per step
-                    if (qmax == 0 && spec_first_pcg > 0 && it < 32 && (e->spec_run_at >> it & 1u)) nb = std::min(1 + n_spec_pcg, 1 + spec_first_pcg);
-                    if (nb > 1) {
-                        NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
-                        double l = lam, n = ni;
-                        for (int j = 0; j < nb; ++j) {
-                            if (j > 0) { l *= n; n *= 2; if (!std::isfinite(l)) break; }
-                            Pending& p = pend[n_pend];
-                            // (followers of an iteration's first trial: the first batch the last run's later trials were confirmed with --
-                            // the milestone of a run's trials, not of the accepted trial before it that first_batch would go by)
-                            p.first = qmax == 0 && j > 0 && e->spec_follow_first > 0 ? e->spec_follow_first : first_batch(qmax + j);
-                            p.set = j - 1; p.lam = l; p.solve_id = ++e->spec_gen; p.pit = 0;
-                            PcgSetView v(c, e, p.set, p.solve_id);
-                            if (p.set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork, 0));
-                            NRS_TRY(pcg_begin(c, e, l, &p.pit));
-                            NRS_TRY(pcg_enqueue_batch(c, e, l, &p.pit, p.first));
-                            hipLaunchKernelGGL(k_apply, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, l, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
-                            NRS_TRY(evaluate<false>(c, e, trial, false));
-                            p.seq = c->seq;
-                            if (p.set >= 0) NRS_HIP(c, hipEventRecord(c->spec_join[p.set], c->stream));
-                            ++n_pend;
-                            if (spec_dbg) fprintf(stderr, "[spec] it %d trial %d: set %d first %d enqueued\n", it, qmax + j, p.set, p.first);
-                        }
-                        NRS_HIP(c, hipGetLastError());
-                    }
-                }
-                if (qmax > 0) e->spec_follow_first = first_batch(qmax);
-                if (i_pend < n_pend) {
-                    const Pending& pp = pend[i_pend++];
-                    if (pp.lam != lam) return c->fail(NRS_ERR_STATE, "speculative trial: damping %.17g does not match the sequence (%.17g)", pp.lam, lam);
-                    // (exact trials evaluate the converged solve only: where its batches end does not matter)
-                    if (!c->opt.exact_trials && pp.first != first_batch(qmax)) {
-                        if (spec_dbg) fprintf(stderr, "[spec] it %d trial %d: first batch %d, now %d: solved again\n", it, qmax, pp.first, first_batch(qmax));
-                        --i_pend;
-                        NRS_TRY(join_batch());
-                    } else {
-                        won = pp.set; pit = pp.pit; spec_seq = pp.seq; spec_id = pp.solve_id; in_flight = true;
-                    }
-                }
-            }
-            {
-            PcgSetView view(c, e, n_spec_pcg > 0 ? won : -1, spec_id);
-            if (won >= 0) { hs = e->h_scal; hf = e->h_flags; }
-            // (a directly solved engine's flag words are cleared by the evaluation that published them: k_finalize, every trial and linearisation)
-            if (!direct && !in_flight) NRS_TRY(pcg_begin(c, e, lam, &pit));
-            auto eval_trial = [&]() -> int {
-                Timer t(c, &c->prof.update_ms, &c->prof.update_launches);
-                const bool one_pose = d.K == 1 && !d.sh_on;      // a2's engines: trial state and reprojection chi2 in one launch
-                if (one_pose)
-                    hipLaunchKernelGGL(k_apply_reproj, dim3(((d.sh_ng + 7) / 8) * 8), dim3(BLK), 0, c->stream, d, lam, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
-                else
-                    hipLaunchKernelGGL(k_apply, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, lam, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
-                if (d.sh_on) NRS_TRY(c->comm->exchange(c, d.xl[trial], e->halo, c->stream));   // the regularisers read the neighbours' boundary keyframes
-                NRS_TRY(evaluate<false>(c, e, trial, one_pose));
-                NRS_TRY(read_scalars(c, e));               // one synchronisation: chi2, scale and the PCG flags
-                const bool check_eval = c->env("NRS_CHECK_EVAL") != nullptr;
-                if (check_eval) {                          // (debug: the same evaluation again on the same state must give the same bits)
-                    const double chi1 = e->h_scal[SC_CHI], sc1 = e->h_scal[SC_SCALE];
-                    NRS_TRY(evaluate<false>(c, e, trial, false));
-                    NRS_TRY(read_scalars(c, e));
-                    if (e->h_scal[SC_CHI] != chi1 || e->h_scal[SC_SCALE] != sc1)
-                        fprintf(stderr, "[nrs] evaluation not reproducible: chi2 %.17g / %.17g, scale %.17g / %.17g\n", chi1, e->h_scal[SC_CHI], sc1, e->h_scal[SC_SCALE]);
-                }
-                return NRS_OK;
-            };
-            const bool peeking = !c->opt.exact_trials;
-            // The first batch of PCG iterations and a speculative evaluation of its result go out
-            // together: most trials are decided by it (converged, or clearly rejected at a peek).  Its
-            // size is what the previous trial needed to reach the first milestone (the kernels record
-            // it), so a trial that is going to be rejected costs a handful of iterations.
-            int seen = 0;                                  // peek levels already evaluated
-            if (direct && n_spec > 0) {
-                if (i_pend == n_pend) {                            // nothing in flight: this trial and, inside a run of rejections, the ones that would follow it
-                    n_pend = i_pend = 0;
-                    // how many: up to the trial that is expected to be accepted -- runs repeat their length from one LM iteration, round and
-                    // frame to the next (c->spec_run: rejections of the last completed run) -- and two at a time beyond it; a trial of the
-                    // batch that turns out not to be needed holds the next linearisation up until it has drained
-                    int nb = 1;
-                    if (qmax == 0 && spec_first > 0) nb = std::min(1 + n_spec, 1 + spec_first);   // (experiment: NRS_SPEC_FIRST=<n> further trials behind the first of an iteration)
-                    if (qmax >= 1) nb = std::min(std::min(std::max(c->spec_run - qmax + 1, 2), 1 + n_spec), 10 - qmax);
-                    if (const char* f = c->env("NRS_SPEC_FIXED")) { if (qmax >= 1) nb = std::min(std::min(std::max(1, atoi(f)), 1 + n_spec), 10 - qmax); }
-                    if (nb > 1) NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
-                    double l = lam, n = ni;
-                    const auto tq0 = std::chrono::steady_clock::now();
-                    for (int j = 0; j < nb; ++j) {
-                        if (j > 0) { l *= n; n *= 2; if (!std::isfinite(l)) break; }
-                        pend[n_pend].set = j - 1; pend[n_pend].lam = l;
-                        NRS_TRY(direct_trial_enqueue(c, e, j - 1, l, &pend[n_pend].seq, &pend[n_pend].solve_id, nb > 1));
-                        ++n_pend;
-                        if (spec_dbg) fprintf(stderr, "[spec] it %d trial %d: set %d enqueued at +%.1f us\n", it, qmax, j - 1, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tq0).count());
-                    }
-                    NRS_HIP(c, hipGetLastError());
-                    t_batch = tq0;
-                }
-                const Pending& pp = pend[i_pend++];
-                if (pp.lam != lam) return c->fail(NRS_ERR_STATE, "speculative trial: damping %.17g does not match the sequence (%.17g)", pp.lam, lam);
-                won = pp.set;
-                if (won >= 0) { hs = e->spec[won].h_scal; hf = e->spec[won].h_flags; }
-                NRS_TRY(wait_published_at(c, hf, pp.seq, won >= 0 ? c->spec_stream[won] : c->stream));
-                if (spec_dbg) fprintf(stderr, "[spec] it %d trial %d: result of set %d at +%.1f us\n", it, qmax, won, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_batch).count());
-                done = true;
-            } else if (direct) {
-                // g2o's own sequence: factorise (H + lambda I), solve, evaluate (linear_solver_eigen.h:92-136); a pivot that is not
-                // positive raises flags[2] and the trial counts as failed below
-                NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam));
-                NRS_TRY(eval_trial());
-                done = true;
-            } else if (in_flight) {                        // (enqueued with the batch: its publication is the one to wait for)
-                NRS_TRY(wait_published_at(c, hf, spec_seq, c->stream));
-                done = hf[0] != 0 || pit >= c->opt.pcg_max_iters;
-            } else {
-                // (after an iteration whose first trial was accepted, the next first trial usually is too:
-                // short solves then go out whole, without the intermediate look)
-                NRS_TRY(pcg_enqueue_batch(c, e, lam, &pit, first_batch(qmax)));
-                NRS_TRY(eval_trial());
-                done = e->h_flags[0] != 0 || pit >= c->opt.pcg_max_iters;
-            }
-            while (true) {
-                temp = hs[SC_CHI];
-                scale = hs[SC_SCALE] + 1e-3;
-                if (done) break;
-                const int lvl = hf[3];
-                if (peeking && lvl > seen) {
-                    // peek: a trial that is clearly going to be rejected is not solved any further --
-                    // its step is discarded, so the iterate sequence is the reference's either way
-                    const double rho_peek = (chi - temp) / scale;
-                    // ... and only when the chi2 increase is well above the noise floor of the fp32
-                    // projection (relative 1e-7 per evaluation): near convergence the gain ratio of a
-                    // tiny step is noise over the 1e-3 regulariser of its denominator, at any accuracy
-                    early = hf[2] == 0 && std::isfinite(temp) && rho_peek < PEEK_RHO_LVL[lvl] && (temp - chi) > PEEK_MIN_REL_INCREASE * chi;
-                    if (peek_debug) { fprintf(stderr, "[peek] it %d trial %d lvl %d pit %d rho %.4f relinc %.3e\n", it, qmax, lvl, pit, rho_peek, (temp - chi) / chi); early = false; }
-                    if (early) break;
-                    seen = lvl;
-                    // the remaining looks exist only to reject: a gain ratio this far above every
-                    // threshold cannot get there any more (estimates are within ~0.15), so the solve
-                    // runs to convergence without further interruptions
-                    if (rho_peek > 0.25 && !peek_debug) seen = peek_levels;
-                }
-                NRS_TRY(pcg_advance(c, e, lam, peeking && seen < peek_levels ? seen + 1 : 0, &pit, &done));
-                NRS_TRY(eval_trial());
-            }
-            }                                              // (the engine's own view again: the state may be swapped below)
-            // (flags[2] == 2: a bounded wait of the direct solver ran out -- a synchronisation fault, not a matrix that is not positive
-            // definite: the factor and the assembly areas hold partial data, so this is an error, never a rejected trial)
-            if (hf[2] == 2) return c->fail(NRS_ERR_HIP, "direct solve: a wait for another workgroup's result timed out (LM iteration %d, trial %d, solve set %d)", it, qmax, won);
-            ok = hf[2] == 0;
-            if (!early && !ok) temp = 1.7976931348623157e308;
-            if (!early) e->pred_iters = hf[1];
-            if (hf[4] > 0) e->pred_peek = hf[4];
-            if (qmax == 0) e->first_trial_accepted = !early && (chi - temp) / scale > 0 && std::isfinite(temp);
-            const int inner = hf[1];
-            rho = (chi - temp) / scale;
-            if (peek_debug) fprintf(stderr, "[peek] it %d trial %d FINAL pit %d rho %.4f\n", it, qmax, pit, rho);
-            const bool accepted = !early && rho > 0 && std::isfinite(temp);
+            LmTrial t;
+            NRS_TRY(run_trial(run, batch, it, qmax, lam, ni, chi, &t));
+            const bool ok = t.status == 0;
+            double temp = t.chi_new;
+            if (!t.early && !ok) temp = 1.7976931348623157e308;    // (ok2 false: tempChi = max, levenberg.cpp:121)
+            if (!t.early) e->pred_iters = t.inner;
+            if (t.peek_it > 0) e->pred_peek = t.peek_it;
+            if (qmax == 0) e->first_trial_accepted = !t.early && (chi - temp) / t.scale > 0 && std::isfinite(temp);
+            rho = (chi - temp) / t.scale;                          // levenberg.cpp:123-126
+            if (run.peek_debug) fprintf(stderr, "[peek] it %d trial %d FINAL pit %d rho %.4f\n", it, qmax, t.pit, rho);
+            const bool accepted = !t.early && rho > 0 && std::isfinite(temp);
             if (trace) {
                 if (trace->trials && trace->count < trace->capacity) {
                     nrs_lm_trial& Tr = trace->trials[trace->count];
                     Tr.round = round; Tr.iter = it; Tr.trial = qmax; Tr.accepted = accepted; Tr.solver_ok = ok;
-                    Tr.inner_iters = inner; Tr.early_rejected = early; Tr.reserved = 0;
+                    Tr.inner_iters = t.inner; Tr.early_rejected = t.early; Tr.reserved = 0;
                     Tr.lambda = lam; Tr.chi2 = chi; Tr.chi2_new = temp; Tr.rho = rho;
                 }
                 trace->count++;
             }
-            if (accepted) {
+            if (accepted) {                                        // levenberg.cpp:128-137
                 double alpha = 1.0 - std::pow(2 * rho - 1, 3);
                 alpha = std::min(alpha, 2.0 / 3.0);
                 lam *= std::max(1.0 / 3.0, alpha);
                 ni = 2;
                 chi = temp;
-                if (won >= 0) {                        // (the state sits in the shadow set's arrays: they become the engine's, the engine's the set's)
-                    std::swap(d.pose[trial], e->spec[won].pose);
-                    std::swap(d.xl[trial], e->spec[won].xl);
+                if (t.set >= 0) {                                  // (the state sits in the shadow set's arrays: they become the engine's, the engine's the set's)
+                    std::swap(d.pose[trial], e->spec[t.set].pose);
+                    std::swap(d.xl[trial], e->spec[t.set].xl);
                 }
-                NRS_TRY(join_batch());                 // (trials of the batch still in flight are discarded; the next linearisation waits for them)
-                if (n_spec > 0 && qmax > 0) c->spec_run = qmax;   // (a run of qmax rejections ended here)
-                if (n_spec_pcg > 0) {
+                NRS_TRY(batch.join());                             // (trials of the batch still in flight are discarded; the next linearisation waits for them)
+                if (run.n_spec > 0 && qmax > 0) c->spec_run = qmax;   // (a run of qmax rejections ended here)
+                if (run.n_spec_pcg > 0) {
                     if (qmax > 0) e->spec_run = qmax;
                     if (it < 32) e->spec_run_at = qmax > 0 ? e->spec_run_at | 1u << it : e->spec_run_at & ~(1u << it);
                 }
-                e->cur = trial;                        // discardTop: the trial state becomes current
-            } else {
+                e->cur = trial;                                    // discardTop: the trial state becomes current
+            } else {                                               // levenberg.cpp:138-143
                 lam *= ni;
-                ni *= 2;                               // pop: current state untouched
+                ni *= 2;                                           // pop: current state untouched
                 if (!std::isfinite(lam)) break;
             }
             ++qmax;
-        } while (rho < 0 && qmax < 10);
-        NRS_TRY(join_batch());
+        } while (rho < 0 && qmax < 10);                            // levenberg.cpp:144 (_maxTrialsAfterFailure = 10)
+        NRS_TRY(batch.join());
         chi_carry = chi;
         if (trace) trace->iterations++;
-        if (qmax == 10 || rho == 0 || !std::isfinite(lam)) break;
+        if (qmax == 10 || rho == 0 || !std::isfinite(lam)) break;   // levenberg.cpp:147-150: no valid step: terminate
     }
-    spec_drain.ok = true;
+    batch.ok = true;
     return NRS_OK;
 }
 

@@ -40,7 +40,7 @@ int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const d
         return NRS_OK;
     }
     NRS_TRY(evaluate<true>(c, e, e->cur));
-    NRS_TRY(read_scalars(c, e));
+    NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));
     if (what == 1 || what == 2) {
         NRS_TRY(kft_assemble(c, e, H, lam));
         NRS_HIP(c, hipStreamSynchronize(c->stream));

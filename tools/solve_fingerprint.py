@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Bit fingerprints of a fixed list of solves through py/nrs.py: per case a SHA-256 over the full LM trial trace (iter, trial, accepted,
+early, inner, lam, chi, chi_new, rho as raw bytes) and the downloaded poses and points.  Run it once per library (NRS_LIB=<path> selects
+one) and compare the outputs: a change that is meant to leave every launch and every number alone gives the same lines.  The bits depend
+on the compiler, so the output is a record (profiles/), not a golden test.
+
+    python tools/solve_fingerprint.py [substring of the case names] > fingerprint.txt"""
+import hashlib
+import os
+import struct
+import sys
+import threading
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "nr-slam_amd", "py"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+import nrs  # noqa: E402
+import nrs_synth as S  # noqa: E402
+import embedded_window_cases as W  # noqa: E402
+
+
+def digest(trials, *arrays):
+    h = hashlib.sha256()
+    for t in trials:
+        h.update(struct.pack("<iiiiidddd", t["iter"], t["trial"], int(t["accepted"]), int(t["early"]), t["inner"], t["lam"], t["chi"], t["chi_new"], t["rho"]))
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return "%s trials=%d inner=%d" % (h.hexdigest(), len(trials), sum(t["inner"] for t in trials))
+
+
+def window(n, k, seed, env=(), steps=1, **opts):
+    p = S.make_dba_problem(n, k, seed)
+    e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
+    cam = nrs.make_camera(p["model"], p["prm"])
+    qt = np.concatenate([p["poses_q"], p["poses_t"]], 1)
+    for name in env:
+        nrs.debug_set(name, env[name])
+    try:
+        c = nrs.Context(**opts)
+        c.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
+        trials = []
+        for _ in range(steps):                                        # (the second step's batches are sized by the first's predictors)
+            c.dba_reset()
+            tr = nrs.Trace()
+            c.dba_optimize(5, tr)
+            trials += tr.trials
+        pq, xyz = c.dba_download()
+        c.close()
+    finally:
+        nrs.debug_clear()
+    return digest(trials, pq, xyz)
+
+
+def frame(direct, **opts):
+    tp = S.make_tracking_problem(1150, 7)
+    cam = nrs.make_camera(tp["model"], tp["prm"])
+    fm = np.arange(1150, dtype=np.int32)
+    c = nrs.Context(direct_solve=direct, **opts)
+    trials, out = [], []
+    for _ in range(2):                                                # (the second frame's speculative batches are sized by the first's runs)
+        tr = nrs.Trace(1024)
+        r = c.track_deform_solve(cam, tp["graph"], tp["X_prev"], fm, tp["status"], tp["uv"], tp["X_prev"], tp["pose_q"], tp["pose_t"], tp["scale"], tr)
+        trials += tr.trials
+        out += [r["pose_q"], r["pose_t"], r["f_pos"], r["f_status"], r["map_pos"]]
+    c.close()
+    return digest(trials, *out)
+
+
+def embedded(solver, **opts):
+    p, flag, nb = W.window(W.CASES[0], "nodes")
+    e = nrs.dba_build_edges_embedded(p["kf_points"], flag, nb)
+    w = S.embedded_window(p, e)
+    c = nrs.Context(embedded_solver=solver, **opts)
+    tr = nrs.Trace()
+    pq, xyz, sk = c.dba_solve_embedded(nrs.make_camera(p["model"], p["prm"]), np.concatenate([p["poses_q"], p["poses_t"]], 1), w, e, p["scale"], 5, tr)
+    c.close()
+    return digest(tr.trials, pq, xyz, sk)
+
+
+def sharded(world=2, **opts):
+    p = S.make_dba_problem(300, 4, 41)
+    e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
+    cam = nrs.make_camera(p["model"], p["prm"])
+    qt = np.concatenate([p["poses_q"], p["poses_t"]], 1)
+    group = nrs.LocalGroup(world)
+    out = [None] * world
+
+    def rank_main(r):
+        c = nrs.Context(**opts)
+        c.comm_init_local(group, r)
+        c.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
+        tr = nrs.Trace()
+        c.dba_optimize(5, tr)
+        pq, xyz = c.dba_download()
+        out[r] = digest(tr.trials, pq, xyz)
+        c.close()
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(120)
+    group.close()
+    return " | ".join(str(o) for o in out)
+
+
+CASES = [
+    ("window 300x4 fused", lambda **o: window(300, 4, 32, **o)),
+    ("window 500x5 NRS_NO_FUSED", lambda **o: window(500, 5, 34, {"NRS_NO_FUSED": "1"}, **o)),
+    ("window 5000x8 two-kernel, speculative trials", lambda **o: window(5000, 8, 21, steps=2, **o)),
+    ("window 5000x8 two-kernel, NRS_SPEC_TRIALS=0", lambda **o: window(5000, 8, 21, {"NRS_SPEC_TRIALS": "0"}, steps=2, **o)),
+    ("a2 frame, direct solver, speculative trials", lambda **o: frame(1, **o)),
+    ("a2 frame, PCG", lambda **o: frame(2, **o)),
+    ("embedded 300x4x40, factorisation", lambda **o: embedded(1, **o)),
+    ("embedded 300x4x40, PCG", lambda **o: embedded(2, **o)),
+    ("sharded 300x4, 2 thread ranks", lambda **o: sharded(2, **o)),
+]
+
+if __name__ == "__main__":
+    only = sys.argv[1] if len(sys.argv) > 1 else ""                  # (a substring of the case names: run those only, e.g. under a tracer)
+    for name, fn in [x for x in CASES if only in x[0]]:
+        for mode, opts in (("default", {}), ("exact_trials", {"exact_trials": 1})):
+            print("%-50s %-13s %s" % (name, mode, fn(**opts)), flush=True)
