@@ -1,6 +1,7 @@
 // Context shared by the C-ABI entry points: one HIP stream, growable device buffers, last-error text.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -147,6 +148,25 @@ struct nrs_ctx {
     } while (0)
 
 namespace nrs {
+// NRS_TIMING: one "[nrs] <who> <stage> <ms>" line per stage on stderr, the stage name padded to `width` (tools/shard_pack_probe.py,
+// shard_rank_setup_probe.py and embedded_window_probe.py read them).  sync: the stage's launches are waited for before its time is taken
+// (host stages are not waited for; synced() waits for one stage only); by_rank: the line names the rank of a sharded context.
+struct StageTimer {
+    nrs_ctx* c; const char* who; bool sync; int width = 18; bool by_rank = sync;
+    bool on = c->env("NRS_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!on) return;
+        if (sync) (void)hipStreamSynchronize(c->stream);
+        const auto now = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(now - t_prev).count();
+        if (by_rank && c->comm) fprintf(stderr, "[nrs] rank %d/%d %s %-*s %.2f ms\n", c->comm->rank, c->comm->world, who, width, what, ms);
+        else fprintf(stderr, "[nrs] %s %-*s %.2f ms\n", who, width, what, ms);
+        t_prev = now;
+    }
+    void synced(const char* what) { if (on) (void)hipStreamSynchronize(c->stream); (*this)(what); }
+};
+
 void dba_free(nrs_ctx* ctx);
 void nd_cache_free(nrs_ctx* ctx);
 void comm_free(nrs_ctx* ctx);

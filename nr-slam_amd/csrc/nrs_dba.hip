@@ -365,14 +365,7 @@ extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, 
     std::vector<int32_t> obs_kf;
     NRS_TRY(window_validate(c, cam, n_kf, poses_qt, kf_rowptr, kf_pt, obs_xyz, obs_uv, n_points, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, obs_kf));
     if (!is_node) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_embedded: bad argument");
-    const bool tm = c->env("NRS_TIMING") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!tm) return;
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nrs] embedded window %-14s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StageTimer mark{c, "embedded window", false, 14};
     std::unique_ptr<EmbWindow> w(new EmbWindow);
     // (more ranks than keyframes, more than 8 ranks: the set-up refuses those alike on every rank -- reached through the host builder)
     const bool shard = c->comm && c->env("NRS_SHARD_EMBWIN_DEVICE") && c->comm->world <= 8 && n_kf >= c->comm->world;
@@ -396,8 +389,7 @@ extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, 
                                         w->sk_kf, w->sk_uv, w->sk_xyz, w->sk_node, w->sk_omega, scale));
     c->dba_embwin = w.release();
     const EmbWindow& r = *c->dba_embwin;
-    if (tm) (void)hipStreamSynchronize(c->stream);
-    mark("set-up");
+    mark.synced("set-up");
     NRS_TRY(nrs_dba_optimize(c, iters, trace));
     std::vector<double> xyz((size_t)r.n_lm * 3), sk((size_t)r.n_skin * 3);
     NRS_TRY(download(c, n_kf, poses_qt, xyz.data()));

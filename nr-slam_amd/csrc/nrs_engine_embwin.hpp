@@ -201,15 +201,7 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     const int n_obs = kf_rowptr[n_kf], nnz = nbr_rowptr[n_points];
     hipStream_t st = c->stream;
     NRS_HIP(c, hipSetDevice(c->device));
-    const bool tm = c->env("NRS_TIMING") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!tm) return;
-        (void)hipStreamSynchronize(st);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nrs] embedded lists %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StageTimer mark{c, "embedded lists", true, 18, false};
     size_t tb = 0;
     (void)rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st);
     int *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_flag, *d_lm, *d_cs, *d_cd, *d_ck, *d_os, *d_od, *d_ok, *d_tot, *d_krp, *d_kfb;

@@ -8,14 +8,7 @@ struct KftEnt { uint64_t key; uint32_t src; double w; };
 static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vector<int>& pose_grp_ptr) {
     const Dev& d = e->d;
     const int K = d.K;
-    const bool tm = c->env("NRS_TIMING") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!tm) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nrs] kft_setup %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+    StageTimer mark{c, "kft_setup", false};
     if (K < 1 || K > 255 || (e->sp_pos.empty() && s.n_sp > 0)) return NRS_OK;
     std::vector<int> kf_nf(K, 0), kf_np(K, 0), row_ci((size_t)d.n_rows, -1);
     int nf_max = 0;

@@ -1682,14 +1682,7 @@ static int nd_engine_finish(nrs_ctx* c, Engine* e, NdEngine* nd, NdPrep& P) {
         P.wait();
         if (tm) fprintf(stderr, "[nrs] direct solve: waited %.2f ms for the plan thread\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
-    const bool tmf = c->env("NRS_TIMING") != nullptr;
-    auto tf_prev = std::chrono::steady_clock::now();
-    auto lapf = [&](const char* what) {
-        if (!tmf) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nrs] direct solve finish: %-18s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tf_prev).count());
-        tf_prev = now;
-    };
+    StageTimer lapf{c, "direct solve finish:", false};
     nd_slot_release(c, nd);                                        // (a rebuild after the fixed set changed: the old plan goes back to the cache)
     if (!P.wanted || !nd_wanted(c, d, P.n_free)) return NRS_OK;
     const NdStruct& T = *P.st;

@@ -6,23 +6,6 @@
 
 namespace nrs {
 
-// NRS_TIMING: one "[nrs] <who> <stage> <ms>" line per stage on stderr (tools/shard_pack_probe.py and shard_rank_setup_probe.py read them).
-// The device packer waits for the stage's launches and names its rank; the host packer's stages are host work and are not waited for.
-struct StageTimer {
-    nrs_ctx* c; const char* who; bool device;
-    bool on = c->env("NRS_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
-    void operator()(const char* what) {
-        if (!on) return;
-        if (device) (void)hipStreamSynchronize(c->stream);
-        const auto now = std::chrono::steady_clock::now();
-        const double ms = std::chrono::duration<double, std::milli>(now - t_prev).count();
-        if (device && c->comm) fprintf(stderr, "[nrs] rank %d/%d %s %-18s %.2f ms\n", c->comm->rank, c->comm->world, who, what, ms);
-        else fprintf(stderr, "[nrs] %s %-18s %.2f ms\n", who, what, ms);
-        t_prev = now;
-    }
-};
-
 // ---- row layout: pose-major, each pose padded to ROW_ALIGN rows
 struct RowGroups {
     std::vector<int> pose_ptr, pose_grp_ptr, grp_pose;             // first vertex / first ROW_ALIGN group of a pose; the pose of a group

@@ -176,3 +176,53 @@ def test_track_deform_on_the_dense_graph(ctx, n, seed, model):
     # all-pairs semantics: nobody falls under the "fewer than 5 good connections" rule here, unlike on a radius-cut graph
     assert (r["f_status"] == 3).sum() == (o["f_status"] == 3).sum()
     g.close()
+
+
+def test_track_deform_does_not_depend_on_the_list_prefix(ctx):
+    """a2 on the dense graph reads prefixes of the GetEdges lists and starts a walk again on longer ones when it runs off a
+    truncated list (stage 1 from cap_per_point, stage 2 from its own hint): with prefixes of 4 entries -- every walk of stage 1
+    runs off them -- and with whole lists (cap_per_point = n) the result is the same to the bit, and each is held to the oracle
+    as in test_track_deform_on_the_dense_graph.  The seed is one whose frame has lost points, so stage 2 runs."""
+    from conftest import compare_lm_traces
+    import nrs_synth as S
+    n, seed = 300, 31
+    tp = S.make_tracking_problem(n, seed, 0)
+    cam = nrs.make_camera(tp["model"], tp["prm"])
+    sigma, th = tp["graph"]["sigma"], tp["graph"]["stretch_th"]
+    ids = np.arange(n, dtype=np.int32)
+    rng = np.random.default_rng(seed)
+    hist = tp["X_prev"].copy()                                   # one earlier frame in which a patch stretched
+    c0 = hist[3]
+    patch = np.linalg.norm(hist - c0, axis=1) < 2.5 * sigma
+    hist[patch] = c0 + (hist[patch] - c0) * np.float32(2.6)
+    upd = np.sort(rng.choice(n, n // 2, replace=False)).astype(np.int32)
+    probe = np.sort(rng.choice(n, 30, replace=False)).astype(np.int32)
+    D = RG.DenseGraph(n, sigma, th)
+    D.add_edges(tp["X_prev"], ids, ids)
+    ref_good = np.array([D.update_vertex(hist, int(i)) for i in upd])
+    otr = []
+    o = O.track_deform_solve(tp["model"], tp["prm"], D, tp["X_prev"], ids, tp["status"], tp["uv"], tp["X_prev"], tp["pose_q"], tp["pose_t"],
+                             tp["scale"], otr)
+    assert len(o["lost"]) >= 1
+    runs = []
+    for cap in (4, n):
+        g = nrs.RGraph(ctx, n, sigma, th)
+        g.add_edges(tp["X_prev"], ids, ids)
+        assert np.array_equal(g.update(hist, upd), ref_good)
+        tr = nrs.Trace(1024)
+        r = ctx.track_deform_solve_rg(cam, g, tp["X_prev"], ids, tp["status"], tp["uv"], tp["X_prev"], tp["pose_q"], tp["pose_t"], tp["scale"], tr, cap)
+        assert np.allclose(r["pose_q"], o["pose_q"], atol=1e-6, rtol=0) and np.allclose(r["pose_t"], o["pose_t"], atol=1e-5, rtol=0)
+        assert np.array_equal(r["f_status"], o["f_status"]) and r["lost"] == o["lost"]
+        assert np.allclose(r["f_pos"], o["f_pos"], atol=1e-4, rtol=0) and np.allclose(r["map_pos"], o["map_pos"], atol=1e-4, rtol=0)
+        assert compare_lm_traces(tr.trials, otr, len(otr)) >= 6
+        mx, mn, d0, st = g.rows(probe)
+        assert np.array_equal(st, D.st[probe])
+        ex = D.st[probe] != RG.NONE
+        assert np.allclose(mx[ex], D.maxd[probe][ex], atol=2e-4, rtol=0) and np.allclose(mn[ex], D.mind[probe][ex], atol=2e-4, rtol=0)
+        assert (r["f_status"] == 3).sum() == (o["f_status"] == 3).sum()
+        g.close()
+        runs.append(r)
+    a, b = runs
+    for k in ("pose_q", "pose_t", "f_pos", "f_status", "map_pos"):
+        assert np.array_equal(a[k], b[k]), k
+    assert a["lost"] == b["lost"] and a["median"] == b["median"]
