@@ -148,6 +148,54 @@ static void check_skinning() {
     same_edges(x, L);
 }
 
+// a frame that is a permuted, partial view of the map: slot, map id, index among the optimised points and vertex are four different numbers.
+// Map points 0..8; slots: 6, none, 2, 7 (tracked without 3D: lost), 0, 4 (just triangulated), 3; map points 1, 5, 8 are not in the frame
+static void check_permuted_frame() {
+    const int32_t f_map[7] = {6, -1, 2, 7, 0, 4, 3}, f_st[7] = {T3, NRS_TRACKED, T3, NRS_TRACKED, T3, NRS_JUST_TRIANGULATED, T3};
+    Lists L(9);
+    L.row(0, {{6, .75f, 2.f, G}, {2, .25f, 5.f, G}, {3, .125f, 6.f, B}, {7, .0625f, 9.f, B}});
+    L.row(2, {{6, .875f, 1.f, G}, {3, .5f, 4.f, G}, {4, .375f, 9.f, G}, {0, .25f, 5.f, G}});
+    L.row(3, {{6, .625f, 3.f, G}, {2, .5f, 4.f, G}, {8, .3125f, 9.f, G}, {0, .125f, 6.f, B}});
+    L.row(6, {{2, .875f, 1.f, G}, {7, .8125f, 9.f, G}, {1, .78125f, 9.f, G}, {0, .75f, 2.f, G}, {3, .625f, 3.f, G}});
+    L.row(7, {{1, .9f, 9.f, G}, {3, .8f, 9.f, G}, {6, .7f, 9.f, G}, {4, .6f, 9.f, G}, {2, .5f, 9.f, G}});
+    {   // every optimised point a node: the optimised points are map points 6, 2, 0, 3 in that order
+        FrameIndex x;
+        assert(frame_index(x, 9, 7, f_map, f_st, nullptr).what == DONE && x.N == 4 && x.M == 4);
+        assert((x.opt_f == VI{0, 2, 4, 6}) && (x.ids == VI{6, 2, 0, 3}) && (x.map_to_frame == VI{4, -1, 2, 6, 5, -1, 0, 3, -1}));
+        assert((x.id_to_idx == VI{2, -1, 1, 3, -1, -1, 0, -1, -1}) && (x.walk_code == VI{2, -1, 1, 3, -1, -1, 0, -2, -1}));
+        EdgeSet e;
+        e.init(x);
+        assert(host_walk(x, L.view(), e).what == DONE);
+        // 6 takes 2, 0 and 3 (7 is lost, 1 is nothing); 2 is paired with 6 already and takes 3 and 0; 0 and 3 are paired with both and end at their BAD entry
+        assert(e.ne == 5 && (e.sp_ij == VI{0, 1, 0, 2, 0, 3, 1, 3, 1, 2}) && (e.dm_w == VF{.875f, .75f, .625f, .5f, .25f}) && (e.sp_d0 == VF{1.f, 2.f, 3.f, 4.f, 5.f}));
+        assert((e.n_acc == std::vector<uint8_t>{3, 2, 0, 0}) && (e.lost_ids() == VI{7}));
+        same_edges(x, L);
+        Stage2 s;
+        s.lost_ids = e.lost_ids();
+        stage2_vertices(x, s);
+        assert(s.NV == 4 && lost_walk(x, L.view(), s).what == DONE && (s.un_ij == VI{4, 3, 4, 0, 4, 1}) && (s.un_w == VF{.8f, .7f, .5f}));
+    }
+    {   // embedded: f_node is laid out per SLOT -- slots 0, 4, 6 (map points 6, 0, 3) are nodes, map point 2 is skinned; read per map id it would make 3 a non-node
+        const uint8_t f_node[7] = {1, 0, 0, 0, 1, 0, 1};
+        FrameIndex x;
+        assert(frame_index(x, 9, 7, f_map, f_st, f_node).what == DONE && x.N == 4 && x.M == 3);
+        assert((x.node_of == VI{0, -1, 1, 2}) && (x.node_idx == VI{0, 2, 3}) && (x.walk_code == VI{2, -1, -1, 3, -1, -1, 0, -2, -1}));
+        assert((x.no_vertex == std::vector<uint8_t>{0, 0, 1, 0, 0, 0, 0, 0, 0}) && (x.is_node == std::vector<uint8_t>{1, 0, 1, 1}));
+        EdgeSet e;
+        e.init(x);
+        assert(host_walk(x, L.view(), e).what == DONE);
+        assert(e.ne == 2 && (e.sp_ij == VI{0, 1, 0, 2}) && (e.dm_w == VF{.75f, .625f}) && (e.sp_d0 == VF{2.f, 3.f}) && (e.lost_ids() == VI{7}));
+        assert((e.sk_idx == VI{1}) && (e.sk_of == VI{-1, 0, -1, -1}) && e.sk_node[0] == 0 && e.sk_node[1] == 2 && e.sk_node[2] == 1 && e.sk_node[3] == -1);
+        assert(e.sk_om[0] == .875 / 1.625 && e.sk_om[1] == .5 / 1.625 && e.sk_om[2] == .25 / 1.625 && e.sk_om[3] == 0.0);
+        same_edges(x, L);
+        Stage2 s;                                                 // vertices: the nodes (6, 0, 3), then the skinned point 2, then the lost point
+        s.lost_ids = e.lost_ids();
+        stage2_vertices(x, s);
+        assert(s.NV == 4 && (s.vert_of == VI{0, 3, 1, 2}) && (s.others == VI{1}));
+        assert(lost_walk(x, L.view(), s).what == DONE && (s.un_ij == VI{4, 2, 4, 0, 4, 3}) && (s.un_w == VF{.8f, .7f, .5f}));
+    }
+}
+
 static void check_statistics() {
     // all magnitudes equal (5): th = 0, every point sits at q3 + th -- status TRACKED, nothing moved, nothing fixed.  N = 1, 3, 4: the
     // order statistics' indices are (0, 0), (0, 2), (1, 3)
@@ -257,6 +305,7 @@ int main() {
     check_parity_walk();
     check_walk_ends();
     check_skinning();
+    check_permuted_frame();
     check_statistics();
     check_stage2();
     check_empty();
