@@ -93,7 +93,7 @@ struct nrs_ctx {
     size_t embwin_pin_cap = 0;
     nrs::DevBuf nd_skin;             // embedded mode (nrs_engine_skin.hpp): the skinned observations of the tracking engine
     void* plan_worker = nullptr;     // nrs_engine_nd.hpp PlanWorker: the helper thread of the direct solver's symbolic phase (one for the context's lifetime)
-    void* nd_cache = nullptr;        // direct solver of the tracking engines (nrs_engine_nd.hpp NdCache): the last few plans with their device arrays
+    void* nd_cache = nullptr;        // direct solver of the tracking engines (nrs_engine_nd.hpp NdCache; kernels: nrs_nd_kernels.hpp): the last few plans with their device arrays
     nrs::DevBuf comm_flag;           // one double: status word the ranks agree on after a sharded upload
     nrs::DevBuf gather_ws;           // sharded download / taps: two full-length row vectors for the gather (a rank holds its own rows only); released after use
     bool err_local = true;           // last set-up failure may be specific to this rank (allocation, HIP, rank-dependent checks)

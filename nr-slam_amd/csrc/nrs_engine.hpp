@@ -13,10 +13,9 @@
 #pragma once
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
+#include "nrs_engine_consts.hpp"      // RF_* bits, SK_MAX
 
 namespace nrs {
-
-enum : uint8_t { RF_OBS = 1, RF_REPROJ_ACTIVE = 2, RF_FIXED = 4 };
 
 struct EngineSpec {
     int K = 0, M = 0;

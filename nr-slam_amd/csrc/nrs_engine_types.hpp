@@ -7,8 +7,7 @@ namespace nrs {
 constexpr int ROW_ALIGN = 256;       // pose row padding; also rows per k_reproj workgroup
 constexpr int BLK = 256;             // threads per workgroup everywhere
 constexpr int NPART = 12;            // per-block partial slots of the SpMV kernel: [0..2] dots, [3..8] pose sums
-constexpr int SK_MAX = 11;           // embedded mode (nrs_engine_skin.hpp): nodes per skinned observation (the walk of OPT:255-279 accepts 11)
-constexpr int SK_RL = 16;            // ... lanes per node-row list of the PCG form, lists per workgroup
+constexpr int SK_RL = 16;            // embedded mode (SK_MAX: nrs_engine_consts.hpp): lanes per node-row list of the PCG form, lists per workgroup
 constexpr int SK_RPB = BLK / SK_RL;
 constexpr int CO_MAX = 84;           // largest coarse system of the two-level preconditioner (fits one workgroup's LDS)
 constexpr int CO_GMAX = (CO_MAX - 6) / 3;   // row groups of the coarse level
@@ -239,7 +238,7 @@ struct SpecSet {
     double *part_spmv, *part_ru, *red, *part_ec;
 };
 
-struct NdEngine;                     // nrs_engine_nd.hpp: the direct solver of a single-frame engine
+struct NdEngine;                     // nrs_engine_nd.hpp: the direct solver of a single-frame engine (its slot of the plan cache; solver: nrs_nd_solver.hpp)
 struct KftHost;                      // nrs_engine_kft.hpp: the keyframe-block factorisation of an embedded BA window
 struct Engine {
     Dev d;

@@ -1,6 +1,6 @@
 // The 64 x 64 pivot block's sweep of the keyframe-block factorisation (nrs_engine_kft.hpp, k_kft_step) in 16-pivot steps.  Kept in a file of its
 // own so that tools/micro/sweep_blk_probe.hip can run it alone against a host inverse.  Needs nd_v4d, nd_rowbcast, nd_fmacn_bcast
-// (nrs_engine_nd.hpp) and KFT_B.
+// (nrs_nd_kernels.hpp) and KFT_B.
 #pragma once
 // (included inside namespace nrs)
 

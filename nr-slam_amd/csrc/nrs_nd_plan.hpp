@@ -1,5 +1,5 @@
 // Symbolic phase of the direct solve of a2's single-frame system (H + lambda I) x = b: nested dissection of the point
-// graph, the separator tree as a set of dense FRONTS, everything the numeric kernels (nrs_engine_nd.hpp) index with.
+// graph, the separator tree as a set of dense FRONTS, everything the numeric kernels (nrs_nd_kernels.hpp) index with.
 //
 // What it replaces: g2o's LinearSolverEigen (reference third_party/g2o/g2o/solvers/eigen/linear_solver_eigen.h:92-173:
 // AMD ordering on the block pattern + symbolic factorisation once per optimize(), numeric SimplicialLLT per LM trial) for
@@ -55,6 +55,8 @@ struct NdFrontD {                   // one front, as the kernels read it
 // or 1 x 3 (kind 2: right-hand side of node `src`) at node positions (r, c) of the front; c is an own column
 struct NdEnt { uint16_t r, c; uint32_t src; };
 constexpr uint32_t ND_KIND_SHIFT = 30, ND_SRC_MASK = (1u << 30) - 1;
+// a pair of an engine's plan, as k_nd_values reads it (filled on the host: nrs_nd_prep_host.hpp nd_value_descriptors)
+struct NdPairD { int kind, a, b, src0, nsrc; };        // kind 0: rows (a, b), sources src[src0 .. src0 + nsrc); 1: (pose half a, row b); 2: the pose's off-diagonal block
 
 struct NdPlan {
     int n_nodes = 0, n_pairs = 0, n_fronts = 0, n_levels = 0;
@@ -67,7 +69,7 @@ struct NdPlan {
     std::vector<int> seg;                       // (front, end row) pairs: NdFrontD::seg_off
     std::vector<int> lvl_wg_ptr, wg;            // workgroups of every level: (front, row block I, row block J <= I), and (front, -1, -1) for every front
     std::vector<int> lvl_wg_split;              // per level: where its off-diagonal workgroups (I > J) start -- the diagonal (I, I) and inverse
-                                                // ones come first, so a crowded level can run as two launches (nrs_engine_nd.hpp k_nd_tile)
+                                                // ones come first, so a crowded level can run as two launches (nrs_nd_kernels.hpp k_nd_tile)
     std::vector<int> pair_hi, pair_lo;          // every pair oriented by elimination order (block rows = hi)
     std::vector<int> elim;                      // node -> elimination position
     size_t L_doubles = 0, U_doubles = 0, A_doubles = 0;

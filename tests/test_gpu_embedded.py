@@ -66,7 +66,7 @@ def test_embedded_mode_matches_its_oracle(ctx, n, m, seed, model):
 
 def test_reused_plan_takes_the_new_frames_skinning_weights():
     """a frame whose structure (optimised set, nodes, which nodes every point is skinned to) an earlier frame had reuses that frame's
-    plan and observation lists (nrs_engine_nd.hpp NdStruct) -- with its OWN skinning weights: the same bits as a context that
+    plan and observation lists (nrs_nd_prep_host.hpp NdStruct) -- with its OWN skinning weights: the same bits as a context that
     builds everything for it"""
     import os
     n, m = 700, 90

@@ -1,4 +1,4 @@
-"""GPU parity of the direct solver's device kernels (nr-slam_amd/csrc/nrs_engine_nd.hpp: k_nd_level / k_nd_back, multifrontal
+"""GPU parity of the direct solver's device kernels (nr-slam_amd/csrc/nrs_nd_kernels.hpp: k_nd_level / k_nd_back, multifrontal
 Cholesky on the nested-dissection plan, fronts on v_mfma_f64_16x16x4) through the C ABI tap nrs_debug_nd_solve, against a dense
 NumPy solve and against the host reference of the same plan (oracle/nd_host.cpp).  Stands for LinearSolverEigen::solve
 (third_party/g2o/g2o/solvers/eigen/linear_solver_eigen.h:92-136).  Tolerance: 1e-10 relative to the largest solution component
