@@ -494,6 +494,11 @@ int nrs_rgraph_get_edges(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32
 int nrs_rgraph_edge(nrs_rgraph* g, int32_t i, int32_t j, float out[4], int32_t* status);
 /* parity tap: rows of the dense state, n_ids x capacity each (status 255 = no edge; any pointer may be null) */
 int nrs_rgraph_rows(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, float* maxd, float* mind, float* d0, uint8_t* status);
+/* Grows the graph to new_capacity >= the current one (the limits of nrs_rgraph_create; its error texts with the call's own name in front): the dense state is
+ * re-laid at the new stride on the device, every new cell is "no edge", every edge between old indices keeps its values, and
+ * the lists a GetEdges left on the device are dropped.  On failure the graph is unchanged.  Callers of nrs_track_deform_solve_rg
+ * pad map_pos to the new capacity (n_points = capacity = rows of map_pos still holds). */
+int nrs_rgraph_resize(nrs_rgraph* g, int32_t new_capacity);
 
 /* ---- f2: DeformableTriangulation, batched (modules/optimization/g2o_optimization.cc:559-814) --------------------
  * One call triangulates every candidate feature of a frame (the reference calls the function once per candidate from
@@ -514,6 +519,48 @@ int nrs_triangulate_batch(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_frames,
                           const uint8_t* has_lm, const float* lm_xyz /* .. x 3 */, const int32_t* last_status /* n_ids */,
                           int32_t n_cand, const int32_t* cand_ids, int32_t min_track, int32_t* out_status,
                           float* out_xyz /* n_cand x 3 */, double* out_debug);
+
+/* ---- Frame mapping: Mapping::LandmarkTriangulation (modules/mapping/mapping.cc:65-236) in one call ---------------
+ * Input: the flat TemporalBuffer of nrs_triangulate_batch (same layout, same checks, oldest snapshot first, n_frames <= 21:
+ * InsertSnapshotFromFrame pops when size() > 20 and then inserts, temporal_buffer.cc:49-55) plus deform_mag[n_frames] =
+ * Snapshot::deformation_magnitud (what nrs_track_deform_solve* return in deform_median), Mapping::Options::rad_per_pixel,
+ * CheckRigidity's threshold (the reference passes 0.004) and the shortest track the deformable leg takes (5).
+ * The candidates are found on the device: GetTriangulationCandidatesIds (temporal_buffer.cc:62-74) = the ids whose last_status
+ * is TRACKED (1), ascending.  Per candidate the call returns both legs:
+ *   rigid_status (mapping.cc:117-190; the track's endpoints are the OLDEST and the NEWEST snapshot holding the id, which the
+ *   reference names current_ / previous_ in that order):
+ *     0 NRS_MAP_OK
+ *     1 NRS_MAP_CLOSE            "Close features" (GetClosestMapPointsToFeature(id, 10, 20, 500) empty; both legs get this code)
+ *     2 NRS_MAP_NOT_RIGID        "Rigidity not detected"
+ *     3 NRS_MAP_MIDPOINT         TriangulateMidPoint's own error (geometry_toolbox.cc:45-79 returns none: never produced)
+ *     4 NRS_MAP_PARALLAX         "Parallax error." -- parallax outside [10, 20] x rad_per_pixel
+ *     5 NRS_MAP_DEPTH_PREVIOUS   "Parallax error." -- negative depth in the previous (newest) camera
+ *     6 NRS_MAP_REPROJ_PREVIOUS  "Parallax error." -- squared reprojection error > 5.991 there
+ *     7 NRS_MAP_DEPTH_CURRENT    "Parallax error." -- negative depth in the current (oldest) camera
+ *     8 NRS_MAP_REPROJ_CURRENT   "Parallax error." -- squared reprojection error > 5.991 there
+ *   deform_status (:97-115): the codes of nrs_triangulate_batch (10 = "Short track") and 11 = "NaN." (a result with a NaN).
+ * counts = n_rigid_triangulations, n_deformable_triangulations and the mode of the vote (:192-209): 1 rigid (n_rigid > 1.5
+ * n_deformable), else 2 deformable (n_deformable >= 1.5 n_rigid; also 0 / 0), else 0 none.  The accepted list (:211-236) is, in
+ * candidate order, every success of the voted leg without a NaN that has a keypoint in snapshot index_snapshot (-1 = the last
+ * one, which is what current_frame->GetId() - 1 names when DoMapping runs: DESIGN.md 4 "Frame mapping").
+ * Every output array needs room for as many entries as there are TRACKED ids (x 3 for positions).  A frame without
+ * candidates returns 0 with *n_cand = *n_accepted = 0, mode 2, and launches nothing. */
+enum { NRS_MAP_OK = 0, NRS_MAP_CLOSE = 1, NRS_MAP_NOT_RIGID = 2, NRS_MAP_MIDPOINT = 3, NRS_MAP_PARALLAX = 4, NRS_MAP_DEPTH_PREVIOUS = 5,
+       NRS_MAP_REPROJ_PREVIOUS = 6, NRS_MAP_DEPTH_CURRENT = 7, NRS_MAP_REPROJ_CURRENT = 8 };
+int nrs_map_frame(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_frames, const float* poses /* n_frames x 7 */, int32_t n_ids,
+                  const uint8_t* has_kp, const float* kp_xy, const uint8_t* has_lm, const float* lm_xyz, const int32_t* last_status,
+                  const float* deform_mag /* n_frames */, float rad_per_pixel, float rigidity_th, int32_t min_track,
+                  int32_t index_snapshot, int32_t* n_cand, int32_t* cand_ids, int32_t* rigid_status, float* rigid_xyz,
+                  int32_t* deform_status, float* deform_xyz, int32_t counts[3], int32_t* n_accepted, int32_t* accepted_ids,
+                  float* accepted_xyz);
+
+/* Graph growth of the same function (mapping.cc:238-256): AddEdge(new, other, pos[other] - pos[new]) for every new landmark
+ * against every map point the frame holds as TRACKED_WITH_3D or JUST_TRIANGULATED -- the new ones included, so a pair of two
+ * new points is added from both sides and the second AddEdge writes the same edge (regularization_graph.cc:38-55).  These are
+ * exactly the semantics of nrs_rgraph_add_edges, which this call forwards to (tests/test_gpu_map.py holds it to
+ * RegularizationGraph.AddEdge of the restatement); the graph must have been resized to hold the new indices. */
+int nrs_map_grow_graph(nrs_ctx* ctx, nrs_rgraph* g, const float* pos, int32_t n_new, const int32_t* new_ids, int32_t n_other,
+                       const int32_t* other_ids);
 
 /* ---- a2: CameraPoseAndDeformationOptimization (g2o_optimization.cc:148-557) ------------------
  * Frame side: n_f landmarks in frame index order with their map-point index (f_map, -1 = none),

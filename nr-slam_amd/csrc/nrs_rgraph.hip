@@ -734,3 +734,54 @@ extern "C" int nrs_rgraph_rows(nrs_rgraph* g, int32_t n_ids, const int32_t* ids,
     }
     return NRS_OK;
 }
+
+// Growth (the map gains points: Mapping::LandmarkTriangulation, mapping.cc:225): four new arrays at the new stride, the old
+// rows copied into their top-left corner on the device, everything else "no edge".  The old arrays are freed only once the new
+// ones are complete, so a failure leaves the graph as it was.
+extern "C" int nrs_rgraph_resize(nrs_rgraph* g, int32_t new_capacity) {
+    if (!g) return NRS_ERR_INVALID;
+    nrs_ctx* c = g->c;
+    if (new_capacity < g->cap) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_resize: capacity %d is below the graph's %d", new_capacity, g->cap);
+    if (new_capacity <= 1 || new_capacity > 200000) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_resize: capacity %d is past the limit of 200000 points (nrs_rgraph_create: bad argument)", new_capacity);
+    if (new_capacity == g->cap) return NRS_OK;
+    NRS_HIP(c, hipSetDevice(c->device));
+    const size_t n2 = (size_t)new_capacity * new_capacity, oc = (size_t)g->cap, ncap = (size_t)new_capacity;
+    float *mx = nullptr, *mn = nullptr, *d0 = nullptr;
+    uint8_t* st = nullptr;
+    hipError_t e = hipMalloc((void**)&mx, n2 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&mn, n2 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&d0, n2 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&st, n2);
+    auto drop = [&]() { if (mx) (void)hipFree(mx); if (mn) (void)hipFree(mn); if (d0) (void)hipFree(d0); if (st) (void)hipFree(st); };
+    if (e != hipSuccess) {
+        const int rc = c->fail(NRS_ERR_ALLOC, "nrs_rgraph_resize (as nrs_rgraph_create): %zu bytes for %d points: %s", n2 * 13, new_capacity, hipGetErrorString(e));
+        (void)hipGetLastError();
+        drop();
+        return rc;
+    }
+    hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, c->stream, st, n2);
+    e = hipGetLastError();
+    // (the float arrays are read only where the status says there is an edge; zeroed all the same so that no cell is undefined)
+    if (e == hipSuccess) e = hipMemsetAsync(mx, 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(mn, 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d0, 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(mx, ncap * 4, g->maxd, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(mn, ncap * 4, g->mind, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(d0, ncap * 4, g->d0, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(st, ncap, g->st, oc, oc, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        const int rc = c->fail(NRS_ERR_HIP, "nrs_rgraph_resize: %s", hipGetErrorString(e));
+        drop();
+        return rc;
+    }
+    (void)hipFree(g->maxd); (void)hipFree(g->mind); (void)hipFree(g->d0); (void)hipFree(g->st);
+    g->maxd = mx; g->mind = mn; g->d0 = d0; g->st = st;
+    g->cap = new_capacity;
+    // what was sized or filled for the old capacity: the GetEdges lists on the device (rg_walk refuses to read them), the full-matrix
+    // mirrors (rebuilt by the next GetEdges) and the position / flag buffers (re-ensured by every call)
+    g->last_n_ids = 0; g->last_cap = 0;
+    c->release(g->mir);
+    g->h_slot.clear();
+    return NRS_OK;
+}

@@ -20,32 +20,14 @@
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
 #include "nrs_geom_f32.hpp"
+#include "nrs_triang_dev.hpp"
 
 namespace nrs {
 
-constexpr int TR_MAXF = 21;                 // TemporalBuffer size (SLAM/system.cc:42: 20, + the current frame)
 constexpr int TR_MAXN = 11;                 // `size() > num_neighbors` with num_neighbors = 10
 constexpr int TR_N = 3 * TR_MAXF;           // unknowns
 constexpr int TR_LD = TR_N + 1;             // leading dimension of the LDS matrices
 constexpr int TR_PAIRS = TR_MAXF * (TR_MAXF - 1) / 2;
-enum { TR_OK = 0, TR_CLOSE, TR_REPROJ1, TR_REPROJ2, TR_PARALLAX, TR_NO_NEIGHBOUR, TR_NEG_DEPTH, TR_EMPTY, TR_BAD_NEIGHBOURS,
-       TR_BAD_ERROR, TR_SHORT };
-
-struct TriArgs {
-    Cam cam;
-    int F, n, n_cand, min_track;
-    const float* poses;          // F x 7: camera_transform_world (qx qy qz qw tx ty tz), Sophus::SE3f
-    const uint8_t* has_kp;       // F x n
-    const float* kp_xy;          // F x n x 2
-    const uint8_t* has_lm;       // F x n
-    const float* lm_xyz;         // F x n x 3
-    const int* status;           // n: LandmarkStatus in the last snapshot
-    const int* cand;             // n_cand
-    int* o_status;               // n_cand
-    float* o_xyz;                // n_cand x 3
-    double* o_dbg;               // n_cand x 4 or null: final chi2, LM iterations, trials, regulariser edges
-};
-
 __device__ inline double wave_sum_all(double v) { return wave_sum(v); }
 __device__ inline double wave_max(double v) {
 #pragma unroll
@@ -71,7 +53,7 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs A) {
     const int lane = threadIdx.x, ci = blockIdx.x;
     if (ci >= A.n_cand) return;
     const int cand = A.cand[ci];
-    const int last = A.F - 1, n = A.n;
+    const int n = A.n;
     auto finish = [&](int code, float x, float y, float z) {
         if (lane == 0) {
             A.o_status[ci] = code;
@@ -80,16 +62,9 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs A) {
     };
     if (A.o_dbg && lane < 4) A.o_dbg[4 * ci + lane] = 0;
     // ================= GetClosestMapPointsToFeature(candidate, 10, 20, 500) on the last snapshot
-    const float cx = A.kp_xy[2 * ((size_t)last * n + cand)], cy = A.kp_xy[2 * ((size_t)last * n + cand) + 1];
-    auto dist_to = [&](int j) -> float {
-        const double ddx = (double)(cx - A.kp_xy[2 * ((size_t)last * n + j)]), ddy = (double)(cy - A.kp_xy[2 * ((size_t)last * n + j) + 1]);
-        return (float)sqrt(ddx * ddx + ddy * ddy);                // cv::norm(Point2f) -> double, stored as float
-    };
-    auto eligible = [&](int j) { return j != cand && A.has_kp[(size_t)last * n + j] && A.status[j] == 0; };
-    int close = 0;
-    for (int j = lane; j < n; j += 64)
-        if (eligible(j)) { const float d = dist_to(j); if (!(d > 500.f) && d < 20.f) close = 1; }
-    close = __any(close);
+    auto dist_to = [&](int j) -> float { return tb_dist(A, cand, j); };
+    auto eligible = [&](int j) { return tb_eligible(A, cand, j); };
+    const int close = A.close_bits ? (A.close_bits[ci] & 1) : __any(tb_scan_close(A, cand, lane, 64) & 1);
     int n_nb = 0;
     {
         float last_d = -1.f;
@@ -419,6 +394,42 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs A) {
     }
 }
 
+int tri_upload(nrs_ctx* c, DevBuf& big, size_t extra, const nrs_camera* cam, int n_frames, const float* poses, int n_ids, const uint8_t* has_kp,
+               const float* kp_xy, const uint8_t* has_lm, const float* lm_xyz, const int32_t* last_status, int min_track, TriArgs& A, char** rest) {
+    NRS_HIP(c, hipSetDevice(c->device));
+    const size_t fn = (size_t)n_frames * n_ids;
+    const size_t bytes = sizeof(float) * 7 * n_frames + 2 * fn + sizeof(float) * 5 * fn + sizeof(int) * (size_t)n_ids + 256 * 7;
+    NRS_TRY(c->ensure(big, bytes + extra));
+    char* p = big.as<char>();                                          // carved with 256-byte alignment
+    A.cam.model = cam->model;
+    for (int i = 0; i < 8; ++i) A.cam.p[i] = cam->params[i];
+    A.F = n_frames; A.n = n_ids; A.n_cand = 0; A.min_track = min_track;
+    auto up = [&](const void* src, size_t nbytes) -> char* {
+        char* d = p;
+        p += (nbytes + 255) / 256 * 256;
+        if (hipMemcpyAsync(d, src, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
+        return d;
+    };
+    A.poses = reinterpret_cast<float*>(up(poses, sizeof(float) * 7 * n_frames));
+    A.has_kp = reinterpret_cast<uint8_t*>(up(has_kp, fn));
+    A.kp_xy = reinterpret_cast<float*>(up(kp_xy, sizeof(float) * 2 * fn));
+    A.has_lm = reinterpret_cast<uint8_t*>(up(has_lm, fn));
+    A.lm_xyz = reinterpret_cast<float*>(up(lm_xyz, sizeof(float) * 3 * fn));
+    A.status = reinterpret_cast<int*>(up(last_status, sizeof(int) * (size_t)n_ids));
+    A.cand = nullptr; A.o_status = nullptr; A.o_xyz = nullptr; A.o_dbg = nullptr; A.close_bits = nullptr;
+    if (!A.poses || !A.has_kp || !A.kp_xy || !A.has_lm || !A.lm_xyz || !A.status) return c->fail(NRS_ERR_HIP, "temporal buffer: upload failed");
+    *rest = p;
+    return NRS_OK;
+}
+
+int tri_launch(nrs_ctx* c, const TriArgs& A) {
+    const size_t shm = sizeof(double) * (2 * TR_N * TR_LD + 7 * TR_N + 7 * TR_MAXF + 5 * TR_PAIRS + 2 * TR_MAXF) + sizeof(int) * (TR_MAXN + 1 + TR_MAXF + 8);
+    NRS_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_triangulate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_triangulate, dim3(A.n_cand), dim3(64), shm, c->stream, A);
+    NRS_HIP(c, hipGetLastError());
+    return NRS_OK;
+}
+
 }  // namespace nrs
 
 using namespace nrs;
@@ -437,39 +448,20 @@ extern "C" int nrs_triangulate_batch(nrs_ctx* c, const nrs_camera* cam, int32_t 
         if (!has_kp[(size_t)(n_frames - 1) * n_ids + cand_ids[i]]) return c->fail(NRS_ERR_INVALID, "candidate %d has no keypoint in the last snapshot", cand_ids[i]);
     }
     if (n_cand == 0) return NRS_OK;
-    NRS_HIP(c, hipSetDevice(c->device));
-    const size_t fn = (size_t)n_frames * n_ids;
-    const size_t bytes = sizeof(float) * 7 * n_frames + 2 * fn + sizeof(float) * 5 * fn + sizeof(int) * ((size_t)n_ids + 2 * (size_t)n_cand) +
-                         sizeof(float) * 3 * (size_t)n_cand + sizeof(double) * 4 * (size_t)n_cand + 1024;
+    const size_t extra = sizeof(int) * 2 * (size_t)n_cand + sizeof(float) * 3 * (size_t)n_cand + sizeof(double) * 4 * (size_t)n_cand + 256 * 5;
     DevBuf big;
-    NRS_TRY(c->ensure(big, bytes + 256 * 12));
     struct Free2 { nrs_ctx* c; DevBuf* b; ~Free2() { c->release(*b); } } fr2{c, &big};
-    char* p = big.as<char>();                                          // carved with 256-byte alignment
     TriArgs A;
-    A.cam.model = cam->model;
-    for (int i = 0; i < 8; ++i) A.cam.p[i] = cam->params[i];
-    A.F = n_frames; A.n = n_ids; A.n_cand = n_cand; A.min_track = min_track;
-    auto up = [&](const void* src, size_t nbytes) -> char* {
-        char* d = p;
-        p += (nbytes + 255) / 256 * 256;
-        if (hipMemcpyAsync(d, src, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
-        return d;
-    };
-    A.poses = reinterpret_cast<float*>(up(poses, sizeof(float) * 7 * n_frames));
-    A.has_kp = reinterpret_cast<uint8_t*>(up(has_kp, fn));
-    A.kp_xy = reinterpret_cast<float*>(up(kp_xy, sizeof(float) * 2 * fn));
-    A.has_lm = reinterpret_cast<uint8_t*>(up(has_lm, fn));
-    A.lm_xyz = reinterpret_cast<float*>(up(lm_xyz, sizeof(float) * 3 * fn));
-    A.status = reinterpret_cast<int*>(up(last_status, sizeof(int) * (size_t)n_ids));
-    A.cand = reinterpret_cast<int*>(up(cand_ids, sizeof(int) * (size_t)n_cand));
-    if (!A.poses || !A.has_kp || !A.kp_xy || !A.has_lm || !A.lm_xyz || !A.status || !A.cand) return c->fail(NRS_ERR_HIP, "nrs_triangulate_batch: upload failed");
+    char* p = nullptr;
+    NRS_TRY(tri_upload(c, big, extra, cam, n_frames, poses, n_ids, has_kp, kp_xy, has_lm, lm_xyz, last_status, min_track, A, &p));
+    A.n_cand = n_cand;
+    A.cand = reinterpret_cast<int*>(p);
+    NRS_HIP(c, hipMemcpyAsync(p, cand_ids, sizeof(int) * (size_t)n_cand, hipMemcpyHostToDevice, c->stream));
+    p += (sizeof(int) * (size_t)n_cand + 255) / 256 * 256;
     A.o_status = reinterpret_cast<int*>(p); p += (sizeof(int) * (size_t)n_cand + 255) / 256 * 256;
     A.o_xyz = reinterpret_cast<float*>(p); p += (sizeof(float) * 3 * (size_t)n_cand + 255) / 256 * 256;
     A.o_dbg = out_debug ? reinterpret_cast<double*>(p) : nullptr;
-    const size_t shm = sizeof(double) * (2 * TR_N * TR_LD + 7 * TR_N + 7 * TR_MAXF + 5 * TR_PAIRS + 2 * TR_MAXF) + sizeof(int) * (TR_MAXN + 1 + TR_MAXF + 8);
-    NRS_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_triangulate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL(k_triangulate, dim3(n_cand), dim3(64), shm, c->stream, A);
-    NRS_HIP(c, hipGetLastError());
+    NRS_TRY(tri_launch(c, A));
     NRS_HIP(c, hipMemcpyAsync(out_status, A.o_status, sizeof(int) * (size_t)n_cand, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipMemcpyAsync(out_xyz, A.o_xyz, sizeof(float) * 3 * (size_t)n_cand, hipMemcpyDeviceToHost, c->stream));
     if (out_debug) NRS_HIP(c, hipMemcpyAsync(out_debug, A.o_dbg, sizeof(double) * 4 * (size_t)n_cand, hipMemcpyDeviceToHost, c->stream));

@@ -30,7 +30,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_comm_unique_id", "nrs_comm_init_rccl", "nrs_comm_rank", "nrs_shard_plan",
            "nrs_local_group_create", "nrs_local_group_destroy", "nrs_comm_init_local",
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
-           "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_triangulate_batch", "nrs_track_deform_solve_rg",
+           "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg",
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
            "nrs_init_options_init", "nrs_init_essential",
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame"]
@@ -410,6 +410,16 @@ class RGraph:
         self.ctx._chk(self.lib.nrs_rgraph_edge(self.h, C.c_int32(i), C.c_int32(j), out, C.byref(st)))
         return dict(w=out[0], d0=out[1], max=out[2], min=out[3], status=st.value)
 
+    def resize(self, new_capacity):
+        """nrs_rgraph_resize: grows the graph (old edges kept, new cells "no edge"); positions passed afterwards have new_capacity rows"""
+        self.ctx._chk(self.lib.nrs_rgraph_resize(self.h, C.c_int32(new_capacity)))
+        self.cap = int(new_capacity)
+
+    def grow(self, pos, new_ids, other_ids):
+        """nrs_map_grow_graph (mapping.cc:238-256): every new landmark against every map point the frame holds with a position"""
+        pos, a, b = self._pos(pos), _i32(new_ids), _i32(other_ids)
+        self.ctx._chk(self.lib.nrs_map_grow_graph(self.ctx.h, self.h, _p(pos, C.c_float), C.c_int32(len(a)), _p(a, C.c_int32), C.c_int32(len(b)), _p(b, C.c_int32)))
+
     def rows(self, ids):
         ids = _i32(ids)
         n = len(ids)
@@ -606,6 +616,32 @@ class Context:
                                                  _p(cand, C.c_int32), C.c_int32(min_track), _p(o_st, C.c_int32), _p(o_xyz, C.c_float),
                                                  _p(dbg, C.c_double)))
         return (o_st, o_xyz, dbg) if debug else (o_st, o_xyz)
+
+    # ---- frame mapping
+    def map_frame(self, cam, tb, deform_mag, rad_per_pixel, rigidity_th=0.004, min_track=5, index_snapshot=-1):
+        """Mapping::LandmarkTriangulation in one call (include/nrs.h nrs_map_frame).  tb: flat temporal buffer dict as for
+        triangulate_batch.  Returns a dict: cand, rigid_status, rigid_xyz, deform_status, deform_xyz, n_rigid, n_deformable, mode
+        (0 none, 1 rigid, 2 deformable), accepted_ids, accepted_xyz."""
+        F, n = np.asarray(tb["has_kp"]).shape
+        poses = _f32(tb["poses"]).reshape(F, 7)
+        has_kp, has_lm = np.ascontiguousarray(tb["has_kp"], np.uint8), np.ascontiguousarray(tb["has_lm"], np.uint8)
+        kp, lm = _f32(tb["kp_xy"]).reshape(F, n, 2), _f32(tb["lm_xyz"]).reshape(F, n, 3)
+        st, mag = _i32(tb["status"]), _f32(deform_mag)
+        if len(mag) != F or len(st) != n:
+            raise ValueError("map_frame: deform_mag needs one value per snapshot, status one per id")
+        m = max(1, int((st == 1).sum()))
+        cand, r_st, d_st, a_id = (np.zeros(m, np.int32) for _ in range(4))
+        r_xyz, d_xyz, a_xyz = (np.zeros((m, 3), np.float32) for _ in range(3))
+        counts = np.zeros(3, np.int32)
+        nc, na = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.nrs_map_frame(self.h, C.byref(cam), C.c_int32(F), _p(poses, C.c_float), C.c_int32(n), _p(has_kp, C.c_uint8),
+                                         _p(kp, C.c_float), _p(has_lm, C.c_uint8), _p(lm, C.c_float), _p(st, C.c_int32), _p(mag, C.c_float),
+                                         C.c_float(rad_per_pixel), C.c_float(rigidity_th), C.c_int32(min_track), C.c_int32(index_snapshot),
+                                         C.byref(nc), _p(cand, C.c_int32), _p(r_st, C.c_int32), _p(r_xyz, C.c_float), _p(d_st, C.c_int32),
+                                         _p(d_xyz, C.c_float), _p(counts, C.c_int32), C.byref(na), _p(a_id, C.c_int32), _p(a_xyz, C.c_float)))
+        nc, na = nc.value, na.value
+        return dict(cand=cand[:nc], rigid_status=r_st[:nc], rigid_xyz=r_xyz[:nc], deform_status=d_st[:nc], deform_xyz=d_xyz[:nc],
+                    n_rigid=int(counts[0]), n_deformable=int(counts[1]), mode=int(counts[2]), accepted_ids=a_id[:na], accepted_xyz=a_xyz[:na])
 
     # ---- f6
     def init_essential(self, cam, ref_xy, cur_xy, status, n_matches, samples=None, taps=True, struct_size=None, **options):

@@ -8,8 +8,11 @@ tracker, one for the two-level reuse tracker); the tests plug the oracle in behi
 
 Keyframes extract new Shi-Tomasi features (tracking.cc:350-372): they enter the frame
 as TRACKED observations without a map point and are followed by LK from then on.  The map is started by `MonoInitializer` +
-`FrameLoop.from_initialization` (tracking.cc:136-214).  Not reproduced (out of the hot-path scope): the mapping thread (triangulation of those features,
-UpdateTriangulatedPoints, BA on keyframes), visualisation.
+`FrameLoop.from_initialization` (tracking.cc:136-214).  With mapping=True the loop also runs the FrameMapping branch of Mapping::DoMapping
+(mapping.cc:36-63) after every tracked frame -- the temporal buffer's snapshot (temporal_buffer.cc:28-56), Mapping::LandmarkTriangulation
+in one backend call, AddGeometryToKeypoint, graph growth -- and Tracking::UpdateTriangulatedPoints (tracking.cc:508-521) at the start of
+the next one, so those features become map points.  Not reproduced: BA on keyframes (KeyFrameMapping and UpdateTrackingFrameFromKeyFrame:
+on the frames where the reference runs them the loop logs that it skipped), visualisation.
 
 Poses are Sophus::SE3f in the reference: unit quaternion + translation in float32, and so is the
 motion-model algebra here (`se3f_*`)."""
@@ -203,10 +206,34 @@ class GpuBackend:
             r["graph"] = graph
             return r
         if self.dense:
-            r = self.ctx.track_deform_solve_rg(self.cam, graph, map_pos, f_map, f_status, f_uv, f_pos, q, t, scale, self.last_trace, self.cap)
+            n = len(map_pos)                                       # (a grown graph's capacity runs ahead of the map: rows beyond it have no edge)
+            r = self.ctx.track_deform_solve_rg(self.cam, graph, map_pos if graph.cap == n else self._padded(map_pos), f_map, f_status, f_uv, f_pos, q, t,
+                                               scale, self.last_trace, self.cap)
+            r["map_pos"] = np.asarray(r["map_pos"])[:n]
             r["graph"] = graph                                     # updated in place on the device
             return r
         return self.ctx.track_deform_solve(self.cam, graph, map_pos, f_map, f_status, f_uv, f_pos, q, t, scale, self.last_trace)
+
+    # ---- frame mapping (include/nrs.h "Frame mapping")
+    def map_frame(self, tb, deform_mag, rad_per_pixel, rigidity_th=0.004, min_track=5):
+        return self.ctx.map_frame(self.cam, tb, deform_mag, rad_per_pixel, rigidity_th, min_track, -1)
+
+    def _padded(self, map_pos):
+        """positions by point index for the dense graph: capacity rows (the graph grows in doubled steps, the map one point at a time)"""
+        pos = np.zeros((self.rg.cap, 3), F32)
+        pos[:len(map_pos)] = map_pos
+        return pos
+
+    def grow_graph(self, graph, map_pos, new_ids, other_ids):
+        """mapping.cc:238-256 on the dense graph, resized in amortised steps (doubled, not +1) to hold len(map_pos) points"""
+        if not self.dense:
+            raise ValueError("mapping needs the dense graph (dense_graph=True)")
+        if self.node_flag is not None:
+            raise ValueError("mapping is not available in the embedded-deformation mode")
+        if len(map_pos) > self.rg.cap:
+            self.rg.resize(max(len(map_pos), 2 * self.rg.cap))
+        self.rg.grow(self._padded(map_pos), new_ids, other_ids)
+        return self.rg
 
     # ---- evaluation (include/nrs.h "f7: evaluation"): FrameEvaluator::EvaluateFrameReconstruction and its sources of ground truth
     def eval_frame(self, q, t, X, kp, depth=None, gt_xyz=None, gt_status=None):
@@ -318,13 +345,62 @@ def sigma_f32(data):
     return F32(np.sqrt(F32(acc / F32(len(data)))))
 
 
+class TemporalBuffer:
+    """TemporalBuffer (modules/map/temporal_buffer.cc:28-56) as a list of snapshots, and its flat form for nrs_map_frame.  The reference
+    pops the oldest snapshot when size() > max_buffer_size BEFORE it inserts: from 20 it goes to 21 without a pop, from 21 to 20 and back to
+    21 -- never more than max + 1 = 21 snapshots, the limit of the flat interface."""
+
+    def __init__(self, max_buffer_size=20):
+        self.max, self.snaps = max_buffer_size, []
+
+    def insert(self, kp_id, kp_xy, pos, status, pose_q, pose_t, deform_mag):
+        keep = (status == TRACKED_WITH_3D) | (status == TRACKED)   # InsertSnapshotFromFrame: GetKeypointsWithStatus({TRACKED_WITH_3D, TRACKED})
+        snap = dict(ids=np.asarray(kp_id, np.int64)[keep], xy=np.asarray(kp_xy, F32)[keep], pos=np.asarray(pos, F32)[keep],
+                    status=np.asarray(status, np.int32)[keep], pose=np.concatenate([pose_q, pose_t]).astype(F32), mag=F32(deform_mag))
+        if len(self.snaps) > self.max:
+            self.snaps.pop(0)
+        self.snaps.append(snap)
+
+    def flat(self, model, prm):
+        """(tb, deform_mag, ids): the dict nrs.Context.map_frame reads over the keypoint ids the buffer holds, ascending (row j = ids[j])"""
+        ids = np.unique(np.concatenate([s["ids"] for s in self.snaps]))
+        F, n = len(self.snaps), len(ids)
+        tb = dict(n_frames=F, poses=np.array([s["pose"] for s in self.snaps], F32), has_kp=np.zeros((F, n), bool), kp_xy=np.zeros((F, n, 2), F32),
+                  has_lm=np.zeros((F, n), bool), lm_xyz=np.zeros((F, n, 3), F32), status=np.full(n, BAD, np.int32), model=model, prm=prm)
+        for f, s in enumerate(self.snaps):
+            j = np.searchsorted(ids, s["ids"])
+            tb["has_kp"][f, j] = True
+            tb["kp_xy"][f, j] = s["xy"]
+            tb["has_lm"][f, j] = True                              # mapppoint_tracks_ holds every keypoint of a snapshot (:41), zeros for TRACKED
+            tb["lm_xyz"][f, j] = s["pos"]
+        tb["status"][np.searchsorted(ids, self.snaps[-1]["ids"])] = self.snaps[-1]["status"]
+        return tb, np.array([s["mag"] for s in self.snaps], F32), ids
+
+
 class FrameLoop:
     """State of Tracking + the slice of Map / Frame it touches, on flat arrays."""
 
     def __init__(self, backend, project_f32, wh, scale, kp0, X0, graph, pose_q, pose_t, im0,
-                 klt_min_ssim=0.7, images_to_insert_keyframe=5, extract_on_keyframes=True):
+                 klt_min_ssim=0.7, images_to_insert_keyframe=5, extract_on_keyframes=True, mapping=False, rad_per_pixel=None, rigidity_th=0.004,
+                 camera=None, max_buffer_size=20):
+        """mapping=True (needs a dense-graph backend, rad_per_pixel = Mapping::Options::rad_per_pixel and camera = (model, params) for the
+        flat temporal buffer): the FrameMapping branch of Mapping::DoMapping after every tracked frame, see the module's header."""
         self.b, self.project, self.wh, self.scale = backend, project_f32, wh, float(scale)
         n = len(kp0)
+        self.mapping = bool(mapping)
+        if self.mapping:
+            if not getattr(backend, "dense", False):
+                raise ValueError("mapping=True needs a backend that keeps the all-pairs graph (dense_graph=True)")
+            if rad_per_pixel is None or camera is None:
+                raise ValueError("mapping=True needs rad_per_pixel and camera=(model, params)")
+            self.rpp, self.rigidity_th, self.camera = float(rad_per_pixel), float(rigidity_th), camera
+            # Keypoint::class_id (a persistent id per slot), the TemporalBuffer and Map::unmapped_keyframes_: the initialisation leaves two
+            # keyframes unmapped (tracking.cc:194-195) and its own DoMapping call takes one (map.cc:62-72), so one is left for the first frame
+            self.kp_id = np.arange(n, dtype=np.int64)
+            self.next_kp_id = n
+            self.tbuf = TemporalBuffer(max_buffer_size)
+            self.unmapped_keyframes = 1
+            self.deform_median = 0.0
         # current frame: slot i observes map point map_index[i]
         self.kp = np.asarray(kp0, F32).copy()
         self.pos = np.asarray(X0, F32).copy()
@@ -375,6 +451,8 @@ class FrameLoop:
 
     # ---- tracking.cc:72-112 (tracked branch)
     def track_image(self, im):
+        if self.mapping:
+            self.update_triangulated_points()                      # tracking.cc:87
         lost = self.track_camera_and_deformation(im)
         reused = self.point_reuse(im, lost)
         n3d = int((self.status == TRACKED_WITH_3D).sum())
@@ -386,7 +464,57 @@ class FrameLoop:
                              reused=reused, n_tracked=n3d, keyframe=kf, n_2d=int((self.status == TRACKED).sum()),
                              kp_2d=self.kp[self.map_index < 0].copy(),
                              status_by_map=self._status_by_map(), pos_by_map=self._pos_by_map()))
+        if self.mapping and n3d >= 10:
+            # Map::SetLastFrame (tracking.cc:105, map.cc:106-118), then System::TrackImage's DoMapping (SLAM/system.cc:128)
+            self.tbuf.insert(self.kp_id, self.kp, self.pos, self.status, self.pose[0], self.pose[1], self.deform_median)
+            self.log[-1]["mapping"] = self.do_mapping(kf)
+            self.log[-1]["map_size"] = len(self.map_pos)
+            self.log[-1]["status_after_mapping"] = self._status_by_map()
         return n3d >= 10
+
+    # ---- Mapping::DoMapping (mapping.cc:36-54) without the BA: a pending keyframe takes the KeyFrameMapping branch, which is skipped
+    def do_mapping(self, keyframe_inserted):
+        if keyframe_inserted:
+            self.unmapped_keyframes += 1
+        if self.unmapped_keyframes > 0:
+            self.unmapped_keyframes -= 1
+            return dict(skipped="KeyFrameMapping", triangulated=[], mode=None)
+        return self.frame_mapping()
+
+    # ---- Mapping::LandmarkTriangulation (mapping.cc:65-257) on the backend's one call
+    def frame_mapping(self):
+        tb, mag, ids = self.tbuf.flat(self.camera[0], self.camera[1])
+        r = self.b.map_frame(tb, mag, self.rpp, self.rigidity_th, 5)
+        acc = ids[np.asarray(r["accepted_ids"], np.int64)]         # keypoint ids, ascending (the order of the candidates)
+        out = dict(skipped=None, triangulated=[int(i) for i in acc], mode=int(r["mode"]), n_rigid=int(r["n_rigid"]),
+                   n_deformable=int(r["n_deformable"]), n_candidates=len(r["cand"]))
+        if not len(acc):
+            return out
+        slot_of = {int(k): i for i, k in enumerate(self.kp_id)}
+        slots = np.array([slot_of[int(k)] for k in acc])
+        n0 = len(self.map_pos)
+        new_mp = np.arange(n0, n0 + len(acc), dtype=np.int32)      # Map::CreateAndInsertMapPoint: the next map point ids
+        xyz = np.asarray(r["accepted_xyz"], F32)
+        self.pos[slots], self.status[slots], self.map_index[slots] = xyz, JUST_TRIANGULATED, new_mp     # Frame::AddGeometryToKeypoint
+        self.map_pos = np.vstack([self.map_pos, xyz]).astype(F32)
+        # :238-256: every new landmark against the frame's map points with a position, the new ones included
+        has = ((self.status == TRACKED_WITH_3D) | (self.status == JUST_TRIANGULATED)) & (self.map_index >= 0)
+        self.graph = self.b.grow_graph(self.graph, self.map_pos, new_mp, self.map_index[has].astype(np.int32))
+        return out
+
+    # ---- Tracking::UpdateTriangulatedPoints (tracking.cc:508-521)
+    def update_triangulated_points(self):
+        slots = np.nonzero(self.status == JUST_TRIANGULATED)[0].astype(np.int32)
+        if not len(slots):
+            return
+        if self.dev_templates:
+            self.b.archive_templates(slots, self.map_index[slots].astype(np.int32))
+        else:
+            tpl = self.b.klt_get_templates(len(self.map_index))
+            self.templates = list(self.templates) + [None] * (len(self.map_pos) - len(self.templates))
+            for i in slots:
+                self.templates[int(self.map_index[i])] = tpl[int(i)]
+        self.status[slots] = TRACKED_WITH_3D
 
     # ---- FrameEvaluator::EvaluateFrameReconstruction (frame_evaluator.cc:35-52), called after track_image as System::TrackImageWithDepth
     # does (SLAM/system.cc:162-187)
@@ -438,6 +566,7 @@ class FrameLoop:
         self.pose = (np.asarray(r["pose_q"], np.float64).astype(F32), np.asarray(r["pose_t"], np.float64).astype(F32))
         self.pos[mm], self.status[mm] = np.asarray(r["f_pos"], F32), np.asarray(r["f_status"], np.int32)
         self.map_pos, self.graph = np.asarray(r["map_pos"], F32), r["graph"]
+        self.deform_median = float(r.get("median", 0.0)) if hasattr(r, "get") else 0.0      # Frame::SetDeformationMaginitud (OPT:455)
         self.motion = se3f_mul(self.pose, se3f_inv(self.last_pose))
         return set(int(x) for x in r["lost"])
 
@@ -490,6 +619,9 @@ class FrameLoop:
             self.pos = np.vstack([self.pos, self.map_pos[nm]]).astype(F32)
             self.status = np.concatenate([self.status, np.full(len(nm), TRACKED_WITH_3D, np.int32)]).astype(np.int32)
             self.map_index = np.concatenate([self.map_index, nm]).astype(np.int32)
+            if self.mapping:                                       # a re-inserted map point gets a fresh class_id
+                self.kp_id = np.concatenate([self.kp_id, self.next_kp_id + np.arange(len(nm))])
+                self.next_kp_id += len(nm)
             if self.dev_templates:
                 self.b.insert_archived(nm.astype(np.int32), xy[nk].astype(F32))
                 return reused
@@ -517,10 +649,15 @@ class FrameLoop:
             self.pos = np.vstack([self.pos, np.zeros((k, 3), F32)]).astype(F32)
             self.status = np.concatenate([self.status, np.full(k, TRACKED, np.int32)]).astype(np.int32)
             self.map_index = np.concatenate([self.map_index, np.full(k, -1, np.int32)]).astype(np.int32)
+            if self.mapping:                                       # extracted corners get fresh class_ids
+                self.kp_id = np.concatenate([self.kp_id, self.next_kp_id + np.arange(k)])
+                self.next_kp_id += k
         # KeyFrame(frame) + Frame::SetFromKeyFrame (keyframe.cc:26-55, frame.cc:47-77): the slots with 3D, then
         # the TRACKED ones; everything else leaves the frame
         order = np.concatenate([np.nonzero(self.status == TRACKED_WITH_3D)[0], np.nonzero(self.status == TRACKED)[0]])
         self.kp, self.pos, self.status, self.map_index = self.kp[order], self.pos[order], self.status[order], self.map_index[order]
+        if self.mapping:
+            self.kp_id = self.kp_id[order]
         self.pos[self.status == TRACKED] = 0
         self.map_index[self.status == TRACKED] = -1               # only the 3D slots keep their map point (frame.cc:56-62)
         self.b.klt_set_reference(im, self.kp)

@@ -357,7 +357,7 @@ def _texture(h, w, rng, margin=32):
     return 120 + tex
 
 
-def make_frame_sequence(n_points=400, n_frames=6, seed=9, model=PINHOLE, step=0.012, occluders=2):
+def make_frame_sequence(n_points=400, n_frames=6, seed=9, model=PINHOLE, step=0.012, occluders=2, half_size=False, deform_amp=1.2):
     """A short consistent monocular sequence for the frame-loop harness: a deforming
     surface seen by a slowly moving camera.  Frame 0 is the initialised map (keyframe): 3D positions
     (truth + noise, map units), keypoints, regularisation graph; frames 1.. are images only.  Images
@@ -367,6 +367,9 @@ def make_frame_sequence(n_points=400, n_frames=6, seed=9, model=PINHOLE, step=0.
     rng = np.random.default_rng(seed)
     prm = HAMLYN_PINHOLE if model == PINHOLE else ENDOMAPPER_KB8
     w, h = (640, 480) if model == PINHOLE else (736, 552)
+    if half_size:                                                  # the same field of view on half as many pixels (320 x 240 for the pinhole)
+        prm = np.concatenate([prm[:4] * F32(0.5), prm[4:]]).astype(F32)
+        w, h = w // 2, h // 2
     Xmm, nrm = surface_points(n_points, rng, model)
     centroid = Xmm.mean(0)
     scale = F32(3.0) / F32(np.median(Xmm[:, 2]))
@@ -380,7 +383,7 @@ def make_frame_sequence(n_points=400, n_frames=6, seed=9, model=PINHOLE, step=0.
         else:
             R = _small_rot(np.array([0.03 * phi, -0.04 * phi, 0.02 * phi]))
             t = -R @ np.array([1.5 * phi, 1.0 * np.sin(np.pi * phi), 2.0 * phi])
-        amp = 1.2 * np.sin(2 * np.pi * f / 40.0) * (0.6 + 0.4 * np.sin(Xmm[:, 0] / 11.0 + 0.3) * np.cos(Xmm[:, 1] / 9.0))
+        amp = deform_amp * np.sin(2 * np.pi * f / 40.0) * (0.6 + 0.4 * np.sin(Xmm[:, 0] / 11.0 + 0.3) * np.cos(Xmm[:, 1] / 9.0))
         X = Xmm + amp[:, None] * nrm
         pc = X @ R.T + t
         poses_R.append(R); poses_t.append(t * s); Xt.append(X * s)
@@ -442,7 +445,7 @@ def edge_checksum(e):
 
 
 def make_temporal_buffer(n_frames=12, seed=3, model=PINHOLE, spacing=26.0, cand_frac=0.3, lm_noise=0.004, kp_noise=0.25,
-                         baseline=0.35):
+                         baseline=0.35, deform_amp=0.8):
     """A flat TemporalBuffer (reference modules/map/temporal_buffer.h:43-63) for DeformableTriangulation: n_frames
     snapshots of a deforming surface seen by a translating camera.  Features sit on a jittered image grid (the
     extractor's non-maximum suppression keeps features apart; GetClosestMapPointsToFeature rejects a candidate with a
@@ -478,7 +481,7 @@ def make_temporal_buffer(n_frames=12, seed=3, model=PINHOLE, spacing=26.0, cand_
         R = _small_rot(np.array([0.002 * f, -0.003 * f, 0.001 * f]))
         C = np.array([baseline * f, 0.12 * baseline * f, 0.0])              # camera centre (mm)
         t = -R @ C
-        amp = 0.8 * np.sin(2 * np.pi * f / 30.0) * (0.6 + 0.4 * np.sin(Xmm[:, 0] / 11.0 + 0.3) * np.cos(Xmm[:, 1] / 9.0))
+        amp = deform_amp * np.sin(2 * np.pi * f / 30.0) * (0.6 + 0.4 * np.sin(Xmm[:, 0] / 11.0 + 0.3) * np.cos(Xmm[:, 1] / 9.0))
         X = Xmm + amp[:, None] * nrm
         uv = _project(model, P, X @ R.T + t) + rng.normal(0, kp_noise, (n, 2))
         q = _rot_to_quat(R)
@@ -494,6 +497,21 @@ def make_temporal_buffer(n_frames=12, seed=3, model=PINHOLE, spacing=26.0, cand_
     cand = np.where(is_cand & has_kp[-1])[0].astype(np.int32)
     return dict(n_frames=n_frames, poses=np.array(poses, F32), has_kp=has_kp, kp_xy=kp_xy, has_lm=has_lm, lm_xyz=lm_xyz,
                 status=status, cand=cand, truth=truth[cand].astype(F32), model=model, prm=prm, scale=F32(scale))
+
+
+def make_mapping_buffer(n_frames=12, seed=3, model=PINHOLE, spacing=26.0, cand_frac=0.3, rad_per_pixel=None, deform_amp=0.2, **kw):
+    """make_temporal_buffer for Mapping::LandmarkTriangulation (include/nrs.h nrs_map_frame): adds `deform_mag` (one
+    Snapshot::deformation_magnitud per snapshot, all below the reference's rigidity threshold 0.004) and `rad_per_pixel` (default:
+    1 / fx), and picks the camera baseline so that the parallax of a track of 0.7 (n_frames - 1) frames at the scene's depth (60 mm) is
+    15 rad_per_pixel: the rigid leg's window [10, 20] rad_per_pixel then holds the longer tracks and rejects the short ones."""
+    prm = HAMLYN_PINHOLE if model == PINHOLE else ENDOMAPPER_KB8
+    rpp = float(1.0 / prm[0]) if rad_per_pixel is None else float(rad_per_pixel)
+    baseline = 15.0 * rpp * 60.0 / (0.7 * (n_frames - 1))
+    tb = make_temporal_buffer(n_frames, seed, model, spacing, cand_frac, baseline=baseline, deform_amp=deform_amp, **kw)
+    rng = np.random.default_rng(seed + 7919)
+    tb["deform_mag"] = rng.uniform(0.0005, 0.003, n_frames).astype(F32)
+    tb["rad_per_pixel"] = rpp
+    return tb
 
 
 def _rot_to_quat(R):
