@@ -88,6 +88,7 @@ struct nrs_ctx {
     nrs::DevBuf pack_ws, pack_ws2, pack_ws3, pack_ws4;   // device-side problem construction (nrs_engine_devpack.hpp): raw inputs + intermediates
     nrs::DevBuf dba_skin;            // ... and of the resident BA window (N2b)
     nrs::DevBuf dba_kft;             // embedded BA window: the keyframe-block factorisation (nrs_engine_kft.hpp)
+    bool kft_attr_done = false;      // ... its kernels' dynamic-LDS attributes are set on this context's device (kft_kernel_attributes)
     nrs::EmbWindow* dba_embwin = nullptr;   // lists of the resident window when nrs_dba_solve_window_embedded made it (dropped by dba_free)
     void* embwin_pin = nullptr;      // pinned host staging of the device-built lists (nrs_engine_embwin.hpp), kept for the context's lifetime
     size_t embwin_pin_cap = 0;

@@ -27,7 +27,7 @@
 
 namespace nrs {
 
-constexpr int KFT_B = 64;            // pivot block / tile of the sweeps
+// (KFT_B, the pivot block / tile of the sweeps, KFT_BD and KFT_TC: nrs_engine_consts.hpp -- the set-up's host stages share them)
 
 struct KftDev {
     int K, ld, nb, m, nfm;           // keyframes; padded block dimension (multiple of KFT_B); ld / KFT_B; middle keyframe; ld / 3 (stride of the per-node tables)
@@ -60,7 +60,6 @@ struct KftDev {
     int k_lo, k_hi, row0;
     const double* bd_val;            // damper values of the couplings across rank boundaries (all-reduced per factorisation; src flag KFT_BD)
 };
-constexpr uint32_t KFT_BD = 0x40000000u;   // te_src: the value is bd_val[index] (pe_src: type 3)
 
 struct KftHost {
     bool on = false;
@@ -773,7 +772,6 @@ __global__ __launch_bounds__(256) void k_kft_gct(KftDev F, int f0, int f1) {
 }
 // one workgroup per KFT_TC columns of S_to: their YT rows in LDS, a thread per 'to' node -- its list is read once for all the columns
 // and its three components
-constexpr int KFT_TC = 4;
 constexpr int KFT_TGT_NT = 512;      // (a keyframe's ~460 nodes in one pass)
 __global__ __launch_bounds__(KFT_TGT_NT) void k_kft_tgt(KftDev F, int f0, int f1) {
     extern __shared__ double yrow[];

@@ -79,6 +79,23 @@ def embedded(solver, **opts):
     return digest(tr.trials, pq, xyz, sk)
 
 
+def run_ranks(group, world, rank_main, out):
+    """One thread per rank; a rank that raises or does not finish says so in its place of the line, not a bare None."""
+    def guarded(r):
+        try:
+            rank_main(r)
+        except Exception as exc:                                      # (e.g. debug_kft_share where the factorisation was dropped)
+            out[r] = "ERROR %s: %s" % (type(exc).__name__, exc)
+
+    th = [threading.Thread(target=guarded, args=(r,), daemon=True) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(120)
+    group.close()
+    return " | ".join("NOT FINISHED" if o is None else str(o) for o in out)
+
+
 def sharded(world=2, **opts):
     p = S.make_dba_problem(300, 4, 41)
     e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
@@ -97,13 +114,29 @@ def sharded(world=2, **opts):
         out[r] = digest(tr.trials, pq, xyz)
         c.close()
 
-    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(120)
-    group.close()
-    return " | ".join(str(o) for o in out)
+    return run_ranks(group, world, rank_main, out)
+
+
+def sharded_embedded(world, **opts):
+    """The embedded 300 x 4 x 40 window with the keyframe-block factorisation sharded over `world` thread ranks (sharded_kft = 1)."""
+    p, flag, nb = W.window(W.CASES[0], "nodes")
+    e = nrs.dba_build_edges_embedded(p["kf_points"], flag, nb)
+    w = S.embedded_window(p, e)
+    cam = nrs.make_camera(p["model"], p["prm"])
+    qt = np.concatenate([p["poses_q"], p["poses_t"]], 1)
+    group = nrs.LocalGroup(world)
+    out = [None] * world
+
+    def rank_main(r):
+        c = nrs.Context(embedded_solver=1, sharded_kft=1, **opts)
+        c.comm_init_local(group, r)
+        tr = nrs.Trace()
+        pq, xyz, sk = c.dba_solve_embedded(cam, qt, w, e, p["scale"], 5, tr)
+        share = c.debug_kft_share()                                   # (an error where the factorisation is not on: its keyframes and what it carved)
+        out[r] = digest(tr.trials, pq, xyz, sk) + " kft k0=%d nk=%d kib=%d" % (share["k0"], share["nk"], share["kib"])
+        c.close()
+
+    return run_ranks(group, world, rank_main, out)
 
 
 CASES = [
@@ -116,6 +149,8 @@ CASES = [
     ("embedded 300x4x40, factorisation", lambda **o: embedded(1, **o)),
     ("embedded 300x4x40, PCG", lambda **o: embedded(2, **o)),
     ("sharded 300x4, 2 thread ranks", lambda **o: sharded(2, **o)),
+    ("sharded embedded 300x4x40, factorisation, 2 ranks", lambda **o: sharded_embedded(2, **o)),
+    ("sharded embedded 300x4x40, factorisation, 3 ranks", lambda **o: sharded_embedded(3, **o)),
 ]
 
 if __name__ == "__main__":
