@@ -629,7 +629,16 @@ int nrs_klt_set_reference(nrs_ctx* ctx, const uint8_t* img, int32_t w, int32_t h
 /* LucasKanadeTracker::Track (LK:170-596).  xy in: initial guess (used when use_initial_flow),
  * out: tracked positions; status in/out: LandmarkStatus, only usable points are tracked and they
  * may become OUT_IMAGE_BOUNDARIES / BAD_FEATURE / BAD; n_good = points that pass the SSIM gate;
- * ssim (may be NULL): SSIM of every point that reached the gate. */
+ * ssim (may be NULL): SSIM of every point that reached the gate.
+ * Two rules are this project's definitions (the reference is undefined there; DESIGN.md 4 "Lucas-Kanade tracker"):
+ *  - top level: the iteration starts at min(max_level, n_levels - 1) of the TRACKED image's pyramid, which is shorter than
+ *    max_level + 1 levels when min(w, h) <= 21 * 2^max_level, and the initial guess (or the previous point) is scaled to that level.
+ *    A tracker configured with max_level >= n_levels returns bit for bit what one configured with n_levels - 1 returns; template
+ *    slots of levels that were not built stay invalid with means of -1.
+ *  - positions: a window origin whose coordinate is not finite, or whose floor does not fit an int, is outside the image.  The test
+ *    comes before every float -> int conversion: the reference point in nrs_klt_set_reference (no template at that level), the
+ *    previous point, every iterate and the SSIM position here (the level ends; OUT_IMAGE_BOUNDARIES at level 0).  A window that is
+ *    all zero in the tracked image (meanJ2 = 0: the step is NaN) ends this way, as does a NaN / inf / 1e30 guess. */
 int nrs_klt_track(nrs_ctx* ctx, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t n,
                   float* xy, int32_t* status, int32_t use_initial_flow, float min_ssim, int32_t* n_good,
                   float* ssim);

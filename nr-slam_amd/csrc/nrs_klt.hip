@@ -107,6 +107,15 @@ __global__ void k_pyr_scharr(PyrLevel L) {
     L.der[(size_t)yo * L.stride + xo] = d;
 }
 
+// floor of a window origin, or false where the coordinate is not finite or its floor does not fit an int: such a position counts as
+// outside the image (include/nrs.h nrs_klt_track; the reference's cvFloor gives INT_MIN there on x86 and takes its out-of-image
+// branch).  Tested BEFORE the float -> int conversion, which is undefined for these values.
+__device__ inline bool win_origin(float px, float py, int& ix, int& iy) {
+    if (!(px >= -2147483648.f && px < 2147483648.f && py >= -2147483648.f && py < 2147483648.f)) return false;          // NaN compares false
+    ix = (int)floorf(px); iy = (int)floorf(py);
+    return true;
+}
+
 __device__ inline int cv_round(float v) { return __float2int_rn(v); }          // round half to even
 
 __device__ inline void bilinear_weights(float a, float b, int& w00, int& w01, int& w10, int& w11) {
@@ -155,9 +164,9 @@ __global__ __launch_bounds__(64) void k_klt_set_reference(Pyr pyr, int n, int le
     const PyrLevel L = pyr.L[level];
     const float half = (KW - 1) * 0.5f;
     const float px = pts[2 * i] / (float)(1 << level) - half, py = pts[2 * i + 1] / (float)(1 << level) - half;
-    const int ix = (int)floorf(px), iy = (int)floorf(py);
+    int ix, iy;
     const int gap = KW / 2;                                      // round(winSize.width/2), LK:58
-    if (ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) return;
+    if (!win_origin(px, py, ix, iy) || ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) return;
     int w00, w01, w10, w11;
     bilinear_weights(px - (float)ix, py - (float)iy, w00, w01, w10, w11);
     bool masked = false;
@@ -214,21 +223,23 @@ __global__ __launch_bounds__(64) void k_klt_track(TrackArgs a) {
     const float FLT_SCALE = 1.f / (1 << 20);
     float ptx = a.pts[2 * i], pty = a.pts[2 * i + 1];
     const float rx = a.prev[2 * i], ry = a.prev[2 * i + 1];
-    for (int level = a.max_level; level >= 0; --level) {
+    // the top level is the highest one the tracked image's pyramid has (a short pyramid: min(w, h) <= 21 * 2^max_level); the initial
+    // guess is scaled there (include/nrs.h nrs_klt_track)
+    const int top = min(a.max_level, a.pyr.n_levels - 1);
+    for (int level = top; level >= 0; --level) {
         if (!usable(st)) break;
-        if (level >= a.pyr.n_levels) continue;
         const PyrLevel L = a.pyr.L[level];
         const float inv = (float)(1. / (1 << level));
         float pvx = rx * inv, pvy = ry * inv;
         float nx, ny;
-        if (level == a.max_level) {
+        if (level == top) {
             if (a.initial_flow) { nx = ptx * inv; ny = pty * inv; }
             else { nx = pvx; ny = pvy; }
         } else { nx = ptx * 2.f; ny = pty * 2.f; }
         ptx = nx; pty = ny;
         pvx -= half; pvy -= half;
-        const int ipx = (int)floorf(pvx), ipy = (int)floorf(pvy);
-        if (ipx < -gap || ipx >= L.w - gap || ipy < -gap || ipy >= L.h - gap) {
+        int ipx, ipy;
+        if (!win_origin(pvx, pvy, ipx, ipy) || ipx < -gap || ipx >= L.w - gap || ipy < -gap || ipy >= L.h - gap) {
             if (level == 0) st = NRS_OUT_IMAGE_BOUNDARIES;
             continue;
         }
@@ -244,8 +255,8 @@ __global__ __launch_bounds__(64) void k_klt_track(TrackArgs a) {
         nx -= half; ny -= half;
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < a.max_iters; ++j) {
-            const int ix = (int)floorf(nx), iy = (int)floorf(ny);
-            if (ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) {
+            int ix, iy;
+            if (!win_origin(nx, ny, ix, iy) || ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) {
                 if (level == 0) st = NRS_OUT_IMAGE_BOUNDARIES;
                 break;
             }
@@ -345,10 +356,9 @@ __global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, int levels, flo
     const float half = (KW - 1) * 0.5f;
     const int gap = KW / 2 + 1;
     const float ptx = pts[2 * i], pty = pts[2 * i + 1];
-    if (isnan(ptx) || isnan(pty)) { if (lane == 0) status[i] = NRS_OUT_IMAGE_BOUNDARIES; return; }
     const float nx = ptx - half, ny = pty - half;
-    const int ix = (int)floorf(nx), iy = (int)floorf(ny);
-    if (ix < -gap || ix >= L.w - gap * 2 || iy < -gap || iy >= L.h - gap * 2) {
+    int ix, iy;
+    if (!win_origin(nx, ny, ix, iy) || ix < -gap || ix >= L.w - gap * 2 || iy < -gap || iy >= L.h - gap * 2) {
         if (lane == 0) status[i] = NRS_OUT_IMAGE_BOUNDARIES;
         return;
     }

@@ -334,7 +334,7 @@ def make_lk_sequence(n_points=500, seed=5, wh=(640, 480), flow_px=6.0):
             blk = e[y:y + cell, x:x + cell]
             k = np.unravel_index(np.argmax(blk), blk.shape)
             pts.append((x + k[1] + rng.uniform(-0.4, 0.4), y + k[0] + rng.uniform(-0.4, 0.4)))
-    pts = np.array(pts, F32)
+    pts = np.array(pts, F32).reshape(-1, 2)                 # (no point at all on an image too small for the 30 px margin)
     if len(pts) > n_points:
         pts = pts[rng.choice(len(pts), n_points, replace=False)]
     fx, fy = flow(pts[:, 0].astype(np.float64), pts[:, 1].astype(np.float64))

@@ -134,6 +134,16 @@ def _sample(L, ix, iy, wts, win, with_deriv=True):
     return val.astype(np.int32), d.astype(np.int32)
 
 
+def _origin(px, py):
+    """(floor(px), floor(py)) of a window origin, or None where a coordinate is not finite or its floor does not fit an int32:
+    such a position counts as outside the image (this project's rule, DESIGN.md 4 "Lucas-Kanade tracker"; the reference's
+    cvFloor gives INT_MIN there on x86 and takes its out-of-image branch).  Tested BEFORE any float -> int conversion."""
+    lo, hi = F32(-2147483648.0), F32(2147483648.0)
+    if not (lo <= px < hi and lo <= py < hi):                         # NaN compares false
+        return None
+    return int(np.floor(px)), int(np.floor(py))
+
+
 def _seq_sum(v):
     """sequential float32 accumulation in row-major order (what the reference's loops do)."""
     v = np.asarray(v, F32).ravel()
@@ -173,7 +183,10 @@ class LucasKanadeOracle:
             for i in range(n):
                 px = F32(pts[i, 0] / F32(sf)) - half
                 py = F32(pts[i, 1] / F32(sf)) - half
-                ix, iy = int(np.floor(px)), int(np.floor(py))
+                o = _origin(px, py)
+                if o is None:
+                    continue
+                ix, iy = o
                 if ix < -gap or ix >= L.w - gap or iy < -gap or iy >= L.h - gap:
                     continue
                 if mask is not None:
@@ -198,14 +211,18 @@ class LucasKanadeOracle:
         pts = np.array(pts, F32).reshape(-1, 2)
         status = np.array(status, np.int32)
         n = len(self.prev)
+        # for the tests' own vetting (tests/lk_cases.py): at which levels a window of the tracked image was sampled, and what the
+        # iteration handed to the SSIM gate
+        self.last_sampled = np.zeros((n, self.max_level + 1), bool)
         win = self.win
         half = F32((win - 1) * 0.5)
         gap = win // 2 + 1                                             # LK:186
         area = F32(win * win)
-        top = self.max_level
+        # the top level is the highest one the tracked image's pyramid HAS (a short pyramid: min(w, h) <= 21 * 2^max_level); the
+        # initial guess is scaled there.  cv::calcOpticalFlowPyrLK does the same with the level count buildOpticalFlowPyramid returns;
+        # the reference indexes its pyramid vector past the end (DESIGN.md 4 "Lucas-Kanade tracker")
+        top = min(self.max_level, len(pyr) - 1)
         for level in range(top, -1, -1):
-            if level >= len(pyr):
-                continue
             L = pyr[level]
             inv = F32(1.0 / (1 << level))
             for i in range(n):
@@ -218,8 +235,8 @@ class LucasKanadeOracle:
                     nxt = pts[i] * F32(2.0)
                 pts[i] = nxt
                 pvx, pvy = prev[0] - half, prev[1] - half
-                ipx, ipy = int(np.floor(pvx)), int(np.floor(pvy))
-                if ipx < -gap or ipx >= L.w - gap or ipy < -gap or ipy >= L.h - gap:
+                o = _origin(pvx, pvy)
+                if o is None or o[0] < -gap or o[0] >= L.w - gap or o[1] < -gap or o[1] >= L.h - gap:
                     if level == 0:
                         status[i] = OUT_IMAGE_BOUNDARIES
                     continue
@@ -234,17 +251,19 @@ class LucasKanadeOracle:
                 nx, ny = F32(nxt[0] - half), F32(nxt[1] - half)
                 pdx = pdy = F32(0)
                 for j in range(self.max_iters):
-                    ix, iy = int(np.floor(nx)), int(np.floor(ny))
-                    if ix < -gap or ix >= L.w - gap or iy < -gap or iy >= L.h - gap:
+                    o = _origin(nx, ny)
+                    if o is None or o[0] < -gap or o[0] >= L.w - gap or o[1] < -gap or o[1] >= L.h - gap:
                         if level == 0:
                             status[i] = OUT_IMAGE_BOUNDARIES
                         break
+                    ix, iy = o
+                    self.last_sampled[i, level] = True
                     val, d = _sample(L, ix, iy, _weights(nx - F32(ix), ny - F32(iy)), win)
                     meanJ = (_seq_sum(val.astype(F32)) * FLT_SCALE) / area
                     meanJ2 = (_seq_sum((val * val).astype(F32)) * FLT_SCALE) / area
                     with np.errstate(divide="ignore", invalid="ignore"):
-                        alpha = F32(np.sqrt(F32(meanI2 / meanJ2)))
-                    beta = F32(meanI - F32(alpha * meanJ))
+                        alpha = F32(np.sqrt(F32(meanI2 / meanJ2)))                    # a window that is all zero: inf or NaN
+                        beta = F32(meanI - F32(alpha * meanJ))
                     Jf = val.astype(F32)
                     with np.errstate(invalid="ignore", over="ignore"):
                         diff = np.trunc(F32(F32(Jf * alpha) - Iw) - beta)
@@ -294,17 +313,17 @@ class LucasKanadeOracle:
         N_inv_1 = F32(1.0) / F32(win * win - 1)
         good = 0
         ssims = np.full(n, np.nan, F32)
+        self.last_track_xy, self.last_track_status = pts.copy(), status.copy()
         for i in range(n):
             if not is_usable(status[i]):
                 continue
-            if np.isnan(pts[i, 0]) or np.isnan(pts[i, 1]):
+            with np.errstate(invalid="ignore"):                                    # (inf - half)
+                nx, ny = F32(pts[i, 0] - half), F32(pts[i, 1] - half)
+            o = _origin(nx, ny)
+            if o is None or o[0] < -gap or o[0] >= L.w - gap * 2 or o[1] < -gap or o[1] >= L.h - gap * 2:
                 status[i] = OUT_IMAGE_BOUNDARIES
                 continue
-            nx, ny = F32(pts[i, 0] - half), F32(pts[i, 1] - half)
-            ix, iy = int(np.floor(nx)), int(np.floor(ny))
-            if ix < -gap or ix >= L.w - gap * 2 or iy < -gap or iy >= L.h - gap * 2:
-                status[i] = OUT_IMAGE_BOUNDARIES
-                continue
+            ix, iy = o
             val, _ = _sample(L, ix, iy, _weights(nx - F32(ix), ny - F32(iy)), win, with_deriv=False)
             cur = np.clip(np.rint(val / 32.0), 0, 255).astype(F32)                 # short/32 then CV_8U
             ref = np.rint(self.Iref[0][i].astype(np.float64) / 32.0).astype(F32)  # short/32

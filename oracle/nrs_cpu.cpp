@@ -1756,6 +1756,21 @@ int nrs_cpu_lk_track(void* h, const uint8_t* img, int32_t w, int32_t hgt, int32_
     if (n_good) *n_good = g;
     return 0;
 }
+// the stored templates in the layout of nrs_klt_get_templates (include/nrs.h): point-major, (max_level + 1) levels a point; a level
+// that was not filled reads gray = grad = 0, mean = -1, valid = 0
+int nrs_cpu_lk_get_templates(void* h, int16_t* gray, int16_t* grad, float* mean, uint8_t* valid) {
+    const LkTracker* t = static_cast<LkTracker*>(h);
+    const size_t nl = t->meanI.size(), npx = (size_t)t->win * t->win;
+    for (size_t i = 0; i < (size_t)t->n; ++i)
+        for (size_t l = 0; l < nl; ++l) {
+            const size_t s = i * nl + l;
+            std::memcpy(gray + s * npx, &t->Iref[l][i * npx], sizeof(int16_t) * npx);
+            std::memcpy(grad + s * npx * 2, &t->Idref[l][i * npx * 2], sizeof(int16_t) * npx * 2);
+            mean[2 * s] = t->meanI[l][i]; mean[2 * s + 1] = t->meanI2[l][i];
+            valid[s] = t->filled[l][i];
+        }
+    return 0;
+}
 
 int nrs_cpu_max_threads() {
 #ifdef _OPENMP

@@ -220,7 +220,7 @@ class LucasKanadeCpp:
         self.lib = lib or load()
         self.lib.nrs_cpu_lk_create.restype = C.c_void_p
         self.h = C.c_void_p(self.lib.nrs_cpu_lk_create(C.c_int32(win), C.c_int32(max_level), C.c_int32(max_iters), C.c_float(epsilon), C.c_float(min_eig)))
-        self.n = 0
+        self.n, self.win, self.max_level = 0, win, max_level
 
     def close(self):
         if self.h:
@@ -245,6 +245,16 @@ class LucasKanadeCpp:
                                   _p(pts, C.c_float), _p(status, C.c_int32), C.c_int32(1 if initial_flow else 0), C.c_float(min_ssim), C.byref(good),
                                   _p(ssim, C.c_float))
         return pts, status, good.value, ssim
+
+    def templates(self):
+        """the stored templates as nrs.Context.klt_get_templates lays them out: gray (n, levels, win, win), grad (n, levels, win, win, 2),
+        mean (n, levels, 2), valid (n, levels); a level that was not filled reads zeros, means of -1 and valid 0"""
+        L, w = self.max_level + 1, self.win
+        gray, grad = np.zeros((self.n, L, w, w), np.int16), np.zeros((self.n, L, w, w, 2), np.int16)
+        mean, valid = np.zeros((self.n, L, 2), np.float32), np.zeros((self.n, L), np.uint8)
+        if self.n:
+            self.lib.nrs_cpu_lk_get_templates(self.h, _p(gray, C.c_int16), _p(grad, C.c_int16), _p(mean, C.c_float), _p(valid, C.c_uint8))
+        return dict(gray=gray, grad=grad, mean=mean, valid=valid)
 
 
 def nd_plan_check(pos, last, pairs, lib=None):

@@ -7,7 +7,8 @@
 //                                           documented pyrDown / Scharr / border behaviour: PARITY UNPINNED
 // Arithmetic: fixed-point bilinear sampling (W_BITS 14, cvRound = round half to even), sequential float32 window sums in row-major
 // order with separate multiply and add (this file is compiled with contraction off for these functions), `int diff` truncation,
-// double precision norms.  Held bit for bit to oracle/lk_oracle.py on the committed golden (tests/test_oracle_cpp_track_cpu.py).
+// double precision norms.  Held bit for bit to oracle/lk_oracle.py on the committed golden (tests/test_oracle_cpp_track_cpu.py) and on
+// the case table tests/lk_cases.py (tests/test_lk_cases_cpu.py: short pyramids, dead windows, the border gates, bad numbers).
 #pragma once
 
 #define LK_NOFMA __attribute__((optimize("fp-contract=off")))
@@ -66,6 +67,14 @@ struct LkLevel {
         }
     }
 };
+
+// floor of a window origin, or false where the coordinate is not finite or its floor does not fit an int: such a position counts as
+// outside the image (oracle/lk_oracle.py _origin; tested BEFORE the float -> int conversion, which is undefined there)
+inline bool lk_origin(float px, float py, int& ix, int& iy) {
+    if (!(px >= -2147483648.0f && px < 2147483648.0f && py >= -2147483648.0f && py < 2147483648.0f)) return false;      // NaN compares false
+    ix = (int)std::floor(px); iy = (int)std::floor(py);
+    return true;
+}
 
 inline void lk_pyr_down(const vector<uint8_t>& src, int w, int h, vector<uint8_t>& out, int& ow, int& oh) {
     ow = (w + 1) / 2; oh = (h + 1) / 2;
@@ -162,8 +171,8 @@ struct LkTracker {
             const float sf = (float)(1 << level);
             for (int i = 0; i < n; ++i) {
                 const float px = pts[2 * i] / sf - half, py = pts[2 * i + 1] / sf - half;
-                const int ix = (int)std::floor(px), iy = (int)std::floor(py);
-                if (ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) continue;
+                int ix, iy;
+                if (!lk_origin(px, py, ix, iy) || ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) continue;
                 int iw[4];
                 weights(px - (float)ix, py - (float)iy, iw);
                 sample(L, ix, iy, iw, win, val.data(), d.data());
@@ -180,11 +189,11 @@ struct LkTracker {
     LK_NOFMA int track(const uint8_t* img, int w, int h, int stride, float* pts, int32_t* status, int initial_flow, float min_ssim, float* ssim_out) {
         vector<LkLevel> pyr;
         build_pyramid(img, w, h, stride, max_level, win, pyr);
-        const int npx = win * win, gap = win / 2 + 1, top = max_level;
+        // the top level is the highest one the tracked image's pyramid has; the initial guess is scaled there (oracle/lk_oracle.py track)
+        const int npx = win * win, gap = win / 2 + 1, top = std::min(max_level, (int)pyr.size() - 1);
         const float half = (float)((win - 1) * 0.5), area = (float)(win * win), flt_scale = 1.0f / (float)(1 << 20);
         vector<int> val(npx), d(2 * npx);
         for (int level = top; level >= 0; --level) {
-            if (level >= (int)pyr.size()) continue;
             const LkLevel& L = pyr[level];
             const float inv = (float)(1.0 / (double)(1 << level));
             for (int i = 0; i < n; ++i) {
@@ -195,8 +204,8 @@ struct LkTracker {
                 else { nx0 = pts[2 * i] * 2.0f; ny0 = pts[2 * i + 1] * 2.0f; }
                 pts[2 * i] = nx0; pts[2 * i + 1] = ny0;
                 const float pvx = pvx0 - half, pvy = pvy0 - half;
-                const int ipx = (int)std::floor(pvx), ipy = (int)std::floor(pvy);
-                if (ipx < -gap || ipx >= L.w - gap || ipy < -gap || ipy >= L.h - gap) { if (level == 0) status[i] = 4; continue; }
+                int ipx, ipy;
+                if (!lk_origin(pvx, pvy, ipx, ipy) || ipx < -gap || ipx >= L.w - gap || ipy < -gap || ipy >= L.h - gap) { if (level == 0) status[i] = 4; continue; }
                 if (!filled[level][i]) { if (level == 0) status[i] = 4; continue; }
                 const float mI = meanI[level][i], mI2 = meanI2[level][i];
                 const int16_t* Iw = &Iref[level][(size_t)i * npx];
@@ -204,8 +213,8 @@ struct LkTracker {
                 const float sx0 = nx0, sy0 = ny0;
                 float nx = nx0 - half, ny = ny0 - half, pdx = 0.f, pdy = 0.f;
                 for (int j = 0; j < max_iters; ++j) {
-                    const int ix = (int)std::floor(nx), iy = (int)std::floor(ny);
-                    if (ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) { if (level == 0) status[i] = 4; break; }
+                    int ix, iy;
+                    if (!lk_origin(nx, ny, ix, iy) || ix < -gap || ix >= L.w - gap || iy < -gap || iy >= L.h - gap) { if (level == 0) status[i] = 4; break; }
                     int iw[4];
                     weights(nx - (float)ix, ny - (float)iy, iw);
                     sample(L, ix, iy, iw, win, val.data(), d.data());
@@ -258,10 +267,9 @@ struct LkTracker {
         for (int i = 0; i < n; ++i) {
             if (ssim_out) ssim_out[i] = std::numeric_limits<float>::quiet_NaN();
             if (!usable(status[i])) continue;
-            if (std::isnan(pts[2 * i]) || std::isnan(pts[2 * i + 1])) { status[i] = 4; continue; }
             const float nx = pts[2 * i] - half, ny = pts[2 * i + 1] - half;
-            const int ix = (int)std::floor(nx), iy = (int)std::floor(ny);
-            if (ix < -gap || ix >= L.w - gap * 2 || iy < -gap || iy >= L.h - gap * 2) { status[i] = 4; continue; }
+            int ix, iy;
+            if (!lk_origin(nx, ny, ix, iy) || ix < -gap || ix >= L.w - gap * 2 || iy < -gap || iy >= L.h - gap * 2) { status[i] = 4; continue; }
             int iw[4];
             weights(nx - (float)ix, ny - (float)iy, iw);
             sample(L, ix, iy, iw, win, val.data(), nullptr);
