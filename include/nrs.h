@@ -172,7 +172,8 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *                 block's sweep in the 4-pivot register form), NRS_KFT_FOUR_WAVES (panel workgroups without the four helper waves), NRS_KFT_NO_RESIDUAL_TEST (M^-1 applied again after the first PCG step
  *                 instead of the step's residual tested on its own)
  *   sharding      NRS_SHARD_PACK_ALL, NRS_SHARD_FULL_VECTORS
- *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR
+ *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR, NRS_RG_MAX_CAP=<n> (a lower limit on the GetEdges
+ *                 prefix a call may ask for: the "ran off at the limit" refusals)
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
  * (what each selects: README.md "Debug switches"; the A/B tests drive every launch form through nrs_debug_set). */
 int nrs_debug_set(nrs_ctx* ctx, const char* name /* "NRS_..." */, const char* value /* NULL: unset */);
@@ -585,6 +586,29 @@ int nrs_track_deform_solve_rg(nrs_ctx* ctx, const nrs_camera* cam, nrs_rgraph* g
                               float* map_pos, int32_t n_f, const int32_t* f_map, int32_t* f_status, const float* f_uv,
                               float* f_pos, double pose_qt[7], float scale, float* deform_median, int32_t* n_lost,
                               int32_t* lost, nrs_lm_trace* trace);
+
+/* LocalDeformableBundleAdjustment (g2o_optimization.cc:880-1161) served by the same device-resident graph: nrs_dba_solve_window
+ * without the neighbour lists.  kf_pt are map-point indices = the graph's indices (the graph's capacity stands for n_points; an index
+ * beyond it is NRS_ERR_INVALID), everything else as for nrs_dba_solve_window.  On the device: the window's distinct map points are
+ * listed in ascending order, GetEdges (OPT:1029-1030) runs for them at cap_per_point entries per point (<= 0: 64) and the lists stay
+ * where it leaves them; the walks of OPT:1033-1074 (springs) and OPT:1086-1135 (dampers) read them there, a wave per landmark.  Those
+ * walks are not a2's: a neighbour the keyframe does not observe is passed over WITHOUT counting (OPT:1041-1043, 1094-1097), so no fixed
+ * prefix of a list is enough.  A walk RAN OFF when it comes to the end of a truncated prefix without having met a BAD connection and
+ * with no more than 10 regularisers counted; if any walk of the window ran off, GetEdges and the walks are redone for the whole window
+ * at twice the prefix length, up to the LIMIT: min(capacity, the candidates k_rg_get_edges can sort in one workgroup's LDS - 1024) --
+ * 3072 entries per point with 64 KB of LDS per workgroup, 7168 with 160 KB; a graph of no more points than that is served whole,
+ * whatever its lists look like.  A walk that still runs off at the
+ * limit is NRS_ERR_INVALID (the message names the map point and the limit), never a shorter window.  The result does not depend on
+ * cap_per_point: the edge lists are index for index those of nrs_dba_build_edges on the full lists, poses, points and trace are
+ * bit for bit those of nrs_dba_solve_window on them (windows below the device packer's threshold copy the device-built lists back
+ * and take the host packer).  nrs_dba_window_edges returns the resident window's lists in both cases.  A context with a communicator
+ * is refused (NRS_ERR_INVALID): sharded and embedded forms of this call do not exist.
+ * nrs_dba_window_rg_stats: out = {distinct map points, final prefix length, GetEdges rounds, walks that ran off in round 1} of the
+ * resident window this call made (NRS_ERR_STATE otherwise).  Debug switch: NRS_RG_MAX_CAP=<n> lowers the limit. */
+int nrs_dba_solve_window_rg(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* poses_qt /* in/out */, const int32_t* kf_rowptr,
+                            const int32_t* kf_pt, float* lm_xyz /* in/out */, const float* lm_uv, nrs_rgraph* g, int32_t cap_per_point,
+                            float scale, int32_t iters, nrs_lm_trace* trace);
+int nrs_dba_window_rg_stats(nrs_ctx* ctx, int64_t out[4]);
 
 /* ---- N2: embedded deformation -- "points x graph nodes" as SURVEY.md 8(d) words it ------------------------------------
  * nrs_track_deform_solve_rg with a node set: f_node[i] != 0 marks the frame landmarks (among the TRACKED_WITH_3D ones) that carry

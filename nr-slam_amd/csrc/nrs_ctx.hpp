@@ -20,6 +20,7 @@ struct DevBuf {
 
 struct Engine;       // nrs_engine.hip
 struct EmbWindow;    // nrs_engine.hpp: the lists of an embedded window built in one call
+struct RgWindow;     // nrs_engine.hpp: what nrs_dba_solve_window_rg leaves next to its resident window
 struct KltState;     // nrs_klt.hip
 struct ShiState;     // nrs_shi.hip
 struct FrontState;   // nrs_front.hip
@@ -90,6 +91,7 @@ struct nrs_ctx {
     nrs::DevBuf dba_kft;             // embedded BA window: the keyframe-block factorisation (nrs_engine_kft.hpp)
     bool kft_attr_done = false;      // ... its kernels' dynamic-LDS attributes are set on this context's device (kft_kernel_attributes)
     nrs::EmbWindow* dba_embwin = nullptr;   // lists of the resident window when nrs_dba_solve_window_embedded made it (dropped by dba_free)
+    nrs::RgWindow* dba_rgwin = nullptr;     // statistics (and host-packed lists) of the resident window when nrs_dba_solve_window_rg made it (dropped by dba_free)
     void* embwin_pin = nullptr;      // pinned host staging of the device-built lists (nrs_engine_embwin.hpp), kept for the context's lifetime
     size_t embwin_pin_cap = 0;
     nrs::DevBuf nd_skin;             // embedded mode (nrs_engine_skin.hpp): the skinned observations of the tracking engine

@@ -13,6 +13,8 @@ void dba_free(nrs_ctx* c) {
     c->dba = nullptr;
     delete c->dba_embwin;                                            // (the lists of a window nrs_dba_solve_window_embedded made)
     c->dba_embwin = nullptr;
+    delete c->dba_rgwin;                                             // (what nrs_dba_solve_window_rg left next to its window)
+    c->dba_rgwin = nullptr;
 }
 
 // constants of OPT:958-973 (float arithmetic, widened to double like g2o does)
@@ -212,21 +214,29 @@ extern "C" int nrs_dba_solve_embedded(nrs_ctx* c, const nrs_camera* cam, int32_t
 
 // LocalDeformableBundleAdjustment in ONE call, as mapping.cc:57 makes it: the edge construction of OPT:927-1137 on the device,
 // then the device-side problem construction and the solve.  Windows that do not qualify take nrs_dba_build_edges + nrs_dba_solve.
-static int window_validate(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
-                           const float* lm_xyz, const float* lm_uv, int32_t n_points, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
-                           const float* nbr_d0, const int32_t* nbr_status, std::vector<int32_t>& lm_kf) {
-    if (!cam || n_kf <= 0 || !poses_qt || !kf_rowptr || !kf_pt || !lm_xyz || !lm_uv || n_points <= 0 || !nbr_rowptr || !nbr_col || !nbr_w || !nbr_d0 || !nbr_status)
+// the keyframe side of the window (shared with the form that takes its lists from the resident graph: n_points = its capacity)
+static int window_validate_kf(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                              const float* lm_xyz, const float* lm_uv, int32_t n_points, const char* beyond, std::vector<int32_t>& lm_kf) {
+    if (!cam || n_kf <= 0 || !poses_qt || !kf_rowptr || !kf_pt || !lm_xyz || !lm_uv || n_points <= 0)
         return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window: bad argument");
     if (cam->model != NRS_CAM_PINHOLE && cam->model != NRS_CAM_KB8) return c->fail(NRS_ERR_INVALID, "unknown camera model %d", cam->model);
     const int32_t n_lm = kf_rowptr[n_kf];
     if (kf_rowptr[0] != 0 || n_lm <= 0) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window: empty window");
     for (int k = 0; k < n_kf; ++k) if (kf_rowptr[k + 1] < kf_rowptr[k]) return c->fail(NRS_ERR_INVALID, "kf_rowptr must be non-decreasing");
-    for (int32_t i = 0; i < n_lm; ++i) if (kf_pt[i] < 0 || kf_pt[i] >= n_points) return c->fail(NRS_ERR_INVALID, "map point index out of range");
+    for (int32_t i = 0; i < n_lm; ++i) if (kf_pt[i] < 0 || kf_pt[i] >= n_points) return c->fail(NRS_ERR_INVALID, beyond, kf_pt[i], n_points);
+    lm_kf.resize(n_lm);
+    for (int k = 0; k < n_kf; ++k) for (int32_t i = kf_rowptr[k]; i < kf_rowptr[k + 1]; ++i) lm_kf[i] = k;
+    return NRS_OK;
+}
+
+static int window_validate(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                           const float* lm_xyz, const float* lm_uv, int32_t n_points, const int32_t* nbr_rowptr, const int32_t* nbr_col, const float* nbr_w,
+                           const float* nbr_d0, const int32_t* nbr_status, std::vector<int32_t>& lm_kf) {
+    if (!nbr_rowptr || !nbr_col || !nbr_w || !nbr_d0 || !nbr_status) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window: bad argument");
+    NRS_TRY(window_validate_kf(c, cam, n_kf, poses_qt, kf_rowptr, kf_pt, lm_xyz, lm_uv, n_points, "map point index out of range", lm_kf));
     if (nbr_rowptr[0] != 0) return c->fail(NRS_ERR_INVALID, "nbr_rowptr must start at 0");
     for (int32_t p = 0; p < n_points; ++p) if (nbr_rowptr[p + 1] < nbr_rowptr[p]) return c->fail(NRS_ERR_INVALID, "nbr_rowptr must be non-decreasing");
     for (int32_t i = 0; i < nbr_rowptr[n_points]; ++i) if (nbr_col[i] < 0 || nbr_col[i] >= n_points) return c->fail(NRS_ERR_INVALID, "neighbour index out of range");
-    lm_kf.resize(n_lm);
-    for (int k = 0; k < n_kf; ++k) for (int32_t i = kf_rowptr[k]; i < kf_rowptr[k + 1]; ++i) lm_kf[i] = k;
     return NRS_OK;
 }
 
@@ -308,7 +318,92 @@ extern "C" int nrs_dba_window_edges(nrs_ctx* c, int32_t* n_spring, int32_t* sp_i
     if (n_spring) *n_spring = ns;
     if (n_damper) *n_damper = nd;
     if (!sp_ij && !sp_d0 && !dm_idx && !dm_w) return NRS_OK;
+    if (c->dba_rgwin && c->dba_rgwin->host_lists) {                 // nrs_dba_solve_window_rg below the device packer's threshold: the device-built lists as copied back
+        const RgWindow& r = *c->dba_rgwin;
+        if (sp_ij) memcpy(sp_ij, r.sp_ij.data(), sizeof(int32_t) * 2 * (size_t)ns);
+        if (sp_d0) memcpy(sp_d0, r.sp_d0.data(), sizeof(float) * (size_t)ns);
+        if (dm_idx) memcpy(dm_idx, r.dm_idx.data(), sizeof(int32_t) * 4 * (size_t)nd);
+        if (dm_w) memcpy(dm_w, r.dm_w.data(), sizeof(float) * (size_t)nd);
+        return NRS_OK;
+    }
     return engine_edges_to_host(c, c->dba, sp_ij, sp_d0, dm_idx, dm_w);
+}
+
+// ---- LocalDeformableBundleAdjustment served by the device-resident all-pairs graph (include/nrs.h nrs_dba_solve_window_rg): the
+// window's GetEdges calls (OPT:1029-1030) and its walks (OPT:1033-1074, 1086-1135) run on the device over the graph's own lists
+// (nrs_engine_devpack.hpp win_edges_device), then the set-up and the solve of nrs_dba_solve_window.
+constexpr int RG_WINDOW_FIRST_CAP = 64;                             // the first prefix length when the caller names none
+extern "C" int nrs_dba_solve_window_rg(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                                       float* lm_xyz, const float* lm_uv, nrs_rgraph* g, int32_t cap_per_point, float scale, int32_t iters, nrs_lm_trace* trace) {
+    if (!c) return NRS_ERR_INVALID;
+    if (!g || rg_context(g) != c) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg: the graph is null or belongs to another context");
+    if (c->comm) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg: not available with a communicator on the context (sharded windows take nrs_dba_solve_window)");
+    std::vector<int32_t> lm_kf;
+    NRS_TRY(window_validate_kf(c, cam, n_kf, poses_qt, kf_rowptr, kf_pt, lm_xyz, lm_uv, rg_capacity(g),
+                               "nrs_dba_solve_window_rg: map point index %d is beyond the graph's capacity %d", lm_kf));
+    const int32_t n_lm = kf_rowptr[n_kf];
+    dba_free(c);                                                     // whatever happens below, no earlier window stays resident
+    NRS_HIP(c, hipSetDevice(c->device));
+    std::unique_ptr<RgWindow> rw(new RgWindow());
+    DevEdges de;
+    NRS_TRY(engine_build_edges_device_rg(c, n_kf, kf_rowptr, kf_pt, lm_kf.data(), g, cap_per_point > 0 ? cap_per_point : RG_WINDOW_FIRST_CAP, &de, rw->stats));
+    EngineSpec s;
+    s.K = n_kf; s.M = n_lm;
+    std::vector<Pose> poses(n_kf);
+    for (int k = 0; k < n_kf; ++k) {
+        for (int i = 0; i < 4; ++i) poses[k].q[i] = poses_qt[7 * k + i];
+        for (int i = 0; i < 3; ++i) poses[k].t[i] = poses_qt[7 * k + 4 + i];
+        quat_normalize(poses[k].q);
+    }
+    std::vector<double> x(3 * (size_t)n_lm);
+    for (size_t i = 0; i < x.size(); ++i) x[i] = (double)lm_xyz[i];
+    std::vector<uint8_t> rflag(n_lm, RF_OBS | RF_REPROJ_ACTIVE);
+    s.poses = poses.data(); s.x = x.data(); s.lm_pose = lm_kf.data(); s.uv = lm_uv; s.rflag = rflag.data();
+    s.cam.model = cam->model;
+    for (int i = 0; i < 8; ++i) s.cam.p[i] = cam->params[i];
+    ba_constants(s, scale);
+    s.delta_pos = 0.0; s.spring_form = 0; s.shard = true;
+    s.n_sp = 1; s.n_dm = 1;                                          // (placeholders for the eligibility test: counts follow)
+    int rc = NRS_ERR_STATE;                                          // (NRS_ERR_STATE: not built on the device)
+    if (engine_device_pack_ok(c, s) && de.n_sp > 0 && de.n_dm > 0) {
+        s.n_sp = de.n_sp; s.sp_ij = de.sp_ij; s.sp_d0 = de.sp_d0;
+        s.n_dm = de.n_dm; s.dm_idx = de.dm_idx; s.dm_w = de.dm_w;
+        s.edges_on_device = true;
+        rc = engine_create(c, s, &c->arena_dba, &c->dba);
+        if (rc != NRS_OK) dba_free(c);
+        if (rc != NRS_OK && rc != NRS_ERR_STATE) return rc;          // (NRS_ERR_STATE: the window's halos exceed the device path's limits)
+    }
+    if (rc == NRS_ERR_STATE) {
+        // the host packer (windows below the device packer's threshold): the device-built lists copied back, then nrs_dba_upload --
+        // the same lists, so the same bits as nrs_dba_solve_window on the full lists
+        rw->sp_ij.resize(2 * (size_t)de.n_sp + 2); rw->sp_d0.resize((size_t)de.n_sp + 1);
+        rw->dm_idx.resize(4 * (size_t)de.n_dm + 4); rw->dm_w.resize((size_t)de.n_dm + 1);
+        NRS_HIP(c, hipStreamSynchronize(c->stream));
+        if (de.n_sp > 0) {
+            NRS_HIP(c, hipMemcpy(rw->sp_ij.data(), de.sp_ij, sizeof(int) * 2 * (size_t)de.n_sp, hipMemcpyDeviceToHost));
+            NRS_HIP(c, hipMemcpy(rw->sp_d0.data(), de.sp_d0, sizeof(float) * (size_t)de.n_sp, hipMemcpyDeviceToHost));
+        }
+        if (de.n_dm > 0) {
+            NRS_HIP(c, hipMemcpy(rw->dm_idx.data(), de.dm_idx, sizeof(int) * 4 * (size_t)de.n_dm, hipMemcpyDeviceToHost));
+            NRS_HIP(c, hipMemcpy(rw->dm_w.data(), de.dm_w, sizeof(float) * (size_t)de.n_dm, hipMemcpyDeviceToHost));
+        }
+        rw->host_lists = true;
+        NRS_TRY(nrs_dba_upload(c, cam, n_kf, poses_qt, n_lm, lm_xyz, lm_kf.data(), lm_uv, de.n_sp, rw->sp_ij.data(), rw->sp_d0.data(), de.n_dm, rw->dm_idx.data(),
+                               rw->dm_w.data(), scale));
+    }
+    c->dba_rgwin = rw.release();
+    NRS_TRY(nrs_dba_optimize(c, iters, trace));
+    std::vector<double> xyz((size_t)n_lm * 3);
+    NRS_TRY(download(c, n_kf, poses_qt, xyz.data()));
+    for (size_t i = 0; i < xyz.size(); ++i) lm_xyz[i] = (float)xyz[i];      // OPT:1158 cast<float>
+    return NRS_OK;
+}
+
+extern "C" int nrs_dba_window_rg_stats(nrs_ctx* c, int64_t out[4]) {
+    if (!c || !out) return NRS_ERR_INVALID;
+    if (!c->dba || !c->dba_rgwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_rg");
+    for (int i = 0; i < 4; ++i) out[i] = c->dba_rgwin->stats[i];
+    return NRS_OK;
 }
 
 // ---- the EMBEDDED window in one call (include/nrs.h): the lists of nrs_dba_build_edges_embedded built on the device

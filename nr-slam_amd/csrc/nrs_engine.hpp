@@ -83,6 +83,24 @@ int engine_skin_stats(const Engine* e, int64_t out[3]);            // skinned ob
 // OPT:927-1137's edge construction on the device (index for index what nrs_dba_build_edges returns); arrays live in ctx scratch
 int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
                               const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out);
+// The same construction served by the device-resident all-pairs graph (include/nrs.h nrs_dba_solve_window_rg): GetEdges of the window's
+// distinct points at a prefix length that is doubled until no walk runs off its prefix.  stats: distinct points, final prefix length,
+// GetEdges rounds, walks that ran off in round 1.  The pieces of nrs_rgraph.hip it stands on:
+struct RgDeviceLists { int n_rows, stride; const int *count, *col, *status; const float *w, *d0; };
+int rg_capacity(const nrs_rgraph* g);
+int rg_max_cap_per_point(const nrs_rgraph* g);
+nrs_ctx* rg_context(const nrs_rgraph* g);
+int rg_get_edges_device(nrs_rgraph* g, int32_t n_ids, const int32_t* d_ids, int32_t cap_per_point, RgDeviceLists* o);
+int engine_build_edges_device_rg(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, nrs_rgraph* g, int cap_per_point,
+                                 DevEdges* out, int64_t stats[4]);
+// what nrs_dba_solve_window_rg leaves next to the resident window (dropped by dba_free): its statistics and, when the window took the
+// host packer, the device-built edge lists as they were copied back (nrs_dba_window_edges returns them)
+struct RgWindow {
+    int64_t stats[4] = {0, 0, 0, 0};
+    std::vector<int> sp_ij, dm_idx;
+    std::vector<float> sp_d0, dm_w;
+    bool host_lists = false;
+};
 // embedded window in one call (nrs_engine_embwin.hpp): node copies, springs / dampers over node-copy indices, skinned observations and
 // the per-observation data gathered for both; the arrays sit in ONE blob laid out by embwin_layout (host: `host`, device-built: the
 // context's pinned staging).  A rank of a sharded window builds its share only: sk_obs whole (n_skin), the heavy skinned arrays (sk_node,

@@ -388,26 +388,47 @@ struct DpScratch {
 };
 
 // ---- edge construction of LocalDeformableBundleAdjustment on the device (OPT:927-1137; the host form is nrs_dba_build_edges,
-// csrc/nrs_host_build.cpp, whose output this reproduces index for index).  One thread per landmark l = (keyframe k, map point p):
+// csrc/nrs_host_build.cpp, whose output this reproduces index for index).  One WAVE per landmark l = (keyframe k, map point p):
 // it walks p's ordered neighbour list as the reference does (stop after more than 10 regularisers or at the first BAD
 // connection, OPT:1033-1050; a duplicate counts as a regulariser too, so the walked prefix of a point does not depend on any
-// other point).  The reference's per-keyframe hash sets (SpatialPoint / TemporalPoint, OPT:980-981) keep the FIRST of the two
-// walks that propose a pair: the pair {p, o} is a duplicate here iff o comes earlier in the keyframe and o's own walk reaches p.
+// other point), 64 contiguous entries at a time as k_rg_walk does: the regularisers before an entry are a prefix count over the
+// lanes, the entry at which the sequential loop breaks is the first lane that sees it.  The reference's per-keyframe hash sets
+// (SpatialPoint / TemporalPoint, OPT:980-981) keep the FIRST of the two walks that propose a pair: the pair {p, o} is a duplicate
+// here iff o comes earlier in the keyframe and o's own walk reaches p (each lane follows the walk of its own o).
+// The lists come in one of two layouts (WinLists): the caller's CSR (nrs_dba_solve_window), or the fixed-stride prefixes
+// k_rg_get_edges leaves on the device, found through a point -> list-row table (nrs_dba_solve_window_rg).  A prefix may be CUT
+// (count > stride): a walk RAN OFF when it comes to the end of a cut prefix without having met a BAD entry and with no more than 10
+// regularisers counted -- the entries behind the prefix could still add to it.  (With more than 10 counted, the next entry would
+// end the walk before it had any effect, whatever it is; a list that is complete never runs off.)
+struct WinLists {
+    const int* rowptr;                                               // CSR: the list of p is [rowptr[p], rowptr[p + 1]); null: fixed stride
+    const int *row, *count;                                          // fixed stride: row[p] = list row of p (-1: not in the window), count[row] = FULL length
+    int stride;
+    const int *col, *status;
+    const float *w, *d0;
+    __device__ void range(int p, int64_t& lo, int& n, bool& cut) const {
+        if (rowptr) { lo = rowptr[p]; n = rowptr[p + 1] - rowptr[p]; cut = false; return; }
+        const int r = row[p], c = count[r];
+        lo = (int64_t)r * stride; n = min(c, stride); cut = c > stride;
+    }
+};
 struct WinDev {
     int n_kf, n_points;
     const int *kf_rowptr, *kf_pt, *lm_k;                             // lm_k[l] = keyframe of landmark l
-    const int *nbr_rowptr, *nbr_col, *nbr_status;
-    const float *nbr_w, *nbr_d0;
+    WinLists L;
     const int* cur;                                                  // n_kf x n_points: landmark of (k, p) or -1
 };
 
+// (a cut prefix that ends before p is reached: false -- o's own walk has then run off and is flagged by the count pass)
 __device__ inline bool win_walk_reaches(const WinDev& W, int k, int o, int p, bool damper) {
     const int* cur = W.cur + (size_t)k * W.n_points;
     const int* nxt = damper ? W.cur + (size_t)(k + 1) * W.n_points : nullptr;
+    int64_t lo; int n; bool cut;
+    W.L.range(o, lo, n, cut);
     int n_reg = 0;
-    for (int e = W.nbr_rowptr[o]; e < W.nbr_rowptr[o + 1]; ++e) {
-        if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) return false;
-        const int x = W.nbr_col[e];
+    for (int64_t e = lo; e < lo + n; ++e) {
+        if (n_reg > 10 || W.L.status[e] == NRS_GRAPH_BAD) return false;
+        const int x = W.L.col[e];
         if (cur[x] < 0 || (damper && nxt[x] < 0)) continue;
         if (x == p) return true;
         ++n_reg;
@@ -415,66 +436,102 @@ __device__ inline bool win_walk_reaches(const WinDev& W, int k, int o, int p, bo
     return false;
 }
 
-// EMIT = false: counts per landmark; true: writes at the scanned offsets
-template <bool EMIT>
-__global__ void k_win_edges(WinDev W, int n_lm, int* cnt_s, int* cnt_d, const int* __restrict__ off_s, const int* __restrict__ off_d,
-                            int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= n_lm) return;
-    const int k = W.lm_k[l], p = W.kf_pt[l];
+// one walk of landmark l by its wave: DAMPER = false the springs (OPT:1033-1074), true the dampers with the next keyframe
+// (OPT:1086-1135).  Returns the number of edges it makes (wave-uniform); *ran_off: see above.  EMIT writes them from `off` on.
+template <bool EMIT, bool DAMPER>
+__device__ inline int win_walk(const WinDev& W, int l, int k, int p, int lane, int off, int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w, bool* ran_off) {
     const int* cur = W.cur + (size_t)k * W.n_points;
-    const int lo = W.nbr_rowptr[p], hi = W.nbr_rowptr[p + 1];
-    int ns = 0, nd = 0, n_reg = 0;
-    for (int e = lo; e < hi; ++e) {                                  // springs (OPT:1033-1074)
-        if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
-        const int o = W.nbr_col[e];
-        if (cur[o] < 0) continue;
-        ++n_reg;
-        if (cur[o] < l && win_walk_reaches(W, k, o, p, false)) continue;        // inserted by o's walk already
-        if (EMIT) { const int q = off_s[l] + ns; sp_ij[2 * (size_t)q] = l; sp_ij[2 * (size_t)q + 1] = cur[o]; sp_d0[q] = W.nbr_d0[e]; }
-        ++ns;
-    }
-    if (k + 1 < W.n_kf) {                                            // dampers with the next keyframe (OPT:1076-1136)
-        const int* nxt = W.cur + (size_t)(k + 1) * W.n_points;
-        if (nxt[p] >= 0) {
-            n_reg = 0;
-            for (int e = lo; e < hi; ++e) {
-                if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
-                const int o = W.nbr_col[e];
-                if (cur[o] < 0 || nxt[o] < 0) continue;
-                ++n_reg;
-                if (cur[o] < l && win_walk_reaches(W, k, o, p, true)) continue;
-                if (EMIT) {
-                    const int q = off_d[l] + nd;
-                    dm_idx[4 * (size_t)q] = l; dm_idx[4 * (size_t)q + 1] = cur[o]; dm_idx[4 * (size_t)q + 2] = nxt[p]; dm_idx[4 * (size_t)q + 3] = nxt[o];
-                    dm_w[q] = W.nbr_w[e];
-                }
-                ++nd;
-            }
+    const int* nxt = DAMPER ? W.cur + (size_t)(k + 1) * W.n_points : nullptr;
+    int64_t lo; int n; bool cut;
+    W.L.range(p, lo, n, cut);
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    int n_reg = 0, n_out = 0;
+    bool broke = false;
+    for (int ch = 0; ch < n && !broke; ch += 64) {
+        const int a = ch + lane;
+        const bool valid = a < n;
+        const int64_t e = lo + a;
+        const int o = valid ? W.L.col[e] : 0;
+        const bool bad = valid && W.L.status[e] == NRS_GRAPH_BAD;
+        const bool pres = valid && cur[o] >= 0 && (!DAMPER || nxt[o] >= 0);      // the other end is observed (by both keyframes)
+        const unsigned long long presm = __ballot(pres);
+        const int before = n_reg + __popcll(presm & below);         // regularisers counted when the loop comes to this entry
+        const unsigned long long brkm = __ballot(valid && (bad || before > 10));
+        const int fb = brkm ? __ffsll((long long)brkm) - 1 : 64;    // the loop breaks at this lane's entry
+        bool make = pres && lane < fb;
+        if (make && cur[o] < l && win_walk_reaches(W, k, o, p, DAMPER)) make = false;   // inserted by o's walk already
+        const unsigned long long makem = __ballot(make);
+        if (EMIT && make) {
+            const size_t q = (size_t)off + n_out + __popcll(makem & below);
+            if (!DAMPER) { sp_ij[2 * q] = l; sp_ij[2 * q + 1] = cur[o]; sp_d0[q] = W.L.d0[e]; }
+            else { dm_idx[4 * q] = l; dm_idx[4 * q + 1] = cur[o]; dm_idx[4 * q + 2] = nxt[p]; dm_idx[4 * q + 3] = nxt[o]; dm_w[q] = W.L.w[e]; }
         }
+        n_out += __popcll(makem);
+        n_reg += __popcll(fb < 64 ? presm & ((1ull << fb) - 1ull) : presm);
+        broke = fb < 64;
     }
-    if (!EMIT) { cnt_s[l] = ns; cnt_d[l] = nd; }
+    *ran_off = cut && !broke && n_reg <= 10;
+    return n_out;
+}
+
+// EMIT = false: counts per landmark, and in flag[0] the walks that ran off, in flag[1] the smallest map point one of them started
+// from (integer atomics of the count pass only; initialised to 0 / INT_MAX); true: writes at the scanned offsets
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_win_edges(WinDev W, int n_lm, int* cnt_s, int* cnt_d, const int* __restrict__ off_s, const int* __restrict__ off_d,
+                                                   int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w, int* flag) {
+    const int lane = threadIdx.x & 63, l = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (l >= n_lm) return;                                           // (wave-uniform)
+    const int k = W.lm_k[l], p = W.kf_pt[l];
+    bool off_end = false;
+    int n_ran = 0;
+    const int ns = win_walk<EMIT, false>(W, l, k, p, lane, EMIT ? off_s[l] : 0, sp_ij, sp_d0, dm_idx, dm_w, &off_end);
+    n_ran += off_end;
+    int nd = 0;
+    if (k + 1 < W.n_kf && W.cur[(size_t)(k + 1) * W.n_points + p] >= 0) {
+        nd = win_walk<EMIT, true>(W, l, k, p, lane, EMIT ? off_d[l] : 0, sp_ij, sp_d0, dm_idx, dm_w, &off_end);
+        n_ran += off_end;
+    }
+    if (!EMIT && lane == 0) {
+        cnt_s[l] = ns; cnt_d[l] = nd;
+        if (n_ran) { atomicAdd(&flag[0], n_ran); atomicMin(&flag[1], p); }
+    }
 }
 __global__ void k_win_cur(int n_lm, const int* __restrict__ lm_k, const int* __restrict__ kf_pt, int n_points, int* cur) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l < n_lm) atomicMax(&cur[(size_t)lm_k[l] * n_points + kf_pt[l]], l);   // (a map point listed twice in a keyframe: the last entry wins, as on the host)
 }
+// the window's distinct map points: mark[p] = 1 where a landmark observes p; after the scan, ids[] ascending and the point -> row table
+__global__ void k_win_mark(int n_lm, const int* __restrict__ kf_pt, int* mark) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < n_lm) mark[kf_pt[l]] = 1;
+}
+__global__ void k_win_rows(int n_points, const int* __restrict__ mark, const int* __restrict__ pos, int* ids, int* row) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_points) return;
+    row[p] = mark[p] ? pos[p] : -1;
+    if (mark[p]) ids[pos[p]] = p;
+}
 
 // Builds the edge lists of a window on the device; the arrays live in the context's third scratch buffer until the next call.
-int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
-                              const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out) {
-    const int n_lm = kf_rowptr[n_kf], nnz = nbr_rowptr[n_points];
+// g = null: the caller's CSR lists (nbr_*, n_points of them).  g: the resident graph serves them (n_points = its capacity, nbr_* unused),
+// first at `cap` entries per point, then at twice as many for as long as a walk runs off (rg_max_cap_per_point at the most).
+static int win_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
+                            const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, nrs_rgraph* g, int cap, int64_t* stats, DevEdges* out) {
+    const int n_lm = kf_rowptr[n_kf], nnz = g ? 0 : nbr_rowptr[n_points];
     hipStream_t st = c->stream;
     size_t tb = 0;
-    (void)rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, (size_t)n_lm + 1, rocprim::plus<int>(), st);
-    int *d_rowptr, *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_cs, *d_cd, *d_os, *d_od;
+    (void)rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, (size_t)std::max(n_lm, g ? n_points : 0) + 1, rocprim::plus<int>(), st);
+    int *d_rowptr, *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_cs, *d_cd, *d_os, *d_od, *d_mark, *d_pos, *d_ids, *d_row, *d_flag;
     float *d_w, *d_d0;
     void* tmp;
     auto layout = [&](DpScratch& W) {
         d_rowptr = W.get<int>(n_kf + 1); d_pt = W.get<int>(n_lm); d_k = W.get<int>(n_lm);
-        d_nrp = W.get<int>(n_points + 1); d_col = W.get<int>(nnz); d_st = W.get<int>(nnz); d_w = W.get<float>(nnz); d_d0 = W.get<float>(nnz);
+        d_nrp = W.get<int>(g ? 0 : n_points + 1); d_col = W.get<int>(nnz); d_st = W.get<int>(nnz); d_w = W.get<float>(nnz); d_d0 = W.get<float>(nnz);
         d_cur = W.get<int>((size_t)n_kf * n_points);
         d_cs = W.get<int>((size_t)n_lm + 1); d_cd = W.get<int>((size_t)n_lm + 1); d_os = W.get<int>((size_t)n_lm + 1); d_od = W.get<int>((size_t)n_lm + 1);
+        d_mark = W.get<int>(g ? (size_t)n_points + 1 : 0); d_pos = W.get<int>(g ? (size_t)n_points + 1 : 0);
+        d_ids = W.get<int>(g ? n_points : 0); d_row = W.get<int>(g ? n_points : 0);
+        d_flag = W.get<int>(2);
         tmp = W.get<char>(tb + 256);
     };
     DpScratch dry{nullptr, 0, 0};
@@ -485,23 +542,59 @@ int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const 
     NRS_HIP(c, hipMemcpyAsync(d_rowptr, kf_rowptr, sizeof(int) * (n_kf + 1), hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemcpyAsync(d_pt, kf_pt, sizeof(int) * (size_t)n_lm, hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemcpyAsync(d_k, lm_kf, sizeof(int) * (size_t)n_lm, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_nrp, nbr_rowptr, sizeof(int) * ((size_t)n_points + 1), hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_col, nbr_col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_st, nbr_status, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_w, nbr_w, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_d0, nbr_d0, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    if (!g) {
+        NRS_HIP(c, hipMemcpyAsync(d_nrp, nbr_rowptr, sizeof(int) * ((size_t)n_points + 1), hipMemcpyHostToDevice, st));
+        NRS_HIP(c, hipMemcpyAsync(d_col, nbr_col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        NRS_HIP(c, hipMemcpyAsync(d_st, nbr_status, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        NRS_HIP(c, hipMemcpyAsync(d_w, nbr_w, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        NRS_HIP(c, hipMemcpyAsync(d_d0, nbr_d0, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    }
     NRS_HIP(c, hipMemsetAsync(d_cur, 0xFF, sizeof(int) * (size_t)n_kf * n_points, st));
     NRS_HIP(c, hipMemsetAsync(d_cs + n_lm, 0, sizeof(int), st));
     NRS_HIP(c, hipMemsetAsync(d_cd + n_lm, 0, sizeof(int), st));
-    const dim3 g((unsigned)((n_lm + 255) / 256)), b(256);
-    hipLaunchKernelGGL(k_win_cur, g, b, 0, st, n_lm, d_k, d_pt, n_points, d_cur);
-    WinDev wd{n_kf, n_points, d_rowptr, d_pt, d_k, d_nrp, d_col, d_st, d_w, d_d0, d_cur};
-    hipLaunchKernelGGL((k_win_edges<false>), g, b, 0, st, wd, n_lm, d_cs, d_cd, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr);
+    const dim3 g1((unsigned)((n_lm + 255) / 256)), gw((unsigned)((n_lm + 3) / 4)), b(256);   // a thread / a wave per landmark
+    hipLaunchKernelGGL(k_win_cur, g1, b, 0, st, n_lm, d_k, d_pt, n_points, d_cur);
+    int n_ids = 0;
+    if (g) {                                                        // the distinct map points, ascending, and the point -> list-row table
+        NRS_HIP(c, hipMemsetAsync(d_mark, 0, sizeof(int) * ((size_t)n_points + 1), st));
+        hipLaunchKernelGGL(k_win_mark, g1, b, 0, st, n_lm, d_pt, d_mark);
+        size_t t1 = tb + 256;
+        NRS_HIP(c, rocprim::exclusive_scan(tmp, t1, d_mark, d_pos, 0, (size_t)n_points + 1, rocprim::plus<int>(), st));
+        hipLaunchKernelGGL(k_win_rows, dim3((unsigned)((n_points + 255) / 256)), b, 0, st, n_points, d_mark, d_pos, d_ids, d_row);
+        NRS_HIP(c, hipGetLastError());
+        NRS_HIP(c, hipMemcpyAsync(&n_ids, d_pos + n_points, sizeof(int), hipMemcpyDeviceToHost, st));
+        NRS_HIP(c, hipStreamSynchronize(st));
+        if (n_ids <= 0 || n_ids > n_points) return c->fail(NRS_ERR_STATE, "nrs_dba_solve_window_rg: %d distinct map points", n_ids);
+    }
+    const int cap_max = g ? rg_max_cap_per_point(g) : 0;
+    cap = std::min(cap, cap_max);
+    WinDev wd{n_kf, n_points, d_rowptr, d_pt, d_k, WinLists{d_nrp, nullptr, nullptr, 0, d_col, d_st, d_w, d_d0}, d_cur};
+    int tot[2] = {0, 0}, rounds = 0, ran_first = 0;
+    for (;;) {                                                      // (the CSR form: once)
+        if (g) {
+            RgDeviceLists rl;
+            NRS_TRY(rg_get_edges_device(g, n_ids, d_ids, cap, &rl));
+            wd.L = WinLists{nullptr, d_row, rl.count, rl.stride, rl.col, rl.status, rl.w, rl.d0};
+        }
+        ++rounds;
+        const int flag0[2] = {0, 0x7FFFFFFF};
+        NRS_HIP(c, hipMemcpyAsync(d_flag, flag0, sizeof(flag0), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL((k_win_edges<false>), gw, b, 0, st, wd, n_lm, d_cs, d_cd, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, d_flag);
+        NRS_HIP(c, hipGetLastError());
+        int flag[2] = {0, 0};
+        NRS_HIP(c, hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st));     // the round's one flag read
+        NRS_HIP(c, hipStreamSynchronize(st));
+        if (flag[0] == 0) break;
+        if (rounds == 1) ran_first = flag[0];
+        if (cap >= cap_max)
+            return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg: the neighbour walk of map point %d ran off its list at the limit of %d entries per point", flag[1], cap_max);
+        cap = std::min(cap_max, 2 * cap);
+    }
+    if (stats) { stats[0] = n_ids; stats[1] = cap; stats[2] = rounds; stats[3] = ran_first; }
     size_t t2 = tb + 256;
     NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_lm + 1, rocprim::plus<int>(), st));
     t2 = tb + 256;
     NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cd, d_od, 0, (size_t)n_lm + 1, rocprim::plus<int>(), st));
-    int tot[2] = {0, 0};
     NRS_HIP(c, hipMemcpyAsync(&tot[0], d_os + n_lm, sizeof(int), hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipMemcpyAsync(&tot[1], d_od + n_lm, sizeof(int), hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipStreamSynchronize(st));
@@ -510,11 +603,19 @@ int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const 
     DpScratch W4{c->pack_ws4.as<char>(), 0, c->pack_ws4.cap};
     int* sp_ij = W4.get<int>(2 * (size_t)tot[0]); float* sp_d0 = W4.get<float>(tot[0]);
     int* dm_idx = W4.get<int>(4 * (size_t)tot[1]); float* dm_w = W4.get<float>(tot[1]);
-    hipLaunchKernelGGL((k_win_edges<true>), g, b, 0, st, wd, n_lm, (int*)nullptr, (int*)nullptr, d_os, d_od, sp_ij, sp_d0, dm_idx, dm_w);
+    hipLaunchKernelGGL((k_win_edges<true>), gw, b, 0, st, wd, n_lm, (int*)nullptr, (int*)nullptr, d_os, d_od, sp_ij, sp_d0, dm_idx, dm_w, (int*)nullptr);
     NRS_HIP(c, hipGetLastError());
     out->n_sp = tot[0]; out->n_dm = tot[1];
     out->sp_ij = sp_ij; out->sp_d0 = sp_d0; out->dm_idx = dm_idx; out->dm_w = dm_w;
     return NRS_OK;
+}
+int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, int n_points, const int* nbr_rowptr,
+                              const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out) {
+    return win_edges_device(c, n_kf, kf_rowptr, kf_pt, lm_kf, n_points, nbr_rowptr, nbr_col, nbr_w, nbr_d0, nbr_status, nullptr, 0, nullptr, out);
+}
+int engine_build_edges_device_rg(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, nrs_rgraph* g, int cap_per_point,
+                                 DevEdges* out, int64_t stats[4]) {
+    return win_edges_device(c, n_kf, kf_rowptr, kf_pt, lm_kf, rg_capacity(g), nullptr, nullptr, nullptr, nullptr, nullptr, g, cap_per_point, stats, out);
 }
 
 static bool devpack_eligible(nrs_ctx* c, const EngineSpec& s, int n_pad_rows) {

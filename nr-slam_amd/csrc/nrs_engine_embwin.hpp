@@ -111,7 +111,7 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
     if (i >= n_obs) return;
     const int k = W.lm_k[i], p = W.kf_pt[i];
     const int* cur = W.cur + (size_t)k * W.n_points;
-    const int lo = W.nbr_rowptr[p], hi = W.nbr_rowptr[p + 1];
+    const int lo = W.L.rowptr[p], hi = W.L.rowptr[p + 1];
     if (!flag[i]) {                                                  // a skinned observation: its walk accepts node copies
         if (EMIT && (i < i_lo || i >= i_hi)) {                       // (another rank's: its place in sk_obs, which the count pass decided)
             if (off_k[i + 1] != off_k[i]) sk_obs[off_k[i]] = i;
@@ -120,9 +120,9 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
         int n_reg = 0;
         double tot = 0.0;
         for (int e = lo; e < hi; ++e) {
-            if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
-            if (cur[W.nbr_col[e]] < 0) continue;
-            tot += (double)W.nbr_w[e];                               // (walk order, from 0.0: the host's sum)
+            if (n_reg > 10 || W.L.status[e] == NRS_GRAPH_BAD) break;
+            if (cur[W.L.col[e]] < 0) continue;
+            tot += (double)W.L.w[e];                               // (walk order, from 0.0: the host's sum)
             ++n_reg;
         }
         if (!EMIT) { cnt_s[i] = 0; cnt_d[i] = 0; cnt_k[i] = n_reg > 0 ? 1 : 0; return; }
@@ -131,10 +131,10 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
         const size_t q = (size_t)(off_k[i] - sk_lo);
         int j = 0;
         for (int e = lo; e < hi && j < n_reg; ++e) {                 // the same walk again: its first n_reg accepted entries
-            const int o = W.nbr_col[e];
+            const int o = W.L.col[e];
             if (cur[o] < 0) continue;
             sk_node[11 * q + j] = cur[o];
-            sk_omega[11 * q + j] = (double)W.nbr_w[e] / tot;
+            sk_omega[11 * q + j] = (double)W.L.w[e] / tot;
             ++j;
         }
         for (; j < 11; ++j) { sk_node[11 * q + j] = -1; sk_omega[11 * q + j] = 0.0; }
@@ -144,12 +144,12 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
     int ns = 0, nd = 0, n_reg = 0;
     if (EMIT) lm_obs[l] = i;
     for (int e = lo; e < hi; ++e) {                                  // springs between node copies (OPT:1033-1074)
-        if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
-        const int o = W.nbr_col[e];
+        if (n_reg > 10 || W.L.status[e] == NRS_GRAPH_BAD) break;
+        const int o = W.L.col[e];
         if (cur[o] < 0) continue;
         ++n_reg;
         if (cur[o] < l && win_walk_reaches(W, k, o, p, false)) continue;        // inserted by o's walk already
-        if (EMIT) { const size_t q = (size_t)(off_s[i] + ns); sp_ij[2 * q] = l; sp_ij[2 * q + 1] = cur[o]; sp_d0[q] = W.nbr_d0[e]; }
+        if (EMIT) { const size_t q = (size_t)(off_s[i] + ns); sp_ij[2 * q] = l; sp_ij[2 * q + 1] = cur[o]; sp_d0[q] = W.L.d0[e]; }
         ++ns;
     }
     if (k + 1 < W.n_kf) {                                            // dampers with the next keyframe (OPT:1076-1136)
@@ -157,15 +157,15 @@ __global__ void k_ew_walk(WinDev W, int n_obs, const int* __restrict__ flag, con
         if (nxt[p] >= 0) {
             n_reg = 0;
             for (int e = lo; e < hi; ++e) {
-                if (n_reg > 10 || W.nbr_status[e] == NRS_GRAPH_BAD) break;
-                const int o = W.nbr_col[e];
+                if (n_reg > 10 || W.L.status[e] == NRS_GRAPH_BAD) break;
+                const int o = W.L.col[e];
                 if (cur[o] < 0 || nxt[o] < 0) continue;
                 ++n_reg;
                 if (cur[o] < l && win_walk_reaches(W, k, o, p, true)) continue;
                 if (EMIT) {
                     const size_t q = (size_t)(off_d[i] + nd);
                     dm_idx[4 * q] = l; dm_idx[4 * q + 1] = cur[o]; dm_idx[4 * q + 2] = nxt[p]; dm_idx[4 * q + 3] = nxt[o];
-                    dm_w[q] = W.nbr_w[e];
+                    dm_w[q] = W.L.w[e];
                 }
                 ++nd;
             }
@@ -251,7 +251,7 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     hipLaunchKernelGGL(k_ew_cur, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur);
     hipLaunchKernelGGL(k_ew_check, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur, d_tot);
     // ---- count pass, scans
-    WinDev wd{n_kf, n_points, nullptr, d_pt, d_k, d_nrp, d_col, d_st, d_w, d_d0, d_cur};
+    WinDev wd{n_kf, n_points, nullptr, d_pt, d_k, WinLists{d_nrp, nullptr, nullptr, 0, d_col, d_st, d_w, d_d0}, d_cur};
     hipLaunchKernelGGL((k_ew_walk<false>), g, b, 0, st, wd, n_obs, d_flag, d_lm, d_cs, d_cd, d_ck, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
                        (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0, n_obs, 0);
     t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));

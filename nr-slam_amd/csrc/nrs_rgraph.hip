@@ -39,6 +39,8 @@ struct nrs_rgraph {
 
 namespace nrs {
 
+struct RgDeviceLists { int n_rows, stride; const int *count, *col, *status; const float *w, *d0; };   // (declared in nrs_engine.hpp as well)
+
 constexpr uint8_t RG_NONE = 0xFF;
 
 // InterpolationWeight (utilities/geometry_toolbox.cc:26-28): float argument, exp evaluated in double and rounded
@@ -458,7 +460,9 @@ int rg_max_cap_per_point(const nrs_rgraph* g) {
     (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, g->c->device);
     size_t cand_max = 512;
     while (sizeof(unsigned long long) * (cand_max << 1) + 4096 + 512 <= (size_t)lds_max) cand_max <<= 1;
-    return std::min(g->cap, (int)cand_max - RG_SLACK);
+    int lim = std::min(g->cap, (int)cand_max - RG_SLACK);
+    if (const char* v = g->c->env("NRS_RG_MAX_CAP")) lim = std::max(1, std::min(lim, atoi(v)));   // (a lower limit, so that the tests reach the callers' "ran off at the limit" refusal)
+    return lim;
 }
 
 // ---- a2's neighbour walk on the device (OPT:252-279 as nrs_track.hip's host loop restates it): optimised point idx (rows of the last
@@ -584,10 +588,12 @@ int rg_walk(nrs_rgraph* g, int n_map, const int* code, const uint8_t* is_node, i
     return NRS_OK;
 }
 
-int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, const int** count, const int** col,
-                        const int** status, const float** w, const float** d0, const uint8_t* pass_over, bool lists_to_host) {   // lists_to_host = false: the lists stay on the device (rg_walk reads them there); only the counts come back
+// d_ids: the ids are on the device already (n_ids ints, each in [0, capacity): the caller's kernels made them) and `ids` is not read
+static int rg_get_edges_impl(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, const int32_t* d_ids, int32_t cap_per_point, const int** count, const int** col,
+                             const int** status, const float** w, const float** d0, const uint8_t* pass_over, bool lists_to_host) {   // lists_to_host = false: the lists stay on the device (rg_walk reads them there); only the counts come back
     nrs_ctx* c = g->c;
-    NRS_TRY(rg_check_ids(g, n_ids, ids, "GetEdges"));               // (also the a2 driver's entry: ids index the dense state)
+    if (d_ids) { if (n_ids <= 0 || n_ids > g->cap) return c->fail(NRS_ERR_INVALID, "GetEdges: %d device-side ids for %d points", n_ids, g->cap); }
+    else NRS_TRY(rg_check_ids(g, n_ids, ids, "GetEdges"));          // (also the a2 driver's entry: ids index the dense state)
     if (cap_per_point <= 0) return c->fail(NRS_ERR_INVALID, "GetEdges: cap_per_point must be positive");
     NRS_HIP(c, hipSetDevice(c->device));
     // the sort buffer of a row lives in LDS: 8 bytes per staged candidate (a power of two of them) + 4 KB of histogram
@@ -616,7 +622,7 @@ int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_
         if (hipHostMalloc((void**)&g->pin, want, hipHostMallocDefault) != hipSuccess) return c->fail(NRS_ERR_ALLOC, "nrs_rgraph_get_edges: %zu bytes of pinned host memory", want);
         g->pin_cap = want;
     }
-    NRS_HIP(c, hipMemcpyAsync(g->ids_a.p, ids, sizeof(int) * (size_t)n_ids, hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(g->ids_a.p, d_ids ? d_ids : ids, sizeof(int) * (size_t)n_ids, d_ids ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     if (pass_over) {                                               // (one byte per point of the dense state)
         NRS_TRY(c->ensure(g->skip, (size_t)g->cap));
         NRS_HIP(c, hipMemcpyAsync(g->skip.p, pass_over, (size_t)g->cap, hipMemcpyHostToDevice, c->stream));
@@ -668,6 +674,27 @@ int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_
     *d0 = reinterpret_cast<const float*>(h + n_ids + 3 * no);
     return NRS_OK;
 }
+int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, const int** count, const int** col,
+                        const int** status, const float** w, const float** d0, const uint8_t* pass_over, bool lists_to_host) {
+    return rg_get_edges_impl(g, n_ids, ids, nullptr, cap_per_point, count, col, status, w, d0, pass_over, lists_to_host);
+}
+// GetEdges of ids a kernel of the caller listed, the lists left on the device in k_rg_get_edges' layout: o->count[row] = the FULL
+// length of the row's list, of which the first min(count, stride) entries stand at [row * stride, ..) of col / status / w / d0
+// (the BA window's walk reads them there, nrs_engine_devpack.hpp).  Valid until the graph's next GetEdges.
+int rg_get_edges_device(nrs_rgraph* g, int32_t n_ids, const int32_t* d_ids, int32_t cap_per_point, RgDeviceLists* o) {
+    const int *h_cnt, *h_col, *h_st;
+    const float *h_w, *h_d0;
+    NRS_TRY(rg_get_edges_impl(g, n_ids, nullptr, d_ids, cap_per_point, &h_cnt, &h_col, &h_st, &h_w, &h_d0, nullptr, false));
+    const size_t no = (size_t)n_ids * cap_per_point;
+    o->n_rows = n_ids; o->stride = cap_per_point;
+    o->count = g->out_i.as<int>();
+    o->col = o->count + n_ids;
+    o->status = o->col + no;
+    o->w = reinterpret_cast<const float*>(o->status + no);
+    o->d0 = o->w + no;
+    return NRS_OK;
+}
+nrs_ctx* rg_context(const nrs_rgraph* g) { return g->c; }
 }  // namespace nrs
 
 extern "C" int nrs_rgraph_get_edges(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, int32_t* count,

@@ -30,7 +30,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_comm_unique_id", "nrs_comm_init_rccl", "nrs_comm_rank", "nrs_shard_plan",
            "nrs_local_group_create", "nrs_local_group_destroy", "nrs_comm_init_local",
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
-           "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg",
+           "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg", "nrs_dba_solve_window_rg", "nrs_dba_window_rg_stats",
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
            "nrs_init_options_init", "nrs_init_essential",
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame"]
@@ -953,6 +953,34 @@ class Context:
                                                 _p(w, C.c_float), _p(d0, C.c_float), _p(st, C.c_int32), C.c_float(scale), C.c_int32(iters),
                                                 C.byref(trace.c) if trace else None))
         return pq, xyz
+
+    def dba_solve_window_rg(self, cam, poses_qt, kf_points, lm_xyz, lm_uv, rg, scale, iters=5, trace=None, cap_per_point=0):
+        """LocalDeformableBundleAdjustment served by the device-resident graph rg (include/nrs.h nrs_dba_solve_window_rg): kf_points hold
+        map-point indices = the graph's; cap_per_point = the first GetEdges prefix (<= 0: the library's default), doubled while a walk runs off"""
+        n_kf = len(kf_points)
+        kf_rowptr = np.zeros(n_kf + 1, np.int32)
+        kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
+        kf_pt = _i32(np.concatenate(kf_points))
+        pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
+        xyz = np.array(lm_xyz, np.float32).reshape(-1, 3).copy()
+        uv = _f32(lm_uv).reshape(-1, 2)
+        assert len(pq) == n_kf and len(xyz) == len(kf_pt) == len(uv)
+        self._chk(self.lib.nrs_dba_solve_window_rg(self.h, C.byref(cam), C.c_int32(n_kf), _p(pq, C.c_double), _p(kf_rowptr, C.c_int32), _p(kf_pt, C.c_int32),
+                                                   _p(xyz, C.c_float), _p(uv, C.c_float), rg.h, C.c_int32(cap_per_point), C.c_float(scale), C.c_int32(iters),
+                                                   C.byref(trace.c) if trace else None))
+        return pq, xyz
+
+    def dba_window_rg_stats(self):
+        """dict(n_points, cap, rounds, ran_off_first) of the resident window dba_solve_window_rg made (nrs_dba_window_rg_stats)"""
+        out = (C.c_int64 * 4)()
+        self._chk(self.lib.nrs_dba_window_rg_stats(self.h, out))
+        return dict(n_points=int(out[0]), cap=int(out[1]), rounds=int(out[2]), ran_off_first=int(out[3]))
+
+    def dba_window_edge_counts(self):
+        """(springs, dampers) of the resident window"""
+        ns, nd = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.nrs_dba_window_edges(self.h, C.byref(ns), None, None, C.byref(nd), None, None))
+        return ns.value, nd.value
 
     def dba_window_edges(self):
         """edge lists of the resident window as the device built them (None if they were built on the host)"""

@@ -11,8 +11,10 @@ as TRACKED observations without a map point and are followed by LK from then on.
 `FrameLoop.from_initialization` (tracking.cc:136-214).  With mapping=True the loop also runs the FrameMapping branch of Mapping::DoMapping
 (mapping.cc:36-63) after every tracked frame -- the temporal buffer's snapshot (temporal_buffer.cc:28-56), Mapping::LandmarkTriangulation
 in one backend call, AddGeometryToKeypoint, graph growth -- and Tracking::UpdateTriangulatedPoints (tracking.cc:508-521) at the start of
-the next one, so those features become map points.  Not reproduced: BA on keyframes (KeyFrameMapping and UpdateTrackingFrameFromKeyFrame:
-on the frames where the reference runs them the loop logs that it skipped), visualisation.
+the next one, so those features become map points.  With keyframe_ba=True (on top of mapping=True) the other branch runs as well: the loop
+keeps the map's keyframes and its unmapped queue (map.cc:37-72), runs Mapping::KeyFrameMapping = LocalDeformableBundleAdjustment on the
+last five keyframes in one backend call (`dba_window`) and Mapping::UpdateTrackingFrameFromKeyFrame (mapping.cc:44-58, 266-270); without
+it the loop logs on those frames that it skipped the step.  Not reproduced: visualisation.
 
 Poses are Sophus::SE3f in the reference: unit quaternion + translation in float32, and so is the
 motion-model algebra here (`se3f_*`)."""
@@ -218,6 +220,15 @@ class GpuBackend:
     def map_frame(self, tb, deform_mag, rad_per_pixel, rigidity_th=0.004, min_track=5):
         return self.ctx.map_frame(self.cam, tb, deform_mag, rad_per_pixel, rigidity_th, min_track, -1)
 
+    # ---- keyframe mapping: LocalDeformableBundleAdjustment on the resident graph (include/nrs.h nrs_dba_solve_window_rg)
+    def dba_window(self, poses_qt, kf_points, lm_xyz, lm_uv, graph, scale, iters=5):
+        if not self.dense or self.node_flag is not None:
+            raise ValueError("keyframe BA needs the dense graph (dense_graph=True) without the embedded-deformation mode")
+        tr = self.nrs.Trace(256)
+        pq, xyz = self.ctx.dba_solve_window_rg(self.cam, poses_qt, kf_points, lm_xyz, lm_uv, graph, scale, iters, tr, self.cap)
+        ns, nd = self.ctx.dba_window_edge_counts()
+        return dict(poses_qt=pq, lm_xyz=xyz, n_spring=ns, n_damper=nd, trials=len(tr.trials))
+
     def _padded(self, map_pos):
         """positions by point index for the dense graph: capacity rows (the graph grows in doubled steps, the map one point at a time)"""
         pos = np.zeros((self.rg.cap, 3), F32)
@@ -377,17 +388,58 @@ class TemporalBuffer:
         return tb, np.array([s["mag"] for s in self.snaps], F32), ids
 
 
+class KeyFrame:
+    """KeyFrame(Frame&) (modules/map/keyframe.cc:26-55) on flat arrays: the TRACKED_WITH_3D slots of the frame, then the TRACKED ones (position
+    zero, no map point); everything else stays behind.  kp_id is carried along so that Frame::SetFromKeyFrame gives the slots their ids back."""
+
+    def __init__(self, kf_id, kp, pos, status, map_index, kp_id, pose):
+        status = np.asarray(status, np.int32)
+        order = np.concatenate([np.nonzero(status == TRACKED_WITH_3D)[0], np.nonzero(status == TRACKED)[0]])
+        self.id = int(kf_id)
+        self.kp, self.pos = np.asarray(kp, F32)[order].copy(), np.asarray(pos, F32)[order].copy()
+        self.status, self.map_index = status[order].copy(), np.asarray(map_index, np.int32)[order].copy()
+        self.kp_id = np.asarray(kp_id, np.int64)[order].copy()
+        self.pos[self.status == TRACKED] = 0
+        self.map_index[self.status == TRACKED] = -1
+        self.pose = (np.asarray(pose[0], F32).copy(), np.asarray(pose[1], F32).copy())
+
+
+class UnmappedQueue:
+    """Map::unmapped_keyframes_ as the reference handles it: InsertKeyFrame pushes the id at the back (map.cc:42),
+    GetNextUnmappedKeyFrame returns the keyframe at the FRONT and pops the BACK (map.cc:62-72).  With one id queued the two are the same
+    keyframe; with more, the oldest is handed out again and again while the newer ones are dropped unmapped.  Reproduced, not repaired."""
+
+    def __init__(self):
+        self.ids = []
+
+    def push(self, kf_id):
+        self.ids.append(int(kf_id))
+
+    def next(self):
+        if not self.ids:
+            return None
+        front = self.ids[0]
+        self.ids.pop()
+        return front
+
+
 class FrameLoop:
     """State of Tracking + the slice of Map / Frame it touches, on flat arrays."""
 
     def __init__(self, backend, project_f32, wh, scale, kp0, X0, graph, pose_q, pose_t, im0,
                  klt_min_ssim=0.7, images_to_insert_keyframe=5, extract_on_keyframes=True, mapping=False, rad_per_pixel=None, rigidity_th=0.004,
-                 camera=None, max_buffer_size=20):
+                 camera=None, max_buffer_size=20, keyframe_ba=False):
         """mapping=True (needs a dense-graph backend, rad_per_pixel = Mapping::Options::rad_per_pixel and camera = (model, params) for the
-        flat temporal buffer): the FrameMapping branch of Mapping::DoMapping after every tracked frame, see the module's header."""
+        flat temporal buffer): the FrameMapping branch of Mapping::DoMapping after every tracked frame, see the module's header.
+        keyframe_ba=True (needs mapping=True and a backend with dba_window): the KeyFrameMapping branch as well."""
         self.b, self.project, self.wh, self.scale = backend, project_f32, wh, float(scale)
         n = len(kp0)
         self.mapping = bool(mapping)
+        self.keyframe_ba = bool(keyframe_ba)
+        if self.keyframe_ba and not self.mapping:
+            raise ValueError("keyframe_ba=True needs mapping=True")
+        if self.keyframe_ba and not hasattr(backend, "dba_window"):
+            raise ValueError("keyframe_ba=True needs a backend with dba_window")
         if self.mapping:
             if not getattr(backend, "dense", False):
                 raise ValueError("mapping=True needs a backend that keeps the all-pairs graph (dense_graph=True)")
@@ -425,6 +477,11 @@ class FrameLoop:
             self.b.archive_templates(np.arange(n, dtype=np.int32), np.arange(n, dtype=np.int32))
         else:
             self.templates = self.b.klt_get_templates(n)
+        if self.keyframe_ba:
+            # Map::keyframes_ and Map::unmapped_keyframes_.  The initial keyframe is queued: one unmapped keyframe is left for the first
+            # frame, as `unmapped_keyframes = 1` above has it, so both settings take the KeyFrameMapping branch on the same frames
+            self.keyframes, self.next_kf_id, self.unmapped = {}, 0, UnmappedQueue()
+            self.insert_keyframe()
         self.log = []
 
     @classmethod
@@ -447,7 +504,26 @@ class FrameLoop:
                    result["pose_q"], t, im, **kw)
         loop.pos = (X * scale).astype(F32)
         loop.init_sigma, loop.init_sigma_graph = sigma, sigma_graph
+        if loop.keyframe_ba:
+            # tracking.cc:190-195: BOTH frames become keyframes -- the reference frame (its keypoints, the reference positions, the identity
+            # pose) and the current one -- and both are queued; the initialisation's own DoMapping (SLAM/system.cc:128) then takes the
+            # front and pops the back, which leaves the reference keyframe for the loop's first frame.  (That call's BA has two keyframes
+            # and returns at OPT:922; its SetFromKeyFrame is not restated: the loop starts from the current frame, as without keyframe_ba.)
+            loop.keyframes, loop.next_kf_id, loop.unmapped = {}, 0, UnmappedQueue()
+            loop.insert_keyframe(kp=np.asarray(result["reference_keypoints"], F32), pos=Xs,
+                                 pose=(np.array([0, 0, 0, 1], F32), np.zeros(3, F32)))
+            loop.insert_keyframe()
+            loop.unmapped.next()
         return loop
+
+    # ---- KeyFrame(frame) + Map::InsertKeyFrame (keyframe.cc:26-55, map.cc:37-45); kp / pos / pose: another frame's, slot for slot
+    def insert_keyframe(self, kp=None, pos=None, pose=None):
+        kf = KeyFrame(self.next_kf_id, self.kp if kp is None else kp, self.pos if pos is None else pos, self.status, self.map_index, self.kp_id,
+                      self.pose if pose is None else pose)
+        self.next_kf_id += 1
+        self.keyframes[kf.id] = kf
+        self.unmapped.push(kf.id)
+        return kf
 
     # ---- tracking.cc:72-112 (tracked branch)
     def track_image(self, im):
@@ -474,12 +550,55 @@ class FrameLoop:
 
     # ---- Mapping::DoMapping (mapping.cc:36-54) without the BA: a pending keyframe takes the KeyFrameMapping branch, which is skipped
     def do_mapping(self, keyframe_inserted):
+        if self.keyframe_ba:                                       # (keyframe_insertion has queued the new keyframe)
+            kf_id = self.unmapped.next()                           # Map::GetNextUnmappedKeyFrame
+            if kf_id is None:
+                return self.frame_mapping()
+            ba = self.keyframe_mapping()
+            self.set_from_keyframe(self.keyframes[kf_id])
+            return dict(skipped=None, ba=ba, set_from=kf_id, triangulated=[], mode=None)
         if keyframe_inserted:
             self.unmapped_keyframes += 1
         if self.unmapped_keyframes > 0:
             self.unmapped_keyframes -= 1
             return dict(skipped="KeyFrameMapping", triangulated=[], mode=None)
         return self.frame_mapping()
+
+    # ---- Mapping::KeyFrameMapping = LocalDeformableBundleAdjustment (mapping.cc:56-58, OPT:892-1161) on the backend's one call
+    def keyframe_mapping(self):
+        ids = sorted(self.keyframes)[-5:]                          # the five largest ids (OPT:894-920), flattened oldest first (OPT:930)
+        if len(ids) < 3:
+            return None                                            # OPT:922-924
+        kfs = [self.keyframes[i] for i in ids]
+        m3 = [kf.status == TRACKED_WITH_3D for kf in kfs]          # in keyframe index order (GetMapPointsIdsWithStatus)
+        kf_points = [kf.map_index[m].astype(np.int32) for kf, m in zip(kfs, m3)]
+        lm_xyz = np.concatenate([kf.pos[m] for kf, m in zip(kfs, m3)]).astype(F32)
+        lm_uv = np.concatenate([kf.kp[m] for kf, m in zip(kfs, m3)]).astype(F32)
+        poses_qt = np.array([np.concatenate([kf.pose[0], kf.pose[1]]) for kf in kfs], np.float64)
+        r = self.b.dba_window(poses_qt, kf_points, lm_xyz, lm_uv, self.graph, self.scale, 5)
+        # OPT:1146-1160, over inserted_landmarks: the keyframes that contributed a landmark get their pose (fp64 unit quaternion and
+        # translation, each cast to fp32) and KeyFrame::LandmarkPositions() of those slots back.  The map points' own positions are
+        # not written (map_pos stays).
+        pq, xyz = np.asarray(r["poses_qt"], np.float64).reshape(-1, 7), np.asarray(r["lm_xyz"]).reshape(-1, 3)
+        at = 0
+        for k, (kf, m) in enumerate(zip(kfs, m3)):
+            n = int(m.sum())
+            if n:
+                kf.pose = (pq[k, :4].astype(F32), pq[k, 4:].astype(F32))
+                kf.pos[m] = xyz[at:at + n].astype(F32)
+            at += n
+        return dict(n_kf=len(kfs), n_lm=at, n_spring=int(r["n_spring"]), n_damper=int(r["n_damper"]), trials=int(r["trials"]))
+
+    # ---- Mapping::UpdateTrackingFrameFromKeyFrame -> Frame::SetFromKeyFrame (mapping.cc:266-270, frame.cc:47-77).  last_frame_ and
+    # current_frame_ are one object in the reference, so the motion model's "last pose" is the keyframe's as well.  The keyframe may be
+    # older than the frame (UnmappedQueue): reproduced, not repaired.
+    def set_from_keyframe(self, kf):
+        order = np.concatenate([np.nonzero(kf.status == TRACKED_WITH_3D)[0], np.nonzero(kf.status == TRACKED)[0]])
+        self.kp, self.pos, self.status = kf.kp[order].copy(), kf.pos[order].copy(), kf.status[order].copy()
+        self.map_index, self.kp_id = kf.map_index[order].copy(), kf.kp_id[order].copy()
+        self.pos[self.status == TRACKED] = 0
+        self.pose = (kf.pose[0].copy(), kf.pose[1].copy())
+        self.last_pose = self.pose
 
     # ---- Mapping::LandmarkTriangulation (mapping.cc:65-257) on the backend's one call
     def frame_mapping(self):
@@ -660,6 +779,8 @@ class FrameLoop:
             self.kp_id = self.kp_id[order]
         self.pos[self.status == TRACKED] = 0
         self.map_index[self.status == TRACKED] = -1               # only the 3D slots keep their map point (frame.cc:56-62)
+        if self.keyframe_ba:
+            self.insert_keyframe()                                 # tracking.cc:354-358: the keyframe of this frame, queued for the mapping
         self.b.klt_set_reference(im, self.kp)
         if self.dev_templates:                                     # Frame::MapPointIdToIndex: slots that have a map point
             slots = np.nonzero(self.map_index >= 0)[0].astype(np.int32)
