@@ -86,7 +86,7 @@ struct nrs_ctx {
     hipEvent_t ev_vec = nullptr, ev_halo = nullptr;
     nrs::DevBuf tap;                 // residual taps (edge lists by vertex + outputs) of the engine `tap_serial`: built on first use
     unsigned long long tap_serial = 0, engine_serial = 0;
-    nrs::DevBuf pack_ws, pack_ws2, pack_ws3, pack_ws4;   // device-side problem construction (nrs_engine_devpack.hpp): raw inputs + intermediates
+    nrs::DevBuf pack_ws, pack_ws2, pack_ws3, pack_ws4;   // device-side problem construction (scratch plans: nrs_devpack_host.hpp): raw inputs + intermediates, window-edge scratch and output
     nrs::DevBuf dba_skin;            // ... and of the resident BA window (N2b)
     nrs::DevBuf dba_kft;             // embedded BA window: the keyframe-block factorisation (nrs_engine_kft.hpp)
     bool kft_attr_done = false;      // ... its kernels' dynamic-LDS attributes are set on this context's device (kft_kernel_attributes)

@@ -331,7 +331,7 @@ extern "C" int nrs_dba_window_edges(nrs_ctx* c, int32_t* n_spring, int32_t* sp_i
 
 // ---- LocalDeformableBundleAdjustment served by the device-resident all-pairs graph (include/nrs.h nrs_dba_solve_window_rg): the
 // window's GetEdges calls (OPT:1029-1030) and its walks (OPT:1033-1074, 1086-1135) run on the device over the graph's own lists
-// (nrs_engine_devpack.hpp win_edges_device), then the set-up and the solve of nrs_dba_solve_window.
+// (nrs_engine_winedges.hpp win_edges_device), then the set-up and the solve of nrs_dba_solve_window.
 constexpr int RG_WINDOW_FIRST_CAP = 64;                             // the first prefix length when the caller names none
 extern "C" int nrs_dba_solve_window_rg(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
                                        float* lm_xyz, const float* lm_uv, nrs_rgraph* g, int32_t cap_per_point, float scale, int32_t iters, nrs_lm_trace* trace) {

@@ -61,7 +61,9 @@
 #include "nrs_engine_plan.hpp"        // the decisions the host packer (setup) and the device packer (devpack) share, and the arena
 #include "nrs_engine_setup.hpp"
 #include "nrs_engine_kft_setup.hpp"
-#include "nrs_engine_devpack.hpp"
+#include "nrs_devpack_kernels.hpp"     // the device packer: its kernels, ...
+#include "nrs_engine_winedges.hpp"     // ... the window-edge construction (WinDev, WinLists: embwin walks the same lists), ...
+#include "nrs_engine_devpack.hpp"      // ... and the staged build (DeviceBuild) engine_create runs
 #include "nrs_engine_embwin.hpp"
 #include "nrs_engine_launch.hpp"      // kernel-variant dispatch (with_lanes, the launchers, Timer) and, through it, nrs_engine_probes.hpp
 

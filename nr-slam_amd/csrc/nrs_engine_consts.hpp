@@ -1,5 +1,5 @@
-// Constants of the engine's interface that host-only code shares with it (no HIP here: nrs_nd_prep_host.hpp, nrs_kft_prep_host.hpp and
-// their stand-alone checks compile with a plain C++ compiler).
+// Constants of the engine's interface that host-only code shares with it (no HIP here: nrs_nd_prep_host.hpp, nrs_kft_prep_host.hpp,
+// nrs_devpack_host.hpp and their stand-alone checks compile with a plain C++ compiler).
 #pragma once
 #include <cstdint>
 
@@ -7,6 +7,7 @@ namespace nrs {
 
 enum : uint8_t { RF_OBS = 1, RF_REPROJ_ACTIVE = 2, RF_FIXED = 4 };   // EngineSpec::rflag
 constexpr int ROW_ALIGN = 256;       // pose row padding; also rows per k_reproj workgroup
+constexpr int BLK = 256;             // threads per workgroup everywhere
 constexpr int SK_MAX = 11;           // embedded mode (nrs_engine_skin.hpp): nodes per skinned observation (the walk of OPT:255-279 accepts 11)
 // keyframe-block factorisation (nrs_engine_kft.hpp; set-up stages: nrs_kft_prep_host.hpp)
 constexpr int KFT_B = 64;            // pivot block / tile of the sweeps

@@ -1,7 +1,7 @@
 // Device-side list construction of the EMBEDDED BA window (part of nrs_engine.hip; include/nrs.h nrs_dba_solve_window_embedded).
 //
 // The host form is nrs_dba_build_edges_embedded (csrc/nrs_host_build.cpp), whose output this reproduces index for index and bit
-// for bit, the fp64 skinning weights included.  It is the per-observation walk of k_win_edges (nrs_engine_devpack.hpp) with two
+// for bit, the fp64 skinning weights included.  It is the per-observation walk of k_win_edges (nrs_engine_winedges.hpp) with two
 // additions: the walks run between NODE copies only, and every observed point that is not a node is bound to the <= 11 node
 // copies its own walk accepts.
 //   numbering   a node copy is an observation whose map point has is_node set; node copies are numbered keyframe by keyframe in
@@ -202,29 +202,17 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     hipStream_t st = c->stream;
     NRS_HIP(c, hipSetDevice(c->device));
     StageTimer mark{c, "embedded lists", true, 18, false};
-    size_t tb = 0;
-    (void)rocprim::exclusive_scan(nullptr, tb, (int*)nullptr, (int*)nullptr, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st);
-    int *d_pt, *d_k, *d_nrp, *d_col, *d_st, *d_cur, *d_flag, *d_lm, *d_cs, *d_cd, *d_ck, *d_os, *d_od, *d_ok, *d_tot, *d_krp, *d_kfb;
-    float *d_w, *d_d0, *d_xyz, *d_uv;
-    uint8_t* d_node;
-    void* tmp;
-    auto layout = [&](DpScratch& W) {
-        d_pt = W.get<int>(n_obs); d_k = W.get<int>(n_obs); d_node = W.get<uint8_t>(n_points);
-        d_nrp = W.get<int>(n_points + 1); d_col = W.get<int>(nnz); d_st = W.get<int>(nnz); d_w = W.get<float>(nnz); d_d0 = W.get<float>(nnz);
-        d_xyz = W.get<float>(3 * (size_t)n_obs); d_uv = W.get<float>(2 * (size_t)n_obs);
-        d_cur = W.get<int>((size_t)n_kf * n_points);
-        d_flag = W.get<int>((size_t)n_obs + 1); d_lm = W.get<int>((size_t)n_obs + 1);
-        d_cs = W.get<int>((size_t)n_obs + 1); d_cd = W.get<int>((size_t)n_obs + 1); d_ck = W.get<int>((size_t)n_obs + 1);
-        d_os = W.get<int>((size_t)n_obs + 1); d_od = W.get<int>((size_t)n_obs + 1); d_ok = W.get<int>((size_t)n_obs + 1);
-        d_tot = W.get<int>(8);
-        d_krp = W.get<int>((size_t)n_kf + 1); d_kfb = W.get<int>(2 * ((size_t)n_kf + 1));
-        tmp = W.get<char>(tb + 256);
-    };
-    DpScratch dry{nullptr, 0, 0};
-    layout(dry);
-    NRS_TRY(c->ensure(c->pack_ws3, dry.off + 4096));
-    DpScratch W{c->pack_ws3.as<char>(), 0, c->pack_ws3.cap};
-    layout(W);
+    const size_t tmp_bytes = win_scan_tmp_bytes(c, (size_t)n_obs + 1);
+    const auto P = dp_embwin_plan(DpEmbWinIn{(size_t)n_kf, (size_t)n_obs, (size_t)n_points, (size_t)nnz, tmp_bytes});
+    NRS_TRY(c->ensure(c->pack_ws3, P.need));
+    char* const w3 = c->pack_ws3.as<char>();
+    int *d_pt = P.at<int>(w3, EL_pt), *d_k = P.at<int>(w3, EL_k), *d_nrp = P.at<int>(w3, EL_nrp), *d_col = P.at<int>(w3, EL_col), *d_st = P.at<int>(w3, EL_st),
+        *d_cur = P.at<int>(w3, EL_cur), *d_flag = P.at<int>(w3, EL_flag), *d_lm = P.at<int>(w3, EL_lm), *d_cs = P.at<int>(w3, EL_cs), *d_cd = P.at<int>(w3, EL_cd),
+        *d_ck = P.at<int>(w3, EL_ck), *d_os = P.at<int>(w3, EL_os), *d_od = P.at<int>(w3, EL_od), *d_ok = P.at<int>(w3, EL_ok), *d_tot = P.at<int>(w3, EL_tot),
+        *d_krp = P.at<int>(w3, EL_krp), *d_kfb = P.at<int>(w3, EL_kfb);
+    float *d_w = P.at<float>(w3, EL_w), *d_d0 = P.at<float>(w3, EL_d0), *d_xyz = P.at<float>(w3, EL_xyz), *d_uv = P.at<float>(w3, EL_uv);
+    uint8_t* d_node = P.at<uint8_t>(w3, EL_node);
+    void* tmp = P.at<char>(w3, EL_tmp);
     NRS_HIP(c, hipMemcpyAsync(d_pt, kf_pt, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemcpyAsync(d_k, obs_kf, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
     NRS_HIP(c, hipMemcpyAsync(d_node, is_node, (size_t)n_points, hipMemcpyHostToDevice, st));
@@ -247,16 +235,16 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     size_t t2;
     // ---- node-copy numbering and the table
     hipLaunchKernelGGL(k_ew_flag, g, b, 0, st, n_obs, d_pt, d_node, d_flag);
-    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_flag, d_lm, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_flag, d_lm, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
     hipLaunchKernelGGL(k_ew_cur, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur);
     hipLaunchKernelGGL(k_ew_check, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur, d_tot);
     // ---- count pass, scans
     WinDev wd{n_kf, n_points, nullptr, d_pt, d_k, WinLists{d_nrp, nullptr, nullptr, 0, d_col, d_st, d_w, d_d0}, d_cur};
     hipLaunchKernelGGL((k_ew_walk<false>), g, b, 0, st, wd, n_obs, d_flag, d_lm, d_cs, d_cd, d_ck, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
                        (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0, n_obs, 0);
-    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
-    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cd, d_od, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
-    t2 = tb + 256; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_ck, d_ok, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cd, d_od, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_ck, d_ok, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
     hipLaunchKernelGGL(k_ew_totals, dim3(1), dim3(64), 0, st, n_obs, d_lm, d_os, d_od, d_ok, d_tot);
     if (own_only) hipLaunchKernelGGL(k_ew_kf_bounds, dim3((unsigned)((n_kf + 256) / 256)), b, 0, st, n_kf, d_krp, d_lm, d_ok, d_kfb);
     NRS_HIP(c, hipGetLastError());

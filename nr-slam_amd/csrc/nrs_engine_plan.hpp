@@ -1,6 +1,6 @@
 // What the two problem constructions decide alike, stated once: row groups, lanes per row, tile classes, LDS and path flags, the shard
 // window, the arena, and the small arrays both finish with.  The host packer (nrs_engine_setup.hpp, engine_create) and the device packer
-// (nrs_engine_devpack.hpp, engine_create_device) call these, so the two give the same bits by construction.
+// (nrs_engine_devpack.hpp, DeviceBuild) call these, so the two give the same bits by construction.
 // Part of nrs_engine.hip (one translation unit); see that file's header for the design.
 #pragma once
 

@@ -1,6 +1,7 @@
 // Host side of the engine: arena, row layout, sliced-ELL packing, halo lists, tile classes, uploads (engine_create and friends).
 // Part of nrs_engine.hip (one translation unit); see that file's header for the design.
 #pragma once
+#include "nrs_devpack_host.hpp"     // the device packer's scratch plans, fall-back reasons and host decisions (DeviceBuild)
 
 namespace nrs {
 
@@ -196,9 +197,6 @@ static int push_masks(nrs_ctx* c, Engine* e, const uint8_t* sp_active, const uin
     return NRS_OK;
 }
 
-static bool devpack_eligible(nrs_ctx* c, const EngineSpec& s, int n_pad_rows);
-static int engine_create_device(nrs_ctx* c, const EngineSpec& s, const RowGroups& g, Arena* arena, Engine* e, bool* done);
-
 // ---- engine_create: the host construction, stage by stage
 // argument checks on inputs every rank of a sharded upload holds alike
 static int spec_validate(nrs_ctx* c, const EngineSpec& s) {
@@ -280,6 +278,48 @@ struct HostBuild {
     void edge_lists();
     void host_mirrors();
     int uploads();
+};
+
+// What a device build holds of the window: the incidences (own_s, own_d) and counted edges (ec_*) of the rows it packs and the sliced-ELL
+// sizes.  rank: the share is a rank's of a sharded window -- tiles of other ranks exist and keep empty lists, the shard fields want every
+// own tile's smallest / largest halo row, and the keys of the counted edges were sorted with the incidence keys (incidences_own)
+struct DpShare { int64_t own_s, own_d; int ec_nsp, ec_ndm; size_t nnz_s, nnz_d; bool rank; };
+// The device packer's state (the stages: nrs_engine_devpack.hpp; scratch plans and host decisions: nrs_devpack_host.hpp): what one stage
+// leaves for the next -- the two scratch buffers as typed pointers, the share, the host copies the decisions read, upload staging.
+// A stage that finds the window does not qualify after all says so in `why`; engine_create then runs the host packer from scratch.
+struct DeviceBuild {
+    nrs_ctx* c; const EngineSpec& s; Engine* e; Dev& d; const RowGroups& g; Arena* arena; int T;
+    StageTimer mark{c, "device pack", true};
+    hipStream_t st = c->stream;
+    const bool sh = c->comm != nullptr && s.shard;                 // a rank of a sharded window packs the incidence records of its own keyframe range only
+    const int K = s.K, M = s.M, n_sp = s.n_sp, n_dm = s.n_dm;
+    const int64_t ni_s = 2 * (int64_t)n_sp, ni_d = 4 * (int64_t)n_dm;
+    DpReason why = DP_BUILT;
+    int n_rows = 0, n_slices = 0, n_tiles = 0, pack_lo = 0, pack_hi = 0, tb0 = 0, tb1 = 0, row_bits = 0;   // [tb0, tb1): the tiles of [pack_lo, pack_hi)
+    size_t tmp_bytes = 0, tmp2_bytes = 0, n_halo = 0;
+    // scratch 1 (bound in uploads): raw inputs + intermediates sized from the inputs
+    double *r_x, *mm; float *r_uv, *r_d0, *r_w; uint64_t *code_a, *code_b; uint32_t *tk_a, *tk_b; void* tmp;
+    int *r_kf, *r_sp, *r_dm, *val_a, *val_b, *cs, *cd, *d_pose_ptr, *d_pgp, *tile_off, *vrow, *row_v, *tv_a, *tv_b, *cnt_s, *cnt_d, *rs_s, *rs_d, *ws, *wd, *d_ss, *d_sd,
+        *hs, *hns, *hmin, *hmax, *d_flag;
+    // scratch 2 (bound in scratch2): sized from the share; the incidence keys live in scratch 1 on one GPU, here on a rank
+    int *S_other, *D_o; uint8_t* S_side; int8_t* D_role; float *t_d0, *t_w; uint64_t *ek_s, *ek_s2, *ek_d, *ek_d2, *key_s, *key_s2, *key_d, *key_d2; void* tmp2 = nullptr;
+    DpShare sr{};
+    int h_nnz[2] = {0, 0}, h_own[4] = {0, 0, 0, 0}, h_flag = 0;     // download targets: they outlive the stage's synchronise
+    std::vector<int> h_hs, h_hns, h_vrow, h_hmin, h_hmax, halo_ptr, tile_list;
+    std::vector<Pose> poses;                                        // upload staging: alive until host_side's synchronise
+    static dim3 nb(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+    bool precheck();
+    int uploads();
+    int row_layout();
+    int slice_offsets();
+    int scratch2();
+    int incidences_whole();
+    int incidences_own();
+    int incidences();
+    int fill_and_halo_sizes();
+    int decide();
+    int final_arrays();
+    int host_side();
 };
 
 // ---- row layout: pose-major, each pose padded to ROW_ALIGN rows (row_groups), Morton order inside
@@ -822,13 +862,23 @@ int engine_create(nrs_ctx* c, const EngineSpec& s, Arena* arena, Engine** out) {
     e->arena = arena;
     HostBuild B{c, s, e, e->d, g, lanes_per_row(c, g.n_pad_rows)};
     StageTimer& mark = B.mark;
-    if (devpack_eligible(c, s, g.n_pad_rows)) {                    // plain BA window on the two-kernel path: built on the device
-        bool done = false;
-        NRS_TRY(engine_create_device(c, s, g, arena, e, &done));
-        if (done) { guard.keep = true; *out = e; return NRS_OK; }
+    DeviceBuild D{c, s, e, e->d, g, arena, B.T};                    // a plain BA window is built on the device, stage by stage (nrs_engine_devpack.hpp)
+    if (D.precheck()) {
+        NRS_TRY(D.uploads());
+        NRS_TRY(D.row_layout());
+        NRS_TRY(D.incidences());
+        NRS_TRY(D.fill_and_halo_sizes());
+        NRS_TRY(D.decide());
+        if (D.why == DP_BUILT) {
+            NRS_TRY(D.final_arrays());
+            NRS_TRY(D.host_side());
+            guard.keep = true; *out = e;
+            return NRS_OK;
+        }
         *e = Engine();                                             // (did not qualify after all: the host path, from scratch)
         e->arena = arena;
     }
+    if (D.mark.on && D.why != DP_INELIGIBLE) fprintf(stderr, "[nrs] device pack: host path (%s)\n", dp_reason_name(D.why));   // (a window that was a candidate)
     if (s.edges_on_device) return c->fail(NRS_ERR_STATE, "device-built edge lists need the device-side construction, which this window does not qualify for");
     // a2's single-frame engines: the direct solver's symbolic phase needs the structure only and runs next to the packing below
     if (s.sk_window() > 0) {                                       // (checked HERE: the plan thread below indexes by these)

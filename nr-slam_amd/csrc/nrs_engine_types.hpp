@@ -4,8 +4,7 @@
 
 namespace nrs {
 
-// (ROW_ALIGN, the pose row padding: nrs_engine_consts.hpp)
-constexpr int BLK = 256;             // threads per workgroup everywhere
+// (ROW_ALIGN, the pose row padding, and BLK, the threads per workgroup: nrs_engine_consts.hpp)
 constexpr int NPART = 12;            // per-block partial slots of the SpMV kernel: [0..2] dots, [3..8] pose sums
 constexpr int SK_RL = 16;            // embedded mode (SK_MAX: nrs_engine_consts.hpp): lanes per node-row list of the PCG form, lists per workgroup
 constexpr int SK_RPB = BLK / SK_RL;

@@ -680,7 +680,7 @@ int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_
 }
 // GetEdges of ids a kernel of the caller listed, the lists left on the device in k_rg_get_edges' layout: o->count[row] = the FULL
 // length of the row's list, of which the first min(count, stride) entries stand at [row * stride, ..) of col / status / w / d0
-// (the BA window's walk reads them there, nrs_engine_devpack.hpp).  Valid until the graph's next GetEdges.
+// (the BA window's walk reads them there, nrs_engine_winedges.hpp).  Valid until the graph's next GetEdges.
 int rg_get_edges_device(nrs_rgraph* g, int32_t n_ids, const int32_t* d_ids, int32_t cap_per_point, RgDeviceLists* o) {
     const int *h_cnt, *h_col, *h_st;
     const float *h_w, *h_d0;

@@ -1,8 +1,9 @@
-"""Device-side problem construction (csrc/nrs_engine_devpack.hpp) against the host construction it replaces
+"""Device-side problem construction (csrc/nrs_engine_devpack.hpp, csrc/nrs_devpack_kernels.hpp) against the host construction it replaces
 (csrc/nrs_engine_setup.hpp): every packed array -- vertex -> row map, sliced-ELL offsets, incidence headers and static data,
 halo lists, tile classes, chi2 edge lists, row data -- bit for bit (FNV checksums through nrs_dba_pack_hash), and the solves on
 top of the two identical to the last bit.  Windows: C2 (BASELINE configs[1]), a ragged window (few keyframes, many points, a
-large share of unobserved points), and C3."""
+large share of unobserved points), and C3.  One window qualifies up front and falls back to the host construction from inside the device
+build (a halo beyond the limits)."""
 import numpy as np
 import pytest
 
@@ -99,3 +100,54 @@ def test_solve_window_builds_the_same_edges_and_result(n, k, seed, model):
     assert [(t["accepted"], t["lam"], t["chi_new"]) for t in tr.trials] == [(t["accepted"], t["lam"], t["chi_new"]) for t in tr2.trials]
     assert np.array_equal(pq, pq2) and np.array_equal(xyz, xyz2)
     c.close(); c2.close()
+
+
+def _hub_window(n=1500, k=3, seed=29):
+    """A window one of whose tiles reaches nearly every row: a map point observed by every keyframe is put at the head of every other
+    point's neighbour list, so every walk makes its pair with it first -- the hub's row then has a spring to every other row of its
+    keyframe and, through the dampers of those pairs, reaches every row of the adjacent keyframes."""
+    p = S.make_dba_problem(n, k, seed)
+    hub = int(sorted(set.intersection(*[set(map(int, kp)) for kp in p["kf_points"]]))[0])
+    nb = p["nbr"]
+    rp = np.asarray(nb["rowptr"])
+    col, w, d0, st = [], [], [], []
+    for o in range(n):
+        a, b = int(rp[o]), int(rp[o + 1])
+        head = [] if o == hub else [hub]
+        col += head + [int(x) for x in nb["col"][a:b]]
+        w += [0.5] * len(head) + [float(x) for x in nb["w"][a:b]]
+        d0 += [1.0] * len(head) + [float(x) for x in nb["d0"][a:b]]
+        st += [S.GRAPH_NEUTRAL] * len(head) + [int(x) for x in nb["status"][a:b]]
+    cnt = np.array([0] + [int(rp[o + 1] - rp[o]) + (o != hub) for o in range(n)])
+    p["nbr"] = dict(rowptr=np.cumsum(cnt).astype(np.int32), col=np.array(col, np.int32), w=np.array(w, np.float32), d0=np.array(d0, np.float32),
+                    status=np.array(st, np.int32))
+    return p, hub
+
+
+def test_a_window_that_fails_late_takes_the_host_path_cleanly(monkeypatch, capfd):
+    """A plain window that passes the up-front eligibility (>= 2 keyframes, >= 2048 padded rows) and turns out not to qualify INSIDE the
+    device build: the halo of the hub's tile is beyond DP_HCAP = 2048 rows (the hub reaches ~1400 rows of its own keyframe and as many
+    of each neighbour's: the NRS_TIMING line names the reason).  engine_create then starts over on the host path: [21] = 0, and every
+    checksum, trial, pose, point and residual is that of the NRS_HOST_PACK=1 run."""
+    p, hub = _hub_window()
+    cnt = np.bincount(p["lm_kf"], minlength=3)
+    assert len(cnt) == 3 and sum(max(1, -(-int(n) // 256)) * 256 for n in cnt) >= 2048
+    e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
+    lm0 = len(p["kf_points"][0]) + int(np.flatnonzero(np.asarray(p["kf_points"][1]) == hub)[0])
+    assert np.count_nonzero(np.asarray(e["sp_ij"]).reshape(-1, 2) == lm0) > 1024        # the hub's row in the middle keyframe: a spring to most of its keyframe
+    cam = nrs.make_camera(p["model"], p["prm"])
+    qt = np.concatenate([p["poses_q"], p["poses_t"]], 1)
+    nrs.debug_set("NRS_TIMING", "1")
+    capfd.readouterr()
+    try:
+        hd, td, qd, xd, rd = _solve(monkeypatch, False, p, e, cam, qt)
+        why = [ln for ln in capfd.readouterr().err.splitlines() if "device pack: host path" in ln]
+        hh, th, qh, xh, rh = _solve(monkeypatch, True, p, e, cam, qt)
+    finally:
+        nrs.debug_set("NRS_TIMING", None)
+    assert why == ["[nrs] device pack: host path (a halo beyond the limits)"], why
+    assert hd[21] == 0 and hh[21] == 0
+    assert hd == hh
+    assert [(t["accepted"], t["inner"], t["lam"], t["chi"], t["chi_new"]) for t in td] == [(t["accepted"], t["inner"], t["lam"], t["chi"], t["chi_new"]) for t in th]
+    assert np.array_equal(qd, qh) and np.array_equal(xd, xh)
+    assert all(np.array_equal(a, b) for a, b in zip(rd, rh))
