@@ -172,7 +172,7 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *                 block's sweep in the 4-pivot register form), NRS_KFT_FOUR_WAVES (panel workgroups without the four helper waves), NRS_KFT_NO_RESIDUAL_TEST (M^-1 applied again after the first PCG step
  *                 instead of the step's residual tested on its own)
  *   sharding      NRS_SHARD_PACK_ALL, NRS_SHARD_FULL_VECTORS
- *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR, NRS_RG_MAX_CAP=<n> (a lower limit on the GetEdges
+ *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_PO_NO_CACHE, NRS_PO_MULTI_GROUPS=<g>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR, NRS_RG_MAX_CAP=<n> (a lower limit on the GetEdges
  *                 prefix a call may ask for: the "ran off at the limit" refusals)
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
  * (what each selects: README.md "Debug switches"; the A/B tests drive every launch form through nrs_debug_set). */

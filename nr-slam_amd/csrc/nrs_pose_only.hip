@@ -577,11 +577,15 @@ extern "C" int nrs_pose_only_solve(nrs_ctx* c, const nrs_camera* cam, int32_t n,
     // One workgroup runs the whole function in ONE launch while its passes are short (the points then sit in its LDS: <= 7168 points);
     // beyond that a pass is spread over the chip and the serial part runs in a kernel of its own between passes (k_po_pass / k_po_step:
     // ~10 us per LM trial whatever the size, where the single workgroup needs n / 512 point evaluations per thread and trial).
-    // NRS_PO_MULTI_MIN moves the hand-over (tests run both forms on the same frames).
+    // NRS_PO_MULTI_MIN moves the hand-over (tests run both forms on the same frames).  NRS_PO_NO_CACHE=1 keeps the single workgroup's
+    // points in global memory at any n (the form of 7169 <= n < 32768); NRS_PO_MULTI_GROUPS=<g> caps the many-workgroup form's grid at g
+    // workgroups (>= 1), so that a frame of a few hundred points takes several grid-stride trips and sums several slots.
     int multi_min = 32768;                                    // (measured: 13.0 ms on one workgroup, 6.0 ms on many at 90k points; the two meet near 35k)
     if (const char* ev = c->env("NRS_PO_MULTI_MIN")) multi_min = atoi(ev);
+    if (const char* ev = c->env("NRS_PO_NO_CACHE")) { if (atoi(ev) != 0) a.cache_pts = 0; }
     if (n >= multi_min && n > 0) {
-        const int G = std::max(1, std::min(2 * c->prop.multiProcessorCount, (n + POM_THREADS - 1) / POM_THREADS));
+        int G = std::max(1, std::min(2 * c->prop.multiProcessorCount, (n + POM_THREADS - 1) / POM_THREADS));
+        if (const char* ev = c->env("NRS_PO_MULTI_GROUPS")) G = std::min(G, std::max(1, atoi(ev)));
         NRS_TRY(c->ensure(c->po_multi, sizeof(PoState) + 256 + sizeof(double) * 32 * (size_t)G));
         PoState* S = c->po_multi.as<PoState>();
         double* part = reinterpret_cast<double*>(c->po_multi.as<char>() + ((sizeof(PoState) + 255) & ~(size_t)255));

@@ -632,9 +632,10 @@ class DamperFixedEdges(EdgeGroup):
 # ----------------------------------------------------------------------------
 # a1: CameraPoseOptimization (g2o_optimization.cc:50-146)
 # ----------------------------------------------------------------------------
-def pose_only_solve(cam_model, cam_prm, uv, X, pose_q, pose_t, trace=None):
+def pose_only_solve(cam_model, cam_prm, uv, X, pose_q, pose_t, trace=None, chi2_out=None):
     """uv (n,2) f32, X (n,3) f32, pose (q xyzw, t) as handed over by the boundary.
-    Returns pose_q, pose_t (fp64), inlier mask (bool)."""
+    Returns pose_q, pose_t (fp64), inlier mask (bool).  chi2_out: a list that receives, per round, the float chi2 of every edge
+    that the round's classification compared with the 5.99 gate."""
     uv = np.asarray(uv, F32)
     X = np.asarray(X, F32)
     n = len(uv)
@@ -656,6 +657,8 @@ def pose_only_solve(cam_model, cam_prm, uv, X, pose_q, pose_t, trace=None):
         if len(out):
             e.err[out] = e.residual(G, out)
         chi = e.chi2().astype(F32)
+        if chi2_out is not None:
+            chi2_out.append(chi.copy())
         inl = ~(chi > TH2_SQ)
         e.level[:] = np.where(inl, 0, 1)
         if rnd == 2:
