@@ -114,7 +114,18 @@ static int evaluate(nrs_ctx* c, Engine* e, int which, bool reproj_done = false) 
         NRS_TRY(c->comm->allreduce(c, d.pk_loc, d.pk, (size_t)(2 + d.sh_world + (LIN ? 27 * d.K : 0))));
         hipLaunchKernelGGL((k_finalize_unpack<LIN>), dim3(1), b, 0, c->stream, d, ++c->seq);
     } else {
-        hipLaunchKernelGGL((k_finalize<LIN>), dim3(1), b, 0, c->stream, d, ++c->seq, (e->nd && e->nd->on) ? 1 : 0);
+        // the status words it leaves behind (publish_flags): a directly solved engine's are cleared every time; a re-arming PCG
+        // window's by the linearisation (the shadow sets' with them) and by the evaluation that finds the trial's solve finished
+        FlagSets fs{};
+        int zero = (e->nd && e->nd->on) ? 1 : 0;
+        if (e->rearm) {
+            zero = LIN ? 1 : 2;
+            if (LIN) {
+                for (int j = 0; j < e->n_spec; ++j) fs.p[fs.n++] = e->spec[j].flags;
+                for (bool& f : e->flags_clean) f = true;
+            }
+        }
+        hipLaunchKernelGGL((k_finalize<LIN>), dim3(1), b, 0, c->stream, d, ++c->seq, zero, fs);
     }
     NRS_HIP(c, hipGetLastError());
     return NRS_OK;
@@ -178,7 +189,7 @@ static int direct_trial_enqueue(nrs_ctx* c, Engine* e, int set, double lam, int*
 
 // The engine seen through shadow set `set` of a PCG BA window (nrs_engine_types.hpp SpecSet; set < 0: the engine itself): everything
 // an LM trial writes -- solve vectors, preconditioner inverses, partials, scalars, status words, trial state, host mirrors -- is the
-// set's, its launches go to the set's stream, its PCG launches become no-ops once the set's abort word holds abort_id.  The
+// set's, its launches go to the set's stream, its launches become no-ops once the set's abort word has reached abort_id.  The
 // linearisation and the current state are the engine's.  pcg_begin / pcg_enqueue_batch / pcg_advance / evaluate and the host waits
 // run unchanged on this view; the engine's own arrays, stream and mirrors come back when it goes.
 struct PcgSetView {
@@ -196,9 +207,10 @@ struct PcgSetView {
         d.pose[1 - e->cur] = q.pose; d.xl[1 - e->cur] = q.xl;
         d.abort = q.abort; d.abort_id = abort_id;
         e->h_scal = q.h_scal; e->h_flags = q.h_flags;
+        e->view_set = set;
         c->stream = c->spec_stream[set];
     }
-    ~PcgSetView() { if (on) { e->d = saved; c->stream = main; e->h_scal = hs; e->h_flags = hf; } }
+    ~PcgSetView() { if (on) { e->d = saved; c->stream = main; e->h_scal = hs; e->h_flags = hf; e->view_set = -1; } }
     PcgSetView(const PcgSetView&) = delete;
     PcgSetView& operator=(const PcgSetView&) = delete;
 };
@@ -216,7 +228,11 @@ constexpr double PEEK_RHO_LVL[5] = {0, -1.0, -0.25, -0.1, -0.03};
 
 static int pcg_begin(nrs_ctx* c, Engine* e, double lam, int* it) {
     const Dev& d = e->d;
-    NRS_HIP(c, hipMemsetAsync(d.flags, 0, sizeof(int) * 8, c->stream));
+    // the status words start at zero: left so by the evaluation that published them last (Engine::rearm), or filled here -- after an
+    // upload, a trial rejected at a peek or discarded, a solve that ran out of iterations, and on every other kind of engine
+    bool& clean = e->flags_clean[1 + e->view_set];
+    if (!(e->rearm && clean)) NRS_HIP(c, hipMemsetAsync(d.flags, 0, sizeof(int) * 8, c->stream));
+    clean = false;
     if (d.coarse) hipLaunchKernelGGL(k_coarse_invert, dim3(1), dim3(BLK), sizeof(double) * (size_t)d.co_n * d.co_n, c->stream, d, lam);
     hipLaunchKernelGGL(k_trial_setup, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, lam);
     if (e->kft && e->kft->on) {                                    // embedded BA window: factorise H + lambda I by keyframe blocks, u_0 = M^-1 b
@@ -336,6 +352,10 @@ static int pcg_advance(nrs_ctx* c, Engine* e, double lam, int stop_level, int* i
         int count = 0;
         if (stop_level == 0 && e->pred_iters > *it_io) count = std::min(std::max((e->pred_iters - *it_io) / 2, c->opt.pcg_batch), 8 * c->opt.pcg_batch);
         if (stop_level == 0 && e->pred_iters >= *it_io && e->pred_iters + 1 - *it_io <= c->opt.pcg_batch) count = e->pred_iters + 1 - *it_io;   // short solves: finish in one batch
+        // past what the last solve needed (its count sized the batch before, and the solve is still running): iteration counts of
+        // successive trials differ by one or two, so two more at a time -- a whole default batch here was one useful launch pair and
+        // seven no-ops in front of the evaluation on C2 (profiles/r10_c2_wasted_launches_parent.txt)
+        if (stop_level == 0 && e->pred_iters > 0 && *it_io > e->pred_iters && e->d.plain && !e->d.sh_on && !e->d.fused) count = 2;
         if (stop_level > 0 && e->pred_peek > 0) count = std::max(2, std::min(e->pred_peek, c->opt.pcg_batch));                                // waiting for a milestone: small steps
         if (*it_io >= c->opt.pcg_max_iters) { *done = true; break; }
         NRS_TRY(pcg_enqueue_batch(c, e, lam, it_io, count, ++c->seq));      // its last launch publishes the flags
@@ -360,6 +380,7 @@ static int first_batch(const nrs_ctx* c, const Engine* e, int q) {
 struct LmRun {
     nrs_ctx* c; Engine* e;
     bool peek_debug, check_chi, spec_dbg;                          // NRS_PEEK_DEBUG, NRS_CHECK_CHI, NRS_SPEC_DBG (host clocks of a batch on stderr)
+    bool rearm;                                                    // plain window on the two-kernel PCG: k_finalize re-arms the status words (Engine::rearm; NRS_NO_REARM: a fill per trial)
     int n_spec, n_spec_pcg;                                        // shadow sets for trials of a directly solved engine / of a PCG window (0: one trial at a time)
     int spec_first, spec_first_pcg;                                // NRS_SPEC_FIRST=<n>: followers behind the first trial of an iteration
 };
@@ -382,6 +403,8 @@ static LmRun lm_run(nrs_ctx* c, Engine* e) {
     r.n_spec_pcg = e->spec_pcg && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && d.sk_n == 0 && !(e->kft && e->kft->on) &&
                            !c->opt.profile && !c->env("NRS_CHECK_EVAL")
                        ? e->n_spec : 0;
+    r.rearm = d.plain && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && !d.coarse && d.sk_n == 0 && !(e->kft && e->kft->on) &&
+              !c->opt.profile && !c->env("NRS_CHECK_EVAL") && !c->env("NRS_NO_REARM");
     r.spec_first = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : 0;
     r.spec_first_pcg = c->env("NRS_SPEC_FIRST") ? r.spec_first : r.n_spec_pcg;
     return r;
@@ -407,8 +430,15 @@ struct TrialBatch {
         nrs_ctx* c = r.c;
         // trials of the batch nobody has asked for yet are not needed: their solves drain (the context's stream is idle here -- the
         // results before them have been read -- so the word is written at once)
-        for (int j = i_pend; j < n_pend && !c->env("NRS_SPEC_NO_ABORT"); ++j)
-            if (pend[j].set >= 0) NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.e->spec[pend[j].set].abort), pend[j].solve_id, 1, c->stream));
+        // PCG windows: one fill for the words of all sets, with the id of the last trial enqueued (Dev::abort: every trial up to it
+        // is over or not needed; later ones carry larger ids)
+        bool any = false;
+        for (int j = i_pend; j < n_pend && !c->env("NRS_SPEC_NO_ABORT"); ++j) {
+            if (pend[j].set < 0) continue;
+            if (r.n_spec_pcg > 0) any = true;
+            else NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.e->spec[pend[j].set].abort), pend[j].solve_id, 1, c->stream));
+        }
+        if (any) NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.e->spec[0].abort), r.e->spec_gen, r.e->n_spec, c->stream));
         for (int j = 0; j < n_pend; ++j)
             if (pend[j].set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_join[pend[j].set], 0));
         n_pend = i_pend = 0;
@@ -601,6 +631,8 @@ static int run_trial(const LmRun& r, TrialBatch& tb, int it, int qmax, double la
     // (flags[2] == 2: a bounded wait of the direct solver ran out -- a synchronisation fault, not a matrix that is not positive
     // definite: the factor and the assembly areas hold partial data, so this is an error, never a rejected trial)
     if (hf[2] == 2) return c->fail(NRS_ERR_HIP, "direct solve: a wait for another workgroup's result timed out (LM iteration %d, trial %d, solve set %d)", it, qmax, won);
+    // (the last publication was an evaluation's: it left the words of a finished solve cleared)
+    if (e->rearm && !direct) e->flags_clean[1 + won] = hf[0] != 0;
     out->chi_new = temp; out->scale = scale; out->early = early;
     out->status = hf[2]; out->inner = hf[1]; out->peek_it = hf[4];
     out->set = won; out->pit = pit;
@@ -615,6 +647,8 @@ int engine_optimize(nrs_ctx* c, Engine* e, int iters, int round, nrs_lm_trace* t
     NRS_HIP(c, hipSetDevice(c->device));
     Dev& d = e->d;
     const LmRun run = lm_run(c, e);
+    e->rearm = run.rearm;
+    for (bool& f : e->flags_clean) f = false;                      // (whatever touched the words since the last call: the first linearisation clears them)
     TrialBatch batch(run);
     double lam = -1, ni = 2;
     double chi_carry = 0;
@@ -904,6 +938,7 @@ int engine_debug_solve(nrs_ctx* c, Engine* e, const double* Hpp21, const double*
     int pit = 0;
     bool done = false;
     e->pred_iters = 0; e->pred_peek = 0;
+    e->rearm = false;
     NRS_TRY(pcg_begin(c, e, lam, &pit));
     NRS_TRY(pcg_advance(c, e, lam, 0, &pit, &done));
     if (iters) *iters = e->h_flags[1];

@@ -16,6 +16,7 @@ template <bool LIN>
 __global__ __launch_bounds__(BLK) void k_reproj(Dev P, const Pose* __restrict__ poses,
                                                 const double* __restrict__ xl) {
     __shared__ double lds[4 * 28];
+    if (!LIN && spec_aborted(P)) return;                           // (a discarded speculative trial)
     const int gi = xcd_tile(blockIdx.x, P.sh_ng);
     if (gi >= P.sh_ng) return;
     const int g = P.sh_g0 + gi;
@@ -910,17 +911,30 @@ __global__ __launch_bounds__(BLK) void k_chi_edges(Dev P, const double* __restri
 // fence, then the sequence number the host is polling for (h_flags[7]) -- a host round trip is then the
 // latency of that word (measured 9.5 us per {two launches + wait} against 15.2 us with
 // hipStreamSynchronize, tools/micro/sync_latency.hip).
-__device__ inline void publish_flags(const Dev& P, int seq, int zero = 0) {   // zero: leave the device words cleared for the next solve (directly solved engines: no memset launch per LM trial)
+// zero: leave the device words cleared for the next solve, no fill dispatch in front of it.  1: always (directly solved engines: every
+// trial and linearisation; a PCG window's linearisation -- no solve is in flight there).  2: only when the solve these words belong to
+// is over (flags[0]): a PCG trial that is evaluated at a peek may go on, and its later batches need its words (Engine::rearm).
+__device__ inline void publish_flags(const Dev& P, int seq, int zero = 0) {
+    const bool z = zero == 1 || (zero == 2 && P.flags[0] != 0);
 #pragma unroll
-    for (int k = 0; k < 7; ++k) { P.h_flags[k] = P.flags[k]; if (zero) P.flags[k] = 0; }
+    for (int k = 0; k < 7; ++k) { P.h_flags[k] = P.flags[k]; if (z) P.flags[k] = 0; }
     __threadfence_system();
     *reinterpret_cast<volatile int*>(P.h_flags + 7) = seq;
 }
 
 template <bool LIN>
-__global__ __launch_bounds__(BLK) void k_finalize(Dev P, int seq, int zero_flags) {
+__global__ __launch_bounds__(BLK) void k_finalize(Dev P, int seq, int zero_flags, FlagSets fs) {
     __shared__ double lds[4 * 3];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // a discarded speculative trial: nobody reads its sums; the publication alone keeps the set's sequence word in step
+    if (!LIN && spec_aborted(P)) {
+        if (tid == 0) publish_flags(P, seq, zero_flags);
+        return;
+    }
+    // the linearisation of a window whose evaluations re-arm the status words: the shadow sets' too (their trials have drained:
+    // the context's stream waited for them before this launch, and the next ones start behind it)
+    if (LIN && tid < 7)
+        for (int j = 0; j < fs.n; ++j) fs.p[j][tid] = 0;
     double chi = 0, md = 0, sc = 0;
     if (!LIN)
         for (int b = tid; b < P.n_vecblk; b += BLK) sc += P.part_apply[b];

@@ -236,7 +236,7 @@ __device__ __forceinline__ void spmv_f_body(const Dev& P, const double lam, cons
     }
     const double gamma0 = P.scal[SC_GAMMA0];
     // launches behind a converged solve are no-ops, and so are those of a discarded speculative trial
-    const int done_flag = P.flags[0] | (P.abort && *reinterpret_cast<const volatile int*>(P.abort) == P.abort_id);
+    const int done_flag = P.flags[0] | (P.abort && *reinterpret_cast<const volatile int*>(P.abort) >= P.abort_id);
     if (DF) {
         stage_rows_d(P, b, tid, P.uv3, lu, lgf, lgb);
         const int row0 = b * P.tile_rows, hb = P.halo_ptr[b], ns = P.halo_ns[b];
@@ -542,7 +542,7 @@ __global__ __launch_bounds__(BLK) void k_pcg_update(Dev P, double lam, int it, d
     const double* rp_in = (it & 1) ? P.rp2 : P.rp;   double* rp_out = (it & 1) ? P.rp : P.rp2;
     // Everything this launch reads is requested before the first dependent use (flag, scalars,
     // partials, the two rows of this thread): otherwise the launch is a chain of four round trips.
-    const int done_flag = P.flags[0] | (P.abort && *reinterpret_cast<const volatile int*>(P.abort) == P.abort_id);   // (a discarded speculative trial: no-op)
+    const int done_flag = P.flags[0] | (P.abort && *reinterpret_cast<const volatile int*>(P.abort) >= P.abort_id);   // (a discarded speculative trial: no-op)
     const double sc_gamma0 = P.scal[SC_GAMMA0];
     const double sc_slot0 = P.scal[(it & 1) ? SC_SLOT1 : SC_SLOT0], sc_slot1 = P.scal[((it & 1) ? SC_SLOT1 : SC_SLOT0) + 1];
     const int n_vec2 = (n_vecblk + 1) >> 1;

@@ -318,6 +318,10 @@ static void carve(ArenaPlan& A, Dev& d, bool has_X0, size_t nnz_s, size_t nnz_d,
         q.pose = A.get<Pose>(K); q.xl = A.get_rows<double>(3);
         q.part_apply = A.get<double>((size_t)d.n_vecblk); q.part_rchi = A.get<double>((size_t)d.n_groups); q.part_reg = A.get<double>(2 * (size_t)d.n_regblk);
         q.scal = A.get<double>(SC_N); q.flags = A.get<int>(8); q.abort = A.get<int>(1);
+        // (the sets' abort words are consecutive, so that one fill discards the trials of every set, TrialBatch::join: they all live
+        // in the first set's slot -- a slot is 256 bytes at the least -- and the later sets' slots stay unused: the arena's size is unchanged)
+        static_assert(SPEC_MAX * sizeof(int) <= 256, "the abort words share one slot");
+        q.abort = e->spec[0].abort + j;
         q.sk_part = q.sk_chi = nullptr;
         q.rv = q.uv3 = q.pv = q.sv = q.wv = q.Dinv = q.Hppinv = q.rp = q.rp2 = q.up = q.up2 = q.pp = q.sp = nullptr;
         q.part_spmv = q.part_ru = q.red = q.part_ec = nullptr;

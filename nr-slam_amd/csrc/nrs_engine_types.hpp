@@ -156,8 +156,10 @@ struct Dev {
     EcSpring* ec_sp; EcDamper* ec_dm; float* ec_w; double* part_ec;
     double* h_scal; int* h_flags;     // host-mapped mirrors, written by k_finalize / k_publish (no copy kernels)
     int* flags;                      // [0] pcg done, [1] pcg iterations, [2] nan flag
-    // speculative PCG trials (SpecSet): a trial on a shadow set is discarded once *abort == abort_id -- the set's queued PCG launches
-    // then return at once, as behind a converged solve (null: the engine's own trials, never discarded)
+    // speculative PCG trials (SpecSet): a trial on a shadow set is discarded once *abort >= abort_id -- the set's queued launches
+    // then return at once, as behind a converged solve (null: the engine's own trials, never discarded).  Ids grow with every
+    // speculative trial of the engine (Engine::spec_gen), so ONE value written to the words of all sets discards every trial
+    // enqueued so far and none that follows (TrialBatch::join)
     const int* abort; int abort_id;
     // shard window (multi-GPU): the layout is the whole problem on every rank, a rank
     // launches the row kernels over its own contiguous range of poses only.  Unsharded: the full ranges.
@@ -228,7 +230,7 @@ struct SpecSet {
     double *xv, *xp, *part_apply, *part_rchi, *part_reg, *scal;
     double *sk_part, *sk_chi;        // embedded mode (the context's skin buffer)
     int* flags;
-    int* abort;                      // id of the set's solve that is not needed any more (NdDev::abort, Dev::abort)
+    int* abort;                      // id of the set's solve that is not needed any more (NdDev::abort, Dev::abort); the sets' words are consecutive ints
     Pose* pose; double* xl;          // the trial state (swapped with the engine's on acceptance)
     double* h_scal; int* h_flags;    // mapped host mirrors of its own (nrs_ctx::pin_spec_*)
     // PCG trials (Engine::spec_pcg; null otherwise)
@@ -253,6 +255,12 @@ struct Engine {
     unsigned spec_run_at = 0;        // PCG windows: LM iterations (< 32) of the last optimize whose first trial was rejected (NRS_SPEC_FIRST)
     int spec_follow_first = 0;       // PCG windows: first-batch size of the last trial after a rejection (NRS_SPEC_FIRST: its followers' guess)
     SpecSet spec[SPEC_MAX];
+    // plain windows on the two-kernel PCG: the evaluation that publishes a set's status words leaves them cleared for the next solve
+    // (k_finalize; set per engine_optimize call).  flags_clean[1 + set] (set -1: the engine's own): the words are known to be zero,
+    // pcg_begin enqueues no fill; view_set: the set the engine is seen through (PcgSetView)
+    bool rearm = false;
+    bool flags_clean[1 + SPEC_MAX] = {false, false, false, false};
+    int view_set = -1;
     int pred_iters = 0;              // inner iterations of the last fully solved LM trial (sizes later batches)
     int pack_rows = 0;               // rows whose incidence records this engine holds (sharded: the rank's keyframe range)
     size_t arena_bytes = 0;          // device bytes carved for it
@@ -290,8 +298,11 @@ struct Engine {
 // a discarded speculative PCG trial (Dev::abort): its set's words may change under a running launch, so a workgroup decides once
 // (P.abort is a kernel argument: the branch is uniform, and launches of the engine's own trials do not pay for the barrier)
 __device__ inline bool spec_aborted(const Dev& P) {
-    return P.abort && __syncthreads_or(*reinterpret_cast<const volatile int*>(P.abort) == P.abort_id);
+    return P.abort && __syncthreads_or(*reinterpret_cast<const volatile int*>(P.abort) >= P.abort_id);
 }
+
+// the shadow sets' status words, for the linearisation's k_finalize to clear with the engine's own (Engine::rearm; n = 0: none)
+struct FlagSets { int* p[SPEC_MAX]; int n; };
 
 __device__ inline int xcd_tile(int b, int nb) {
     const int nb8 = (nb + 7) >> 3;
