@@ -602,13 +602,33 @@ int nrs_track_deform_solve_rg(nrs_ctx* ctx, const nrs_camera* cam, nrs_rgraph* g
  * cap_per_point: the edge lists are index for index those of nrs_dba_build_edges on the full lists, poses, points and trace are
  * bit for bit those of nrs_dba_solve_window on them (windows below the device packer's threshold copy the device-built lists back
  * and take the host packer).  nrs_dba_window_edges returns the resident window's lists in both cases.  A context with a communicator
- * is refused (NRS_ERR_INVALID): sharded and embedded forms of this call do not exist.
+ * is refused (NRS_ERR_INVALID): a sharded form of this call does not exist; the embedded form is nrs_dba_solve_window_rg_embedded.
  * nrs_dba_window_rg_stats: out = {distinct map points, final prefix length, GetEdges rounds, walks that ran off in round 1} of the
  * resident window this call made (NRS_ERR_STATE otherwise).  Debug switch: NRS_RG_MAX_CAP=<n> lowers the limit. */
 int nrs_dba_solve_window_rg(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* poses_qt /* in/out */, const int32_t* kf_rowptr,
                             const int32_t* kf_pt, float* lm_xyz /* in/out */, const float* lm_uv, nrs_rgraph* g, int32_t cap_per_point,
                             float scale, int32_t iters, nrs_lm_trace* trace);
 int nrs_dba_window_rg_stats(nrs_ctx* ctx, int64_t out[4]);
+
+/* The EMBEDDED window (nrs_dba_solve_window_embedded) served by the device-resident graph: nrs_dba_solve_window_rg with a node set.
+ * kf_pt are the graph's indices, obs_xyz / obs_uv are per observation, is_node is indexed by graph index and holds as many entries as
+ * the graph has capacity.  No neighbour array crosses the host.  On the device: the distinct map points of ALL observations, nodes or
+ * not, are listed; GetEdges runs for them at cap_per_point entries per point (<= 0: 64); a wave per observation walks its list there
+ * (csrc/nrs_engine_embwin.hpp k_ew_walk_wave): a node copy its springs and dampers between node copies, any other observation the walk
+ * that accepts its <= 11 node copies.  All three walks pass over a neighbour that is not a node copy of the keyframe without counting,
+ * so each of them can RUN OFF a truncated prefix under the rule above; rounds, limit, NRS_RG_MAX_CAP and the refusal at the limit
+ * (NRS_ERR_INVALID; the message names this call, the map point and the limit) are those of nrs_dba_solve_window_rg.  Then the shared
+ * construction of nrs_dba_solve_window_embedded (one copy back, the set-up of nrs_dba_upload_embedded), optimize(iters) and the download.
+ * Arguments are checked as for nrs_dba_solve_window_rg, and is_node must not be null; a NODE listed twice in one keyframe is
+ * NRS_ERR_INVALID; a context with a communicator is refused.  The result does not depend on cap_per_point: the lists are index for index
+ * and bit for bit those of nrs_dba_build_edges_embedded on the graph's full lists, poses, obs_xyz and trace those of
+ * nrs_dba_solve_window_embedded on them.  On return the window is resident as after nrs_dba_upload_embedded and obs_xyz is written as
+ * nrs_dba_solve_window_embedded writes it; nrs_dba_window_edges_embedded returns the lists (*on_device = 1) and nrs_dba_window_rg_stats
+ * the four statistics.  After an error nothing is resident and neither tap answers (NRS_ERR_STATE). */
+int nrs_dba_solve_window_rg_embedded(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_kf, double* poses_qt /* in/out */, const int32_t* kf_rowptr,
+                                     const int32_t* kf_pt, float* obs_xyz /* n_obs x 3, in/out */, const float* obs_uv, nrs_rgraph* g,
+                                     const uint8_t* is_node /* by graph index, capacity entries */, int32_t cap_per_point, float scale, int32_t iters,
+                                     nrs_lm_trace* trace);
 
 /* ---- N2: embedded deformation -- "points x graph nodes" as SURVEY.md 8(d) words it ------------------------------------
  * nrs_track_deform_solve_rg with a node set: f_node[i] != 0 marks the frame landmarks (among the TRACKED_WITH_3D ones) that carry

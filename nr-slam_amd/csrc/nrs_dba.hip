@@ -216,12 +216,13 @@ extern "C" int nrs_dba_solve_embedded(nrs_ctx* c, const nrs_camera* cam, int32_t
 // then the device-side problem construction and the solve.  Windows that do not qualify take nrs_dba_build_edges + nrs_dba_solve.
 // the keyframe side of the window (shared with the form that takes its lists from the resident graph: n_points = its capacity)
 static int window_validate_kf(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, const double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
-                              const float* lm_xyz, const float* lm_uv, int32_t n_points, const char* beyond, std::vector<int32_t>& lm_kf) {
+                              const float* lm_xyz, const float* lm_uv, int32_t n_points, const char* beyond, std::vector<int32_t>& lm_kf,
+                              const char* who = "nrs_dba_solve_window") {
     if (!cam || n_kf <= 0 || !poses_qt || !kf_rowptr || !kf_pt || !lm_xyz || !lm_uv || n_points <= 0)
-        return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window: bad argument");
+        return c->fail(NRS_ERR_INVALID, "%s: bad argument", who);
     if (cam->model != NRS_CAM_PINHOLE && cam->model != NRS_CAM_KB8) return c->fail(NRS_ERR_INVALID, "unknown camera model %d", cam->model);
     const int32_t n_lm = kf_rowptr[n_kf];
-    if (kf_rowptr[0] != 0 || n_lm <= 0) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window: empty window");
+    if (kf_rowptr[0] != 0 || n_lm <= 0) return c->fail(NRS_ERR_INVALID, "%s: empty window", who);
     for (int k = 0; k < n_kf; ++k) if (kf_rowptr[k + 1] < kf_rowptr[k]) return c->fail(NRS_ERR_INVALID, "kf_rowptr must be non-decreasing");
     for (int32_t i = 0; i < n_lm; ++i) if (kf_pt[i] < 0 || kf_pt[i] >= n_points) return c->fail(NRS_ERR_INVALID, beyond, kf_pt[i], n_points);
     lm_kf.resize(n_lm);
@@ -401,7 +402,7 @@ extern "C" int nrs_dba_solve_window_rg(nrs_ctx* c, const nrs_camera* cam, int32_
 
 extern "C" int nrs_dba_window_rg_stats(nrs_ctx* c, int64_t out[4]) {
     if (!c || !out) return NRS_ERR_INVALID;
-    if (!c->dba || !c->dba_rgwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_rg");
+    if (!c->dba || !c->dba_rgwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_rg or nrs_dba_solve_window_rg_embedded");
     for (int i = 0; i < 4; ++i) out[i] = c->dba_rgwin->stats[i];
     return NRS_OK;
 }
@@ -451,6 +452,20 @@ static int embwin_build_host(nrs_ctx* c, int32_t n_kf, const int32_t* kf_rowptr,
     return NRS_OK;
 }
 
+// optimize(iters) on the resident window c->dba_embwin describes, the download, and obs_xyz written through lm_obs / sk_obs
+static int embwin_solve(nrs_ctx* c, int32_t n_kf, double* poses_qt, float* obs_xyz, int32_t iters, nrs_lm_trace* trace) {
+    const EmbWindow& r = *c->dba_embwin;
+    NRS_TRY(nrs_dba_optimize(c, iters, trace));
+    std::vector<double> xyz((size_t)r.n_lm * 3), sk((size_t)r.n_skin * 3);
+    NRS_TRY(download(c, n_kf, poses_qt, xyz.data()));
+    if (r.n_skin > 0) NRS_TRY(engine_skin_positions(c, c->dba, sk.data()));
+    for (int32_t i = 0; i < r.n_lm; ++i)                             // OPT:1158 cast<float>, as nrs_dba_solve_embedded
+        for (int a = 0; a < 3; ++a) obs_xyz[3 * (size_t)r.lm_obs[i] + a] = (float)xyz[3 * (size_t)i + a];
+    for (int32_t i = 0; i < r.n_skin; ++i)
+        for (int a = 0; a < 3; ++a) obs_xyz[3 * (size_t)r.sk_obs[i] + a] = (float)sk[3 * (size_t)i + a];
+    return NRS_OK;
+}
+
 extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
                                              float* obs_xyz, const float* obs_uv, int32_t n_points, const uint8_t* is_node, const int32_t* nbr_rowptr,
                                              const int32_t* nbr_col, const float* nbr_w, const float* nbr_d0, const int32_t* nbr_status, float scale, int32_t iters,
@@ -483,16 +498,41 @@ extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, 
         NRS_TRY(nrs_dba_upload_embedded(c, cam, n_kf, poses_qt, w->n_lm, w->lm_xyz, w->lm_kf, w->lm_uv, w->n_sp, w->sp_ij, w->sp_d0, w->n_dm, w->dm_idx, w->dm_w, w->n_skin,
                                         w->sk_kf, w->sk_uv, w->sk_xyz, w->sk_node, w->sk_omega, scale));
     c->dba_embwin = w.release();
-    const EmbWindow& r = *c->dba_embwin;
     mark.synced("set-up");
-    NRS_TRY(nrs_dba_optimize(c, iters, trace));
-    std::vector<double> xyz((size_t)r.n_lm * 3), sk((size_t)r.n_skin * 3);
-    NRS_TRY(download(c, n_kf, poses_qt, xyz.data()));
-    if (r.n_skin > 0) NRS_TRY(engine_skin_positions(c, c->dba, sk.data()));
-    for (int32_t i = 0; i < r.n_lm; ++i)                             // OPT:1158 cast<float>, as nrs_dba_solve_embedded
-        for (int a = 0; a < 3; ++a) obs_xyz[3 * (size_t)r.lm_obs[i] + a] = (float)xyz[3 * (size_t)i + a];
-    for (int32_t i = 0; i < r.n_skin; ++i)
-        for (int a = 0; a < 3; ++a) obs_xyz[3 * (size_t)r.sk_obs[i] + a] = (float)sk[3 * (size_t)i + a];
+    NRS_TRY(embwin_solve(c, n_kf, poses_qt, obs_xyz, iters, trace));
+    mark("solve + download");
+    return NRS_OK;
+}
+
+// ---- the embedded window served by the device-resident graph (include/nrs.h nrs_dba_solve_window_rg_embedded): the marking, the
+// GetEdges rounds and the walks of nrs_dba_solve_window_rg over node copies and skinned observations (csrc/nrs_engine_embwin.hpp
+// engine_build_embedded_window_device_rg), then the set-up and the solve of nrs_dba_solve_window_embedded.
+extern "C" int nrs_dba_solve_window_rg_embedded(nrs_ctx* c, const nrs_camera* cam, int32_t n_kf, double* poses_qt, const int32_t* kf_rowptr, const int32_t* kf_pt,
+                                                float* obs_xyz, const float* obs_uv, nrs_rgraph* g, const uint8_t* is_node, int32_t cap_per_point, float scale,
+                                                int32_t iters, nrs_lm_trace* trace) {
+    if (!c) return NRS_ERR_INVALID;
+    dba_free(c);                                                     // whatever happens below, no earlier window stays resident
+    if (!g || rg_context(g) != c) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg_embedded: the graph is null or belongs to another context");
+    if (c->comm)
+        return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg_embedded: not available with a communicator on the context (sharded windows take nrs_dba_solve_window_embedded)");
+    std::vector<int32_t> obs_kf;
+    NRS_TRY(window_validate_kf(c, cam, n_kf, poses_qt, kf_rowptr, kf_pt, obs_xyz, obs_uv, rg_capacity(g),
+                               "nrs_dba_solve_window_rg_embedded: map point index %d is beyond the graph's capacity %d", obs_kf, "nrs_dba_solve_window_rg_embedded"));
+    if (!is_node) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg_embedded: bad argument");
+    StageTimer mark{c, "embedded window (rg)", false, 14};
+    std::unique_ptr<EmbWindow> w(new EmbWindow);
+    std::unique_ptr<RgWindow> rw(new RgWindow());
+    bool duplicate = false;
+    NRS_TRY(engine_build_embedded_window_device_rg(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, g, is_node,
+                                                   cap_per_point > 0 ? cap_per_point : RG_WINDOW_FIRST_CAP, w.get(), &duplicate, rw->stats));
+    if (duplicate) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg_embedded: a map point is listed twice in one keyframe");
+    mark("construction");
+    NRS_TRY(nrs_dba_upload_embedded(c, cam, n_kf, poses_qt, w->n_lm, w->lm_xyz, w->lm_kf, w->lm_uv, w->n_sp, w->sp_ij, w->sp_d0, w->n_dm, w->dm_idx, w->dm_w, w->n_skin,
+                                    w->sk_kf, w->sk_uv, w->sk_xyz, w->sk_node, w->sk_omega, scale));
+    c->dba_embwin = w.release();                                     // both taps answer: nrs_dba_window_edges_embedded and nrs_dba_window_rg_stats
+    c->dba_rgwin = rw.release();
+    mark.synced("set-up");
+    NRS_TRY(embwin_solve(c, n_kf, poses_qt, obs_xyz, iters, trace));
     mark("solve + download");
     return NRS_OK;
 }
@@ -501,7 +541,7 @@ extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, 
 extern "C" int nrs_dba_window_edges_embedded(nrs_ctx* c, int32_t* on_device, int32_t* n_lm, int32_t* lm_obs, int32_t* n_spring, int32_t* sp_ij, float* sp_d0,
                                              int32_t* n_damper, int32_t* dm_idx, float* dm_w, int32_t* n_skin, int32_t* sk_obs, int32_t* sk_node, double* sk_omega) {
     if (!c) return NRS_ERR_INVALID;
-    if (!c->dba || !c->dba_embwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_embedded");
+    if (!c->dba || !c->dba_embwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_embedded or nrs_dba_solve_window_rg_embedded");
     const EmbWindow& r = *c->dba_embwin;
     if (on_device) *on_device = r.on_device;
     if (n_lm) *n_lm = r.n_lm;
@@ -521,7 +561,7 @@ extern "C" int nrs_dba_window_edges_embedded(nrs_ctx* c, int32_t* on_device, int
 
 extern "C" int nrs_dba_window_slice_embedded(nrs_ctx* c, int64_t out[6]) {
     if (!c || !out) return NRS_ERR_INVALID;
-    if (!c->dba || !c->dba_embwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_embedded");
+    if (!c->dba || !c->dba_embwin) return c->fail(NRS_ERR_STATE, "the resident window was not made by nrs_dba_solve_window_embedded or nrs_dba_solve_window_rg_embedded");
     const EmbWindow& r = *c->dba_embwin;
     out[0] = r.sk_base; out[1] = r.sk_held; out[2] = r.k0; out[3] = r.k1; out[4] = (int64_t)r.bytes; out[5] = (int64_t)r.sk_bytes;
     return NRS_OK;

@@ -99,20 +99,26 @@ inline DpPlan<WO_COUNT> dp_winout_plan(size_t n_sp, size_t n_dm) {
     return dp_place(t, DP_MARGIN);
 }
 
-// embedded-lists scratch (pack_ws3, nrs_engine_embwin.hpp): n_obs observations of n_kf keyframes over n_points lists of nnz entries
+// embedded-lists scratch (pack_ws3, nrs_engine_embwin.hpp): n_obs observations of n_kf keyframes over n_points lists of nnz entries.
+// rg form (the resident graph serves the lists, as for the window-edge scratch): nnz = 0, n_points = the graph's capacity, and behind the
+// CSR form's arrays the mark / scan / id / list-row tables of the distinct map points, the two words of the ran-off flag, and per observation
+// the accepted count and the fp64 weight sum the count pass leaves for the emit pass
 enum DpEmbWin {
-    EL_pt, EL_k, EL_node, EL_nrp, EL_col, EL_st, EL_w, EL_d0, EL_xyz, EL_uv, EL_cur, EL_flag, EL_lm, EL_cs, EL_cd, EL_ck, EL_os, EL_od, EL_ok, EL_tot, EL_krp, EL_kfb, EL_tmp, EL_COUNT
+    EL_pt, EL_k, EL_node, EL_nrp, EL_col, EL_st, EL_w, EL_d0, EL_xyz, EL_uv, EL_cur, EL_flag, EL_lm, EL_cs, EL_cd, EL_ck, EL_os, EL_od, EL_ok, EL_tot, EL_krp, EL_kfb, EL_tmp,
+    EL_mark, EL_pos, EL_ids, EL_row, EL_ran, EL_skn, EL_sktot, EL_COUNT
 };
-struct DpEmbWinIn { size_t n_kf, n_obs, n_points, nnz, tmp_bytes; };
+struct DpEmbWinIn { size_t n_kf, n_obs, n_points, nnz, tmp_bytes; bool rg = false; };
 inline DpPlan<EL_COUNT> dp_embwin_plan(const DpEmbWinIn& n) {
     const size_t I = 4, F = 4;
     const DpArr t[EL_COUNT] = {
         {EL_pt, I, n.n_obs, true}, {EL_k, I, n.n_obs, true}, {EL_node, 1, n.n_points, true},
-        {EL_nrp, I, n.n_points + 1, true}, {EL_col, I, n.nnz, true}, {EL_st, I, n.nnz, true}, {EL_w, F, n.nnz, true}, {EL_d0, F, n.nnz, true},
+        {EL_nrp, I, n.rg ? 0 : n.n_points + 1, true}, {EL_col, I, n.nnz, true}, {EL_st, I, n.nnz, true}, {EL_w, F, n.nnz, true}, {EL_d0, F, n.nnz, true},
         {EL_xyz, F, 3 * n.n_obs, true}, {EL_uv, F, 2 * n.n_obs, true}, {EL_cur, I, n.n_kf * n.n_points, true},
         {EL_flag, I, n.n_obs + 1, true}, {EL_lm, I, n.n_obs + 1, true}, {EL_cs, I, n.n_obs + 1, true}, {EL_cd, I, n.n_obs + 1, true}, {EL_ck, I, n.n_obs + 1, true},
         {EL_os, I, n.n_obs + 1, true}, {EL_od, I, n.n_obs + 1, true}, {EL_ok, I, n.n_obs + 1, true},
-        {EL_tot, I, 8, true}, {EL_krp, I, n.n_kf + 1, true}, {EL_kfb, I, 2 * (n.n_kf + 1), true}, {EL_tmp, 1, n.tmp_bytes, true}};
+        {EL_tot, I, 8, true}, {EL_krp, I, n.n_kf + 1, true}, {EL_kfb, I, 2 * (n.n_kf + 1), true}, {EL_tmp, 1, n.tmp_bytes, true},
+        {EL_mark, I, n.n_points + 1, n.rg}, {EL_pos, I, n.n_points + 1, n.rg}, {EL_ids, I, n.n_points, n.rg}, {EL_row, I, n.n_points, n.rg}, {EL_ran, I, 2, n.rg},
+        {EL_skn, I, n.n_obs, n.rg}, {EL_sktot, 8, n.n_obs, n.rg}};
     return dp_place(t, DP_MARGIN);
 }
 

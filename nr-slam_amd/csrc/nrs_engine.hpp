@@ -121,6 +121,10 @@ void embwin_own_range(int n_kf, const int* kf_nodes, int world, int rank, int* k
 int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
                                         int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
                                         const int* nbr_status, bool own_only, EmbWindow* out, bool* duplicate);   // own_only: the share of the context's rank
+// the same lists served by the device-resident graph (include/nrs.h nrs_dba_solve_window_rg_embedded): is_node by graph index (capacity
+// entries), the prefix rounds and stats of engine_build_edges_device_rg
+int engine_build_embedded_window_device_rg(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
+                                           nrs_rgraph* g, const uint8_t* is_node, int cap_per_point, EmbWindow* out, bool* duplicate, int64_t stats[4]);
 bool engine_device_pack_ok(nrs_ctx* c, const EngineSpec& s);      // would engine_create build this window on the device?
 int engine_edges_to_host(nrs_ctx* c, Engine* e, int* sp_ij, float* sp_d0, int* dm_idx, float* dm_w);   // parity tap of the device edge builder    // checksums of the packed arrays (host- or device-built)       // solver order, caller vertex order
 // parity tap: (H + lam I) x = b for explicitly given blocks (one pose, M landmark rows, no regularisers) through

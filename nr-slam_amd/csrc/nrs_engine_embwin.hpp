@@ -28,9 +28,12 @@
 // copies, springs, dampers and sk_obs (4 bytes an observation: the caller's scatter goes through it) are emitted whole; sk_node,
 // sk_omega, sk_xyz, sk_uv and sk_kf -- 156 of the 160 bytes of a skinned observation -- for the slice only, at slot - sk_base.  The blob,
 // its device scratch and the pinned staging are sized from sk_held.
+// RESIDENT GRAPH.  nrs_dba_solve_window_rg_embedded takes the lists from the device-resident all-pairs graph instead of the caller: the same
+// walks by k_ew_walk_wave, a wave per observation over fixed-stride prefixes, in the doubling rounds of nrs_engine_winedges.hpp; every
+// stage around the two walk kernels is shared (ew_begin / ew_number / ew_finish).
 // The lists end up in pinned host memory of the context (one copy back), laid out by embwin_layout, and are handed to the set-up
-// nrs_dba_upload_embedded runs (nrs_engine_setup.hpp reads host arrays).  Plain C++ and vector stores only; the only atomic is the
-// atomicMax on `cur`, as in k_win_cur.
+// nrs_dba_upload_embedded runs (nrs_engine_setup.hpp reads host arrays).  Plain C++ and vector stores only; the atomics are the
+// atomicMax on `cur`, as in k_win_cur, and the two integer atomics of the ran-off flag in k_ew_walk_wave's count pass.
 #pragma once
 
 namespace nrs {
@@ -192,66 +195,172 @@ __global__ void k_ew_gather(int n_a, const int* __restrict__ obs_a, int n_b, con
     }
 }
 
-// Builds the lists of an embedded window on the device and copies them to the context's pinned staging (out's pointers: valid until
-// the next call).  The arguments are validated by the caller (indices in range, nnz > 0; own_only: a communicator of at most n_kf ranks).
-int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
-                                        int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
-                                        const int* nbr_status, bool own_only, EmbWindow* out, bool* duplicate) {
-    *duplicate = false;
-    const int n_obs = kf_rowptr[n_kf], nnz = nbr_rowptr[n_points];
+// ---- the same walks, a WAVE per observation, over either list layout (WinLists::range: the caller's CSR, or the fixed-stride prefixes the
+// resident graph leaves on the device -- nrs_dba_solve_window_rg_embedded).  A node copy's springs and dampers are win_walk itself on the
+// node-copy table.  The walk of a skinned observation steps through its list 64 contiguous entries at a time with win_walk's ballots and
+// its stop rule (the first BAD entry, or an entry that arrives with more than 10 accepted); it RAN OFF under the rule of
+// nrs_engine_winedges.hpp.  The fp64 weight sum is the host's: carried wave-uniformly from 0.0, the accepted lanes' weights widened and
+// added one by one in ascending lane order, chunk after chunk -- walk order, no tree.
+// WRITE = false: returns the number of accepted node copies (<= 11), their weight sum in *tot.  WRITE = true: the same walk again, the
+// accepted node copies and weight / *tot into row q of sk_node / sk_omega (an accepted entry's place is the number accepted before it).
+template <bool WRITE>
+__device__ inline int ew_skin_walk(const WinDev& W, int k, int p, int lane, double* tot, size_t q, int* sk_node, double* sk_omega, bool* ran_off) {
+#pragma clang fp contract(off)
+    const int* cur = W.cur + (size_t)k * W.n_points;
+    int64_t lo; int n; bool cut;
+    W.L.range(p, lo, n, cut);
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    int n_reg = 0;
+    bool broke = false;
+    double sum = 0.0;
+    for (int ch = 0; ch < n && !broke; ch += 64) {
+        const int a = ch + lane;
+        const bool valid = a < n;
+        const int64_t e = lo + a;
+        const int o = valid ? W.L.col[e] : 0;
+        const bool bad = valid && W.L.status[e] == NRS_GRAPH_BAD;
+        const bool pres = valid && cur[o] >= 0;                      // a node copy of this keyframe
+        const unsigned long long presm = __ballot(pres);
+        const int before = n_reg + __popcll(presm & below);         // accepted when the loop comes to this entry
+        const unsigned long long brkm = __ballot(valid && (bad || before > 10));
+        const int fb = brkm ? __ffsll((long long)brkm) - 1 : 64;    // the loop breaks at this lane's entry
+        const unsigned long long accm = fb < 64 ? presm & ((1ull << fb) - 1ull) : presm;
+        const bool acc = pres && lane < fb;
+        const float w = acc ? W.L.w[e] : 0.f;
+        if (!WRITE) {
+            for (unsigned long long m = accm; m; m &= m - 1ull) sum += (double)__shfl(w, __ffsll((long long)m) - 1);
+        } else if (acc) {
+            sk_node[11 * q + before] = cur[o];
+            sk_omega[11 * q + before] = (double)w / *tot;
+        }
+        n_reg += __popcll(accm);
+        broke = fb < 64;
+    }
+    if (!WRITE) *tot = sum;
+    *ran_off = cut && !broke && n_reg <= 10;
+    return n_reg;
+}
+
+// A wave per observation i; the arguments of k_ew_walk without the rank's slice.  EMIT = false: counts per observation, and in ran[0] the
+// walks that ran off, in ran[1] the smallest map point one of them started from (the flag of k_win_edges<false>: integer atomics of the
+// count pass only); of a skinned observation also the number of accepted node copies and their weight sum (sk_n / sk_tot: the last count
+// round's stand).  true: writes at the scanned offsets; a skinned observation's one walk divides by the saved sum.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_ew_walk_wave(WinDev W, int n_obs, const int* __restrict__ flag, const int* __restrict__ lm_of, int* cnt_s, int* cnt_d, int* cnt_k,
+                                                      const int* __restrict__ off_s, const int* __restrict__ off_d, const int* __restrict__ off_k, int* lm_obs, int* sp_ij,
+                                                      float* sp_d0, int* dm_idx, float* dm_w, int* sk_obs, int* sk_node, double* sk_omega, int* ran, int* sk_n, double* sk_tot) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n_obs) return;                                          // (wave-uniform)
+    const int k = W.lm_k[i], p = W.kf_pt[i];
+    bool off_end = false;
+    int n_ran = 0;
+    if (!flag[i]) {                                                  // a skinned observation
+        if (!EMIT) {
+            double tot = 0.0;
+            const int n_acc = ew_skin_walk<false>(W, k, p, lane, &tot, 0, nullptr, nullptr, &off_end);
+            if (lane == 0) {
+                cnt_s[i] = 0; cnt_d[i] = 0; cnt_k[i] = n_acc > 0 ? 1 : 0;
+                sk_n[i] = n_acc; sk_tot[i] = tot;
+                if (off_end) { atomicAdd(&ran[0], 1); atomicMin(&ran[1], p); }
+            }
+            return;
+        }
+        const int n_acc = sk_n[i];
+        if (n_acc == 0) return;                                      // (no node copy within reach: it constrains nothing)
+        double tot = sk_tot[i];
+        const size_t q = (size_t)off_k[i];
+        if (lane == 0) sk_obs[q] = i;
+        (void)ew_skin_walk<true>(W, k, p, lane, &tot, q, sk_node, sk_omega, &off_end);
+        if (lane >= n_acc && lane < 11) { sk_node[11 * q + lane] = -1; sk_omega[11 * q + lane] = 0.0; }
+        return;
+    }
+    const int l = lm_of[i];
+    if (EMIT && lane == 0) lm_obs[l] = i;
+    const int ns = win_walk<EMIT, false>(W, l, k, p, lane, EMIT ? off_s[i] : 0, sp_ij, sp_d0, dm_idx, dm_w, &off_end);
+    n_ran += off_end;
+    int nd = 0;
+    if (k + 1 < W.n_kf && W.cur[(size_t)(k + 1) * W.n_points + p] >= 0) {
+        nd = win_walk<EMIT, true>(W, l, k, p, lane, EMIT ? off_d[i] : 0, sp_ij, sp_d0, dm_idx, dm_w, &off_end);
+        n_ran += off_end;
+    }
+    if (!EMIT && lane == 0) {
+        cnt_s[i] = ns; cnt_d[i] = nd; cnt_k[i] = 0;
+        if (n_ran) { atomicAdd(&ran[0], n_ran); atomicMin(&ran[1], p); }
+    }
+}
+
+// ---- the construction in stages, shared by the CSR form (engine_build_embedded_window_device) and the resident-graph form
+// (engine_build_embedded_window_device_rg); the two differ in where the lists come from and in the kernel of the count and emit passes.
+struct EwBuild {                                                     // one build: its sizes and its scratch (pack_ws3, dp_embwin_plan)
+    int n_kf, n_obs, n_points;
+    size_t tmp_bytes;
+    DpPlan<EL_COUNT> P;
+    char* w3;
+    int *d_pt, *d_k, *d_cur, *d_flag, *d_lm, *d_cs, *d_cd, *d_ck, *d_os, *d_od, *d_ok, *d_tot, *d_krp, *d_kfb;
+    float *d_xyz, *d_uv;
+    uint8_t* d_node;
+    void* tmp;
+};
+// scratch, the uploads every form makes (the observations, their data, the node flags) and the cleared words
+static int ew_begin(nrs_ctx* c, EwBuild& B, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv, int n_points,
+                    const uint8_t* is_node, size_t nnz, bool rg, bool own_only) {
     hipStream_t st = c->stream;
-    NRS_HIP(c, hipSetDevice(c->device));
-    StageTimer mark{c, "embedded lists", true, 18, false};
-    const size_t tmp_bytes = win_scan_tmp_bytes(c, (size_t)n_obs + 1);
-    const auto P = dp_embwin_plan(DpEmbWinIn{(size_t)n_kf, (size_t)n_obs, (size_t)n_points, (size_t)nnz, tmp_bytes});
-    NRS_TRY(c->ensure(c->pack_ws3, P.need));
-    char* const w3 = c->pack_ws3.as<char>();
-    int *d_pt = P.at<int>(w3, EL_pt), *d_k = P.at<int>(w3, EL_k), *d_nrp = P.at<int>(w3, EL_nrp), *d_col = P.at<int>(w3, EL_col), *d_st = P.at<int>(w3, EL_st),
-        *d_cur = P.at<int>(w3, EL_cur), *d_flag = P.at<int>(w3, EL_flag), *d_lm = P.at<int>(w3, EL_lm), *d_cs = P.at<int>(w3, EL_cs), *d_cd = P.at<int>(w3, EL_cd),
-        *d_ck = P.at<int>(w3, EL_ck), *d_os = P.at<int>(w3, EL_os), *d_od = P.at<int>(w3, EL_od), *d_ok = P.at<int>(w3, EL_ok), *d_tot = P.at<int>(w3, EL_tot),
-        *d_krp = P.at<int>(w3, EL_krp), *d_kfb = P.at<int>(w3, EL_kfb);
-    float *d_w = P.at<float>(w3, EL_w), *d_d0 = P.at<float>(w3, EL_d0), *d_xyz = P.at<float>(w3, EL_xyz), *d_uv = P.at<float>(w3, EL_uv);
-    uint8_t* d_node = P.at<uint8_t>(w3, EL_node);
-    void* tmp = P.at<char>(w3, EL_tmp);
-    NRS_HIP(c, hipMemcpyAsync(d_pt, kf_pt, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_k, obs_kf, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_node, is_node, (size_t)n_points, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_nrp, nbr_rowptr, sizeof(int) * ((size_t)n_points + 1), hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_col, nbr_col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_st, nbr_status, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_w, nbr_w, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_d0, nbr_d0, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_xyz, obs_xyz, sizeof(float) * 3 * (size_t)n_obs, hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemcpyAsync(d_uv, obs_uv, sizeof(float) * 2 * (size_t)n_obs, hipMemcpyHostToDevice, st));
-    if (own_only) NRS_HIP(c, hipMemcpyAsync(d_krp, kf_rowptr, sizeof(int) * ((size_t)n_kf + 1), hipMemcpyHostToDevice, st));
-    NRS_HIP(c, hipMemsetAsync(d_cur, 0xFF, sizeof(int) * (size_t)n_kf * n_points, st));
-    NRS_HIP(c, hipMemsetAsync(d_flag + n_obs, 0, sizeof(int), st));
-    NRS_HIP(c, hipMemsetAsync(d_cs + n_obs, 0, sizeof(int), st));
-    NRS_HIP(c, hipMemsetAsync(d_cd + n_obs, 0, sizeof(int), st));
-    NRS_HIP(c, hipMemsetAsync(d_ck + n_obs, 0, sizeof(int), st));
-    NRS_HIP(c, hipMemsetAsync(d_tot, 0, sizeof(int) * 8, st));
-    mark("uploads");
-    const dim3 g((unsigned)((n_obs + 255) / 256)), b(256);
+    const int n_obs = kf_rowptr[n_kf];
+    B.n_kf = n_kf; B.n_obs = n_obs; B.n_points = n_points;
+    B.tmp_bytes = win_scan_tmp_bytes(c, (size_t)std::max(n_obs, rg ? n_points : 0) + 1);
+    B.P = dp_embwin_plan(DpEmbWinIn{(size_t)n_kf, (size_t)n_obs, (size_t)n_points, nnz, B.tmp_bytes, rg});
+    NRS_TRY(c->ensure(c->pack_ws3, B.P.need));
+    char* const w3 = B.w3 = c->pack_ws3.as<char>();
+    const auto& P = B.P;
+    B.d_pt = P.at<int>(w3, EL_pt); B.d_k = P.at<int>(w3, EL_k); B.d_cur = P.at<int>(w3, EL_cur); B.d_flag = P.at<int>(w3, EL_flag); B.d_lm = P.at<int>(w3, EL_lm);
+    B.d_cs = P.at<int>(w3, EL_cs); B.d_cd = P.at<int>(w3, EL_cd); B.d_ck = P.at<int>(w3, EL_ck); B.d_os = P.at<int>(w3, EL_os); B.d_od = P.at<int>(w3, EL_od);
+    B.d_ok = P.at<int>(w3, EL_ok); B.d_tot = P.at<int>(w3, EL_tot); B.d_krp = P.at<int>(w3, EL_krp); B.d_kfb = P.at<int>(w3, EL_kfb);
+    B.d_xyz = P.at<float>(w3, EL_xyz); B.d_uv = P.at<float>(w3, EL_uv);
+    B.d_node = P.at<uint8_t>(w3, EL_node);
+    B.tmp = P.at<char>(w3, EL_tmp);
+    NRS_HIP(c, hipMemcpyAsync(B.d_pt, kf_pt, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(B.d_k, obs_kf, sizeof(int) * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(B.d_node, is_node, (size_t)n_points, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(B.d_xyz, obs_xyz, sizeof(float) * 3 * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(B.d_uv, obs_uv, sizeof(float) * 2 * (size_t)n_obs, hipMemcpyHostToDevice, st));
+    if (own_only) NRS_HIP(c, hipMemcpyAsync(B.d_krp, kf_rowptr, sizeof(int) * ((size_t)n_kf + 1), hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemsetAsync(B.d_cur, 0xFF, sizeof(int) * (size_t)n_kf * n_points, st));
+    NRS_HIP(c, hipMemsetAsync(B.d_flag + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(B.d_cs + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(B.d_cd + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(B.d_ck + n_obs, 0, sizeof(int), st));
+    NRS_HIP(c, hipMemsetAsync(B.d_tot, 0, sizeof(int) * 8, st));
+    return NRS_OK;
+}
+// node-copy numbering, the table and the duplicate-node check (its word: d_tot[4])
+static int ew_number(nrs_ctx* c, const EwBuild& B) {
+    hipStream_t st = c->stream;
+    const dim3 g((unsigned)((B.n_obs + 255) / 256)), b(256);
+    hipLaunchKernelGGL(k_ew_flag, g, b, 0, st, B.n_obs, B.d_pt, B.d_node, B.d_flag);
+    size_t t2 = B.tmp_bytes;
+    NRS_HIP(c, rocprim::exclusive_scan(B.tmp, t2, B.d_flag, B.d_lm, 0, (size_t)B.n_obs + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(k_ew_cur, g, b, 0, st, B.n_obs, B.d_k, B.d_pt, B.d_flag, B.d_lm, B.n_points, B.d_cur);
+    hipLaunchKernelGGL(k_ew_check, g, b, 0, st, B.n_obs, B.d_k, B.d_pt, B.d_flag, B.d_lm, B.n_points, B.d_cur, B.d_tot);
+    return NRS_OK;
+}
+// Behind the count pass: the scans and the totals, the rank's share (own_only), the emit pass (`emit(dv)`: the form's kernel, writing into
+// the device blob dv is bound to), the gathers, one copy back into the pinned blob and out's pointers into it.
+template <class Emit>
+static int ew_finish(nrs_ctx* c, const EwBuild& B, const int* kf_rowptr, bool own_only, StageTimer& mark, Emit&& emit, EmbWindow* out, bool* duplicate) {
+    hipStream_t st = c->stream;
+    const int n_kf = B.n_kf, n_obs = B.n_obs;
+    const dim3 b(256);
     size_t t2;
-    // ---- node-copy numbering and the table
-    hipLaunchKernelGGL(k_ew_flag, g, b, 0, st, n_obs, d_pt, d_node, d_flag);
-    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_flag, d_lm, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(k_ew_cur, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur);
-    hipLaunchKernelGGL(k_ew_check, g, b, 0, st, n_obs, d_k, d_pt, d_flag, d_lm, n_points, d_cur, d_tot);
-    // ---- count pass, scans
-    WinDev wd{n_kf, n_points, nullptr, d_pt, d_k, WinLists{d_nrp, nullptr, nullptr, 0, d_col, d_st, d_w, d_d0}, d_cur};
-    hipLaunchKernelGGL((k_ew_walk<false>), g, b, 0, st, wd, n_obs, d_flag, d_lm, d_cs, d_cd, d_ck, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
-                       (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0, n_obs, 0);
-    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cs, d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
-    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_cd, d_od, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
-    t2 = tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(tmp, t2, d_ck, d_ok, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(k_ew_totals, dim3(1), dim3(64), 0, st, n_obs, d_lm, d_os, d_od, d_ok, d_tot);
-    if (own_only) hipLaunchKernelGGL(k_ew_kf_bounds, dim3((unsigned)((n_kf + 256) / 256)), b, 0, st, n_kf, d_krp, d_lm, d_ok, d_kfb);
+    t2 = B.tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(B.tmp, t2, B.d_cs, B.d_os, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = B.tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(B.tmp, t2, B.d_cd, B.d_od, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    t2 = B.tmp_bytes; NRS_HIP(c, rocprim::exclusive_scan(B.tmp, t2, B.d_ck, B.d_ok, 0, (size_t)n_obs + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(k_ew_totals, dim3(1), dim3(64), 0, st, n_obs, B.d_lm, B.d_os, B.d_od, B.d_ok, B.d_tot);
+    if (own_only) hipLaunchKernelGGL(k_ew_kf_bounds, dim3((unsigned)((n_kf + 256) / 256)), b, 0, st, n_kf, B.d_krp, B.d_lm, B.d_ok, B.d_kfb);
     NRS_HIP(c, hipGetLastError());
     int tot[5] = {0, 0, 0, 0, 0};
     std::vector<int> kfb(own_only ? 2 * ((size_t)n_kf + 1) : 0);
-    NRS_HIP(c, hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-    if (own_only) NRS_HIP(c, hipMemcpyAsync(kfb.data(), d_kfb, sizeof(int) * kfb.size(), hipMemcpyDeviceToHost, st));
+    NRS_HIP(c, hipMemcpyAsync(tot, B.d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    if (own_only) NRS_HIP(c, hipMemcpyAsync(kfb.data(), B.d_kfb, sizeof(int) * kfb.size(), hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipStreamSynchronize(st));
     mark("count + scans");
     if (tot[4]) { *duplicate = true; return NRS_OK; }
@@ -279,12 +388,11 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     }
     EmbWindow dv = *out;
     embwin_bind(&dv, c->pack_ws4.as<char>());
-    hipLaunchKernelGGL((k_ew_walk<true>), g, b, 0, st, wd, n_obs, d_flag, d_lm, (int*)nullptr, (int*)nullptr, (int*)nullptr, d_os, d_od, d_ok, dv.lm_obs, dv.sp_ij, dv.sp_d0,
-                       dv.dm_idx, dv.dm_w, dv.sk_obs, dv.sk_node, dv.sk_omega, kf_rowptr[dv.k0], kf_rowptr[dv.k1], dv.sk_base);
+    emit(dv);
     const int n_g = std::max(dv.n_lm, dv.sk_held);                   // (the gather of the skinned observations: the slice of sk_obs)
     if (n_g > 0)
-        hipLaunchKernelGGL(k_ew_gather, dim3((unsigned)((n_g + 255) / 256)), b, 0, st, dv.n_lm, dv.lm_obs, dv.sk_held, dv.sk_obs + dv.sk_base, d_xyz, d_uv, d_k, dv.lm_xyz,
-                           dv.lm_uv, dv.lm_kf, dv.sk_xyz, dv.sk_uv, dv.sk_kf);
+        hipLaunchKernelGGL(k_ew_gather, dim3((unsigned)((n_g + 255) / 256)), b, 0, st, dv.n_lm, dv.lm_obs, dv.sk_held, dv.sk_obs + dv.sk_base, B.d_xyz, B.d_uv, B.d_k,
+                           dv.lm_xyz, dv.lm_uv, dv.lm_kf, dv.sk_xyz, dv.sk_uv, dv.sk_kf);
     NRS_HIP(c, hipGetLastError());
     mark("emit + gathers");
     NRS_HIP(c, hipMemcpyAsync(c->embwin_pin, c->pack_ws4.as<char>(), bytes, hipMemcpyDeviceToHost, st));
@@ -293,6 +401,85 @@ int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowp
     embwin_bind(out, static_cast<char*>(c->embwin_pin));
     out->on_device = 1;
     return NRS_OK;
+}
+
+// Builds the lists of an embedded window on the device and copies them to the context's pinned staging (out's pointers: valid until
+// the next call).  The arguments are validated by the caller (indices in range, nnz > 0; own_only: a communicator of at most n_kf ranks).
+int engine_build_embedded_window_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
+                                        int n_points, const uint8_t* is_node, const int* nbr_rowptr, const int* nbr_col, const float* nbr_w, const float* nbr_d0,
+                                        const int* nbr_status, bool own_only, EmbWindow* out, bool* duplicate) {
+    *duplicate = false;
+    const int n_obs = kf_rowptr[n_kf], nnz = nbr_rowptr[n_points];
+    hipStream_t st = c->stream;
+    NRS_HIP(c, hipSetDevice(c->device));
+    StageTimer mark{c, "embedded lists", true, 18, false};
+    EwBuild B;
+    NRS_TRY(ew_begin(c, B, n_kf, kf_rowptr, kf_pt, obs_kf, obs_xyz, obs_uv, n_points, is_node, (size_t)nnz, false, own_only));
+    int *d_nrp = B.P.at<int>(B.w3, EL_nrp), *d_col = B.P.at<int>(B.w3, EL_col), *d_st = B.P.at<int>(B.w3, EL_st);
+    float *d_w = B.P.at<float>(B.w3, EL_w), *d_d0 = B.P.at<float>(B.w3, EL_d0);
+    NRS_HIP(c, hipMemcpyAsync(d_nrp, nbr_rowptr, sizeof(int) * ((size_t)n_points + 1), hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_col, nbr_col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_st, nbr_status, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_w, nbr_w, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    NRS_HIP(c, hipMemcpyAsync(d_d0, nbr_d0, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    mark("uploads");
+    NRS_TRY(ew_number(c, B));
+    // ---- count pass (a thread per observation), then the shared stages with k_ew_walk's emit pass
+    const dim3 g((unsigned)((n_obs + 255) / 256)), b(256);
+    WinDev wd{n_kf, n_points, nullptr, B.d_pt, B.d_k, WinLists{d_nrp, nullptr, nullptr, 0, d_col, d_st, d_w, d_d0}, B.d_cur};
+    hipLaunchKernelGGL((k_ew_walk<false>), g, b, 0, st, wd, n_obs, B.d_flag, B.d_lm, B.d_cs, B.d_cd, B.d_ck, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr,
+                       (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0, n_obs, 0);
+    return ew_finish(c, B, kf_rowptr, own_only, mark, [&](const EmbWindow& dv) {
+        hipLaunchKernelGGL((k_ew_walk<true>), g, b, 0, st, wd, n_obs, B.d_flag, B.d_lm, (int*)nullptr, (int*)nullptr, (int*)nullptr, B.d_os, B.d_od, B.d_ok, dv.lm_obs, dv.sp_ij,
+                           dv.sp_d0, dv.dm_idx, dv.dm_w, dv.sk_obs, dv.sk_node, dv.sk_omega, kf_rowptr[dv.k0], kf_rowptr[dv.k1], dv.sk_base);
+    }, out, duplicate);
+}
+
+// The same lists served by the device-resident all-pairs graph (include/nrs.h nrs_dba_solve_window_rg_embedded): no neighbour array is
+// uploaded.  The window's distinct map points -- over ALL observations, node or not: every walk starts from an observed point and follows
+// only points its keyframe observes -- are listed as for the plain window (k_win_mark, the scan, k_win_rows); GetEdges and the count pass
+// (k_ew_walk_wave<false>) run in win_count_rounds' doubling rounds; then the shared stages.  stats: as engine_build_edges_device_rg.
+int engine_build_embedded_window_device_rg(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* obs_kf, const float* obs_xyz, const float* obs_uv,
+                                           nrs_rgraph* g, const uint8_t* is_node, int cap_per_point, EmbWindow* out, bool* duplicate, int64_t stats[4]) {
+    *duplicate = false;
+    const int n_obs = kf_rowptr[n_kf], n_points = rg_capacity(g);
+    hipStream_t st = c->stream;
+    NRS_HIP(c, hipSetDevice(c->device));
+    StageTimer mark{c, "embedded lists (rg)", true, 18, false};
+    EwBuild B;
+    NRS_TRY(ew_begin(c, B, n_kf, kf_rowptr, kf_pt, obs_kf, obs_xyz, obs_uv, n_points, is_node, 0, true, false));
+    int *d_mark = B.P.at<int>(B.w3, EL_mark), *d_pos = B.P.at<int>(B.w3, EL_pos), *d_ids = B.P.at<int>(B.w3, EL_ids), *d_row = B.P.at<int>(B.w3, EL_row),
+        *d_ran = B.P.at<int>(B.w3, EL_ran), *d_skn = B.P.at<int>(B.w3, EL_skn);
+    double* d_sktot = B.P.at<double>(B.w3, EL_sktot);
+    mark("uploads");
+    NRS_TRY(ew_number(c, B));
+    // ---- the distinct map points, ascending, and the point -> list-row table
+    const dim3 g1((unsigned)((n_obs + 255) / 256)), gw((unsigned)((n_obs + 3) / 4)), b(256);       // a thread / a wave per observation
+    NRS_HIP(c, hipMemsetAsync(d_mark, 0, sizeof(int) * ((size_t)n_points + 1), st));
+    hipLaunchKernelGGL(k_win_mark, g1, b, 0, st, n_obs, B.d_pt, d_mark);
+    size_t t1 = B.tmp_bytes;
+    NRS_HIP(c, rocprim::exclusive_scan(B.tmp, t1, d_mark, d_pos, 0, (size_t)n_points + 1, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(k_win_rows, dim3((unsigned)((n_points + 255) / 256)), b, 0, st, n_points, d_mark, d_pos, d_ids, d_row);
+    NRS_HIP(c, hipGetLastError());
+    int n_ids = 0, dup = 0;
+    NRS_HIP(c, hipMemcpyAsync(&n_ids, d_pos + n_points, sizeof(int), hipMemcpyDeviceToHost, st));
+    NRS_HIP(c, hipMemcpyAsync(&dup, B.d_tot + 4, sizeof(int), hipMemcpyDeviceToHost, st));       // (ew_number's duplicate-node word: refused before any round)
+    NRS_HIP(c, hipStreamSynchronize(st));
+    if (dup) { *duplicate = true; return NRS_OK; }
+    if (n_ids <= 0 || n_ids > n_points) return c->fail(NRS_ERR_STATE, "nrs_dba_solve_window_rg_embedded: %d distinct map points", n_ids);
+    // ---- GetEdges and the count pass, in rounds
+    const int cap_max = rg_max_cap_per_point(g);
+    WinDev wd{n_kf, n_points, nullptr, B.d_pt, B.d_k, WinLists{nullptr, d_row, nullptr, 0, nullptr, nullptr, nullptr, nullptr}, B.d_cur};
+    WinRounds wr;
+    NRS_TRY(win_count_rounds(c, g, wd, n_ids, d_ids, d_row, d_ran, std::min(cap_per_point, cap_max), cap_max, "nrs_dba_solve_window_rg_embedded", [&] {
+        hipLaunchKernelGGL((k_ew_walk_wave<false>), gw, b, 0, st, wd, n_obs, B.d_flag, B.d_lm, B.d_cs, B.d_cd, B.d_ck, (const int*)nullptr, (const int*)nullptr,
+                           (const int*)nullptr, (int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, d_ran, d_skn, d_sktot);
+    }, &wr));
+    if (stats) { stats[0] = n_ids; stats[1] = wr.cap; stats[2] = wr.rounds; stats[3] = wr.ran_first; }
+    return ew_finish(c, B, kf_rowptr, false, mark, [&](const EmbWindow& dv) {
+        hipLaunchKernelGGL((k_ew_walk_wave<true>), gw, b, 0, st, wd, n_obs, B.d_flag, B.d_lm, (int*)nullptr, (int*)nullptr, (int*)nullptr, B.d_os, B.d_od, B.d_ok, dv.lm_obs,
+                           dv.sp_ij, dv.sp_d0, dv.dm_idx, dv.dm_w, dv.sk_obs, dv.sk_node, dv.sk_omega, (int*)nullptr, d_skn, d_sktot);
+    }, out, duplicate);
 }
 
 }  // namespace nrs

@@ -146,13 +146,14 @@ struct WinIn {
     int n_points; const int *nbr_rowptr, *nbr_col; const float *nbr_w, *nbr_d0; const int* nbr_status;
 };
 
-// The count pass (k_win_edges<false>: counts per landmark in cs / cd).  The CSR form (g = null): once.  The resident graph's lists: first
-// at `cap` entries per point, then at twice as many for as long as a walk runs off, cap_max at the most -- beyond it the run-off is an error.
+// The count pass of a window's walks (`count` launches it over wd: k_win_edges<false> here, k_ew_walk_wave<false> in nrs_engine_embwin.hpp;
+// both add the walks that ran off into d_flag).  The CSR form (g = null): once.  The resident graph's lists: first at `cap` entries per
+// point, then at twice as many for as long as a walk runs off, cap_max at the most -- beyond it the run-off is an error in the name of `who`.
 struct WinRounds { int cap, rounds, ran_first; };                  // the cap that served, the passes, the walks that ran off in the first
-static int win_count_rounds(nrs_ctx* c, nrs_rgraph* g, WinDev& wd, int n_lm, int n_ids, const int* d_ids, const int* d_row, int* d_cs, int* d_cd, int* d_flag,
-                            int cap, int cap_max, WinRounds* out) {
+template <class Count>
+static int win_count_rounds(nrs_ctx* c, nrs_rgraph* g, WinDev& wd, int n_ids, const int* d_ids, const int* d_row, int* d_flag, int cap, int cap_max, const char* who,
+                            Count&& count, WinRounds* out) {
     hipStream_t st = c->stream;
-    const dim3 gw((unsigned)((n_lm + 3) / 4)), b(256);               // a wave per landmark
     int rounds = 0, ran_first = 0;
     for (;;) {
         if (g) {
@@ -163,7 +164,7 @@ static int win_count_rounds(nrs_ctx* c, nrs_rgraph* g, WinDev& wd, int n_lm, int
         ++rounds;
         const int flag0[2] = {0, 0x7FFFFFFF};
         NRS_HIP(c, hipMemcpyAsync(d_flag, flag0, sizeof(flag0), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((k_win_edges<false>), gw, b, 0, st, wd, n_lm, d_cs, d_cd, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, d_flag);
+        count();
         NRS_HIP(c, hipGetLastError());
         int flag[2] = {0, 0};
         NRS_HIP(c, hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, st));     // the round's one flag read
@@ -171,7 +172,7 @@ static int win_count_rounds(nrs_ctx* c, nrs_rgraph* g, WinDev& wd, int n_lm, int
         if (flag[0] == 0) break;
         if (rounds == 1) ran_first = flag[0];
         if (cap >= cap_max)
-            return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_rg: the neighbour walk of map point %d ran off its list at the limit of %d entries per point", flag[1], cap_max);
+            return c->fail(NRS_ERR_INVALID, "%s: the neighbour walk of map point %d ran off its list at the limit of %d entries per point", who, flag[1], cap_max);
         cap = std::min(cap_max, 2 * cap);
     }
     *out = WinRounds{cap, rounds, ran_first};
@@ -225,7 +226,9 @@ static int win_edges_device(nrs_ctx* c, const WinIn& in, nrs_rgraph* g, int cap,
     const int cap_max = g ? rg_max_cap_per_point(g) : 0;
     WinDev wd{n_kf, n_points, d_rowptr, d_pt, d_k, WinLists{d_nrp, nullptr, nullptr, 0, d_col, d_st, d_w, d_d0}, d_cur};
     WinRounds wr;
-    NRS_TRY(win_count_rounds(c, g, wd, n_lm, n_ids, d_ids, d_row, d_cs, d_cd, d_flag, std::min(cap, cap_max), cap_max, &wr));
+    NRS_TRY(win_count_rounds(c, g, wd, n_ids, d_ids, d_row, d_flag, std::min(cap, cap_max), cap_max, "nrs_dba_solve_window_rg", [&] {
+        hipLaunchKernelGGL((k_win_edges<false>), gw, b, 0, st, wd, n_lm, d_cs, d_cd, (const int*)nullptr, (const int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr, d_flag);
+    }, &wr));
     if (stats) { stats[0] = n_ids; stats[1] = wr.cap; stats[2] = wr.rounds; stats[3] = wr.ran_first; }
     int tot[2] = {0, 0};
     size_t t2 = tmp_bytes;

@@ -118,11 +118,12 @@ static void check_winout(int tot0, int tot1) {
     check_plan(dp_winout_plan((size_t)tot0, (size_t)tot1), W4, asked, 4096);
 }
 
-// ---- embedded-lists scratch: engine_build_embedded_window_device's `layout`
-static void check_embwin(int n_kf, int n_obs, int n_points, int nnz, size_t tb) {
+// ---- embedded-lists scratch: the `layout` of engine_build_embedded_window_device; g: of engine_build_embedded_window_device_rg (the
+// resident graph serves the lists: nnz = 0, n_points = its capacity, the tables of the distinct map points behind the CSR form's arrays)
+static void check_embwin(int n_kf, int n_obs, int n_points, int nnz, size_t tb, bool g) {
     Old W;
     W.get<int>(EL_pt, n_obs); W.get<int>(EL_k, n_obs); W.get<uint8_t>(EL_node, n_points);
-    W.get<int>(EL_nrp, n_points + 1); W.get<int>(EL_col, nnz); W.get<int>(EL_st, nnz); W.get<float>(EL_w, nnz); W.get<float>(EL_d0, nnz);
+    W.get<int>(EL_nrp, g ? 0 : n_points + 1); W.get<int>(EL_col, nnz); W.get<int>(EL_st, nnz); W.get<float>(EL_w, nnz); W.get<float>(EL_d0, nnz);
     W.get<float>(EL_xyz, 3 * (size_t)n_obs); W.get<float>(EL_uv, 2 * (size_t)n_obs);
     W.get<int>(EL_cur, (size_t)n_kf * n_points);
     W.get<int>(EL_flag, (size_t)n_obs + 1); W.get<int>(EL_lm, (size_t)n_obs + 1);
@@ -131,7 +132,11 @@ static void check_embwin(int n_kf, int n_obs, int n_points, int nnz, size_t tb) 
     W.get<int>(EL_tot, 8);
     W.get<int>(EL_krp, (size_t)n_kf + 1); W.get<int>(EL_kfb, 2 * ((size_t)n_kf + 1));
     W.get<char>(EL_tmp, tb + 256);
-    const auto P = dp_embwin_plan(DpEmbWinIn{(size_t)n_kf, (size_t)n_obs, (size_t)n_points, (size_t)nnz, tb + 256});
+    if (g) {
+        W.get<int>(EL_mark, (size_t)n_points + 1); W.get<int>(EL_pos, (size_t)n_points + 1); W.get<int>(EL_ids, n_points); W.get<int>(EL_row, n_points);
+        W.get<int>(EL_ran, 2); W.get<int>(EL_skn, n_obs); W.get<double>(EL_sktot, n_obs);
+    }
+    const auto P = dp_embwin_plan(DpEmbWinIn{(size_t)n_kf, (size_t)n_obs, (size_t)n_points, (size_t)nnz, tb + 256, g});
     check_plan(P, W, W.off + 4096, 4096);
 }
 
@@ -153,7 +158,8 @@ static void check_plans() {
     for (const auto& x : we) {
         check_winedge(x.n_kf, x.n_lm, x.n_points, x.nnz, x.tb, false);
         check_winedge(x.n_kf, x.n_lm, x.n_points, 0, x.tb, true);
-        check_embwin(x.n_kf, x.n_lm, x.n_points, x.nnz, x.tb);
+        check_embwin(x.n_kf, x.n_lm, x.n_points, x.nnz, x.tb, false);
+        check_embwin(x.n_kf, x.n_lm, x.n_points, 0, x.tb, true);
     }
     const int wo[][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}, {600000, 550000}, {63, 65}, {BIG, BIG}};
     for (const auto& x : wo) check_winout(x[0], x[1]);

@@ -30,7 +30,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_comm_unique_id", "nrs_comm_init_rccl", "nrs_comm_rank", "nrs_shard_plan",
            "nrs_local_group_create", "nrs_local_group_destroy", "nrs_comm_init_local",
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
-           "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg", "nrs_dba_solve_window_rg", "nrs_dba_window_rg_stats",
+           "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg", "nrs_dba_solve_window_rg", "nrs_dba_window_rg_stats", "nrs_dba_solve_window_rg_embedded",
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
            "nrs_init_options_init", "nrs_init_essential",
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame"]
@@ -1013,6 +1013,27 @@ class Context:
                                                          None if node is None else _p(node, C.c_uint8), _p(rp, C.c_int32), _p(col, C.c_int32),
                                                          _p(w, C.c_float), _p(d0, C.c_float), _p(st, C.c_int32), C.c_float(scale), C.c_int32(iters),
                                                          C.byref(trace.c) if trace else None))
+        n = [C.c_int32(0) for _ in range(4)]
+        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, None, C.byref(n[0]), None, C.byref(n[1]), None, None, C.byref(n[2]), None, None, C.byref(n[3]), None, None, None))
+        self._n_kf, self._n_lm, self._n_sp, self._n_dm, self._n_skin = n_kf, n[0].value, n[1].value, n[2].value, n[3].value
+        return pq, xyz
+
+    def dba_solve_window_rg_embedded(self, cam, poses_qt, kf_points, obs_xyz, obs_uv, rg, is_node, scale, iters=5, trace=None, cap_per_point=0):
+        """The embedded window served by the device-resident graph rg (include/nrs.h nrs_dba_solve_window_rg_embedded): kf_points hold
+        map-point indices = the graph's, is_node is indexed by them and has rg.cap entries; cap_per_point as for dba_solve_window_rg.
+        Returns (poses_qt, obs_xyz) as dba_solve_window_embedded; dba_window_edges_embedded and dba_window_rg_stats answer afterwards."""
+        n_kf = len(kf_points)
+        kf_rowptr = np.zeros(n_kf + 1, np.int32)
+        kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
+        kf_pt = _i32(np.concatenate(kf_points))
+        pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
+        xyz = np.array(obs_xyz, np.float32).reshape(-1, 3).copy()
+        uv = _f32(obs_uv).reshape(-1, 2)
+        node = None if is_node is None else np.ascontiguousarray(is_node, np.uint8)
+        assert len(pq) == n_kf and len(xyz) == len(kf_pt) == len(uv) and (node is None or len(node) == rg.cap)
+        self._chk(self.lib.nrs_dba_solve_window_rg_embedded(self.h, C.byref(cam), C.c_int32(n_kf), _p(pq, C.c_double), _p(kf_rowptr, C.c_int32), _p(kf_pt, C.c_int32),
+                                                            _p(xyz, C.c_float), _p(uv, C.c_float), rg.h, None if node is None else _p(node, C.c_uint8),
+                                                            C.c_int32(cap_per_point), C.c_float(scale), C.c_int32(iters), C.byref(trace.c) if trace else None))
         n = [C.c_int32(0) for _ in range(4)]
         self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, None, C.byref(n[0]), None, C.byref(n[1]), None, None, C.byref(n[2]), None, None, C.byref(n[3]), None, None, None))
         self._n_kf, self._n_lm, self._n_sp, self._n_dm, self._n_skin = n_kf, n[0].value, n[1].value, n[2].value, n[3].value

@@ -90,7 +90,8 @@ class GpuBackend:
     def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None):
         """n_nodes > 0: EMBEDDED-DEFORMATION mode (include/nrs.h nrs_track_deform_solve_embedded; needs the dense graph): n_nodes map points
         (farthest-point sampling on the initial map, nrs_skin_select_nodes) carry the deformation vertices for the whole sequence, every
-        other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call)
+        other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call).  Mapping
+        keeps that node set (map points added later are always skinned) and keyframe BA runs as nrs_dba_solve_window_rg_embedded
         front: None / False = the images handed to the loop are grey and go to the tracker as they are, without masks (as before).  True or a
         list of filters (nrs.Context.front_configure) = the loop is handed the RAW frames of System::TrackImage (SLAM/system.cc:113-132): each
         is uploaded once through nrs_front_process, LK and Shi-Tomasi run on the resident grey image (tracking.cc:92,353,367) and
@@ -203,8 +204,10 @@ class GpuBackend:
     def track_deform(self, graph, map_pos, f_map, f_status, f_uv, f_pos, q, t, scale):
         self.last_trace = self.nrs.Trace(1024)
         if self.node_flag is not None:
-            r = self.ctx.track_deform_solve_embedded(self.cam, graph, map_pos, f_map, f_status, f_uv, f_pos, self.node_flag[np.asarray(f_map)], q, t, scale,
-                                                     self.last_trace, max(self.cap, 128))
+            n = len(map_pos)                                       # (as below: a grown graph's capacity runs ahead of the map)
+            r = self.ctx.track_deform_solve_embedded(self.cam, graph, map_pos if graph.cap == n else self._padded(map_pos), f_map, f_status, f_uv, f_pos,
+                                                     self.node_flag[np.asarray(f_map)], q, t, scale, self.last_trace, max(self.cap, 128))
+            r["map_pos"] = np.asarray(r["map_pos"])[:n]
             r["graph"] = graph
             return r
         if self.dense:
@@ -220,11 +223,17 @@ class GpuBackend:
     def map_frame(self, tb, deform_mag, rad_per_pixel, rigidity_th=0.004, min_track=5):
         return self.ctx.map_frame(self.cam, tb, deform_mag, rad_per_pixel, rigidity_th, min_track, -1)
 
-    # ---- keyframe mapping: LocalDeformableBundleAdjustment on the resident graph (include/nrs.h nrs_dba_solve_window_rg)
+    # ---- keyframe mapping: LocalDeformableBundleAdjustment on the resident graph (include/nrs.h nrs_dba_solve_window_rg; in the
+    # embedded-deformation mode nrs_dba_solve_window_rg_embedded with the sequence's node set: lm_xyz is then per observation -- node
+    # copies optimised, skinned observations at their skinned position, observations bound to no node unchanged)
     def dba_window(self, poses_qt, kf_points, lm_xyz, lm_uv, graph, scale, iters=5):
-        if not self.dense or self.node_flag is not None:
-            raise ValueError("keyframe BA needs the dense graph (dense_graph=True) without the embedded-deformation mode")
+        if not self.dense:
+            raise ValueError("keyframe BA needs the dense graph (dense_graph=True)")
         tr = self.nrs.Trace(256)
+        if self.node_flag is not None:
+            pq, xyz = self.ctx.dba_solve_window_rg_embedded(self.cam, poses_qt, kf_points, lm_xyz, lm_uv, graph, self._node_flag_at(graph.cap), scale, iters, tr, self.cap)
+            e = self.ctx.dba_window_edges_embedded()
+            return dict(poses_qt=pq, lm_xyz=xyz, n_spring=len(e["sp_d0"]), n_damper=len(e["dm_w"]), trials=len(tr.trials))
         pq, xyz = self.ctx.dba_solve_window_rg(self.cam, poses_qt, kf_points, lm_xyz, lm_uv, graph, scale, iters, tr, self.cap)
         ns, nd = self.ctx.dba_window_edge_counts()
         return dict(poses_qt=pq, lm_xyz=xyz, n_spring=ns, n_damper=nd, trials=len(tr.trials))
@@ -235,14 +244,20 @@ class GpuBackend:
         pos[:len(map_pos)] = map_pos
         return pos
 
+    def _node_flag_at(self, cap):
+        """the node flags by graph index, extended with zeros to `cap` entries"""
+        if len(self.node_flag) >= cap:
+            return self.node_flag
+        return np.concatenate([self.node_flag, np.zeros(cap - len(self.node_flag), np.uint8)])
+
     def grow_graph(self, graph, map_pos, new_ids, other_ids):
         """mapping.cc:238-256 on the dense graph, resized in amortised steps (doubled, not +1) to hold len(map_pos) points"""
         if not self.dense:
             raise ValueError("mapping needs the dense graph (dense_graph=True)")
-        if self.node_flag is not None:
-            raise ValueError("mapping is not available in the embedded-deformation mode")
         if len(map_pos) > self.rg.cap:
             self.rg.resize(max(len(map_pos), 2 * self.rg.cap))
+        if self.node_flag is not None:                             # the node set stays the one of the initial map: new map points are skinned
+            self.node_flag = self._node_flag_at(self.rg.cap)
         self.rg.grow(self._padded(map_pos), new_ids, other_ids)
         return self.rg
 

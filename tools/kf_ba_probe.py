@@ -2,7 +2,9 @@
 existing call costs: GetEdges of every point at capacity - 1 (nrs_rgraph_get_edges: the whole lists through the host), the CSR made of
 them, nrs_dba_solve_window.  A 5-keyframe window (every keyframe without its own third of the points) at about 1k and 5k map points, the
 graph all-pairs with one update.  Wall clock around the synchronous calls, medians after a warm-up; the two results are compared bit for bit.
-    python tools/kf_ba_probe.py [--reps 7] [--out profiles/kf_ba_probe.txt]"""
+--nodes M: the EMBEDDED window instead -- M nodes at 5000 points, M / 5 at 1000 (farthest-point sampling, nrs_synth.pick_nodes): the one call
+nrs_dba_solve_window_rg_embedded against the same GetEdges of every point at capacity - 1, its download and nrs_dba_solve_window_embedded.
+    python tools/kf_ba_probe.py [--reps 7] [--nodes M] [--out profiles/kf_ba_probe.txt]"""
 import argparse
 import os
 import sys
@@ -30,6 +32,7 @@ def median_ms(fn, reps, warm=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--nodes", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ctx = nrs.Context()
@@ -48,7 +51,12 @@ def main():
         cam = nrs.make_camera(p["model"], p["prm"])
         qt = np.concatenate([p["poses_q"], p["poses_t"]], 1)
 
+        m_nodes = max(1, a.nodes * n // 5000) if a.nodes > 0 else 0
+        flag = S.pick_nodes(p["scene"]["X0"], m_nodes) if m_nodes else None
+
         def one_call():
+            if flag is not None:
+                return ctx.dba_solve_window_rg_embedded(cam, qt, p["kf_points"], p["lm_xyz"], p["lm_uv"], rg, flag, p["scale"], 5)
             return ctx.dba_solve_window_rg(cam, qt, p["kf_points"], p["lm_xyz"], p["lm_uv"], rg, p["scale"], 5)
 
         def through_the_host():
@@ -57,14 +65,21 @@ def main():
             rowptr[1:] = np.cumsum(cnt)
             keep = np.arange(n - 1)[None, :] < cnt[:, None]
             g = dict(rowptr=rowptr, col=col[keep], w=w[keep], d0=d0[keep], status=st[keep])
+            if flag is not None:
+                return ctx.dba_solve_window_embedded(cam, qt, p["kf_points"], p["lm_xyz"], p["lm_uv"], flag, g, p["scale"], 5)
             return ctx.dba_solve_window(cam, qt, p["kf_points"], p["lm_xyz"], p["lm_uv"], g, p["scale"], 5)
 
         r1 = one_call()
         st = ctx.dba_window_rg_stats()
-        ns, nd = ctx.dba_window_edge_counts()
+        if flag is not None:
+            e = ctx.dba_window_edges_embedded()
+            ns, nd = len(e["sp_d0"]), len(e["dm_w"])
+            what = "%d observations (%d nodes: %d node copies, %d skinned)" % (sum(len(k) for k in p["kf_points"]), m_nodes, len(e["lm_obs"]), len(e["sk_obs"]))
+        else:
+            ns, nd = ctx.dba_window_edge_counts()
+            what = "%d landmarks" % sum(len(k) for k in p["kf_points"])
         m = median_ms(one_call, a.reps)
-        head = "%5d points x 5 keyframes: %d landmarks, %d springs, %d dampers; prefix %d after %d round(s)" % (
-            n, sum(len(k) for k in p["kf_points"]), ns, nd, st["cap"], st["rounds"])
+        head = "%5d points x 5 keyframes: %s, %d springs, %d dampers; prefix %d after %d round(s)" % (n, what, ns, nd, st["cap"], st["rounds"])
         try:
             r2 = through_the_host()
         except nrs.NrsError as e:                                  # (lists longer than GetEdges sorts in one workgroup's LDS on this device)
