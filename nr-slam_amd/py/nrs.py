@@ -938,15 +938,28 @@ class Context:
         self._chk(self.lib.nrs_dba_solve(*args, C.c_int32(iters), C.byref(trace.c) if trace else None))
         return self._keep[0].copy(), self._keep[1].copy()
 
-    def dba_solve_window(self, cam, poses_qt, kf_points, lm_xyz, lm_uv, graph, scale, iters=5, trace=None):
-        """LocalDeformableBundleAdjustment in one call (include/nrs.h nrs_dba_solve_window): edge construction included"""
+    def _window_args(self, poses_qt, kf_points, xyz, uv):
+        """what the four one-call window wrappers marshal alike: (n_kf, kf_rowptr, kf_pt, poses n_kf x 7, points as a fresh fp32 copy the call
+        writes into, uv), one row of xyz and of uv per entry of kf_points"""
         n_kf = len(kf_points)
         kf_rowptr = np.zeros(n_kf + 1, np.int32)
         kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
         kf_pt = _i32(np.concatenate(kf_points))
         pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
-        xyz = np.array(lm_xyz, np.float32).reshape(-1, 3).copy()
-        uv = _f32(lm_uv).reshape(-1, 2)
+        xyz = np.array(xyz, np.float32).reshape(-1, 3).copy()
+        uv = _f32(uv).reshape(-1, 2)
+        assert len(pq) == n_kf and len(xyz) == len(kf_pt) == len(uv)
+        return n_kf, kf_rowptr, kf_pt, pq, xyz, uv
+
+    def _embedded_window_counts(self, n_kf):
+        """the counts of the resident embedded window, for the downloads and taps that size their arrays by them"""
+        n = [C.c_int32(0) for _ in range(4)]
+        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, None, C.byref(n[0]), None, C.byref(n[1]), None, None, C.byref(n[2]), None, None, C.byref(n[3]), None, None, None))
+        self._n_kf, self._n_lm, self._n_sp, self._n_dm, self._n_skin = n_kf, n[0].value, n[1].value, n[2].value, n[3].value
+
+    def dba_solve_window(self, cam, poses_qt, kf_points, lm_xyz, lm_uv, graph, scale, iters=5, trace=None):
+        """LocalDeformableBundleAdjustment in one call (include/nrs.h nrs_dba_solve_window): edge construction included"""
+        n_kf, kf_rowptr, kf_pt, pq, xyz, uv = self._window_args(poses_qt, kf_points, lm_xyz, lm_uv)
         rp, col, w, d0, st = (_i32(graph["rowptr"]), _i32(graph["col"]), _f32(graph["w"]), _f32(graph["d0"]), _i32(graph["status"]))
         self._chk(self.lib.nrs_dba_solve_window(self.h, C.byref(cam), C.c_int32(n_kf), _p(pq, C.c_double), _p(kf_rowptr, C.c_int32), _p(kf_pt, C.c_int32),
                                                 _p(xyz, C.c_float), _p(uv, C.c_float), C.c_int32(len(rp) - 1), _p(rp, C.c_int32), _p(col, C.c_int32),
@@ -957,14 +970,7 @@ class Context:
     def dba_solve_window_rg(self, cam, poses_qt, kf_points, lm_xyz, lm_uv, rg, scale, iters=5, trace=None, cap_per_point=0):
         """LocalDeformableBundleAdjustment served by the device-resident graph rg (include/nrs.h nrs_dba_solve_window_rg): kf_points hold
         map-point indices = the graph's; cap_per_point = the first GetEdges prefix (<= 0: the library's default), doubled while a walk runs off"""
-        n_kf = len(kf_points)
-        kf_rowptr = np.zeros(n_kf + 1, np.int32)
-        kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
-        kf_pt = _i32(np.concatenate(kf_points))
-        pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
-        xyz = np.array(lm_xyz, np.float32).reshape(-1, 3).copy()
-        uv = _f32(lm_uv).reshape(-1, 2)
-        assert len(pq) == n_kf and len(xyz) == len(kf_pt) == len(uv)
+        n_kf, kf_rowptr, kf_pt, pq, xyz, uv = self._window_args(poses_qt, kf_points, lm_xyz, lm_uv)
         self._chk(self.lib.nrs_dba_solve_window_rg(self.h, C.byref(cam), C.c_int32(n_kf), _p(pq, C.c_double), _p(kf_rowptr, C.c_int32), _p(kf_pt, C.c_int32),
                                                    _p(xyz, C.c_float), _p(uv, C.c_float), rg.h, C.c_int32(cap_per_point), C.c_float(scale), C.c_int32(iters),
                                                    C.byref(trace.c) if trace else None))
@@ -998,13 +1004,7 @@ class Context:
         """The embedded window in one call (include/nrs.h nrs_dba_solve_window_embedded): the lists of dba_build_edges_embedded are built
         on the device.  obs_xyz / obs_uv are per observation (position in the concatenation of kf_points).  Returns (poses_qt, obs_xyz):
         node copies optimised, skinned observations at their skinned position, observations bound to nothing unchanged."""
-        n_kf = len(kf_points)
-        kf_rowptr = np.zeros(n_kf + 1, np.int32)
-        kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
-        kf_pt = _i32(np.concatenate(kf_points))
-        pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
-        xyz = np.array(obs_xyz, np.float32).reshape(-1, 3).copy()
-        uv = _f32(obs_uv).reshape(-1, 2)
+        n_kf, kf_rowptr, kf_pt, pq, xyz, uv = self._window_args(poses_qt, kf_points, obs_xyz, obs_uv)
         node = None if is_node is None else np.ascontiguousarray(is_node, np.uint8)
         rp, col, w, d0, st = (_i32(graph["rowptr"]), _i32(graph["col"]), _f32(graph["w"]), _f32(graph["d0"]), _i32(graph["status"]))
         assert node is None or len(node) == len(rp) - 1
@@ -1013,30 +1013,20 @@ class Context:
                                                          None if node is None else _p(node, C.c_uint8), _p(rp, C.c_int32), _p(col, C.c_int32),
                                                          _p(w, C.c_float), _p(d0, C.c_float), _p(st, C.c_int32), C.c_float(scale), C.c_int32(iters),
                                                          C.byref(trace.c) if trace else None))
-        n = [C.c_int32(0) for _ in range(4)]
-        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, None, C.byref(n[0]), None, C.byref(n[1]), None, None, C.byref(n[2]), None, None, C.byref(n[3]), None, None, None))
-        self._n_kf, self._n_lm, self._n_sp, self._n_dm, self._n_skin = n_kf, n[0].value, n[1].value, n[2].value, n[3].value
+        self._embedded_window_counts(n_kf)
         return pq, xyz
 
     def dba_solve_window_rg_embedded(self, cam, poses_qt, kf_points, obs_xyz, obs_uv, rg, is_node, scale, iters=5, trace=None, cap_per_point=0):
         """The embedded window served by the device-resident graph rg (include/nrs.h nrs_dba_solve_window_rg_embedded): kf_points hold
         map-point indices = the graph's, is_node is indexed by them and has rg.cap entries; cap_per_point as for dba_solve_window_rg.
         Returns (poses_qt, obs_xyz) as dba_solve_window_embedded; dba_window_edges_embedded and dba_window_rg_stats answer afterwards."""
-        n_kf = len(kf_points)
-        kf_rowptr = np.zeros(n_kf + 1, np.int32)
-        kf_rowptr[1:] = np.cumsum([len(k) for k in kf_points])
-        kf_pt = _i32(np.concatenate(kf_points))
-        pq = np.ascontiguousarray(np.array(poses_qt, np.float64)).reshape(-1, 7)
-        xyz = np.array(obs_xyz, np.float32).reshape(-1, 3).copy()
-        uv = _f32(obs_uv).reshape(-1, 2)
+        n_kf, kf_rowptr, kf_pt, pq, xyz, uv = self._window_args(poses_qt, kf_points, obs_xyz, obs_uv)
         node = None if is_node is None else np.ascontiguousarray(is_node, np.uint8)
-        assert len(pq) == n_kf and len(xyz) == len(kf_pt) == len(uv) and (node is None or len(node) == rg.cap)
+        assert node is None or len(node) == rg.cap
         self._chk(self.lib.nrs_dba_solve_window_rg_embedded(self.h, C.byref(cam), C.c_int32(n_kf), _p(pq, C.c_double), _p(kf_rowptr, C.c_int32), _p(kf_pt, C.c_int32),
                                                             _p(xyz, C.c_float), _p(uv, C.c_float), rg.h, None if node is None else _p(node, C.c_uint8),
                                                             C.c_int32(cap_per_point), C.c_float(scale), C.c_int32(iters), C.byref(trace.c) if trace else None))
-        n = [C.c_int32(0) for _ in range(4)]
-        self._chk(self.lib.nrs_dba_window_edges_embedded(self.h, None, C.byref(n[0]), None, C.byref(n[1]), None, None, C.byref(n[2]), None, None, C.byref(n[3]), None, None, None))
-        self._n_kf, self._n_lm, self._n_sp, self._n_dm, self._n_skin = n_kf, n[0].value, n[1].value, n[2].value, n[3].value
+        self._embedded_window_counts(n_kf)
         return pq, xyz
 
     def dba_window_edges_embedded(self):

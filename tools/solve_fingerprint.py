@@ -19,6 +19,8 @@ for p in (os.path.join(ROOT, "nr-slam_amd", "py"), os.path.join(ROOT, "oracle"),
 import nrs  # noqa: E402
 import nrs_synth as S  # noqa: E402
 import embedded_window_cases as W  # noqa: E402
+import window_rg_cases as RGW  # noqa: E402
+import window_rg_embedded_cases as RGE  # noqa: E402
 
 
 def digest(trials, *arrays):
@@ -139,6 +141,95 @@ def sharded_embedded(world, **opts):
     return run_ranks(group, world, rank_main, out)
 
 
+# ---- the one-call windows (nrs_dba_solve_window*): validation, edge lists, set-up, solve and download inside one entry point
+def _qt(p):
+    return np.concatenate([p["poses_q"], p["poses_t"]], 1)
+
+
+def one_call_window(**opts):
+    p = S.make_dba_problem(300, 4, 32)
+    c = nrs.Context(**opts)
+    tr = nrs.Trace()
+    pq, xyz = c.dba_solve_window(nrs.make_camera(p["model"], p["prm"]), _qt(p), p["kf_points"], p["lm_xyz"], p["lm_uv"], p["nbr"], p["scale"], 5, tr)
+    c.close()
+    return digest(tr.trials, pq, xyz)
+
+
+def _resident_graph(ctx, c):
+    """the device-resident graph of a tests/window_rg_cases.py case: all pairs at the start positions, one update at the perturbed ones"""
+    ids = np.arange(c["n"], dtype=np.int32)
+    rg = nrs.RGraph(ctx, c["n"], c["sigma"], RGW.STRETCH_TH)
+    rg.add_edges(c["X0"], ids, ids)
+    rg.update(c["X1"], ids)
+    return rg
+
+
+def one_call_window_rg(name, **opts):
+    """900x6_kb8: the smallest case of tests/window_rg_cases.py the device packer builds (4608 padded rows against its threshold of 2048);
+    120x3 (768 rows): the smallest that falls to the host packer with the device-built lists copied back"""
+    c = RGW.case(name)
+    p = c["p"]
+    ctx = nrs.Context(**opts)
+    rg = _resident_graph(ctx, c)
+    tr = nrs.Trace()
+    pq, xyz = ctx.dba_solve_window_rg(nrs.make_camera(p["model"], p["prm"]), _qt(p), p["kf_points"], p["lm_xyz"], p["lm_uv"], rg, p["scale"], 5, tr)
+    rg.close()
+    ctx.close()
+    return digest(tr.trials, pq, xyz)
+
+
+def one_call_embedded(**opts):
+    p, flag, nb = W.window(W.CASES[0], "nodes")
+    c = nrs.Context(**opts)
+    tr = nrs.Trace()
+    pq, xyz = c.dba_solve_window_embedded(nrs.make_camera(p["model"], p["prm"]), _qt(p), p["kf_points"], p["lm_xyz"], p["lm_uv"], flag, nb, p["scale"], 5, tr)
+    on_device = c.dba_window_edges_embedded()["on_device"]
+    c.close()
+    return digest(tr.trials, pq, xyz) + " on_device=%d" % on_device
+
+
+def one_call_embedded_rg(**opts):
+    c = RGE.case(RGE.CASES[0])
+    p = c["p"]
+    ctx = nrs.Context(**opts)
+    rg = _resident_graph(ctx, c)
+    tr = nrs.Trace()
+    pq, xyz = ctx.dba_solve_window_rg_embedded(nrs.make_camera(p["model"], p["prm"]), _qt(p), p["kf_points"], p["lm_xyz"], p["lm_uv"], rg, c["flag"], p["scale"], 5, tr)
+    rg.close()
+    ctx.close()
+    return digest(tr.trials, pq, xyz)
+
+
+def one_call_sharded(embedded, world=2, env=(), **opts):
+    """the one-call window (plain 300 x 4, or its 40-node embedded form) on `world` thread ranks; env: switches set for the ranks' contexts"""
+    if embedded:
+        p, flag, nb = W.window(W.CASES[0], "nodes")
+    else:
+        p = S.make_dba_problem(300, 4, 32)
+    cam = nrs.make_camera(p["model"], p["prm"])
+    group = nrs.LocalGroup(world)
+    out = [None] * world
+
+    def rank_main(r):
+        c = nrs.Context(**opts)
+        c.comm_init_local(group, r)
+        tr = nrs.Trace()
+        if embedded:
+            pq, xyz = c.dba_solve_window_embedded(cam, _qt(p), p["kf_points"], p["lm_xyz"], p["lm_uv"], flag, nb, p["scale"], 5, tr)
+            out[r] = digest(tr.trials, pq, xyz) + " on_device=%d" % c.dba_window_edges_embedded()["on_device"]
+        else:
+            pq, xyz = c.dba_solve_window(cam, _qt(p), p["kf_points"], p["lm_xyz"], p["lm_uv"], p["nbr"], p["scale"], 5, tr)
+            out[r] = digest(tr.trials, pq, xyz)
+        c.close()
+
+    for name in env:
+        nrs.debug_set(name, env[name])
+    try:
+        return run_ranks(group, world, rank_main, out)
+    finally:
+        nrs.debug_clear()
+
+
 CASES = [
     ("window 300x4 fused", lambda **o: window(300, 4, 32, **o)),
     ("window 500x5 NRS_NO_FUSED", lambda **o: window(500, 5, 34, {"NRS_NO_FUSED": "1"}, **o)),
@@ -151,6 +242,14 @@ CASES = [
     ("sharded 300x4, 2 thread ranks", lambda **o: sharded(2, **o)),
     ("sharded embedded 300x4x40, factorisation, 2 ranks", lambda **o: sharded_embedded(2, **o)),
     ("sharded embedded 300x4x40, factorisation, 3 ranks", lambda **o: sharded_embedded(3, **o)),
+    ("one call: window 300x4", one_call_window),
+    ("one call: rg window 900x6_kb8", lambda **o: one_call_window_rg("900x6_kb8", **o)),
+    ("one call: rg window 120x3", lambda **o: one_call_window_rg("120x3", **o)),
+    ("one call: embedded 300x4x40", one_call_embedded),
+    ("one call: rg embedded 900x6_kb8", one_call_embedded_rg),
+    ("one call, 2 thread ranks: window 300x4", lambda **o: one_call_sharded(False, **o)),
+    ("one call, 2 thread ranks: embedded 300x4x40", lambda **o: one_call_sharded(True, **o)),
+    ("one call, 2 ranks, SHARD_EMBWIN: embedded 300x4x40", lambda **o: one_call_sharded(True, env={"NRS_SHARD_EMBWIN_DEVICE": "1"}, **o)),
 ]
 
 if __name__ == "__main__":
