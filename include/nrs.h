@@ -155,14 +155,19 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  * a host application may call setenv at any time -- and a switch is changed through nrs_debug_set only (value NULL: unset;
  * takes effect at the next problem upload / solve of that context).  The host edge builders, which take no context, read
  * NRS_HOST_THREADS from a process-wide snapshot taken at their first call.
+ * Every switch is a row of ONE table (nr-slam_amd/csrc/nrs_switches.hpp: kind, default, group, one line on what it does); a name that is
+ * not in it is accepted and does nothing.  A switch written without a value below goes by presence: it is on when set to anything, "0"
+ * included (NRS_NO_LDS=0 turns the LDS path off); one written with a value is read with atoi / atof (garbage reads as 0).
  *   measurement   NRS_TIMING (stage marks of engine_create and the a2 driver on stderr), NRS_ND_DBG / NRS_ND_DBG2 (phase clocks of one
  *                 direct solve through nrs_debug_nd_solve), NRS_PEEK_DEBUG (gain ratios at the early-rejection looks)
  *   checks        NRS_POISON (fresh device allocations filled with NaN patterns), NRS_CHECK_EVAL / NRS_CHECK_FUSED / NRS_CHECK_CHI (an
  *                 evaluation / a single-launch PCG iteration / the carried chi2 computed twice and compared)
  *   direct solver NRS_ND=0|1, NRS_ND_MAX_ROWS, NRS_ND_NO_CACHE, NRS_ND_NO_COVER, NRS_ND_CHAIN, NRS_ND_LEVELS, NRS_ND_THREADS=256,
  *                 NRS_ND_STEP32=0, NRS_ND_BACK_FLAGS, NRS_ND_LEAF=<n>, NRS_ND_NO_SPLIT, NRS_ND_PLAN_PAR=<n>
- *   a2 LM trials  NRS_SPEC_TRIALS=<0..3> (shadow sets for the speculative trials of a run of rejections; 0: one at a time; read when an
- *                 engine is created), NRS_SPEC_FIXED=<n>, NRS_SPEC_FIRST=<n>, NRS_SPEC_NO_ABORT, NRS_SPEC_DBG
+ *   LM trials     NRS_SPEC_TRIALS=<0..3> (shadow sets for the speculative trials of a run of rejections; 0: one at a time; read when an
+ *                 engine is created), NRS_SPEC_FIXED=<n>, NRS_SPEC_FIRST=<n>, NRS_SPEC_NO_ABORT, NRS_SPEC_DBG, NRS_SPEC_MAX_ROWS=<n> (rows up
+ *                 to which a BA window on the two-kernel PCG carves shadow sets; default 2^18), NRS_NO_REARM (plain windows: the PCG's
+ *                 status words cleared by a fill per trial, not re-armed by k_finalize)
  *   PCG / packing NRS_NO_LDS, NRS_NO_FUSED, NRS_FUSED_MAX_ROWS=<n>, NRS_NO_COARSE, NRS_COARSE_MIN_TILES=<n>, NRS_NO_ONE_XCD, NRS_NO_ECD, NRS_HIER,
  *                 NRS_NO_PLAIN, NRS_NO_H4, NRS_RC=<0..3>, NRS_NT=0|1, NRS_DFORM, NRS_NO_EDGE_CHI, NRS_SELL_T=<lanes>, NRS_NO_MORTON,
  *                 NRS_NO_TILE_SORT, NRS_ONE_CLASS, NRS_TILE_CUT_PCT=<p>, NRS_HOST_PACK, NRS_HOST_THREADS=<n>, NRS_HOST_THREADS_SMALL=<n>,
@@ -175,6 +180,8 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_PO_NO_CACHE, NRS_PO_MULTI_GROUPS=<g>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR, NRS_RG_MAX_CAP=<n> (a lower limit on the GetEdges
  *                 prefix a call may ask for: the "ran off at the limit" refusals)
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
+ *   probes        (read by a `make PROBES=1` build only) NRS_LIN_DBG / NRS_SPMV_DBG / NRS_PCG_DBG (phase clocks of one lineariser /
+ *                 operator / single-launch PCG iteration launch), NRS_LIN_EXP=<n> (lineariser removal experiments: wrong results on purpose)
  * (what each selects: README.md "Debug switches"; the A/B tests drive every launch form through nrs_debug_set). */
 int nrs_debug_set(nrs_ctx* ctx, const char* name /* "NRS_..." */, const char* value /* NULL: unset */);
 void nrs_destroy(nrs_ctx* ctx);

@@ -9,6 +9,7 @@
 #include <utility>
 #include <vector>
 #include "../../include/nrs.h"
+#include "nrs_switches.hpp"
 
 namespace nrs {
 
@@ -42,25 +43,6 @@ struct Comm {
 };
 struct Arena { char* base = nullptr; size_t cap = 0, off = 0; };
 
-// Debug / A-B switches (include/nrs.h "Debug switches").  A context takes the NRS_* variables of the environment ONCE, when it is created
-// (plus NRS_DEBUG="NAME=VALUE,NAME2=VALUE2", names without the prefix), and is changed afterwards through nrs_debug_set only: the library
-// never looks at the environment again -- a host application may call setenv at any time, and no launch path pays for a lookup (the list
-// is empty in normal use).  Entry points without a context (the host edge builder) read a process-wide snapshot taken on first use.
-struct DebugOpts {
-    std::vector<std::pair<std::string, std::string>> kv;
-    const char* get(const char* name) const {
-        for (const auto& p : kv) if (p.first == name) return p.second.c_str();
-        return nullptr;
-    }
-    void set(const char* name, const char* value) {
-        for (size_t i = 0; i < kv.size(); ++i)
-            if (kv[i].first == name) { if (value) kv[i].second = value; else kv.erase(kv.begin() + i); return; }
-        if (value) kv.emplace_back(name, value);
-    }
-    void load_environment();         // nrs_pose_only.hip: the one place that reads the environment
-    static const DebugOpts& process();
-};
-
 }  // namespace nrs
 
 struct nrs_ctx {
@@ -68,8 +50,7 @@ struct nrs_ctx {
     hipStream_t stream = nullptr;
     hipDeviceProp_t prop;
     nrs_options opt;
-    nrs::DebugOpts dbg;              // debug / A-B switches: read once at nrs_create, changed by nrs_debug_set only
-    const char* env(const char* name) const { return dbg.get(name); }
+    nrs::DebugOpts dbg;              // debug / A-B switches (nrs_switches.hpp): read once at nrs_create, changed by nrs_debug_set only
     char err[512];
     nrs_profile prof;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -126,7 +107,7 @@ struct nrs_ctx {
         hipError_t e = hipMalloc(&b.p, want);
         if (e != hipSuccess) return fail(NRS_ERR_ALLOC, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
         b.cap = want;
-        if (env("NRS_POISON")) { (void)hipMemset(b.p, 0xFF, want); (void)hipDeviceSynchronize(); }     // (debug: a read of memory nobody wrote shows up as NaN)
+        if (dbg.is_set(nrs::SW_POISON)) { (void)hipMemset(b.p, 0xFF, want); (void)hipDeviceSynchronize(); }     // (debug: a read of memory nobody wrote shows up as NaN)
         return NRS_OK;
     }
     void release(nrs::DevBuf& b) {
@@ -156,7 +137,7 @@ namespace nrs {
 // (host stages are not waited for; synced() waits for one stage only); by_rank: the line names the rank of a sharded context.
 struct StageTimer {
     nrs_ctx* c; const char* who; bool sync; int width = 18; bool by_rank = sync;
-    bool on = c->env("NRS_TIMING") != nullptr;
+    bool on = c->dbg.is_set(SW_TIMING);
     std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
     void operator()(const char* what) {
         if (!on) return;

@@ -474,8 +474,8 @@ extern "C" int nrs_dba_solve_window_embedded(nrs_ctx* c, const nrs_camera* cam, 
     if (!is_node) return c->fail(NRS_ERR_INVALID, "nrs_dba_solve_window_embedded: bad argument");
     StageTimer mark{c, "embedded window", false, 14};
     std::unique_ptr<EmbWindow> w(new EmbWindow);
-    const nrs_dba::EmbwinBuilder by = nrs_dba::embwin_builder(c->comm != nullptr, c->comm ? c->comm->world : 1, n_kf, c->env("NRS_SHARD_EMBWIN_DEVICE") != nullptr,
-                                                              c->env("NRS_HOST_PACK") != nullptr, nbr_rowptr[n_points] > 0);
+    const nrs_dba::EmbwinBuilder by = nrs_dba::embwin_builder(c->comm != nullptr, c->comm ? c->comm->world : 1, n_kf, c->dbg.is_set(SW_SHARD_EMBWIN_DEVICE),
+                                                              c->dbg.is_set(SW_HOST_PACK), nbr_rowptr[n_points] > 0);
     if (by.device) {
         bool duplicate = false;
         int rc = engine_build_embedded_window_device(c, n_kf, kf_rowptr, kf_pt, obs_kf.data(), obs_xyz, obs_uv, n_points, is_node, nbr_rowptr, nbr_col, nbr_w, nbr_d0,

@@ -256,7 +256,7 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
     // keyframe-block factorisation: the first step's residual is tested on its own before M^-1 is applied again (k_kft_rnorm,
     // nrs_engine_kft.hpp): the batch that holds iteration 0 ends with it, and u = M^-1 r is enqueued only when the solve goes on
     const bool kft_on = e->kft && e->kft->on;
-    const bool kft_lazy = kft_on && it == 0 && stop > 0 && !c->opt.profile && !c->env("NRS_KFT_NO_RESIDUAL_TEST");
+    const bool kft_lazy = kft_on && it == 0 && stop > 0 && !c->opt.profile && !c->dbg.is_set(SW_KFT_NO_RESIDUAL_TEST);
     if (kft_lazy) stop = 1;
     if (kft_on && e->kft->apply_pending) {
         NRS_TRY(kft_apply(c, e->kft, d.rv, ((it - 1) & 1) ? d.rp : d.rp2, d.uv3, ((it - 1) & 1) ? d.up : d.up2, d.flags));
@@ -269,14 +269,14 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
             // frames of <= 32 tiles: every tile on a workgroup of ONE XCD (workgroups are dealt to the XCDs round-robin; the other seven
             // of every eight return at once) -- the vectors then stay in one L2 instead of being written through eight: 19.0 -> 18.0 us
             // per iteration all-in at 543 points, 22.8 -> 21.9 at 1013.  Placement only: the result does not depend on where a workgroup lands.
-            const bool one_xcd_off = c->env("NRS_NO_ONE_XCD") != nullptr;
+            const bool one_xcd_off = c->dbg.is_set(SW_NO_ONE_XCD);
             const bool one_xcd = !one_xcd_off && d.n_regblk <= 32;
             Dev d1 = d;
             d1.one_xcd = one_xcd ? 1 : 0;
             const Dev& d = d1;
             const dim3 g(one_xcd ? 8 * d.n_regblk : ((d.n_regblk + 7) / 8) * 8), bb(BLK);
             const size_t shm = sizeof(double) * (6 * (size_t)(d.tile_rows + d.max_halo) + (d.coarse ? 12 * (size_t)d.n_regblk + 16 * CO_MAX : 0));
-            if (c->env("NRS_CHECK_FUSED") && !d.coarse && d.T == 8) { NRS_TRY(check_fused_launch(c, d, g, shm, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub)); continue; }
+            if (c->dbg.is_set(SW_CHECK_FUSED) && !d.coarse && d.T == 8) { NRS_TRY(check_fused_launch(c, d, g, shm, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub)); continue; }
             NRS_TRY(with_lanes(c, d.T, [&](auto L) {
                 constexpr int T = decltype(L)::value;
                 hipLaunchKernelGGL((d.coarse ? k_pcg_fused<T, true> : k_pcg_fused<T, false>), g, bb, shm, c->stream, d, lam, it, tol2, PEEK_RTOL * PEEK_RTOL, pub);
@@ -318,7 +318,7 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
             if (!skin_op_done) hipLaunchKernelGGL(k_skin_op, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, it);
             // the row pass: inside k_pcg_update<true> (for the rows it updates) unless the update is the generic kernel's (a sharded
             // window reduces hierarchically, k_reduce_partials + all-reduce, and still takes the fused form: the update reads red)
-            skin_rows_fused = (d.sh_on || !d.hier) && !d.ecd && !c->env("NRS_SKIN_ROWS_OWN_LAUNCH");
+            skin_rows_fused = (d.sh_on || !d.hier) && !d.ecd && !c->dbg.is_set(SW_SKIN_ROWS_OWN_LAUNCH);
             if (!skin_rows_fused) hipLaunchKernelGGL(k_skin_op_rows, dim3(d.sh_nvb * BLK / SK_RPB), dim3(BLK), 0, c->stream, d);
         }
         if (d.sh_on) {
@@ -387,13 +387,13 @@ struct LmRun {
 static LmRun lm_run(nrs_ctx* c, Engine* e) {
     const Dev& d = e->d;
     LmRun r{c, e};
-    r.peek_debug = c->env("NRS_PEEK_DEBUG") != nullptr;
-    r.check_chi = c->env("NRS_CHECK_CHI") != nullptr;
-    r.spec_dbg = c->env("NRS_SPEC_DBG") != nullptr;
+    r.peek_debug = c->dbg.is_set(SW_PEEK_DEBUG);
+    r.check_chi = c->dbg.is_set(SW_CHECK_CHI);
+    r.spec_dbg = c->dbg.is_set(SW_SPEC_DBG);
     // Speculative trials (directly solved single-pose engines; nrs_engine_types.hpp SpecSet): after a rejected trial the rest of the run
     // goes out as a batch -- the trial g2o would try next on the engine's own arrays, the ones after it (lam x ni, then x 2 ni, ...) on
     // the shadow sets -- and the results are read in order.  NRS_SPEC_TRIALS=0: one at a time (the same trials, the same bits).
-    r.n_spec = e->nd && e->nd->on && d.K == 1 && !d.sh_on && !d.ec_on && !c->opt.profile && !c->env("NRS_CHECK_EVAL") &&
+    r.n_spec = e->nd && e->nd->on && d.K == 1 && !d.sh_on && !d.ec_on && !c->opt.profile && !c->dbg.is_set(SW_CHECK_EVAL) &&
                        e->nd->S().chain_from >= e->nd->S().plan.n_levels       // (the chained factorisation's workgroups wait for each other too: one such launch at a time)
                    ? std::min(e->n_spec, e->nd->S().n_alt) : 0;
     // ... and BA windows on the two-kernel PCG (PcgSetView): a trial of the batch is its pcg_begin, its first PCG batch and its
@@ -401,12 +401,12 @@ static LmRun lm_run(nrs_ctx* c, Engine* e) {
     // The first batch's size depends on the milestone the trials before it reached (first_batch): a trial whose size the host does
     // not confirm when it gets to it is discarded with the rest of the batch and solved again on the engine's own arrays.
     r.n_spec_pcg = e->spec_pcg && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && d.sk_n == 0 && !(e->kft && e->kft->on) &&
-                           !c->opt.profile && !c->env("NRS_CHECK_EVAL")
+                           !c->opt.profile && !c->dbg.is_set(SW_CHECK_EVAL)
                        ? e->n_spec : 0;
     r.rearm = d.plain && !(e->nd && e->nd->on) && !d.sh_on && !d.fused && !d.coarse && d.sk_n == 0 && !(e->kft && e->kft->on) &&
-              !c->opt.profile && !c->env("NRS_CHECK_EVAL") && !c->env("NRS_NO_REARM");
-    r.spec_first = c->env("NRS_SPEC_FIRST") ? atoi(c->env("NRS_SPEC_FIRST")) : 0;
-    r.spec_first_pcg = c->env("NRS_SPEC_FIRST") ? r.spec_first : r.n_spec_pcg;
+              !c->opt.profile && !c->dbg.is_set(SW_CHECK_EVAL) && !c->dbg.is_set(SW_NO_REARM);
+    r.spec_first = c->dbg.int_of(SW_SPEC_FIRST);
+    r.spec_first_pcg = c->dbg.is_set(SW_SPEC_FIRST) ? r.spec_first : r.n_spec_pcg;
     return r;
 }
 
@@ -433,7 +433,7 @@ struct TrialBatch {
         // PCG windows: one fill for the words of all sets, with the id of the last trial enqueued (Dev::abort: every trial up to it
         // is over or not needed; later ones carry larger ids)
         bool any = false;
-        for (int j = i_pend; j < n_pend && !c->env("NRS_SPEC_NO_ABORT"); ++j) {
+        for (int j = i_pend; j < n_pend && !c->dbg.is_set(SW_SPEC_NO_ABORT); ++j) {
             if (pend[j].set < 0) continue;
             if (r.n_spec_pcg > 0) any = true;
             else NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.e->spec[pend[j].set].abort), pend[j].solve_id, 1, c->stream));
@@ -497,7 +497,7 @@ struct TrialBatch {
         int nb = 1;
         if (qmax == 0 && r.spec_first > 0) nb = std::min(1 + r.n_spec, 1 + r.spec_first);   // (experiment: NRS_SPEC_FIRST=<n> further trials behind the first of an iteration)
         if (qmax >= 1) nb = std::min(std::min(std::max(c->spec_run - qmax + 1, 2), 1 + r.n_spec), 10 - qmax);
-        if (const char* f = c->env("NRS_SPEC_FIXED")) { if (qmax >= 1) nb = std::min(std::min(std::max(1, atoi(f)), 1 + r.n_spec), 10 - qmax); }
+        if (c->dbg.is_set(SW_SPEC_FIXED) && qmax >= 1) nb = std::min(std::min(std::max(1, c->dbg.int_of(SW_SPEC_FIXED)), 1 + r.n_spec), 10 - qmax);
         if (nb > 1) NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
         double l = lam, n = ni;
         const auto tq0 = std::chrono::steady_clock::now();
@@ -527,7 +527,7 @@ static int eval_trial(nrs_ctx* c, Engine* e, double lam) {
     if (d.sh_on) NRS_TRY(c->comm->exchange(c, d.xl[trial], e->halo, c->stream));   // the regularisers read the neighbours' boundary keyframes
     NRS_TRY(evaluate<false>(c, e, trial, one_pose));
     NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));
-    if (c->env("NRS_CHECK_EVAL")) {                                // (debug: the same evaluation again on the same state must give the same bits)
+    if (c->dbg.is_set(SW_CHECK_EVAL)) {                                // (debug: the same evaluation again on the same state must give the same bits)
         const double chi1 = e->h_scal[SC_CHI], sc1 = e->h_scal[SC_SCALE];
         NRS_TRY(evaluate<false>(c, e, trial, false));
         NRS_TRY(wait_published(c, e->h_flags, c->seq, c->stream));

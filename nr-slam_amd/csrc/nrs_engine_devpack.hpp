@@ -34,8 +34,7 @@
 namespace nrs {
 
 static bool devpack_eligible(nrs_ctx* c, const EngineSpec& s, int n_pad_rows) {
-    if (c->env("NRS_HOST_PACK") || c->env("NRS_NO_PLAIN") || c->env("NRS_NO_LDS") || c->env("NRS_DFORM") || c->env("NRS_NO_EDGE_CHI") || c->env("NRS_NO_FUSED") ||
-        c->env("NRS_SELL_T") || c->env("NRS_FUSED_MAX_ROWS") || c->env("NRS_TILE_CUT_PCT") || c->env("NRS_HIER") || c->env("NRS_NO_ECD") || c->env("NRS_SHARD_PACK_ALL"))
+    if (c->dbg.forces_host_pack())                                 // (a switch marked HOST_PACK in nrs_switches.hpp is set)
         return false;                                                // (test / A-B switches are honoured by the host path)
     // a communicator: one window over its ranks, with a rank count the sharded path accepts (engine_create has refused the others)
     if (c->comm && (!s.shard || c->comm->world > 8 || s.K < c->comm->world)) return false;
@@ -110,12 +109,12 @@ int DeviceBuild::uploads() {
 // ---- row layout: Morton order inside a keyframe, then (damper, spring) incidence counts inside a tile
 int DeviceBuild::row_layout() {
     hipLaunchKernelGGL(k_dp_minmax, dim3(1), dim3(1024), 0, st, M, r_x, mm);
-    hipLaunchKernelGGL(k_dp_morton, nb(M), dim3(256), 0, st, M, r_x, mm, c->env("NRS_NO_MORTON") ? 0 : 1, code_a, val_a);
+    hipLaunchKernelGGL(k_dp_morton, nb(M), dim3(256), 0, st, M, r_x, mm, c->dbg.is_set(SW_NO_MORTON) ? 0 : 1, code_a, val_a);
     size_t tb = tmp_bytes;
     NRS_HIP(c, rocprim::segmented_radix_sort_pairs(tmp, tb, code_a, code_b, val_a, val_b, (size_t)M, (unsigned)K, d_pose_ptr, d_pose_ptr + 1, 0, 64, st));
     NRS_HIP(c, hipMemsetAsync(row_v, 0xFF, sizeof(int) * (size_t)n_rows, st));
     hipLaunchKernelGGL(k_dp_rows0, nb(M), dim3(256), 0, st, M, val_b, r_kf, d_pose_ptr, d_pgp, vrow, row_v);
-    if (!c->env("NRS_NO_TILE_SORT")) {
+    if (!c->dbg.is_set(SW_NO_TILE_SORT)) {
         NRS_HIP(c, hipMemsetAsync(cs, 0, sizeof(int) * (size_t)M, st));
         NRS_HIP(c, hipMemsetAsync(cd, 0, sizeof(int) * (size_t)M, st));
         hipLaunchKernelGGL(k_dp_vcounts, nb(std::max(ni_s, ni_d)), dim3(256), 0, st, n_sp, r_sp, n_dm, r_dm, cs, cd);

@@ -898,7 +898,7 @@ __global__ __launch_bounds__(256) void k_kft_gemv(KftDev F, int mode, int k0, in
 // ------------------------------------------------------------------------------------------------------------------ host
 static int kft_invert(nrs_ctx* c, const KftHost& H, int kf0, int kf1, int* flags, int nbu) {   // nbu: of the one-GPU pair (a rank may run one chain of it)
     const KftDev& F = H.d;
-    if (c->env("NRS_KFT_TWO_LAUNCHES")) {                           // (A/B: the panel and the trailing update of a step as launches of their own)
+    if (c->dbg.is_set(SW_KFT_TWO_LAUNCHES)) {                           // (A/B: the panel and the trailing update of a step as launches of their own)
         for (int j = 0; j < F.nb; ++j) {
             hipLaunchKernelGGL(k_kft_panel, dim3(F.nb, 2), dim3(256), KFT_PANEL_LDS, c->stream, F, j, kf0, kf1, flags);
             hipLaunchKernelGGL(k_kft_update, dim3(F.nb * F.nb, 2), dim3(256), 0, c->stream, F, j, kf0, kf1, j + 1 == F.nb ? 1 : 0);
@@ -906,8 +906,8 @@ static int kft_invert(nrs_ctx* c, const KftHost& H, int kf0, int kf1, int* flags
         return NRS_OK;
     }
     for (int j = 0; j <= nbu; ++j)
-        if (c->env("NRS_KFT_SCALAR_SWEEP")) hipLaunchKernelGGL(k_kft_step<false>, dim3(2 * (nbu + nbu * nbu)), dim3(256), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
-        else if (c->env("NRS_KFT_FOUR_WAVES")) hipLaunchKernelGGL(k_kft_step<true>, dim3(2 * (nbu + nbu * nbu)), dim3(256), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
+        if (c->dbg.is_set(SW_KFT_SCALAR_SWEEP)) hipLaunchKernelGGL(k_kft_step<false>, dim3(2 * (nbu + nbu * nbu)), dim3(256), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
+        else if (c->dbg.is_set(SW_KFT_FOUR_WAVES)) hipLaunchKernelGGL(k_kft_step<true>, dim3(2 * (nbu + nbu * nbu)), dim3(256), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
         else hipLaunchKernelGGL((k_kft_step<true, true>), dim3(2 * (nbu + nbu * nbu)), dim3(512), KFT_STEP_LDS, c->stream, F, j, kf0, kf1, flags, nbu);
     return NRS_OK;
 }

@@ -138,7 +138,7 @@ static int launch_spmv(nrs_ctx* c, const Dev& d0, double lam, int it, double tol
         const size_t shm = d.dform ? sizeof(double) * 3 * (3 * (size_t)(d.tile_rows + d.cap_h[cls] + 1) + d.tile_rows + d.cap_s[cls] + 1)
                                    : sizeof(double) * 3 * (size_t)(2 * d.tile_rows + d.cap_h[cls] + ((rc_of(d, cls) & 2) ? d.cap_h[cls] : d.cap_s[cls]) + 2);
         const bool last_cls = cls == 1 || d.sh_nt[1] + d.sh_ntb[1] == 0;
-        if (!d.dform && with_skin_op && last_cls && !(d.T == 2 && d.plain && d.tp_ok) && !c->env("NRS_SKIN_OP_OWN_LAUNCH")) {
+        if (!d.dform && with_skin_op && last_cls && !(d.T == 2 && d.plain && d.tp_ok) && !c->dbg.is_set(SW_SKIN_OP_OWN_LAUNCH)) {
             NRS_TRY(with_lanes(c, d.T, [&](auto L) { hipLaunchKernelGGL((k_spmv_f_skin<decltype(L)::value>), dim3(g.x + d.sk_nblk), b, shm, c->stream, d, lam, cls, it, tol2, (int)g.x); }));
             if (merged) *merged = true;
             continue;

@@ -76,8 +76,8 @@ static void nd_slot_release(nrs_ctx* c, NdEngine* nd) {            // the engine
 // Ahead at every measured size; the default window ends where nothing has been measured.
 static bool nd_mode_allows(nrs_ctx* c, int n_free) {
     int mode = c->opt.direct_solve;
-    if (const char* ev = c->env("NRS_ND")) mode = atoi(ev) ? 1 : 2;
-    const int nmax = c->env("NRS_ND_MAX_ROWS") ? atoi(c->env("NRS_ND_MAX_ROWS")) : 8000;
+    if (c->dbg.is_set(SW_ND)) mode = c->dbg.int_of(SW_ND) ? 1 : 2;
+    const int nmax = c->dbg.int_of(SW_ND_MAX_ROWS);
     return mode != 2 && n_free > 0 && (mode == 1 || n_free <= nmax);
 }
 static bool nd_wanted(nrs_ctx* c, const Dev& d, int n_free) {
@@ -155,14 +155,14 @@ static void nd_prep_run(nrs_ctx* c, const NdIn& in, NdPrep& P) {
 }
 // halves of a dissection of this many nodes go to threads of their own (first two levels; NRS_ND_PLAN_PAR=0: never; NRS_HOST_THREADS=1 likewise)
 static int nd_plan_par_min(const nrs_ctx* c) {
-    if (const char* v = c->env("NRS_ND_PLAN_PAR")) return atoi(v);
-    if (const char* v = c->env("NRS_HOST_THREADS")) if (atoi(v) <= 1) return 0;
+    if (c->dbg.is_set(SW_ND_PLAN_PAR)) return c->dbg.int_of(SW_ND_PLAN_PAR);
+    if (c->dbg.is_set(SW_HOST_THREADS) && c->dbg.int_of(SW_HOST_THREADS) <= 1) return 0;
     return std::thread::hardware_concurrency() >= 4 ? 700 : 0;
 }
 // the cache (read only here: nobody changes it while an engine is being set up): the free slot an earlier frame left with this key
 static NdSlot* nd_cache_lookup(nrs_ctx* c, const NdPrep& P) {
     const NdCache* nc = static_cast<const NdCache*>(c->nd_cache);
-    if (!nc || c->env("NRS_ND_NO_CACHE")) return nullptr;
+    if (!nc || c->dbg.is_set(SW_ND_NO_CACHE)) return nullptr;
     for (NdSlot* sl : nc->slots)
         if (!sl->busy && sl->st && sl->hash == P.hash && sl->key == P.key) return sl;
     return nullptr;
@@ -170,7 +170,7 @@ static NdSlot* nd_cache_lookup(nrs_ctx* c, const NdPrep& P) {
 // phase A, stage by stage (nrs_nd_prep_host.hpp): number, allowed?, key, look-up, edge keys, skin, merge, pose, plan, observation lists
 static void nd_prep_run_body(nrs_ctx* c, const NdIn& in, NdPrep& P) {
     P.wanted = false; P.plan_ok = false; P.hit = nullptr; P.st.reset();
-    const bool tm = c->env("NRS_TIMING") != nullptr;
+    const bool tm = c->dbg.is_set(SW_TIMING);
     auto t_prev = std::chrono::steady_clock::now();
     double t_ms[3] = {0, 0, 0};                                    // key + look-up, pairs, plan
     auto lap = [&](int k) { const auto now = std::chrono::steady_clock::now(); t_ms[k] = std::chrono::duration<double, std::milli>(now - t_prev).count(); t_prev = now; };
@@ -197,7 +197,7 @@ static void nd_prep_run_body(nrs_ctx* c, const NdIn& in, NdPrep& P) {
     lap(1);
     const std::vector<double> pos = nd_node_positions(in, P);
     const NdStruct& T = *P.st;
-    P.plan_ok = nd_build_plan(P.n_nodes, pos.data(), P.last.data(), (int)T.pkind.size(), T.pairs.data(), P.plan, &P.err, leaf_n, ND_SMAXN, false, nd_plan_par_min(c), c->env("NRS_ND_NO_COVER") == nullptr);
+    P.plan_ok = nd_build_plan(P.n_nodes, pos.data(), P.last.data(), (int)T.pkind.size(), T.pairs.data(), P.plan, &P.err, leaf_n, ND_SMAXN, false, nd_plan_par_min(c), !c->dbg.is_set(SW_ND_NO_COVER));
     if (P.plan_ok && in.n_skin > 0) { nd_prep_ske(P, P.plan); nd_prep_ske_values(P, in.sk_om); }
     lap(2);
     if (tm) fprintf(stderr, "[nrs] direct solve set-up thread: key %.2f ms, pairs %.2f ms, plan %.2f ms\n", t_ms[0], t_ms[1], t_ms[2]);
@@ -232,12 +232,12 @@ static NdSlot* nd_slot_acquire(nrs_ctx* c, NdCache* nc, const NdPrep& P, bool* h
     *hit = P.hit && !P.hit->busy;
     if (*hit) {
         ++nc->hits;
-        if (c->env("NRS_TIMING")) fprintf(stderr, "[nrs] direct solve: plan of an earlier frame reused (%llu reused, %llu built)\n", (unsigned long long)nc->hits, (unsigned long long)nc->misses);
+        if (c->dbg.is_set(SW_TIMING)) fprintf(stderr, "[nrs] direct solve: plan of an earlier frame reused (%llu reused, %llu built)\n", (unsigned long long)nc->hits, (unsigned long long)nc->misses);
         return P.hit;
     }
     if (P.hit) { *rc = c->fail(NRS_ERR_STATE, "direct solve: the plan this engine was set up on was taken by another engine meanwhile (engines of one context are created one at a time)"); return nullptr; }
     if (!P.plan_ok) {
-        if (c->env("NRS_TIMING")) fprintf(stderr, "[nrs] direct solve not used: %s\n", P.err.c_str());
+        if (c->dbg.is_set(SW_TIMING)) fprintf(stderr, "[nrs] direct solve not used: %s\n", P.err.c_str());
         return nullptr;
     }
     ++nc->misses;
@@ -255,7 +255,7 @@ static int nd_slot_upload_plan(nrs_ctx* c, NdSlot* sl, NdPrep& P, int n_spec, bo
     sl->S.plan = std::move(P.plan);
     const int up = nd_upload(c, sl->S);
     if (up != NRS_ERR_INVALID) return up;
-    if (c->env("NRS_TIMING")) fprintf(stderr, "[nrs] direct solve not used: %s\n", c->err);
+    if (c->dbg.is_set(SW_TIMING)) fprintf(stderr, "[nrs] direct solve not used: %s\n", c->err);
     *fits = false;
     return NRS_OK;
 }
@@ -313,7 +313,7 @@ static int nd_engine_bind(nrs_ctx* c, Engine* e, NdEngine* nd, NdSlot* sl) {
 // nd->on = false if the problem does not qualify
 static int nd_engine_finish(nrs_ctx* c, Engine* e, NdEngine* nd, NdPrep& P) {
     {
-        const bool tm = c->env("NRS_TIMING") != nullptr;
+        const bool tm = c->dbg.is_set(SW_TIMING);
         const auto t0 = std::chrono::steady_clock::now();
         P.wait();
         if (tm) fprintf(stderr, "[nrs] direct solve: waited %.2f ms for the plan thread\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -347,7 +347,7 @@ static int nd_engine_finish(nrs_ctx* c, Engine* e, NdEngine* nd, NdPrep& P) {
     nd->slot = sl; nd->on = true;
     if (!hit) { sl->key.swap(P.key); sl->hash = P.hash; sl->st = P.st; }
     sguard.keep = true;
-    if (c->env("NRS_TIMING"))
+    if (c->dbg.is_set(SW_TIMING))
         fprintf(stderr, "[nrs] direct solve: %d free rows, %d pairs, %d fronts on %d levels, %d workgroups, %.1f MFLOP per factorisation\n", sl->n_free,
                 sl->n_pairs, sl->S.plan.n_fronts, sl->S.plan.n_levels, (int)sl->S.plan.wg.size() / 3, sl->S.plan.flops / 1e6);
     return NRS_OK;

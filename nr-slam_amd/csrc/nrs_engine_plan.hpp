@@ -28,10 +28,8 @@ static RowGroups row_groups(const EngineSpec& s) {
 // lanes per row: 2 measured best on C2 (92k rows), 8 on single-frame problems (4.5k rows), where
 // the kernels are bound by per-lane latency chains rather than by traffic (profiles/README.md)
 static int lanes_per_row(const nrs_ctx* c, int n_pad_rows) {
-    if (const char* ev = c->env("NRS_SELL_T")) {
-        const int v = atoi(ev);
-        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) return v;
-    }
+    const int v = c->dbg.int_of(SW_SELL_T);                       // (0 unless set)
+    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) return v;
     return n_pad_rows >= 32768 ? 2 : 8;
 }
 
@@ -66,9 +64,9 @@ static std::vector<int> tile_classes(const nrs_ctx* c, Dev& d, const std::vector
         // for the bulk to fit the LDS budget at all)
         const int p97 = sorted[(size_t)(0.97 * (nb - 1))];
         const bool fits = sizeof(double) * 3 * (size_t)(2 * d.tile_rows + d.max_halo + d.max_halo_s + 2) <= 48 * 1024;
-        if (4 * d.max_halo > 5 * p97 && (nb - (int)(0.97 * nb) >= 1024 || !fits) && !c->env("NRS_ONE_CLASS")) cut = p97;
+        if (4 * d.max_halo > 5 * p97 && (nb - (int)(0.97 * nb) >= 1024 || !fits) && !c->dbg.is_set(SW_ONE_CLASS)) cut = p97;
     }
-    if (c->env("NRS_TILE_CUT_PCT")) cut = sorted[(size_t)(atof(c->env("NRS_TILE_CUT_PCT")) / 100.0 * (nb - 1))];   // test switch: force a split at a percentile
+    if (c->dbg.is_set(SW_TILE_CUT_PCT)) cut = sorted[(size_t)(c->dbg.real_of(SW_TILE_CUT_PCT) / 100.0 * (nb - 1))];   // test switch: force a split at a percentile
     int n0 = 0;
     for (int b = 0; b < nb; ++b) if (hs[b] <= cut) tile_list[n0++] = b;
     d.n_tiles_cls[0] = n0; d.n_tiles_cls[1] = nb - n0;
@@ -94,16 +92,16 @@ static void path_flags(const nrs_ctx* c, Dev& d, const EngineSpec& s) {
         lds_need = std::max(lds_need, sizeof(double) * 3 * (size_t)(d.tile_rows + d.cap_h[cls]) * (s.X0 ? 2 : 1));                          // linearise
         lds_need = std::max(lds_need, sizeof(double) * 3 * (size_t)(2 * d.tile_rows + d.cap_h[cls] + d.cap_s[cls] + 2));                    // operator: u + positions
     }
-    d.use_lds = !(c->env("NRS_NO_LDS") || s.force_gather || lds_need > 64 * 1024 - 512 || d.tile_rows + d.max_halo >= 65535);   // irregular graph / A-B switch
+    d.use_lds = !(c->dbg.is_set(SW_NO_LDS) || s.force_gather || lds_need > 64 * 1024 - 512 || d.tile_rows + d.max_halo >= 65535);   // irregular graph / A-B switch
     if (!d.use_lds) d.dform = 0;
     d.lin_rb = d.use_lds ? ROW_ALIGN / d.tile_rows : 1;              // lineariser partials: per tile (LDS path) or per group
     // single-launch PCG iteration for problems that are bound by launch latency, not by traffic
-    const int fused_max = c->env("NRS_FUSED_MAX_ROWS") ? atoi(c->env("NRS_FUSED_MAX_ROWS")) : 32768;
-    d.fused = (d.use_lds && d.n_rows < fused_max && !c->env("NRS_NO_FUSED")) ? 1 : 0;
+    const int fused_max = c->dbg.int_of(SW_FUSED_MAX_ROWS);
+    d.fused = (d.use_lds && d.n_rows < fused_max && !c->dbg.is_set(SW_NO_FUSED)) ? 1 : 0;
     if (s.sk_window() > 0) d.fused = 0;                            // embedded mode: the skinned observations' operator kernels sit between the two launches of an iteration
-    d.hier = (d.n_regblk > 4096 || c->env("NRS_HIER")) ? 1 : 0;
+    d.hier = (d.n_regblk > 4096 || c->dbg.is_set(SW_HIER)) ? 1 : 0;
     // (a profiling context times full operator launches only: no convergence-detecting early exits)
-    d.ecd = (d.use_lds && !d.fused && !c->opt.profile && !c->env("NRS_NO_ECD")) ? 1 : 0;
+    d.ecd = (d.use_lds && !d.fused && !c->opt.profile && !c->dbg.is_set(SW_NO_ECD)) ? 1 : 0;
     // two-level preconditioner: fused path, one pose, small enough coarse system
     d.co_n = 3 * d.n_groups + 6;
     // (worth its per-iteration cost on the pose + deformation problems; the lost-point stage, pose
@@ -112,9 +110,9 @@ static void path_flags(const nrs_ctx* c, Dev& d, const EngineSpec& s) {
     const size_t fused_shm = sizeof(double) * (6 * (size_t)(d.tile_rows + d.max_halo) + 12 * (size_t)d.n_regblk + 16 * CO_MAX);
     // (and only from ~1.5k rows on: below, its per-iteration cost outweighs the iterations it saves -- 1013 points 31.3 ms with it,
     // 29.2 without; 2220 points 47.4 / 51.8; 4525 points 76.7 / 94.1, tools/small_frame_probe.py)
-    const int co_min_tiles = c->env("NRS_COARSE_MIN_TILES") ? atoi(c->env("NRS_COARSE_MIN_TILES")) : 48;
+    const int co_min_tiles = c->dbg.int_of(SW_COARSE_MIN_TILES);
     d.coarse = (d.fused && s.K == 1 && pose_free && d.co_n <= CO_MAX && d.n_regblk <= BLK && d.n_regblk >= co_min_tiles && fused_shm <= 63 * 1024 &&
-                !c->env("NRS_NO_COARSE")) ? 1 : 0;
+                !c->dbg.is_set(SW_NO_COARSE)) ? 1 : 0;
 }
 
 // Contiguous keyframe ranges for `world` ranks, balanced by padded rows, every rank at least one
@@ -138,7 +136,7 @@ void shard_plan(int K, const int* grp_ptr, int world, int* kb) {
 // exchange), not records.  Packing time and record memory scale with 1 / ranks.
 static void pack_range(const nrs_ctx* c, const EngineSpec& s, const RowGroups& g, int& lo, int& hi) {
     lo = 0; hi = g.n_pad_rows;
-    if (!(c->comm && s.shard && c->comm->world <= 8 && s.K >= c->comm->world) || c->env("NRS_SHARD_PACK_ALL")) return;
+    if (!(c->comm && s.shard && c->comm->world <= 8 && s.K >= c->comm->world) || c->dbg.is_set(SW_SHARD_PACK_ALL)) return;
     std::vector<int> kb(c->comm->world + 1);
     shard_plan(s.K, g.pose_grp_ptr.data(), c->comm->world, kb.data());
     lo = g.pose_grp_ptr[kb[c->comm->rank]] * ROW_ALIGN; hi = g.pose_grp_ptr[kb[c->comm->rank + 1]] * ROW_ALIGN;
@@ -182,7 +180,7 @@ static int shard_window(nrs_ctx* c, Dev& d, HaloPlan& h, const EngineSpec& s, co
     // ... so the rank holds the per-row arrays (state, vectors, diagonal blocks: ~410 bytes a row) of its own keyframes and of ONE ghost
     // keyframe either side only: its tiles' halos end there (just checked), the boundary exchange fills the ghosts, and no launch of
     // this rank touches a row beyond them (ArenaPlan::get_rows).  NRS_SHARD_FULL_VECTORS=1: every row, the round-1..4 form.
-    if (W > 1 && !d.dform && !c->env("NRS_SHARD_FULL_VECTORS")) { d.row_lo = r_lo; d.row_hi = r_hi; }
+    if (W > 1 && !d.dform && !c->dbg.is_set(SW_SHARD_FULL_VECTORS)) { d.row_lo = r_lo; d.row_hi = r_hi; }
     // boundary tiles (they read rows of another rank) sit at the two ends of the rank's tile range:
     // they run after the interior tiles, once the neighbours' rows have arrived
     const int own_lo = d.sh_g0 * ROW_ALIGN, own_hi = (d.sh_g0 + d.sh_ng) * ROW_ALIGN;
@@ -356,7 +354,7 @@ static int arena_fit(nrs_ctx* c, Arena* arena, Engine* e, Dev& d, bool has_X0, s
         hipError_t he = hipMalloc((void**)&arena->base, want);
         if (he != hipSuccess) return c->fail(NRS_ERR_ALLOC, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(he));
         arena->cap = want;
-        if (c->env("NRS_POISON")) { (void)hipMemset(arena->base, 0xFF, want); (void)hipDeviceSynchronize(); }    // (debug: a read of memory nobody wrote shows up as NaN)
+        if (c->dbg.is_set(SW_POISON)) { (void)hipMemset(arena->base, 0xFF, want); (void)hipDeviceSynchronize(); }    // (debug: a read of memory nobody wrote shows up as NaN)
     }
     ArenaPlan real{arena, false};
     carve(real, d, has_X0, nnz_s, nnz_d, n_slices, n_halo, e);

@@ -53,7 +53,7 @@ struct PhaseClocks {
 // NRS_SPMV_DBG=1: one operator launch (compact headers, PCG iteration 3), per wave
 static bool spmv_clocks_wanted(nrs_ctx* c, const Dev& d, int it) {
     static bool done = false;
-    if (!(d.h4 && it == 3 && !done && c->env("NRS_SPMV_DBG"))) return false;
+    if (!(d.h4 && it == 3 && !done && c->dbg.is_set(SW_SPMV_DBG))) return false;
     return done = true;
 }
 
@@ -61,11 +61,11 @@ static bool spmv_clocks_wanted(nrs_ctx* c, const Dev& d, int it) {
 template <bool LIN>
 static int lin_clocks_once(nrs_ctx* c, const Dev& d, const double* xl) {
     static bool done = false;
-    if (!LIN || !d.plain || !c->env("NRS_LIN_DBG") || done) return NRS_OK;
+    if (!LIN || !d.plain || !c->dbg.is_set(SW_LIN_DBG) || done) return NRS_OK;
     done = true;
     Dev dd = d;
     PhaseClocks p(c, true, dd, (size_t)d.n_rows / (64 / d.T), "k_lin_plain", "wave", {"stage", "springs", "dampers", "reproj", "tail"});
-    if (!p.buf) return c->fail(NRS_ERR_ALLOC, "NRS_LIN_DBG: no memory for the phase clocks");
+    if (!p.buf) return c->fail(NRS_ERR_ALLOC, "%s: no memory for the phase clocks", SWITCHES[SW_LIN_DBG].name);
     return launch_reg<LIN>(c, dd, xl);
 }
 
@@ -73,7 +73,7 @@ static int lin_clocks_once(nrs_ctx* c, const Dev& d, const double* xl) {
 // (returns whether it went out)
 static bool pcg_clocks_once(nrs_ctx* c, const Dev& d, double lam, int it, double tol2, double peek_tol2, int pub) {
     static bool done = false;
-    if (!(d.fused && it == 20 && d.coarse && c->env("NRS_PCG_DBG")) || done) return false;
+    if (!(d.fused && it == 20 && d.coarse && c->dbg.is_set(SW_PCG_DBG)) || done) return false;
     done = true;
     Dev dd = d;
     PhaseClocks p(c, true, dd, (size_t)d.n_regblk, "k_pcg_fused<8,true>", "tile",
@@ -87,8 +87,8 @@ static bool pcg_clocks_once(nrs_ctx* c, const Dev& d, double lam, int it, double
 
 // NRS_LIN_EXP=<n>: timing experiments on the lanes = 2 pinhole lineariser (wrong results for 1..5): a piece of the pass removed
 static KLin lin_exp_kernel(nrs_ctx* c, const Dev& d) {
-    if (!(d.cam.model == 0 && d.tp_ok && c->env("NRS_LIN_EXP"))) return nullptr;
-    switch (atoi(c->env("NRS_LIN_EXP"))) {
+    if (!(d.cam.model == 0 && d.tp_ok && c->dbg.is_set(SW_LIN_EXP))) return nullptr;
+    switch (c->dbg.int_of(SW_LIN_EXP)) {
         case 1: return k_lin_plain<2, 4, 0, true, 1>;
         case 2: return k_lin_plain<2, 4, 0, true, 2>;
         case 3: return k_lin_plain<2, 4, 0, true, 3>;

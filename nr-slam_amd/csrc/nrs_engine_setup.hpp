@@ -43,11 +43,11 @@ static int spec_prepare(nrs_ctx* c, Engine* e) {
 
 // shadow sets of a single-frame engine (speculative LM trials, nrs_engine_types.hpp): NRS_SPEC_TRIALS=<0..3> (0: one trial at a time)
 static int spec_sets(const nrs_ctx* c) {
+    static_assert(SPEC_TRIALS_MAX == SPEC_MAX, "the clamp of NRS_SPEC_TRIALS is the number of shadow sets");
     if (c->opt.profile) return 0;                                  // (a profiling context times its launches one by one)
-    if (const char* v = c->env("NRS_SPEC_TRIALS")) return std::max(0, std::min(SPEC_MAX, atoi(v)));
     // two shadow sets = three trials in flight: a fourth stream's launches are serialised behind another stream's on this runtime (its result
     // arrives a whole trial after the third's: 240 / 266 / 298 / 516 us at 1k points), so a third set only adds work that may be discarded
-    return 2;
+    return c->dbg.int_of(SW_SPEC_TRIALS);                          // (2 unless set)
 }
 
 // shadow sets of a BA window on the two-kernel PCG (speculative LM trials, nrs_engine_types.hpp): unsharded windows without skinned
@@ -56,7 +56,7 @@ static int spec_sets(const nrs_ctx* c) {
 // rows) takes 17.5 ms per step with sets against 17.0 without, so larger windows carve none.
 static void spec_pcg_sets(const nrs_ctx* c, Engine* e, int n_skin) {
     const Dev& d = e->d;
-    const long max_rows = c->env("NRS_SPEC_MAX_ROWS") ? atol(c->env("NRS_SPEC_MAX_ROWS")) : (1L << 18);
+    const long max_rows = c->dbg.long_of(SW_SPEC_MAX_ROWS);
     const bool on = !e->nd && !d.fused && !d.coarse && !d.sh_on && n_skin == 0 && !c->opt.profile && (long)d.n_rows <= max_rows;
     e->spec_pcg = on;
     e->n_spec = on ? spec_sets(c) : 0;
@@ -83,11 +83,11 @@ static int host_threads(const nrs_ctx* c, size_t work) {
     if (work < 600000) {
         // single-frame problems (a 4.5k-point frame: 0.3 M incidences): sixteen threads per stage cost more than they save (8 ms per frame,
         // round 2); NRS_HOST_THREADS_SMALL=<n> tries a few (round 5: see profiles/README.md)
-        if (const char* ev = c->env("NRS_HOST_THREADS_SMALL")) if (work >= 100000) return std::max(1, std::min(8, atoi(ev)));
+        if (c->dbg.is_set(SW_HOST_THREADS_SMALL) && work >= 100000) return std::max(1, std::min(8, c->dbg.int_of(SW_HOST_THREADS_SMALL)));
         return 1;
     }
     int n = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char* ev = c->env("NRS_HOST_THREADS")) n = std::max(1, std::min(64, atoi(ev)));
+    if (c->dbg.is_set(SW_HOST_THREADS)) n = c->dbg.int_of(SW_HOST_THREADS);
     return n;
 }
 // plain two-kernel windows whose rows all know their temporal partners: the dampers' 8-byte headers {o0, o1, o2, meta} shrink
@@ -103,13 +103,13 @@ __global__ void k_compact_headers(size_t n, const uint2* __restrict__ hdr, uint3
 static void engine_compact_headers(nrs_ctx* c, Engine* e) {
     Dev& d = e->d;
     d.h4 = 0; d.rc = 0; d.nt = 0;
-    if (!(d.plain && d.tp_ok && d.use_lds && !d.fused && d.T == 2) || c->env("NRS_NO_H4")) return;
+    if (!(d.plain && d.tp_ok && d.use_lds && !d.fused && d.T == 2) || c->dbg.is_set(SW_NO_H4)) return;
     if (d.tile_rows + std::max(d.cap_h[0], d.cap_h[1]) + 2 >= 4096 || d.sd_nnz <= 0) return;
     hipLaunchKernelGGL(k_compact_headers, dim3((unsigned)(((size_t)d.sd_nnz + 255) / 256)), dim3(256), 0, c->stream, (size_t)d.sd_nnz, d.d_hdr, d.d_h4);
     d.h4 = 1;
-    if (const char* v = c->env("NRS_RC")) d.rc = atoi(v) & 3;
+    d.rc = c->dbg.int_of(SW_RC);
     d.nt = 12 * ((size_t)d.ss_nnz + (size_t)d.sd_nnz) > ((size_t)128 << 20);   // the streams (with the vectors next to them) do not stay in the 256 MB Infinity Cache between launches
-    if (const char* v = c->env("NRS_NT")) d.nt = atoi(v) != 0;
+    if (c->dbg.is_set(SW_NT)) d.nt = c->dbg.int_of(SW_NT) != 0;
 }
 
 template <class F>
@@ -232,7 +232,7 @@ static int nd_plan_start(nrs_ctx* c, const EngineSpec& s, Engine* e, NdIn& nd_in
     nd_in.n_sp = s.n_sp; nd_in.sp_ij = s.sp_ij; nd_in.n_dm = s.n_dm; nd_in.dm_idx = s.dm_idx;
     nd_in.n_skin = s.n_skin; nd_in.sk_vert = s.sk_node; nd_in.sk_om = s.sk_om;
     nd_in.vpos = e->nd->pos.data();
-    bool inline_run = c->env("NRS_HOST_THREADS") && atoi(c->env("NRS_HOST_THREADS")) <= 1;
+    bool inline_run = c->dbg.is_set(SW_HOST_THREADS) && c->dbg.int_of(SW_HOST_THREADS) <= 1;
     if (!inline_run) {
         PlanWorker* pw = static_cast<PlanWorker*>(c->plan_worker);
         if (!pw) {
@@ -339,7 +339,7 @@ void HostBuild::row_layout() {
             v = (v | v << 2) & 0x1249249249249249ULL;
             return v;
         };
-        const bool morton = c->env("NRS_NO_MORTON") == nullptr;
+        const bool morton = !c->dbg.is_set(SW_NO_MORTON);
         parallel_for(std::min(nt_all, s.K), [&](int ti, int nt) {
         std::vector<std::pair<uint64_t, int>> keys;
         int64_t k0, k1;
@@ -364,7 +364,7 @@ void HostBuild::row_layout() {
     // Inside a tile the row order is free (neighbour ids are tile-local, the vector kernels stream): rows are sorted
     // by their incidence counts, so that the rows of a slice (64 / T consecutive rows share the slice's width) have
     // similar counts.  C2: sliced-ELL padding 1.34x / 1.37x (springs / dampers) -> 1.22x / 1.15x of the incidences.
-    if (!c->env("NRS_NO_TILE_SORT")) {
+    if (!c->dbg.is_set(SW_NO_TILE_SORT)) {
         std::vector<int> cs(s.M, 0), cd(s.M, 0);
         parallel_for(nt_all, [&](int ti, int n) {                  // integer counts: order-free
             int64_t a, b;
@@ -518,11 +518,11 @@ void HostBuild::temporal_form() {
     // offsets or unary dampers, and the two-kernel path (the fused single-launch iteration re-derives u for halo rows
     // and keeps the generic four-vertex records)
     {
-        const int fused_max0 = c->env("NRS_FUSED_MAX_ROWS") ? atoi(c->env("NRS_FUSED_MAX_ROWS")) : 32768;
-        bool plain = !s.X0 && s.n_un == 0 && s.n_dm > 0 && !s.sp_active && !s.dm_active && !s.pose_fixed && !c->env("NRS_NO_EDGE_CHI") && c->env("NRS_DFORM") &&
-                     !c->env("NRS_NO_LDS") && !s.force_gather;
+        const int fused_max0 = c->dbg.int_of(SW_FUSED_MAX_ROWS);
+        bool plain = !s.X0 && s.n_un == 0 && s.n_dm > 0 && !s.sp_active && !s.dm_active && !s.pose_fixed && !c->dbg.is_set(SW_NO_EDGE_CHI) && c->dbg.is_set(SW_DFORM) &&
+                     !c->dbg.is_set(SW_NO_LDS) && !s.force_gather;
         for (int v = 0; v < s.M && plain; ++v) plain = !(s.rflag[v] & RF_FIXED);
-        const bool two_kernel = d.n_rows >= fused_max0 || c->env("NRS_NO_FUSED") || (c->comm && s.shard);
+        const bool two_kernel = d.n_rows >= fused_max0 || c->dbg.is_set(SW_NO_FUSED) || (c->comm && s.shard);
         if (plain && two_kernel) {
             nxt_row.assign(d.n_rows, -1); prv_row.assign(d.n_rows, -1);
             for (int q = 0; q < s.n_dm && plain; ++q) {
@@ -549,7 +549,7 @@ void HostBuild::halo_lists() {
     {
         // tiles are independent: a few host threads each take a contiguous range of tiles
         int nt = std::max(1, std::min({8, (int)std::thread::hardware_concurrency(), d.n_regblk / 32}));   // (a 4.5k-point frame: 4 threads, 1.5 -> 0.5 ms)
-        if (const char* ev = c->env("NRS_HOST_THREADS")) nt = std::max(1, std::min({64, atoi(ev), std::max(1, d.n_regblk)}));
+        if (c->dbg.is_set(SW_HOST_THREADS)) nt = std::min(c->dbg.int_of(SW_HOST_THREADS), std::max(1, d.n_regblk));
         std::vector<std::vector<int>> part(nt);
         std::vector<int> cnt(d.n_regblk, 0);
         auto work = [&](int ti) {
@@ -682,11 +682,11 @@ void HostBuild::ec_lists_build() {
 
 // ---- chi2 edge lists, the specialised (plain) lineariser's conditions, and the temporal partners of its rows
 void HostBuild::edge_lists() {
-    bool plain = !s.X0 && s.n_un == 0 && !s.sp_active && !s.dm_active && !s.pose_fixed && !c->env("NRS_NO_EDGE_CHI");
+    bool plain = !s.X0 && s.n_un == 0 && !s.sp_active && !s.dm_active && !s.pose_fixed && !c->dbg.is_set(SW_NO_EDGE_CHI);
     for (int v = 0; v < s.M && plain; ++v) plain = !(s.rflag[v] & RF_FIXED);
     d.ec_on = plain ? 1 : 0;
     {   // the specialised lineariser additionally wants every damper with its four vertices and springs without a kernel
-        bool p4 = plain && d.use_lds && !d.dform && !(s.delta_pos > 0) && s.spring_form == 0 && !c->env("NRS_NO_PLAIN");
+        bool p4 = plain && d.use_lds && !d.dform && !(s.delta_pos > 0) && s.spring_form == 0 && !c->dbg.is_set(SW_NO_PLAIN);
         for (int64_t q = 0; q < 4 * (int64_t)s.n_dm && p4; ++q) p4 = s.dm_idx[q] >= 0;
         d.plain = p4 ? 1 : 0;
         if (d.plain) d.lin_rb = ROW_ALIGN / (64 / T);          // k_lin_plain leaves one partial slot per SLICE (no workgroup barrier behind its loops)

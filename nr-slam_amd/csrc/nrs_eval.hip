@@ -343,7 +343,7 @@ extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float
     if (D.Wr < 1 || D.Hr < 1) return c->fail(NRS_ERR_INVALID, "nrs_stereo_match_pattern: no search position in a %d x %d image", w, h);
     if (n == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
-    const bool plain = c->env("NRS_STEREO_NO_MFMA") != nullptr;
+    const bool plain = c->dbg.is_set(SW_STEREO_NO_MFMA);
     const int npad = (n + ST_NG - 1) / ST_NG * ST_NG;
     const dim3 grid = plain ? dim3((D.Wr + PL_B - 1) / PL_B, (D.Hr + PL_B - 1) / PL_B, npad / ST_NG)
                             : dim3((D.Wr + MF_W - 1) / MF_W, (D.Hr + MF_H - 1) / MF_H, npad / ST_NG);

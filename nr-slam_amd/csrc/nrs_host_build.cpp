@@ -16,7 +16,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/nrs.h"
-namespace nrs { const char* process_debug_option(const char* name); }   // nrs_pose_only.hip: the process-wide snapshot of the NRS_* switches
+#include "nrs_switches.hpp"   // DebugOpts::process(): the process-wide snapshot of the NRS_* switches (nrs_ctx.hip)
 
 namespace {
 constexpr int kRegularizersPerPoint = 10;      // OPT:958
@@ -136,7 +136,7 @@ extern "C" int nrs_dba_build_edges(int32_t n_kf, const int32_t* kf_rowptr, const
     int nt = 1;
     if (n_kf > 1 && kf_rowptr[n_kf] >= 20000) {
         nt = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-        if (const char* ev = nrs::process_debug_option("NRS_HOST_THREADS")) nt = std::max(1, std::min(64, atoi(ev)));
+        if (nrs::DebugOpts::process().is_set(nrs::SW_HOST_THREADS)) nt = nrs::DebugOpts::process().int_of(nrs::SW_HOST_THREADS);
         nt = std::min(nt, n_kf);
     }
     std::vector<int64_t> cs((size_t)n_kf + 1, 0), cd((size_t)n_kf + 1, 0);

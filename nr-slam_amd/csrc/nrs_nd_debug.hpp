@@ -31,7 +31,7 @@ static void nd_debug_report_clocks(nrs_ctx* c, const NdPlan& P, const std::vecto
         for (int w = a; w < b2; ++w) {
             const long long* q = &h[8 * (P.wg.size() / 3 + (size_t)w)];
             if (q[3] == 0) continue;                            // (a root)
-            if (b2 - a <= 2 && c->env("NRS_ND_DBG2")) fprintf(stderr, "   front %d (s %d b %d nseg %d): start %.1f seg-loop-begin %.1f released %.1f gathered %.1f gemv %.1f end %.1f\n", w, P.fr[P.lvl_fronts[w]].s, P.fr[P.lvl_fronts[w]].b, P.fr[P.lvl_fronts[w]].n_seg, (q[0]-t00)/100.0, (q[5]-t00)/100.0, (q[4]-t00)/100.0, (q[1]-t00)/100.0, (q[2]-t00)/100.0, (q[3]-t00)/100.0);
+            if (b2 - a <= 2 && c->dbg.is_set(SW_ND_DBG2)) fprintf(stderr, "   front %d (s %d b %d nseg %d): start %.1f seg-loop-begin %.1f released %.1f gathered %.1f gemv %.1f end %.1f\n", w, P.fr[P.lvl_fronts[w]].s, P.fr[P.lvl_fronts[w]].b, P.fr[P.lvl_fronts[w]].n_seg, (q[0]-t00)/100.0, (q[5]-t00)/100.0, (q[4]-t00)/100.0, (q[1]-t00)/100.0, (q[2]-t00)/100.0, (q[3]-t00)/100.0);
             // (single launch: [4] = released by the parent; "loads" is then the gather of the boundary values only)
             for (int k = 0; k < 3; ++k) { const double d = (double)(q[k + 1] - (k == 0 && q[4] ? q[4] : q[k])) / 100.0; mean[k] += d / (b2 - a); mx[k] = std::max(mx[k], d); }
             lo = std::min(lo, q[4] ? q[4] : q[0]); hi = std::max(hi, q[3]);
@@ -64,7 +64,7 @@ int engine_nd_debug_solve(nrs_ctx* c, int n_nodes, const double* pos, const uint
     NRS_HIP(c, hipSetDevice(c->device));
     NdSolver S;
     std::string err;
-    if (!nd_build_plan(n_nodes, pos, last, n_pairs, pairs, S.plan, &err, nd_leaf_n(c), ND_SMAXN, true, 0, c->env("NRS_ND_NO_COVER") == nullptr)) return c->fail(NRS_ERR_INVALID, "direct solve: %s", err.c_str());
+    if (!nd_build_plan(n_nodes, pos, last, n_pairs, pairs, S.plan, &err, nd_leaf_n(c), ND_SMAXN, true, 0, !c->dbg.is_set(SW_ND_NO_COVER))) return c->fail(NRS_ERR_INVALID, "direct solve: %s", err.c_str());
     nd_stats(S.plan, stats);
     struct Rel { nrs_ctx* c; NdSolver* s; ~Rel() { (void)hipStreamSynchronize(c->stream); c->release(s->own); } } rel{c, &S};
     NRS_TRY(nd_upload(c, S));
@@ -87,7 +87,7 @@ int engine_nd_debug_solve(nrs_ctx* c, int n_nodes, const double* pos, const uint
         NRS_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
         if (ms_per_solve) *ms_per_solve = ms / repeats;
     }
-    if (c->env("NRS_ND_DBG")) NRS_TRY(nd_debug_phase_clocks(c, S, lam));
+    if (c->dbg.is_set(SW_ND_DBG)) NRS_TRY(nd_debug_phase_clocks(c, S, lam));
     int fl[4] = {0, 0, 0, 0};
     NRS_HIP(c, hipMemcpyAsync(fl, S.dev.flags, sizeof(fl), hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipMemcpyAsync(x, S.dev.xn, 24 * (size_t)n_nodes, hipMemcpyDeviceToHost, c->stream));

@@ -61,7 +61,7 @@ static void nd_fill_descriptors(nrs_ctx* c, NdSolver& S, NdWgD* hw, NdFrontD* hl
     // Measured with 512-thread workgroups (round 5): the launch boundaries are the cheaper hand-over at every size -- 155 us per factorise +
     // solve against 163 chained at 543 points (everything resident), 201 / 223 at 1013, 480 / 501 at 4446 (top seven levels chained) -- so
     // the chained form is opt-in (NRS_ND_CHAIN=1, read when a plan is uploaded; the tests hold it to the per-level form bit for bit)
-    if (P.n_levels - S.chain_from < 2 || !c->env("NRS_ND_CHAIN")) S.chain_from = P.n_levels;
+    if (P.n_levels - S.chain_from < 2 || !c->dbg.is_set(SW_ND_CHAIN)) S.chain_from = P.n_levels;
     for (size_t f = 0; f < P.fr.size(); ++f)
         if (P.fr[f].par >= 0 && lvl_of[f] >= S.chain_from) need[P.fr[f].par] += P.fr[f].nR * (P.fr[f].nR + 1) / 2;
     for (size_t w = 0; w < P.wg.size() / 3; ++w) { hw[w] = NdWgD{P.fr[P.wg[3 * w]], P.wg[3 * w + 1], P.wg[3 * w + 2], need[P.wg[3 * w]]}; hw[w].F.cmap_off = P.wg[3 * w]; }
@@ -129,7 +129,7 @@ static int nd_upload(nrs_ctx* c, NdSolver& S) {
     D.ev = S.d_ev;
     D.Lp = G.at<double>(o_L); D.A = G.at<double>(o_A); D.xn = G.at<double>(o_x);
     D.flags = G.at<int>(o_fl); D.done = G.at<int>(o_dn); D.fcnt = G.at<int>(o_fc);
-    D.n_x3 = 3 * P.n_nodes; D.x_poll = c->env("NRS_ND_BACK_FLAGS") ? 0 : 1;
+    D.n_x3 = 3 * P.n_nodes; D.x_poll = c->dbg.is_set(SW_ND_BACK_FLAGS) ? 0 : 1;
     S.epoch = 0; S.chained = 0;
     for (int j = 0; j <= S.n_alt; ++j) {
         char* bj = base + (size_t)j * S.alt_stride;
@@ -163,14 +163,12 @@ static int nd_solve_enqueue(nrs_ctx* c, NdSolver& S, double lam, const NdDev* al
     // dispatcher hands workgroups of a launch out in block-index order -- observed on every CDNA part, not promised by HIP; hence the
     // bounded spins in k_nd_level / k_nd_back (a wait that runs out raises flags[2] = 2 -> NRS_ERR_HIP, never a hang) and the
     // resident-at-once condition, under which the order does not matter at all.
-    const bool per_level = c->env("NRS_ND_LEVELS") != nullptr;     // (read per call: the tests switch it between solves)
+    const bool per_level = c->dbg.is_set(SW_ND_LEVELS);     // (read per call: the tests switch it between solves)
     // 512 threads per workgroup unless NRS_ND_THREADS=256 (a level is one workgroup's latency: eight waves shorten its trailing updates,
     // its reads of the children's slots and its Schur tiles; same bits either way)
-    const char* nth_env = c->env("NRS_ND_THREADS");
-    const bool wide = !(nth_env && atoi(nth_env) == 256);
+    const bool wide = !(c->dbg.is_set(SW_ND_THREADS) && c->dbg.int_of(SW_ND_THREADS) == 256);
     // 32-column panel steps (k_nd_level<.., true>) unless NRS_ND_STEP32=0; same bits as the 16-column form
-    const char* s32_env = c->env("NRS_ND_STEP32");
-    const bool step32 = !(s32_env && atoi(s32_env) == 0);
+    const bool step32 = !(c->dbg.is_set(SW_ND_STEP32) && c->dbg.int_of(SW_ND_STEP32) == 0);
     int first = 1;                                                 // (the first launch of the solve poisons xn)
     auto level = [&](int n, size_t shm, int wg0, int chained) {
         if (wide && step32) hipLaunchKernelGGL((k_nd_level<512, true>), dim3(n), dim3(512), shm, c->stream, dev, wg0, lam, epoch, chained, first);
@@ -184,7 +182,7 @@ static int nd_solve_enqueue(nrs_ctx* c, NdSolver& S, double lam, const NdDev* al
         // a CROWDED level (more workgroups than CUs: they would run in rounds, one per CU, each factorising its front's panel for one
         // tile) runs as two launches: the diagonal and inverse workgroups factorise and leave their rows of L21, k_nd_tile makes the
         // off-diagonal tiles from them (NRS_ND_NO_SPLIT=1: one launch per level throughout; the bits are the same)
-        const bool no_split = c->env("NRS_ND_NO_SPLIT") != nullptr;
+        const bool no_split = c->dbg.is_set(SW_ND_NO_SPLIT);
         for (int l = 0; l < chain_from; ++l) {
             const int n = P.lvl_wg_ptr[l + 1] - P.lvl_wg_ptr[l], nA = P.lvl_wg_split[l] - P.lvl_wg_ptr[l];
             if (!no_split && n > c->prop.multiProcessorCount && n > nA) {
@@ -211,7 +209,7 @@ static int nd_solve_enqueue(nrs_ctx* c, NdSolver& S, double lam, const NdDev* al
 
 // leaf size of the dissection (nodes): ND_LEAFN unless NRS_ND_LEAF says otherwise (a tuning knob: part of the plan cache's key)
 static int nd_leaf_n(const nrs_ctx* c) {
-    if (const char* v = c->env("NRS_ND_LEAF")) return std::max(4, std::min(ND_LEAFN, atoi(v)));
+    if (c->dbg.is_set(SW_ND_LEAF)) return std::max(4, std::min(ND_LEAFN, c->dbg.int_of(SW_ND_LEAF)));
     return ND_LEAFN;
 }
 }  // namespace nrs

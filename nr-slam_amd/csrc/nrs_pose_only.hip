@@ -397,143 +397,6 @@ __global__ __launch_bounds__(64) void k_po_step(PoseOnlyArgs a, PoState* S, cons
 
 using namespace nrs;
 
-extern char** environ;
-namespace nrs {
-void DebugOpts::load_environment() {
-    kv.clear();
-    if (!environ) return;
-    const char* list = nullptr;
-    for (char** e = environ; *e; ++e) {
-        if (strncmp(*e, "NRS_", 4) != 0) continue;
-        const char* eq = strchr(*e, '=');
-        if (!eq) continue;
-        const std::string name(*e, eq - *e);
-        if (name == "NRS_DEBUG") { list = eq + 1; continue; }
-        kv.emplace_back(name, eq + 1);
-    }
-    for (const char* p = list; p && *p;) {                          // NRS_DEBUG="ND=0,NO_LDS=1": NAME=VALUE pairs, names without the NRS_ prefix
-        const char* end = strchr(p, ',');
-        const std::string item = end ? std::string(p, end - p) : std::string(p);
-        const size_t eq = item.find('=');
-        if (!item.empty()) set(("NRS_" + (eq == std::string::npos ? item : item.substr(0, eq))).c_str(), eq == std::string::npos ? "1" : item.c_str() + eq + 1);
-        p = end ? end + 1 : nullptr;
-    }
-}
-const char* process_debug_option(const char* name) { return DebugOpts::process().get(name); }
-const DebugOpts& DebugOpts::process() {
-    static const DebugOpts snap = [] { DebugOpts d; d.load_environment(); return d; }();
-    return snap;
-}
-}  // namespace nrs
-
-extern "C" int nrs_debug_set(nrs_ctx* c, const char* name, const char* value) {
-    if (!c || !name || strncmp(name, "NRS_", 4) != 0) return NRS_ERR_INVALID;
-    c->dbg.set(name, value);
-    return NRS_OK;
-}
-
-extern "C" void nrs_options_init(nrs_options* opt) {
-    if (!opt) return;
-    memset(opt, 0, sizeof(*opt));
-    opt->device = -1;
-    opt->struct_size = (uint32_t)sizeof(*opt);
-}
-
-extern "C" int nrs_create(nrs_ctx** out, const nrs_options* opt) {
-    if (!out) return NRS_ERR_INVALID;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return NRS_ERR_NO_DEVICE;
-    nrs_ctx* c = new (std::nothrow) nrs_ctx();
-    if (!c) return NRS_ERR_ALLOC;
-    memset(&c->opt, 0, sizeof(c->opt));
-    c->opt.device = -1;
-    if (opt) {
-        // the caller's struct may be shorter than this build's (an older header): its bytes only, defaults behind them
-        size_t n = opt->struct_size ? opt->struct_size : offsetof(nrs_options, direct_solve);
-        if (n < offsetof(nrs_options, pcg_rtol) || n > 4096) { delete c; return NRS_ERR_INVALID; }   // (shorter than the first field / an uninitialised word)
-        memcpy(&c->opt, opt, std::min(n, sizeof(c->opt)));
-        c->opt.struct_size = (uint32_t)sizeof(c->opt);
-    }
-    if (c->opt.direct_solve < 0 || c->opt.direct_solve > 2) c->opt.direct_solve = 0;
-    if (c->opt.embedded_solver < 0 || c->opt.embedded_solver > 2) c->opt.embedded_solver = 0;
-    if (c->opt.sharded_kft != 1) c->opt.sharded_kft = 0;
-    if (c->opt.pcg_rtol <= 0) c->opt.pcg_rtol = 1e-10;
-    c->dbg.load_environment();
-    if (const char* e = c->env("NRS_PCG_RTOL")) { const double v = atof(e); if (v > 0) c->opt.pcg_rtol = v; }   // experiments only
-    if (c->opt.pcg_max_iters <= 0) c->opt.pcg_max_iters = 2000;
-    if (c->opt.pcg_batch <= 0) c->opt.pcg_batch = 8;
-    c->err[0] = 0;
-    memset(&c->prof, 0, sizeof(c->prof));
-    int dev = c->opt.device;
-    if (dev < 0) {
-        if (hipGetDevice(&dev) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
-    }
-    if (dev >= ndev || hipSetDevice(dev) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
-    c->device = dev;
-    if (hipGetDeviceProperties(&c->prop, dev) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-        delete c;
-        return NRS_ERR_NO_DEVICE;
-    }
-    *out = c;
-    return NRS_OK;
-}
-
-extern "C" void nrs_destroy(nrs_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    nrs::dba_free(c);
-    nrs::klt_free(c);
-    nrs::shi_free(c);
-    nrs::front_free(c);
-    nrs::comm_free(c);
-    if (c->pin_scal) (void)hipHostFree(c->pin_scal);
-    if (c->pin_flags) (void)hipHostFree(c->pin_flags);
-    if (c->pin_spec_scal) (void)hipHostFree(c->pin_spec_scal);
-    if (c->pin_spec_flags) (void)hipHostFree(c->pin_spec_flags);
-    if (c->embwin_pin) (void)hipHostFree(c->embwin_pin);
-    for (int j = 0; j < 3; ++j) {
-        if (c->spec_stream[j]) { (void)hipStreamSynchronize(c->spec_stream[j]); (void)hipStreamDestroy(c->spec_stream[j]); }
-        if (c->spec_join[j]) (void)hipEventDestroy(c->spec_join[j]);
-    }
-    if (c->spec_fork) (void)hipEventDestroy(c->spec_fork);
-    for (int j = 0; j < 4; ++j) if (c->spec_back[j]) (void)hipEventDestroy(c->spec_back[j]);
-    if (c->arena_dba.base) (void)hipFree(c->arena_dba.base);
-    if (c->arena_trk.base) (void)hipFree(c->arena_trk.base);
-    c->release(c->po_uv); c->release(c->po_X); c->release(c->po_err);
-    c->release(c->po_level); c->release(c->po_out); c->release(c->po_trace); c->release(c->comm_flag); c->release(c->gather_ws); c->release(c->tap); c->release(c->pack_ws); c->release(c->pack_ws2); c->release(c->pack_ws3); c->release(c->pack_ws4); c->release(c->nd_skin); c->release(c->dba_skin); c->release(c->dba_kft); c->release(c->po_multi);
-    nrs::nd_cache_free(c);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-extern "C" const char* nrs_last_error(const nrs_ctx* c) { return c ? c->err : "null context"; }
-
-extern "C" int nrs_device_name(const nrs_ctx* c, char* buf, int32_t len) {
-    if (!c || !buf || len <= 0) return NRS_ERR_INVALID;
-    snprintf(buf, (size_t)len, "%s (%s, %d CUs)", c->prop.name, c->prop.gcnArchName, c->prop.multiProcessorCount);
-    return NRS_OK;
-}
-
-extern "C" int nrs_get_profile(const nrs_ctx* c, nrs_profile* out) {
-    if (!c || !out) return NRS_ERR_INVALID;
-    *out = c->prof;
-    return NRS_OK;
-}
-
-extern "C" int nrs_reset_profile(nrs_ctx* c) {
-    if (!c) return NRS_ERR_INVALID;
-    memset(&c->prof, 0, sizeof(c->prof));
-    return NRS_OK;
-}
-
-extern "C" void* nrs_stream(nrs_ctx* c) { return c ? (void*)c->stream : nullptr; }
-
 extern "C" int nrs_pose_only_solve(nrs_ctx* c, const nrs_camera* cam, int32_t n, const float* uv,
                                    const float* X, double pose_qt[7], uint8_t* inlier,
                                    nrs_lm_trace* trace) {
@@ -580,12 +443,11 @@ extern "C" int nrs_pose_only_solve(nrs_ctx* c, const nrs_camera* cam, int32_t n,
     // NRS_PO_MULTI_MIN moves the hand-over (tests run both forms on the same frames).  NRS_PO_NO_CACHE=1 keeps the single workgroup's
     // points in global memory at any n (the form of 7169 <= n < 32768); NRS_PO_MULTI_GROUPS=<g> caps the many-workgroup form's grid at g
     // workgroups (>= 1), so that a frame of a few hundred points takes several grid-stride trips and sums several slots.
-    int multi_min = 32768;                                    // (measured: 13.0 ms on one workgroup, 6.0 ms on many at 90k points; the two meet near 35k)
-    if (const char* ev = c->env("NRS_PO_MULTI_MIN")) multi_min = atoi(ev);
-    if (const char* ev = c->env("NRS_PO_NO_CACHE")) { if (atoi(ev) != 0) a.cache_pts = 0; }
+    const int multi_min = c->dbg.int_of(SW_PO_MULTI_MIN);     // 32768 (measured: 13.0 ms on one workgroup, 6.0 ms on many at 90k points; the two meet near 35k)
+    if (c->dbg.int_of(SW_PO_NO_CACHE) != 0) a.cache_pts = 0;
     if (n >= multi_min && n > 0) {
         int G = std::max(1, std::min(2 * c->prop.multiProcessorCount, (n + POM_THREADS - 1) / POM_THREADS));
-        if (const char* ev = c->env("NRS_PO_MULTI_GROUPS")) G = std::min(G, std::max(1, atoi(ev)));
+        if (c->dbg.is_set(SW_PO_MULTI_GROUPS)) G = std::min(G, std::max(1, c->dbg.int_of(SW_PO_MULTI_GROUPS)));
         NRS_TRY(c->ensure(c->po_multi, sizeof(PoState) + 256 + sizeof(double) * 32 * (size_t)G));
         PoState* S = c->po_multi.as<PoState>();
         double* part = reinterpret_cast<double*>(c->po_multi.as<char>() + ((sizeof(PoState) + 255) & ~(size_t)255));

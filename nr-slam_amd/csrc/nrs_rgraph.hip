@@ -461,7 +461,7 @@ int rg_max_cap_per_point(const nrs_rgraph* g) {
     size_t cand_max = 512;
     while (sizeof(unsigned long long) * (cand_max << 1) + 4096 + 512 <= (size_t)lds_max) cand_max <<= 1;
     int lim = std::min(g->cap, (int)cand_max - RG_SLACK);
-    if (const char* v = g->c->env("NRS_RG_MAX_CAP")) lim = std::max(1, std::min(lim, atoi(v)));   // (a lower limit, so that the tests reach the callers' "ran off at the limit" refusal)
+    if (g->c->dbg.is_set(SW_RG_MAX_CAP)) lim = std::max(1, std::min(lim, g->c->dbg.int_of(SW_RG_MAX_CAP)));   // (a lower limit, so that the tests reach the callers' "ran off at the limit" refusal)
     return lim;
 }
 
@@ -561,7 +561,7 @@ int rg_walk(nrs_rgraph* g, int n_map, const int* code, const uint8_t* is_node, i
     };
     int done = 0, hc[MAXP];
     int max_p = MAXP;                                              // (NRS_WALK_MAX_PASSES: a lower cap, so that the tests reach the caller's host fallback)
-    if (const char* v = c->env("NRS_WALK_MAX_PASSES")) max_p = std::max(1, std::min(MAXP, atoi(v)));
+    if (c->dbg.is_set(SW_WALK_MAX_PASSES)) max_p = std::max(1, std::min(MAXP, c->dbg.int_of(SW_WALK_MAX_PASSES)));
     while (done < max_p && !*converged) {                          // batches of passes, one look at their change counts per batch
         const int batch = std::min(done == 0 ? 6 : 8, max_p - done);
         for (int q = 0; q < batch; ++q) pass(done + q, 0);
@@ -631,7 +631,7 @@ static int rg_get_edges_impl(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, c
     // many rows (a2's first GetEdges of a frame: every tracked point): the kernel scans full symmetric copies of the two arrays it reads
     const uint8_t* st_f = nullptr;
     const float* maxd_f = nullptr;
-    if ((int64_t)n_ids * 8 >= g->cap && g->cap >= 512 && !c->env("NRS_RG_NO_MIRROR")) {
+    if ((int64_t)n_ids * 8 >= g->cap && g->cap >= 512 && !c->dbg.is_set(SW_RG_NO_MIRROR)) {
         const size_t cc = (size_t)g->cap * g->cap, o_m = (cc + 255) & ~(size_t)255;
         if (c->ensure(g->mir, o_m + 4 * cc) == NRS_OK) {           // (5 bytes per pair on top of the 13 of the state)
             const int nt = (g->cap + 63) / 64;

@@ -320,7 +320,7 @@ template <class Body> static int walk_to_completion(nrs_ctx* c, NeighbourSource&
 
 // ---- edge construction OPT:224-337: GetEdges of the optimised points and the walk over them (order as in the reference)
 static int build_edges(nrs_ctx* c, NeighbourSource& src, const th::FrameIndex& x, th::EdgeSet& es, StageTimer& mark) {
-    const bool host_walk = c->env("NRS_HOST_WALK") != nullptr;     // (A/B switch: the walk on the host, as before round 5)
+    const bool host_walk = c->dbg.is_set(SW_HOST_WALK);     // (A/B switch: the walk on the host, as before round 5)
     es.init(x);
     if (x.M < x.N) src.pass_over = &x.no_vertex;
     int ran_off_idx = -1;

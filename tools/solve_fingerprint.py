@@ -4,7 +4,9 @@ early, inner, lam, chi, chi_new, rho as raw bytes) and the downloaded poses and 
 one) and compare the outputs: a change that is meant to leave every launch and every number alone gives the same lines.  The bits depend
 on the compiler, so the output is a record (profiles/), not a golden test.
 
-    python tools/solve_fingerprint.py [substring of the case names] > fingerprint.txt"""
+    python tools/solve_fingerprint.py [substring of the case names | -substring: all but those] > fingerprint.txt
+
+The group `switches` (SWITCH_TRIPLES below) is a step of its own: `... "switches: "`, and `... "-switches: "` for the rest."""
 import hashlib
 import os
 import struct
@@ -32,7 +34,7 @@ def digest(trials, *arrays):
     return "%s trials=%d inner=%d" % (h.hexdigest(), len(trials), sum(t["inner"] for t in trials))
 
 
-def window(n, k, seed, env=(), steps=1, **opts):
+def window(n, k, seed, env=(), steps=1, pack=False, **opts):
     p = S.make_dba_problem(n, k, seed)
     e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
     cam = nrs.make_camera(p["model"], p["prm"])
@@ -42,6 +44,7 @@ def window(n, k, seed, env=(), steps=1, **opts):
     try:
         c = nrs.Context(**opts)
         c.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
+        head = pack_digest(c) if pack else ""
         trials = []
         for _ in range(steps):                                        # (the second step's batches are sized by the first's predictors)
             c.dba_reset()
@@ -52,7 +55,22 @@ def window(n, k, seed, env=(), steps=1, **opts):
         c.close()
     finally:
         nrs.debug_clear()
-    return digest(trials, pq, xyz)
+    return head + digest(trials, pq, xyz)
+
+
+def pack_digest(c):
+    """the 24 words of nrs_dba_pack_hash (the checksums of every packed array; word 21: built on the device) as one short hash"""
+    return "pack=%s " % hashlib.sha256(np.ascontiguousarray(c.dba_pack_hash()).tobytes()).hexdigest()[:16]
+
+
+def with_switches(env, fn):
+    """fn() with the switches of env set for the contexts it creates (and for the live ones)"""
+    for name in env:
+        nrs.debug_set(name, env[name])
+    try:
+        return fn()
+    finally:
+        nrs.debug_clear()
 
 
 def frame(direct, **opts):
@@ -98,7 +116,7 @@ def run_ranks(group, world, rank_main, out):
     return " | ".join("NOT FINISHED" if o is None else str(o) for o in out)
 
 
-def sharded(world=2, **opts):
+def sharded(world=2, pack=False, **opts):
     p = S.make_dba_problem(300, 4, 41)
     e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
     cam = nrs.make_camera(p["model"], p["prm"])
@@ -110,10 +128,11 @@ def sharded(world=2, **opts):
         c = nrs.Context(**opts)
         c.comm_init_local(group, r)
         c.dba_upload(cam, qt, p["lm_xyz"], p["lm_kf"], p["lm_uv"], e, p["scale"])
+        head = pack_digest(c) if pack else ""
         tr = nrs.Trace()
         c.dba_optimize(5, tr)
         pq, xyz = c.dba_download()
-        out[r] = digest(tr.trials, pq, xyz)
+        out[r] = head + digest(tr.trials, pq, xyz)
         c.close()
 
     return run_ranks(group, world, rank_main, out)
@@ -222,12 +241,44 @@ def one_call_sharded(embedded, world=2, env=(), **opts):
             out[r] = digest(tr.trials, pq, xyz)
         c.close()
 
-    for name in env:
-        nrs.debug_set(name, env[name])
-    try:
-        return run_ranks(group, world, rank_main, out)
-    finally:
-        nrs.debug_clear()
+    return with_switches(env, lambda: run_ranks(group, world, rank_main, out))
+
+
+# ---- the group `switches`: ONE switch set on a small case of a kind on which a test or a tool sets it, one line per triple -- the pack
+# hash where the case is a BA window, and the solve digest.  Equal-result A/B tests cannot see two rows of the switch table
+# (nr-slam_amd/csrc/nrs_switches.hpp) mapped to each other; the lines of two libraries run on THIS list can.  The list is written out
+# here, not read from the table: both libraries must run the same one.  (The four probe switches do nothing in a product build.)
+SWITCH_CASES = {
+    "window 500x5": lambda env: window(500, 5, 34, env, pack=True),
+    "window 5000x8": lambda env: window(5000, 8, 21, env, pack=True),
+    "embedded 300x4x40, factorisation": lambda env: with_switches(env, lambda: embedded(1)),
+    "embedded 300x4x40, PCG": lambda env: with_switches(env, lambda: embedded(2)),
+    "a2 frame, direct solver": lambda env: with_switches(env, lambda: frame(1)),
+    "a2 frame, PCG": lambda env: with_switches(env, lambda: frame(2)),
+    "sharded 300x4, 2 ranks": lambda env: with_switches(env, lambda: sharded(2, pack=True)),
+    "one call, 2 ranks: embedded 300x4x40": lambda env: one_call_sharded(True, env=env),
+}
+SWITCH_TRIPLES = [
+    ("NRS_HOST_PACK", "1", "window 500x5"), ("NRS_NO_FUSED", "1", "window 500x5"), ("NRS_NO_LDS", "1", "window 500x5"), ("NRS_NO_LDS", "0", "window 500x5"),
+    ("NRS_FUSED_MAX_ROWS", "0", "window 500x5"), ("NRS_SELL_T", "4", "window 500x5"), ("NRS_NO_EDGE_CHI", "1", "window 500x5"),
+    ("NRS_HOST_THREADS", "3", "window 500x5"), ("NRS_POISON", "1", "window 500x5"), ("NRS_CHECK_EVAL", "1", "window 500x5"),
+    ("NRS_HOST_PACK", "1", "window 5000x8"), ("NRS_DFORM", "1", "window 5000x8"), ("NRS_TILE_CUT_PCT", "60", "window 5000x8"), ("NRS_NO_ECD", "1", "window 5000x8"),
+    ("NRS_NO_H4", "1", "window 5000x8"), ("NRS_RC", "1", "window 5000x8"), ("NRS_RC", "2", "window 5000x8"), ("NRS_RC", "7", "window 5000x8"),
+    ("NRS_NT", "1", "window 5000x8"), ("NRS_SPEC_TRIALS", "1", "window 5000x8"), ("NRS_SPEC_FIRST", "2", "window 5000x8"), ("NRS_SPEC_MAX_ROWS", "1000", "window 5000x8"),
+    ("NRS_NO_REARM", "1", "window 5000x8"), ("NRS_HOST_THREADS", "1", "window 5000x8"),
+    ("NRS_KFT_TWO_LAUNCHES", "1", "embedded 300x4x40, factorisation"), ("NRS_KFT_SCALAR_SWEEP", "1", "embedded 300x4x40, factorisation"),
+    ("NRS_KFT_FOUR_WAVES", "1", "embedded 300x4x40, factorisation"), ("NRS_KFT_NO_RESIDUAL_TEST", "1", "embedded 300x4x40, factorisation"),
+    ("NRS_SKIN_OP_OWN_LAUNCH", "1", "embedded 300x4x40, PCG"), ("NRS_SKIN_ROWS_OWN_LAUNCH", "1", "embedded 300x4x40, PCG"), ("NRS_HIER", "1", "embedded 300x4x40, PCG"),
+    ("NRS_NO_LDS", "1", "embedded 300x4x40, PCG"),
+    ("NRS_ND_NO_CACHE", "1", "a2 frame, direct solver"), ("NRS_ND_CHAIN", "1", "a2 frame, direct solver"), ("NRS_ND_LEVELS", "1", "a2 frame, direct solver"),
+    ("NRS_ND_THREADS", "256", "a2 frame, direct solver"), ("NRS_ND_STEP32", "0", "a2 frame, direct solver"), ("NRS_ND_BACK_FLAGS", "1", "a2 frame, direct solver"),
+    ("NRS_ND_MAX_ROWS", "300", "a2 frame, direct solver"), ("NRS_ND_NO_SPLIT", "1", "a2 frame, direct solver"), ("NRS_SPEC_TRIALS", "0", "a2 frame, direct solver"),
+    ("NRS_SPEC_TRIALS", "3", "a2 frame, direct solver"), ("NRS_SPEC_FIXED", "2", "a2 frame, direct solver"), ("NRS_SPEC_FIRST", "3", "a2 frame, direct solver"),
+    ("NRS_SPEC_NO_ABORT", "1", "a2 frame, direct solver"), ("NRS_HOST_THREADS", "1", "a2 frame, direct solver"), ("NRS_HOST_WALK", "1", "a2 frame, direct solver"),
+    ("NRS_WALK_MAX_PASSES", "2", "a2 frame, direct solver"), ("NRS_COARSE_MIN_TILES", "0", "a2 frame, PCG"),
+    ("NRS_SHARD_FULL_VECTORS", "1", "sharded 300x4, 2 ranks"), ("NRS_TILE_CUT_PCT", "60", "sharded 300x4, 2 ranks"),
+    ("NRS_HOST_PACK", "1", "sharded 300x4, 2 ranks"), ("NRS_SHARD_EMBWIN_DEVICE", "1", "one call, 2 ranks: embedded 300x4x40"),
+]
 
 
 CASES = [
@@ -251,9 +302,10 @@ CASES = [
     ("one call, 2 thread ranks: embedded 300x4x40", lambda **o: one_call_sharded(True, **o)),
     ("one call, 2 ranks, SHARD_EMBWIN: embedded 300x4x40", lambda **o: one_call_sharded(True, env={"NRS_SHARD_EMBWIN_DEVICE": "1"}, **o)),
 ]
+CASES += [("switches: %s=%s, %s" % (sw, v, case), lambda sw=sw, v=v, case=case: SWITCH_CASES[case]({sw: v})) for sw, v, case in SWITCH_TRIPLES]
 
 if __name__ == "__main__":
     only = sys.argv[1] if len(sys.argv) > 1 else ""                  # (a substring of the case names: run those only, e.g. under a tracer)
-    for name, fn in [x for x in CASES if only in x[0]]:
-        for mode, opts in (("default", {}), ("exact_trials", {"exact_trials": 1})):
+    for name, fn in [x for x in CASES if (only[1:] not in x[0] if only.startswith("-") else only in x[0])]:
+        for mode, opts in (("default", {}),) if name.startswith("switches: ") else (("default", {}), ("exact_trials", {"exact_trials": 1})):
             print("%-50s %-13s %s" % (name, mode, fn(**opts)), flush=True)
