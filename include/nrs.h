@@ -723,6 +723,36 @@ int nrs_klt_insert_templates(nrs_ctx* ctx, int32_t count, const float* xy, const
 int nrs_klt_archive_templates(nrs_ctx* ctx, int32_t n, const int32_t* slots, const int32_t* keys);
 int nrs_klt_insert_archived(nrs_ctx* ctx, nrs_ctx* src, int32_t n, const int32_t* keys, const float* xy);
 
+/* Tracking::PointReuse (tracking.cc:394-506) in ONE call on the context that tracks the frame: nothing but the frame's bookkeeping is
+ * uploaded, the image is the pyramid this context's last nrs_klt_track[_front] / nrs_klt_set_reference[_front] built (levels 0 and 1
+ * of it are what PointReuse's own LucasKanadeTracker(21x21, maxLevel 1) would build), the templates are the archive entries whose key
+ * is the MAP INDEX, read in place.  Every fp32 expression below runs without contraction, in the stated order (DESIGN.md 4
+ * "PointReuse (one call)").
+ *   1 project    R from pose_qt (qx qy qz qw tx ty tz) entry by entry as 1 - 2(yy + zz), 2(xy - zw), ...;
+ *                pc_r = ((R_r0 X0 + R_r1 X1) + R_r2 X2) + t_r;  uv = the camera model's fp32 projection of pc
+ *   2 candidates ascending map index: (lost or (not present and pc.z >= 0)) and inside, where inside = 0 <= u < w and 0 <= v < h
+ *                (a NaN coordinate is outside), present = frame_slot[i] >= 0 and slot_status[frame_slot[i]] is TRACKED_WITH_3D or
+ *                JUST_TRIANGULATED, lost = i is listed in lost_ids.  Lost points are not tested for z (the reference does not either)
+ *   3 track      every candidate from status TRACKED_WITH_3D: reference point and initial guess = its uv (the seed), top level
+ *                min(1, pyramid levels - 1), this context's max_iters / epsilon / min_eig_threshold, then the SSIM gate with
+ *                min_ssim -- nrs_klt_track's arithmetic.  A key nothing was archived under is a template that was never filled:
+ *                OUT_IMAGE_BOUNDARIES, no error (an empty archive: every candidate ends so)
+ *   4 gate       accepted = status still TRACKED_WITH_3D and not (ex ex + ey ey > 5.99f), ex = u - x, ey = v - y
+ *   5 outputs    caller buffers of n_map entries (x 2 for seed_xy / xy), the first n_cand of them written: cand_id (map index),
+ *                seed_xy, xy, status, accepted (0 / 1); n_reused = number accepted
+ *   6 insert_new != 0: the accepted candidates with frame_slot < 0 are appended to this context's tracker in candidate order, each with
+ *                its xy as reference point -- the state nrs_klt_insert_archived(ctx, ctx, those ids, those xy) leaves; n_new = their
+ *                number (0 with insert_new = 0).  With no candidate the tracker is untouched.
+ * One host wait for n_cand, one at the end (the tracker's buffers growing aside).
+ * NRS_ERR_STATE: no pyramid has been built, or w x h is not its level 0.  NRS_ERR_INVALID: a null pointer, a negative count, a
+ * frame_slot at or above n_slots, a lost id outside the map, n_map at or above 2^20 (the archive's key bound), an archive of fewer
+ * than 2 levels (or, with insert_new, of fewer levels than this tracker has). */
+int nrs_point_reuse(nrs_ctx* ctx, const nrs_camera* cam, const float pose_qt[7], int32_t w, int32_t h, int32_t n_map,
+                    const float* map_pos /* n_map x 3 */, const int32_t* frame_slot /* n_map */, int32_t n_slots,
+                    const int32_t* slot_status /* n_slots */, int32_t n_lost, const int32_t* lost_ids, float min_ssim, int32_t insert_new,
+                    int32_t* n_cand, int32_t* cand_id, float* seed_xy, float* xy, int32_t* status, int32_t* accepted, int32_t* n_reused,
+                    int32_t* n_new);
+
 /* ---- f5: the image front end -- System::ImageProcessing + Masker::GetAllMasks (modules/SLAM/system.cc:113-201) ------------
  * What the reference does to every frame before the tracker is entered, on the device, with ONE upload of the frame:
  *   grey    cv::cvtColor(RGB2GRAY) (system.cc:193): 8-bit fixed point (R*9798 + G*19235 + B*3735 + 2^14) >> 15, channel 0 = R

@@ -20,6 +20,7 @@
 #include <vector>
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
+#include "nrs_reuse_host.hpp"
 
 namespace nrs {
 
@@ -51,6 +52,9 @@ struct KltState {
     DevBuf aI, aD, aMean, aValid, a_idx;
     int a_cap = 0, a_levels = 0;
     std::vector<uint8_t> a_has;
+    // ... and the same "has" byte per key on the device, for the kernels that address the archive by key (nrs_point_reuse); the upload,
+    // scratch and packed result of that call
+    DevBuf aHas, reuse_in, reuse_ws, reuse_out;
 };
 
 __device__ __host__ inline int reflect101(int i, int n) {
@@ -209,7 +213,21 @@ struct TrackArgs {
 
 __device__ inline bool usable(int s) { return s == NRS_TRACKED_WITH_3D || s == NRS_TRACKED || s == NRS_JUST_TRIANGULATED; }
 
-__global__ __launch_bounds__(64) void k_klt_track(TrackArgs a) {
+// Where point i's templates are: SlotOwn = the tracker's own slots, point-major (slot i, `levels` levels a point); SlotKeyed = the archive
+// entry under key[i], read in place (nrs_point_reuse: `levels` is then the archive's level count).  A key nothing was archived under --
+// beyond the archive, or its "has" byte zero -- is a template that was never filled at any level.
+struct SlotOwn {
+    __device__ size_t base(int i, int levels) const { return (size_t)i * levels; }
+    __device__ bool has(int) const { return true; }
+};
+struct SlotKeyed {
+    const int* key; const uint8_t* a_has; int a_cap;
+    __device__ size_t base(int i, int levels) const { return (size_t)key[i] * levels; }
+    __device__ bool has(int i) const { const int k = key[i]; return k >= 0 && k < a_cap && a_has[k] != 0; }
+};
+
+template <class Slot>
+__device__ inline void klt_track_point(const TrackArgs& a, const Slot sl) {
 #pragma clang fp contract(off)
     __shared__ float s_t[5][KA];          // per-pixel terms of b1, b2, A11, A22, A12
     __shared__ float s_j2[KA];
@@ -243,8 +261,8 @@ __global__ __launch_bounds__(64) void k_klt_track(TrackArgs a) {
             if (level == 0) st = NRS_OUT_IMAGE_BOUNDARIES;
             continue;
         }
-        const size_t slot = (size_t)i * a.levels + level;
-        if (!a.tValid[slot]) {
+        const size_t slot = sl.base(i, a.levels) + level;
+        if (!sl.has(i) || !a.tValid[slot]) {
             if (level == 0) st = NRS_OUT_IMAGE_BOUNDARIES;
             continue;
         }
@@ -336,6 +354,9 @@ __global__ __launch_bounds__(64) void k_klt_track(TrackArgs a) {
     if (lane == 0) { a.pts[2 * i] = ptx; a.pts[2 * i + 1] = pty; a.status[i] = st; }
 }
 
+__global__ __launch_bounds__(64) void k_klt_track(TrackArgs a) { klt_track_point(a, SlotOwn()); }
+__global__ __launch_bounds__(64) void k_klt_track_keyed(TrackArgs a, SlotKeyed sl) { klt_track_point(a, sl); }
+
 // ---------------------------------------------------------------------------------------------
 // SSIM gate at level 0 (LK:465-592), one wave per point
 // ---------------------------------------------------------------------------------------------
@@ -346,8 +367,9 @@ __device__ inline int div32_rne(int v) {                         // saturate_cas
     return q;
 }
 
-__global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, int levels, float* pts, int* status, const short* tI,
-                                                  const float* tMean, float min_ssim, float* ssim_out, int* n_good) {
+template <class Slot>
+__device__ inline void klt_ssim_point(const Pyr& pyr, int levels, float* pts, int* status, const short* tI, float min_ssim, float* ssim_out,
+                                      int* n_good, const Slot sl) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x, i = blockIdx.x;
     int st = status[i];
@@ -364,7 +386,7 @@ __global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, int levels, flo
     }
     int w00, w01, w10, w11;
     bilinear_weights(nx - (float)ix, ny - (float)iy, w00, w01, w10, w11);
-    const size_t slot = (size_t)i * levels;
+    const size_t slot = sl.base(i, levels);
     int cur[7], ref[7], sc = 0, sr = 0;
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
@@ -404,6 +426,16 @@ __global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, int levels, flo
     }
 }
 
+__global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, int levels, float* pts, int* status, const short* tI,
+                                                  const float* tMean, float min_ssim, float* ssim_out, int* n_good) {
+    klt_ssim_point(pyr, levels, pts, status, tI, min_ssim, ssim_out, n_good, SlotOwn());
+}
+// (a point that reaches the gate is still usable, so the track kernel found its key's entry: the gate reads no entry that is not there)
+__global__ __launch_bounds__(64) void k_klt_ssim_keyed(Pyr pyr, int levels, float* pts, int* status, const short* tI, float min_ssim, int* n_good,
+                                                        SlotKeyed sl) {
+    klt_ssim_point(pyr, levels, pts, status, tI, min_ssim, nullptr, n_good, sl);
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -415,7 +447,7 @@ static KltState* klt(nrs_ctx* c) {
 void klt_free(nrs_ctx* c) {
     if (!c->klt) return;
     KltState* k = c->klt;
-    DevBuf* bufs[] = {&k->pyr_buf, &k->img_in, &k->mask_in, &k->tI, &k->tD, &k->tMean, &k->tValid, &k->prev, &k->pts, &k->status, &k->misc, &k->aI, &k->aD, &k->aMean, &k->aValid, &k->a_idx};
+    DevBuf* bufs[] = {&k->pyr_buf, &k->img_in, &k->mask_in, &k->tI, &k->tD, &k->tMean, &k->tValid, &k->prev, &k->pts, &k->status, &k->misc, &k->aI, &k->aD, &k->aMean, &k->aValid, &k->a_idx, &k->aHas, &k->reuse_in, &k->reuse_ws, &k->reuse_out};
     for (auto b : bufs) c->release(*b);
     delete k;
     c->klt = nullptr;
@@ -684,12 +716,14 @@ extern "C" int nrs_klt_insert_templates(nrs_ctx* c, int32_t count, const float* 
 
 
 // ---- the template archive (device to device) ----------------------------------------------------------------------------------
-// one workgroup per template: `lv` levels of entry src_idx[i] (src_levels levels an entry) into entry dst_idx[i] (dst_levels)
+// one workgroup per template: `lv` levels of entry src_idx[i] (src_levels levels an entry) into entry dst_idx[i] (dst_levels);
+// d_has (nullable): the destination's per-entry "has" byte, set
 __global__ __launch_bounds__(256) void k_klt_copy_templates(int n, const int* __restrict__ src_idx, const int* __restrict__ dst_idx, int lv, int src_levels,
                                                             int dst_levels, const short* __restrict__ sI, const short2* __restrict__ sD, const float* __restrict__ sM,
-                                                            const uint8_t* __restrict__ sV, short* dI, short2* dD, float* dM, uint8_t* dV) {
+                                                            const uint8_t* __restrict__ sV, short* dI, short2* dD, float* dM, uint8_t* dV, uint8_t* d_has) {
     const int i = blockIdx.x;
     if (i >= n) return;
+    if (d_has && threadIdx.x == 0) d_has[dst_idx[i]] = 1;
     const size_t so = (size_t)src_idx[i] * src_levels, d_o = (size_t)dst_idx[i] * dst_levels;
     for (int e = threadIdx.x; e < lv * KA; e += 256) { dI[d_o * KA + e] = sI[so * KA + e]; dD[d_o * KA + e] = sD[so * KA + e]; }
     for (int e = threadIdx.x; e < 2 * lv; e += 256) dM[2 * d_o + e] = sM[2 * so + e];
@@ -702,33 +736,42 @@ constexpr int NRS_KLT_ARCHIVE_MAX_KEY = 1 << 20;
 static int klt_archive_reserve(nrs_ctx* c, KltState* k, int cap_want) {
     if (k->a_levels != k->levels && k->a_cap > 0) {                // (another level count: the archive starts over)
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        c->release(k->aI); c->release(k->aD); c->release(k->aMean); c->release(k->aValid);
+        c->release(k->aI); c->release(k->aD); c->release(k->aMean); c->release(k->aValid); c->release(k->aHas);
         k->a_cap = 0; k->a_has.clear();
     }
     k->a_levels = k->levels;
     if (cap_want <= k->a_cap) return NRS_OK;
     const int cap = std::max(cap_want + cap_want / 2, 256);
     const size_t L = (size_t)k->a_levels;
-    DevBuf nI, nD, nM, nV;
+    DevBuf nI, nD, nM, nV, nH;
     int rc = c->ensure(nI, sizeof(short) * KA * L * cap);
     if (rc == NRS_OK) rc = c->ensure(nD, sizeof(short2) * KA * L * cap);
     if (rc == NRS_OK) rc = c->ensure(nM, sizeof(float) * 2 * L * cap);
     if (rc == NRS_OK) rc = c->ensure(nV, L * cap);
-    if (rc != NRS_OK) { c->release(nI); c->release(nD); c->release(nM); c->release(nV); return rc; }
+    if (rc == NRS_OK) rc = c->ensure(nH, (size_t)cap);
+    if (rc != NRS_OK) { c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nH); return rc; }
+    {                                                              // the "has" bytes start at zero where the archive grows
+        const hipError_t he = hipMemsetAsync(nH.p, 0, (size_t)cap, c->stream);
+        if (he != hipSuccess) {
+            c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nH);
+            return c->fail(NRS_ERR_HIP, "template archive: clearing the grown buffers failed: %s", hipGetErrorString(he));
+        }
+    }
     if (k->a_cap > 0) {
         const size_t m = (size_t)k->a_cap;
         hipError_t he = hipMemcpyAsync(nI.p, k->aI.p, sizeof(short) * KA * L * m, hipMemcpyDeviceToDevice, c->stream);
         if (he == hipSuccess) he = hipMemcpyAsync(nD.p, k->aD.p, sizeof(short2) * KA * L * m, hipMemcpyDeviceToDevice, c->stream);
         if (he == hipSuccess) he = hipMemcpyAsync(nM.p, k->aMean.p, sizeof(float) * 2 * L * m, hipMemcpyDeviceToDevice, c->stream);
         if (he == hipSuccess) he = hipMemcpyAsync(nV.p, k->aValid.p, L * m, hipMemcpyDeviceToDevice, c->stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(nH.p, k->aHas.p, m, hipMemcpyDeviceToDevice, c->stream);
         if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
         if (he != hipSuccess) {                                    // (the new buffers do not outlive a failed copy; the archive stays as it was)
-            c->release(nI); c->release(nD); c->release(nM); c->release(nV);
+            c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nH);
             return c->fail(NRS_ERR_HIP, "template archive: copy to the grown buffers failed: %s", hipGetErrorString(he));
         }
     }
-    c->release(k->aI); c->release(k->aD); c->release(k->aMean); c->release(k->aValid);
-    k->aI = nI; k->aD = nD; k->aMean = nM; k->aValid = nV;
+    c->release(k->aI); c->release(k->aD); c->release(k->aMean); c->release(k->aValid); c->release(k->aHas);
+    k->aI = nI; k->aD = nD; k->aMean = nM; k->aValid = nV; k->aHas = nH;
     k->a_cap = cap;
     k->a_has.resize((size_t)cap, 0);
     return NRS_OK;
@@ -762,7 +805,7 @@ extern "C" int nrs_klt_archive_templates(nrs_ctx* c, int32_t n, const int32_t* s
     NRS_HIP(c, hipMemcpyAsync(d_idx + m, u_key.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_klt_copy_templates, dim3(m), dim3(256), 0, c->stream, m, d_idx, d_idx + m, k->levels, k->levels, k->a_levels,
                        k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>(),
-                       k->aI.as<short>(), k->aD.as<short2>(), k->aMean.as<float>(), k->aValid.as<uint8_t>());
+                       k->aI.as<short>(), k->aD.as<short2>(), k->aMean.as<float>(), k->aValid.as<uint8_t>(), k->aHas.as<uint8_t>());
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipStreamSynchronize(c->stream));                   // (the caller's index arrays are free again; the archive is complete for any stream)
     for (int i = 0; i < n; ++i) k->a_has[keys[i]] = 1;
@@ -792,9 +835,217 @@ extern "C" int nrs_klt_insert_archived(nrs_ctx* c, nrs_ctx* src, int32_t n, cons
     NRS_HIP(c, hipMemcpyAsync(k->prev.as<float>() + 2 * (size_t)k->n, xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_klt_copy_templates, dim3(n), dim3(256), 0, c->stream, n, d_idx, d_idx + n, k->levels, ks->a_levels, k->levels,
                        ks->aI.as<short>(), ks->aD.as<short2>(), ks->aMean.as<float>(), ks->aValid.as<uint8_t>(),
-                       k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>());
+                       k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>(), (uint8_t*)nullptr);
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     k->n += n;
+    return NRS_OK;
+}
+
+
+// ---- PointReuse in one call (tracking.cc:394-506; include/nrs.h nrs_point_reuse) -------------------------------------------------
+// Four launches on the pyramid this context's last Track / SetReferenceImage built: candidates (project, flag, compact), the two-level
+// tracker and its SSIM gate on the archive entries read in place by key, the 5.99 gate with the packed result and the ordered list
+// of new slots, and the device-to-device append of those slots.  The compactions are stable (candidate order is ascending map index):
+// ONE workgroup walks its list in chunks of REUSE_BLOCK and carries the running count, so no second launch and no wait between
+// workgroups is needed -- a map holds thousands of points, a handful of chunks.
+namespace nrs {
+
+constexpr int REUSE_BLOCK = 1024;
+
+struct ReuseIn {
+    Cam cam;
+    float R[9], t[3];
+    int w, h, n_map;
+    const float* map_pos; const int* frame_slot; const int* slot_status; const uint8_t* lost;
+};
+
+struct ReusePacked { unsigned cand, seed, xy, status, accepted; };          // word offsets of ReuseLayout
+
+// rank of this thread's flag among the workgroup's set flags (thread order) and their total: wave ballots + one LDS row of wave counts
+__device__ inline int block_rank(bool flag, int* s_wave, int& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                               // (the row's previous use is over)
+    if (lane == 0) s_wave[wv] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    total = 0;
+    for (int k = 0; k < REUSE_BLOCK / 64; ++k) { const int cnt = s_wave[k]; if (k < wv) off += cnt; total += cnt; }
+    return off + before;
+}
+
+// stages 1 + 2: pc = R X + t in the frame loop's float32 form, uv = project_f32(pc), the flags, and the stable compaction.  A candidate
+// leaves with its map index, its seed (reference point AND initial guess) and status TRACKED_WITH_3D.  hdr: n_cand, 0, 0, 0 (n_good)
+__global__ __launch_bounds__(REUSE_BLOCK) void k_reuse_candidates(ReuseIn a, int* hdr, int* cand_id, float* seed, float* xy, int* status) {
+#pragma clang fp contract(off)
+    __shared__ int s_wave[REUSE_BLOCK / 64];
+    int base = 0;
+    for (int c0 = 0; c0 < a.n_map; c0 += REUSE_BLOCK) {
+        const int i = c0 + (int)threadIdx.x;
+        bool cand = false;
+        float u = 0.f, v = 0.f;
+        if (i < a.n_map) {
+            const float X0 = a.map_pos[3 * i], X1 = a.map_pos[3 * i + 1], X2 = a.map_pos[3 * i + 2];
+            const float pcx = ((a.R[0] * X0 + a.R[1] * X1) + a.R[2] * X2) + a.t[0];
+            const float pcy = ((a.R[3] * X0 + a.R[4] * X1) + a.R[5] * X2) + a.t[1];
+            const float pcz = ((a.R[6] * X0 + a.R[7] * X1) + a.R[8] * X2) + a.t[2];
+            project_f32(a.cam, pcx, pcy, pcz, u, v);
+            const bool inside = u >= 0.f && u < (float)a.w && v >= 0.f && v < (float)a.h;          // (NaN compares false)
+            const int sl = a.frame_slot[i];
+            bool present = false;
+            if (sl >= 0) { const int s = a.slot_status[sl]; present = s == NRS_TRACKED_WITH_3D || s == NRS_JUST_TRIANGULATED; }
+            cand = (a.lost[i] != 0 || (!present && pcz >= 0.f)) && inside;      // lost points are not tested for z (tracking.cc:397-414)
+        }
+        int total;
+        const int r = block_rank(cand, s_wave, total);
+        if (cand) {
+            const int o = base + r;
+            cand_id[o] = i;
+            seed[2 * o] = u; seed[2 * o + 1] = v;
+            xy[2 * o] = u; xy[2 * o + 1] = v;
+            status[o] = NRS_TRACKED_WITH_3D;
+        }
+        base += total;
+    }
+    if (threadIdx.x == 0) { hdr[0] = base; hdr[1] = 0; hdr[2] = 0; hdr[3] = 0; }
+}
+
+// stages 4 + 5: accepted = still TRACKED_WITH_3D and within sqrt(5.99) px of the seed; the packed result; with insert_new the accepted
+// candidates the frame holds no slot for, in candidate order: their keys, and their xy as the reference points of slots n0, n0 + 1, ...
+__global__ __launch_bounds__(REUSE_BLOCK) void k_reuse_gate(int n_cand, const int* __restrict__ cand_id, const float* __restrict__ seed,
+                                                             const float* __restrict__ xy, const int* __restrict__ status,
+                                                             const int* __restrict__ frame_slot, int insert_new, int n0, float* prev, int* new_key,
+                                                             int* out, ReusePacked P) {
+#pragma clang fp contract(off)
+    __shared__ int s_wave[REUSE_BLOCK / 64];
+    int n_acc = 0, n_new = 0;
+    for (int c0 = 0; c0 < n_cand; c0 += REUSE_BLOCK) {
+        const int i = c0 + (int)threadIdx.x;
+        bool acc = false, nw = false;
+        int key = 0;
+        float x = 0.f, y = 0.f;
+        if (i < n_cand) {
+            key = cand_id[i];
+            x = xy[2 * i]; y = xy[2 * i + 1];
+            const float sx = seed[2 * i], sy = seed[2 * i + 1];
+            const float ex = sx - x, ey = sy - y;
+            const int st = status[i];
+            acc = st == NRS_TRACKED_WITH_3D && !(ex * ex + ey * ey > 5.99f);
+            nw = insert_new && acc && frame_slot[key] < 0;
+            out[P.cand + i] = key;
+            out[P.status + i] = st;
+            out[P.accepted + i] = acc ? 1 : 0;
+            float* of = reinterpret_cast<float*>(out);
+            of[P.seed + 2 * i] = sx; of[P.seed + 2 * i + 1] = sy;
+            of[P.xy + 2 * i] = x; of[P.xy + 2 * i + 1] = y;
+        }
+        int tot_a, tot_n;
+        block_rank(acc, s_wave, tot_a);
+        const int r = block_rank(nw, s_wave, tot_n);
+        if (nw) {
+            const int o = n_new + r;
+            new_key[o] = key;
+            prev[2 * (size_t)(n0 + o)] = x; prev[2 * (size_t)(n0 + o) + 1] = y;
+        }
+        n_acc += tot_a; n_new += tot_n;
+    }
+    if (threadIdx.x == 0) { out[0] = n_cand; out[1] = n_acc; out[2] = n_new; out[3] = 0; }
+}
+
+// stage 6: archive entry new_key[i] -> tracker slot n0 + i, `lv` levels (what nrs_klt_insert_archived copies); one workgroup per
+// candidate is launched, the ones at or beyond n_new (out[2]) leave
+__global__ __launch_bounds__(256) void k_reuse_append(const int* __restrict__ out, const int* __restrict__ new_key, int n0, int lv, int src_levels, int dst_levels,
+                                                      const short* __restrict__ sI, const short2* __restrict__ sD, const float* __restrict__ sM,
+                                                      const uint8_t* __restrict__ sV, short* dI, short2* dD, float* dM, uint8_t* dV) {
+    const int i = blockIdx.x;
+    if (i >= out[2]) return;
+    const size_t so = (size_t)new_key[i] * src_levels, d_o = (size_t)(n0 + i) * dst_levels;
+    for (int e = threadIdx.x; e < lv * KA; e += 256) { dI[d_o * KA + e] = sI[so * KA + e]; dD[d_o * KA + e] = sD[so * KA + e]; }
+    for (int e = threadIdx.x; e < 2 * lv; e += 256) dM[2 * d_o + e] = sM[2 * so + e];
+    for (int e = threadIdx.x; e < lv; e += 256) dV[d_o + e] = sV[so + e];
+}
+
+}  // namespace nrs
+
+extern "C" int nrs_point_reuse(nrs_ctx* c, const nrs_camera* cam, const float pose_qt[7], int32_t w, int32_t h, int32_t n_map, const float* map_pos,
+                               const int32_t* frame_slot, int32_t n_slots, const int32_t* slot_status, int32_t n_lost, const int32_t* lost_ids,
+                               float min_ssim, int32_t insert_new, int32_t* n_cand, int32_t* cand_id, float* seed_xy, float* xy, int32_t* status,
+                               int32_t* accepted, int32_t* n_reused, int32_t* n_new) {
+    if (!c) return NRS_ERR_INVALID;
+    const ReuseArgs ra{cam, cam ? cam->model : 0, pose_qt, w, h, n_map, map_pos, frame_slot, n_slots, slot_status, n_lost, lost_ids,
+                       {n_cand, cand_id, seed_xy, xy, status, accepted, n_reused, n_new}};
+    char msg[256];
+    if (reuse_check_args(ra, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    KltState* k = c->klt;
+    if (!k || k->pyr.n_levels <= 0 || !k->pyr_buf.p)
+        return c->fail(NRS_ERR_STATE, "nrs_point_reuse: no pyramid has been built (it tracks on the image of the last nrs_klt_track[_front] / nrs_klt_set_reference[_front])");
+    if (w != k->pyr.L[0].w || h != k->pyr.L[0].h)
+        return c->fail(NRS_ERR_STATE, "nrs_point_reuse: %d x %d is not the size of the pyramid this context holds (%d x %d)", w, h, k->pyr.L[0].w, k->pyr.L[0].h);
+    if (k->a_cap > 0 && k->a_levels < 2)
+        return c->fail(NRS_ERR_INVALID, "nrs_point_reuse: the archive holds %d level(s), PointReuse's tracker needs 2", k->a_levels);
+    if (insert_new && k->a_cap > 0 && k->levels > k->a_levels)
+        return c->fail(NRS_ERR_INVALID, "nrs_point_reuse: the archive holds %d levels, this tracker needs %d", k->a_levels, k->levels);
+    *n_cand = 0; *n_reused = 0; *n_new = 0;
+    if (n_map == 0) return NRS_OK;
+    NRS_HIP(c, hipSetDevice(c->device));
+    const ReuseUpload U((size_t)n_map, (size_t)n_slots);
+    const ReuseScratch S((size_t)n_map);
+    std::vector<char> up(U.bytes);
+    reuse_pack_upload(ra, up.data());
+    NRS_TRY(c->ensure(k->reuse_in, U.bytes));
+    NRS_TRY(c->ensure(k->reuse_ws, sizeof(int) * S.words));
+    NRS_HIP(c, hipMemcpyAsync(k->reuse_in.p, up.data(), U.bytes, hipMemcpyHostToDevice, c->stream));
+    char* d_in = k->reuse_in.as<char>();
+    int* ws = k->reuse_ws.as<int>();
+    ReuseIn in;
+    in.cam.model = cam->model;
+    for (int i = 0; i < 8; ++i) in.cam.p[i] = cam->params[i];
+    reuse_rotation(pose_qt, in.R);
+    for (int i = 0; i < 3; ++i) in.t[i] = pose_qt[4 + i];
+    in.w = w; in.h = h; in.n_map = n_map;
+    in.map_pos = reinterpret_cast<const float*>(d_in + U.pos); in.frame_slot = reinterpret_cast<const int*>(d_in + U.slot);
+    in.slot_status = reinterpret_cast<const int*>(d_in + U.status); in.lost = reinterpret_cast<const uint8_t*>(d_in + U.lost);
+    int* d_cand = ws + S.cand;
+    float *d_seed = reinterpret_cast<float*>(ws + S.seed), *d_xy = reinterpret_cast<float*>(ws + S.xy);
+    int *d_status = ws + S.status, *d_new_key = ws + S.new_key;
+    hipLaunchKernelGGL(k_reuse_candidates, dim3(1), dim3(REUSE_BLOCK), 0, c->stream, in, ws, d_cand, d_seed, d_xy, d_status);
+    NRS_HIP(c, hipGetLastError());
+    int n = 0;
+    NRS_HIP(c, hipMemcpyAsync(&n, ws, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));                   // the one wait before the last: n_cand sizes the launches below
+    if (n < 0 || n > n_map) return c->fail(NRS_ERR_HIP, "nrs_point_reuse: the candidate count came back as %d (map of %d)", n, n_map);
+    if (n == 0) return NRS_OK;                                     // (the tracker is untouched)
+    const int n0 = k->n;
+    if (insert_new) NRS_TRY(reserve_points(c, k, n0 + n, true));   // (room for every candidate; the buffers grow in amortised steps)
+    const ReuseLayout L((size_t)n);
+    NRS_TRY(c->ensure(k->reuse_out, sizeof(int) * L.words));
+    int* d_out = k->reuse_out.as<int>();
+    TrackArgs a;
+    a.pyr = k->pyr; a.n = n; a.levels = k->a_levels; a.max_level = 1; a.max_iters = k->max_iters;
+    a.eps = k->eps; a.min_eig = k->min_eig; a.initial_flow = 1;
+    a.prev = d_seed; a.pts = d_xy; a.status = d_status;
+    a.tI = k->aI.as<short>(); a.tD = k->aD.as<short2>(); a.tMean = k->aMean.as<float>(); a.tValid = k->aValid.as<uint8_t>();
+    const SlotKeyed sl{d_cand, k->aHas.as<uint8_t>(), k->a_cap};
+    hipLaunchKernelGGL(k_klt_track_keyed, dim3(n), dim3(64), 0, c->stream, a, sl);
+    hipLaunchKernelGGL(k_klt_ssim_keyed, dim3(n), dim3(64), 0, c->stream, k->pyr, k->a_levels, d_xy, d_status, a.tI, min_ssim, ws + 3, sl);
+    const ReusePacked P{(unsigned)L.cand, (unsigned)L.seed, (unsigned)L.xy, (unsigned)L.status, (unsigned)L.accepted};
+    hipLaunchKernelGGL(k_reuse_gate, dim3(1), dim3(REUSE_BLOCK), 0, c->stream, n, d_cand, d_seed, d_xy, d_status, in.frame_slot, insert_new ? 1 : 0, n0,
+                       k->prev.as<float>(), d_new_key, d_out, P);
+    if (insert_new)
+        hipLaunchKernelGGL(k_reuse_append, dim3(n), dim3(256), 0, c->stream, d_out, d_new_key, n0, k->levels, k->a_levels, k->levels,
+                           k->aI.as<short>(), k->aD.as<short2>(), k->aMean.as<float>(), k->aValid.as<uint8_t>(),
+                           k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>());
+    NRS_HIP(c, hipGetLastError());
+    std::vector<int32_t> packed(L.words);
+    NRS_HIP(c, hipMemcpyAsync(packed.data(), d_out, sizeof(int) * L.words, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    const ReuseOut out{n_cand, cand_id, seed_xy, xy, status, accepted, n_reused, n_new};
+    if (reuse_unpack(packed.data(), n, out) != 0) {
+        *n_cand = 0; *n_reused = 0; *n_new = 0;
+        return c->fail(NRS_ERR_HIP, "nrs_point_reuse: the packed result's header (%d, %d, %d) contradicts the candidate count %d", packed[0], packed[1], packed[2], n);
+    }
+    k->n = n0 + *n_new;
     return NRS_OK;
 }

@@ -24,7 +24,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_graph_select_neighbours", "nrs_graph_update", "nrs_track_deform_solve",
            "nrs_klt_configure", "nrs_klt_clear", "nrs_klt_num_points", "nrs_klt_set_reference",
            "nrs_klt_track", "nrs_klt_get_template", "nrs_klt_insert_template", "nrs_klt_get_templates",
-           "nrs_klt_insert_templates", "nrs_klt_archive_templates", "nrs_klt_insert_archived",
+           "nrs_klt_insert_templates", "nrs_klt_archive_templates", "nrs_klt_insert_archived", "nrs_point_reuse",
            "nrs_shi_configure", "nrs_shi_extract", "nrs_shi_buffers",
            "nrs_front_configure", "nrs_front_process", "nrs_klt_set_reference_front", "nrs_klt_track_front", "nrs_shi_extract_front",
            "nrs_comm_unique_id", "nrs_comm_init_rccl", "nrs_comm_rank", "nrs_shard_plan",
@@ -907,6 +907,29 @@ class Context:
         keys, xy = _i32(keys), _f32(xy).reshape(-1, 2)
         assert len(keys) == len(xy)
         self._chk(self.lib.nrs_klt_insert_archived(self.h, src.h, C.c_int32(len(keys)), _p(keys, C.c_int32), _p(xy, C.c_float)))
+
+    def point_reuse(self, cam, pose_q, pose_t, wh, map_pos, frame_slot, slot_status, lost, min_ssim=0.75, insert_new=True):
+        """Tracking::PointReuse in one call on this context's resident pyramid and archive (include/nrs.h nrs_point_reuse).  frame_slot: per
+        map point the frame slot that holds it or -1; slot_status: the frame's LandmarkStatus per slot; lost: map indices.  Returns
+        dict(n_cand, cand_id, seed_xy, xy, status, accepted (bool), n_reused, n_new), the arrays trimmed to n_cand."""
+        qt = np.concatenate([_f32(pose_q).reshape(4), _f32(pose_t).reshape(3)]).astype(np.float32)
+        map_pos = _f32(map_pos).reshape(-1, 3)
+        frame_slot, slot_status = _i32(frame_slot).reshape(-1), _i32(slot_status).reshape(-1)
+        lost = _i32(sorted(int(x) for x in lost)) if isinstance(lost, (set, frozenset)) else _i32(lost).reshape(-1)
+        n = len(map_pos)
+        assert len(frame_slot) == n
+        cap = max(n, 1)
+        cand, st, acc = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        seed, xy = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        n_cand, n_reused, n_new = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.nrs_point_reuse(
+            self.h, C.byref(cam), _p(qt, C.c_float), C.c_int32(int(wh[0])), C.c_int32(int(wh[1])), C.c_int32(n), _p(map_pos, C.c_float),
+            _p(frame_slot, C.c_int32), C.c_int32(len(slot_status)), _p(slot_status, C.c_int32), C.c_int32(len(lost)), _p(lost, C.c_int32),
+            C.c_float(min_ssim), C.c_int32(1 if insert_new else 0), C.byref(n_cand), _p(cand, C.c_int32), _p(seed, C.c_float), _p(xy, C.c_float),
+            _p(st, C.c_int32), _p(acc, C.c_int32), C.byref(n_reused), C.byref(n_new)))
+        k = n_cand.value
+        return dict(n_cand=k, cand_id=cand[:k].copy(), seed_xy=seed[:k].copy(), xy=xy[:k].copy(), status=st[:k].copy(), accepted=acc[:k] != 0,
+                    n_reused=n_reused.value, n_new=n_new.value)
 
     def klt_insert_templates(self, ts):
         """append several templates (each as returned by klt_get_template; levels beyond this tracker's are ignored)."""

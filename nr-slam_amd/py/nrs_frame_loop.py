@@ -4,7 +4,8 @@ Tracking::TrackImage (reference modules/tracking/tracking.cc:72-112): DataAssoci
 CameraPoseAndDeformationEstimation (:321-333) -> PointReuse (:394-506) -> KeyFrameInsertion
 cadence (:336-392) -> SetLastFrame.  It only orchestrates: every numerical step is a call through a
 *backend* -- `GpuBackend` = the C ABI of libnrs_hip.so through ctypes (one context for the main
-tracker, one for the two-level reuse tracker); the tests plug the oracle in behind the same calls.
+tracker, one for the two-level reuse tracker -- or, with device_reuse=True, PointReuse as one call
+on the main context: nrs_point_reuse); the tests plug the oracle in behind the same calls.
 
 Keyframes extract new Shi-Tomasi features (tracking.cc:350-372): they enter the frame
 as TRACKED observations without a map point and are followed by LK from then on.  The map is started by `MonoInitializer` +
@@ -85,9 +86,10 @@ def project_f32(model, prm, p):
 
 
 class GpuBackend:
-    """The product path: two nrs contexts (each owns one LucasKanadeTracker state)."""
+    """The product path: one nrs context for the main tracker and, made on first use, one for PointReuse's two-level tracker (with
+    device_reuse=True PointReuse is one call on the main context and the second one is never made)."""
 
-    def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None):
+    def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None, device_reuse=False):
         """n_nodes > 0: EMBEDDED-DEFORMATION mode (include/nrs.h nrs_track_deform_solve_embedded; needs the dense graph): n_nodes map points
         (farthest-point sampling on the initial map, nrs_skin_select_nodes) carry the deformation vertices for the whole sequence, every
         other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call).  Mapping
@@ -95,20 +97,30 @@ class GpuBackend:
         front: None / False = the images handed to the loop are grey and go to the tracker as they are, without masks (as before).  True or a
         list of filters (nrs.Context.front_configure) = the loop is handed the RAW frames of System::TrackImage (SLAM/system.cc:113-132): each
         is uploaded once through nrs_front_process, LK and Shi-Tomasi run on the resident grey image (tracking.cc:92,353,367) and
-        SetReferenceImage / ExtractFeatures take the resident Global mask.  Only PointReuse's own tracker, a second context, still gets
-        the grey bytes from the host."""
+        SetReferenceImage / ExtractFeatures take the resident Global mask.  PointReuse's own tracker, a second context, still gets
+        the grey bytes from the host -- unless device_reuse is on.
+        device_reuse: True = FrameLoop.point_reuse makes ONE call, nrs_point_reuse, on the main context: candidates, the two-level tracker on
+        the pyramid this frame's klt_track built, the 5.99 gate and the append of the new slots (include/nrs.h); no image goes anywhere.
+        False (the default) = the two-context path: host projection, reuse_track_archived on ctx_reuse, insert_archived."""
         self.nrs = nrs
         self.dense, self.cap, self.rg = dense_graph or n_nodes > 0, cap_per_point, None
         self.n_nodes, self.node_flag = n_nodes, None
         self.cam = nrs.make_camera(model, prm)
         self.ctx = nrs.Context(direct_solve=direct_solve)      # (nrs_options.direct_solve: the linear solver of the pose-and-deformation solve)
-        self.ctx_reuse = nrs.Context()
+        self._ctx_reuse = None                                 # (made by the first step that needs it: the ctx_reuse property)
+        self.device_reuse, self.n_device_reuse = bool(device_reuse), 0
         self.klt_opts = klt_opts
         self.ctx.klt_configure(klt_opts["win"], klt_opts["max_level"], klt_opts["max_iters"], klt_opts["epsilon"], klt_opts["min_eig"])
         self.front = bool(front) or isinstance(front, (list, tuple))
         self._front_im, self._front_gray = None, None
         if self.front:
             self.ctx.front_configure(front if isinstance(front, (list, tuple)) else ())
+
+    @property
+    def ctx_reuse(self):
+        if self._ctx_reuse is None:
+            self._ctx_reuse = self.nrs.Context()
+        return self._ctx_reuse
 
     # front mode: one nrs_front_process per frame.  The loop hands the SAME array to every step of a frame and starts each frame with
     # klt_track, which therefore always processes; the later steps process only when they see another array
@@ -149,6 +161,11 @@ class GpuBackend:
 
     def insert_archived(self, mps, xy):
         self.ctx.klt_insert_archived(self.ctx, mps, xy)
+
+    # PointReuse in one call on the main context (include/nrs.h nrs_point_reuse): the image is the pyramid of this frame's klt_track
+    def point_reuse(self, pose, wh, map_pos, frame_slot, slot_status, lost, min_ssim, insert_new=True):
+        self.n_device_reuse += 1
+        return self.ctx.point_reuse(self.cam, pose[0], pose[1], wh, map_pos, frame_slot, slot_status, lost, min_ssim, insert_new)
 
     def reuse_track_archived(self, im, pts, mps, min_ssim):
         o = self.klt_opts
@@ -285,7 +302,8 @@ class GpuBackend:
         if getattr(self, "ctx_stereo", None) is not None:
             self.ctx_stereo.close()
         self.ctx.close()
-        self.ctx_reuse.close()
+        if self._ctx_reuse is not None:
+            self._ctx_reuse.close()
 
 
 class MonoInitializer:
@@ -710,6 +728,13 @@ class FrameLoop:
         in_frame = np.full(len(self.map_pos), -1, np.int64)
         has_mp = self.map_index >= 0
         in_frame[self.map_index[has_mp]] = np.nonzero(has_mp)[0]
+        if self.dev_templates and getattr(self.b, "device_reuse", False) and hasattr(self.b, "point_reuse"):
+            # one backend call: candidates, tracking, gate and the append of the new slots' photometric information
+            r = self.b.point_reuse(self.pose, self.wh, self.map_pos, in_frame.astype(np.int32), self.status, sorted(int(x) for x in lost), 0.75, True)
+            if not r["n_cand"]:
+                self.last_reuse = dict(cand_id=np.zeros(0, np.int64), accepted=np.zeros(0, bool))
+                return 0
+            return self._reuse_bookkeeping(in_frame, np.asarray(r["cand_id"], np.int64), np.asarray(r["xy"], F32), np.asarray(r["accepted"], bool), True)
         pc = se3f_act(self.pose, self.map_pos)
         uv = self.project(pc) if len(pc) else np.zeros((0, 2), F32)
         inside = (uv[:, 0] >= 0) & (uv[:, 0] < w) & (uv[:, 1] >= 0) & (uv[:, 1] < h)
@@ -727,6 +752,7 @@ class FrameLoop:
             is_cand &= inside & ~np.isnan(uv).any(1)
         cand = np.nonzero(is_cand)[0]
         if not len(cand):
+            self.last_reuse = dict(cand_id=np.zeros(0, np.int64), accepted=np.zeros(0, bool))
             return 0
         seeds = uv[cand].astype(F32)
         if self.dev_templates:
@@ -738,6 +764,12 @@ class FrameLoop:
         ex = uv[cand, 0].astype(F32) - xy[:, 0].astype(F32)
         ey = uv[cand, 1].astype(F32) - xy[:, 1].astype(F32)
         ok = (np.asarray(st) == TRACKED_WITH_3D) & ~(ex * ex + ey * ey > F32(5.99))
+        return self._reuse_bookkeeping(in_frame, cand, xy, ok, False)
+
+    # tracking.cc:449-503: what the accepted candidates do to the frame.  appended: the backend has already appended the new slots'
+    # photometric information to its tracker (the one-call path)
+    def _reuse_bookkeeping(self, in_frame, cand, xy, ok, appended):
+        self.last_reuse = dict(cand_id=np.asarray(cand, np.int64).copy(), accepted=np.asarray(ok, bool).copy())      # (for tests and probes)
         slot = in_frame[cand]
         upd = ok & (slot >= 0)                          # the frame holds a slot for the point: it is refreshed
         if upd.any():
@@ -756,6 +788,8 @@ class FrameLoop:
             if self.mapping:                                       # a re-inserted map point gets a fresh class_id
                 self.kp_id = np.concatenate([self.kp_id, self.next_kp_id + np.arange(len(nm))])
                 self.next_kp_id += len(nm)
+            if appended:
+                return reused
             if self.dev_templates:
                 self.b.insert_archived(nm.astype(np.int32), xy[nk].astype(F32))
                 return reused
