@@ -842,7 +842,8 @@ int nrs_skin_select_nodes(nrs_ctx* ctx, int32_t n_points, const float* pos /* n_
  * THE INDEXING QUIRK.  FindEssentialWithRANSAC fills the inlier flags by COMPACT index; ReconstructEnvironment / ReconstructPoints read
  * inliers[idx], reference_keypoints_[idx] and current_keypoints_[idx] by KEYPOINT index over idx < n_matches (:266-267, :331-338).
  * compact_indexing = 0 restates exactly that (with every keypoint TRACKED the two coincide); 1 reads keypoint compact_map[idx] instead.
- * Not built: RefineSolution (never called in the reference) and the DBSCAN labels of FeatureTracksClustering (visualiser only). */
+ * Not built: RefineSolution (never called in the reference) and the DBSCAN labels of FeatureTracksClustering (visualiser only; Dbscan3D itself
+ * is nrs_dbscan3d, f8). */
 typedef struct {
     uint32_t struct_size;
     int32_t  n_hypotheses;        /* 0 = the reference's count, ComputeMaxTries(0.8, 0.95) = 16 (:78-81,130-132); 1..4096              */
@@ -932,6 +933,57 @@ int nrs_eval_rmse(int32_t n, const float* est_z, const float* gt_z, const uint8_
 int nrs_eval_frame(nrs_ctx* ctx, const nrs_camera* cam, const float pose_qt[7], int32_t n, const float* world_xyz, const float* xy,
                    const float* depth, int32_t w, int32_t h, int32_t stride, const float* gt_xyz, const int32_t* gt_status,
                    float* rmse, float* scale, int32_t counts[3], float* gt_world, int32_t* gt_status_out);
+
+/* ---- f8: stereo map initialisation -- Tracking::StereoMapInitialization (modules/tracking/tracking.cc:216-289) with Dbscan3D
+ * (modules/utilities/dbscan.cc:61-104).  Arithmetic of record: DESIGN.md 4 "Stereo map initialisation".
+ *
+ * nrs_dbscan3d.  mlpack is not in the tree, so the clustering rule is THIS PROJECT'S DEFINITION (parity unpinned):
+ *   neighbour   j != i and d2(i, j) <= eps * eps; d2 = (dx*dx + dy*dy) + dz*dz in fp64 on the fp32 coordinates converted to double, no
+ *               contraction; eps * eps one double product; the boundary is inclusive; a pair with a non-finite d2 is no neighbour pair
+ *   core        at least min_points neighbours (the point itself is not counted)
+ *   clusters    the connected components of the core points under the neighbour relation; raw labels 0, 1, ... in ascending order of a
+ *               component's lowest-index core point; a non-core point with a core neighbour takes the lowest raw label among its core
+ *               neighbours; every other point is noise, -1
+ *   ranking     (dbscan.cc:80-101) classes by raw label, size descending, ties by ascending raw key; with noise_competes = 1 noise is a
+ *               class with key -1 (as in the reference's std::map), with 0 noise keeps -1 and is never rank 0.  The reference's tie
+ *               comparator compares a label with a size (p1.first < p2.second): it is no ordering and is not reproduced
+ * raw_label (nullable) / label: n each; counts: clusters, noise points, size of label 0.  n up to 16384.  NRS_ERR_INVALID: n outside
+ * 0..16384, eps not finite or <= 0, min_points < 1, a null pointer. */
+#define NRS_DBSCAN_MAX_POINTS 16384
+int nrs_dbscan3d(nrs_ctx* ctx, int32_t n, const float* xyz /* n x 3 */, double eps, int32_t min_points, int32_t noise_competes,
+                 int32_t* raw_label /* n, nullable */, int32_t* label /* n */, int32_t counts[3]);
+
+typedef struct {
+    uint32_t struct_size;
+    float    bf;                  /* 3886.37: the matcher's baseline_ (baseline times focal length)                                     */
+    float    z_min, z_max;        /* 35.5, 70.5: the depth gate, both ends excluded (tracking.cc:229-233)                               */
+    double   eps;                 /* 2.5                                                                                                */
+    int32_t  min_points;          /* 5                                                                                                  */
+    int32_t  noise_competes;      /* 1: the reference's behaviour, noise can be the winning class                                       */
+} nrs_init_stereo_options;
+/* Caller-owned; struct_size must be set; every pointer may be NULL. */
+typedef struct {
+    uint32_t struct_size;
+    int32_t  verdict;             /* 0 ok; 1 no keypoint passed the gate (the reference would read an empty vector)                     */
+    int32_t  n_matched, n_gated, n_clusters, n_noise, n_selected;
+    float    median_depth;        /* nth_element at n_selected / 2 of the selected z (:239-248); NaN when nothing is selected           */
+    float*   xyz;                 /* n x 3: the matcher's, NaN where match_status != 0                                                  */
+    int32_t* match_status;        /* n, nrs_eval_status                                                                                 */
+    int32_t* code;                /* n: 0 selected; 1 matcher rejected; 2 depth outside the gate; 3 clustered but not rank 0            */
+    int32_t* raw_label;           /* n: nrs_dbscan3d's raw label of the gated points, -2 for codes 1 and 2                              */
+    int32_t* label;               /* n: the rank, likewise                                                                              */
+    int32_t* selected;            /* n (n_selected written): keypoint indices of the rank-0 points in keypoint order                    */
+    float*   selected_xyz;        /* n x 3 (n_selected rows written)                                                                    */
+} nrs_init_stereo_result;
+void nrs_init_stereo_options_init(nrs_init_stereo_options* opt);
+/* One upload of the two images and the keypoints, every stage on the device, one packed download:
+ *   1 the kernels of nrs_stereo_match_pattern (:226-228)     2 gate: status OK and z_min < z < z_max, float against float, a NaN
+ *   fails; survivors compacted stably in keypoint order (:229-233)     3 nrs_dbscan3d's kernels on them     4 the rank-0 points in
+ *   keypoint order (:254-263)     5 median_depth.  scale is the reference's constant 1.
+ * A verdict is not an error.  NRS_ERR_INVALID: a wrong struct_size, the matcher's own refusals, n > 16384, eps not finite or <= 0,
+ * min_points < 1, z_min >= z_max (or either NaN). */
+int nrs_init_stereo(nrs_ctx* ctx, const nrs_camera* cam, const nrs_init_stereo_options* opt, const uint8_t* left, const uint8_t* right,
+                    int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, nrs_init_stereo_result* out);
 
 #ifdef __cplusplus
 }

@@ -161,6 +161,14 @@ void front_free(nrs_ctx* ctx);
 // nrs_front.hip, for the *_front entry points of the tracker and the extractor: the resident image (NRS_FRONT_IMAGE_*) and, when asked for,
 // the Global mask of the last nrs_front_process -- packed w x h bytes on the device; NRS_ERR_STATE when there is none or its size differs
 int front_resident(nrs_ctx* ctx, const char* who, int w, int h, int image, int use_global_mask, const uint8_t** img, const uint8_t** mask);
+// nrs_eval.hip, for nrs_stereo_match_pattern and nrs_init_stereo (nrs_sinit.hip): the pattern matcher's refusals under the caller's name,
+// the bytes of its intermediates, and its launches on packed w x h images and n keypoints that are already on the device (n > 0; ws:
+// stereo_match_ws_bytes bytes, 256-byte aligned; d_score / d_match as long as the entry point's outputs, never null here)
+int stereo_match_check(nrs_ctx* ctx, const char* who, const nrs_camera* cam, const uint8_t* left, const uint8_t* right, int w, int h, int stride_l,
+                       int stride_r, int n, bool arrays_ok);
+size_t stereo_match_ws_bytes(nrs_ctx* ctx, int w, int h, int n);
+int stereo_match_enqueue(nrs_ctx* ctx, const nrs_camera* cam, float bf, int w, int h, int n, const uint8_t* d_left, const uint8_t* d_right,
+                         const float* d_xy, char* ws, float* d_xyz, int* d_status, double* d_score, int* d_match);
 // mask bytes under n device-side keypoints (x, y floats, truncated), downloaded to host_out
 int front_mask_at(nrs_ctx* ctx, const uint8_t* d_mask, int w, int h, const float* d_xy, int n, uint8_t* host_out);
 }

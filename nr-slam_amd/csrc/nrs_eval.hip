@@ -329,28 +329,86 @@ Cam to_cam(const nrs_camera* cam) {
 
 using namespace nrs;
 
+// ---- the pattern matcher behind its two entry points: nrs_stereo_match_pattern (upload / download shell below) and nrs_init_stereo
+// (nrs_sinit.hip), which keeps the images and the result on the device.  Both run exactly these launches.
+namespace nrs {
+namespace {
+struct StereoPlan {
+    StereoDims D;
+    bool plain;
+    int npad;
+    dim3 grid;
+    size_t n_chunks, npos;
+};
+StereoPlan stereo_plan(nrs_ctx* c, int w, int h, int n) {
+    StereoPlan P;
+    P.D.w = w; P.D.h = h;
+    P.D.Wr = (w - 3) - (ST_T - 1);
+    P.D.Hr = 2 * (int)((float)(h - 1) / 2.f - 2.f) - (ST_T - 1);
+    P.plain = c->dbg.is_set(SW_STEREO_NO_MFMA);
+    P.npad = (n + ST_NG - 1) / ST_NG * ST_NG;
+    P.grid = P.plain ? dim3((P.D.Wr + PL_B - 1) / PL_B, (P.D.Hr + PL_B - 1) / PL_B, P.npad / ST_NG)
+                     : dim3((P.D.Wr + MF_W - 1) / MF_W, (P.D.Hr + MF_H - 1) / MF_H, P.npad / ST_NG);
+    P.n_chunks = (size_t)P.grid.x * P.grid.y;
+    P.npos = (size_t)(P.D.Wr > 0 ? P.D.Wr : 0) * (size_t)(P.D.Hr > 0 ? P.D.Hr : 0);
+    return P;
+}
+}  // namespace
+
+int stereo_match_check(nrs_ctx* c, const char* who, const nrs_camera* cam, const uint8_t* left, const uint8_t* right, int w, int h, int stride_l,
+                       int stride_r, int n, bool arrays_ok) {
+    if (!cam || !left || !right || n < 0 || (n > 0 && !arrays_ok) || stride_l < w || stride_r < w) return c->fail(NRS_ERR_INVALID, "%s: bad argument", who);
+    if (w < 32 || h < 32 || w > 16384 || h > 16384) return c->fail(NRS_ERR_INVALID, "%s: image %d x %d (32 .. 16384 a side)", who, w, h);
+    const StereoPlan P = stereo_plan(c, w, h, 1);
+    if (P.D.Wr < 1 || P.D.Hr < 1) return c->fail(NRS_ERR_INVALID, "%s: no search position in a %d x %d image", who, w, h);
+    return NRS_OK;
+}
+
+size_t stereo_match_ws_bytes(nrs_ctx* c, int w, int h, int n) {
+    const StereoPlan P = stereo_plan(c, w, h, n);
+    return 2 * padded((size_t)P.npad * ST_KP) + 3 * padded(sizeof(int) * P.npad) + 2 * padded(sizeof(int) * P.npos) +
+           padded(sizeof(double) * P.n_chunks * P.npad) + padded(sizeof(int) * P.n_chunks * P.npad);
+}
+
+int stereo_match_enqueue(nrs_ctx* c, const nrs_camera* cam, float bf, int w, int h, int n, const uint8_t* d_left, const uint8_t* d_right,
+                         const float* d_xy, char* ws, float* d_xyz, int* d_status, double* d_score, int* d_match) {
+    const StereoPlan P = stereo_plan(c, w, h, n);
+    const StereoDims D = P.D;
+    const int npad = P.npad;
+    Carver cv(ws);
+    int8_t* d_Tp = cv.take<int8_t>((size_t)npad * ST_KP);
+    uint8_t* d_Tu = cv.take<uint8_t>((size_t)npad * ST_KP);
+    int* d_sumT = cv.take<int>(npad);
+    int* d_T2 = cv.take<int>(npad);
+    int* d_st = cv.take<int>(npad);
+    int* d_boxI = cv.take<int>(P.npos);
+    int* d_boxI2 = cv.take<int>(P.npos);
+    double* d_ps = cv.take<double>(P.n_chunks * npad);
+    int* d_pp = cv.take<int>(P.n_chunks * npad);
+    if (cv.used > stereo_match_ws_bytes(c, w, h, n)) return c->fail(NRS_ERR_STATE, "the pattern matcher's workspace accounting");
+    hipLaunchKernelGGL(k_stereo_prep, dim3((npad + 63) / 64), dim3(64), 0, c->stream, d_left, D, n, npad, d_xy, d_Tp, d_Tu, d_sumT, d_T2, d_st);
+    hipLaunchKernelGGL(k_stereo_box, dim3((D.Wr + 255) / 256, D.Hr), dim3(256), 0, c->stream, d_right, D, d_boxI, d_boxI2);
+    if (P.plain)
+        hipLaunchKernelGGL(k_corr_plain, P.grid, dim3(256), 0, c->stream, d_right, D, npad, d_Tu, d_T2, d_boxI2, d_ps, d_pp);
+    else
+        hipLaunchKernelGGL(k_corr_mfma, P.grid, dim3(256), 0, c->stream, d_right, D, npad, d_Tp, d_sumT, d_T2, d_boxI, d_boxI2, d_ps, d_pp);
+    hipLaunchKernelGGL(k_stereo_final, dim3((n + 63) / 64), dim3(64), 0, c->stream, D, n, npad, (int)P.n_chunks, d_xy, d_st, d_ps, d_pp, to_cam(cam), bf,
+                       d_xyz, d_status, d_score, d_match);
+    NRS_HIP(c, hipGetLastError());
+    return NRS_OK;
+}
+}  // namespace nrs
+
 extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float bf, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h,
                                         int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, float* xyz, int32_t* status,
                                         double* score, int32_t* match_xy) {
     if (!c) return NRS_ERR_INVALID;
-    if (!cam || !left || !right || n < 0 || (n > 0 && (!xy || !xyz || !status)) || stride_l < w || stride_r < w)
-        return c->fail(NRS_ERR_INVALID, "nrs_stereo_match_pattern: bad argument");
-    if (w < 32 || h < 32 || w > 16384 || h > 16384) return c->fail(NRS_ERR_INVALID, "nrs_stereo_match_pattern: image %d x %d (32 .. 16384 a side)", w, h);
-    StereoDims D;
-    D.w = w; D.h = h;
-    D.Wr = (w - 3) - (ST_T - 1);
-    D.Hr = 2 * (int)((float)(h - 1) / 2.f - 2.f) - (ST_T - 1);
-    if (D.Wr < 1 || D.Hr < 1) return c->fail(NRS_ERR_INVALID, "nrs_stereo_match_pattern: no search position in a %d x %d image", w, h);
+    NRS_TRY(stereo_match_check(c, "nrs_stereo_match_pattern", cam, left, right, w, h, stride_l, stride_r, n, xy && xyz && status));
     if (n == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
-    const bool plain = c->dbg.is_set(SW_STEREO_NO_MFMA);
-    const int npad = (n + ST_NG - 1) / ST_NG * ST_NG;
-    const dim3 grid = plain ? dim3((D.Wr + PL_B - 1) / PL_B, (D.Hr + PL_B - 1) / PL_B, npad / ST_NG)
-                            : dim3((D.Wr + MF_W - 1) / MF_W, (D.Hr + MF_H - 1) / MF_H, npad / ST_NG);
-    const size_t n_chunks = (size_t)grid.x * grid.y, npos = (size_t)D.Wr * D.Hr, img = (size_t)w * h;
-    const size_t bytes = 2 * padded(img) + padded(sizeof(float) * 2 * n) + 2 * padded((size_t)npad * ST_KP) + 3 * padded(sizeof(int) * npad) +
-                         2 * padded(sizeof(int) * npos) + padded(sizeof(double) * n_chunks * npad) + padded(sizeof(int) * n_chunks * npad) +
-                         padded(sizeof(float) * 3 * n) + padded(sizeof(int) * n) + padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n);
+    const size_t img = (size_t)w * h, ws_bytes = stereo_match_ws_bytes(c, w, h, n);
+    const size_t bytes = 2 * padded(img) + padded(sizeof(float) * 2 * n) + ws_bytes + padded(sizeof(float) * 3 * n) + padded(sizeof(int) * n) +
+                         padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n);
     DevBuf big;
     NRS_TRY(c->ensure(big, bytes));
     struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
@@ -358,15 +416,7 @@ extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float
     uint8_t* d_left = cv.take<uint8_t>(img);
     uint8_t* d_right = cv.take<uint8_t>(img);
     float* d_xy = cv.take<float>(2 * (size_t)n);
-    int8_t* d_Tp = cv.take<int8_t>((size_t)npad * ST_KP);
-    uint8_t* d_Tu = cv.take<uint8_t>((size_t)npad * ST_KP);
-    int* d_sumT = cv.take<int>(npad);
-    int* d_T2 = cv.take<int>(npad);
-    int* d_st = cv.take<int>(npad);
-    int* d_boxI = cv.take<int>(npos);
-    int* d_boxI2 = cv.take<int>(npos);
-    double* d_ps = cv.take<double>(n_chunks * npad);
-    int* d_pp = cv.take<int>(n_chunks * npad);
+    char* d_ws = cv.take<char>(ws_bytes);
     float* d_xyz = cv.take<float>(3 * (size_t)n);
     int* d_status = cv.take<int>(n);
     double* d_score = cv.take<double>(n);
@@ -375,15 +425,7 @@ extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float
     NRS_HIP(c, hipMemcpy2DAsync(d_left, w, left, stride_l, w, h, hipMemcpyHostToDevice, c->stream));      // packed on the device
     NRS_HIP(c, hipMemcpy2DAsync(d_right, w, right, stride_r, w, h, hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_stereo_prep, dim3((npad + 63) / 64), dim3(64), 0, c->stream, d_left, D, n, npad, d_xy, d_Tp, d_Tu, d_sumT, d_T2, d_st);
-    hipLaunchKernelGGL(k_stereo_box, dim3((D.Wr + 255) / 256, D.Hr), dim3(256), 0, c->stream, d_right, D, d_boxI, d_boxI2);
-    if (plain)
-        hipLaunchKernelGGL(k_corr_plain, grid, dim3(256), 0, c->stream, d_right, D, npad, d_Tu, d_T2, d_boxI2, d_ps, d_pp);
-    else
-        hipLaunchKernelGGL(k_corr_mfma, grid, dim3(256), 0, c->stream, d_right, D, npad, d_Tp, d_sumT, d_T2, d_boxI, d_boxI2, d_ps, d_pp);
-    hipLaunchKernelGGL(k_stereo_final, dim3((n + 63) / 64), dim3(64), 0, c->stream, D, n, npad, (int)n_chunks, d_xy, d_st, d_ps, d_pp, to_cam(cam), bf,
-                       d_xyz, d_status, d_score, d_match);
-    NRS_HIP(c, hipGetLastError());
+    NRS_TRY(stereo_match_enqueue(c, cam, bf, w, h, n, d_left, d_right, d_xy, d_ws, d_xyz, d_status, d_score, d_match));
     NRS_HIP(c, hipMemcpyAsync(xyz, d_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipMemcpyAsync(status, d_status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
     if (score) NRS_HIP(c, hipMemcpyAsync(score, d_score, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));

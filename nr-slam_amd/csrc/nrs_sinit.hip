@@ -1,0 +1,406 @@
+// f8: stereo map initialisation (include/nrs.h "f8"; DESIGN.md 4 "Stereo map initialisation").
+//   nrs_dbscan3d      Dbscan3D (modules/utilities/dbscan.cc:61-104): this project's definition of the clustering, the reference's ranking
+//   nrs_init_stereo   Tracking::StereoMapInitialization (modules/tracking/tracking.cc:216-289) up to the selected landmarks
+//
+// The clustering runs on m points whose count is a word on the device (nrs_init_stereo's gate leaves it there), in rows of W = ceil(cap / 64)
+// 64-bit words where cap is the host's bound on m.  Launches:
+//   k_db_neigh     a wave per point over all m: d2 in fp64 in the stated order, one ballot per 64 points = one word of the point's adjacency
+//                  row; the neighbour count, the core flag and the starting label (its own index for a core point)
+//   k_db_comp      ONE workgroup: the core bit mask, then minimum-label propagation over the core points with pointer jumping until a
+//                  whole sweep changes nothing.  Labels only ever decrease and are always the index of a core point of the same component,
+//                  so the fixed point -- every core point holds its component's lowest core index -- is unique and the result does not
+//                  depend on the order in which the waves run.  Then the roots (label == index) in ascending order get the raw labels:
+//                  a stable compaction in chunks of 1024 with a carried count (the form of nrs_point_reuse)
+//   k_db_border    a wave per point: a core point takes its root's raw label, a non-core point the lowest raw label among its core
+//                  neighbours, else -1; class sizes by integer atomics
+//   k_db_rank      a thread per class: rank = classes that are larger, or as large with a lower key (noise: key -1, class 0 here)
+//   k_db_label     label = rank of the raw label's class
+// nrs_init_stereo puts k_si_gate (status / depth gate, stable compaction in keypoint order) between the matcher's launches
+// (stereo_match_enqueue, nrs_eval.hip) and these, and k_si_select (codes, labels by keypoint, the rank-0 points in keypoint order) behind.
+// One workgroup never waits for another; the only persistent loop is inside k_db_comp's single workgroup.
+#include <climits>
+#include "nrs_ctx.hpp"
+#include "nrs_device.hpp"
+#include "nrs_sinit_host.hpp"
+
+namespace nrs {
+namespace {
+
+typedef unsigned long long u64;
+constexpr int DB_BLOCK = 1024;                            // the single-workgroup kernels: a compaction chunk
+constexpr int DB_WORDS = SINIT_MAX / 64;                  // words of the longest adjacency row (256)
+
+inline size_t padded(size_t bytes) { return (bytes + 255) / 256 * 256; }
+struct Carver {                                            // 256-byte aligned pieces of one allocation
+    char* p;
+    size_t used = 0;
+    explicit Carver(char* base) : p(base) {}
+    template <class T> T* take(size_t count) {
+        T* r = reinterpret_cast<T*>(p + used);
+        used += padded(count * sizeof(T));
+        return r;
+    }
+};
+
+// the clustering's device arrays for up to cap points
+struct DbWs {
+    int cap, W;
+    u64* adj;            // cap x W
+    u64* coremask;       // DB_WORDS
+    int* core;           // cap
+    int* lab;            // cap: lowest core index of the component so far (INT_MAX: not a core point)
+    int* rawid;          // cap: raw label of a root
+    int* size;           // cap + 1: class sizes, noise first
+    int* rank;           // cap + 1
+};
+size_t db_ws_bytes(int cap) {
+    const size_t W = (size_t)(cap + 63) / 64;
+    return padded(sizeof(u64) * (size_t)cap * W) + padded(sizeof(u64) * DB_WORDS) + 3 * padded(sizeof(int) * (size_t)cap) +
+           2 * padded(sizeof(int) * ((size_t)cap + 1));
+}
+DbWs db_carve(char* base, int cap) {
+    Carver cv(base);
+    DbWs w;
+    w.cap = cap; w.W = (cap + 63) / 64;
+    w.adj = cv.take<u64>((size_t)cap * w.W);
+    w.coremask = cv.take<u64>(DB_WORDS);
+    w.core = cv.take<int>(cap);
+    w.lab = cv.take<int>(cap);
+    w.rawid = cv.take<int>(cap);
+    w.size = cv.take<int>((size_t)cap + 1);
+    w.rank = cv.take<int>((size_t)cap + 1);
+    return w;
+}
+
+__device__ inline int ld_relaxed(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline int wave_min(int v) {
+    for (int m = 1; m < 64; m <<= 1) v = min(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ inline int lowest_bit(u64 b) { return __ffsll((long long)b) - 1; }
+
+// rank of this thread's flag among the workgroup's set flags (thread order) and their total: wave ballots + one LDS row of wave counts
+__device__ inline int db_block_rank(bool flag, int* s_wave, int& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const u64 m = __ballot(flag);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                               // (the row's previous use is over)
+    if (lane == 0) s_wave[wv] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    total = 0;
+    for (int k = 0; k < DB_BLOCK / 64; ++k) { const int cnt = s_wave[k]; if (k < wv) off += cnt; total += cnt; }
+    return off + before;
+}
+
+__global__ __launch_bounds__(256) void k_db_neigh(const int* __restrict__ d_m, int cap, int W, const float* __restrict__ xyz, double eps2,
+                                                  int min_points, u64* __restrict__ adj, int* __restrict__ core, int* __restrict__ lab) {
+#pragma clang fp contract(off)
+    const int m = min(*d_m, cap);
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= m) return;                                            // (uniform over the wave)
+    const double xi = (double)xyz[3 * i], yi = (double)xyz[3 * i + 1], zi = (double)xyz[3 * i + 2];
+    const int Wm = (m + 63) / 64;
+    int cnt = 0;
+    for (int wd = 0; wd < Wm; ++wd) {
+        const int j = wd * 64 + lane;
+        bool nb = false;
+        if (j < m && j != i) {
+            const double dx = (double)xyz[3 * j] - xi, dy = (double)xyz[3 * j + 1] - yi, dz = (double)xyz[3 * j + 2] - zi;
+            const double xx = dx * dx;
+            const double yy = dy * dy;
+            const double zz = dz * dz;
+            const double s = xx + yy;
+            const double d2 = s + zz;
+            nb = d2 <= eps2;                                       // inclusive; NaN and +inf compare false
+        }
+        const u64 word = __ballot(nb);
+        if (lane == 0) adj[(size_t)i * W + wd] = word;
+        cnt += __popcll(word);
+    }
+    if (lane == 0) {
+        const bool c = cnt >= min_points;
+        core[i] = c ? 1 : 0;
+        lab[i] = c ? i : INT_MAX;
+    }
+}
+
+__global__ __launch_bounds__(DB_BLOCK) void k_db_comp(const int* __restrict__ d_m, int cap, int W, const u64* __restrict__ adj,
+                                                      const int* __restrict__ core, int* lab, u64* __restrict__ coremask,
+                                                      int* __restrict__ rawid, int* __restrict__ size, int* __restrict__ counts) {
+    __shared__ u64 s_core[DB_WORDS];
+    __shared__ int s_wave[DB_BLOCK / 64];
+    __shared__ int s_changed;
+    const int m = min(*d_m, cap);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int Wm = (m + 63) / 64;
+    for (int k = tid; k < DB_WORDS; k += DB_BLOCK) s_core[k] = 0ull;
+    __syncthreads();
+    for (int c0 = 0; c0 < m; c0 += DB_BLOCK) {
+        const int i = c0 + tid;
+        const u64 mask = __ballot(i < m && core[i] != 0);
+        if (lane == 0) s_core[(c0 >> 6) + wv] = mask;              // (c0 <= 15360: word (c0 >> 6) + wv <= 255)
+    }
+    __syncthreads();
+    for (int k = tid; k < DB_WORDS; k += DB_BLOCK) coremask[k] = s_core[k];
+    // minimum-label propagation, a wave per core point and sweep; every value read is a label some wave wrote or the starting one
+    for (;;) {
+        __syncthreads();
+        if (tid == 0) s_changed = 0;
+        __syncthreads();
+        for (int i = wv; i < m; i += DB_BLOCK / 64) {
+            if (!((s_core[i >> 6] >> (i & 63)) & 1ull)) continue;  // (uniform over the wave)
+            const int cur = ld_relaxed(lab + i);
+            int mn = cur;
+            for (int wd = lane; wd < Wm; wd += 64) {
+                u64 bits = adj[(size_t)i * W + wd] & s_core[wd];
+                while (bits) {
+                    const int j = wd * 64 + lowest_bit(bits);
+                    bits &= bits - 1ull;
+                    mn = min(mn, ld_relaxed(lab + j));
+                }
+            }
+            mn = wave_min(mn);
+            for (int r = ld_relaxed(lab + mn); r < mn; r = ld_relaxed(lab + mn)) mn = r;      // pointer jumping: strictly decreasing
+            if (mn < cur && lane == 0) { atomicMin(lab + i, mn); s_changed = 1; }
+        }
+        __syncthreads();
+        if (!s_changed) break;
+    }
+    // raw labels of the roots in ascending index; the class sizes start at 0
+    for (int k = tid; k <= m; k += DB_BLOCK) size[k] = 0;
+    int base = 0;
+    for (int c0 = 0; c0 < m; c0 += DB_BLOCK) {
+        const int i = c0 + tid;
+        const bool root = i < m && core[i] != 0 && ld_relaxed(lab + i) == i;
+        int total;
+        const int r = db_block_rank(root, s_wave, total);
+        if (root) rawid[i] = base + r;
+        base += total;
+    }
+    if (tid == 0) { counts[0] = base; counts[1] = 0; counts[2] = 0; }
+}
+
+__global__ __launch_bounds__(256) void k_db_border(const int* __restrict__ d_m, int cap, int W, const u64* __restrict__ adj,
+                                                   const u64* __restrict__ coremask, const int* __restrict__ core, const int* __restrict__ lab,
+                                                   const int* __restrict__ rawid, int* __restrict__ raw, int* size) {
+    const int m = min(*d_m, cap);
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= m) return;
+    int r;
+    if (core[i]) r = rawid[lab[i]];
+    else {
+        const int Wm = (m + 63) / 64;
+        int mn = INT_MAX;
+        for (int wd = lane; wd < Wm; wd += 64) {
+            u64 bits = adj[(size_t)i * W + wd] & coremask[wd];
+            while (bits) {
+                const int j = wd * 64 + lowest_bit(bits);
+                bits &= bits - 1ull;
+                mn = min(mn, rawid[lab[j]]);
+            }
+        }
+        mn = wave_min(mn);
+        r = mn == INT_MAX ? -1 : mn;
+    }
+    if (lane == 0) { raw[i] = r; atomicAdd(size + (r + 1), 1); }
+}
+
+__global__ void k_db_rank(int cap, int noise_competes, const int* __restrict__ size, int* __restrict__ rank, int* counts) {
+    const int ncl = min(counts[0], cap);
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;           // class k has the key k - 1
+    if (k > ncl) return;
+    const int sz = size[k];
+    if (k == 0) {
+        counts[1] = sz;
+        if (!noise_competes) { rank[0] = -1; return; }
+    }
+    int r = 0;
+    for (int k2 = noise_competes ? 0 : 1; k2 <= ncl; ++k2) {
+        const int s2 = size[k2];
+        if (s2 > sz || (s2 == sz && k2 < k)) ++r;
+    }
+    rank[k] = r;
+    if (r == 0) counts[2] = sz;
+}
+
+__global__ void k_db_label(const int* __restrict__ d_m, int cap, const int* __restrict__ raw, const int* __restrict__ rank, int* __restrict__ label) {
+    const int m = min(*d_m, cap);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) label[i] = rank[raw[i] + 1];
+}
+
+// the five launches on cap >= 1; d_m, xyz, raw, label and counts are device pointers (raw / label: cap entries, counts: 3)
+void dbscan_enqueue(nrs_ctx* c, const DbWs& w, const int* d_m, const float* d_xyz, double eps, int min_points, int noise_competes, int* d_raw,
+                    int* d_label, int* d_counts) {
+    const double eps2 = eps * eps;
+    const int cap = w.cap;
+    hipLaunchKernelGGL(k_db_neigh, dim3((cap + 3) / 4), dim3(256), 0, c->stream, d_m, cap, w.W, d_xyz, eps2, min_points, w.adj, w.core, w.lab);
+    hipLaunchKernelGGL(k_db_comp, dim3(1), dim3(DB_BLOCK), 0, c->stream, d_m, cap, w.W, w.adj, w.core, w.lab, w.coremask, w.rawid, w.size, d_counts);
+    hipLaunchKernelGGL(k_db_border, dim3((cap + 3) / 4), dim3(256), 0, c->stream, d_m, cap, w.W, w.adj, w.coremask, w.core, w.lab, w.rawid, d_raw, w.size);
+    hipLaunchKernelGGL(k_db_rank, dim3((cap + 1 + 255) / 256), dim3(256), 0, c->stream, cap, noise_competes ? 1 : 0, w.size, w.rank, d_counts);
+    hipLaunchKernelGGL(k_db_label, dim3((cap + 255) / 256), dim3(256), 0, c->stream, d_m, cap, d_raw, w.rank, d_label);
+}
+
+struct SiPacked { unsigned xyz, status, code, raw, label, selected, sel_xyz; };          // word offsets of SinitLayout
+
+// tracking.cc:229-233: status OK and z_min < z < z_max (a NaN fails), survivors in keypoint order.  hdr[0] n_matched, hdr[1] n_gated
+// (the clustering's point count); codes 1 / 2 are final, a survivor's code is written by k_si_select
+__global__ __launch_bounds__(DB_BLOCK) void k_si_gate(int n, float z_min, float z_max, int* out, SiPacked P, int* __restrict__ gidx,
+                                                      float* __restrict__ gxyz) {
+    __shared__ int s_wave[DB_BLOCK / 64];
+    const float* of = reinterpret_cast<const float*>(out);
+    int n_ok = 0, n_gate = 0;
+    for (int c0 = 0; c0 < n; c0 += DB_BLOCK) {
+        const int i = c0 + (int)threadIdx.x;
+        bool ok = false, pass = false;
+        float x = 0.f, y = 0.f, z = 0.f;
+        if (i < n) {
+            ok = out[P.status + i] == NRS_EVAL_OK;
+            x = of[P.xyz + 3 * i]; y = of[P.xyz + 3 * i + 1]; z = of[P.xyz + 3 * i + 2];
+            pass = ok && z > z_min && z < z_max;
+            out[P.code + i] = !ok ? 1 : (pass ? 0 : 2);
+            out[P.raw + i] = -2;
+            out[P.label + i] = -2;
+        }
+        int tot_ok, tot;
+        db_block_rank(ok, s_wave, tot_ok);
+        const int r = db_block_rank(pass, s_wave, tot);
+        if (pass) {
+            const int o = n_gate + r;
+            gidx[o] = i;
+            gxyz[3 * o] = x; gxyz[3 * o + 1] = y; gxyz[3 * o + 2] = z;
+        }
+        n_ok += tot_ok; n_gate += tot;
+    }
+    if (threadIdx.x == 0) { out[0] = n_ok; out[1] = n_gate; out[2] = 0; out[3] = 0; out[4] = 0; out[5] = 0; out[6] = 0; out[7] = 0; }
+}
+
+// tracking.cc:254-263: the points of rank 0 in keypoint order; every clustered point's labels go back to its keypoint
+__global__ __launch_bounds__(DB_BLOCK) void k_si_select(int n, const int* __restrict__ gidx, const float* __restrict__ gxyz,
+                                                        const int* __restrict__ raw, const int* __restrict__ label, const int* __restrict__ counts,
+                                                        int* out, SiPacked P) {
+    __shared__ int s_wave[DB_BLOCK / 64];
+    float* of = reinterpret_cast<float*>(out);
+    const int m = min(out[1], n);
+    int n_sel = 0;
+    for (int c0 = 0; c0 < m; c0 += DB_BLOCK) {
+        const int o = c0 + (int)threadIdx.x;
+        bool sel = false;
+        int i = 0;
+        if (o < m) {
+            i = gidx[o];
+            const int l = label[o];
+            sel = l == 0;
+            out[P.raw + i] = raw[o];
+            out[P.label + i] = l;
+            out[P.code + i] = sel ? 0 : 3;
+        }
+        int tot;
+        const int r = db_block_rank(sel, s_wave, tot);
+        if (sel) {
+            const int s = n_sel + r;
+            out[P.selected + s] = i;
+            of[P.sel_xyz + 3 * s] = gxyz[3 * o]; of[P.sel_xyz + 3 * s + 1] = gxyz[3 * o + 1]; of[P.sel_xyz + 3 * s + 2] = gxyz[3 * o + 2];
+        }
+        n_sel += tot;
+    }
+    if (threadIdx.x == 0) { out[2] = counts[0]; out[3] = counts[1]; out[4] = n_sel; out[5] = counts[2]; }
+}
+
+}  // namespace
+}  // namespace nrs
+
+using namespace nrs;
+
+extern "C" int nrs_dbscan3d(nrs_ctx* c, int32_t n, const float* xyz, double eps, int32_t min_points, int32_t noise_competes, int32_t* raw_label,
+                            int32_t* label, int32_t counts[3]) {
+    if (!c) return NRS_ERR_INVALID;
+    char msg[256];
+    if (dbscan_check_args(n, xyz, eps, min_points, label, counts, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    counts[0] = counts[1] = counts[2] = 0;
+    if (n == 0) return NRS_OK;
+    NRS_HIP(c, hipSetDevice(c->device));
+    // in: m | xyz[3n];  out: counts[4] | raw[n] | label[n], one download
+    const size_t in_bytes = padded(sizeof(int)) + padded(sizeof(float) * 3 * (size_t)n), out_words = 4 + 2 * (size_t)n;
+    const size_t bytes = in_bytes + padded(sizeof(int) * out_words) + db_ws_bytes(n);
+    DevBuf big;
+    NRS_TRY(c->ensure(big, bytes));
+    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
+    Carver cv(big.as<char>());
+    int* d_m = cv.take<int>(1);
+    float* d_xyz = cv.take<float>(3 * (size_t)n);
+    int* d_out = cv.take<int>(out_words);
+    const DbWs w = db_carve(big.as<char>() + cv.used, n);
+    NRS_HIP(c, hipMemcpyAsync(d_m, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    dbscan_enqueue(c, w, d_m, d_xyz, eps, min_points, noise_competes, d_out + 4, d_out + 4 + n, d_out);
+    NRS_HIP(c, hipGetLastError());
+    std::vector<int32_t> host(out_words);
+    NRS_HIP(c, hipMemcpyAsync(host.data(), d_out, sizeof(int) * out_words, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (host[0] < 0 || host[0] > n || host[1] < 0 || host[1] > n || host[2] < 0 || host[2] > n)
+        return c->fail(NRS_ERR_HIP, "nrs_dbscan3d: the counts came back as (%d, %d, %d) for %d points", host[0], host[1], host[2], n);
+    counts[0] = host[0]; counts[1] = host[1]; counts[2] = host[2];
+    if (raw_label) memcpy(raw_label, host.data() + 4, sizeof(int32_t) * (size_t)n);
+    memcpy(label, host.data() + 4 + n, sizeof(int32_t) * (size_t)n);
+    return NRS_OK;
+}
+
+extern "C" void nrs_init_stereo_options_init(nrs_init_stereo_options* opt) {
+    if (opt) sinit_options_init(opt);
+}
+
+extern "C" int nrs_init_stereo(nrs_ctx* c, const nrs_camera* cam, const nrs_init_stereo_options* opt, const uint8_t* left, const uint8_t* right,
+                               int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, nrs_init_stereo_result* out) {
+    if (!c) return NRS_ERR_INVALID;
+    char msg[256];
+    if (sinit_check_args(opt, out, n, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    NRS_TRY(stereo_match_check(c, "nrs_init_stereo", cam, left, right, w, h, stride_l, stride_r, n, xy != nullptr));
+    sinit_clear(out);
+    if (n == 0) return NRS_OK;
+    NRS_HIP(c, hipSetDevice(c->device));
+    const SinitUpload U((size_t)w, (size_t)h, (size_t)n);
+    const SinitLayout L((size_t)n);
+    const size_t ws_bytes = stereo_match_ws_bytes(c, w, h, n);
+    const size_t bytes = padded(U.bytes) + ws_bytes + padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n) + padded(sizeof(int) * L.words) +
+                         padded(sizeof(int) * n) + padded(sizeof(float) * 3 * n) + 2 * padded(sizeof(int) * n) + padded(sizeof(int) * 4) + db_ws_bytes(n);
+    DevBuf big;
+    NRS_TRY(c->ensure(big, bytes));
+    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
+    Carver cv(big.as<char>());
+    char* d_in = cv.take<char>(U.bytes);
+    char* d_ws = cv.take<char>(ws_bytes);
+    double* d_score = cv.take<double>(n);
+    int* d_match = cv.take<int>(2 * (size_t)n);
+    int* d_out = cv.take<int>(L.words);
+    int* d_gidx = cv.take<int>(n);
+    float* d_gxyz = cv.take<float>(3 * (size_t)n);
+    int* d_raw = cv.take<int>(n);
+    int* d_label = cv.take<int>(n);
+    int* d_counts = cv.take<int>(4);
+    const DbWs dw = db_carve(big.as<char>() + cv.used, n);
+    if (cv.used + db_ws_bytes(n) > bytes) return c->fail(NRS_ERR_STATE, "nrs_init_stereo: workspace accounting");
+    std::vector<char> up(U.bytes);
+    sinit_pack_upload(U, left, stride_l, right, stride_r, xy, up.data());
+    NRS_HIP(c, hipMemcpyAsync(d_in, up.data(), U.bytes, hipMemcpyHostToDevice, c->stream));              // the one upload
+    const uint8_t* d_left = reinterpret_cast<const uint8_t*>(d_in + U.left);
+    const uint8_t* d_right = reinterpret_cast<const uint8_t*>(d_in + U.right);
+    const float* d_xy = reinterpret_cast<const float*>(d_in + U.xy);
+    const SiPacked P{(unsigned)L.xyz, (unsigned)L.status, (unsigned)L.code, (unsigned)L.raw, (unsigned)L.label, (unsigned)L.selected, (unsigned)L.sel_xyz};
+    NRS_TRY(stereo_match_enqueue(c, cam, opt->bf, w, h, n, d_left, d_right, d_xy, d_ws, reinterpret_cast<float*>(d_out + L.xyz), d_out + L.status,
+                                 d_score, d_match));
+    hipLaunchKernelGGL(k_si_gate, dim3(1), dim3(DB_BLOCK), 0, c->stream, n, opt->z_min, opt->z_max, d_out, P, d_gidx, d_gxyz);
+    dbscan_enqueue(c, dw, d_out + 1, d_gxyz, opt->eps, opt->min_points, opt->noise_competes, d_raw, d_label, d_counts);
+    hipLaunchKernelGGL(k_si_select, dim3(1), dim3(DB_BLOCK), 0, c->stream, n, d_gidx, d_gxyz, d_raw, d_label, d_counts, d_out, P);
+    NRS_HIP(c, hipGetLastError());
+    std::vector<int32_t> packed(L.words);
+    NRS_HIP(c, hipMemcpyAsync(packed.data(), d_out, sizeof(int) * L.words, hipMemcpyDeviceToHost, c->stream));   // the one download
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (sinit_unpack(packed.data(), n, out) != 0) {
+        sinit_clear(out);
+        return c->fail(NRS_ERR_HIP, "nrs_init_stereo: the packed result's header (%d, %d, %d, %d, %d, %d) contradicts itself for %d keypoints", packed[0],
+                       packed[1], packed[2], packed[3], packed[4], packed[5], n);
+    }
+    return NRS_OK;
+}

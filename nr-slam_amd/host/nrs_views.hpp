@@ -366,6 +366,51 @@ private:
     nrs_init_result last_{};
 };
 
+// Tracking::StereoMapInitialization (modules/tracking/tracking.cc:216-263) on flat arrays: the stereo matcher, the depth gate, Dbscan3D and
+// the selection of the winning class in one call (include/nrs.h nrs_init_stereo).  Initialize returns the verdict (0 ok; 1 no keypoint
+// passed the gate); the caller then inserts one map point per selected keypoint with status TRACKED_WITH_3D, builds the graph at 10.5 and
+// makes the keyframe (:254-288).  Images are grey bytes, strides in bytes.
+class StereoMapInitialization {
+public:
+    struct Options {                      // what the reference hard-codes (tracking.cc:226-233, dbscan.cc:63)
+        float bf = 3886.37f, z_min = 35.5f, z_max = 70.5f;
+        double eps = 2.5;
+        int min_points = 5;
+        bool noise_competes = true;       // the reference's std::map counts noise as a class
+    };
+    StereoMapInitialization(Engine& e, const Options& options, const CameraView& calibration) : e_(e), options_(options), cam_(calibration) {}
+    int Initialize(const uint8_t* im_left, const uint8_t* im_right, int w, int h, int stride_left, int stride_right,
+                   const std::vector<float>& keypoints_xy, std::vector<int32_t>& selected, std::vector<float>& landmarks_position,
+                   std::vector<int32_t>& keypoint_code) {
+        const size_t n = keypoints_xy.size() / 2;
+        nrs_init_stereo_options opt;
+        nrs_init_stereo_options_init(&opt);
+        opt.bf = options_.bf; opt.z_min = options_.z_min; opt.z_max = options_.z_max;
+        opt.eps = options_.eps; opt.min_points = options_.min_points; opt.noise_competes = options_.noise_competes ? 1 : 0;
+        selected.assign(n, -1);
+        landmarks_position.assign(3 * n, 0.f);
+        keypoint_code.assign(n, 1);
+        nrs_init_stereo_result out{};
+        out.struct_size = (uint32_t)sizeof(out);
+        out.selected = selected.data();
+        out.selected_xyz = landmarks_position.data();
+        out.code = keypoint_code.data();
+        e_.check_rc(nrs_init_stereo(e_.raw(), &cam_.cam, &opt, im_left, im_right, w, h, stride_left, stride_right, (int32_t)n, keypoints_xy.data(), &out));
+        selected.resize((size_t)out.n_selected);
+        landmarks_position.resize(3 * (size_t)out.n_selected);
+        last_ = out;
+        last_.selected = nullptr; last_.selected_xyz = nullptr; last_.code = nullptr;
+        return out.verdict;
+    }
+    const nrs_init_stereo_result& last() const { return last_; }   // the counts and the median depth of the last call (no arrays)
+
+private:
+    Engine& e_;
+    Options options_;
+    CameraView cam_;
+    nrs_init_stereo_result last_{};
+};
+
 // RegularizationGraph (modules/map/regularization_graph.h:34-96) at the reference's all-pairs density, device resident.
 // Point "ids" are indices 0 .. capacity-1 (the shim keeps the MapPoint ID <-> index map, as it does for frames).
 class RegularizationGraph {

@@ -33,7 +33,8 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg", "nrs_dba_solve_window_rg", "nrs_dba_window_rg_stats", "nrs_dba_solve_window_rg_embedded",
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
            "nrs_init_options_init", "nrs_init_essential",
-           "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame"]
+           "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame",
+           "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo"]
 
 
 class NrsError(RuntimeError):
@@ -122,6 +123,23 @@ class InitResult(C.Structure):
                 ("pose_qt", C.c_float * 7), ("inlier", C.c_void_p), ("xyz", C.c_void_p), ("code", C.c_void_p), ("hyp_E", C.c_void_p),
                 ("hyp_score", C.c_void_p), ("samples_out", C.c_void_p), ("labels", C.c_void_p), ("centres", C.c_void_p)]
 
+
+class InitStereoOptions(C.Structure):
+    """nrs_init_stereo_options (f8)"""
+    _fields_ = [("struct_size", C.c_uint32), ("bf", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("eps", C.c_double),
+                ("min_points", C.c_int32), ("noise_competes", C.c_int32)]
+
+
+class InitStereoResult(C.Structure):
+    """nrs_init_stereo_result (f8): scalars in the record, arrays through caller-owned pointers (each nullable)"""
+    _fields_ = [("struct_size", C.c_uint32), ("verdict", C.c_int32), ("n_matched", C.c_int32), ("n_gated", C.c_int32), ("n_clusters", C.c_int32),
+                ("n_noise", C.c_int32), ("n_selected", C.c_int32), ("median_depth", C.c_float), ("xyz", C.c_void_p), ("match_status", C.c_void_p),
+                ("code", C.c_void_p), ("raw_label", C.c_void_p), ("label", C.c_void_p), ("selected", C.c_void_p), ("selected_xyz", C.c_void_p)]
+
+
+SINIT_OK, SINIT_NOTHING_GATED = 0, 1
+SINIT_SELECTED, SINIT_MATCHER_REJECTED, SINIT_OUTSIDE_GATE, SINIT_OTHER_CLUSTER = 0, 1, 2, 3
+DBSCAN_MAX_POINTS = 16384
 
 INIT_OK, INIT_FEW_MATCHES, INIT_FEW_LANDMARKS, INIT_LOW_PARALLAX = 0, 1, 2, 3
 INIT_COUNTERS = ("N", "n_triangulated", "n_parallax", "n_depth_1", "n_reprojection_error_1", "n_depth_2", "n_reprojection_error_2",
@@ -686,6 +704,52 @@ class Context:
             r.update(hyp_E=a["hyp_E"], hyp_score=a["hyp_score"], samples=a["samples_out"])
             if samples is None:
                 r.update(labels=a["labels"], centres=a["centres"])
+        return r
+
+    # ---- f8: stereo map initialisation
+    def dbscan3d(self, xyz, eps=2.5, min_points=5, noise_competes=True, n=None):
+        """nrs_dbscan3d -> (raw_label [n], label [n], counts (clusters, noise points, size of label 0)).  n: the count passed to the
+        library when it is not len(xyz) (refusal tests)"""
+        xyz = _f32(xyz).reshape(-1, 3)
+        m = len(xyz)
+        raw, lab, counts = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(3, np.int32)
+        self._chk(self.lib.nrs_dbscan3d(self.h, C.c_int32(m if n is None else n), _p(xyz, C.c_float), C.c_double(eps), C.c_int32(min_points),
+                                        C.c_int32(1 if noise_competes else 0), _p(raw, C.c_int32), _p(lab, C.c_int32), _p(counts, C.c_int32)))
+        return raw, lab, counts
+
+    def init_stereo(self, cam, left, right, xy, stride_l=None, stride_r=None, width=None, struct_size=None, result_struct_size=None, n=None,
+                    **options):
+        """Tracking::StereoMapInitialization up to the selected landmarks, in one call.  options: the fields of nrs_init_stereo_options
+        (defaults from nrs_init_stereo_options_init).  left / right as in stereo_match_pattern.  Returns a dict: verdict, n_matched,
+        n_gated, n_clusters, n_noise, n_selected, median_depth, xyz[n,3], match_status[n], code[n], raw_label[n], label[n],
+        selected[n_selected], selected_xyz[n_selected,3]."""
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        h = left.shape[0]
+        w = left.shape[1] if width is None else int(width)
+        xy = _f32(xy).reshape(-1, 2)
+        m = len(xy)
+        opt = InitStereoOptions()
+        self.lib.nrs_init_stereo_options_init(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(InitStereoOptions._fields_) or k == "struct_size":
+                raise TypeError("init_stereo: unknown option %r" % k)
+            setattr(opt, k, v)
+        if struct_size is not None:
+            opt.struct_size = struct_size
+        out = InitStereoResult()
+        out.struct_size = C.sizeof(InitStereoResult) if result_struct_size is None else result_struct_size
+        a = dict(xyz=np.zeros((m, 3), np.float32), match_status=np.zeros(m, np.int32), code=np.zeros(m, np.int32), raw_label=np.zeros(m, np.int32),
+                 label=np.zeros(m, np.int32), selected=np.zeros(m, np.int32), selected_xyz=np.zeros((m, 3), np.float32))
+        for k, v in a.items():
+            setattr(out, k, v.ctypes.data if v.size else None)
+        self._chk(self.lib.nrs_init_stereo(self.h, C.byref(cam), C.byref(opt), _p(left, C.c_uint8), _p(right, C.c_uint8), C.c_int32(w), C.c_int32(h),
+                                           C.c_int32(stride_l or left.strides[0]), C.c_int32(stride_r or right.strides[0]),
+                                           C.c_int32(m if n is None else n), _p(xy, C.c_float), C.byref(out)))
+        ns = out.n_selected
+        r = dict(verdict=out.verdict, n_matched=out.n_matched, n_gated=out.n_gated, n_clusters=out.n_clusters, n_noise=out.n_noise,
+                 n_selected=ns, median_depth=np.float32(out.median_depth), bf=np.float32(opt.bf))
+        r.update(a)
+        r["selected"], r["selected_xyz"] = a["selected"][:ns].copy(), a["selected_xyz"][:ns].copy()
         return r
 
     # ---- f7: evaluation

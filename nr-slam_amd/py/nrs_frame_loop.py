@@ -204,6 +204,17 @@ class GpuBackend:
     def init_essential(self, ref_xy, cur_xy, status, n_matches, **options):
         return self.ctx.init_essential(self.cam, ref_xy, cur_xy, status, n_matches, taps=False, **options)
 
+    # Tracking::StereoMapInitialization (tracking.cc:216-263) on the device: include/nrs.h nrs_init_stereo.  The images are grey bytes from
+    # the host (the resident-frame variant is not built); the result carries the selected keypoints for FrameLoop.from_stereo_initialization
+    def init_stereo(self, left, right, kp, **options):
+        kp = np.asarray(kp, F32).reshape(-1, 2)
+        r = self.ctx.init_stereo(self.cam, left, right, kp, **options)
+        r["selected_keypoints"] = kp[r["selected"]].copy()
+        return r
+
+    def dbscan3d(self, xyz, eps=2.5, min_points=5, noise_competes=True):
+        return self.ctx.dbscan3d(xyz, eps, min_points, noise_competes)
+
     # dense_graph: the map's RegularizationGraph at the reference's density -- every pair of initial map points connected
     # (modules/map/map.cc:148-166) -- resident on the device; otherwise the caller's flat graph
     def make_graph(self, graph, X0):
@@ -546,6 +557,30 @@ class FrameLoop:
             loop.insert_keyframe(kp=np.asarray(result["reference_keypoints"], F32), pos=Xs,
                                  pose=(np.array([0, 0, 0, 1], F32), np.zeros(3, F32)))
             loop.insert_keyframe()
+            loop.unmapped.next()
+        return loop
+
+    @classmethod
+    def from_stereo_initialization(cls, backend, project_f32, wh, result, im_left, sigma=10.5, stretch_th=1.1, **kw):
+        """The tail of Tracking::StereoMapInitialization (tracking.cc:252-288) on a backend's init_stereo result: identity pose, scale 1 (the
+        map is metric), the selected keypoints and positions, every one TRACKED_WITH_3D, the all-pairs graph at sigma = 10.5 (:268; the
+        backend keeps it: a dense-graph backend is required), klt_set_reference on the left image and the template archive (both in
+        __init__).  The reference makes ONE keyframe (:283-286) and System::TrackImageWithStereo's own DoMapping (SLAM/system.cc:150)
+        takes it from the unmapped queue (a one-keyframe BA returns at once), so the loop's first frame finds no unmapped keyframe and
+        takes the FrameMapping branch -- the mono start's first frame takes KeyFrameMapping."""
+        if not getattr(backend, "dense", False):
+            raise ValueError("from_stereo_initialization needs a backend that keeps the all-pairs graph (dense_graph=True)")
+        if int(result["verdict"]) != 0 or int(result["n_selected"]) == 0:
+            raise ValueError("from_stereo_initialization: the initialisation selected no point (verdict %d)" % int(result["verdict"]))
+        kp, X = np.asarray(result["selected_keypoints"], F32).reshape(-1, 2), np.asarray(result["selected_xyz"], F32).reshape(-1, 3)
+        loop = cls(backend, project_f32, wh, 1.0, kp, X, dict(sigma=float(sigma), stretch_th=stretch_th),
+                   np.array([0, 0, 0, 1], F32), np.zeros(3, F32), im_left, **kw)
+        loop.status[:] = TRACKED_WITH_3D
+        loop.init_median_depth = F32(result["median_depth"])
+        if loop.mapping:
+            loop.unmapped_keyframes = 0
+        if loop.keyframe_ba:
+            # __init__ has made and queued the one keyframe (an identity-pose copy of this frame); the initialisation's own DoMapping takes it
             loop.unmapped.next()
         return loop
 

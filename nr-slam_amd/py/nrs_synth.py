@@ -771,3 +771,88 @@ def make_depth_image(sq, frame):
     lin = griddata(uv, zc, (xs, ys), method="linear")
     near = griddata(uv, zc, (xs, ys), method="nearest")
     return np.where(np.isnan(lin), near, lin).astype(F32)
+
+
+# ---- f8: stereo map initialisation (include/nrs.h "f8")
+def make_cluster_cases():
+    """Hand-made point sets for nrs_dbscan3d: a list of dict(name, xyz [n,3] fp32, eps, min_points).  The smallest shapes at which the
+    kernels can go wrong: the empty set and sets around min_points, around a wave (64) and around a compaction chunk (1024), the inclusive
+    boundary, a long chain (in order and shuffled), two chains joined through a non-core point, equal sizes, noise in the majority,
+    coincident points, a NaN and an infinite coordinate, min_points = 1.  Every set is clustered with noise competing and not."""
+    rng = np.random.default_rng(61)
+    eps, mp = 2.5, 5
+    cases = []
+
+    def add(name, xyz, eps=eps, min_points=mp):
+        cases.append(dict(name=name, xyz=np.asarray(xyz, F32).reshape(-1, 3), eps=float(eps), min_points=int(min_points)))
+
+    def blobs(n, k=3, spread=1.1, noise=0.25):
+        nn = int(n * noise)
+        c = rng.uniform(-14, 14, (k, 3))
+        p = c[rng.integers(0, k, n - nn)] + rng.normal(0, spread, (n - nn, 3))
+        p = np.concatenate([p, rng.uniform(-30, 30, (nn, 3))])
+        return p[rng.permutation(n)]
+
+    add("empty", np.zeros((0, 3)))
+    add("one", [[1, 2, 3]])
+    add("min_points", [[0, 0, 0], [2, 0, 0], [2.1, 0.1, 0], [2, 0.2, 0.1], [1.9, 0, 0.2]])      # 4 neighbours each: nobody is core
+    # point 0 has exactly min_points neighbours (core); points 1-4 have min_points - 1 (border); point 5 has one (border)
+    add("min_points+1", [[0, 0, 0], [2, 0, 0], [2.1, 0.1, 0], [2, 0.2, 0.1], [1.9, 0, 0.2], [-2.4, 0, 0]])
+    for n in (63, 64, 65):
+        add("blobs%d" % n, blobs(n, 2, 0.9))
+    for n in (1023, 1024, 1025):
+        add("blobs%d" % n, blobs(n, 5, 2.0))
+    # exactly eps apart (d2 = 6.25 exactly: neighbours) and one fp32 ulp beyond (not)
+    beyond = np.nextafter(F32(2.5), F32(3))
+    add("boundary", [[0, 0, 0], [2.5, 0, 0], [0, 100, 0], [beyond, 100, 0]], min_points=1)
+    chain = np.stack([np.arange(300) * 0.9 * eps, np.zeros(300), np.zeros(300)], 1)
+    add("chain300", chain, min_points=2)
+    add("chain300_shuffled", chain[rng.permutation(300)], min_points=2)
+    add("chain300_reversed", chain[::-1], min_points=2)
+    # min_points 3, spacing 0.45 eps: interior points have 4 neighbours.  The bridge (index 0) lies 0.9 eps beyond the end of either chain:
+    # it has 2 neighbours, both core, and is not core itself -- the chains stay two clusters; chain B holds the lower indices
+    s = 0.45 * eps
+    a = np.stack([np.arange(20) * s, np.zeros(20), np.zeros(20)], 1)
+    bridge = np.array([[19 * s + 0.9 * eps, 0, 0]])
+    b = np.stack([bridge[0, 0] + 0.9 * eps + np.arange(20) * s, np.zeros(20), np.zeros(20)], 1)
+    add("bridge", np.concatenate([bridge, b, a]), min_points=3)
+    cube = rng.uniform(0, 1, (8, 3))
+    add("equal_sizes", np.concatenate([cube + [50, 0, 0], cube]), min_points=5)
+    lone = np.stack([np.arange(20) * 10.0, np.full(20, 40.0), np.zeros(20)], 1)
+    add("noise_majority", np.concatenate([lone[:7], cube, lone[7:], cube[:6] + [0, -40, 0]]), min_points=5)
+    add("coincident", np.tile([[3.25, -1.5, 60.0]], (10, 1)))
+    p = blobs(40, 1, 0.8, 0.1)
+    p[7, 1] = np.nan
+    p[21, 2] = np.inf
+    add("nan_inf", p)
+    add("min_points_1", rng.uniform(-8, 8, (70, 3)), min_points=1)
+    return cases
+
+
+def make_stereo_init_sequence(n_points=500, n_frames=3, seed=3, wh=(320, 240), step=0.35, rot_step=(0.0006, -0.0009, 0.0004), bf=2400.0):
+    """make_init_sequence's surface, texture and warp (the same random stream, so the same left images) plus a RIGHT view of frame 0: the
+    same warp for a camera displaced by the baseline along +x only, so the pair is rectified -- a point at depth z that the left image shows
+    at (u, v) is found at (u - bf / z, v).  bf (baseline times focal length, in mm px) puts the surface's 52-68 mm at disparities of
+    about 35-46 px: one disparity step is about 1.5 mm of depth.  Returned with the scene: bf, the z gate around the surface's range
+    (z_min, z_max) and eps -- the extractor leaves a few hundred keypoints on 50 x 38 mm of surface, about 0.15 per square mm, so the
+    reference's 2.5 mm radius (Hamlyn images hold several times as many) would find no core point; eps = 6 mm holds about 15."""
+    from scipy.interpolate import griddata
+    sq = make_init_sequence(n_points, n_frames, seed, wh, step, rot_step)
+    rng = np.random.default_rng(seed)                              # the stream of make_init_sequence: surface, then texture
+    w, h = wh
+    X, _ = surface_points(n_points, rng, PINHOLE)
+    tex = _texture(h, w, rng)
+    uv0 = _project(PINHOLE, sq["prm"].astype(np.float64), X)
+    disp = float(bf) / X[:, 2]
+    uvr = uv0 - np.stack([disp, np.zeros(len(X))], 1)              # the right camera sees the point `disp` pixels to the left
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    gx = griddata(uvr, disp, (xs, ys), method="linear")
+    nx = griddata(uvr, disp, (xs, ys), method="nearest")
+    gx = np.where(np.isnan(gx), nx, gx)
+    sx2, sy2 = np.clip(xs + gx + 32, 0, w + 62.0), np.clip(ys + 32, 0, h + 62.0)
+    x0, y0 = np.minimum(np.floor(sx2).astype(int), w + 62), np.minimum(np.floor(sy2).astype(int), h + 62)
+    fx, fy = sx2 - x0, sy2 - y0
+    v = (tex[y0, x0] * (1 - fx) + tex[y0, x0 + 1] * fx) * (1 - fy) + (tex[y0 + 1, x0] * (1 - fx) + tex[y0 + 1, x0 + 1] * fx) * fy
+    sq.update(right=np.clip(np.rint(v), 0, 255).astype(np.uint8), bf=float(bf), z_min=45.0, z_max=75.0, eps=6.0, min_points=5,
+              disparity_at=lambda xy: griddata(uv0, disp, np.asarray(xy, np.float64), method="linear"))
+    return sq
