@@ -180,6 +180,8 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *   a1 / graph    NRS_PO_MULTI_MIN=<n>, NRS_PO_NO_CACHE, NRS_PO_MULTI_GROUPS=<g>, NRS_HOST_WALK, NRS_WALK_MAX_PASSES=<n>, NRS_RG_NO_MIRROR, NRS_RG_MAX_CAP=<n> (a lower limit on the GetEdges
  *                 prefix a call may ask for: the "ran off at the limit" refusals)
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
+ *   front end     NRS_FRONT_PER_EYE (nrs_front_process_stereo: grey and CLAHE issued per eye with the single-frame kernels instead of the
+ *                 pair launches; the same bytes)
  *   probes        (read by a `make PROBES=1` build only) NRS_LIN_DBG / NRS_SPMV_DBG / NRS_PCG_DBG (phase clocks of one lineariser /
  *                 operator / single-launch PCG iteration launch), NRS_LIN_EXP=<n> (lineariser removal experiments: wrong results on purpose)
  * (what each selects: README.md "Debug switches"; the A/B tests drive every launch form through nrs_debug_set). */
@@ -802,6 +804,21 @@ int nrs_klt_track_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int32
                         int32_t use_initial_flow, float min_ssim, int32_t* n_good, float* ssim);
 int nrs_shi_extract_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int32_t use_global_mask, int32_t n_prev,
                           const float* prev_xy, int32_t capacity, float* out_xy, int32_t* out_id, int32_t* n_out);
+/* The front end of System::TrackImageWithStereo (system.cc:134-160): ImageProcessing on BOTH images (:137-138), the masks from the
+ * left one only (:144).  left / right: two images of the same size and channel count, each with its own row stride in bytes, each
+ * uploaded once.  The left eye gets everything nrs_front_process does; the right eye gets the grey conversion and CLAHE and no mask.
+ * The stages both eyes share -- grey, the CLAHE tile LUTs, the CLAHE blend -- run as ONE launch each over both eyes (the eye is the
+ * grid's third dimension: 128 LUT workgroups where a frame gives 64); each eye's bytes are, byte for byte, what nrs_front_process
+ * gives for that image alone (tests/test_gpu_front_stereo.py).  Outputs: those of nrs_front_process for the left eye, and
+ * gray_right_out / clahe_right_out; every one may be NULL.
+ * State: afterwards the left slot is exactly what nrs_front_process(left) leaves -- every nrs_*_front call above works on it
+ * unchanged -- and the right eye's grey and CLAHE images are resident next to it for the nrs_*_front calls of the stereo section
+ * below.  nrs_front_process (one image) invalidates the right slot; nrs_front_configure drops both.  The call synchronises the
+ * context's stream before it returns: this is what makes the resident pair safe to read from ANOTHER context of the same device
+ * (nrs_stereo_match_lk_front).  NRS_ERR_INVALID: the refusals of nrs_front_process, for either image. */
+int nrs_front_process_stereo(nrs_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h, int32_t stride_l, int32_t stride_r,
+                             int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out,
+                             uint8_t* gray_right_out, uint8_t* clahe_right_out);
 
 /* ---- N2: the skinned mode ("5k points x 500 graph nodes") --------------------------------------------------------
  * The reference has no separate node set; its skinning is stage 2 of CameraPoseAndDeformationOptimization
@@ -984,6 +1001,33 @@ void nrs_init_stereo_options_init(nrs_init_stereo_options* opt);
  * min_points < 1, z_min >= z_max (or either NaN). */
 int nrs_init_stereo(nrs_ctx* ctx, const nrs_camera* cam, const nrs_init_stereo_options* opt, const uint8_t* left, const uint8_t* right,
                     int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, nrs_init_stereo_result* out);
+
+/* ---- the resident stereo pair: the stages of System::TrackImageWithStereo (system.cc:134-160) joined on the device.  After
+ * nrs_front_process_stereo both eyes lie in the context; the calls below read them where they lie, so each image crosses the bus
+ * once.  Each takes the arguments of its host-pointer form without the image pointers and strides, plus w, h and `image`
+ * (NRS_FRONT_IMAGE_GRAY or NRS_FRONT_IMAGE_CLAHE, applied to both eyes), runs the same internals and gives bit for bit what the
+ * host-pointer form gives on the downloaded bytes (tests/test_gpu_front_stereo.py).  NRS_ERR_STATE when no pair is resident (none
+ * processed, a one-image nrs_front_process or nrs_front_configure since) or when w x h is not the resident pair's size.
+ *
+ * nrs_stereo_match_pattern_front: StereoPatternMatching::computeStereo3D (stereo_pattern_matching.cc:33-94), the launches of
+ *   nrs_stereo_match_pattern; NRS_STEREO_NO_MFMA selects the plain correlation here too.
+ * nrs_init_stereo_front: Tracking::StereoMapInitialization (tracking.cc:216-263), the stages and the packed download of
+ *   nrs_init_stereo; only the keypoints go up.
+ * nrs_stereo_match_lk_front: StereoLucasKanade::ComputeStereo3D (stereo_lucas_kanade.cc:38-75): SetReferenceImage (no mask) on the
+ *   resident left eye of ctx_front, Track (initial flow, min_ssim) on its resident right eye -- both in the tracker state of
+ *   ctx_tracker -- and the loop of nrs_stereo_from_tracks on the tracks.  right_xy (n x 2) / track_status (n): the tracker's output.
+ *   The two contexts may be the same one: the call then REPLACES its tracking templates (the reference's matcher owns a tracker of
+ *   its own, SLAM/system.cc:45-54: keep a context for stereo, as for nrs_klt_set_reference + nrs_klt_track).  Two different contexts
+ *   must be on the same device (NRS_ERR_INVALID otherwise; the precedent is nrs_klt_insert_archived); the read of ctx_front's
+ *   buffers is ordered by the stream synchronisation at the end of nrs_front_process_stereo, and ctx_front must not process another
+ *   frame while the call runs.  Errors are reported on ctx_tracker. */
+int nrs_stereo_match_pattern_front(nrs_ctx* ctx, const nrs_camera* cam, float bf, int32_t w, int32_t h, int32_t image, int32_t n,
+                                   const float* xy, float* xyz, int32_t* status, double* score, int32_t* match_xy);
+int nrs_init_stereo_front(nrs_ctx* ctx, const nrs_camera* cam, const nrs_init_stereo_options* opt, int32_t w, int32_t h, int32_t image,
+                          int32_t n, const float* xy, nrs_init_stereo_result* out);
+int nrs_stereo_match_lk_front(nrs_ctx* ctx_tracker, nrs_ctx* ctx_front, const nrs_camera* cam, float bf, int32_t w, int32_t h, int32_t image,
+                              int32_t n, const float* xy, float min_ssim, float* xyz, int32_t* status, float* right_xy,
+                              int32_t* track_status);
 
 #ifdef __cplusplus
 }

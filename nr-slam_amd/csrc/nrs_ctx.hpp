@@ -161,6 +161,9 @@ void front_free(nrs_ctx* ctx);
 // nrs_front.hip, for the *_front entry points of the tracker and the extractor: the resident image (NRS_FRONT_IMAGE_*) and, when asked for,
 // the Global mask of the last nrs_front_process -- packed w x h bytes on the device; NRS_ERR_STATE when there is none or its size differs
 int front_resident(nrs_ctx* ctx, const char* who, int w, int h, int image, int use_global_mask, const uint8_t** img, const uint8_t** mask);
+// ... and for the *_front entry points of the stereo stages: the same image of both eyes after nrs_front_process_stereo; NRS_ERR_STATE when
+// no pair is resident (a one-image nrs_front_process invalidates the right eye) or its size differs
+int front_resident_pair(nrs_ctx* ctx, const char* who, int w, int h, int image, const uint8_t** left, const uint8_t** right);
 // nrs_eval.hip, for nrs_stereo_match_pattern and nrs_init_stereo (nrs_sinit.hip): the pattern matcher's refusals under the caller's name,
 // the bytes of its intermediates, and its launches on packed w x h images and n keypoints that are already on the device (n > 0; ws:
 // stereo_match_ws_bytes bytes, 256-byte aligned; d_score / d_match as long as the entry point's outputs, never null here)

@@ -399,31 +399,36 @@ int stereo_match_enqueue(nrs_ctx* c, const nrs_camera* cam, float bf, int w, int
 }
 }  // namespace nrs
 
-extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float bf, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h,
-                                        int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, float* xyz, int32_t* status,
-                                        double* score, int32_t* match_xy) {
-    if (!c) return NRS_ERR_INVALID;
-    NRS_TRY(stereo_match_check(c, "nrs_stereo_match_pattern", cam, left, right, w, h, stride_l, stride_r, n, xy && xyz && status));
+// The upload / download shell of the pattern matcher.  on_device: left / right are packed w x h images the device already holds (the
+// resident pair of nrs_front_process_stereo) and only the keypoints go up; otherwise host images, packed while they are uploaded
+static int stereo_match_shell(nrs_ctx* c, const char* who, const nrs_camera* cam, float bf, const uint8_t* left, const uint8_t* right, bool on_device,
+                              int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, float* xyz, int32_t* status,
+                              double* score, int32_t* match_xy) {
+    NRS_TRY(stereo_match_check(c, who, cam, left, right, w, h, stride_l, stride_r, n, xy && xyz && status));
     if (n == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
-    const size_t img = (size_t)w * h, ws_bytes = stereo_match_ws_bytes(c, w, h, n);
+    const size_t img = on_device ? 0 : (size_t)w * h, ws_bytes = stereo_match_ws_bytes(c, w, h, n);
     const size_t bytes = 2 * padded(img) + padded(sizeof(float) * 2 * n) + ws_bytes + padded(sizeof(float) * 3 * n) + padded(sizeof(int) * n) +
                          padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n);
     DevBuf big;
     NRS_TRY(c->ensure(big, bytes));
     struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
     Carver cv(big.as<char>());
-    uint8_t* d_left = cv.take<uint8_t>(img);
-    uint8_t* d_right = cv.take<uint8_t>(img);
+    const uint8_t *d_left = left, *d_right = right;
+    if (!on_device) {
+        uint8_t* up_l = cv.take<uint8_t>(img);
+        uint8_t* up_r = cv.take<uint8_t>(img);
+        NRS_HIP(c, hipMemcpy2DAsync(up_l, w, left, stride_l, w, h, hipMemcpyHostToDevice, c->stream));      // packed on the device
+        NRS_HIP(c, hipMemcpy2DAsync(up_r, w, right, stride_r, w, h, hipMemcpyHostToDevice, c->stream));
+        d_left = up_l; d_right = up_r;
+    }
     float* d_xy = cv.take<float>(2 * (size_t)n);
     char* d_ws = cv.take<char>(ws_bytes);
     float* d_xyz = cv.take<float>(3 * (size_t)n);
     int* d_status = cv.take<int>(n);
     double* d_score = cv.take<double>(n);
     int* d_match = cv.take<int>(2 * (size_t)n);
-    if (cv.used > bytes) return c->fail(NRS_ERR_STATE, "nrs_stereo_match_pattern: workspace accounting");
-    NRS_HIP(c, hipMemcpy2DAsync(d_left, w, left, stride_l, w, h, hipMemcpyHostToDevice, c->stream));      // packed on the device
-    NRS_HIP(c, hipMemcpy2DAsync(d_right, w, right, stride_r, w, h, hipMemcpyHostToDevice, c->stream));
+    if (cv.used > bytes) return c->fail(NRS_ERR_STATE, "%s: workspace accounting", who);
     NRS_HIP(c, hipMemcpyAsync(d_xy, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     NRS_TRY(stereo_match_enqueue(c, cam, bf, w, h, n, d_left, d_right, d_xy, d_ws, d_xyz, d_status, d_score, d_match));
     NRS_HIP(c, hipMemcpyAsync(xyz, d_xyz, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
@@ -432,6 +437,21 @@ extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float
     if (match_xy) NRS_HIP(c, hipMemcpyAsync(match_xy, d_match, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     return NRS_OK;
+}
+
+extern "C" int nrs_stereo_match_pattern(nrs_ctx* c, const nrs_camera* cam, float bf, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h,
+                                        int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, float* xyz, int32_t* status,
+                                        double* score, int32_t* match_xy) {
+    if (!c) return NRS_ERR_INVALID;
+    return stereo_match_shell(c, "nrs_stereo_match_pattern", cam, bf, left, right, false, w, h, stride_l, stride_r, n, xy, xyz, status, score, match_xy);
+}
+
+extern "C" int nrs_stereo_match_pattern_front(nrs_ctx* c, const nrs_camera* cam, float bf, int32_t w, int32_t h, int32_t image, int32_t n,
+                                              const float* xy, float* xyz, int32_t* status, double* score, int32_t* match_xy) {
+    if (!c) return NRS_ERR_INVALID;
+    const uint8_t *left = nullptr, *right = nullptr;
+    NRS_TRY(front_resident_pair(c, "nrs_stereo_match_pattern_front", w, h, image, &left, &right));
+    return stereo_match_shell(c, "nrs_stereo_match_pattern_front", cam, bf, left, right, true, w, h, w, w, n, xy, xyz, status, score, match_xy);
 }
 
 extern "C" int nrs_eval_depth_ground_truth(nrs_ctx* c, const nrs_camera* cam, const float* depth, int32_t w, int32_t h, int32_t stride, int32_t n,

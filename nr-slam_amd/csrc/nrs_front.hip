@@ -9,6 +9,7 @@
 //   k_front_gray           8-bit fixed point (R*9798 + G*19235 + B*3735 + 2^14) >> 15, channel 0 = R
 //   k_front_clahe_lut      one workgroup per tile: LDS histogram (integer atomics), clip, redistribution, scan, LUT
 //   k_front_clahe_apply    bilinear blend of the four neighbouring LUTs, fp32, contraction off
+//   k_front_*_pair         the three above over a stereo pair in one launch each, the eye in grid.z (nrs_front_process_stereo)
 //   k_front_erode_ellipse  union of the element's row spans over a tile staged in LDS (the threshold of BrightFilter is
 //                          applied while the tile is loaded)
 //   k_front_rowmin/colmin  the rectangles, separably; the row pass reads its source through a functor: a plain image, the
@@ -44,7 +45,9 @@ struct FrontState {
     int tiles_x = 8, tiles_y = 8;
     int w = 0, h = 0;
     bool valid = false;                        // a frame has been processed under this configuration
+    bool valid_right = false;                  // ... and it was a stereo pair: the right eye's grey and CLAHE are resident too
     DevBuf raw, gray, clahe, global, tmp_a, tmp_f, lut, at;
+    DevBuf raw_r, gray_r, clahe_r, lut_r;      // the right eye of nrs_front_process_stereo (its 64 LUTs; it has no masks)
     DevBuf fmask[NRS_FRONT_MAX_FILTERS];       // BRIGHT / BORDER: the last frame's mask; PREDEFINED: the eroded mask (made once)
     EllSpans e11, e20;
     GaussW gw;
@@ -121,6 +124,83 @@ __global__ void k_front_clahe_apply(const uint8_t* __restrict__ gray, int w, int
     const float txf = (float)x * inv_tw - 0.5f, tyf = (float)y * inv_th - 0.5f;
     int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
     const float xa = txf - (float)tx1, ya = tyf - (float)ty1;     // before the indices are clamped
+    const float xa1 = 1.f - xa, ya1 = 1.f - ya;
+    const int tx2 = min(tx1 + 1, tiles_x - 1), ty2 = min(ty1 + 1, tiles_y - 1);
+    tx1 = max(tx1, 0); ty1 = max(ty1, 0);
+    const int v = gray[(size_t)y * w + x];
+    const float l11 = (float)lut[((size_t)ty1 * tiles_x + tx1) * 256 + v], l12 = (float)lut[((size_t)ty1 * tiles_x + tx2) * 256 + v];
+    const float l21 = (float)lut[((size_t)ty2 * tiles_x + tx1) * 256 + v], l22 = (float)lut[((size_t)ty2 * tiles_x + tx2) * 256 + v];
+    const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
+    dst[(size_t)y * w + x] = front_sat_rint(res);
+}
+
+// ---- the pair forms (nrs_front_process_stereo): the three stages both eyes take, one launch each over both eyes.  blockIdx.z is the eye;
+// the statements are those of the single-frame kernels above, so an eye's bytes are the bytes of that image processed alone.  The LUT
+// stage is 2 x 64 workgroups of 1 KiB LDS each: with one workgroup per tile a single frame fills 64 of the 256 CUs, the pair 128, and the
+// LDS histogram atomics of the two eyes never meet (a workgroup owns its tile's 256 bins).
+struct EyesIn { const uint8_t* p[2]; };
+struct EyesOut { uint8_t* p[2]; };
+
+__global__ void k_front_gray_pair(EyesIn src, int stride, int ch, int w, int h, EyesOut dst) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* s = (blockIdx.z ? src.p[1] : src.p[0]) + (size_t)y * stride + (size_t)x * ch;
+    int v = s[0];
+    if (ch > 1) v = (s[0] * 9798 + s[1] * 19235 + s[2] * 3735 + (1 << 14)) >> 15;
+    (blockIdx.z ? dst.p[1] : dst.p[0])[(size_t)y * w + x] = (uint8_t)v;
+}
+
+// grid = (tiles_x, tiles_y, 2)
+__global__ __launch_bounds__(256) void k_front_clahe_lut_pair(EyesIn grays, int w, int h, int tw, int th, int clip, EyesOut luts) {
+#pragma clang fp contract(off)
+    __shared__ int hist[256];
+    __shared__ int s_excess;
+    const uint8_t* __restrict__ gray = blockIdx.z ? grays.p[1] : grays.p[0];
+    uint8_t* __restrict__ lut = blockIdx.z ? luts.p[1] : luts.p[0];
+    const int tid = threadIdx.x;
+    hist[tid] = 0;
+    if (tid == 0) s_excess = 0;
+    __syncthreads();
+    const int area = tw * th;
+    for (int i = tid; i < area; i += 256) {
+        const int ly = i / tw, lx = i - ly * tw;
+        const int gx = front_reflect101(blockIdx.x * tw + lx, w), gy = front_reflect101(blockIdx.y * th + ly, h);
+        atomicAdd(&hist[gray[(size_t)gy * w + gx]], 1);
+    }
+    __syncthreads();
+    int v = hist[tid];
+    if (v > clip) { atomicAdd(&s_excess, v - clip); v = clip; }
+    __syncthreads();
+    const int excess = s_excess, batch = excess / 256;
+    int residual = excess - batch * 256;
+    v += batch;
+    if (residual > 0) {
+        const int step = max(256 / residual, 1);
+        if (tid % step == 0 && tid / step < residual) v += 1;
+    }
+    hist[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int t = tid >= off ? hist[tid - off] : 0;
+        __syncthreads();
+        hist[tid] += t;
+        __syncthreads();
+    }
+    const float scale = 255.f / (float)area;
+    lut[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = front_sat_rint((float)hist[tid] * scale);
+}
+
+__global__ void k_front_clahe_apply_pair(EyesIn grays, int w, int h, int tw, int th, int tiles_x, int tiles_y, EyesIn luts, EyesOut dsts) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* __restrict__ gray = blockIdx.z ? grays.p[1] : grays.p[0];
+    const uint8_t* __restrict__ lut = blockIdx.z ? luts.p[1] : luts.p[0];
+    uint8_t* __restrict__ dst = blockIdx.z ? dsts.p[1] : dsts.p[0];
+    const float inv_tw = 1.f / (float)tw, inv_th = 1.f / (float)th;
+    const float txf = (float)x * inv_tw - 0.5f, tyf = (float)y * inv_th - 0.5f;
+    int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
+    const float xa = txf - (float)tx1, ya = tyf - (float)ty1;
     const float xa1 = 1.f - xa, ya1 = 1.f - ya;
     const int tx2 = min(tx1 + 1, tiles_x - 1), ty2 = min(ty1 + 1, tiles_y - 1);
     tx1 = max(tx1, 0); ty1 = max(ty1, 0);
@@ -222,7 +302,7 @@ __global__ void k_front_mask_at(const uint8_t* __restrict__ mask, int w, int h, 
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 static void front_release(nrs_ctx* c, FrontState* f) {
-    DevBuf* bufs[] = {&f->raw, &f->gray, &f->clahe, &f->global, &f->tmp_a, &f->tmp_f, &f->lut, &f->at};
+    DevBuf* bufs[] = {&f->raw, &f->gray, &f->clahe, &f->global, &f->tmp_a, &f->tmp_f, &f->lut, &f->at, &f->raw_r, &f->gray_r, &f->clahe_r, &f->lut_r};
     for (auto b : bufs) c->release(*b);
     for (auto& b : f->fmask) c->release(b);
     delete f;
@@ -279,6 +359,16 @@ int front_resident(nrs_ctx* c, const char* who, int w, int h, int image, int use
     if (image != NRS_FRONT_IMAGE_GRAY && image != NRS_FRONT_IMAGE_CLAHE) return c->fail(NRS_ERR_INVALID, "%s: image selector must be GRAY or CLAHE", who);
     *img = image == NRS_FRONT_IMAGE_GRAY ? f->gray.as<uint8_t>() : f->clahe.as<uint8_t>();
     *mask = use_global_mask ? f->global.as<uint8_t>() : nullptr;
+    return NRS_OK;
+}
+
+int front_resident_pair(nrs_ctx* c, const char* who, int w, int h, int image, const uint8_t** left, const uint8_t** right) {
+    const FrontState* f = c->front;
+    if (!f || !f->valid || !f->valid_right) return c->fail(NRS_ERR_STATE, "%s: no stereo pair has been processed (nrs_front_process_stereo)", who);
+    if (w != f->w || h != f->h) return c->fail(NRS_ERR_STATE, "%s: the resident pair is %d x %d, not %d x %d", who, f->w, f->h, w, h);
+    if (image != NRS_FRONT_IMAGE_GRAY && image != NRS_FRONT_IMAGE_CLAHE) return c->fail(NRS_ERR_INVALID, "%s: image selector must be GRAY or CLAHE", who);
+    *left = image == NRS_FRONT_IMAGE_GRAY ? f->gray.as<uint8_t>() : f->clahe.as<uint8_t>();
+    *right = image == NRS_FRONT_IMAGE_GRAY ? f->gray_r.as<uint8_t>() : f->clahe_r.as<uint8_t>();
     return NRS_OK;
 }
 
@@ -346,12 +436,15 @@ extern "C" int nrs_front_configure(nrs_ctx* c, int32_t n_filters, const nrs_fron
     return NRS_OK;
 }
 
-extern "C" int nrs_front_process(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t channels, uint8_t* gray_out,
-                                 uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out) {
-    if (!c) return NRS_ERR_INVALID;
-    if (!img || w <= 0 || h <= 0) return c->fail(NRS_ERR_INVALID, "nrs_front_process: empty image");
-    if (channels != 1 && channels != 3 && channels != 4) return c->fail(NRS_ERR_INVALID, "nrs_front_process: %d channels (1, 3 or 4)", channels);
-    if ((int64_t)stride < (int64_t)w * channels) return c->fail(NRS_ERR_INVALID, "nrs_front_process: stride below the row length");
+// One frame (right == nullptr: nrs_front_process, the single-frame kernels) or a stereo pair (nrs_front_process_stereo: the right eye is
+// uploaded next to the left one and takes grey + CLAHE in the same launches; the masks are the left eye's).  Everything else is shared.
+static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint8_t* right, int32_t w, int32_t h, int32_t stride, int32_t stride_r,
+                     int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out,
+                     uint8_t* gray_right_out, uint8_t* clahe_right_out) {
+    if (!img || w <= 0 || h <= 0) return c->fail(NRS_ERR_INVALID, "%s: empty image", who);
+    if (channels != 1 && channels != 3 && channels != 4) return c->fail(NRS_ERR_INVALID, "%s: %d channels (1, 3 or 4)", who, channels);
+    if ((int64_t)stride < (int64_t)w * channels || (right && (int64_t)stride_r < (int64_t)w * channels))
+        return c->fail(NRS_ERR_INVALID, "%s: stride below the row length", who);
     NRS_HIP(c, hipSetDevice(c->device));
     FrontState* f = front_default(c);                              // (never configured: no filters, clip 3.0, 8x8)
     if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
@@ -360,20 +453,26 @@ extern "C" int nrs_front_process(nrs_ctx* c, const uint8_t* img, int32_t w, int3
     for (int i = 0; i < nf; ++i) {
         const FrontFilter& q = f->filters[i];
         if (q.kind == NRS_FRONT_PREDEFINED && (q.mw != w || q.mh != h))
-            return c->fail(NRS_ERR_INVALID, "nrs_front_process: filter %d: the predefined mask is %d x %d, the image %d x %d", i, q.mw, q.mh, w, h);
+            return c->fail(NRS_ERR_INVALID, "%s: filter %d: the predefined mask is %d x %d, the image %d x %d", who, i, q.mw, q.mh, w, h);
         if (q.kind == NRS_FRONT_BORDER) {                          // cv::Rect(cb, rb, w - ce - cb, h - re - rb)
             const int rb = q.p[0], re = q.p[1], cb = q.p[2], ce = q.p[3];
             const int64_t rw = (int64_t)w - ce - cb, rh = (int64_t)h - re - rb;
             if (rw <= 0 || rh <= 0 || cb + rw > w || rb + rh > h)
-                return c->fail(NRS_ERR_INVALID, "nrs_front_process: filter %d: the ROI is empty or leaves the %d x %d image", i, w, h);
+                return c->fail(NRS_ERR_INVALID, "%s: filter %d: the ROI is empty or leaves the %d x %d image", who, i, w, h);
             bsrc[i].x0 = cb; bsrc[i].y0 = rb; bsrc[i].x1 = cb + (int)rw; bsrc[i].y1 = rb + (int)rh;
         }
     }
-    f->valid = false;
+    f->valid = false; f->valid_right = false;
     const size_t n = (size_t)w * h, row = (size_t)w * channels;
     NRS_TRY(c->ensure(f->raw, row * h));
     NRS_TRY(c->ensure(f->gray, n));
     NRS_TRY(c->ensure(f->clahe, n));
+    if (right) {
+        NRS_TRY(c->ensure(f->raw_r, row * h));
+        NRS_TRY(c->ensure(f->gray_r, n));
+        NRS_TRY(c->ensure(f->clahe_r, n));
+        NRS_TRY(c->ensure(f->lut_r, (size_t)f->tiles_x * f->tiles_y * 256));
+    }
     NRS_TRY(c->ensure(f->global, n));
     NRS_TRY(c->ensure(f->tmp_a, n));
     NRS_TRY(c->ensure(f->lut, (size_t)f->tiles_x * f->tiles_y * 256));
@@ -382,18 +481,37 @@ extern "C" int nrs_front_process(nrs_ctx* c, const uint8_t* img, int32_t w, int3
         if (f->filters[i].kind == NRS_FRONT_BRIGHT) NRS_TRY(c->ensure(f->tmp_f, sizeof(float) * n));
     }
     NRS_HIP(c, hipMemcpy2DAsync(f->raw.p, row, img, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
+    if (right) NRS_HIP(c, hipMemcpy2DAsync(f->raw_r.p, row, right, (size_t)stride_r, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
     const dim3 blk(256), grid = front_grid(w, h);
     uint8_t* gray = f->gray.as<uint8_t>();
     uint8_t* tmp = f->tmp_a.as<uint8_t>();
-    hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, f->raw.as<uint8_t>(), (int)row, channels, w, h, gray);
     // CLAHE (createCLAHE(clip, Size(8,8))->apply): tiles of the image extended to multiples of the grid
     int pw = w, ph = h;
     if (w % f->tiles_x != 0 || h % f->tiles_y != 0) { pw = w + f->tiles_x - w % f->tiles_x; ph = h + f->tiles_y - h % f->tiles_y; }
     const int tw = pw / f->tiles_x, th = ph / f->tiles_y;
     const int clip = std::max(1, (int)(f->clip * (float)(tw * th) / 256.f));
-    hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, gray, w, h, tw, th, clip, f->lut.as<uint8_t>());
-    hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, gray, w, h, tw, th, f->tiles_x, f->tiles_y, f->lut.as<uint8_t>(),
-                       f->clahe.as<uint8_t>());
+    if (right && !c->dbg.is_set(SW_FRONT_PER_EYE)) {               // the pair: one launch per shared stage, the eye in grid.z
+        const EyesIn raws{{f->raw.as<uint8_t>(), f->raw_r.as<uint8_t>()}}, grays{{gray, f->gray_r.as<uint8_t>()}};
+        const EyesIn luts{{f->lut.as<uint8_t>(), f->lut_r.as<uint8_t>()}};
+        const EyesOut grays_o{{gray, f->gray_r.as<uint8_t>()}}, luts_o{{f->lut.as<uint8_t>(), f->lut_r.as<uint8_t>()}};
+        const EyesOut clahes_o{{f->clahe.as<uint8_t>(), f->clahe_r.as<uint8_t>()}};
+        hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, raws, (int)row, channels, w, h, grays_o);
+        hipLaunchKernelGGL(k_front_clahe_lut_pair, dim3(f->tiles_x, f->tiles_y, 2), blk, 0, c->stream, grays, w, h, tw, th, clip, luts_o);
+        hipLaunchKernelGGL(k_front_clahe_apply_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, grays, w, h, tw, th, f->tiles_x, f->tiles_y, luts,
+                           clahes_o);
+    } else {
+        hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, f->raw.as<uint8_t>(), (int)row, channels, w, h, gray);
+        hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, gray, w, h, tw, th, clip, f->lut.as<uint8_t>());
+        hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, gray, w, h, tw, th, f->tiles_x, f->tiles_y, f->lut.as<uint8_t>(),
+                           f->clahe.as<uint8_t>());
+        if (right) {                                               // NRS_FRONT_PER_EYE: the right eye through the same three kernels
+            uint8_t* gray_r = f->gray_r.as<uint8_t>();
+            hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, f->raw_r.as<uint8_t>(), (int)row, channels, w, h, gray_r);
+            hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, gray_r, w, h, tw, th, clip, f->lut_r.as<uint8_t>());
+            hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, gray_r, w, h, tw, th, f->tiles_x, f->tiles_y, f->lut_r.as<uint8_t>(),
+                               f->clahe_r.as<uint8_t>());
+        }
+    }
     AndSrc all;
     all.n = nf;
     for (int i = 0; i < NRS_FRONT_MAX_FILTERS; ++i) all.p[i] = nullptr;
@@ -421,7 +539,24 @@ extern "C" int nrs_front_process(nrs_ctx* c, const uint8_t* img, int32_t w, int3
     if (filter_masks_out)
         for (int i = 0; i < nf; ++i)
             if (filter_masks_out[i]) NRS_HIP(c, hipMemcpyAsync(filter_masks_out[i], f->fmask[i].p, n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipStreamSynchronize(c->stream));
-    f->w = w; f->h = h; f->valid = true;
+    if (right && gray_right_out) NRS_HIP(c, hipMemcpyAsync(gray_right_out, f->gray_r.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (right && clahe_right_out) NRS_HIP(c, hipMemcpyAsync(clahe_right_out, f->clahe_r.p, n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));                   // (also what lets another context read the resident images afterwards)
+    f->w = w; f->h = h; f->valid = true; f->valid_right = right != nullptr;
     return NRS_OK;
+}
+
+extern "C" int nrs_front_process(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t channels, uint8_t* gray_out,
+                                 uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out) {
+    if (!c) return NRS_ERR_INVALID;
+    return front_run(c, "nrs_front_process", img, nullptr, w, h, stride, 0, channels, gray_out, clahe_out, global_out, filter_masks_out, nullptr, nullptr);
+}
+
+extern "C" int nrs_front_process_stereo(nrs_ctx* c, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h, int32_t stride_l,
+                                        int32_t stride_r, int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out,
+                                        uint8_t* const* filter_masks_out, uint8_t* gray_right_out, uint8_t* clahe_right_out) {
+    if (!c) return NRS_ERR_INVALID;
+    if (!right) return c->fail(NRS_ERR_INVALID, "nrs_front_process_stereo: empty image");
+    return front_run(c, "nrs_front_process_stereo", left, right, w, h, stride_l, stride_r, channels, gray_out, clahe_out, global_out, filter_masks_out,
+                     gray_right_out, clahe_right_out);
 }

@@ -647,6 +647,24 @@ extern "C" int nrs_klt_track_front(nrs_ctx* c, int32_t w, int32_t h, int32_t ima
     return klt_track_impl(c, img, w, h, w, true, n, xy, status, use_initial_flow, min_ssim, n_good, ssim);
 }
 
+// StereoLucasKanade::ComputeStereo3D (stereo_lucas_kanade.cc:38-75) on the resident pair of cf, in the tracker state of c (c == cf: its
+// tracking templates are replaced).  cf's images were complete when nrs_front_process_stereo returned (it synchronises cf's stream), and every
+// launch here is waited for on c's stream before the call returns, so nothing reads them afterwards.
+extern "C" int nrs_stereo_match_lk_front(nrs_ctx* c, nrs_ctx* cf, const nrs_camera* cam, float bf, int32_t w, int32_t h, int32_t image, int32_t n,
+                                         const float* xy, float min_ssim, float* xyz, int32_t* status, float* right_xy, int32_t* track_status) {
+    if (!c || !cf) return c ? c->fail(NRS_ERR_INVALID, "nrs_stereo_match_lk_front: no front-end context") : NRS_ERR_INVALID;
+    if (c->device != cf->device) return c->fail(NRS_ERR_INVALID, "nrs_stereo_match_lk_front: the two contexts are on different devices");
+    const uint8_t *left = nullptr, *right = nullptr;
+    const int rc = front_resident_pair(cf, "nrs_stereo_match_lk_front", w, h, image, &left, &right);
+    if (rc != NRS_OK) return c == cf ? rc : c->fail(rc, "%s", cf->err);
+    if (!cam || w <= KW || h <= KW || n < 0 || (n > 0 && (!xy || !xyz || !status || !right_xy || !track_status)))
+        return c->fail(NRS_ERR_INVALID, "nrs_stereo_match_lk_front: bad argument");
+    NRS_TRY(klt_set_reference_impl(c, left, w, h, w, nullptr, true, n, xy));                       // SetReferenceImage(left, keypoints), no mask
+    for (int i = 0; i < n; ++i) { right_xy[2 * i] = xy[2 * i]; right_xy[2 * i + 1] = xy[2 * i + 1]; track_status[i] = NRS_TRACKED; }
+    NRS_TRY(klt_track_impl(c, right, w, h, w, true, n, right_xy, track_status, 1, min_ssim, nullptr, nullptr));   // Track(right), seeded at the keypoints
+    return nrs_stereo_from_tracks(cam, bf, n, xy, right_xy, track_status, xyz, status);
+}
+
 extern "C" int nrs_klt_get_template(nrs_ctx* c, int32_t idx, float xy[2], int16_t* gray, int16_t* grad, float* mean,
                                     uint8_t* valid) {
     if (!c) return NRS_ERR_INVALID;

@@ -351,16 +351,17 @@ extern "C" void nrs_init_stereo_options_init(nrs_init_stereo_options* opt) {
     if (opt) sinit_options_init(opt);
 }
 
-extern "C" int nrs_init_stereo(nrs_ctx* c, const nrs_camera* cam, const nrs_init_stereo_options* opt, const uint8_t* left, const uint8_t* right,
-                               int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, nrs_init_stereo_result* out) {
-    if (!c) return NRS_ERR_INVALID;
+// Both entry points: nrs_init_stereo (host images: ONE upload of the two images and the keypoints) and nrs_init_stereo_front (on_device: left /
+// right are the packed resident images of nrs_front_process_stereo, only the keypoints go up).  Everything behind the upload is shared.
+static int sinit_run(nrs_ctx* c, const char* who, const nrs_camera* cam, const nrs_init_stereo_options* opt, const uint8_t* left, const uint8_t* right,
+                     bool on_device, int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, nrs_init_stereo_result* out) {
     char msg[256];
     if (sinit_check_args(opt, out, n, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
-    NRS_TRY(stereo_match_check(c, "nrs_init_stereo", cam, left, right, w, h, stride_l, stride_r, n, xy != nullptr));
+    NRS_TRY(stereo_match_check(c, who, cam, left, right, w, h, stride_l, stride_r, n, xy != nullptr));
     sinit_clear(out);
     if (n == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
-    const SinitUpload U((size_t)w, (size_t)h, (size_t)n);
+    const SinitUpload U(on_device ? 0 : (size_t)w, on_device ? 0 : (size_t)h, (size_t)n);     // (resident images: the upload is the keypoints alone)
     const SinitLayout L((size_t)n);
     const size_t ws_bytes = stereo_match_ws_bytes(c, w, h, n);
     const size_t bytes = padded(U.bytes) + ws_bytes + padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n) + padded(sizeof(int) * L.words) +
@@ -380,12 +381,12 @@ extern "C" int nrs_init_stereo(nrs_ctx* c, const nrs_camera* cam, const nrs_init
     int* d_label = cv.take<int>(n);
     int* d_counts = cv.take<int>(4);
     const DbWs dw = db_carve(big.as<char>() + cv.used, n);
-    if (cv.used + db_ws_bytes(n) > bytes) return c->fail(NRS_ERR_STATE, "nrs_init_stereo: workspace accounting");
+    if (cv.used + db_ws_bytes(n) > bytes) return c->fail(NRS_ERR_STATE, "%s: workspace accounting", who);
     std::vector<char> up(U.bytes);
-    sinit_pack_upload(U, left, stride_l, right, stride_r, xy, up.data());
+    sinit_pack_upload(U, left, stride_l, right, stride_r, xy, up.data());                                // (on_device: zero image rows, the keypoints only)
     NRS_HIP(c, hipMemcpyAsync(d_in, up.data(), U.bytes, hipMemcpyHostToDevice, c->stream));              // the one upload
-    const uint8_t* d_left = reinterpret_cast<const uint8_t*>(d_in + U.left);
-    const uint8_t* d_right = reinterpret_cast<const uint8_t*>(d_in + U.right);
+    const uint8_t* d_left = on_device ? left : reinterpret_cast<const uint8_t*>(d_in + U.left);
+    const uint8_t* d_right = on_device ? right : reinterpret_cast<const uint8_t*>(d_in + U.right);
     const float* d_xy = reinterpret_cast<const float*>(d_in + U.xy);
     const SiPacked P{(unsigned)L.xyz, (unsigned)L.status, (unsigned)L.code, (unsigned)L.raw, (unsigned)L.label, (unsigned)L.selected, (unsigned)L.sel_xyz};
     NRS_TRY(stereo_match_enqueue(c, cam, opt->bf, w, h, n, d_left, d_right, d_xy, d_ws, reinterpret_cast<float*>(d_out + L.xyz), d_out + L.status,
@@ -399,8 +400,22 @@ extern "C" int nrs_init_stereo(nrs_ctx* c, const nrs_camera* cam, const nrs_init
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     if (sinit_unpack(packed.data(), n, out) != 0) {
         sinit_clear(out);
-        return c->fail(NRS_ERR_HIP, "nrs_init_stereo: the packed result's header (%d, %d, %d, %d, %d, %d) contradicts itself for %d keypoints", packed[0],
+        return c->fail(NRS_ERR_HIP, "%s: the packed result's header (%d, %d, %d, %d, %d, %d) contradicts itself for %d keypoints", who, packed[0],
                        packed[1], packed[2], packed[3], packed[4], packed[5], n);
     }
     return NRS_OK;
+}
+
+extern "C" int nrs_init_stereo(nrs_ctx* c, const nrs_camera* cam, const nrs_init_stereo_options* opt, const uint8_t* left, const uint8_t* right,
+                               int32_t w, int32_t h, int32_t stride_l, int32_t stride_r, int32_t n, const float* xy, nrs_init_stereo_result* out) {
+    if (!c) return NRS_ERR_INVALID;
+    return sinit_run(c, "nrs_init_stereo", cam, opt, left, right, false, w, h, stride_l, stride_r, n, xy, out);
+}
+
+extern "C" int nrs_init_stereo_front(nrs_ctx* c, const nrs_camera* cam, const nrs_init_stereo_options* opt, int32_t w, int32_t h, int32_t image,
+                                     int32_t n, const float* xy, nrs_init_stereo_result* out) {
+    if (!c) return NRS_ERR_INVALID;
+    const uint8_t *left = nullptr, *right = nullptr;
+    NRS_TRY(front_resident_pair(c, "nrs_init_stereo_front", w, h, image, &left, &right));
+    return sinit_run(c, "nrs_init_stereo_front", cam, opt, left, right, true, w, h, w, w, n, xy, out);
 }

@@ -34,7 +34,8 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
            "nrs_init_options_init", "nrs_init_essential",
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame",
-           "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo"]
+           "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo",
+           "nrs_front_process_stereo", "nrs_stereo_match_pattern_front", "nrs_init_stereo_front", "nrs_stereo_match_lk_front"]
 
 
 class NrsError(RuntimeError):
@@ -168,6 +169,12 @@ def load_library(path=LIB_PATH):
     lib.nrs_rgraph_min_weight.argtypes = [C.c_void_p]
     lib.nrs_local_group_destroy.argtypes = [C.c_void_p]
     lib.nrs_comm_init_local.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    # the resident stereo pair (include/nrs.h "the resident stereo pair")
+    i32, f32, ptr = C.c_int32, C.c_float, C.c_void_p
+    lib.nrs_front_process_stereo.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
+    lib.nrs_stereo_match_pattern_front.argtypes = [ptr, ptr, f32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]
+    lib.nrs_init_stereo_front.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr]
+    lib.nrs_stereo_match_lk_front.argtypes = [ptr, ptr, ptr, f32, i32, i32, i32, i32, ptr, f32, ptr, ptr, ptr, ptr]
     return lib
 
 
@@ -244,6 +251,20 @@ def stereo_lk(ctx_stereo, cam, bf, left, right, xy, min_ssim=0.5):
     ctx_stereo.klt_set_reference(left, xy)
     rxy, st, _, _ = ctx_stereo.klt_track(right, xy, np.full(len(xy), 1, np.int32), initial_flow=True, min_ssim=min_ssim)
     xyz, status = stereo_from_tracks(cam, bf, xy, rxy, st, ctx_stereo.lib)
+    return xyz, status, rxy, st
+
+
+def stereo_lk_front(ctx_stereo, ctx_front, cam, bf, xy, min_ssim=0.5, image=FRONT_GRAY, shape=None):
+    """nrs_stereo_match_lk_front: stereo_lk on the resident pair ctx_front holds after front_process_stereo, in the tracker state of
+    ctx_stereo (a context kept for stereo, on the same device).  The two may be the same context: the call then REPLACES its tracking
+    templates, as stereo_lk replaces those of its ctx_stereo.  -> (xyz, status, right_xy, track_status)"""
+    hh, ww = shape or ctx_front._front_shape
+    xy = _f32(xy).reshape(-1, 2)
+    n = len(xy)
+    xyz, status = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+    rxy, st = np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
+    ctx_stereo._chk(ctx_stereo.lib.nrs_stereo_match_lk_front(ctx_stereo.h, ctx_front.h, C.byref(cam), bf, ww, hh, int(image), n, _p(xy, C.c_float),
+                                                             min_ssim, _p(xyz, C.c_float), _p(status, C.c_int32), _p(rxy, C.c_float), _p(st, C.c_int32)))
     return xyz, status, rxy, st
 
 
@@ -553,6 +574,44 @@ class Context:
                                              _p(out.get("gray"), C.c_uint8), _p(out.get("clahe"), C.c_uint8), _p(out.get("global"), C.c_uint8), ptrs))
         return out
 
+    def front_process_stereo(self, left, right, outputs=True, stride_l=None, stride_r=None, width=None, channels=1):
+        """nrs_front_process_stereo: both eyes of a stereo pair in one call (the left one as front_process, the right one grey + CLAHE).  left /
+        right: h x w or h x w x 3 / 4 uint8 of the same shape -- or, with stride_l / stride_r (bytes), width and channels, the raw h x stride byte
+        arrays.  outputs: True, False or the names wanted of "gray", "clahe", "global", "masks", "gray_right", "clahe_right".  -> dict of those.
+        The C entry point takes ONE w, h and channel count, so two arrays that differ in size or channel count cannot reach it: THIS BINDING
+        refuses them, raising NrsError with NRS_ERR_INVALID before the library is called.  A right image of None goes to the library as NULL
+        and is refused there."""
+        left = np.asarray(left, np.uint8)
+        none_right = right is None                                  # (handed to the library as NULL: it refuses)
+        right = left if none_right else np.asarray(right, np.uint8)
+        if (stride_l is None) != (stride_r is None):
+            raise ValueError("front_process_stereo: give both strides or neither")
+        if stride_l is None:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+            if left.shape != right.shape:
+                raise NrsError(-1, "front_process_stereo: the eyes differ in size or channel count: %s and %s" % (left.shape, right.shape))
+            hh, ww = left.shape[:2]
+            ch = 1 if left.ndim == 2 else left.shape[2]
+            stride_l = stride_r = left.strides[0] if hh else ww * ch
+        else:
+            if left.shape[0] != right.shape[0]:
+                raise NrsError(-1, "front_process_stereo: the eyes differ in height: %d and %d" % (left.shape[0], right.shape[0]))
+            hh, ww, ch = left.shape[0], int(width), int(channels)
+        nf = getattr(self, "_front_n", 0)
+        names = ("gray", "clahe", "global", "gray_right", "clahe_right")
+        want = names + ("masks",) if outputs is True else tuple(outputs or ())
+        out = {k: np.zeros((hh, ww), np.uint8) for k in names if k in want}
+        ptrs = None
+        if "masks" in want:
+            out["masks"] = [np.zeros((hh, ww), np.uint8) for _ in range(nf)]
+            if nf:
+                ptrs = (C.c_void_p * nf)(*[m.ctypes.data for m in out["masks"]])
+        self._chk(self.lib.nrs_front_process_stereo(self.h, left.ctypes.data, None if none_right else right.ctypes.data, ww, hh, int(stride_l), int(stride_r), ch,
+                                                    _p(out.get("gray"), C.c_uint8), _p(out.get("clahe"), C.c_uint8), _p(out.get("global"), C.c_uint8),
+                                                    ptrs, _p(out.get("gray_right"), C.c_uint8), _p(out.get("clahe_right"), C.c_uint8)))
+        self._front_shape = (hh, ww)                                # (after the call: a refused pair leaves the resident size as it was)
+        return out
+
     def klt_set_reference_front(self, xy, image=FRONT_GRAY, use_global_mask=True, shape=None):
         hh, ww = shape or self._front_shape
         xy = _f32(xy).reshape(-1, 2)
@@ -726,6 +785,17 @@ class Context:
         left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
         h = left.shape[0]
         w = left.shape[1] if width is None else int(width)
+        return self._init_stereo(cam, xy, options, struct_size, result_struct_size, n, lambda opt, xy, m, out: self.lib.nrs_init_stereo(
+            self.h, C.byref(cam), C.byref(opt), _p(left, C.c_uint8), _p(right, C.c_uint8), C.c_int32(w), C.c_int32(h),
+            C.c_int32(stride_l or left.strides[0]), C.c_int32(stride_r or right.strides[0]), C.c_int32(m), _p(xy, C.c_float), C.byref(out)))
+
+    def init_stereo_front(self, cam, xy, image=FRONT_GRAY, shape=None, **options):
+        """nrs_init_stereo_front: init_stereo on the resident pair of front_process_stereo (only the keypoints go up); the same dict"""
+        hh, ww = shape or self._front_shape
+        return self._init_stereo(cam, xy, options, None, None, None, lambda opt, xy, m, out: self.lib.nrs_init_stereo_front(
+            self.h, C.byref(cam), C.byref(opt), ww, hh, int(image), m, _p(xy, C.c_float), C.byref(out)))
+
+    def _init_stereo(self, cam, xy, options, struct_size, result_struct_size, n, call):
         xy = _f32(xy).reshape(-1, 2)
         m = len(xy)
         opt = InitStereoOptions()
@@ -742,9 +812,7 @@ class Context:
                  label=np.zeros(m, np.int32), selected=np.zeros(m, np.int32), selected_xyz=np.zeros((m, 3), np.float32))
         for k, v in a.items():
             setattr(out, k, v.ctypes.data if v.size else None)
-        self._chk(self.lib.nrs_init_stereo(self.h, C.byref(cam), C.byref(opt), _p(left, C.c_uint8), _p(right, C.c_uint8), C.c_int32(w), C.c_int32(h),
-                                           C.c_int32(stride_l or left.strides[0]), C.c_int32(stride_r or right.strides[0]),
-                                           C.c_int32(m if n is None else n), _p(xy, C.c_float), C.byref(out)))
+        self._chk(call(opt, xy, m if n is None else n, out))
         ns = out.n_selected
         r = dict(verdict=out.verdict, n_matched=out.n_matched, n_gated=out.n_gated, n_clusters=out.n_clusters, n_noise=out.n_noise,
                  n_selected=ns, median_depth=np.float32(out.median_depth), bf=np.float32(opt.bf))
@@ -767,6 +835,17 @@ class Context:
                                                     C.c_int32(h), C.c_int32(stride_l or left.strides[0]), C.c_int32(stride_r or right.strides[0]),
                                                     C.c_int32(n), _p(xy, C.c_float), _p(xyz, C.c_float), _p(status, C.c_int32),
                                                     _p(score, C.c_double), _p(match, C.c_int32)))
+        return xyz, status, score, match
+
+    def stereo_match_pattern_front(self, cam, bf, xy, image=FRONT_GRAY, shape=None):
+        """nrs_stereo_match_pattern_front: stereo_match_pattern on the resident pair of front_process_stereo; the same four outputs"""
+        hh, ww = shape or self._front_shape
+        xy = _f32(xy).reshape(-1, 2)
+        n = len(xy)
+        xyz, status = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        score, match = np.zeros(n, np.float64), np.zeros((n, 2), np.int32)
+        self._chk(self.lib.nrs_stereo_match_pattern_front(self.h, C.byref(cam), bf, ww, hh, int(image), n, _p(xy, C.c_float), _p(xyz, C.c_float),
+                                                          _p(status, C.c_int32), _p(score, C.c_double), _p(match, C.c_int32)))
         return xyz, status, score, match
 
     def eval_depth_ground_truth(self, cam, depth, xy):

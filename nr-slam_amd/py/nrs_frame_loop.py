@@ -113,6 +113,7 @@ class GpuBackend:
         self.ctx.klt_configure(klt_opts["win"], klt_opts["max_level"], klt_opts["max_iters"], klt_opts["epsilon"], klt_opts["min_eig"])
         self.front = bool(front) or isinstance(front, (list, tuple))
         self._front_im, self._front_gray = None, None
+        self._front_right, self._front_fresh, self.n_front_calls = None, None, 0      # (n_front_calls: front-end calls made, one or two eyes each)
         if self.front:
             self.ctx.front_configure(front if isinstance(front, (list, tuple)) else ())
 
@@ -127,8 +128,23 @@ class GpuBackend:
     def _front_frame(self, im, force=False):
         if force or im is not self._front_im:
             self._front_gray = self.ctx.front_process(im, outputs=("gray",))["gray"]
-            self._front_im = im
+            self._front_im, self._front_right, self._front_fresh = im, None, None      # (a single frame invalidates the resident right eye)
+            self.n_front_calls += 1
         return self._front_gray
+
+    # front mode, stereo: one nrs_front_process_stereo per pair -- the same identity rule on (left, right).  Afterwards the left eye is the
+    # resident frame of every step above (they see the same `left` array and do not process again) and both eyes are there for init_stereo /
+    # stereo_pattern / stereo_lk.  force: the start of a frame (FrameLoop.track_image_with_stereo); the klt_track that follows on the same
+    # left array then tracks on the resident eye instead of processing it a second time
+    def front_stereo(self, left, right, force=False):
+        if not self.front:
+            raise ValueError("front_stereo needs the front mode (front=True or a list of filters)")
+        if force or left is not self._front_im or right is not self._front_right:
+            self._front_gray = self.ctx.front_process_stereo(left, right, outputs=("gray",))["gray"]
+            self._front_im, self._front_right = left, right
+            self.n_front_calls += 1
+            if force:
+                self._front_fresh = left
 
     # main tracker
     def klt_set_reference(self, im, pts):
@@ -139,7 +155,10 @@ class GpuBackend:
 
     def klt_track(self, im, pts, status, min_ssim):
         if self.front:
-            self._front_frame(im, force=True)
+            if im is self._front_fresh:                            # this frame's pair has just been processed: its left eye is resident
+                self._front_fresh = None
+            else:
+                self._front_frame(im, force=True)
             xy, st, good, _ = self.ctx.klt_track_front(pts, status, self.nrs.FRONT_GRAY, initial_flow=True, min_ssim=min_ssim)
             return xy, st
         xy, st, good, _ = self.ctx.klt_track(im, pts, status, initial_flow=True, min_ssim=min_ssim)
@@ -204,11 +223,16 @@ class GpuBackend:
     def init_essential(self, ref_xy, cur_xy, status, n_matches, **options):
         return self.ctx.init_essential(self.cam, ref_xy, cur_xy, status, n_matches, taps=False, **options)
 
-    # Tracking::StereoMapInitialization (tracking.cc:216-263) on the device: include/nrs.h nrs_init_stereo.  The images are grey bytes from
-    # the host (the resident-frame variant is not built); the result carries the selected keypoints for FrameLoop.from_stereo_initialization
+    # Tracking::StereoMapInitialization (tracking.cc:216-263) on the device: include/nrs.h nrs_init_stereo.  Without the front mode the images
+    # are grey bytes from the host; in front mode they are the RAW frames, processed once as a pair (front_stereo) and matched where they
+    # lie (nrs_init_stereo_front).  The result carries the selected keypoints for FrameLoop.from_stereo_initialization
     def init_stereo(self, left, right, kp, **options):
         kp = np.asarray(kp, F32).reshape(-1, 2)
-        r = self.ctx.init_stereo(self.cam, left, right, kp, **options)
+        if self.front:
+            self.front_stereo(left, right)
+            r = self.ctx.init_stereo_front(self.cam, kp, self.nrs.FRONT_GRAY, **options)
+        else:
+            r = self.ctx.init_stereo(self.cam, left, right, kp, **options)
         r["selected_keypoints"] = kp[r["selected"]].copy()
         return r
 
@@ -293,17 +317,26 @@ class GpuBackend:
     def eval_frame(self, q, t, X, kp, depth=None, gt_xyz=None, gt_status=None):
         return self.ctx.eval_frame(self.cam, q, t, X, kp, depth=depth, gt_xyz=gt_xyz, gt_status=gt_status)
 
+    # (front mode: left / right are the raw frames; the pair is processed once -- front_stereo -- and matched where it lies)
     def stereo_pattern(self, left, right, kp, bf):
+        if self.front:
+            self.front_stereo(left, right)
+            xyz, st, _, _ = self.ctx.stereo_match_pattern_front(self.cam, bf, kp, self.nrs.FRONT_GRAY)
+            return xyz, st
         xyz, st, _, _ = self.ctx.stereo_match_pattern(self.cam, bf, left, right, kp)
         return xyz, st
 
     # the reference's LK stereo matcher owns its tracker (SLAM/system.cc:45-54): a third context, made on first use, so that the
-    # tracking templates of self.ctx are left alone
+    # tracking templates of self.ctx are left alone.  In front mode it reads the pair resident in self.ctx (nrs_stereo_match_lk_front)
     def stereo_lk(self, left, right, kp, bf, min_ssim=0.5):
         if getattr(self, "ctx_stereo", None) is None:
             o = self.klt_opts
             self.ctx_stereo = self.nrs.Context()
             self.ctx_stereo.klt_configure(o["win"], o["max_level"], o["max_iters"], o["epsilon"], o["min_eig"])
+        if self.front:
+            self.front_stereo(left, right)
+            xyz, st, _, _ = self.nrs.stereo_lk_front(self.ctx_stereo, self.ctx, self.cam, bf, kp, min_ssim, self.nrs.FRONT_GRAY)
+            return xyz, st
         xyz, st, _, _ = self.nrs.stereo_lk(self.ctx_stereo, self.cam, bf, left, right, kp, min_ssim)
         return xyz, st
 
@@ -616,6 +649,20 @@ class FrameLoop:
             self.log[-1]["status_after_mapping"] = self._status_by_map()
         return n3d >= 10
 
+    # ---- System::TrackImageWithStereo (SLAM/system.cc:134-160): ImageProcessing on both images (:137-138), the masks from the left one
+    # (:144), TrackImage and DoMapping on the left (:146-150) and -- compiled out in the reference by `if (false && ...)` at :153, so off by
+    # default here -- the evaluation against the stereo matcher.  Needs a front-mode backend: the pair is processed in ONE call, the tracker's
+    # klt_track of this frame runs on the resident left eye, and evaluate() matches the resident pair.
+    def track_image_with_stereo(self, left, right, evaluate=False, matcher="pattern", bf=1.0):
+        if not getattr(self.b, "front", False) or not hasattr(self.b, "front_stereo"):
+            raise ValueError("track_image_with_stereo needs a front-mode backend (GpuBackend(front=...))")
+        self.b.front_stereo(left, right, force=True)
+        self.stereo_pair = (left, right)
+        ok = self.track_image(left)
+        if evaluate:
+            self.evaluate(right=right, matcher=matcher, left=left, bf=bf)
+        return ok
+
     # ---- Mapping::DoMapping (mapping.cc:36-54) without the BA: a pending keyframe takes the KeyFrameMapping branch, which is skipped
     def do_mapping(self, keyframe_inserted):
         if self.keyframe_ba:                                       # (keyframe_insertion has queued the new keyframe)
@@ -709,9 +756,14 @@ class FrameLoop:
         """Scores the current frame: the TRACKED_WITH_3D slots against a depth image (fp32, h x w) or against a stereo matcher run on
         (left, right) grey images -- matcher "pattern" (StereoPatternMatching) or "lk" (StereoLucasKanade); bf is the matcher's baseline_.
         Appends dict(rmse, scale, counts, n, rc) to self.rmse and returns it (rmse NaN, rc -1: too few points with ground truth); the
-        world-frame ground truth of the evaluated slots is kept in self.ground_truth (slot indices in self.ground_truth_slots)."""
+        world-frame ground truth of the evaluated slots is kept in self.ground_truth (slot indices in self.ground_truth_slots).
+        With a front-mode backend left / right are the RAW frames and the matcher runs on the resident pair (processed once; nothing is
+        processed when they are the arrays track_image_with_stereo has just been given); left may then be left out after
+        track_image_with_stereo: it is that call's left frame."""
         if not hasattr(self, "rmse"):
             self.rmse = []
+        if left is None and right is not None and getattr(self.b, "front", False) and getattr(self, "stereo_pair", None) is not None:
+            left = self.stereo_pair[0]
         slots = np.nonzero(self.status == TRACKED_WITH_3D)[0]
         kp, X = self.kp[slots], self.pos[slots]
         if depth is not None:
