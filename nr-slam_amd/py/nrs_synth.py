@@ -829,6 +829,159 @@ def make_cluster_cases():
     return cases
 
 
+DB_CHUNK, DB_TRIP = 1024, 4096       # nrs_dbscan3d: points of a compaction chunk; points behind one trip of a lane-strided word loop (64 x 64)
+
+
+def _star(centre):
+    """a core point with six neighbours that are no neighbours of each other (2 apart along the axes, eps 2.5): with min_points 5 the
+    centre is the cluster's only core point, the six are border points"""
+    c = np.asarray(centre, np.float64)
+    return c, c + 2.0 * np.concatenate([np.eye(3), -np.eye(3)])
+
+
+def _roots(raw, core):
+    """lowest core index of every cluster, by raw label (ascending, since raw labels are given in that order)"""
+    r = np.full(int(raw.max()) + 1 if len(raw) else 0, len(raw), np.int64)
+    idx = np.nonzero(core)[0]
+    np.minimum.at(r, raw[idx], idx)
+    return r
+
+
+def _holds_roots_in_three_chunks(c, raw, core, nb):
+    roots = _roots(raw, core)
+    n = len(raw)
+    assert np.all(roots < n) and np.all(np.diff(roots) > 0)
+    per_chunk = np.bincount(roots // DB_CHUNK, minlength=3)
+    assert len(per_chunk) == 3 and per_chunk.min() >= 20, per_chunk
+    size = np.bincount(raw[raw >= 0])
+    chunks_of_size = {}
+    for k, s in enumerate(size):
+        chunks_of_size.setdefault(int(s), set()).add(int(roots[k] // DB_CHUNK))
+    assert any(len(v) > 1 for v in chunks_of_size.values())       # equal sizes, roots in different chunks: the ranking's tie-break
+    assert (raw < 0).any()
+
+
+def _holds_first_root_late(c, raw, core, nb):
+    assert not core[:2 * DB_CHUNK].any() and core[2 * DB_CHUNK:].sum() >= 2
+    assert (raw[:2 * DB_CHUNK] >= 0).any() and (raw[:2 * DB_CHUNK] < 0).any()      # border points and noise in front
+    assert raw.max() >= 1
+
+
+def _holds_second_trip(c, raw, core, nb):
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import connected_components
+    n = len(raw)
+    assert n > DB_TRIP
+    low = core & (np.arange(n) < DB_TRIP)
+    g = csr_matrix(nb & low[:, None] & low[None, :])
+    _, comp = connected_components(g, directed=False)              # components of the core points that the first trip alone sees
+    first = [i for i in range(64) if core[i]]
+    assert any(raw[i] == raw[j] and comp[i] != comp[j] for i in first for j in first), "joined only through a core point behind the trip"
+    only_high = wrong_not_noise = False
+    for q in np.nonzero(~core & (raw >= 0))[0]:
+        cn = np.nonzero(nb[q] & core)[0]
+        lo, hi = cn[cn < DB_TRIP], cn[cn >= DB_TRIP]
+        if len(hi) and not len(lo):
+            only_high = True
+        if len(hi) and len(lo) and raw[lo].min() > raw[hi].min():
+            wrong_not_noise = True
+    assert only_high and wrong_not_noise
+
+
+def _holds_one_chain(c, raw, core, nb):
+    n = len(raw)
+    assert n > DB_TRIP and np.all(raw == 0) and core.sum() == n - 2          # (the two ends have one neighbour: border points)
+    assert nb[:DB_TRIP, DB_TRIP:].any()                            # neighbours on either side of the word-64 boundary
+
+
+def _holds_full(c, raw, core, nb):
+    n = len(raw)
+    assert n > 16384 - 64 and (n + 63) // 64 == 256
+    roots = _roots(raw, core)
+    assert len(np.unique(roots // DB_CHUNK)) >= 8
+    last = np.nonzero(core[16320:])[0] + 16320
+    assert any(roots[raw[i]] < DB_CHUNK for i in last)
+
+
+def make_large_cluster_cases():
+    """Point sets for nrs_dbscan3d past one compaction chunk (1024 points), past one trip of the lane-strided word loops (4096 points) and
+    at the limit (16384 points): the list of make_cluster_cases' dicts, each with `holds(case, raw, core, nb)`, which asserts from the
+    oracle's raw labels, core flags and neighbour matrix that the set holds what it is made for.
+      roots_in_three_chunks   clusters whose lowest core index lies in each of [0, 1024), [1024, 2048), [2048, n): blobs of 8 points whose
+                              members all come at or after their chunk's start, and for the narrow last chunk stars (`_star`) whose centre
+                              comes there; blobs of equal size in different chunks
+      first_root_late         no core point before index 2048: star satellites and noise in front, the star centres and one blob behind
+      second_trip4097 / 4160  around the origin + (1000, 0, 0), min_points 3: C (index >= 4096) joins A and B (indices 3 and 40); P touches
+                              C alone; Q touches C and D (index 50, a cluster of its own with a higher raw label); leaves make A, B, D core
+      chain4200_shuffled      one chain, min_points 2, 0.9 eps apart
+      full16384 / full16321   the blob recipe shuffled; a member of the first blob point's blob is moved to the last index"""
+    rng = np.random.default_rng(67)
+    eps, mp = 2.5, 5
+    cases = []
+
+    def add(name, xyz, holds, eps=eps, min_points=mp):
+        cases.append(dict(name=name, xyz=np.ascontiguousarray(xyz, F32).reshape(-1, 3), eps=float(eps), min_points=int(min_points), holds=holds))
+
+    def centres(k):
+        return rng.uniform(-300, 300, (k, 3))
+
+    def blob_points(c):
+        return (c[:, None, :] + rng.normal(0, 0.6, (len(c), 8, 3))).reshape(-1, 3)
+
+    # roots_in_three_chunks: 100 blobs free, 100 blobs at index >= 1024, 30 stars with the centre at index >= 2048, 290 noise points
+    n = 2100
+    free = np.concatenate([blob_points(centres(100)), rng.uniform(-300, 300, (290, 3))])
+    mid = blob_points(centres(100))
+    stars = [_star(c) for c in centres(30)]
+    late = np.array([s[0] for s in stars])
+    free = np.concatenate([free] + [s[1] for s in stars])
+    free, mid = free[rng.permutation(len(free))], mid[rng.permutation(len(mid))]
+    n_late_mid = n - 2 * DB_CHUNK - len(late)                      # the last chunk: the star centres and this many points of `mid`
+    tail = np.concatenate([late, mid[:n_late_mid]])
+    middle = np.concatenate([mid[n_late_mid:], free[:DB_CHUNK - (len(mid) - n_late_mid)]])
+    front = free[DB_CHUNK - (len(mid) - n_late_mid):]
+    assert len(front) == DB_CHUNK and len(middle) == DB_CHUNK and len(tail) == n - 2 * DB_CHUNK
+    add("roots_in_three_chunks", np.concatenate([front[rng.permutation(DB_CHUNK)], middle[rng.permutation(DB_CHUNK)], tail[rng.permutation(len(tail))]]),
+        _holds_roots_in_three_chunks)
+
+    # first_root_late: 8 star centres and a blob of 44 behind index 2047; the 48 satellites and 2000 noise points in front
+    stars = [_star(c) for c in centres(8)]
+    front = np.concatenate([s[1] for s in stars] + [rng.uniform(-300, 300, (2 * DB_CHUNK - 48, 3))])
+    tail = np.concatenate([np.array([s[0] for s in stars]), centres(1) + rng.normal(0, 0.6, (44, 3))])
+    add("first_root_late", np.concatenate([front[rng.permutation(len(front))], tail[rng.permutation(len(tail))]]), _holds_first_root_late)
+
+    # second_trip: the planted points by name -> (index, position); everything else is blobs and noise within +-300
+    for n, ic in ((DB_TRIP + 1, DB_TRIP), (DB_TRIP + 64, DB_TRIP + 63)):
+        k = (n - 12) // 9
+        fill = np.concatenate([blob_points(centres(k)), rng.uniform(-300, 300, (n - 12 - 8 * k, 3))])
+        fill = fill[rng.permutation(len(fill))]
+        planted = {3: (-2, 0, 0), 7: (-2, 2, 0), 8: (-2, -2, 0),                  # A and its leaves
+                   40: (2, 0, 0), 41: (2, 2, 0), 42: (2, -2, 0),                  # B and its leaves
+                   50: (0, 0, -4), 51: (0, 2, -4), 52: (0, -2, -4),               # D and its leaves
+                   60: (0, 0, 2), 61: (0, 0, -2), ic: (0, 0, 0)}                  # P, Q and C
+        xyz = np.zeros((n, 3))
+        rest = np.array([i for i in range(n) if i not in planted])
+        xyz[rest] = fill
+        for i, p in planted.items():
+            xyz[i] = np.array(p, np.float64) + (1000.0, 0.0, 0.0)
+        add("second_trip%d" % n, xyz, _holds_second_trip, min_points=3)
+
+    chain = np.stack([np.arange(4200) * 0.9 * eps, np.zeros(4200), np.zeros(4200)], 1)
+    add("chain4200_shuffled", chain[rng.permutation(4200)], _holds_one_chain, min_points=2)
+
+    for n in (16384, 16384 - 63):
+        k = int(n * 0.9) // 8
+        member = np.concatenate([np.repeat(np.arange(k), 8), np.full(n - 8 * k, -1)])
+        xyz = np.concatenate([blob_points(centres(k)), rng.uniform(-300, 300, (n - 8 * k, 3))])
+        order = rng.permutation(n)
+        xyz, member = xyz[order], member[order]
+        first = int(np.nonzero(member >= 0)[0][0])                 # (index 0 or just behind it)
+        other = int(np.nonzero(member == member[first])[0][1])
+        xyz[[other, n - 1]] = xyz[[n - 1, other]]
+        add("full%d" % n, xyz, _holds_full)
+    return cases
+
+
 def make_stereo_init_sequence(n_points=500, n_frames=3, seed=3, wh=(320, 240), step=0.35, rot_step=(0.0006, -0.0009, 0.0004), bf=2400.0):
     """make_init_sequence's surface, texture and warp (the same random stream, so the same left images) plus a RIGHT view of frame 0: the
     same warp for a camera displaced by the baseline along +x only, so the pair is rectified -- a point at depth z that the left image shows

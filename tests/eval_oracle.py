@@ -27,7 +27,9 @@ def search_dims(w, h):
     return (w - 3) - 14, 2 * int(F32(h - 1) / F32(2) - F32(2)) - 14
 
 
-def stereo_match_pattern(prm, bf, left, right, xy):
+def stereo_match_pattern_per_keypoint(prm, bf, left, right, xy):
+    """the statement this module started with: one full correlation per keypoint.  tests/test_eval_oracle_cpu.py holds
+    `stereo_match_pattern` (below) to it byte for byte"""
     left, right = np.asarray(left, np.uint8), np.asarray(right, np.uint8)
     h, w = right.shape
     Wr, Hr = search_dims(w, h)
@@ -58,6 +60,71 @@ def stereo_match_pattern(prm, bf, left, right, xy):
         my, mx = divmod(k, Wr)
         score[i], match[i] = s[my, mx], (mx, my)
         if s[my, mx] < 0.99:
+            status[i] = LOW_CORRELATION
+            continue
+        disp = np.abs(F32(mx + 7) - x)
+        if disp == 0:
+            status[i] = ZERO_DISPARITY
+            continue
+        xyz[i] = disparity_to_point(prm, bf, disp, x, y)
+    return xyz, status, score, match
+
+
+class ScoreMaps:
+    """The fp64 TM_CCORR_NORMED map of a template cell: the 15 x 15 window of `left` whose top-left corner is (ox, oy) against every search
+    position of `right`, [Hr, Wr].  A keypoint's result depends on the images and on its integer cell only, so `best` remembers the first
+    maximum per cell; case builders read `map` to assert what a scene holds."""
+
+    def __init__(self, left, right):
+        self.left, right = np.asarray(left, np.uint8), np.asarray(right, np.uint8)
+        self.h, self.w = right.shape
+        self.Wr, self.Hr = search_dims(self.w, self.h)
+        self.win = sliding_window_view(right[:self.Hr + 14, :self.Wr + 14].astype(np.int64), (15, 15))      # Hr x Wr x 15 x 15
+        self.I2 = (self.win * self.win).sum((2, 3))
+        self._best = {}
+
+    def template(self, ox, oy):
+        return self.left[oy:oy + 15, ox:ox + 15].astype(np.int64)
+
+    def map(self, ox, oy):
+        T = self.template(ox, oy)
+        TI = (self.win * T).sum((2, 3))
+        den = np.sqrt((T * T).sum().astype(np.float64) * self.I2.astype(np.float64))
+        return np.where(den > 0, TI.astype(np.float64) / np.where(den > 0, den, 1.0), 0.0)
+
+    def best(self, ox, oy):
+        """-> (score, mx, my) of the first maximum in row-major order"""
+        if (ox, oy) not in self._best:
+            s = self.map(ox, oy)
+            my, mx = divmod(int(np.argmax(s)), self.Wr)
+            self._best[(ox, oy)] = (s[my, mx], mx, my)
+        return self._best[(ox, oy)]
+
+
+def stereo_match_pattern(prm, bf, left, right, xy):
+    """stereo_match_pattern_per_keypoint with one correlation per template CELL of the call (ScoreMaps.best)"""
+    maps = ScoreMaps(left, right)
+    h, w = maps.h, maps.w
+    xy = np.asarray(xy, F32).reshape(-1, 2)
+    n = len(xy)
+    xyz = np.full((n, 3), np.nan, F32)
+    status = np.zeros(n, np.int32)
+    score = np.full(n, np.nan, np.float64)
+    match = np.full((n, 2), -1, np.int32)
+    for i, (x, y) in enumerate(xy):
+        if x < 0 or y < 0 or y > F32(h - 20) or x > F32(w - 20) or not (x == x and y == y):
+            status[i] = OUT_OF_BOUNDS
+            continue
+        if F32(x - F32(7)) < 20 or F32(y - F32(7)) < 0 or F32(x + F32(7)) > w or F32(y + F32(7)) > h:
+            status[i] = OUT_OF_BOUNDS
+            continue
+        ox, oy = int(F32(x - F32(7))), int(F32(y - F32(7)))
+        if maps.template(ox, oy).max() > 250:
+            status[i] = SATURATED
+            continue
+        s, mx, my = maps.best(ox, oy)
+        score[i], match[i] = s, (mx, my)
+        if s < 0.99:
             status[i] = LOW_CORRELATION
             continue
         disp = np.abs(F32(mx + 7) - x)

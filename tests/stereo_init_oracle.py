@@ -50,9 +50,11 @@ def rank_labels(raw, noise_competes):
     return label, counts
 
 
-def dbscan3d(xyz, eps=2.5, min_points=5, noise_competes=True):
-    """-> (raw_label, label, counts).  The sequential algorithm: OrderedPointSelection, a queue per cluster"""
-    nb = neighbours(xyz, eps)
+def dbscan3d_raw(xyz, eps=2.5, min_points=5, nb=None):
+    """-> (raw_label, core flags).  The sequential algorithm: OrderedPointSelection, a queue per cluster.  nb: `neighbours(xyz, eps)` when
+    the caller holds it already (the large cases, whose properties are asserted on the same matrix)"""
+    if nb is None:
+        nb = neighbours(xyz, eps)
     n = len(nb)
     core = nb.sum(1) >= min_points
     raw = np.full(n, -1, np.int32)
@@ -73,6 +75,12 @@ def dbscan3d(xyz, eps=2.5, min_points=5, noise_competes=True):
                     visited[j] = True
                     queue.append(int(j))
         next_label += 1
+    return raw, core
+
+
+def dbscan3d(xyz, eps=2.5, min_points=5, noise_competes=True):
+    """-> (raw_label, label, counts): dbscan3d_raw and the reference's ranking"""
+    raw, _ = dbscan3d_raw(xyz, eps, min_points)
     label, counts = rank_labels(raw, noise_competes)
     return raw, label, counts
 

@@ -46,6 +46,31 @@ def test_oracle_returns_the_intended_status_of_each_special_keypoint(pair):
     assert np.isnan(score[oob]).all() and (match[oob] == -1).all()
 
 
+def test_one_correlation_per_cell_gives_the_bytes_of_one_per_keypoint(pair):
+    """stereo_match_pattern remembers the first maximum per template cell; the statement it replaced (kept as
+    stereo_match_pattern_per_keypoint) correlates once per keypoint.  The same bytes, also when cells repeat and on strided-row scenes'
+    images and on the scene of the resident pair"""
+    import stereo_cases as SC
+    sc = SC.pattern_scene()
+    twice = np.concatenate([pair["xy"][:16], pair["xy"][:16][::-1] + F32(0.125)])       # cells that repeat, with other fractions
+    for left, right, xy, bf in ((pair["left"], pair["right"], pair["xy"], 2000.0), (pair["left"], pair["right"], twice, 400.0),
+                                (sc["left"], sc["right"], sc["xy"], SC.BF_PATTERN), (pair["left"], pair["right"], pair["xy"][:0], 2000.0)):
+        a = E.stereo_match_pattern(PRM, bf, left, right, xy)
+        b = E.stereo_match_pattern_per_keypoint(PRM, bf, left, right, xy)
+        for x, y, name in zip(a, b, ("xyz", "status", "score", "match")):
+            assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), name
+    assert np.array_equal(E.ScoreMaps(pair["left"], pair["right"]).map(30, 8).shape, E.search_dims(*pair["wh"])[::-1])
+
+
+@pytest.mark.parametrize("wh, disp, n", [((96, 64), (0, 8), 40), ((203, 131), (8, 16, 4, 10, 6), 90)], ids=["96x64", "203x131"])
+def test_one_correlation_per_cell_on_the_scenes_of_the_stereo_start(wh, disp, n):
+    p = S.make_stereo_pair(wh, 3, disp, n)
+    a = E.stereo_match_pattern(PRM, 400.0, p["left"], p["right"], p["xy"])
+    b = E.stereo_match_pattern_per_keypoint(PRM, 400.0, p["left"], p["right"], p["xy"])
+    for x, y, name in zip(a, b, ("xyz", "status", "score", "match")):
+        assert x.dtype == y.dtype and x.tobytes() == y.tobytes(), name
+
+
 def test_stereo_from_tracks_matches_the_oracle_bit_for_bit(lib_built):
     nrs = lib_built
     rng = np.random.default_rng(4)

@@ -6,6 +6,7 @@ import pytest
 import eval_oracle as E
 import nrs
 import nrs_synth as S
+import stereo_cases as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +61,35 @@ def test_plain_form_gives_identical_bits(ctx, case):
     _same(b, case["oracle"])
     assert np.array_equal(a[1], b[1]) and np.array_equal(a[3], b[3])
     assert a[2].tobytes() == b[2].tobytes() and a[0].tobytes() == b[0].tobytes()
+
+
+def _run_scene(ctx, sc, plain):
+    if plain:
+        nrs.debug_set("NRS_STEREO_NO_MFMA", "1")
+    return ctx.stereo_match_pattern(nrs.make_camera(0, SC.PRM), SC.BF_PATTERN, sc["left"], sc["right"], sc["xy"])
+
+
+@pytest.mark.parametrize("plain", [False, True], ids=["mfma", "plain"])
+@pytest.mark.parametrize("second_workgroup", [False, True], ids=["first_position", "second_workgroup"])
+def test_exact_ties_at_every_reduction_level(ctx, second_workgroup, plain):
+    """a lattice of positions that all score exactly 1.0: ties between a lane's registers and rows, lane groups, waves, workgroups (and
+    the plain form's tiles) in x and y; the first row-major position must win -- in the first workgroup, and in the second one in x and
+    y (tests/stereo_cases.py lattice_scene; the conditions are asserted in tests/test_stereo_cases_cpu.py)"""
+    sc = SC.lattice_scene(second_workgroup)
+    SC.lattice_holds(sc)
+    dev = _run_scene(ctx, sc, plain)
+    print(dev[3].tolist())
+    _same(dev, sc["oracle"])
+
+
+@pytest.mark.parametrize("plain", [False, True], ids=["mfma", "plain"])
+@pytest.mark.parametrize("name", list(SC.NEAR_TIES))
+def test_near_ties_are_decided_in_fp64(ctx, name, plain):
+    """two windows that differ in one grey level of one pixel: scores about 1e-7 apart (relative), which fp32 cannot order -- the later
+    and better one must replace the earlier one (in one workgroup's rows, and across two workgroups), the later and worse one must not"""
+    sc = SC.near_tie_scene(name)
+    print(name, "relative gap %.3e" % SC.near_tie_holds(sc))
+    _same(_run_scene(ctx, sc, plain), sc["oracle"])
 
 
 @pytest.mark.parametrize("plain", [False, True], ids=["mfma", "plain"])

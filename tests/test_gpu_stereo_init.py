@@ -7,6 +7,7 @@ import pytest
 import eval_oracle as E
 import nrs
 import nrs_synth as S
+import stereo_cases as SC
 import stereo_init_oracle as SO
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +35,38 @@ def test_dbscan3d_matches_the_sequential_oracle(ctx, case):
         assert np.array_equal(raw, o_raw), (case["name"], nc)
         assert np.array_equal(lab, o_lab), (case["name"], nc)
         assert np.array_equal(counts, o_counts), (case["name"], nc)
+
+
+LARGE = SC.LARGE_CLUSTER_CASES
+
+
+@pytest.mark.parametrize("case", LARGE, ids=[c["name"] for c in LARGE])
+def test_dbscan3d_past_one_chunk_and_one_trip(ctx, case):
+    """the carried count of the root compaction (roots in the second and third chunk of 1024), the second to fourth trip of the
+    lane-strided word loops (more than 4096 points) and the limit of 16384 points; tests/test_stereo_init_oracle_cpu.py asserts that every
+    case holds its property"""
+    exp = SC.cluster_expected(case["name"])
+    for nc in (True, False):
+        raw, lab, counts = ctx.dbscan3d(case["xyz"], case["eps"], case["min_points"], nc)
+        o_raw, o_lab, o_counts = exp[nc]
+        print(case["name"], nc, "counts", list(counts), "oracle", list(o_counts))
+        assert np.array_equal(raw, o_raw), (case["name"], nc)
+        assert np.array_equal(lab, o_lab), (case["name"], nc)
+        assert np.array_equal(counts, o_counts), (case["name"], nc)
+
+
+def test_dbscan3d_at_the_limit_twice_then_a_small_set_in_the_same_buffer(ctx):
+    full = SC.cluster_case("full16384")
+    assert len(full["xyz"]) == nrs.DBSCAN_MAX_POINTS
+    a = ctx.dbscan3d(full["xyz"], full["eps"], full["min_points"], True)
+    b = ctx.dbscan3d(full["xyz"], full["eps"], full["min_points"], True)
+    for x, y, o in zip(a, b, SC.cluster_expected("full16384")[True]):
+        assert x.tobytes() == y.tobytes() and np.array_equal(x, o)
+    small = next(c for c in CLUSTER_CASES if c["name"] == "blobs63")
+    for nc in (True, False):
+        r = ctx.dbscan3d(small["xyz"], small["eps"], small["min_points"], nc)
+        for x, o in zip(r, SO.dbscan3d(small["xyz"], small["eps"], small["min_points"], nc)):
+            assert np.array_equal(x, o), nc
 
 
 def test_dbscan3d_refusals(ctx):
@@ -148,3 +181,50 @@ def test_init_stereo_refusals(ctx, scene):
         ctx.init_stereo(cam, np.zeros((24, 40), np.uint8), np.zeros((24, 40), np.uint8), scene["xy"])
     assert e.value.code == -1
     _same(_run(ctx, scene), scene["oracle"])                           # the context still works
+
+
+# ---- three chunks of keypoints: the carried counts of k_si_gate (over the keypoints) and k_si_select (over the gated points), rows of the
+# clustering wider than the words in use.  tests/test_stereo_cases_cpu.py asserts the scene's conditions without a device too
+@pytest.fixture(scope="module")
+def big():
+    p = SC.init_scene_three_chunks()
+    SC.init_three_chunks_holds(p)                                      # before the device is asked
+    return p
+
+
+def _run_big(ctx, p, nc=1):
+    return ctx.init_stereo(nrs.make_camera(0, PRM), p["left"], p["right"], p["xy"], noise_competes=nc, **p["opts"])
+
+
+@pytest.mark.parametrize("nc", [1, 0], ids=["noise_competes", "noise_apart"])
+def test_init_stereo_with_three_chunks_of_keypoints(ctx, big, nc):
+    o = big["oracle"][nc]
+    print({k: o[k] for k in FIELDS}, "codes", np.bincount(o["code"], minlength=4))
+    _same(_run_big(ctx, big, nc), o)
+
+
+def test_init_stereo_three_chunks_plain_form_gives_identical_bits(ctx, big):
+    a = _run_big(ctx, big)
+    nrs.debug_set("NRS_STEREO_NO_MFMA", "1")
+    try:
+        b = _run_big(ctx, big)
+    finally:
+        nrs.debug_set("NRS_STEREO_NO_MFMA", None)
+    _same(b, big["oracle"][1])
+    for k in ARRAYS + ("xyz", "selected_xyz"):
+        assert a[k].tobytes() == b[k].tobytes(), k
+
+
+def test_init_stereo_three_chunks_on_the_resident_pair_and_the_matcher_alone(ctx, big):
+    cam = nrs.make_camera(0, PRM)
+    dev = nrs.Context()
+    try:
+        out = dev.front_process_stereo(big["left"], big["right"], outputs=("gray", "gray_right"))
+        assert np.array_equal(out["gray"], big["left"]) and np.array_equal(out["gray_right"], big["right"])
+        for nc in (1, 0):
+            _same(dev.init_stereo_front(cam, big["xy"], noise_competes=nc, **big["opts"]), big["oracle"][nc])
+    finally:
+        dev.close()
+    xyz, st, _, _ = ctx.stereo_match_pattern(cam, BF, big["left"], big["right"], big["xy"])
+    r = _run_big(ctx, big)
+    assert np.array_equal(st, r["match_status"]) and xyz.tobytes() == r["xyz"].tobytes()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import nrs_synth as S
+import stereo_cases as SC
 import stereo_init_oracle as SO
 
 F32 = np.float32
@@ -26,6 +27,33 @@ def test_sequential_equals_fixed_point(case):
         b = SO.dbscan3d_fixed_point(case["xyz"], case["eps"], case["min_points"], nc)
         for x, y, name in zip(a, b, ("raw_label", "label", "counts")):
             assert np.array_equal(x, y), (case["name"], nc, name)
+
+
+LARGE = SC.LARGE_CLUSTER_CASES
+
+
+@pytest.mark.parametrize("case", LARGE, ids=[c["name"] for c in LARGE])
+def test_the_large_cases_hold_what_they_are_made_for(case):
+    """roots in every compaction chunk, no core point in the first two chunks, relations that exist only through points behind the first
+    trip of the word loops, the limit of 16384 points: each case's `holds` (nrs_synth.make_large_cluster_cases) on the oracle's output"""
+    exp = SC.cluster_expected(case["name"], check=True)
+    raw, lab, counts = exp[True]
+    print(case["name"], len(raw), "points, counts", list(counts))
+    assert len(raw) == len(case["xyz"]) and counts[0] == raw.max() + 1
+    if len(raw) <= SC.BRUTE_FORCE_MAX_POINTS:
+        # the brute-force closure sweeps once per hop of a component's longest shortest path (thousands on the long chain) and is a
+        # Python loop over the core points: it is held to the sequential oracle on the cases of at most BRUTE_FORCE_MAX_POINTS points
+        for nc in (True, False):
+            b = SO.dbscan3d_fixed_point(case["xyz"], case["eps"], case["min_points"], nc)
+            for x, y, name in zip(exp[nc], b, ("raw_label", "label", "counts")):
+                assert np.array_equal(x, y), (case["name"], nc, name)
+
+
+def test_large_case_names_and_sizes():
+    sizes = {c["name"]: len(c["xyz"]) for c in LARGE}
+    assert sizes == {"roots_in_three_chunks": 2100, "first_root_late": 2100, "second_trip4097": 4097, "second_trip4160": 4160,
+                     "chain4200_shuffled": 4200, "full16384": 16384, "full16321": 16321}
+    assert not {c["name"] for c in CASES} & set(sizes)
 
 
 def _case(name):
