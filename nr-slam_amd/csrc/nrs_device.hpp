@@ -21,6 +21,16 @@ struct Pose {          // T_camera_world
     double t[3];
 };
 
+// index i of an axis of n samples extended by reflection about its end samples (OpenCV's BORDER_REFLECT_101): the pyramid's padding
+// (nrs_klt.hip), CLAHE's tiles and the Gaussian's taps (nrs_front.hip)
+__host__ __device__ inline int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    const int p = 2 * (n - 1);
+    i %= p;
+    if (i < 0) i += p;
+    return i >= n ? p - i : i;
+}
+
 // ---- quaternion / SE(3), restating g2o SE3Quat on Eigen quaternions
 // (reference third_party/g2o/g2o/types/slam3d/se3quat.h:96-102,201-229,250-255)
 __host__ __device__ inline void quat_to_R(const double* q, double* R) {

@@ -21,6 +21,7 @@
 #include <new>
 #include <vector>
 #include "nrs_ctx.hpp"
+#include "nrs_device.hpp"
 
 namespace nrs {
 
@@ -53,15 +54,8 @@ struct FrontState {
     GaussW gw;
 };
 
-__device__ __host__ inline int front_reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i >= n ? p - i : i;
-}
-
-__global__ void k_front_gray(const uint8_t* __restrict__ src, int stride, int ch, int w, int h, uint8_t* __restrict__ dst) {
+// ---- the three stages both eyes take: one body each, entered by the single-frame kernel and by the pair kernel -----------------------
+__device__ inline void front_gray_px(const uint8_t* __restrict__ src, int stride, int ch, int w, uint8_t* __restrict__ dst) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
     const uint8_t* s = src + (size_t)y * stride + (size_t)x * ch;
@@ -75,10 +69,9 @@ __device__ inline uint8_t front_sat_rint(float v) {
     return (uint8_t)min(255, max(0, i));
 }
 
-// ---- CLAHE ------------------------------------------------------------------------------------------------------------------
-// grid = (tiles_x, tiles_y); the tile is cut from the image extended to (tw tiles_x) x (th tiles_y) by reflect-101
-__global__ __launch_bounds__(256) void k_front_clahe_lut(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int clip,
-                                                         uint8_t* __restrict__ lut) {
+// CLAHE, one workgroup of 256 per tile, grid.x x grid.y = tiles_x x tiles_y; the tile is cut from the image extended to
+// (tw tiles_x) x (th tiles_y) by reflect-101
+__device__ inline void front_clahe_lut_tile(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int clip, uint8_t* __restrict__ lut) {
 #pragma clang fp contract(off)
     __shared__ int hist[256];
     __shared__ int s_excess;
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(256) void k_front_clahe_lut(const uint8_t* __restri
     const int area = tw * th;
     for (int i = tid; i < area; i += 256) {
         const int ly = i / tw, lx = i - ly * tw;
-        const int gx = front_reflect101(blockIdx.x * tw + lx, w), gy = front_reflect101(blockIdx.y * th + ly, h);
+        const int gx = reflect101(blockIdx.x * tw + lx, w), gy = reflect101(blockIdx.y * th + ly, h);
         atomicAdd(&hist[gray[(size_t)gy * w + gx]], 1);
     }
     __syncthreads();
@@ -115,8 +108,8 @@ __global__ __launch_bounds__(256) void k_front_clahe_lut(const uint8_t* __restri
     lut[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = front_sat_rint((float)hist[tid] * scale);
 }
 
-__global__ void k_front_clahe_apply(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int tiles_x, int tiles_y,
-                                    const uint8_t* __restrict__ lut, uint8_t* __restrict__ dst) {
+__device__ inline void front_clahe_blend_px(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int tiles_x, int tiles_y,
+                                            const uint8_t* __restrict__ lut, uint8_t* __restrict__ dst) {
 #pragma clang fp contract(off)
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
@@ -134,81 +127,32 @@ __global__ void k_front_clahe_apply(const uint8_t* __restrict__ gray, int w, int
     dst[(size_t)y * w + x] = front_sat_rint(res);
 }
 
-// ---- the pair forms (nrs_front_process_stereo): the three stages both eyes take, one launch each over both eyes.  blockIdx.z is the eye;
-// the statements are those of the single-frame kernels above, so an eye's bytes are the bytes of that image processed alone.  The LUT
-// stage is 2 x 64 workgroups of 1 KiB LDS each: with one workgroup per tile a single frame fills 64 of the 256 CUs, the pair 128, and the
-// LDS histogram atomics of the two eyes never meet (a workgroup owns its tile's 256 bins).
-struct EyesIn { const uint8_t* p[2]; };
-struct EyesOut { uint8_t* p[2]; };
-
-__global__ void k_front_gray_pair(EyesIn src, int stride, int ch, int w, int h, EyesOut dst) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= w) return;
-    const uint8_t* s = (blockIdx.z ? src.p[1] : src.p[0]) + (size_t)y * stride + (size_t)x * ch;
-    int v = s[0];
-    if (ch > 1) v = (s[0] * 9798 + s[1] * 19235 + s[2] * 3735 + (1 << 14)) >> 15;
-    (blockIdx.z ? dst.p[1] : dst.p[0])[(size_t)y * w + x] = (uint8_t)v;
+__global__ void k_front_gray(const uint8_t* __restrict__ src, int stride, int ch, int w, int h, uint8_t* __restrict__ dst) {
+    front_gray_px(src, stride, ch, w, dst);
+}
+__global__ __launch_bounds__(256) void k_front_clahe_lut(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int clip,
+                                                         uint8_t* __restrict__ lut) {
+    front_clahe_lut_tile(gray, w, h, tw, th, clip, lut);
+}
+__global__ void k_front_clahe_apply(const uint8_t* __restrict__ gray, int w, int h, int tw, int th, int tiles_x, int tiles_y,
+                                    const uint8_t* __restrict__ lut, uint8_t* __restrict__ dst) {
+    front_clahe_blend_px(gray, w, h, tw, th, tiles_x, tiles_y, lut, dst);
 }
 
-// grid = (tiles_x, tiles_y, 2)
-__global__ __launch_bounds__(256) void k_front_clahe_lut_pair(EyesIn grays, int w, int h, int tw, int th, int clip, EyesOut luts) {
-#pragma clang fp contract(off)
-    __shared__ int hist[256];
-    __shared__ int s_excess;
-    const uint8_t* __restrict__ gray = blockIdx.z ? grays.p[1] : grays.p[0];
-    uint8_t* __restrict__ lut = blockIdx.z ? luts.p[1] : luts.p[0];
-    const int tid = threadIdx.x;
-    hist[tid] = 0;
-    if (tid == 0) s_excess = 0;
-    __syncthreads();
-    const int area = tw * th;
-    for (int i = tid; i < area; i += 256) {
-        const int ly = i / tw, lx = i - ly * tw;
-        const int gx = front_reflect101(blockIdx.x * tw + lx, w), gy = front_reflect101(blockIdx.y * th + ly, h);
-        atomicAdd(&hist[gray[(size_t)gy * w + gx]], 1);
-    }
-    __syncthreads();
-    int v = hist[tid];
-    if (v > clip) { atomicAdd(&s_excess, v - clip); v = clip; }
-    __syncthreads();
-    const int excess = s_excess, batch = excess / 256;
-    int residual = excess - batch * 256;
-    v += batch;
-    if (residual > 0) {
-        const int step = max(256 / residual, 1);
-        if (tid % step == 0 && tid / step < residual) v += 1;
-    }
-    hist[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int t = tid >= off ? hist[tid - off] : 0;
-        __syncthreads();
-        hist[tid] += t;
-        __syncthreads();
-    }
-    const float scale = 255.f / (float)area;
-    lut[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = front_sat_rint((float)hist[tid] * scale);
-}
+// The pair forms (nrs_front_process_stereo): one launch per stage over both eyes, blockIdx.z is the eye, so an eye's bytes are the bytes of
+// that image processed alone.  The LUT stage is 2 x 64 workgroups of 1 KiB LDS each: with one workgroup per tile a single frame fills 64 of
+// the 256 CUs, the pair 128, and the LDS histogram atomics of the two eyes never meet (a workgroup owns its tile's 256 bins).
+struct Eyes {
+    uint8_t* p[2];
+    __device__ uint8_t* mine() const { return blockIdx.z ? p[1] : p[0]; }
+};
 
-__global__ void k_front_clahe_apply_pair(EyesIn grays, int w, int h, int tw, int th, int tiles_x, int tiles_y, EyesIn luts, EyesOut dsts) {
-#pragma clang fp contract(off)
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= w) return;
-    const uint8_t* __restrict__ gray = blockIdx.z ? grays.p[1] : grays.p[0];
-    const uint8_t* __restrict__ lut = blockIdx.z ? luts.p[1] : luts.p[0];
-    uint8_t* __restrict__ dst = blockIdx.z ? dsts.p[1] : dsts.p[0];
-    const float inv_tw = 1.f / (float)tw, inv_th = 1.f / (float)th;
-    const float txf = (float)x * inv_tw - 0.5f, tyf = (float)y * inv_th - 0.5f;
-    int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
-    const float xa = txf - (float)tx1, ya = tyf - (float)ty1;
-    const float xa1 = 1.f - xa, ya1 = 1.f - ya;
-    const int tx2 = min(tx1 + 1, tiles_x - 1), ty2 = min(ty1 + 1, tiles_y - 1);
-    tx1 = max(tx1, 0); ty1 = max(ty1, 0);
-    const int v = gray[(size_t)y * w + x];
-    const float l11 = (float)lut[((size_t)ty1 * tiles_x + tx1) * 256 + v], l12 = (float)lut[((size_t)ty1 * tiles_x + tx2) * 256 + v];
-    const float l21 = (float)lut[((size_t)ty2 * tiles_x + tx1) * 256 + v], l22 = (float)lut[((size_t)ty2 * tiles_x + tx2) * 256 + v];
-    const float res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya;
-    dst[(size_t)y * w + x] = front_sat_rint(res);
+__global__ void k_front_gray_pair(Eyes src, int stride, int ch, int w, int h, Eyes dst) { front_gray_px(src.mine(), stride, ch, w, dst.mine()); }
+__global__ __launch_bounds__(256) void k_front_clahe_lut_pair(Eyes grays, int w, int h, int tw, int th, int clip, Eyes luts) {
+    front_clahe_lut_tile(grays.mine(), w, h, tw, th, clip, luts.mine());
+}
+__global__ void k_front_clahe_apply_pair(Eyes grays, int w, int h, int tw, int th, int tiles_x, int tiles_y, Eyes luts, Eyes dsts) {
+    front_clahe_blend_px(grays.mine(), w, h, tw, th, tiles_x, tiles_y, luts.mine(), dsts.mine());
 }
 
 // ---- morphology -------------------------------------------------------------------------------------------------------------
@@ -278,7 +222,7 @@ __global__ void k_front_gauss_h(const uint8_t* __restrict__ src, int w, int h, G
     const uint8_t* row = src + (size_t)y * w;
     float acc = 0.f;
 #pragma unroll
-    for (int i = 0; i < 11; ++i) acc = acc + g.w[i] * (float)row[front_reflect101(x + i - 5, w)];
+    for (int i = 0; i < 11; ++i) acc = acc + g.w[i] * (float)row[reflect101(x + i - 5, w)];
     dst[(size_t)y * w + x] = acc;
 }
 
@@ -288,7 +232,7 @@ __global__ void k_front_gauss_v(const float* __restrict__ src, int w, int h, Gau
     if (x >= w) return;
     float acc = 0.f;
 #pragma unroll
-    for (int i = 0; i < 11; ++i) acc = acc + g.w[i] * src[(size_t)front_reflect101(y + i - 5, h) * w + x];
+    for (int i = 0; i < 11; ++i) acc = acc + g.w[i] * src[(size_t)reflect101(y + i - 5, h) * w + x];
     dst[(size_t)y * w + x] = front_sat_rint(acc);
 }
 
@@ -352,21 +296,27 @@ static FrontState* front_default(nrs_ctx* c) {
     return c->front;
 }
 
-int front_resident(nrs_ctx* c, const char* who, int w, int h, int image, int use_global_mask, const uint8_t** img, const uint8_t** mask) {
+// what is resident (a frame, or -- pair -- both eyes), its size and the image selector
+static int front_resident_check(nrs_ctx* c, const char* who, bool pair, int w, int h, int image) {
     const FrontState* f = c->front;
-    if (!f || !f->valid) return c->fail(NRS_ERR_STATE, "%s: no frame has been processed (nrs_front_process)", who);
-    if (w != f->w || h != f->h) return c->fail(NRS_ERR_STATE, "%s: the resident frame is %d x %d, not %d x %d", who, f->w, f->h, w, h);
+    if (!f || !f->valid || (pair && !f->valid_right))
+        return c->fail(NRS_ERR_STATE, "%s: no %s has been processed (nrs_front_process%s)", who, pair ? "stereo pair" : "frame", pair ? "_stereo" : "");
+    if (w != f->w || h != f->h) return c->fail(NRS_ERR_STATE, "%s: the resident %s is %d x %d, not %d x %d", who, pair ? "pair" : "frame", f->w, f->h, w, h);
     if (image != NRS_FRONT_IMAGE_GRAY && image != NRS_FRONT_IMAGE_CLAHE) return c->fail(NRS_ERR_INVALID, "%s: image selector must be GRAY or CLAHE", who);
+    return NRS_OK;
+}
+
+int front_resident(nrs_ctx* c, const char* who, int w, int h, int image, int use_global_mask, const uint8_t** img, const uint8_t** mask) {
+    NRS_TRY(front_resident_check(c, who, false, w, h, image));
+    const FrontState* f = c->front;
     *img = image == NRS_FRONT_IMAGE_GRAY ? f->gray.as<uint8_t>() : f->clahe.as<uint8_t>();
     *mask = use_global_mask ? f->global.as<uint8_t>() : nullptr;
     return NRS_OK;
 }
 
 int front_resident_pair(nrs_ctx* c, const char* who, int w, int h, int image, const uint8_t** left, const uint8_t** right) {
+    NRS_TRY(front_resident_check(c, who, true, w, h, image));
     const FrontState* f = c->front;
-    if (!f || !f->valid || !f->valid_right) return c->fail(NRS_ERR_STATE, "%s: no stereo pair has been processed (nrs_front_process_stereo)", who);
-    if (w != f->w || h != f->h) return c->fail(NRS_ERR_STATE, "%s: the resident pair is %d x %d, not %d x %d", who, f->w, f->h, w, h);
-    if (image != NRS_FRONT_IMAGE_GRAY && image != NRS_FRONT_IMAGE_CLAHE) return c->fail(NRS_ERR_INVALID, "%s: image selector must be GRAY or CLAHE", who);
     *left = image == NRS_FRONT_IMAGE_GRAY ? f->gray.as<uint8_t>() : f->clahe.as<uint8_t>();
     *right = image == NRS_FRONT_IMAGE_GRAY ? f->gray_r.as<uint8_t>() : f->clahe_r.as<uint8_t>();
     return NRS_OK;
@@ -490,26 +440,17 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
     if (w % f->tiles_x != 0 || h % f->tiles_y != 0) { pw = w + f->tiles_x - w % f->tiles_x; ph = h + f->tiles_y - h % f->tiles_y; }
     const int tw = pw / f->tiles_x, th = ph / f->tiles_y;
     const int clip = std::max(1, (int)(f->clip * (float)(tw * th) / 256.f));
+    const Eyes raws{{f->raw.as<uint8_t>(), f->raw_r.as<uint8_t>()}}, grays{{gray, f->gray_r.as<uint8_t>()}};
+    const Eyes luts{{f->lut.as<uint8_t>(), f->lut_r.as<uint8_t>()}}, clahes{{f->clahe.as<uint8_t>(), f->clahe_r.as<uint8_t>()}};
     if (right && !c->dbg.is_set(SW_FRONT_PER_EYE)) {               // the pair: one launch per shared stage, the eye in grid.z
-        const EyesIn raws{{f->raw.as<uint8_t>(), f->raw_r.as<uint8_t>()}}, grays{{gray, f->gray_r.as<uint8_t>()}};
-        const EyesIn luts{{f->lut.as<uint8_t>(), f->lut_r.as<uint8_t>()}};
-        const EyesOut grays_o{{gray, f->gray_r.as<uint8_t>()}}, luts_o{{f->lut.as<uint8_t>(), f->lut_r.as<uint8_t>()}};
-        const EyesOut clahes_o{{f->clahe.as<uint8_t>(), f->clahe_r.as<uint8_t>()}};
-        hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, raws, (int)row, channels, w, h, grays_o);
-        hipLaunchKernelGGL(k_front_clahe_lut_pair, dim3(f->tiles_x, f->tiles_y, 2), blk, 0, c->stream, grays, w, h, tw, th, clip, luts_o);
-        hipLaunchKernelGGL(k_front_clahe_apply_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, grays, w, h, tw, th, f->tiles_x, f->tiles_y, luts,
-                           clahes_o);
+        hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, raws, (int)row, channels, w, h, grays);
+        hipLaunchKernelGGL(k_front_clahe_lut_pair, dim3(f->tiles_x, f->tiles_y, 2), blk, 0, c->stream, grays, w, h, tw, th, clip, luts);
+        hipLaunchKernelGGL(k_front_clahe_apply_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, grays, w, h, tw, th, f->tiles_x, f->tiles_y, luts, clahes);
     } else {
-        hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, f->raw.as<uint8_t>(), (int)row, channels, w, h, gray);
-        hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, gray, w, h, tw, th, clip, f->lut.as<uint8_t>());
-        hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, gray, w, h, tw, th, f->tiles_x, f->tiles_y, f->lut.as<uint8_t>(),
-                           f->clahe.as<uint8_t>());
-        if (right) {                                               // NRS_FRONT_PER_EYE: the right eye through the same three kernels
-            uint8_t* gray_r = f->gray_r.as<uint8_t>();
-            hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, f->raw_r.as<uint8_t>(), (int)row, channels, w, h, gray_r);
-            hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, gray_r, w, h, tw, th, clip, f->lut_r.as<uint8_t>());
-            hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, gray_r, w, h, tw, th, f->tiles_x, f->tiles_y, f->lut_r.as<uint8_t>(),
-                               f->clahe_r.as<uint8_t>());
+        for (int e = 0; e < (right ? 2 : 1); ++e) {                // a single frame, or NRS_FRONT_PER_EYE: the right eye through the same three kernels
+            hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, raws.p[e], (int)row, channels, w, h, grays.p[e]);
+            hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, grays.p[e], w, h, tw, th, clip, luts.p[e]);
+            hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, grays.p[e], w, h, tw, th, f->tiles_x, f->tiles_y, luts.p[e], clahes.p[e]);
         }
     }
     AndSrc all;

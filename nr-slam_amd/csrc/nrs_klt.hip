@@ -20,11 +20,12 @@
 #include <vector>
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
+#include "nrs_klt_host.hpp"
 #include "nrs_reuse_host.hpp"
 
 namespace nrs {
 
-constexpr int KW = 21, KA = KW * KW, KPAD = 21, KMAXL = 8;
+constexpr int KPAD = 21, KMAXL = 8;
 constexpr int W_BITS = 14;
 
 struct PyrLevel {
@@ -38,32 +39,83 @@ struct Pyr {
     int n_levels;
 };
 
+// What a kernel is handed of a set of templates: entry e, level l is item e * levels + l of every array (sizes: nrs_klt_host.hpp)
+struct TemplateView {
+    short* I; short2* D; float* mean; uint8_t* valid;
+    int levels;
+};
+
+// A set of templates in HBM: the four arrays, `levels` levels an entry, room for `cap` entries, and one side array of side_bytes per
+// entry -- the tracker's reference points, or the archive's "has" bytes (side_zero: they read zero wherever the set has grown)
+struct TemplateSet {
+    DevBuf arr[KLT_ARRAYS], side;
+    int levels, cap = 0;
+    size_t side_bytes;
+    bool side_zero;
+    const char* what;                        // names the set in an error text
+    TemplateSet(int levels_, size_t side_bytes_, bool side_zero_, const char* what_) : levels(levels_), side_bytes(side_bytes_), side_zero(side_zero_), what(what_) {}
+    TemplateView view() const { return TemplateView{arr[0].as<short>(), arr[1].as<short2>(), arr[2].as<float>(), arr[3].as<uint8_t>(), levels}; }
+    void release(nrs_ctx* c) {
+        for (DevBuf& b : arr) c->release(b);
+        c->release(side);
+        cap = 0;
+    }
+    // Room for `want` entries, the first `keep` of them carried over.  All or nothing: after a failure the set is what it was, nothing
+    // new is left allocated and the context's error is set.  Waits for the stream once, behind the copies
+    int reserve(nrs_ctx* c, int want, int keep) {
+        if (want <= cap) return NRS_OK;
+        hipError_t he = hipSetDevice(c->device);                   // (an entry point may come here without having set it)
+        if (he != hipSuccess) return c->fail(NRS_ERR_HIP, "%s: hipSetDevice failed: %s", what, hipGetErrorString(he));
+        TemplateSet g(levels, side_bytes, side_zero, what);
+        g.cap = klt_grow_capacity(want);
+        int rc = NRS_OK;
+        for (int a = 0; a < KLT_ARRAYS && rc == NRS_OK; ++a) rc = c->ensure(g.arr[a], klt_entry_bytes(a, levels) * g.cap);
+        if (rc == NRS_OK) rc = c->ensure(g.side, side_bytes * g.cap);
+        if (rc != NRS_OK) { g.release(c); return rc; }             // nothing of a half-made set is kept
+        if (side_zero) {
+            he = hipMemsetAsync(g.side.p, 0, side_bytes * g.cap, c->stream);
+            if (he != hipSuccess) { g.release(c); return c->fail(NRS_ERR_HIP, "%s: clearing the grown buffers failed: %s", what, hipGetErrorString(he)); }
+        }
+        if (keep > 0) {
+            const size_t m = (size_t)keep;
+            for (int a = 0; a < KLT_ARRAYS && he == hipSuccess; ++a)
+                he = hipMemcpyAsync(g.arr[a].p, arr[a].p, klt_entry_bytes(a, levels) * m, hipMemcpyDeviceToDevice, c->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(g.side.p, side.p, side_bytes * m, hipMemcpyDeviceToDevice, c->stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+            if (he != hipSuccess) {                                // (the new buffers do not outlive a failed copy; the set stays as it was)
+                g.release(c);
+                return c->fail(NRS_ERR_HIP, "%s: copy to the grown buffers failed: %s", what, hipGetErrorString(he));
+            }
+        }
+        const int grown = g.cap;
+        release(c);
+        for (int a = 0; a < KLT_ARRAYS; ++a) arr[a] = g.arr[a];
+        side = g.side;
+        cap = grown;
+        return NRS_OK;
+    }
+};
+
 struct KltState {
     int win = KW, max_level = 4, max_iters = 10;
     float eps = 1e-4f, min_eig = 1e-4f;
-    int n = 0, cap = 0, levels = 5;          // levels = max_level + 1 slots per point
+    int n = 0;
     DevBuf pyr_buf, img_in, mask_in;
     Pyr pyr;
     int pyr_w = 0, pyr_h = 0;
-    DevBuf tI, tD, tMean, tValid, prev, pts, status, misc;
+    // the tracker's own templates, point-major: n of them, max_level + 1 levels a point; side array: the reference points (`prev`)
+    TemplateSet tmpl{5, KLT_XY_BYTES, false, "tracker templates"};
+    DevBuf pts, status, misc;
     // the archive: photometric information kept by a caller's key (the map point id) -- what the reference keeps in its Map per map
     // point (GetPhotometricInformation at keyframes, InsertPhotometricInformation when a point is reused: tracking.cc:383-391,457-460)
-    // -- in HBM, so that templates never travel to the host and back (nrs_klt_archive_templates / nrs_klt_insert_archived)
-    DevBuf aI, aD, aMean, aValid, a_idx;
-    int a_cap = 0, a_levels = 0;
+    // -- in HBM, so that templates never travel to the host and back (nrs_klt_archive_templates / nrs_klt_insert_archived).  Side array:
+    // the "has" byte per key, for the kernels that address the archive by key (nrs_point_reuse); a_has is its host copy
+    TemplateSet arch{0, KLT_HAS_BYTES, true, "template archive"};
     std::vector<uint8_t> a_has;
-    // ... and the same "has" byte per key on the device, for the kernels that address the archive by key (nrs_point_reuse); the upload,
-    // scratch and packed result of that call
-    DevBuf aHas, reuse_in, reuse_ws, reuse_out;
+    // index lists of the device-to-device copies; the upload, scratch and packed result of nrs_point_reuse
+    DevBuf a_idx, reuse_in, reuse_ws, reuse_out;
+    float* prev() const { return tmpl.side.as<float>(); }
 };
-
-__device__ __host__ inline int reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i >= n ? p - i : i;
-}
 
 // level 0: caller image -> padded reflect-101 copy
 __global__ void k_pyr_copy(const uint8_t* __restrict__ src, int sstride, PyrLevel L) {
@@ -155,15 +207,14 @@ __device__ inline float seq_sum_441(const float* v) {          // row-major sequ
 // ---------------------------------------------------------------------------------------------
 // a21: SetReferenceImage, one wave per (point, level)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_klt_set_reference(Pyr pyr, int n, int levels, const float* __restrict__ pts,
-                                                           const uint8_t* __restrict__ mask, int mw, int mh,
-                                                           short* tI, short2* tD, float* tMean, uint8_t* tValid) {
+__global__ __launch_bounds__(64) void k_klt_set_reference(Pyr pyr, int n, TemplateView t, const float* __restrict__ pts,
+                                                           const uint8_t* __restrict__ mask, int mw, int mh) {
 #pragma clang fp contract(off)
     __shared__ float s_v[KA], s_v2[KA];
     const int lane = threadIdx.x;
-    const int i = blockIdx.x / levels, level = blockIdx.x % levels;
-    const size_t slot = (size_t)i * levels + level;
-    if (lane == 0) { tValid[slot] = 0; tMean[2 * slot] = -1.f; tMean[2 * slot + 1] = -1.f; }
+    const int i = blockIdx.x / t.levels, level = blockIdx.x % t.levels;
+    const size_t slot = (size_t)i * t.levels + level;
+    if (lane == 0) { t.valid[slot] = 0; t.mean[2 * slot] = -1.f; t.mean[2 * slot + 1] = -1.f; }
     if (level >= pyr.n_levels) return;
     const PyrLevel L = pyr.L[level];
     const float half = (KW - 1) * 0.5f;
@@ -177,8 +228,8 @@ __global__ __launch_bounds__(64) void k_klt_set_reference(Pyr pyr, int n, int le
     for (int p = lane; p < KA; p += 64) {
         int val, dx, dy;
         sample_px(L, ix, iy, p, w00, w01, w10, w11, val, dx, dy, true);
-        tI[slot * KA + p] = (short)val;
-        tD[slot * KA + p] = make_short2((short)dx, (short)dy);
+        t.I[slot * KA + p] = (short)val;
+        t.D[slot * KA + p] = make_short2((short)dx, (short)dy);
         s_v[p] = (float)val;
         s_v2[p] = (float)(val * val);
         if (mask) {                                              // LK:125-131 (out-of-image reads: not masked)
@@ -193,8 +244,8 @@ __global__ __launch_bounds__(64) void k_klt_set_reference(Pyr pyr, int n, int le
     if (lane == 0) r = seq_sum_441(s_v);
     if (lane == 1) r = seq_sum_441(s_v2);
     const float FLT_SCALE = 1.f / (1 << 20);
-    if (lane < 2) tMean[2 * slot + lane] = (r * FLT_SCALE) / (float)KA;
-    if (lane == 0) tValid[slot] = 1;
+    if (lane < 2) t.mean[2 * slot + lane] = (r * FLT_SCALE) / (float)KA;
+    if (lane == 0) t.valid[slot] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -202,13 +253,13 @@ __global__ __launch_bounds__(64) void k_klt_set_reference(Pyr pyr, int n, int le
 // ---------------------------------------------------------------------------------------------
 struct TrackArgs {
     Pyr pyr;
-    int n, levels, max_level, max_iters;
+    int n, max_level, max_iters;
     float eps, min_eig;
     int initial_flow;
     const float* prev;
     float* pts;            // in/out
     int* status;           // in/out
-    const short* tI; const short2* tD; const float* tMean; const uint8_t* tValid;
+    TemplateView t;        // read only
 };
 
 __device__ inline bool usable(int s) { return s == NRS_TRACKED_WITH_3D || s == NRS_TRACKED || s == NRS_JUST_TRIANGULATED; }
@@ -261,14 +312,14 @@ __device__ inline void klt_track_point(const TrackArgs& a, const Slot sl) {
             if (level == 0) st = NRS_OUT_IMAGE_BOUNDARIES;
             continue;
         }
-        const size_t slot = sl.base(i, a.levels) + level;
-        if (!sl.has(i) || !a.tValid[slot]) {
+        const size_t slot = sl.base(i, a.t.levels) + level;
+        if (!sl.has(i) || !a.t.valid[slot]) {
             if (level == 0) st = NRS_OUT_IMAGE_BOUNDARIES;
             continue;
         }
-        const float meanI = a.tMean[2 * slot], meanI2 = a.tMean[2 * slot + 1];
+        const float meanI = a.t.mean[2 * slot], meanI2 = a.t.mean[2 * slot + 1];
         __syncthreads();
-        for (int p = lane; p < KA; p += 64) { s_I[p] = a.tI[slot * KA + p]; s_D[p] = a.tD[slot * KA + p]; }
+        for (int p = lane; p < KA; p += 64) { s_I[p] = a.t.I[slot * KA + p]; s_D[p] = a.t.D[slot * KA + p]; }
         const float sx0 = nx, sy0 = ny;                           // startCoordinates
         nx -= half; ny -= half;
         float pdx = 0.f, pdy = 0.f;
@@ -368,7 +419,7 @@ __device__ inline int div32_rne(int v) {                         // saturate_cas
 }
 
 template <class Slot>
-__device__ inline void klt_ssim_point(const Pyr& pyr, int levels, float* pts, int* status, const short* tI, float min_ssim, float* ssim_out,
+__device__ inline void klt_ssim_point(const Pyr& pyr, const TemplateView& t, float* pts, int* status, float min_ssim, float* ssim_out,
                                       int* n_good, const Slot sl) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x, i = blockIdx.x;
@@ -386,7 +437,7 @@ __device__ inline void klt_ssim_point(const Pyr& pyr, int levels, float* pts, in
     }
     int w00, w01, w10, w11;
     bilinear_weights(nx - (float)ix, ny - (float)iy, w00, w01, w10, w11);
-    const size_t slot = sl.base(i, levels);
+    const size_t slot = sl.base(i, t.levels);
     int cur[7], ref[7], sc = 0, sr = 0;
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
@@ -396,7 +447,7 @@ __device__ inline void klt_ssim_point(const Pyr& pyr, int levels, float* pts, in
             int val, dx, dy;
             sample_px(L, ix, iy, p, w00, w01, w10, w11, val, dx, dy, false);
             cur[q] = min(255, max(0, div32_rne(val)));
-            const int rv = tI[slot * KA + p];
+            const int rv = t.I[slot * KA + p];
             ref[q] = rv >= 0 ? div32_rne(rv) : -div32_rne(-rv);
             sc += cur[q]; sr += ref[q];
         }
@@ -426,14 +477,13 @@ __device__ inline void klt_ssim_point(const Pyr& pyr, int levels, float* pts, in
     }
 }
 
-__global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, int levels, float* pts, int* status, const short* tI,
-                                                  const float* tMean, float min_ssim, float* ssim_out, int* n_good) {
-    klt_ssim_point(pyr, levels, pts, status, tI, min_ssim, ssim_out, n_good, SlotOwn());
+__global__ __launch_bounds__(64) void k_klt_ssim(Pyr pyr, int n, TemplateView t, float* pts, int* status, float min_ssim, float* ssim_out,
+                                                  int* n_good) {
+    klt_ssim_point(pyr, t, pts, status, min_ssim, ssim_out, n_good, SlotOwn());
 }
 // (a point that reaches the gate is still usable, so the track kernel found its key's entry: the gate reads no entry that is not there)
-__global__ __launch_bounds__(64) void k_klt_ssim_keyed(Pyr pyr, int levels, float* pts, int* status, const short* tI, float min_ssim, int* n_good,
-                                                        SlotKeyed sl) {
-    klt_ssim_point(pyr, levels, pts, status, tI, min_ssim, nullptr, n_good, sl);
+__global__ __launch_bounds__(64) void k_klt_ssim_keyed(Pyr pyr, TemplateView t, float* pts, int* status, float min_ssim, int* n_good, SlotKeyed sl) {
+    klt_ssim_point(pyr, t, pts, status, min_ssim, nullptr, n_good, sl);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -447,8 +497,10 @@ static KltState* klt(nrs_ctx* c) {
 void klt_free(nrs_ctx* c) {
     if (!c->klt) return;
     KltState* k = c->klt;
-    DevBuf* bufs[] = {&k->pyr_buf, &k->img_in, &k->mask_in, &k->tI, &k->tD, &k->tMean, &k->tValid, &k->prev, &k->pts, &k->status, &k->misc, &k->aI, &k->aD, &k->aMean, &k->aValid, &k->a_idx, &k->aHas, &k->reuse_in, &k->reuse_ws, &k->reuse_out};
+    DevBuf* bufs[] = {&k->pyr_buf, &k->img_in, &k->mask_in, &k->pts, &k->status, &k->misc, &k->a_idx, &k->reuse_in, &k->reuse_ws, &k->reuse_out};
     for (auto b : bufs) c->release(*b);
+    k->tmpl.release(c);
+    k->arch.release(c);
     delete k;
     c->klt = nullptr;
 }
@@ -492,37 +544,6 @@ static int build_pyramid(nrs_ctx* c, KltState* k, const uint8_t* img, int w, int
     return NRS_OK;
 }
 
-static int reserve_points(nrs_ctx* c, KltState* k, int n, bool keep) {
-    if (n <= k->cap) return NRS_OK;
-    const int cap = std::max(n + n / 2, 256);
-    const size_t L = (size_t)k->levels;
-    DevBuf nI, nD, nM, nV, nP;
-    {
-        int rc = c->ensure(nI, sizeof(short) * KA * L * cap);
-        if (rc == NRS_OK) rc = c->ensure(nD, sizeof(short2) * KA * L * cap);
-        if (rc == NRS_OK) rc = c->ensure(nM, sizeof(float) * 2 * L * cap);
-        if (rc == NRS_OK) rc = c->ensure(nV, L * cap);
-        if (rc == NRS_OK) rc = c->ensure(nP, sizeof(float) * 2 * cap);
-        if (rc != NRS_OK) {                                        // nothing of a half-made set is kept
-            c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nP);
-            return rc;
-        }
-    }
-    if (keep && k->n > 0) {
-        const size_t m = (size_t)k->n;
-        NRS_HIP(c, hipMemcpyAsync(nI.p, k->tI.p, sizeof(short) * KA * L * m, hipMemcpyDeviceToDevice, c->stream));
-        NRS_HIP(c, hipMemcpyAsync(nD.p, k->tD.p, sizeof(short2) * KA * L * m, hipMemcpyDeviceToDevice, c->stream));
-        NRS_HIP(c, hipMemcpyAsync(nM.p, k->tMean.p, sizeof(float) * 2 * L * m, hipMemcpyDeviceToDevice, c->stream));
-        NRS_HIP(c, hipMemcpyAsync(nV.p, k->tValid.p, L * m, hipMemcpyDeviceToDevice, c->stream));
-        NRS_HIP(c, hipMemcpyAsync(nP.p, k->prev.p, sizeof(float) * 2 * m, hipMemcpyDeviceToDevice, c->stream));
-        NRS_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    c->release(k->tI); c->release(k->tD); c->release(k->tMean); c->release(k->tValid); c->release(k->prev);
-    k->tI = nI; k->tD = nD; k->tMean = nM; k->tValid = nV; k->prev = nP;
-    k->cap = cap;
-    return NRS_OK;
-}
-
 }  // namespace nrs
 
 using namespace nrs;
@@ -534,13 +555,12 @@ extern "C" int nrs_klt_configure(nrs_ctx* c, const nrs_klt_config* cfg) {
     KltState* k = klt(c);
     if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
     if (k->n > 0 && cfg->max_level != k->max_level) return c->fail(NRS_ERR_STATE, "cannot change max_level while templates are stored (call nrs_klt_clear)");
-    if (cfg->max_level + 1 != k->levels && k->cap > 0) {
+    if (cfg->max_level + 1 != k->tmpl.levels && k->tmpl.cap > 0) {
         // the template buffers are sized cap x levels: another level count invalidates them (k->n == 0 here)
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        c->release(k->tI); c->release(k->tD); c->release(k->tMean); c->release(k->tValid); c->release(k->prev);
-        k->cap = 0;
+        k->tmpl.release(c);
     }
-    k->max_level = cfg->max_level; k->levels = cfg->max_level + 1;
+    k->max_level = cfg->max_level; k->tmpl.levels = cfg->max_level + 1;          // max_level + 1 slots per point
     k->max_iters = cfg->max_iters; k->eps = cfg->epsilon; k->min_eig = cfg->min_eig_threshold;
     return NRS_OK;
 }
@@ -561,10 +581,10 @@ static int klt_set_reference_impl(nrs_ctx* c, const uint8_t* img, int32_t w, int
     if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
     NRS_TRY(build_pyramid(c, k, img, w, h, stride, on_device));
     k->n = 0;
-    NRS_TRY(reserve_points(c, k, n, false));
+    NRS_TRY(k->tmpl.reserve(c, n, 0));
     k->n = n;
     if (n == 0) return NRS_OK;
-    NRS_HIP(c, hipMemcpyAsync(k->prev.p, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(k->prev(), xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream));
     const uint8_t* dmask = nullptr;
     if (mask && on_device) dmask = mask;
     else if (mask) {
@@ -572,9 +592,7 @@ static int klt_set_reference_impl(nrs_ctx* c, const uint8_t* img, int32_t w, int
         NRS_HIP(c, hipMemcpyAsync(k->mask_in.p, mask, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
         dmask = k->mask_in.as<uint8_t>();
     }
-    hipLaunchKernelGGL(k_klt_set_reference, dim3(n * k->levels), dim3(64), 0, c->stream, k->pyr, n, k->levels,
-                       k->prev.as<float>(), dmask, w, h, k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(),
-                       k->tValid.as<uint8_t>());
+    hipLaunchKernelGGL(k_klt_set_reference, dim3(n * k->tmpl.levels), dim3(64), 0, c->stream, k->pyr, n, k->tmpl.view(), k->prev(), dmask, w, h);
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     return NRS_OK;
@@ -613,14 +631,13 @@ static int klt_track_impl(nrs_ctx* c, const uint8_t* img, int32_t w, int32_t h, 
     NRS_HIP(c, hipMemcpyAsync(k->status.p, status, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipMemsetAsync(k->misc.p, 0, sizeof(int) * 4, c->stream));
     TrackArgs a;
-    a.pyr = k->pyr; a.n = n; a.levels = k->levels; a.max_level = k->max_level; a.max_iters = k->max_iters;
+    a.pyr = k->pyr; a.n = n; a.max_level = k->max_level; a.max_iters = k->max_iters;
     a.eps = k->eps; a.min_eig = k->min_eig; a.initial_flow = use_initial_flow ? 1 : 0;
-    a.prev = k->prev.as<float>(); a.pts = k->pts.as<float>(); a.status = k->status.as<int>();
-    a.tI = k->tI.as<short>(); a.tD = k->tD.as<short2>(); a.tMean = k->tMean.as<float>(); a.tValid = k->tValid.as<uint8_t>();
+    a.prev = k->prev(); a.pts = k->pts.as<float>(); a.status = k->status.as<int>();
+    a.t = k->tmpl.view();
     hipLaunchKernelGGL(k_klt_track, dim3(n), dim3(64), 0, c->stream, a);
     float* d_ssim = reinterpret_cast<float*>(k->misc.as<char>() + sizeof(int) * 4);
-    hipLaunchKernelGGL(k_klt_ssim, dim3(n), dim3(64), 0, c->stream, k->pyr, n, k->levels, a.pts, a.status, a.tI, a.tMean,
-                       min_ssim, ssim ? d_ssim : nullptr, k->misc.as<int>());
+    hipLaunchKernelGGL(k_klt_ssim, dim3(n), dim3(64), 0, c->stream, k->pyr, n, a.t, a.pts, a.status, min_ssim, ssim ? d_ssim : nullptr, k->misc.as<int>());
     NRS_HIP(c, hipGetLastError());
     int good = 0;
     NRS_HIP(c, hipMemcpyAsync(xy, k->pts.p, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, c->stream));
@@ -665,36 +682,44 @@ extern "C" int nrs_stereo_match_lk_front(nrs_ctx* c, nrs_ctx* cf, const nrs_came
     return nrs_stereo_from_tracks(cam, bf, n, xy, right_xy, track_status, xyz, status);
 }
 
+// `count` templates from slot `first` on, between the tracker's set and the caller's arrays (to_device: into the set).  host: the reference
+// points, then the four arrays in the set's order; the callers have checked them and the range
+static int klt_transfer(nrs_ctx* c, const TemplateSet& t, int first, int count, bool to_device, void* const host[1 + KLT_ARRAYS]) {
+    for (int a = -1; a < KLT_ARRAYS; ++a) {
+        const size_t per = a < 0 ? t.side_bytes : klt_entry_bytes(a, t.levels);
+        char* dev = (a < 0 ? t.side : t.arr[a]).as<char>() + per * (size_t)first;
+        if (to_device) NRS_HIP(c, hipMemcpy(dev, host[a + 1], per * (size_t)count, hipMemcpyHostToDevice));
+        else NRS_HIP(c, hipMemcpy(host[a + 1], dev, per * (size_t)count, hipMemcpyDeviceToHost));
+    }
+    return NRS_OK;
+}
+
+// ... appended behind the stored ones (the set grows as needed)
+static int klt_append(nrs_ctx* c, int count, const float* xy, const int16_t* gray, const int16_t* grad, const float* mean, const uint8_t* valid) {
+    KltState* k = klt(c);
+    if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
+    NRS_TRY(k->tmpl.reserve(c, k->n + count, k->n));
+    void* const host[] = {const_cast<float*>(xy), const_cast<int16_t*>(gray), const_cast<int16_t*>(grad), const_cast<float*>(mean), const_cast<uint8_t*>(valid)};
+    NRS_TRY(klt_transfer(c, k->tmpl, k->n, count, true, host));
+    k->n += count;
+    return NRS_OK;
+}
+
 extern "C" int nrs_klt_get_template(nrs_ctx* c, int32_t idx, float xy[2], int16_t* gray, int16_t* grad, float* mean,
                                     uint8_t* valid) {
     if (!c) return NRS_ERR_INVALID;
     KltState* k = c->klt;
     if (!k || idx < 0 || idx >= k->n) return c->fail(NRS_ERR_INVALID, "template index out of range");
     if (!xy || !gray || !grad || !mean || !valid) return c->fail(NRS_ERR_INVALID, "null output");
-    const size_t L = (size_t)k->levels, s = (size_t)idx * L;
-    NRS_HIP(c, hipMemcpy(xy, k->prev.as<float>() + 2 * idx, sizeof(float) * 2, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(gray, k->tI.as<short>() + s * KA, sizeof(short) * KA * L, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(grad, k->tD.as<short2>() + s * KA, sizeof(short2) * KA * L, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(mean, k->tMean.as<float>() + 2 * s, sizeof(float) * 2 * L, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(valid, k->tValid.as<uint8_t>() + s, L, hipMemcpyDeviceToHost));
-    return NRS_OK;
+    void* const host[] = {xy, gray, grad, mean, valid};
+    return klt_transfer(c, k->tmpl, idx, 1, false, host);
 }
 
 extern "C" int nrs_klt_insert_template(nrs_ctx* c, const float xy[2], const int16_t* gray, const int16_t* grad,
                                        const float* mean, const uint8_t* valid) {
     if (!c) return NRS_ERR_INVALID;
     if (!xy || !gray || !grad || !mean || !valid) return c->fail(NRS_ERR_INVALID, "null input");
-    KltState* k = klt(c);
-    if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
-    NRS_TRY(reserve_points(c, k, k->n + 1, true));
-    const size_t L = (size_t)k->levels, s = (size_t)k->n * L;
-    NRS_HIP(c, hipMemcpy(k->prev.as<float>() + 2 * k->n, xy, sizeof(float) * 2, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tI.as<short>() + s * KA, gray, sizeof(short) * KA * L, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tD.as<short2>() + s * KA, grad, sizeof(short2) * KA * L, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tMean.as<float>() + 2 * s, mean, sizeof(float) * 2 * L, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tValid.as<uint8_t>() + s, valid, L, hipMemcpyHostToDevice));
-    k->n += 1;
-    return NRS_OK;
+    return klt_append(c, 1, xy, gray, grad, mean, valid);
 }
 
 extern "C" int nrs_klt_get_templates(nrs_ctx* c, int32_t first, int32_t count, float* xy, int16_t* gray, int16_t* grad,
@@ -704,13 +729,8 @@ extern "C" int nrs_klt_get_templates(nrs_ctx* c, int32_t first, int32_t count, f
     if (!k || first < 0 || count < 0 || first + count > k->n) return c->fail(NRS_ERR_INVALID, "template range out of bounds");
     if (count == 0) return NRS_OK;
     if (!xy || !gray || !grad || !mean || !valid) return c->fail(NRS_ERR_INVALID, "null output");
-    const size_t L = (size_t)k->levels, s = (size_t)first * L, n = (size_t)count;
-    NRS_HIP(c, hipMemcpy(xy, k->prev.as<float>() + 2 * first, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(gray, k->tI.as<short>() + s * KA, sizeof(short) * KA * L * n, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(grad, k->tD.as<short2>() + s * KA, sizeof(short2) * KA * L * n, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(mean, k->tMean.as<float>() + 2 * s, sizeof(float) * 2 * L * n, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(valid, k->tValid.as<uint8_t>() + s, L * n, hipMemcpyDeviceToHost));
-    return NRS_OK;
+    void* const host[] = {xy, gray, grad, mean, valid};
+    return klt_transfer(c, k->tmpl, first, count, false, host);
 }
 
 extern "C" int nrs_klt_insert_templates(nrs_ctx* c, int32_t count, const float* xy, const int16_t* gray,
@@ -719,111 +739,58 @@ extern "C" int nrs_klt_insert_templates(nrs_ctx* c, int32_t count, const float* 
     if (count < 0) return c->fail(NRS_ERR_INVALID, "count < 0");
     if (count == 0) return NRS_OK;
     if (!xy || !gray || !grad || !mean || !valid) return c->fail(NRS_ERR_INVALID, "null input");
-    KltState* k = klt(c);
-    if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
-    NRS_TRY(reserve_points(c, k, k->n + count, true));
-    const size_t L = (size_t)k->levels, s = (size_t)k->n * L, n = (size_t)count;
-    NRS_HIP(c, hipMemcpy(k->prev.as<float>() + 2 * k->n, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tI.as<short>() + s * KA, gray, sizeof(short) * KA * L * n, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tD.as<short2>() + s * KA, grad, sizeof(short2) * KA * L * n, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tMean.as<float>() + 2 * s, mean, sizeof(float) * 2 * L * n, hipMemcpyHostToDevice));
-    NRS_HIP(c, hipMemcpy(k->tValid.as<uint8_t>() + s, valid, L * n, hipMemcpyHostToDevice));
-    k->n += count;
-    return NRS_OK;
+    return klt_append(c, count, xy, gray, grad, mean, valid);
 }
 
-
 // ---- the template archive (device to device) ----------------------------------------------------------------------------------
-// one workgroup per template: `lv` levels of entry src_idx[i] (src_levels levels an entry) into entry dst_idx[i] (dst_levels);
-// d_has (nullable): the destination's per-entry "has" byte, set
-__global__ __launch_bounds__(256) void k_klt_copy_templates(int n, const int* __restrict__ src_idx, const int* __restrict__ dst_idx, int lv, int src_levels,
-                                                            int dst_levels, const short* __restrict__ sI, const short2* __restrict__ sD, const float* __restrict__ sM,
-                                                            const uint8_t* __restrict__ sV, short* dI, short2* dD, float* dM, uint8_t* dV, uint8_t* d_has) {
+// `lv` levels of entry se of s into entry de of d, by one workgroup of 256 threads.  (The source arrays pass through __restrict__
+// parameters: a view's members cannot carry the promise, and without it the loops' loads are not batched ahead of the stores.)
+__device__ inline void copy_levels(const short* __restrict__ sI, const short2* __restrict__ sD, const float* __restrict__ sM, const uint8_t* __restrict__ sV,
+                                   size_t so, const TemplateView& d, size_t d_o, int lv) {
+    for (int e = threadIdx.x; e < lv * KA; e += 256) { d.I[d_o * KA + e] = sI[so * KA + e]; d.D[d_o * KA + e] = sD[so * KA + e]; }
+    for (int e = threadIdx.x; e < 2 * lv; e += 256) d.mean[2 * d_o + e] = sM[2 * so + e];
+    for (int e = threadIdx.x; e < lv; e += 256) d.valid[d_o + e] = sV[so + e];
+}
+__device__ inline void copy_template(const TemplateView& s, int se, const TemplateView& d, int de, int lv) {
+    copy_levels(s.I, s.D, s.mean, s.valid, (size_t)se * s.levels, d, (size_t)de * d.levels, lv);
+}
+
+// one workgroup per template: `lv` levels of entry src_idx[i] of s into entry dst_idx[i] of d; d_has (nullable): the destination's
+// per-entry "has" byte, set
+__global__ __launch_bounds__(256) void k_klt_copy_templates(int n, const int* __restrict__ src_idx, const int* __restrict__ dst_idx, int lv, TemplateView s,
+                                                            TemplateView d, uint8_t* d_has) {
     const int i = blockIdx.x;
     if (i >= n) return;
     if (d_has && threadIdx.x == 0) d_has[dst_idx[i]] = 1;
-    const size_t so = (size_t)src_idx[i] * src_levels, d_o = (size_t)dst_idx[i] * dst_levels;
-    for (int e = threadIdx.x; e < lv * KA; e += 256) { dI[d_o * KA + e] = sI[so * KA + e]; dD[d_o * KA + e] = sD[so * KA + e]; }
-    for (int e = threadIdx.x; e < 2 * lv; e += 256) dM[2 * d_o + e] = sM[2 * so + e];
-    for (int e = threadIdx.x; e < lv; e += 256) dV[d_o + e] = sV[so + e];
-}
-
-// The archive is DENSE by key (a map point id indexes its slot: no lookup on the device): KA x levels x 6 bytes per key, so the key range is bounded --
-// 2^20 map points = 2.9 GB at 5 levels; the reference's maps hold thousands (include/nrs.h nrs_klt_archive_templates)
-constexpr int NRS_KLT_ARCHIVE_MAX_KEY = 1 << 20;
-static int klt_archive_reserve(nrs_ctx* c, KltState* k, int cap_want) {
-    if (k->a_levels != k->levels && k->a_cap > 0) {                // (another level count: the archive starts over)
-        NRS_HIP(c, hipStreamSynchronize(c->stream));
-        c->release(k->aI); c->release(k->aD); c->release(k->aMean); c->release(k->aValid); c->release(k->aHas);
-        k->a_cap = 0; k->a_has.clear();
-    }
-    k->a_levels = k->levels;
-    if (cap_want <= k->a_cap) return NRS_OK;
-    const int cap = std::max(cap_want + cap_want / 2, 256);
-    const size_t L = (size_t)k->a_levels;
-    DevBuf nI, nD, nM, nV, nH;
-    int rc = c->ensure(nI, sizeof(short) * KA * L * cap);
-    if (rc == NRS_OK) rc = c->ensure(nD, sizeof(short2) * KA * L * cap);
-    if (rc == NRS_OK) rc = c->ensure(nM, sizeof(float) * 2 * L * cap);
-    if (rc == NRS_OK) rc = c->ensure(nV, L * cap);
-    if (rc == NRS_OK) rc = c->ensure(nH, (size_t)cap);
-    if (rc != NRS_OK) { c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nH); return rc; }
-    {                                                              // the "has" bytes start at zero where the archive grows
-        const hipError_t he = hipMemsetAsync(nH.p, 0, (size_t)cap, c->stream);
-        if (he != hipSuccess) {
-            c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nH);
-            return c->fail(NRS_ERR_HIP, "template archive: clearing the grown buffers failed: %s", hipGetErrorString(he));
-        }
-    }
-    if (k->a_cap > 0) {
-        const size_t m = (size_t)k->a_cap;
-        hipError_t he = hipMemcpyAsync(nI.p, k->aI.p, sizeof(short) * KA * L * m, hipMemcpyDeviceToDevice, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(nD.p, k->aD.p, sizeof(short2) * KA * L * m, hipMemcpyDeviceToDevice, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(nM.p, k->aMean.p, sizeof(float) * 2 * L * m, hipMemcpyDeviceToDevice, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(nV.p, k->aValid.p, L * m, hipMemcpyDeviceToDevice, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(nH.p, k->aHas.p, m, hipMemcpyDeviceToDevice, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-        if (he != hipSuccess) {                                    // (the new buffers do not outlive a failed copy; the archive stays as it was)
-            c->release(nI); c->release(nD); c->release(nM); c->release(nV); c->release(nH);
-            return c->fail(NRS_ERR_HIP, "template archive: copy to the grown buffers failed: %s", hipGetErrorString(he));
-        }
-    }
-    c->release(k->aI); c->release(k->aD); c->release(k->aMean); c->release(k->aValid); c->release(k->aHas);
-    k->aI = nI; k->aD = nD; k->aMean = nM; k->aValid = nV; k->aHas = nH;
-    k->a_cap = cap;
-    k->a_has.resize((size_t)cap, 0);
-    return NRS_OK;
+    copy_template(s, src_idx[i], d, dst_idx[i], lv);
 }
 
 extern "C" int nrs_klt_archive_templates(nrs_ctx* c, int32_t n, const int32_t* slots, const int32_t* keys) {
     if (!c) return NRS_ERR_INVALID;
-    if (n < 0 || (n > 0 && (!slots || !keys))) return c->fail(NRS_ERR_INVALID, "nrs_klt_archive_templates: bad argument");
-    if (n == 0) return NRS_OK;
     KltState* k = c->klt;
-    if (!k) return c->fail(NRS_ERR_STATE, "nrs_klt_archive_templates: no tracker state");
-    int kmax = -1;
-    for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= k->n) return c->fail(NRS_ERR_INVALID, "nrs_klt_archive_templates: slot %d out of range", slots[i]);
-        if (keys[i] < 0 || keys[i] >= NRS_KLT_ARCHIVE_MAX_KEY) return c->fail(NRS_ERR_INVALID, "nrs_klt_archive_templates: key %d out of range (the archive is dense by key: keys below %d)", keys[i], NRS_KLT_ARCHIVE_MAX_KEY);
-        kmax = std::max(kmax, keys[i]);
-    }
+    char msg[256];
+    int kmax;
+    const int bad = klt_archive_check(n, slots, keys, k != nullptr, k ? k->n : 0, &kmax, msg, sizeof msg);
+    if (bad) return c->fail(bad == -2 ? NRS_ERR_STATE : NRS_ERR_INVALID, "%s", msg);
+    if (n == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
-    NRS_TRY(klt_archive_reserve(c, k, kmax + 1));
-    // a key listed more than once: its LAST occurrence stands (the copies run side by side: two of them must not share a destination)
-    std::vector<int> u_slot, u_key;
-    {
-        std::vector<int> last((size_t)kmax + 1, -1);
-        for (int i = 0; i < n; ++i) last[keys[i]] = i;
-        for (int i = 0; i < n; ++i) if (last[keys[i]] == i) { u_slot.push_back(slots[i]); u_key.push_back(keys[i]); }
+    if (k->arch.levels != k->tmpl.levels && k->arch.cap > 0) {     // (another level count: the archive starts over)
+        NRS_HIP(c, hipStreamSynchronize(c->stream));
+        k->arch.release(c);
+        k->a_has.clear();
     }
+    k->arch.levels = k->tmpl.levels;
+    NRS_TRY(k->arch.reserve(c, kmax + 1, k->arch.cap));
+    k->a_has.resize((size_t)k->arch.cap, 0);
+    std::vector<int> u_slot, u_key;
+    klt_archive_last_stands(n, slots, keys, kmax, u_slot, u_key);
     const int m = (int)u_key.size();
     NRS_TRY(c->ensure(k->a_idx, sizeof(int) * 2 * (size_t)m));
     int* d_idx = k->a_idx.as<int>();
     NRS_HIP(c, hipMemcpyAsync(d_idx, u_slot.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipMemcpyAsync(d_idx + m, u_key.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_klt_copy_templates, dim3(m), dim3(256), 0, c->stream, m, d_idx, d_idx + m, k->levels, k->levels, k->a_levels,
-                       k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>(),
-                       k->aI.as<short>(), k->aD.as<short2>(), k->aMean.as<float>(), k->aValid.as<uint8_t>(), k->aHas.as<uint8_t>());
+    hipLaunchKernelGGL(k_klt_copy_templates, dim3(m), dim3(256), 0, c->stream, m, d_idx, d_idx + m, k->tmpl.levels, k->tmpl.view(), k->arch.view(),
+                       k->arch.side.as<uint8_t>());
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipStreamSynchronize(c->stream));                   // (the caller's index arrays are free again; the archive is complete for any stream)
     for (int i = 0; i < n; ++i) k->a_has[keys[i]] = 1;
@@ -836,24 +803,24 @@ extern "C" int nrs_klt_insert_archived(nrs_ctx* c, nrs_ctx* src, int32_t n, cons
     if (n == 0) return NRS_OK;
     if (c->device != src->device) return c->fail(NRS_ERR_INVALID, "nrs_klt_insert_archived: the two contexts are on different devices");
     KltState* ks = src->klt;
-    if (!ks || ks->a_cap == 0) return c->fail(NRS_ERR_STATE, "nrs_klt_insert_archived: the source context holds no archive");
+    if (!ks || ks->arch.cap == 0) return c->fail(NRS_ERR_STATE, "nrs_klt_insert_archived: the source context holds no archive");
     KltState* k = klt(c);
     if (!k) return c->fail(NRS_ERR_ALLOC, "out of host memory");
-    if (k->levels > ks->a_levels) return c->fail(NRS_ERR_INVALID, "nrs_klt_insert_archived: the archive holds %d levels, this tracker needs %d", ks->a_levels, k->levels);
+    if (k->tmpl.levels > ks->arch.levels)
+        return c->fail(NRS_ERR_INVALID, "nrs_klt_insert_archived: the archive holds %d levels, this tracker needs %d", ks->arch.levels, k->tmpl.levels);
     for (int i = 0; i < n; ++i)
-        if (keys[i] < 0 || keys[i] >= ks->a_cap || !ks->a_has[keys[i]]) return c->fail(NRS_ERR_INVALID, "nrs_klt_insert_archived: nothing archived under key %d", keys[i]);
+        if (keys[i] < 0 || keys[i] >= ks->arch.cap || !ks->a_has[keys[i]]) return c->fail(NRS_ERR_INVALID, "nrs_klt_insert_archived: nothing archived under key %d", keys[i]);
     NRS_HIP(c, hipSetDevice(c->device));
-    NRS_TRY(reserve_points(c, k, k->n + n, true));
+    NRS_TRY(k->tmpl.reserve(c, k->n + n, k->n));
     NRS_TRY(c->ensure(k->a_idx, sizeof(int) * 2 * (size_t)n));
     std::vector<int> dst((size_t)n);
     for (int i = 0; i < n; ++i) dst[i] = k->n + i;
     int* d_idx = k->a_idx.as<int>();
     NRS_HIP(c, hipMemcpyAsync(d_idx, keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipMemcpyAsync(d_idx + n, dst.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(k->prev.as<float>() + 2 * (size_t)k->n, xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_klt_copy_templates, dim3(n), dim3(256), 0, c->stream, n, d_idx, d_idx + n, k->levels, ks->a_levels, k->levels,
-                       ks->aI.as<short>(), ks->aD.as<short2>(), ks->aMean.as<float>(), ks->aValid.as<uint8_t>(),
-                       k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>(), (uint8_t*)nullptr);
+    NRS_HIP(c, hipMemcpyAsync(k->prev() + 2 * (size_t)k->n, xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_klt_copy_templates, dim3(n), dim3(256), 0, c->stream, n, d_idx, d_idx + n, k->tmpl.levels, ks->arch.view(), k->tmpl.view(),
+                       (uint8_t*)nullptr);
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     k->n += n;
@@ -974,15 +941,10 @@ __global__ __launch_bounds__(REUSE_BLOCK) void k_reuse_gate(int n_cand, const in
 
 // stage 6: archive entry new_key[i] -> tracker slot n0 + i, `lv` levels (what nrs_klt_insert_archived copies); one workgroup per
 // candidate is launched, the ones at or beyond n_new (out[2]) leave
-__global__ __launch_bounds__(256) void k_reuse_append(const int* __restrict__ out, const int* __restrict__ new_key, int n0, int lv, int src_levels, int dst_levels,
-                                                      const short* __restrict__ sI, const short2* __restrict__ sD, const float* __restrict__ sM,
-                                                      const uint8_t* __restrict__ sV, short* dI, short2* dD, float* dM, uint8_t* dV) {
+__global__ __launch_bounds__(256) void k_reuse_append(const int* __restrict__ out, const int* __restrict__ new_key, int n0, int lv, TemplateView s, TemplateView d) {
     const int i = blockIdx.x;
     if (i >= out[2]) return;
-    const size_t so = (size_t)new_key[i] * src_levels, d_o = (size_t)(n0 + i) * dst_levels;
-    for (int e = threadIdx.x; e < lv * KA; e += 256) { dI[d_o * KA + e] = sI[so * KA + e]; dD[d_o * KA + e] = sD[so * KA + e]; }
-    for (int e = threadIdx.x; e < 2 * lv; e += 256) dM[2 * d_o + e] = sM[2 * so + e];
-    for (int e = threadIdx.x; e < lv; e += 256) dV[d_o + e] = sV[so + e];
+    copy_template(s, new_key[i], d, n0 + i, lv);
 }
 
 }  // namespace nrs
@@ -1001,10 +963,10 @@ extern "C" int nrs_point_reuse(nrs_ctx* c, const nrs_camera* cam, const float po
         return c->fail(NRS_ERR_STATE, "nrs_point_reuse: no pyramid has been built (it tracks on the image of the last nrs_klt_track[_front] / nrs_klt_set_reference[_front])");
     if (w != k->pyr.L[0].w || h != k->pyr.L[0].h)
         return c->fail(NRS_ERR_STATE, "nrs_point_reuse: %d x %d is not the size of the pyramid this context holds (%d x %d)", w, h, k->pyr.L[0].w, k->pyr.L[0].h);
-    if (k->a_cap > 0 && k->a_levels < 2)
-        return c->fail(NRS_ERR_INVALID, "nrs_point_reuse: the archive holds %d level(s), PointReuse's tracker needs 2", k->a_levels);
-    if (insert_new && k->a_cap > 0 && k->levels > k->a_levels)
-        return c->fail(NRS_ERR_INVALID, "nrs_point_reuse: the archive holds %d levels, this tracker needs %d", k->a_levels, k->levels);
+    if (k->arch.cap > 0 && k->arch.levels < 2)
+        return c->fail(NRS_ERR_INVALID, "nrs_point_reuse: the archive holds %d level(s), PointReuse's tracker needs 2", k->arch.levels);
+    if (insert_new && k->arch.cap > 0 && k->tmpl.levels > k->arch.levels)
+        return c->fail(NRS_ERR_INVALID, "nrs_point_reuse: the archive holds %d levels, this tracker needs %d", k->arch.levels, k->tmpl.levels);
     *n_cand = 0; *n_reused = 0; *n_new = 0;
     if (n_map == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
@@ -1036,25 +998,23 @@ extern "C" int nrs_point_reuse(nrs_ctx* c, const nrs_camera* cam, const float po
     if (n < 0 || n > n_map) return c->fail(NRS_ERR_HIP, "nrs_point_reuse: the candidate count came back as %d (map of %d)", n, n_map);
     if (n == 0) return NRS_OK;                                     // (the tracker is untouched)
     const int n0 = k->n;
-    if (insert_new) NRS_TRY(reserve_points(c, k, n0 + n, true));   // (room for every candidate; the buffers grow in amortised steps)
+    if (insert_new) NRS_TRY(k->tmpl.reserve(c, n0 + n, n0));   // (room for every candidate; the buffers grow in amortised steps)
     const ReuseLayout L((size_t)n);
     NRS_TRY(c->ensure(k->reuse_out, sizeof(int) * L.words));
     int* d_out = k->reuse_out.as<int>();
     TrackArgs a;
-    a.pyr = k->pyr; a.n = n; a.levels = k->a_levels; a.max_level = 1; a.max_iters = k->max_iters;
+    a.pyr = k->pyr; a.n = n; a.max_level = 1; a.max_iters = k->max_iters;
     a.eps = k->eps; a.min_eig = k->min_eig; a.initial_flow = 1;
     a.prev = d_seed; a.pts = d_xy; a.status = d_status;
-    a.tI = k->aI.as<short>(); a.tD = k->aD.as<short2>(); a.tMean = k->aMean.as<float>(); a.tValid = k->aValid.as<uint8_t>();
-    const SlotKeyed sl{d_cand, k->aHas.as<uint8_t>(), k->a_cap};
+    a.t = k->arch.view();
+    const SlotKeyed sl{d_cand, k->arch.side.as<uint8_t>(), k->arch.cap};
     hipLaunchKernelGGL(k_klt_track_keyed, dim3(n), dim3(64), 0, c->stream, a, sl);
-    hipLaunchKernelGGL(k_klt_ssim_keyed, dim3(n), dim3(64), 0, c->stream, k->pyr, k->a_levels, d_xy, d_status, a.tI, min_ssim, ws + 3, sl);
+    hipLaunchKernelGGL(k_klt_ssim_keyed, dim3(n), dim3(64), 0, c->stream, k->pyr, a.t, d_xy, d_status, min_ssim, ws + 3, sl);
     const ReusePacked P{(unsigned)L.cand, (unsigned)L.seed, (unsigned)L.xy, (unsigned)L.status, (unsigned)L.accepted};
     hipLaunchKernelGGL(k_reuse_gate, dim3(1), dim3(REUSE_BLOCK), 0, c->stream, n, d_cand, d_seed, d_xy, d_status, in.frame_slot, insert_new ? 1 : 0, n0,
-                       k->prev.as<float>(), d_new_key, d_out, P);
+                       k->prev(), d_new_key, d_out, P);
     if (insert_new)
-        hipLaunchKernelGGL(k_reuse_append, dim3(n), dim3(256), 0, c->stream, d_out, d_new_key, n0, k->levels, k->a_levels, k->levels,
-                           k->aI.as<short>(), k->aD.as<short2>(), k->aMean.as<float>(), k->aValid.as<uint8_t>(),
-                           k->tI.as<short>(), k->tD.as<short2>(), k->tMean.as<float>(), k->tValid.as<uint8_t>());
+        hipLaunchKernelGGL(k_reuse_append, dim3(n), dim3(256), 0, c->stream, d_out, d_new_key, n0, k->tmpl.levels, a.t, k->tmpl.view());
     NRS_HIP(c, hipGetLastError());
     std::vector<int32_t> packed(L.words);
     NRS_HIP(c, hipMemcpyAsync(packed.data(), d_out, sizeof(int) * L.words, hipMemcpyDeviceToHost, c->stream));

@@ -32,7 +32,9 @@ def _padded(img, ch, pad):
 
 
 @pytest.mark.parametrize("ch", [1, 3, 4])
-@pytest.mark.parametrize("wh", [(64, 48), (70, 52)], ids=lambda s: "%dx%d" % s)     # tiles divide the image / the CLAHE padding branch
+# tiles divide the image / the CLAHE padding branch / past one block of 256 in x (w > 256, w % 256 != 0, w % 8 != 0: the second block's
+# x >= w guard, which the other two sizes never reach, and the padding branch again)
+@pytest.mark.parametrize("wh", [(64, 48), (70, 52), (300, 44)], ids=lambda s: "%dx%d" % s)
 def test_pair_equals_the_oracle_per_eye(wh, ch):
     w, h = wh
     left = FC.blobs(h, w, ch, 100 + w + ch)

@@ -198,3 +198,129 @@ def test_archived_templates_equal_the_host_hand_over(ctx):
         other.close()
     ctx.klt_clear()
     ctx.klt_configure()
+
+
+# ---- the template stores where they grow (csrc/nrs_klt.hip TemplateSet::reserve).  A store's first capacity is max(n + n / 2, 256) and it
+# never shrinks, so every test here starts from contexts of its own; what is expected is read from the tracker before the growth.
+KEYS = ("xy", "gray", "grad", "mean", "valid")
+OUT_IMAGE_BOUNDARIES = 4
+
+
+def _same_bytes(got, want, tag):
+    assert len(got) == len(want), tag
+    for i, (a, b) in enumerate(zip(got, want)):
+        for k in KEYS:
+            assert a[k].tobytes() == b[k].tobytes(), (tag, i, k)
+
+
+def _grown_tracker():
+    """200 stored points (capacity 300), then the first 150 inserted again: 350 points, which forces the store to grow with all 200 kept.
+    Returns the context, the sequence, the 200 points, their templates as read BEFORE the growth and their track on im1 before it."""
+    sq = S.make_lk_sequence(260, 17)
+    pts = sq["pts"][:200]
+    assert len(pts) == 200
+    c = nrs.Context()
+    c.klt_configure()
+    c.klt_set_reference(sq["im0"], pts)
+    before = c.klt_get_templates(0, 200)
+    assert sum(int(t["valid"][0]) for t in before) > 150 and len({t["gray"].tobytes() for t in before}) > 150      # (the slots differ: a mix-up shows)
+    track0 = c.klt_track(sq["im1"], pts + np.float32(0.7), np.zeros(200, np.int32))
+    c.klt_insert_templates(before[:150])
+    assert c.klt_num_points() == 350
+    return c, sq, pts, before, track0
+
+
+def test_tracker_growth_keeps_the_stored_templates():
+    c, sq, pts, before, track0 = _grown_tracker()
+    try:
+        _same_bytes(c.klt_get_templates(0, 200), before, "kept")
+        _same_bytes(c.klt_get_templates(200, 150), before[:150], "inserted")
+        guess = np.concatenate([pts, pts[:150]]) + np.float32(0.7)
+        xy, st, good, _ = c.klt_track(sq["im1"], guess, np.zeros(350, np.int32))
+        assert np.array_equal(xy[:150], xy[200:], equal_nan=True) and np.array_equal(st[:150], st[200:])
+        assert np.array_equal(xy[:200], track0[0], equal_nan=True) and np.array_equal(st[:200], track0[1])      # ... and what they gave before the growth
+        assert good == track0[2] + int((st[200:] == 0).sum()) and (st == 0).sum() > 175
+    finally:
+        c.close()
+
+
+def test_tracker_growth_entered_through_insert_archived():
+    c, sq, pts, before, _ = _grown_tracker()
+    try:
+        c.klt_archive_templates(np.arange(200), np.arange(200))
+        xy = pts + np.float32(0.25)
+        c.klt_insert_archived(c, np.arange(200), xy)                # 550 > 525: the store grows inside the call, 350 kept
+        assert c.klt_num_points() == 550
+        _same_bytes(c.klt_get_templates(0, 350), before + before[:150], "kept")
+        _same_bytes(c.klt_get_templates(350, 200), [dict(t, xy=xy[i]) for i, t in enumerate(before)], "archived")
+    finally:
+        c.close()
+
+
+def test_archive_growth_keeps_its_entries_and_their_has_bytes():
+    """key 10 (archive capacity 256), then key 1000 (capacity 1501): key 10's entry and its device-side "has" byte are carried over, the
+    "has" bytes of the keys between read zero -- on the host (insert_archived refuses them) and on the device (point_reuse finds key 999
+    never filled, and key 10 filled)"""
+    sq = S.make_lk_sequence(40, 13)
+    pts = sq["pts"]
+    c, other = nrs.Context(), nrs.Context()
+    try:
+        c.klt_configure()
+        c.klt_set_reference(sq["im0"], pts)
+        host = c.klt_get_templates(0, len(pts))
+        c.klt_archive_templates([3], [10])
+        c.klt_archive_templates([7], [1000])
+        other.klt_configure()
+        xy = np.stack([host[3]["xy"], host[7]["xy"]]) + np.float32(0.5)
+        other.klt_insert_archived(c, [10, 1000], xy)
+        _same_bytes(other.klt_get_templates(0, 2), [dict(host[3], xy=xy[0]), dict(host[7], xy=xy[1])], "archive")
+        for key in (11, 999):
+            with pytest.raises(nrs.NrsError):
+                other.klt_insert_archived(c, [key], xy[:1])
+        assert other.klt_num_points() == 2
+        # the device side: a map of 1000 points, all held by the frame but 10 and 999, which project onto two of the stored points
+        h, w = sq["im0"].shape
+        prm = np.array([64, 64, w / 2, h / 2, 0, 0, 0, 0], np.float32)
+        uv = np.stack([host[3]["xy"], host[7]["xy"]]).astype(np.float64)
+        map_pos = np.tile(np.array([[0.05, 0.05, 2]], np.float32), (1000, 1))
+        map_pos[[10, 999]] = np.stack([(uv[:, 0] - prm[2]) / prm[0] * 2, (uv[:, 1] - prm[3]) / prm[1] * 2, np.full(2, 2.0)], 1).astype(np.float32)
+        frame_slot = np.arange(1000)
+        frame_slot[[10, 999]] = -1
+        n0 = c.klt_num_points()
+        d = c.point_reuse(nrs.make_camera(S.PINHOLE, prm), np.array([0, 0, 0, 1], np.float32), np.zeros(3, np.float32), (w, h), map_pos, frame_slot,
+                          np.zeros(1000, np.int32), [], 0.75, False)
+        assert d["cand_id"].tolist() == [10, 999]
+        assert d["status"][1] == OUT_IMAGE_BOUNDARIES and not d["accepted"][1]          # never filled (test_key_that_was_never_archived)
+        assert d["status"][0] == 0 and d["accepted"][0] and np.abs(d["xy"][0] - d["seed_xy"][0]).max() < 0.1      # its own image: it stays
+        assert d["n_new"] == 0 and c.klt_num_points() == n0
+    finally:
+        c.close()
+        other.close()
+
+
+def test_archive_starts_over_under_another_level_count():
+    sq = S.make_lk_sequence(40, 13)
+    pts = sq["pts"]
+    c, two, five = nrs.Context(), nrs.Context(), nrs.Context()
+    try:
+        c.klt_configure()
+        c.klt_set_reference(sq["im0"], pts)
+        c.klt_archive_templates([3], [5])
+        c.klt_clear()
+        c.klt_configure(21, 1)
+        c.klt_set_reference(sq["im0"], pts[:4])
+        want = c.klt_get_templates(0, 1)
+        assert want[0]["gray"].shape[0] == 2
+        c.klt_archive_templates([0], [9])
+        two.klt_configure(21, 1)
+        five.klt_configure()
+        with pytest.raises(nrs.NrsError):
+            two.klt_insert_archived(c, [5], pts[:1])                # archived under five levels only: gone with the restart
+        two.klt_insert_archived(c, [9], pts[:1])
+        _same_bytes(two.klt_get_templates(0, 1), want, "two levels")
+        with pytest.raises(nrs.NrsError):
+            five.klt_insert_archived(c, [9], pts[:1])               # the new entry has two levels: a five-level tracker cannot take it
+    finally:
+        c.close()
+        two.close()
+        five.close()
