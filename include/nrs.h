@@ -158,7 +158,7 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  * Every switch is a row of ONE table (nr-slam_amd/csrc/nrs_switches.hpp: kind, default, group, one line on what it does); a name that is
  * not in it is accepted and does nothing.  A switch written without a value below goes by presence: it is on when set to anything, "0"
  * included (NRS_NO_LDS=0 turns the LDS path off); one written with a value is read with atoi / atof (garbage reads as 0).
- *   measurement   NRS_TIMING (stage marks of engine_create and the a2 driver on stderr), NRS_ND_DBG / NRS_ND_DBG2 (phase clocks of one
+ *   measurement   NRS_TIMING (stage marks of engine_create, the a2 driver and the frame-mapping entry points on stderr), NRS_ND_DBG / NRS_ND_DBG2 (phase clocks of one
  *                 direct solve through nrs_debug_nd_solve), NRS_PEEK_DEBUG (gain ratios at the early-rejection looks)
  *   checks        NRS_POISON (fresh device allocations filled with NaN patterns), NRS_CHECK_EVAL / NRS_CHECK_FUSED / NRS_CHECK_CHI (an
  *                 evaluation / a single-launch PCG iteration / the carried chi2 computed twice and compared)
@@ -571,6 +571,49 @@ int nrs_map_frame(nrs_ctx* ctx, const nrs_camera* cam, int32_t n_frames, const f
  * RegularizationGraph.AddEdge of the restatement); the graph must have been resized to hold the new indices. */
 int nrs_map_grow_graph(nrs_ctx* ctx, nrs_rgraph* g, const float* pos, int32_t n_new, const int32_t* new_ids, int32_t n_other,
                        const int32_t* other_ids);
+
+/* ---- The resident TemporalBuffer (reference modules/map/temporal_buffer.cc:28-74) ----------------------------------------------
+ * The buffer nrs_map_frame takes flattened from the host, held on the device by an object a context owns (as nrs_rgraph): a frame
+ * enters with ONE upload and frame mapping reads the buffer where it lies.
+ *   nrs_tbuf_create   TemporalBuffer(Options&): max_buffer_size in [1, 20] (the reference's 20, SLAM/system.cc:42)
+ *   nrs_tbuf_insert   InsertSnapshotFromFrame (:28-56).  The caller passes the frame's n slots UNFILTERED: keypoint id (class_id),
+ *                     keypoint, landmark position and LandmarkStatus per slot; only the slots whose status is TRACKED_WITH_3D (0) or
+ *                     TRACKED (1) enter the snapshot (:31-34).  has_lm: null = every kept slot has a landmark entry, as in the
+ *                     reference (:41, zeros for TRACKED); else one byte per slot (the synthetic buffers of the tests have keypoints
+ *                     without one).  pose_qt = camera_transform_world (qx qy qz qw tx ty tz), deform_mag = deformation_magnitud.
+ *                     The pop rule is the reference's (:49-55): the oldest snapshot leaves when size() > max_buffer_size BEFORE the
+ *                     insert, so the buffer fills to max + 1, then goes max + 1 -> max -> max + 1 inside every call: never more than max + 1 <= 21.
+ *                     Refused with NRS_ERR_INVALID, the buffer unchanged: a null array with n > 0; a negative id among the kept
+ *                     slots; two kept slots with one id (the reference's map would silently overwrite the first: this build refuses
+ *                     and says so; ids of slots that are not kept are not looked at); held ids that would span more than 4 194 304
+ *                     (2^22: the device addresses a row through tables over [lowest, highest] held id).
+ *                     The snapshot is staged in pinned memory and copied in one asynchronous transfer; the slots grow by doubling,
+ *                     so a steady state allocates nothing.
+ *   nrs_tbuf_clear    forgets every snapshot (the slots stay allocated)
+ *   nrs_tbuf_info     snapshots held, distinct keypoint ids over them, GetTriangulationCandidatesIds().size() (:62-74) -- known on
+ *                     the host (per-id reference counts), nothing is read back
+ *   nrs_tbuf_flat     debug download of the dense form the device builds for a mapping call: the distinct ids ascending (row j =
+ *                     ids[j]), has_kp / has_lm [n_frames x n_ids], kp_xy [.. x 2], lm_xyz [.. x 3], last_status [n_ids] (BAD (3) for
+ *                     an id the last snapshot does not hold), poses [n_frames x 7], deform_mag [n_frames], oldest snapshot first;
+ *                     values under a clear flag are zero.  Sizes from nrs_tbuf_info.
+ *   nrs_map_frame_tbuf  nrs_map_frame (above: same arguments, same outputs, same bits) on the resident buffer, except that cand_ids
+ *                     and accepted_ids are KEYPOINT IDS (ascending, as the rows are), translated on the device.  The outputs need
+ *                     room for as many entries as nrs_tbuf_info's candidates.  No candidates: 0 / 0, mode 2, nothing launched.
+ *                     An empty buffer is NRS_ERR_STATE; a buffer of another context, index_snapshot outside [-1, snapshots held)
+ *                     or a non-finite threshold NRS_ERR_INVALID. */
+typedef struct nrs_tbuf nrs_tbuf;
+int nrs_tbuf_create(nrs_ctx* ctx, int32_t max_buffer_size, nrs_tbuf** out);
+void nrs_tbuf_destroy(nrs_tbuf* tb);
+int nrs_tbuf_clear(nrs_tbuf* tb);
+int nrs_tbuf_insert(nrs_tbuf* tb, int32_t n, const int32_t* kp_id, const float* kp_xy /* n x 2 */, const float* lm_xyz /* n x 3 */,
+                    const int32_t* status, const uint8_t* has_lm /* n or null */, const float pose_qt[7], float deform_mag);
+int nrs_tbuf_info(const nrs_tbuf* tb, int32_t* n_frames, int32_t* n_ids, int32_t* n_candidates);
+int nrs_tbuf_flat(nrs_tbuf* tb, int32_t* ids, uint8_t* has_kp, float* kp_xy, uint8_t* has_lm, float* lm_xyz, int32_t* last_status,
+                  float* poses, float* deform_mag);
+int nrs_map_frame_tbuf(nrs_ctx* ctx, const nrs_camera* cam, nrs_tbuf* tb, float rad_per_pixel, float rigidity_th, int32_t min_track,
+                       int32_t index_snapshot, int32_t* n_cand, int32_t* cand_ids, int32_t* rigid_status, float* rigid_xyz,
+                       int32_t* deform_status, float* deform_xyz, int32_t counts[3], int32_t* n_accepted, int32_t* accepted_ids,
+                       float* accepted_xyz);
 
 /* ---- a2: CameraPoseAndDeformationOptimization (g2o_optimization.cc:148-557) ------------------
  * Frame side: n_f landmarks in frame index order with their map-point index (f_map, -1 = none),

@@ -8,7 +8,8 @@
 //   k_triangulate     (nrs_triang.hip, one wave per candidate) the deformable leg (:97-115) on the same device buffer and list
 //   k_map_vote        one workgroup: "NaN." (:101-102), the two counts, the rigid / deformable vote (:192-209) and the accepted list
 //                     (:211-236) compacted in candidate order by a workgroup scan -- no atomics, the order is the reference's
-// and one download of the packed result (nrs_map_host.hpp).  The fp32 steps use the operation order of oracle/triang_oracle.py
+// and one download of the packed result (nrs_map_host.hpp).  Everything behind the upload is map_run, which nrs_map_frame_tbuf
+// (nrs_tbuf.hip) calls on the tables it rebuilds from the resident buffer; k_map_row_ids then turns its two id lists into keypoint ids.  The fp32 steps use the operation order of oracle/triang_oracle.py
 // (contraction off); every comparison is written as the reference writes it, so a NaN passes the gates it passes there.
 #include <cmath>
 #include <vector>
@@ -161,6 +162,53 @@ __global__ __launch_bounds__(MAP_T) void k_map_vote(MapArgs A) {
     if (tid == 0) { A.hdr[1] = n_rigid; A.hdr[2] = n_def; A.hdr[3] = mode; A.hdr[4] = n_acc; A.hdr[5] = 0; A.hdr[6] = 0; A.hdr[7] = 0; }
 }
 
+// the ids of the resident buffer's callers: rows -> keypoint ids, in place, once nothing reads the two lists as rows any more
+__global__ __launch_bounds__(256) void k_map_row_ids(int n_cand, const int* __restrict__ hdr, const int* __restrict__ row_id, int* cand, int* a_id) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_cand) return;
+    cand[i] = row_id[cand[i]];
+    if (i < hdr[4]) a_id[i] = row_id[a_id[i]];
+}
+
+size_t map_ws_bytes(int nc) { return 4 * MapLayout((size_t)nc).words + (size_t)nc + 1024; }
+
+// Everything of nrs_map_frame behind the upload, for both of its forms: T holds the camera, the sizes and the device-side flat buffer,
+// ws (256-byte aligned, map_ws_bytes(nc) bytes) takes the close bits and the packed result.  row_id (device, T.n ints) or null: the two id
+// lists leave as row_id[row] (nrs_map_frame_tbuf).
+int map_run(nrs_ctx* c, const char* who, const TriArgs& T, const float* d_deform_mag, char* ws, int nc, float rad_per_pixel, float rigidity_th,
+            int index_snapshot, const int* d_row_id, const MapOut& out) {
+    const MapLayout L((size_t)nc);
+    StageTimer tm{c, who, true};                                   // (NRS_TIMING only: the marks wait for the stream)
+    MapArgs A;
+    A.T = T;
+    A.deform_mag = d_deform_mag;
+    char* p = ws;
+    A.close_bits = reinterpret_cast<uint8_t*>(p);
+    p += ((size_t)nc + 255) / 256 * 256;
+    int* pk = reinterpret_cast<int*>(p);                           // the packed result
+    A.hdr = pk; A.cand = pk + L.cand; A.r_st = pk + L.r_st; A.r_xyz = reinterpret_cast<float*>(pk + L.r_xyz);
+    A.a_id = pk + L.a_id; A.a_xyz = reinterpret_cast<float*>(pk + L.a_xyz);
+    A.T.n_cand = nc; A.T.cand = A.cand; A.T.o_status = pk + L.d_st; A.T.o_xyz = reinterpret_cast<float*>(pk + L.d_xyz); A.T.o_dbg = nullptr;
+    A.rpp = rad_per_pixel; A.rigidity_th = rigidity_th; A.index_snapshot = index_snapshot;
+    NRS_HIP(c, hipMemsetAsync(pk, 0, 4 * L.words, c->stream));
+    hipLaunchKernelGGL(k_map_candidates, dim3(1), dim3(MAP_T), 0, c->stream, A, nc);
+    A.T.close_bits = A.close_bits;
+    hipLaunchKernelGGL(k_map_close, dim3(nc), dim3(64), 0, c->stream, A);
+    hipLaunchKernelGGL(k_map_rigid, dim3((nc + 63) / 64), dim3(64), 0, c->stream, A);
+    NRS_HIP(c, hipGetLastError());
+    NRS_TRY(tri_launch(c, A.T));
+    hipLaunchKernelGGL(k_map_vote, dim3(1), dim3(MAP_T), 0, c->stream, A);
+    if (d_row_id) hipLaunchKernelGGL(k_map_row_ids, dim3((nc + 255) / 256), dim3(256), 0, c->stream, nc, A.hdr, d_row_id, A.cand, A.a_id);
+    NRS_HIP(c, hipGetLastError());
+    tm("mapping kernels");
+    std::vector<int32_t> h(L.words);
+    NRS_HIP(c, hipMemcpyAsync(h.data(), pk, 4 * L.words, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (map_unpack(h.data(), nc, out) != 0) return c->fail(NRS_ERR_STATE, "%s: the device's result header does not match the %d candidates counted", who, nc);
+    tm("download");
+    return NRS_OK;
+}
+
 }  // namespace nrs
 
 using namespace nrs;
@@ -182,37 +230,18 @@ extern "C" int nrs_map_frame(nrs_ctx* c, const nrs_camera* cam, int32_t n_frames
         counts[0] = 0; counts[1] = 0; counts[2] = MAP_MODE_DEFORMABLE;
         return NRS_OK;
     }
-    const MapLayout L((size_t)nc);
     const size_t fbytes = (sizeof(float) * (size_t)n_frames + 255) / 256 * 256;
     DevBuf big;
     struct Free2 { nrs_ctx* c; DevBuf* b; ~Free2() { c->release(*b); } } fr2{c, &big};
-    MapArgs A;
+    TriArgs T;
     char* p = nullptr;
-    NRS_TRY(tri_upload(c, big, fbytes + 4 * L.words + (size_t)nc + 1024, cam, n_frames, poses, n_ids, has_kp, kp_xy, has_lm, lm_xyz, last_status, min_track, A.T, &p));
-    A.deform_mag = reinterpret_cast<float*>(p);
+    StageTimer tm{c, "nrs_map_frame", true};
+    NRS_TRY(tri_upload(c, big, fbytes + map_ws_bytes(nc), cam, n_frames, poses, n_ids, has_kp, kp_xy, has_lm, lm_xyz, last_status, min_track, T, &p));
+    const float* d_mag = reinterpret_cast<float*>(p);
     NRS_HIP(c, hipMemcpyAsync(p, deform_mag, sizeof(float) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
     p += fbytes;
-    A.close_bits = reinterpret_cast<uint8_t*>(p);
-    p += ((size_t)nc + 255) / 256 * 256;
-    int* pk = reinterpret_cast<int*>(p);                           // the packed result
-    A.hdr = pk; A.cand = pk + L.cand; A.r_st = pk + L.r_st; A.r_xyz = reinterpret_cast<float*>(pk + L.r_xyz);
-    A.a_id = pk + L.a_id; A.a_xyz = reinterpret_cast<float*>(pk + L.a_xyz);
-    A.T.n_cand = nc; A.T.cand = A.cand; A.T.o_status = pk + L.d_st; A.T.o_xyz = reinterpret_cast<float*>(pk + L.d_xyz); A.T.o_dbg = nullptr;
-    A.rpp = rad_per_pixel; A.rigidity_th = rigidity_th; A.index_snapshot = index_snapshot;
-    NRS_HIP(c, hipMemsetAsync(pk, 0, 4 * L.words, c->stream));
-    hipLaunchKernelGGL(k_map_candidates, dim3(1), dim3(MAP_T), 0, c->stream, A, nc);
-    A.T.close_bits = A.close_bits;
-    hipLaunchKernelGGL(k_map_close, dim3(nc), dim3(64), 0, c->stream, A);
-    hipLaunchKernelGGL(k_map_rigid, dim3((nc + 63) / 64), dim3(64), 0, c->stream, A);
-    NRS_HIP(c, hipGetLastError());
-    NRS_TRY(tri_launch(c, A.T));
-    hipLaunchKernelGGL(k_map_vote, dim3(1), dim3(MAP_T), 0, c->stream, A);
-    NRS_HIP(c, hipGetLastError());
-    std::vector<int32_t> h(L.words);
-    NRS_HIP(c, hipMemcpyAsync(h.data(), pk, 4 * L.words, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipStreamSynchronize(c->stream));
-    if (map_unpack(h.data(), nc, out) != 0) return c->fail(NRS_ERR_STATE, "nrs_map_frame: the device's result header does not match the %d candidates counted", nc);
-    return NRS_OK;
+    tm("upload");
+    return map_run(c, "nrs_map_frame", T, d_mag, p, nc, rad_per_pixel, rigidity_th, index_snapshot, nullptr, out);
 }
 
 extern "C" int nrs_map_grow_graph(nrs_ctx* c, nrs_rgraph* g, const float* pos, int32_t n_new, const int32_t* new_ids, int32_t n_other,

@@ -54,4 +54,11 @@ int tri_upload(nrs_ctx* c, DevBuf& big, size_t extra, const nrs_camera* cam, int
 // k_triangulate over A.cand[0 .. A.n_cand) on the context's stream (cand, o_status, o_xyz, o_dbg are device pointers)
 int tri_launch(nrs_ctx* c, const TriArgs& A);
 
+// nrs_map.hip, for both forms of frame mapping (nrs_map_frame on a flat buffer from the host, nrs_map_frame_tbuf on the resident one,
+// nrs_tbuf.hip): the launches behind the upload, the download of the packed result and its unpacking
+struct MapOut;
+size_t map_ws_bytes(int n_cand);
+int map_run(nrs_ctx* c, const char* who, const TriArgs& T, const float* d_deform_mag, char* ws, int n_cand, float rad_per_pixel, float rigidity_th,
+            int index_snapshot, const int* d_row_id, const MapOut& out);
+
 }  // namespace nrs

@@ -35,7 +35,8 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_init_options_init", "nrs_init_essential",
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame",
            "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo",
-           "nrs_front_process_stereo", "nrs_stereo_match_pattern_front", "nrs_init_stereo_front", "nrs_stereo_match_lk_front"]
+           "nrs_front_process_stereo", "nrs_stereo_match_pattern_front", "nrs_init_stereo_front", "nrs_stereo_match_lk_front",
+           "nrs_tbuf_create", "nrs_tbuf_destroy", "nrs_tbuf_clear", "nrs_tbuf_insert", "nrs_tbuf_info", "nrs_tbuf_flat", "nrs_map_frame_tbuf"]
 
 
 class NrsError(RuntimeError):
@@ -175,6 +176,15 @@ def load_library(path=LIB_PATH):
     lib.nrs_stereo_match_pattern_front.argtypes = [ptr, ptr, f32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]
     lib.nrs_init_stereo_front.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr]
     lib.nrs_stereo_match_lk_front.argtypes = [ptr, ptr, ptr, f32, i32, i32, i32, i32, ptr, f32, ptr, ptr, ptr, ptr]
+    # the resident temporal buffer (include/nrs.h "The resident TemporalBuffer")
+    lib.nrs_tbuf_create.argtypes = [ptr, i32, ptr]
+    lib.nrs_tbuf_destroy.restype = None
+    lib.nrs_tbuf_destroy.argtypes = [ptr]
+    lib.nrs_tbuf_clear.argtypes = [ptr]
+    lib.nrs_tbuf_insert.argtypes = [ptr, i32, ptr, ptr, ptr, ptr, ptr, ptr, f32]
+    lib.nrs_tbuf_info.argtypes = [ptr, ptr, ptr, ptr]
+    lib.nrs_tbuf_flat.argtypes = [ptr] + [ptr] * 8
+    lib.nrs_map_frame_tbuf.argtypes = [ptr, ptr, ptr, f32, f32, i32, i32] + [ptr] * 10
     return lib
 
 
@@ -467,6 +477,73 @@ class RGraph:
         self.ctx._chk(self.lib.nrs_rgraph_rows(self.h, C.c_int32(n), _p(ids, C.c_int32), _p(mx, C.c_float), _p(mn, C.c_float), _p(d0, C.c_float),
                                                _p(st, C.c_uint8)))
         return mx, mn, d0, st
+
+
+class TBuf:
+    """nrs_tbuf_* (include/nrs.h): the device-resident TemporalBuffer of a context"""
+
+    def __init__(self, ctx, max_buffer_size=20):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        ctx._chk(self.lib.nrs_tbuf_create(ctx.h, max_buffer_size, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.lib.nrs_tbuf_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def clear(self):
+        self.ctx._chk(self.lib.nrs_tbuf_clear(self.h))
+
+    def insert(self, kp_id, kp_xy, lm_xyz, status, pose_qt, deform_mag, has_lm=None):
+        """InsertSnapshotFromFrame: the frame's slots unfiltered (the call keeps TRACKED_WITH_3D / TRACKED).  Ids must fit an int32."""
+        ids64 = np.asarray(kp_id, np.int64).reshape(-1)
+        n = len(ids64)
+        if n and (ids64.max() > 2**31 - 1 or ids64.min() < -2**31):
+            raise ValueError("TBuf.insert: a keypoint id does not fit 32 bits")
+        ids, xy, xyz, st = _i32(ids64), _f32(kp_xy).reshape(-1, 2), _f32(lm_xyz).reshape(-1, 3), _i32(status).reshape(-1)
+        if len(xy) != n or len(xyz) != n or len(st) != n:
+            raise ValueError("TBuf.insert: kp_id, kp_xy, lm_xyz and status differ in length")
+        hl = None if has_lm is None else np.ascontiguousarray(has_lm, np.uint8).reshape(-1)
+        if hl is not None and len(hl) != n:
+            raise ValueError("TBuf.insert: has_lm needs one flag per slot")
+        pose = _f32(pose_qt).reshape(7)
+        self.ctx._chk(self.lib.nrs_tbuf_insert(self.h, n, _p(ids, C.c_int32), _p(xy, C.c_float), _p(xyz, C.c_float), _p(st, C.c_int32),
+                                               _p(hl, C.c_uint8), _p(pose, C.c_float), float(deform_mag)))
+
+    def info(self):
+        """-> (snapshots held, distinct keypoint ids, triangulation candidates)"""
+        f, n, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self.ctx._chk(self.lib.nrs_tbuf_info(self.h, C.byref(f), C.byref(n), C.byref(c)))
+        return f.value, n.value, c.value
+
+    def flat(self):
+        """nrs_tbuf_flat -> (tb, deform_mag, ids) as nrs_frame_loop.TemporalBuffer.flat returns them (without model / prm)"""
+        F, n, _ = self.info()
+        ids, st = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        has_kp, has_lm = np.zeros((F, n), np.uint8), np.zeros((F, n), np.uint8)
+        kp, lm = np.zeros((F, n, 2), np.float32), np.zeros((F, n, 3), np.float32)
+        poses, mag = np.zeros((F, 7), np.float32), np.zeros(F, np.float32)
+        self.ctx._chk(self.lib.nrs_tbuf_flat(self.h, _p(ids, C.c_int32), _p(has_kp, C.c_uint8), _p(kp, C.c_float), _p(has_lm, C.c_uint8),
+                                             _p(lm, C.c_float), _p(st, C.c_int32), _p(poses, C.c_float), _p(mag, C.c_float)))
+        tb = dict(n_frames=F, poses=poses, has_kp=has_kp.astype(bool), kp_xy=kp, has_lm=has_lm.astype(bool), lm_xyz=lm, status=st)
+        return tb, mag, ids
+
+    def map_frame(self, cam, rad_per_pixel, rigidity_th=0.004, min_track=5, index_snapshot=-1, ctx=None):
+        """nrs_map_frame_tbuf: Context.map_frame's dict, with `cand` and `accepted_ids` as KEYPOINT IDS.  ctx: the context to call on
+        (the buffer's own; another one is refused)"""
+        ctx = ctx or self.ctx
+        m = max(1, self.info()[2])
+        cand, r_st, d_st, a_id = (np.zeros(m, np.int32) for _ in range(4))
+        r_xyz, d_xyz, a_xyz = (np.zeros((m, 3), np.float32) for _ in range(3))
+        counts = np.zeros(3, np.int32)
+        nc, na = C.c_int32(0), C.c_int32(0)
+        ctx._chk(self.lib.nrs_map_frame_tbuf(ctx.h, C.byref(cam), self.h, rad_per_pixel, rigidity_th, min_track, index_snapshot,
+                                             C.byref(nc), _p(cand, C.c_int32), _p(r_st, C.c_int32), _p(r_xyz, C.c_float), _p(d_st, C.c_int32),
+                                             _p(d_xyz, C.c_float), _p(counts, C.c_int32), C.byref(na), _p(a_id, C.c_int32), _p(a_xyz, C.c_float)))
+        nc, na = nc.value, na.value
+        return dict(cand=cand[:nc], rigid_status=r_st[:nc], rigid_xyz=r_xyz[:nc], deform_status=d_st[:nc], deform_xyz=d_xyz[:nc],
+                    n_rigid=int(counts[0]), n_deformable=int(counts[1]), mode=int(counts[2]), accepted_ids=a_id[:na], accepted_xyz=a_xyz[:na])
 
 
 class Context:

@@ -89,7 +89,8 @@ class GpuBackend:
     """The product path: one nrs context for the main tracker and, made on first use, one for PointReuse's two-level tracker (with
     device_reuse=True PointReuse is one call on the main context and the second one is never made)."""
 
-    def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None, device_reuse=False):
+    def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None, device_reuse=False,
+                 device_tbuf=False):
         """n_nodes > 0: EMBEDDED-DEFORMATION mode (include/nrs.h nrs_track_deform_solve_embedded; needs the dense graph): n_nodes map points
         (farthest-point sampling on the initial map, nrs_skin_select_nodes) carry the deformation vertices for the whole sequence, every
         other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call).  Mapping
@@ -101,8 +102,12 @@ class GpuBackend:
         the grey bytes from the host -- unless device_reuse is on.
         device_reuse: True = FrameLoop.point_reuse makes ONE call, nrs_point_reuse, on the main context: candidates, the two-level tracker on
         the pyramid this frame's klt_track built, the 5.99 gate and the append of the new slots (include/nrs.h); no image goes anywhere.
-        False (the default) = the two-context path: host projection, reuse_track_archived on ctx_reuse, insert_archived."""
+        False (the default) = the two-context path: host projection, reuse_track_archived on ctx_reuse, insert_archived.
+        device_tbuf: True = the loop's TemporalBuffer is the resident one of the main context (include/nrs.h nrs_tbuf): a frame enters
+        with one upload (tbuf_insert) and frame mapping reads it in place (map_frame_resident), which hands keypoint ids back.
+        False (the default) = nrs_frame_loop.TemporalBuffer on the host, flattened and uploaded whole by every map_frame."""
         self.nrs = nrs
+        self.device_tbuf, self.tb = bool(device_tbuf), None
         self.dense, self.cap, self.rg = dense_graph or n_nodes > 0, cap_per_point, None
         self.n_nodes, self.node_flag = n_nodes, None
         self.cam = nrs.make_camera(model, prm)
@@ -275,6 +280,19 @@ class GpuBackend:
     def map_frame(self, tb, deform_mag, rad_per_pixel, rigidity_th=0.004, min_track=5):
         return self.ctx.map_frame(self.cam, tb, deform_mag, rad_per_pixel, rigidity_th, min_track, -1)
 
+    # ---- the same on the resident TemporalBuffer (device_tbuf=True; include/nrs.h "The resident TemporalBuffer")
+    def tbuf_reset(self, max_buffer_size=20):
+        if self.tb is not None:
+            self.tb.close()
+        self.tb = self.nrs.TBuf(self.ctx, max_buffer_size)
+
+    def tbuf_insert(self, kp_id, kp, pos, status, pose, deform_mag):
+        self.tb.insert(kp_id, kp, pos, status, np.concatenate([pose[0], pose[1]]).astype(F32), deform_mag)
+
+    def map_frame_resident(self, rad_per_pixel, rigidity_th=0.004, min_track=5):
+        """map_frame's dict; `cand` and `accepted_ids` are keypoint ids"""
+        return self.tb.map_frame(self.cam, rad_per_pixel, rigidity_th, min_track, -1)
+
     # ---- keyframe mapping: LocalDeformableBundleAdjustment on the resident graph (include/nrs.h nrs_dba_solve_window_rg; in the
     # embedded-deformation mode nrs_dba_solve_window_rg_embedded with the sequence's node set: lm_xyz is then per observation -- node
     # copies optimised, skinned observations at their skinned position, observations bound to no node unchanged)
@@ -343,6 +361,8 @@ class GpuBackend:
     def close(self):
         if self.rg is not None:
             self.rg.close()
+        if self.tb is not None:
+            self.tb.close()
         if getattr(self, "ctx_stereo", None) is not None:
             self.ctx_stereo.close()
         self.ctx.close()
@@ -527,7 +547,12 @@ class FrameLoop:
             # keyframes unmapped (tracking.cc:194-195) and its own DoMapping call takes one (map.cc:62-72), so one is left for the first frame
             self.kp_id = np.arange(n, dtype=np.int64)
             self.next_kp_id = n
-            self.tbuf = TemporalBuffer(max_buffer_size)
+            self.dev_tbuf = bool(getattr(backend, "device_tbuf", False))     # the backend holds the buffer on the device
+            if self.dev_tbuf:
+                self.tbuf = None
+                backend.tbuf_reset(max_buffer_size)
+            else:
+                self.tbuf = TemporalBuffer(max_buffer_size)
             self.unmapped_keyframes = 1
             self.deform_median = 0.0
         # current frame: slot i observes map point map_index[i]
@@ -643,7 +668,10 @@ class FrameLoop:
                              status_by_map=self._status_by_map(), pos_by_map=self._pos_by_map()))
         if self.mapping and n3d >= 10:
             # Map::SetLastFrame (tracking.cc:105, map.cc:106-118), then System::TrackImage's DoMapping (SLAM/system.cc:128)
-            self.tbuf.insert(self.kp_id, self.kp, self.pos, self.status, self.pose[0], self.pose[1], self.deform_median)
+            if self.dev_tbuf:
+                self.b.tbuf_insert(self.kp_id, self.kp, self.pos, self.status, self.pose, self.deform_median)
+            else:
+                self.tbuf.insert(self.kp_id, self.kp, self.pos, self.status, self.pose[0], self.pose[1], self.deform_median)
             self.log[-1]["mapping"] = self.do_mapping(kf)
             self.log[-1]["map_size"] = len(self.map_pos)
             self.log[-1]["status_after_mapping"] = self._status_by_map()
@@ -717,9 +745,13 @@ class FrameLoop:
 
     # ---- Mapping::LandmarkTriangulation (mapping.cc:65-257) on the backend's one call
     def frame_mapping(self):
-        tb, mag, ids = self.tbuf.flat(self.camera[0], self.camera[1])
-        r = self.b.map_frame(tb, mag, self.rpp, self.rigidity_th, 5)
-        acc = ids[np.asarray(r["accepted_ids"], np.int64)]         # keypoint ids, ascending (the order of the candidates)
+        if self.dev_tbuf:
+            r = self.b.map_frame_resident(self.rpp, self.rigidity_th, 5)
+            acc = np.asarray(r["accepted_ids"], np.int64)          # keypoint ids already: the device translated the rows
+        else:
+            tb, mag, ids = self.tbuf.flat(self.camera[0], self.camera[1])
+            r = self.b.map_frame(tb, mag, self.rpp, self.rigidity_th, 5)
+            acc = ids[np.asarray(r["accepted_ids"], np.int64)]     # keypoint ids, ascending (the order of the candidates)
         out = dict(skipped=None, triangulated=[int(i) for i in acc], mode=int(r["mode"]), n_rigid=int(r["n_rigid"]),
                    n_deformable=int(r["n_deformable"]), n_candidates=len(r["cand"]))
         if not len(acc):
