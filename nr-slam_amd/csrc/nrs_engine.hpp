@@ -14,6 +14,7 @@
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
 #include "nrs_engine_consts.hpp"      // RF_* bits, SK_MAX
+#include "nrs_rgraph.hpp"             // the resident graph behind the _rg windows and a2
 
 namespace nrs {
 
@@ -85,12 +86,7 @@ int engine_build_edges_device(nrs_ctx* c, int n_kf, const int* kf_rowptr, const 
                               const int* nbr_col, const float* nbr_w, const float* nbr_d0, const int* nbr_status, DevEdges* out);
 // The same construction served by the device-resident all-pairs graph (include/nrs.h nrs_dba_solve_window_rg): GetEdges of the window's
 // distinct points at a prefix length that is doubled until no walk runs off its prefix.  stats: distinct points, final prefix length,
-// GetEdges rounds, walks that ran off in round 1.  The pieces of nrs_rgraph.hip it stands on:
-struct RgDeviceLists { int n_rows, stride; const int *count, *col, *status; const float *w, *d0; };
-int rg_capacity(const nrs_rgraph* g);
-int rg_max_cap_per_point(const nrs_rgraph* g);
-nrs_ctx* rg_context(const nrs_rgraph* g);
-int rg_get_edges_device(nrs_rgraph* g, int32_t n_ids, const int32_t* d_ids, int32_t cap_per_point, RgDeviceLists* o);
+// GetEdges rounds, walks that ran off in round 1.  It stands on nrs_rgraph.hpp.
 int engine_build_edges_device_rg(nrs_ctx* c, int n_kf, const int* kf_rowptr, const int* kf_pt, const int* lm_kf, nrs_rgraph* g, int cap_per_point,
                                  DevEdges* out, int64_t stats[4]);
 // what nrs_dba_solve_window_rg leaves next to the resident window (dropped by dba_free): its statistics and, when the window took the

@@ -22,41 +22,80 @@
 #include <new>
 #include <vector>
 #include "nrs_ctx.hpp"
+#include "nrs_rgraph_host.hpp"
 
-struct nrs_rgraph {
+namespace nrs {
+__global__ void k_rg_fill(uint8_t* st, size_t n);
+
+// The dense state: four capacity x capacity arrays, held all or not at all
+struct RgDense {
+    float *maxd = nullptr, *mind = nullptr, *d0 = nullptr;
+    uint8_t* st = nullptr;
+    // the four arrays and, enqueued on `s`, the "no edge" fill of the status.  On failure nothing is held; *filling: the arrays were
+    // there and the fill's launch failed
+    hipError_t alloc(int cap, hipStream_t s, bool* filling) {
+        const size_t n2 = (size_t)cap * cap;
+        *filling = false;
+        hipError_t e = hipMalloc((void**)&maxd, n2 * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&mind, n2 * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&d0, n2 * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&st, n2);
+        if (e == hipSuccess) {
+            *filling = true;
+            hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, st, n2);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) free();
+        return e;
+    }
+    void free() {
+        for (void* p : {(void*)maxd, (void*)mind, (void*)d0, (void*)st}) if (p) (void)hipFree(p);
+        *this = RgDense();
+    }
+};
+}  // namespace nrs
+
+struct nrs_rgraph : nrs::RgDense {
     nrs_ctx* c = nullptr;
     int cap = 0;
     float sigma = 1.f, stretch_th = 1.1f, min_w = 0.f;
-    float *maxd = nullptr, *mind = nullptr, *d0 = nullptr;
-    uint8_t* st = nullptr;
-    nrs::DevBuf pos, ids_a, ids_b, out_i, out_f, good, skip, slot, walk;   // (walk: the device-side neighbour walk of a2, rg_walk)
+    nrs::DevBuf pos, ids_a, ids_b, out_i, good, skip, slot, walk;   // (walk: the device-side neighbour walk of a2, rg_walk)
     nrs::DevBuf mir;                 // status + longest distance once more as FULL matrices (k_rg_mirror), for GetEdges over many rows
+    void release_bufs() { for (nrs::DevBuf* b : {&pos, &ids_a, &ids_b, &out_i, &good, &skip, &slot, &walk, &mir}) c->release(*b); }
     int last_n_ids = 0, last_cap = 0;  // shape of the lists out_i holds (the last GetEdges)
     std::vector<int> h_slot;
     char* pin = nullptr;             // pinned staging area of the GetEdges results (page-faulting pageable targets cost more than the kernel)
     size_t pin_cap = 0;
+    void set_sigma(float s) { sigma = s; min_w = nrs::rg_min_weight(s); }
+    nrs::RgDense& dense() { return *this; }
 };
 
 namespace nrs {
 
-struct RgDeviceLists { int n_rows, stride; const int *count, *col, *status; const float *w, *d0; };   // (declared in nrs_engine.hpp as well)
-
 constexpr uint8_t RG_NONE = 0xFF;
-
-// InterpolationWeight (utilities/geometry_toolbox.cc:26-28): float argument, exp evaluated in double and rounded
-// to float (the definition shared with the oracle and nrs_track.hip, DESIGN.md "weights")
-__host__ __device__ inline float rg_weight(float d, float sigma) {
-#pragma clang fp contract(off)
-    const float arg = -(d * d) / (2.0f * sigma * sigma);
-    return (float)exp((double)arg);
-}
 
 __device__ inline size_t rg_at(int i, int j, int cap) { return i < j ? (size_t)i * cap + j : (size_t)j * cap + i; }
 
-__device__ inline float rg_dist(const float* __restrict__ pos, int i, int j) {
+// the distance of a pair, the one every kernel forms: symmetric to the last bit
+__device__ inline float rg_dist(float ax, float ay, float az, float bx, float by, float bz) {
 #pragma clang fp contract(off)
-    const float dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
+    const float dx = ax - bx, dy = ay - by, dz = az - bz;
     return sqrtf(dx * dx + dy * dy + dz * dz);
+}
+__device__ inline float rg_dist(const float* __restrict__ pos, int i, int j) {
+    return rg_dist(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2]);
+}
+
+// UpdateConnection (regularization_graph.cc:89-128) of the stored pair k at the current distance d: longest / shortest distance, the
+// stretch test, BAD where it fails.  true: the connection passes (UpdateVertex counts it)
+__device__ inline bool rg_update_connection(float d, size_t k, float* maxd, float* mind, uint8_t* st, float stretch_th) {
+#pragma clang fp contract(off)
+    float mx = maxd[k], mn = mind[k];
+    if (d > mx) mx = d;
+    if (d < mn) mn = d;
+    maxd[k] = mx; mind[k] = mn;
+    if (fabsf((mx - mn) / mn) > stretch_th) { st[k] = (uint8_t)NRS_GRAPH_BAD; return false; }
+    return true;
 }
 
 // AddEdge (regularization_graph.cc:38-55) for every (new, other) pair, new != other: a fresh NEUTRAL edge whose
@@ -84,13 +123,7 @@ __global__ __launch_bounds__(256) void k_rg_update(int n_ids, const int* __restr
         if (j == i) continue;
         const size_t k = rg_at(i, j, cap);
         if (st[k] == RG_NONE) continue;
-        const float d = rg_dist(pos, i, j);
-        float mx = maxd[k], mn = mind[k];
-        if (d > mx) mx = d;
-        if (d < mn) mn = d;
-        maxd[k] = mx; mind[k] = mn;
-        if (fabsf((mx - mn) / mn) > stretch_th) st[k] = (uint8_t)NRS_GRAPH_BAD;
-        else ++n_good;
+        if (rg_update_connection(rg_dist(pos, i, j), k, maxd, mind, st, stretch_th)) ++n_good;
     }
     for (int off = 32; off > 0; off >>= 1) n_good += __shfl_xor(n_good, off, 64);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n_good;
@@ -129,16 +162,7 @@ __global__ __launch_bounds__(RG_TC) void k_rg_update_tri(const int* __restrict__
         bool pass = false;
         if (jin && j > r && (ur >= 0 || uj >= 0)) {
             const size_t k = (size_t)r * cap + j;
-            if (st[k] != RG_NONE) {
-                const float dx = rpos[rr][0] - px, dy = rpos[rr][1] - py, dz = rpos[rr][2] - pz;
-                const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-                float mx = maxd[k], mn = mind[k];
-                if (d > mx) mx = d;
-                if (d < mn) mn = d;
-                maxd[k] = mx; mind[k] = mn;
-                if (fabsf((mx - mn) / mn) > stretch_th) st[k] = (uint8_t)NRS_GRAPH_BAD;
-                else pass = true;
-            }
+            if (st[k] != RG_NONE) pass = rg_update_connection(rg_dist(rpos[rr][0], rpos[rr][1], rpos[rr][2], px, py, pz), k, maxd, mind, st, stretch_th);
         }
         if (pass && uj >= 0) ++ccnt;
         if (ur >= 0) {                                              // (block-uniform)
@@ -187,7 +211,6 @@ __global__ __launch_bounds__(256) void k_rg_mirror(int cap, const uint8_t* __res
 
 constexpr int RG_BINS = 256;     // weight histogram bins per status class (selection of the first out_cap entries)
 constexpr int RG_CLASSES = 4;    // NRS_GRAPH_VERIFIED .. NRS_GRAPH_BAD
-constexpr int RG_SLACK = 1024;   // candidates staged beyond out_cap (the population of the bin the cut falls into)
 
 // Only the first out_cap entries of the list are wanted (the callers walk a prefix), and with the reference's sigma most
 // of the N - 1 connections survive the min_weight cut.  So the row is read twice: pass 1 finds s* and a 256-bin histogram
@@ -326,11 +349,18 @@ __global__ void k_rg_fill(uint8_t* st, size_t n) {
     if (i < n) st[i] = RG_NONE;
 }
 
-static int rg_check_ids(nrs_rgraph* g, int n, const int32_t* ids, const char* what) {
-    if (n < 0 || (n > 0 && !ids)) return g->c->fail(NRS_ERR_INVALID, "%s: null / negative id list", what);
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 0 || ids[i] >= g->cap) return g->c->fail(NRS_ERR_INVALID, "%s: point index %d outside [0, %d)", what, ids[i], g->cap);
-    return NRS_OK;
+// a check of nrs_rgraph_host.hpp (0, or the refusal in msg) as an entry point's return value
+static int rg_refused(nrs_ctx* c, int rc, const char* msg) { return rc == 0 ? NRS_OK : c->fail(NRS_ERR_INVALID, "%s", msg); }
+
+// the four arrays of a graph of `cap` points with the fill enqueued, or the failure in the name of `who` with nothing held
+static int rg_alloc_dense(nrs_ctx* c, RgDense* d, int cap, const char* who) {
+    bool filling = false;
+    const hipError_t e = d->alloc(cap, c->stream, &filling);
+    if (e == hipSuccess) return NRS_OK;
+    if (filling) return c->fail(NRS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    const int rc = c->fail(NRS_ERR_ALLOC, "%s: %zu bytes for %d points: %s", who, (size_t)cap * cap * 13, cap, hipGetErrorString(e));
+    (void)hipGetLastError();
+    return rc;
 }
 
 }  // namespace nrs
@@ -340,29 +370,19 @@ using namespace nrs;
 extern "C" int nrs_rgraph_create(nrs_ctx* c, int32_t capacity, float sigma, float stretch_th, nrs_rgraph** out) {
     if (!c || !out) return NRS_ERR_INVALID;
     *out = nullptr;
-    if (capacity <= 1 || capacity > 200000 || !(sigma > 0) || !(stretch_th > 0)) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_create: bad argument");
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_create(capacity, sigma, stretch_th, msg, sizeof(msg)), msg));
     NRS_HIP(c, hipSetDevice(c->device));
     nrs_rgraph* g = new (std::nothrow) nrs_rgraph();
     if (!g) return c->fail(NRS_ERR_ALLOC, "out of host memory");
     g->c = c; g->cap = capacity; g->stretch_th = stretch_th;
-    g->sigma = sigma;
-    g->min_w = rg_weight((float)((double)sigma * 1.5), sigma);          // regularization_graph.cc:29 (float * double literal -> float argument)
-    const size_t n2 = (size_t)capacity * capacity;
-    hipError_t e = hipMalloc((void**)&g->maxd, n2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->mind, n2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d0, n2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->st, n2);
-    if (e != hipSuccess) {
-        const int rc = c->fail(NRS_ERR_ALLOC, "nrs_rgraph_create: %zu bytes for %d points: %s", n2 * 13, capacity, hipGetErrorString(e));
-        if (g->maxd) (void)hipFree(g->maxd);
-        if (g->mind) (void)hipFree(g->mind);
-        if (g->d0) (void)hipFree(g->d0);
-        delete g;
-        return rc;
+    g->set_sigma(sigma);
+    int rc = rg_alloc_dense(c, g, capacity, "nrs_rgraph_create");
+    if (rc == NRS_OK) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { rc = c->fail(NRS_ERR_HIP, "nrs_rgraph_create: %s", hipGetErrorString(e)); g->free(); }
     }
-    hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, c->stream, g->st, n2);
-    NRS_HIP(c, hipGetLastError());
-    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (rc != NRS_OK) { delete g; return rc; }                     // (nothing is held: neither the arrays nor the object)
     *out = g;
     return NRS_OK;
 }
@@ -372,17 +392,16 @@ extern "C" void nrs_rgraph_destroy(nrs_rgraph* g) {
     nrs_ctx* c = g->c;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(g->maxd); (void)hipFree(g->mind); (void)hipFree(g->d0); (void)hipFree(g->st);
+    g->free();
     if (g->pin) (void)hipHostFree(g->pin);
-    c->release(g->pos); c->release(g->ids_a); c->release(g->ids_b); c->release(g->out_i); c->release(g->out_f); c->release(g->good); c->release(g->skip); c->release(g->slot); c->release(g->walk); c->release(g->mir);
+    g->release_bufs();
     delete g;
 }
 
 extern "C" int nrs_rgraph_set_sigma(nrs_rgraph* g, float sigma) {
     if (!g) return NRS_ERR_INVALID;
     if (!(sigma > 0)) return g->c->fail(NRS_ERR_INVALID, "sigma must be positive");
-    g->sigma = sigma;
-    g->min_w = rg_weight((float)((double)sigma * 1.5), sigma);          // RegularizationGraph::SetSigma (:33-36)
+    g->set_sigma(sigma);
     return NRS_OK;
 }
 
@@ -393,8 +412,9 @@ extern "C" int nrs_rgraph_add_edges(nrs_rgraph* g, const float* pos, int32_t n_n
     if (!g) return NRS_ERR_INVALID;
     nrs_ctx* c = g->c;
     if (!pos) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_add_edges: null positions");
-    NRS_TRY(rg_check_ids(g, n_new, new_ids, "nrs_rgraph_add_edges"));
-    NRS_TRY(rg_check_ids(g, n_other, other_ids, "nrs_rgraph_add_edges"));
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_ids(g->cap, n_new, new_ids, "nrs_rgraph_add_edges", msg, sizeof(msg)), msg));
+    NRS_TRY(rg_refused(c, rg_check_ids(g->cap, n_other, other_ids, "nrs_rgraph_add_edges", msg, sizeof(msg)), msg));
     if (n_new == 0 || n_other == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
     NRS_TRY(c->ensure(g->pos, sizeof(float) * 3 * (size_t)g->cap));
@@ -417,7 +437,8 @@ extern "C" int nrs_rgraph_update(nrs_rgraph* g, const float* pos, int32_t n_ids,
     if (!g) return NRS_ERR_INVALID;
     nrs_ctx* c = g->c;
     if (!pos || (n_ids > 0 && !good_count)) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_update: null argument");
-    NRS_TRY(rg_check_ids(g, n_ids, ids, "nrs_rgraph_update"));
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_ids(g->cap, n_ids, ids, "nrs_rgraph_update", msg, sizeof(msg)), msg));
     if (n_ids == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
     NRS_TRY(c->ensure(g->pos, sizeof(float) * 3 * (size_t)g->cap));
@@ -426,12 +447,7 @@ extern "C" int nrs_rgraph_update(nrs_rgraph* g, const float* pos, int32_t n_ids,
     NRS_HIP(c, hipMemcpyAsync(g->pos.p, pos, sizeof(float) * 3 * (size_t)g->cap, hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipMemcpyAsync(g->ids_a.p, ids, sizeof(int) * (size_t)n_ids, hipMemcpyHostToDevice, c->stream));
     NRS_HIP(c, hipMemsetAsync(g->good.p, 0, sizeof(int) * (size_t)n_ids, c->stream));
-    // most of the points listed, each once: the one-pass form
-    bool tri = (size_t)n_ids * 4 >= (size_t)g->cap;
-    if (tri) {
-        g->h_slot.assign(g->cap, -1);
-        for (int a = 0; a < n_ids && tri; ++a) { if (g->h_slot[ids[a]] >= 0) tri = false; g->h_slot[ids[a]] = a; }
-    }
+    const bool tri = rg_update_one_pass(g->cap, n_ids, ids, g->h_slot);
     if (tri) {
         NRS_TRY(c->ensure(g->slot, sizeof(int) * (size_t)g->cap));
         NRS_HIP(c, hipMemcpyAsync(g->slot.p, g->h_slot.data(), sizeof(int) * (size_t)g->cap, hipMemcpyHostToDevice, c->stream));
@@ -450,19 +466,14 @@ extern "C" int nrs_rgraph_update(nrs_rgraph* g, const float* pos, int32_t n_ids,
     return NRS_OK;
 }
 
-// GetEdges of the listed points into the graph's pinned staging area: count[n_ids] | col | status | weight | first distance
-// (each n_ids x cap_per_point).  nrs_rgraph_get_edges copies from there; the a2 driver reads it in place.
 namespace nrs {
 int rg_capacity(const nrs_rgraph* g) { return g->cap; }
-// the longest GetEdges prefix a call can ask for: the candidates of a row are sorted in LDS
+nrs_ctx* rg_context(const nrs_rgraph* g) { return g->c; }
 int rg_max_cap_per_point(const nrs_rgraph* g) {
     int lds_max = 65536;
     (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, g->c->device);
-    size_t cand_max = 512;
-    while (sizeof(unsigned long long) * (cand_max << 1) + 4096 + 512 <= (size_t)lds_max) cand_max <<= 1;
-    int lim = std::min(g->cap, (int)cand_max - RG_SLACK);
-    if (g->c->dbg.is_set(SW_RG_MAX_CAP)) lim = std::max(1, std::min(lim, g->c->dbg.int_of(SW_RG_MAX_CAP)));   // (a lower limit, so that the tests reach the callers' "ran off at the limit" refusal)
-    return lim;
+    const DebugOpts& dbg = g->c->dbg;
+    return rg_cap_limit(g->cap, rg_cand_limit((size_t)lds_max), dbg.is_set(SW_RG_MAX_CAP), dbg.int_of(SW_RG_MAX_CAP));
 }
 
 // ---- a2's neighbour walk on the device (OPT:252-279 as nrs_track.hip's host loop restates it): optimised point idx (rows of the last
@@ -473,7 +484,6 @@ int rg_max_cap_per_point(const nrs_rgraph* g) {
 // entries at a time) and is repeated until a pass changes nothing (a pass without a change is a fixed point; correct sets never change
 // again, so the passes needed are the longest chain of dependent points + 1).  The last pass (final = 1) also leaves weights, first
 // distances, the lost-point flags of the entries the walk visits and whether it ended before its list did.
-constexpr int RG_WALK_MAX = 11;
 __global__ __launch_bounds__(256) void k_rg_walk(int n, int cap, const int* __restrict__ cnt, const int* __restrict__ col, const int* __restrict__ st,
                                                  const float* __restrict__ w, const float* __restrict__ d0, const int* __restrict__ code,
                                                  const uint8_t* __restrict__ is_node, int* acc, int* n_acc, float* acc_w, float* acc_d0,
@@ -526,38 +536,28 @@ __global__ __launch_bounds__(256) void k_rg_walk(int n, int cap, const int* __re
     }
 }
 
-// The walk over the lists of the last rg_get_edges_staged(.., lists_to_host = false) call.  code: n_map ints (nrs_track.hip walk_code);
-// is_node: one byte per row or null (every optimised point a vertex).  Outputs (host): n_acc[n], acc[11 n] (indices among the optimised
-// points), acc_w / acc_d0[11 n], ended[n], lost[n_map].  *converged = 0: the passes ran out (the caller walks on the host instead).
+// (nrs_rgraph.hpp) the passes over the lists the last GetEdges left on the device, in the scratch of RgWalkPlan
 int rg_walk(nrs_rgraph* g, int n_map, const int* code, const uint8_t* is_node, int* n_acc, int* acc, float* acc_w, float* acc_d0,
             uint8_t* ended, uint8_t* lost, int* converged, int* passes) {
     nrs_ctx* c = g->c;
     const int n = g->last_n_ids, cap = g->last_cap;
     *converged = 0; *passes = 0;
     if (n <= 0 || n_map > g->cap) return c->fail(NRS_ERR_STATE, "rg_walk: no lists on the device");
-    const size_t no = (size_t)n * cap;
-    const int* d_cnt = g->out_i.as<int>();
-    const int* d_col = d_cnt + n;
-    const int* d_st = d_col + no;
-    const float* d_w = reinterpret_cast<const float*>(d_st + no);
-    const float* d_d0 = d_w + no;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    constexpr int MAXP = 96;
-    const size_t o_code = 0, o_node = o_code + al(4 * (size_t)n_map), o_acc = o_node + al((size_t)n), o_nacc = o_acc + al(4 * (size_t)RG_WALK_MAX * n),
-                 o_w = o_nacc + al(4 * (size_t)n), o_d0 = o_w + al(4 * (size_t)RG_WALK_MAX * n), o_end = o_d0 + al(4 * (size_t)RG_WALK_MAX * n),
-                 o_lost = o_end + al((size_t)n), o_chg = o_lost + al((size_t)n_map), total = o_chg + al(4 * (MAXP + 1));
-    NRS_TRY(c->ensure(g->walk, total));
+    const RgDeviceLists L = RgListLayout(n, cap).view(g->out_i.p);
+    constexpr int MAXP = RG_WALK_PASSES;
+    const RgWalkPlan P((size_t)n_map, (size_t)n);
+    NRS_TRY(c->ensure(g->walk, P.total));
     char* b = g->walk.as<char>();
-    NRS_HIP(c, hipMemcpyAsync(b + o_code, code, 4 * (size_t)n_map, hipMemcpyHostToDevice, c->stream));
-    if (is_node) NRS_HIP(c, hipMemcpyAsync(b + o_node, is_node, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    NRS_HIP(c, hipMemsetAsync(b + o_nacc, 0, 4 * (size_t)n, c->stream));
-    NRS_HIP(c, hipMemsetAsync(b + o_lost, 0, o_chg - o_lost + 4 * (MAXP + 1), c->stream));
-    int* chg = reinterpret_cast<int*>(b + o_chg);
+    NRS_HIP(c, hipMemcpyAsync(b + P.code, code, 4 * (size_t)n_map, hipMemcpyHostToDevice, c->stream));
+    if (is_node) NRS_HIP(c, hipMemcpyAsync(b + P.node, is_node, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipMemsetAsync(b + P.n_acc, 0, 4 * (size_t)n, c->stream));
+    NRS_HIP(c, hipMemsetAsync(b + P.lost, 0, P.zero_bytes, c->stream));
+    int* chg = reinterpret_cast<int*>(b + P.changed);
     auto pass = [&](int slot, int final) {
-        hipLaunchKernelGGL(k_rg_walk, dim3((n + 3) / 4), dim3(256), 0, c->stream, n, cap, d_cnt, d_col, d_st, d_w, d_d0, reinterpret_cast<const int*>(b + o_code),
-                           is_node ? reinterpret_cast<const uint8_t*>(b + o_node) : nullptr, reinterpret_cast<int*>(b + o_acc), reinterpret_cast<int*>(b + o_nacc),
-                           reinterpret_cast<float*>(b + o_w), reinterpret_cast<float*>(b + o_d0), reinterpret_cast<uint8_t*>(b + o_end),
-                           reinterpret_cast<uint8_t*>(b + o_lost), chg + slot, final);
+        hipLaunchKernelGGL(k_rg_walk, dim3((n + 3) / 4), dim3(256), 0, c->stream, n, cap, L.count, L.col, L.status, L.w, L.d0, reinterpret_cast<const int*>(b + P.code),
+                           is_node ? reinterpret_cast<const uint8_t*>(b + P.node) : nullptr, reinterpret_cast<int*>(b + P.acc), reinterpret_cast<int*>(b + P.n_acc),
+                           reinterpret_cast<float*>(b + P.w), reinterpret_cast<float*>(b + P.d0), reinterpret_cast<uint8_t*>(b + P.ended),
+                           reinterpret_cast<uint8_t*>(b + P.lost), chg + slot, final);
     };
     int done = 0, hc[MAXP];
     int max_p = MAXP;                                              // (NRS_WALK_MAX_PASSES: a lower cap, so that the tests reach the caller's host fallback)
@@ -575,12 +575,12 @@ int rg_walk(nrs_rgraph* g, int n_map, const int* code, const uint8_t* is_node, i
     if (!*converged) return NRS_OK;
     pass(MAXP, 1);                                                 // (the sets are final: this pass changes nothing and leaves the outputs)
     NRS_HIP(c, hipGetLastError());
-    NRS_HIP(c, hipMemcpyAsync(n_acc, b + o_nacc, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(acc, b + o_acc, 4 * (size_t)RG_WALK_MAX * n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(acc_w, b + o_w, 4 * (size_t)RG_WALK_MAX * n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(acc_d0, b + o_d0, 4 * (size_t)RG_WALK_MAX * n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(ended, b + o_end, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipMemcpyAsync(lost, b + o_lost, (size_t)n_map, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(n_acc, b + P.n_acc, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(acc, b + P.acc, 4 * (size_t)RG_WALK_MAX * n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(acc_w, b + P.w, 4 * (size_t)RG_WALK_MAX * n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(acc_d0, b + P.d0, 4 * (size_t)RG_WALK_MAX * n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(ended, b + P.ended, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(lost, b + P.lost, (size_t)n_map, hipMemcpyDeviceToHost, c->stream));
     int last = 0;
     NRS_HIP(c, hipMemcpyAsync(&last, chg + MAXP, 4, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
@@ -588,131 +588,139 @@ int rg_walk(nrs_rgraph* g, int n_map, const int* code, const uint8_t* is_node, i
     return NRS_OK;
 }
 
-// d_ids: the ids are on the device already (n_ids ints, each in [0, capacity): the caller's kernels made them) and `ids` is not read
-static int rg_get_edges_impl(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, const int32_t* d_ids, int32_t cap_per_point, const int** count, const int** col,
-                             const int** status, const float** w, const float** d0, const uint8_t* pass_over, bool lists_to_host) {   // lists_to_host = false: the lists stay on the device (rg_walk reads them there); only the counts come back
+// ---- GetEdges of the listed points, stage by stage.  d_ids: the ids are on the device already (n_ids ints, each in [0, capacity): the
+// caller's kernels made them) and `ids` is not read.  lists_to_host = false: the lists stay on the device; only the counts come back
+struct RgGetEdges { int32_t n_ids; const int32_t* ids; const int32_t* d_ids; int32_t cap_per_point; const uint8_t* pass_over; bool lists_to_host; };
+
+// the arguments (also the a2 driver's entry: ids index the dense state), and that a row's candidates fit this device's LDS
+static int rg_ge_check(nrs_rgraph* g, const RgGetEdges& a, size_t* cand_limit) {
     nrs_ctx* c = g->c;
-    if (d_ids) { if (n_ids <= 0 || n_ids > g->cap) return c->fail(NRS_ERR_INVALID, "GetEdges: %d device-side ids for %d points", n_ids, g->cap); }
-    else NRS_TRY(rg_check_ids(g, n_ids, ids, "GetEdges"));          // (also the a2 driver's entry: ids index the dense state)
-    if (cap_per_point <= 0) return c->fail(NRS_ERR_INVALID, "GetEdges: cap_per_point must be positive");
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_get_edges(g->cap, a.n_ids, a.ids, a.d_ids != nullptr, a.cap_per_point, msg, sizeof(msg)), msg));
     NRS_HIP(c, hipSetDevice(c->device));
-    // the sort buffer of a row lives in LDS: 8 bytes per staged candidate (a power of two of them) + 4 KB of histogram
     int lds_max = 0;
     NRS_HIP(c, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    size_t cand_max = 512;
-    while (sizeof(unsigned long long) * (cand_max << 1) + 4096 + 512 <= (size_t)lds_max) cand_max <<= 1;
-    if ((size_t)std::min(g->cap, cap_per_point + RG_SLACK) > cand_max)
-        return c->fail(NRS_ERR_INVALID, "GetEdges: cap_per_point %d needs more than the %zu candidates per row that fit this device's %d bytes of LDS",
-                       cap_per_point, cand_max, lds_max);
-    const size_t no = (size_t)n_ids * cap_per_point;
-    NRS_TRY(c->ensure(g->ids_a, sizeof(int) * (size_t)n_ids));
-    NRS_TRY(c->ensure(g->out_i, sizeof(int) * (4 * no + (size_t)n_ids + 4)));
-    // one device block in the staging layout: count | col | status | weight | first distance | overflow word
-    int* d_cnt = g->out_i.as<int>();
-    int* d_col = d_cnt + n_ids;
-    int* d_st = d_col + no;
-    float* d_w = reinterpret_cast<float*>(d_st + no);
-    float* d_d0 = d_w + no;
-    int* d_ovf = reinterpret_cast<int*>(d_d0 + no);
-    const size_t bytes = sizeof(int) * (4 * no + (size_t)n_ids + 1);
-    if (bytes > g->pin_cap) {
+    *cand_limit = rg_cand_limit((size_t)lds_max);
+    return rg_refused(c, rg_check_fits_lds(g->cap, a.cap_per_point, *cand_limit, lds_max, msg, sizeof(msg)), msg);
+}
+
+// the block on the device and the pinned area its copy lands in
+static int rg_ge_staging(nrs_rgraph* g, const RgListLayout& L) {
+    nrs_ctx* c = g->c;
+    NRS_TRY(c->ensure(g->ids_a, sizeof(int) * (size_t)L.n_ids));
+    NRS_TRY(c->ensure(g->out_i, L.bytes()));
+    if (L.bytes() > g->pin_cap) {
         if (g->pin) (void)hipHostFree(g->pin);
         g->pin = nullptr; g->pin_cap = 0;
-        const size_t want = bytes + bytes / 4;
+        const size_t want = L.bytes() + L.bytes() / 4;
         if (hipHostMalloc((void**)&g->pin, want, hipHostMallocDefault) != hipSuccess) return c->fail(NRS_ERR_ALLOC, "nrs_rgraph_get_edges: %zu bytes of pinned host memory", want);
         g->pin_cap = want;
     }
-    NRS_HIP(c, hipMemcpyAsync(g->ids_a.p, d_ids ? d_ids : ids, sizeof(int) * (size_t)n_ids, d_ids ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    if (pass_over) {                                               // (one byte per point of the dense state)
+    return NRS_OK;
+}
+
+static int rg_ge_upload(nrs_rgraph* g, const RgGetEdges& a) {
+    nrs_ctx* c = g->c;
+    NRS_HIP(c, hipMemcpyAsync(g->ids_a.p, a.d_ids ? a.d_ids : a.ids, sizeof(int) * (size_t)a.n_ids, a.d_ids ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (a.pass_over) {                                             // (one byte per point of the dense state)
         NRS_TRY(c->ensure(g->skip, (size_t)g->cap));
-        NRS_HIP(c, hipMemcpyAsync(g->skip.p, pass_over, (size_t)g->cap, hipMemcpyHostToDevice, c->stream));
+        NRS_HIP(c, hipMemcpyAsync(g->skip.p, a.pass_over, (size_t)g->cap, hipMemcpyHostToDevice, c->stream));
     }
-    const float d_hi = (float)((double)g->sigma * 1.5 * (1.0 + 1e-4));
-    // many rows (a2's first GetEdges of a frame: every tracked point): the kernel scans full symmetric copies of the two arrays it reads
-    const uint8_t* st_f = nullptr;
-    const float* maxd_f = nullptr;
-    if ((int64_t)n_ids * 8 >= g->cap && g->cap >= 512 && !c->dbg.is_set(SW_RG_NO_MIRROR)) {
-        const size_t cc = (size_t)g->cap * g->cap, o_m = (cc + 255) & ~(size_t)255;
-        if (c->ensure(g->mir, o_m + 4 * cc) == NRS_OK) {           // (5 bytes per pair on top of the 13 of the state)
-            const int nt = (g->cap + 63) / 64;
-            hipLaunchKernelGGL(k_rg_mirror, dim3(nt, nt), dim3(256), 0, c->stream, g->cap, g->st, g->maxd, g->mir.as<uint8_t>(), reinterpret_cast<float*>(g->mir.as<char>() + o_m));
-            NRS_HIP(c, hipGetLastError());
-            st_f = g->mir.as<uint8_t>(); maxd_f = reinterpret_cast<const float*>(g->mir.as<char>() + o_m);
-        } else {                                                   // no memory for the copies: the triangular state serves the call (slower, same lists)
-            (void)hipGetLastError();
-            c->err[0] = 0;
-        }
+    return NRS_OK;
+}
+
+// many rows (a2's first GetEdges of a frame: every tracked point): the kernel scans full symmetric copies of the two arrays it reads.
+// *st_f / *maxd_f stay null where the triangular state serves the call
+static int rg_ge_mirror(nrs_rgraph* g, int n_ids, const uint8_t** st_f, const float** maxd_f) {
+    nrs_ctx* c = g->c;
+    if (!rg_use_mirror(n_ids, g->cap, c->dbg.is_set(SW_RG_NO_MIRROR))) return NRS_OK;
+    const size_t cc = (size_t)g->cap * g->cap, o_m = (cc + 255) & ~(size_t)255;
+    if (c->ensure(g->mir, o_m + 4 * cc) != NRS_OK) {               // (5 bytes per pair on top of the 13 of the state) no memory for the copies: slower, same lists
+        (void)hipGetLastError();
+        c->err[0] = 0;
+        return NRS_OK;
     }
-    // first the selecting form (stages <= cap_per_point + one histogram bin per row); if a bin overflows the staging area
-    // (many equal distances), once more with every survivor of a row staged
+    const int nt = (g->cap + 63) / 64;
+    uint8_t* s = g->mir.as<uint8_t>();
+    float* m = reinterpret_cast<float*>(g->mir.as<char>() + o_m);
+    hipLaunchKernelGGL(k_rg_mirror, dim3(nt, nt), dim3(256), 0, c->stream, g->cap, g->st, g->maxd, s, m);
+    NRS_HIP(c, hipGetLastError());
+    *st_f = s; *maxd_f = m;
+    return NRS_OK;
+}
+
+// first the selecting form (stages <= cap_per_point + one histogram bin per row); if a bin overflows the staging area (many equal
+// distances), once more with every survivor of a row staged.  Each pass ends with its copy back and a look at the overflow word
+static int rg_ge_passes(nrs_rgraph* g, const RgGetEdges& a, const RgListLayout& L, size_t cand_limit, const uint8_t* st_f, const float* maxd_f) {
+    nrs_ctx* c = g->c;
+    int* d = g->out_i.as<int>();
     int* h = reinterpret_cast<int*>(g->pin);
-    int cand_cap = 0;
+    const float d_hi = rg_far_distance(g->sigma);
+    g->last_n_ids = 0; g->last_cap = 0;                            // (the lists out_i held are overwritten from here on)
     for (int pass = 0; pass < 2; ++pass) {
-        cand_cap = pass == 0 ? std::min(g->cap, cap_per_point + RG_SLACK) : (int)std::min<size_t>({(size_t)g->cap, (size_t)12000, cand_max});
-        NRS_HIP(c, hipMemsetAsync(d_ovf, 0, sizeof(int), c->stream));
-        size_t pad = 512;                                          // the long-list path sorts a power-of-two number of keys
-        while (pad < (size_t)cand_cap) pad <<= 1;
-        const size_t shm = sizeof(unsigned long long) * pad;
-        NRS_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rg_get_edges), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        hipLaunchKernelGGL(k_rg_get_edges, dim3(n_ids), dim3(64), shm, c->stream, n_ids, g->ids_a.as<int>(), g->cap,
-                           g->maxd, g->d0, g->st, g->sigma, g->min_w, d_hi, cand_cap, cap_per_point, pass, pass_over ? g->skip.as<uint8_t>() : nullptr, d_cnt, d_col, d_w, d_d0, d_st, d_ovf, st_f, maxd_f);
+        const RgPass p = rg_pass_plan(pass, g->cap, a.cap_per_point, cand_limit);
+        NRS_HIP(c, hipMemsetAsync(d + L.overflow, 0, sizeof(int), c->stream));
+        NRS_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rg_get_edges), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+        hipLaunchKernelGGL(k_rg_get_edges, dim3(a.n_ids), dim3(64), p.lds_bytes, c->stream, a.n_ids, g->ids_a.as<int>(), g->cap, g->maxd, g->d0, g->st, g->sigma,
+                           g->min_w, d_hi, p.cand_cap, a.cap_per_point, pass, a.pass_over ? g->skip.as<uint8_t>() : nullptr, d, d + L.col,
+                           reinterpret_cast<float*>(d + L.w), reinterpret_cast<float*>(d + L.d0), d + L.status, d + L.overflow, st_f, maxd_f);
         NRS_HIP(c, hipGetLastError());
-        if (lists_to_host) NRS_HIP(c, hipMemcpyAsync(h, d_cnt, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (a.lists_to_host) NRS_HIP(c, hipMemcpyAsync(h, d, L.bytes(), hipMemcpyDeviceToHost, c->stream));
         else {
-            NRS_HIP(c, hipMemcpyAsync(h, d_cnt, sizeof(int) * (size_t)n_ids, hipMemcpyDeviceToHost, c->stream));
-            NRS_HIP(c, hipMemcpyAsync(h + 4 * no + (size_t)n_ids, d_ovf, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            NRS_HIP(c, hipMemcpyAsync(h, d, sizeof(int) * (size_t)a.n_ids, hipMemcpyDeviceToHost, c->stream));
+            NRS_HIP(c, hipMemcpyAsync(h + L.overflow, d + L.overflow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         }
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        g->last_n_ids = n_ids; g->last_cap = cap_per_point;
-        if (h[4 * no + (size_t)n_ids] == 0) break;
-        if (pass == 1) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_get_edges: a point has %d connections at or above min_weight: more than this build stages per row (%d)", h[4 * no + (size_t)n_ids], cand_cap);
+        if (h[L.overflow] == 0) {
+            g->last_n_ids = a.n_ids; g->last_cap = a.cap_per_point;
+            return NRS_OK;
+        }
+        if (pass == 1) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_get_edges: a point has %d connections at or above min_weight: more than this build stages per row (%d)", h[L.overflow], p.cand_cap);
     }
-    *count = h;
-    *col = h + n_ids;
-    *status = h + n_ids + no;
-    *w = reinterpret_cast<const float*>(h + n_ids + 2 * no);
-    *d0 = reinterpret_cast<const float*>(h + n_ids + 3 * no);
     return NRS_OK;
 }
-int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, const int** count, const int** col,
-                        const int** status, const float** w, const float** d0, const uint8_t* pass_over, bool lists_to_host) {
-    return rg_get_edges_impl(g, n_ids, ids, nullptr, cap_per_point, count, col, status, w, d0, pass_over, lists_to_host);
+
+// *host: the lists where they landed in the pinned staging area (lists_to_host = false: its counts only)
+static int rg_get_edges_impl(nrs_rgraph* g, const RgGetEdges& a, RgDeviceLists* host) {
+    size_t cand_limit = 0;
+    NRS_TRY(rg_ge_check(g, a, &cand_limit));
+    const RgListLayout L(a.n_ids, a.cap_per_point);
+    NRS_TRY(rg_ge_staging(g, L));
+    NRS_TRY(rg_ge_upload(g, a));
+    const uint8_t* st_f = nullptr;
+    const float* maxd_f = nullptr;
+    NRS_TRY(rg_ge_mirror(g, a.n_ids, &st_f, &maxd_f));
+    NRS_TRY(rg_ge_passes(g, a, L, cand_limit, st_f, maxd_f));
+    *host = L.view(g->pin);
+    return NRS_OK;
 }
-// GetEdges of ids a kernel of the caller listed, the lists left on the device in k_rg_get_edges' layout: o->count[row] = the FULL
-// length of the row's list, of which the first min(count, stride) entries stand at [row * stride, ..) of col / status / w / d0
-// (the BA window's walk reads them there, nrs_engine_winedges.hpp).  Valid until the graph's next GetEdges.
+int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, RgDeviceLists* host, const uint8_t* pass_over, bool lists_to_host) {
+    return rg_get_edges_impl(g, RgGetEdges{n_ids, ids, nullptr, cap_per_point, pass_over, lists_to_host}, host);
+}
 int rg_get_edges_device(nrs_rgraph* g, int32_t n_ids, const int32_t* d_ids, int32_t cap_per_point, RgDeviceLists* o) {
-    const int *h_cnt, *h_col, *h_st;
-    const float *h_w, *h_d0;
-    NRS_TRY(rg_get_edges_impl(g, n_ids, nullptr, d_ids, cap_per_point, &h_cnt, &h_col, &h_st, &h_w, &h_d0, nullptr, false));
-    const size_t no = (size_t)n_ids * cap_per_point;
-    o->n_rows = n_ids; o->stride = cap_per_point;
-    o->count = g->out_i.as<int>();
-    o->col = o->count + n_ids;
-    o->status = o->col + no;
-    o->w = reinterpret_cast<const float*>(o->status + no);
-    o->d0 = o->w + no;
+    RgDeviceLists host;
+    NRS_TRY(rg_get_edges_impl(g, RgGetEdges{n_ids, nullptr, d_ids, cap_per_point, nullptr, false}, &host));
+    *o = RgListLayout(n_ids, cap_per_point).view(g->out_i.p);
     return NRS_OK;
 }
-nrs_ctx* rg_context(const nrs_rgraph* g) { return g->c; }
 }  // namespace nrs
 
 extern "C" int nrs_rgraph_get_edges(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, int32_t* count,
                                     int32_t* col, float* w, float* d0, int32_t* status) {
     if (!g) return NRS_ERR_INVALID;
     nrs_ctx* c = g->c;
-    if (cap_per_point <= 0 || (n_ids > 0 && (!count || !col || !w || !d0 || !status))) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_get_edges: bad argument");
-    NRS_TRY(rg_check_ids(g, n_ids, ids, "nrs_rgraph_get_edges"));
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_get_edges_abi(n_ids, cap_per_point, count && col && w && d0 && status, msg, sizeof(msg)), msg));
+    NRS_TRY(rg_refused(c, rg_check_ids(g->cap, n_ids, ids, "nrs_rgraph_get_edges", msg, sizeof(msg)), msg));
     if (n_ids == 0) return NRS_OK;
-    const int *h_cnt, *h_col, *h_st;
-    const float *h_w, *h_d0;
-    NRS_TRY(rg_get_edges_staged(g, n_ids, ids, cap_per_point, &h_cnt, &h_col, &h_st, &h_w, &h_d0, nullptr, true));
-    const size_t no = (size_t)n_ids * cap_per_point;
-    memcpy(count, h_cnt, sizeof(int) * (size_t)n_ids);
-    memcpy(col, h_col, sizeof(int) * no);
-    memcpy(status, h_st, sizeof(int) * no);
-    memcpy(w, h_w, sizeof(float) * no);
-    memcpy(d0, h_d0, sizeof(float) * no);
+    RgDeviceLists h;
+    NRS_TRY(rg_get_edges_staged(g, n_ids, ids, cap_per_point, &h, nullptr, true));
+    const size_t cells = (size_t)h.n_rows * h.stride;
+    memcpy(count, h.count, sizeof(int) * (size_t)n_ids);
+    memcpy(col, h.col, sizeof(int) * cells);
+    memcpy(status, h.status, sizeof(int) * cells);
+    memcpy(w, h.w, sizeof(float) * cells);
+    memcpy(d0, h.d0, sizeof(float) * cells);
     return NRS_OK;
 }
 
@@ -737,7 +745,8 @@ extern "C" int nrs_rgraph_edge(nrs_rgraph* g, int32_t i, int32_t j, float out[4]
 extern "C" int nrs_rgraph_rows(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, float* maxd, float* mind, float* d0, uint8_t* status) {
     if (!g) return NRS_ERR_INVALID;
     nrs_ctx* c = g->c;
-    NRS_TRY(rg_check_ids(g, n_ids, ids, "nrs_rgraph_rows"));
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_ids(g->cap, n_ids, ids, "nrs_rgraph_rows", msg, sizeof(msg)), msg));
     NRS_HIP(c, hipSetDevice(c->device));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     const int cap = g->cap;
@@ -768,42 +777,29 @@ extern "C" int nrs_rgraph_rows(nrs_rgraph* g, int32_t n_ids, const int32_t* ids,
 extern "C" int nrs_rgraph_resize(nrs_rgraph* g, int32_t new_capacity) {
     if (!g) return NRS_ERR_INVALID;
     nrs_ctx* c = g->c;
-    if (new_capacity < g->cap) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_resize: capacity %d is below the graph's %d", new_capacity, g->cap);
-    if (new_capacity <= 1 || new_capacity > 200000) return c->fail(NRS_ERR_INVALID, "nrs_rgraph_resize: capacity %d is past the limit of 200000 points (nrs_rgraph_create: bad argument)", new_capacity);
+    char msg[256];
+    NRS_TRY(rg_refused(c, rg_check_resize(g->cap, new_capacity, msg, sizeof(msg)), msg));
     if (new_capacity == g->cap) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
     const size_t n2 = (size_t)new_capacity * new_capacity, oc = (size_t)g->cap, ncap = (size_t)new_capacity;
-    float *mx = nullptr, *mn = nullptr, *d0 = nullptr;
-    uint8_t* st = nullptr;
-    hipError_t e = hipMalloc((void**)&mx, n2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&mn, n2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&d0, n2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&st, n2);
-    auto drop = [&]() { if (mx) (void)hipFree(mx); if (mn) (void)hipFree(mn); if (d0) (void)hipFree(d0); if (st) (void)hipFree(st); };
-    if (e != hipSuccess) {
-        const int rc = c->fail(NRS_ERR_ALLOC, "nrs_rgraph_resize (as nrs_rgraph_create): %zu bytes for %d points: %s", n2 * 13, new_capacity, hipGetErrorString(e));
-        (void)hipGetLastError();
-        drop();
-        return rc;
-    }
-    hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, c->stream, st, n2);
-    e = hipGetLastError();
+    RgDense n;
+    NRS_TRY(rg_alloc_dense(c, &n, new_capacity, "nrs_rgraph_resize (as nrs_rgraph_create)"));
     // (the float arrays are read only where the status says there is an edge; zeroed all the same so that no cell is undefined)
-    if (e == hipSuccess) e = hipMemsetAsync(mx, 0, n2 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(mn, 0, n2 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d0, 0, n2 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(mx, ncap * 4, g->maxd, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(mn, ncap * 4, g->mind, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(d0, ncap * 4, g->d0, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(st, ncap, g->st, oc, oc, oc, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = hipMemsetAsync(n.maxd, 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(n.mind, 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(n.d0, 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.maxd, ncap * 4, g->maxd, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.mind, ncap * 4, g->mind, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.d0, ncap * 4, g->d0, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.st, ncap, g->st, oc, oc, oc, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         const int rc = c->fail(NRS_ERR_HIP, "nrs_rgraph_resize: %s", hipGetErrorString(e));
-        drop();
+        n.free();
         return rc;
     }
-    (void)hipFree(g->maxd); (void)hipFree(g->mind); (void)hipFree(g->d0); (void)hipFree(g->st);
-    g->maxd = mx; g->mind = mn; g->d0 = d0; g->st = st;
+    g->free();
+    g->dense() = n;
     g->cap = new_capacity;
     // what was sized or filled for the old capacity: the GetEdges lists on the device (rg_walk refuses to read them), the full-matrix
     // mirrors (rebuilt by the next GetEdges) and the position / flag buffers (re-ensured by every call)

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <chrono>
 #include "nrs_engine.hpp"
+#include "nrs_rgraph.hpp"
 #include "nrs_track_host.hpp"
 
 namespace nrs {
@@ -256,13 +257,6 @@ struct FlatSource : NeighbourSource {
     int update(const float* map_pos, int n, const int* ids, int* good) override { return graph_update(c, G, g, map_pos, n, ids, good); }
 };
 
-int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, const int** count, const int** col,
-                        const int** status, const float** w, const float** d0, const uint8_t* pass_over, bool lists_to_host = true);   // nrs_rgraph.hip
-int rg_walk(nrs_rgraph* g, int n_map, const int* code, const uint8_t* is_node, int* n_acc, int* acc, float* acc_w, float* acc_d0,
-            uint8_t* ended, uint8_t* lost, int* converged, int* passes);
-int rg_capacity(const nrs_rgraph* g);
-int rg_max_cap_per_point(const nrs_rgraph* g);
-
 struct DenseSource : NeighbourSource {
     nrs_ctx* c; nrs_rgraph* g; int cap;
     int select(const std::vector<int>& want) override {           // (the lists are read where they land: the graph's pinned staging area)
@@ -271,12 +265,13 @@ struct DenseSource : NeighbourSource {
         truncated.assign(n, 0);
         col = nullptr; w = nullptr; d0 = nullptr; st = nullptr;
         if (m == 0) return NRS_OK;
-        const int* cnt;
-        NRS_TRY(rg_get_edges_staged(g, (int32_t)m, want.data(), cap, &cnt, &col, &st, &w, &d0, pass_over ? pass_over->data() : nullptr));
+        RgDeviceLists l;
+        NRS_TRY(rg_get_edges_staged(g, (int32_t)m, want.data(), cap, &l, pass_over ? pass_over->data() : nullptr));
+        col = l.col; st = l.status; w = l.w; d0 = l.d0;
         for (size_t r = 0; r < m; ++r) {
             const int p = want[r];
-            truncated[p] = cnt[r] > cap;
-            beg[p] = (int)(r * (size_t)cap); end[p] = beg[p] + std::min(cnt[r], cap);
+            truncated[p] = l.count[r] > cap;
+            beg[p] = (int)(r * (size_t)cap); end[p] = beg[p] + std::min(l.count[r], cap);
         }
         return NRS_OK;
     }
@@ -284,10 +279,10 @@ struct DenseSource : NeighbourSource {
         *done = false;
         const size_t n = (size_t)n_points, m = want.size();
         if (m == 0 || code.size() != n) return NRS_OK;
-        const int *cnt, *c1, *c2; const float *f1, *f2;
-        NRS_TRY(rg_get_edges_staged(g, (int32_t)m, want.data(), cap, &cnt, &c1, &c2, &f1, &f2, pass_over ? pass_over->data() : nullptr, false));
+        RgDeviceLists l;                                           // (its counts only: the lists stay on the device)
+        NRS_TRY(rg_get_edges_staged(g, (int32_t)m, want.data(), cap, &l, pass_over ? pass_over->data() : nullptr, false));
         truncated.assign(n, 0);
-        for (size_t r = 0; r < m; ++r) truncated[want[r]] = cnt[r] > cap;
+        for (size_t r = 0; r < m; ++r) truncated[want[r]] = l.count[r] > cap;
         o.n_acc.resize(m); o.acc.resize(11 * m); o.w.resize(11 * m); o.d0.resize(11 * m); o.ended.resize(m); o.lost.resize(n);
         int conv = 0;
         NRS_TRY(rg_walk(g, (int)n, code.data(), is_node, o.n_acc.data(), o.acc.data(), o.w.data(), o.d0.data(), o.ended.data(), o.lost.data(), &conv, &o.passes));

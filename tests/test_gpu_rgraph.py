@@ -226,3 +226,139 @@ def test_track_deform_does_not_depend_on_the_list_prefix(ctx):
     for k in ("pose_q", "pose_t", "f_pos", "f_status", "map_pos"):
         assert np.array_equal(a[k], b[k]), k
     assert a["lost"] == b["lost"] and a["median"] == b["median"]
+
+
+# ---- the resident graph's two update forms, its two GetEdges sources, growth and the create refusals (capacities 321 and 577: one
+# 256-column tile and five 64-row tiles, nine 64-tiles and one column -- ragged edges in both directions)
+
+def _stretch_patch(pos, centre, radius, factor):
+    """positions with the patch around point `centre` blown up in the image plane: its edges stretch past the threshold"""
+    out = pos.copy()
+    patch = np.linalg.norm(out[:, :2] - out[centre, :2], axis=1) < radius
+    out[patch, :2] = out[centre, :2] + (out[patch, :2] - out[centre, :2]) * np.float32(factor)
+    return out
+
+
+def _all_pairs(ctx, n, pos, sigma=2.2, th=1.1, count=1):
+    ids = np.arange(n, dtype=np.int32)
+    D = RG.DenseGraph(n, sigma, th)
+    D.add_edges(pos, ids, ids)
+    gs = [nrs.RGraph(ctx, n, sigma, th) for _ in range(count)]
+    for g in gs:
+        g.add_edges(pos, ids, ids)
+    return D, gs
+
+
+def _rows_bytes_equal(a, b):
+    """two rows() results: the status bytes everywhere, the three distances wherever the status says there is an edge (a cell without an
+    edge -- the diagonal -- is never written: its floats are whatever the allocation held)"""
+    assert a[3].tobytes() == b[3].tobytes()
+    ex = a[3] != RG.NONE
+    return all(x[ex].tobytes() == y[ex].tobytes() for x, y in zip(a[:3], b[:3]))
+
+
+def test_both_update_forms_give_the_same_bits(ctx):
+    n = 321
+    rng, pos = _scene(n, 41)
+    D, (g1, g2) = _all_pairs(ctx, n, pos, count=2)
+    every = np.arange(n, dtype=np.int32)
+    pos2 = _stretch_patch(pos + rng.normal(0, 0.02, pos.shape).astype(np.float32), 5, 3.0, 2.6)
+    lst = np.sort(rng.choice(n, 200, replace=False)).astype(np.int32)
+    dup = np.concatenate([lst, lst[:1]]).astype(np.int32)
+    assert 4 * len(lst) >= n and len(set(lst.tolist())) == len(lst)      # the one-pass form by the rule (nrs_rgraph_host.hpp rg_update_one_pass) ...
+    assert 4 * len(dup) >= n and len(set(dup.tolist())) < len(dup)       # ... and the per-vertex form: a duplicate
+    ref = np.array([D.update_vertex(pos2, int(i)) for i in lst])
+    ref_again = D.update_vertex(pos2, int(lst[0]))
+    st = D.st[lst]
+    assert (st == O.GRAPH_BAD).any() and (st == O.GRAPH_NEUTRAL).any()
+    good1, good2 = g1.update(pos2, lst), g2.update(pos2, dup)
+    assert np.array_equal(good1, ref)
+    assert np.array_equal(good2[:-1], ref) and good2[-1] == ref_again == ref[0]
+    r1, r2 = g1.rows(every), g2.rows(every)
+    assert _rows_bytes_equal(r1, r2)
+    _compare_rows(g1, D, every)
+    # a short list: the per-vertex form by the rule, on both graphs
+    pos3 = _stretch_patch(pos2, 200, 2.5, 2.4)
+    few = np.sort(rng.choice(n, 80, replace=False)).astype(np.int32)
+    assert 4 * len(few) < n
+    ref3 = np.array([D.update_vertex(pos3, int(i)) for i in few])
+    assert np.array_equal(g1.update(pos3, few), ref3) and np.array_equal(g2.update(pos3, few), ref3)
+    assert _rows_bytes_equal(g1.rows(every), g2.rows(every))
+    _compare_rows(g2, D, every)
+    g1.close()
+    g2.close()
+
+
+def test_mirror_and_triangular_state_give_the_same_lists(ctx):
+    n = 577
+    rng, pos = _scene(n, 42)
+    D, (g,) = _all_pairs(ctx, n, pos)
+    pos2 = _stretch_patch(pos, 64, 3.0, 2.6)
+    upd = np.sort(rng.choice(n, 300, replace=False)).astype(np.int32)
+    assert np.array_equal(g.update(pos2, upd), np.array([D.update_vertex(pos2, int(i)) for i in upd]))
+    assert (D.st == O.GRAPH_BAD).any()
+    fixed = np.array([0, 63, 64, 576], np.int32)
+    ids = np.sort(np.concatenate([fixed, rng.choice(np.setdiff1d(np.arange(n), fixed), 76, replace=False)])).astype(np.int32)
+    assert len(ids) == 80 and 8 * len(ids) >= n and n >= 512             # the first call qualifies for the mirror (nrs_rgraph_host.hpp rg_use_mirror)
+    try:
+        for cap in (16, 256):
+            nrs.debug_set("NRS_RG_NO_MIRROR", None)
+            a = g.get_edges(ids, cap)
+            nrs.debug_set("NRS_RG_NO_MIRROR", 1)
+            b = g.get_edges(ids, cap)
+            assert a[0].tobytes() == b[0].tobytes()
+            for r in range(len(ids)):
+                m = min(int(a[0][r]), cap)
+                assert all(x[r, :m].tobytes() == y[r, :m].tobytes() for x, y in zip(a[1:], b[1:]))
+            cnt = _compare_get_edges(g, D, ids, cap)                     # (under the switch) ...
+            nrs.debug_set("NRS_RG_NO_MIRROR", None)
+            assert np.array_equal(_compare_get_edges(g, D, ids, cap), cnt)   # ... and without it
+            assert cnt.max() > 16 and (cnt.max() <= 256 or cap == 16)    # truncated prefixes at 16; whole lists at 256
+    finally:
+        nrs.debug_set("NRS_RG_NO_MIRROR", None)
+        g.close()
+
+
+def test_resize_keeps_the_state(ctx):
+    n0, n = 130, 577
+    rng, pos = _scene(n, 43)
+    D = RG.DenseGraph(n, 2.2, 1.1)
+    g = nrs.RGraph(ctx, n0, 2.2, 1.1)
+    old, every = np.arange(n0, dtype=np.int32), np.arange(n, dtype=np.int32)
+    g.add_edges(pos[:n0], old, old)
+    D.add_edges(pos, old, old)
+    pos2 = _stretch_patch(pos, 7, 3.0, 2.6)
+    upd = np.sort(rng.choice(n0, 90, replace=False)).astype(np.int32)
+    assert np.array_equal(g.update(pos2[:n0], upd), np.array([D.update_vertex(pos2, int(i)) for i in upd]))
+    assert (D.st[:n0, :n0] == O.GRAPH_BAD).any()
+    g.resize(n)
+    mx, mn, d0, st = g.rows(old)
+    assert np.array_equal(st, D.st[old]) and (st[:, n0:] == RG.NONE).all() and (st[:, :n0] != RG.NONE).sum() == n0 * (n0 - 1)
+    _compare_rows(g, D, old)
+    _compare_rows(g, D, np.array([n0, n - 1], np.int32))                # new points: no edge yet
+    new = np.arange(n0, n, dtype=np.int32)
+    g.add_edges(pos2, new, every)
+    D.add_edges(pos2, new, every)
+    ids = np.sort(np.concatenate([rng.choice(n0, 40, replace=False), [n0 - 1, n0, n - 1], n0 + 1 + rng.choice(n - n0 - 2, 37, replace=False)])).astype(np.int32)
+    assert (ids < n0).any() and (ids >= n0).any() and len(set(ids.tolist())) == 80
+    _compare_get_edges(g, D, ids, 64)
+    _compare_get_edges(g, D, ids[:9], 64)                                # (few rows: the triangular state)
+    with pytest.raises(nrs.NrsError, match="nrs_rgraph_resize: capacity 100 is below the graph's 577"):
+        g.resize(100)
+    with pytest.raises(nrs.NrsError, match=r"nrs_rgraph_resize: capacity 200001 is past the limit of 200000 points \(nrs_rgraph_create: bad argument\)"):
+        g.resize(200001)
+    assert g.cap == n
+    _compare_rows(g, D, ids[::8])
+    _compare_get_edges(g, D, ids[::8], 64)
+    g.close()
+
+
+def test_create_refusals_leave_the_context_usable(ctx):
+    for cap, sigma, th in ((1, 2.2, 1.1), (8, 0.0, 1.1), (8, 2.2, 0.0)):
+        with pytest.raises(nrs.NrsError, match="nrs_rgraph_create: bad argument") as e:
+            nrs.RGraph(ctx, cap, sigma, th)
+        assert e.value.code == -1
+    rng, pos = _scene(8, 44)
+    D, (g,) = _all_pairs(ctx, 8, pos, sigma=20.0)
+    _compare_get_edges(g, D, np.arange(8, dtype=np.int32), 8)
+    g.close()
