@@ -182,7 +182,9 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
  *   front end     NRS_FRONT_PER_EYE (nrs_front_process_stereo: grey and CLAHE issued per eye with the single-frame kernels instead of the
  *                 pair launches; the same bytes)
- *   probes        (read by a `make PROBES=1` build only) NRS_LIN_DBG / NRS_SPMV_DBG / NRS_PCG_DBG (phase clocks of one lineariser /
+ *   initialisation NRS_DBND_NO_TILE (nrs_dbscan_nd and nrs_flow_tracks_cluster: the neighbour stage as a wave per point with candidates
+ *                 from global memory instead of the LDS tiles; the same bits)
+ *   probes      (read by a `make PROBES=1` build only) NRS_LIN_DBG / NRS_SPMV_DBG / NRS_PCG_DBG (phase clocks of one lineariser /
  *                 operator / single-launch PCG iteration launch), NRS_LIN_EXP=<n> (lineariser removal experiments: wrong results on purpose)
  * (what each selects: README.md "Debug switches"; the A/B tests drive every launch form through nrs_debug_set). */
 int nrs_debug_set(nrs_ctx* ctx, const char* name /* "NRS_..." */, const char* value /* NULL: unset */);
@@ -902,8 +904,8 @@ int nrs_skin_select_nodes(nrs_ctx* ctx, int32_t n_points, const float* pos /* n_
  * THE INDEXING QUIRK.  FindEssentialWithRANSAC fills the inlier flags by COMPACT index; ReconstructEnvironment / ReconstructPoints read
  * inliers[idx], reference_keypoints_[idx] and current_keypoints_[idx] by KEYPOINT index over idx < n_matches (:266-267, :331-338).
  * compact_indexing = 0 restates exactly that (with every keypoint TRACKED the two coincide); 1 reads keypoint compact_map[idx] instead.
- * Not built: RefineSolution (never called in the reference) and the DBSCAN labels of FeatureTracksClustering (visualiser only; Dbscan3D itself
- * is nrs_dbscan3d, f8). */
+ * Not built: RefineSolution (never called in the reference).  The DBSCAN labels of FeatureTracksClustering are nrs_flow_tracks_cluster,
+ * below the solve. */
 typedef struct {
     uint32_t struct_size;
     int32_t  n_hypotheses;        /* 0 = the reference's count, ComputeMaxTries(0.8, 0.95) = 16 (:78-81,130-132); 1..4096              */
@@ -942,6 +944,42 @@ void nrs_init_options_init(nrs_init_options* opt);
  * n_matches above the TRACKED count, a sample index outside the compact range. */
 int nrs_init_essential(nrs_ctx* ctx, const nrs_camera* cam, const nrs_init_options* opt, int32_t n, const float* ref_xy,
                        const float* cur_xy, const int32_t* status, int32_t n_matches, const int32_t* samples, nrs_init_result* out);
+
+/* Flow-track clustering -- MonocularMapInitializer::FeatureTracksClustering (modules/tracking/monocular_map_initializer.cc:185-219) with
+ * DbscanND (modules/utilities/dbscan.cc:106-131), which ProcessNewImage runs on every image between a reset and a start (:62-63) and whose
+ * labels InitializationRefinement receives as track_labels (:238,260).  Arithmetic of record: DESIGN.md 4 "Flow-track clustering".
+ *
+ * The clustering over dim coordinates.  mlpack is not in the tree, so the rule is THIS PROJECT'S DEFINITION (parity unpinned), the one of
+ * Dbscan3D (f8) at any dimension:
+ *   data        n points of dim fp32 coordinates, point-major; 0 <= n <= NRS_DBSCAN_MAX_POINTS, 1 <= dim <= NRS_DBSCAN_MAX_DIM
+ *   neighbour   j != i and d2(i, j) <= eps * eps; d2 = the fp64 sum over k = 0 .. dim-1, in ascending k, of (double(a_k) - double(b_k))^2:
+ *               one product and one add per coordinate, the first product starts the sum, no contraction; eps * eps one double product;
+ *               the boundary is inclusive; a pair with a non-finite d2 is no neighbour pair.  At dim = 3 this is, bit for bit, Dbscan3D's
+ *               (dx*dx + dy*dy) + dz*dz
+ *   core        at least min_points neighbours (the point itself is not counted)
+ *   clusters    the connected components of the core points under the neighbour relation; raw labels 0, 1, ... in ascending order of a
+ *               component's lowest-index core point; a non-core point with a core neighbour takes the lowest raw label among its core
+ *               neighbours; every other point is noise, -1
+ *   no ranking  DbscanND has none: the raw label is the label
+ * label: n; counts: clusters, noise points.  NRS_ERR_INVALID: n outside 0..16384, dim outside 1..64, eps not finite or <= 0,
+ * min_points < 1, a null pointer.  n = 0 succeeds with counts (0, 0).
+ *
+ * The flow tracks (:191-211).  A track is `length` keypoints (2 <= length <= 33), its point has dim = 2 (length - 1) coordinates:
+ * coordinate 2(t-1) is x_t - x_(t-1) and coordinate 2(t-1)+1 is y_t - y_(t-1), each ONE fp32 subtraction (cv::Point2f::operator-).
+ * eps = double(float(0.1 * double(dim))) -- the reference stores the product in a float -- and min_points = 10 (:212-213).  Only tracks of the
+ * maximal length take part (:194); the caller passes them in ascending feature index (the reference iterates a hash map whose order nothing
+ * fixes).  DEPARTURE: InitializationRefinement reads feature_labels[idx] by KEYPOINT index although the vector is in full-length-track
+ * order (:260); that misindexing is not reproduced, a track's label is its own.
+ * flows_out (nullable): n_tracks x dim, the points that were clustered.  NRS_ERR_INVALID: n_tracks outside 0..16384, length outside 2..33, a
+ * null pointer.
+ *
+ * Each call: one upload, every stage on the context's stream and scratch, one packed download.  The neighbour stage streams the candidates
+ * through LDS tiles of 64 points; NRS_DBND_NO_TILE (nrs_debug_set) selects its plain form, the same bits. */
+#define NRS_DBSCAN_MAX_DIM 64
+int nrs_dbscan_nd(nrs_ctx* ctx, int32_t n, int32_t dim, const float* data /* n x dim */, double eps, int32_t min_points,
+                  int32_t* label /* n */, int32_t counts[2] /* clusters, noise points */);
+int nrs_flow_tracks_cluster(nrs_ctx* ctx, int32_t n_tracks, int32_t length, const float* tracks_xy /* n x length x 2 */,
+                            float* flows_out /* nullable: n x 2(length-1) */, int32_t* label, int32_t counts[2]);
 
 /* ---- f7: evaluation -- FrameEvaluator (modules/utilities/frame_evaluator.cc) and its two sources of ground truth, the stereo matchers
  * (modules/stereo/) and a depth image.  Arithmetic and the stated departures: DESIGN.md 4 "Evaluation (f7)".  Per-point status: */

@@ -18,10 +18,17 @@
 // nrs_init_stereo puts k_si_gate (status / depth gate, stable compaction in keypoint order) between the matcher's launches
 // (stereo_match_enqueue, nrs_eval.hip) and these, and k_si_select (codes, labels by keypoint, the rank-0 points in keypoint order) behind.
 // One workgroup never waits for another; the only persistent loop is inside k_db_comp's single workgroup.
+//
+// f6: flow-track clustering (include/nrs.h "f6"; DESIGN.md 4 "Flow-track clustering"), on the same rows.
+//   nrs_dbscan_nd             DbscanND (modules/utilities/dbscan.cc:106-131): the same rule over dim <= 64 coordinates, no ranking
+//   nrs_flow_tracks_cluster   MonocularMapInitializer::FeatureTracksClustering (modules/tracking/monocular_map_initializer.cc:185-219)
+// Launches: k_flow_build (tracks only), k_db_neigh_nd (LDS tiles of 64 candidates shared by a workgroup's queries; NRS_DBND_NO_TILE:
+// k_db_neigh_nd_plain, a wave per point), then k_db_comp and k_db_border as above and k_dbnd_counts; the raw label is the label.
 #include <climits>
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
 #include "nrs_sinit_host.hpp"
+#include "nrs_flowc_host.hpp"
 
 namespace nrs {
 namespace {
@@ -53,22 +60,18 @@ struct DbWs {
     int* size;           // cap + 1: class sizes, noise first
     int* rank;           // cap + 1
 };
-size_t db_ws_bytes(int cap) {
-    const size_t W = (size_t)(cap + 63) / 64;
-    return padded(sizeof(u64) * (size_t)cap * W) + padded(sizeof(u64) * DB_WORDS) + 3 * padded(sizeof(int) * (size_t)cap) +
-           2 * padded(sizeof(int) * ((size_t)cap + 1));
-}
+size_t db_ws_bytes(int cap) { return DbRowsLayout((size_t)cap).bytes; }     // (nrs_flowc_host.hpp: the piece's layout, checked on the host)
 DbWs db_carve(char* base, int cap) {
-    Carver cv(base);
+    const DbRowsLayout L((size_t)cap);
     DbWs w;
-    w.cap = cap; w.W = (cap + 63) / 64;
-    w.adj = cv.take<u64>((size_t)cap * w.W);
-    w.coremask = cv.take<u64>(DB_WORDS);
-    w.core = cv.take<int>(cap);
-    w.lab = cv.take<int>(cap);
-    w.rawid = cv.take<int>(cap);
-    w.size = cv.take<int>((size_t)cap + 1);
-    w.rank = cv.take<int>((size_t)cap + 1);
+    w.cap = cap; w.W = (int)L.W;
+    w.adj = reinterpret_cast<u64*>(base + L.adj);
+    w.coremask = reinterpret_cast<u64*>(base + L.coremask);
+    w.core = reinterpret_cast<int*>(base + L.core);
+    w.lab = reinterpret_cast<int*>(base + L.lab);
+    w.rawid = reinterpret_cast<int*>(base + L.rawid);
+    w.size = reinterpret_cast<int*>(base + L.size);
+    w.rank = reinterpret_cast<int*>(base + L.rank);
     return w;
 }
 
@@ -240,6 +243,164 @@ void dbscan_enqueue(nrs_ctx* c, const DbWs& w, const int* d_m, const float* d_xy
     hipLaunchKernelGGL(k_db_border, dim3((cap + 3) / 4), dim3(256), 0, c->stream, d_m, cap, w.W, w.adj, w.coremask, w.core, w.lab, w.rawid, d_raw, w.size);
     hipLaunchKernelGGL(k_db_rank, dim3((cap + 1 + 255) / 256), dim3(256), 0, c->stream, cap, noise_competes ? 1 : 0, w.size, w.rank, d_counts);
     hipLaunchKernelGGL(k_db_label, dim3((cap + 255) / 256), dim3(256), 0, c->stream, d_m, cap, d_raw, w.rank, d_label);
+}
+
+// ---- flow-track clustering (include/nrs.h "f6"; DESIGN.md 4 "Flow-track clustering"): the neighbour stage over dim coordinates, the one
+// stage that knows the dimension.  k_db_comp and k_db_border follow unchanged; no ranking, the raw label is the label.
+
+// monocular_map_initializer.cc:191-211: a thread per (track, step), two fp32 subtractions
+__global__ __launch_bounds__(256) void k_flow_build(int n, int length, const float* __restrict__ xy, float* __restrict__ flow) {
+#pragma clang fp contract(off)
+    const int steps = length - 1;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)n * steps) return;
+    const size_t trk = e / steps, t = e - trk * steps + 1;
+    const float* p = xy + (trk * length + t) * 2;
+    flow[trk * 2 * steps + 2 * (t - 1)] = p[0] - p[-2];
+    flow[trk * 2 * steps + 2 * (t - 1) + 1] = p[1] - p[-1];
+}
+
+// The tiled form.  A workgroup of four waves owns 4 R consecutive query points (a wave R of them) and streams ALL m candidates through LDS in
+// tiles of 64 points: the tile is a contiguous span of the point-major array, read once per workgroup with consecutive threads on
+// consecutive floats, and held dimension-major with an odd stride (65 floats), so that the transposing writes of consecutive threads (same
+// point, next coordinate) fall on consecutive banks and a lane's walk over k reads lane-consecutive words.  The query coordinates lie in LDS
+// as doubles, [k][query]: every lane of a wave reads the same address (a broadcast).  A lane owns candidate 64 wd + lane and accumulates d2
+// for its wave's R queries in fp64, ascending k, the first product starting the sum; one ballot per tile and query is one adjacency word.
+// Lanes past the tail tile's points and the candidate i itself give zero bits.
+template <int R>
+__global__ __launch_bounds__(256) void k_db_neigh_nd(const int* __restrict__ d_m, int cap, int W, int dim, const float* __restrict__ data,
+                                                     double eps2, int min_points, u64* __restrict__ adj, int* __restrict__ core,
+                                                     int* __restrict__ lab) {
+#pragma clang fp contract(off)
+    constexpr int Q = 4 * R;
+    __shared__ float s_tile[FLOWC_MAX_DIM * FLOWC_TILE_STRIDE];
+    __shared__ double s_q[FLOWC_MAX_DIM * Q];
+    const int m = min(*d_m, cap);
+    const int q0 = blockIdx.x * Q;
+    if (q0 >= m) return;                                           // (uniform over the workgroup: before any barrier)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int step_p = 256 / dim, step_k = 256 % dim;              // what 256 floats further is in (point, coordinate)
+    for (int e = tid; e < Q * dim; e += 256) {
+        const int q = e / dim, k = e - q * dim, i = q0 + q;
+        s_q[k * Q + q] = i < m ? (double)data[(size_t)i * dim + k] : 0.0;
+    }
+    int cnt[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) cnt[r] = 0;
+    const int Wm = (m + 63) / 64;
+    for (int wd = 0; wd < Wm; ++wd) {
+        const int j0 = wd * FLOWC_TILE, np = min(FLOWC_TILE, m - j0);
+        __syncthreads();                                           // the previous tile is read (first trip: the queries are written)
+        const float* src = data + (size_t)j0 * dim;
+        int p = tid / dim, k = tid - p * dim;
+        for (int e = tid; e < np * dim; e += 256) {
+            s_tile[k * FLOWC_TILE_STRIDE + p] = src[e];
+            p += step_p; k += step_k;
+            if (k >= dim) { k -= dim; ++p; }
+        }
+        __syncthreads();
+        double acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = 0.0;
+        if (lane < np) {
+            const double c0 = (double)s_tile[lane];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double d = c0 - s_q[wv * R + r];
+                acc[r] = d * d;
+            }
+            for (int kk = 1; kk < dim; ++kk) {
+                const double cj = (double)s_tile[kk * FLOWC_TILE_STRIDE + lane];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double d = cj - s_q[kk * Q + wv * R + r];
+                    const double pr = d * d;
+                    acc[r] = acc[r] + pr;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = q0 + wv * R + r;
+            const bool nb = lane < np && j0 + lane != i && acc[r] <= eps2;       // inclusive; NaN and +inf compare false
+            const u64 word = __ballot(nb);
+            if (i < m) {
+                if (lane == 0) adj[(size_t)i * W + wd] = word;
+                cnt[r] += __popcll(word);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = q0 + wv * R + r;
+        if (i < m && lane == 0) {
+            const bool c = cnt[r] >= min_points;
+            core[i] = c ? 1 : 0;
+            lab[i] = c ? i : INT_MAX;
+        }
+    }
+}
+
+// NRS_DBND_NO_TILE: k_db_neigh with a loop over the coordinates -- a wave per point, every lane fetches its candidate from global memory;
+// the same sum in the same order, the same bits
+__global__ __launch_bounds__(256) void k_db_neigh_nd_plain(const int* __restrict__ d_m, int cap, int W, int dim, const float* __restrict__ data,
+                                                           double eps2, int min_points, u64* __restrict__ adj, int* __restrict__ core,
+                                                           int* __restrict__ lab) {
+#pragma clang fp contract(off)
+    const int m = min(*d_m, cap);
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= m) return;                                            // (uniform over the wave)
+    const float* pi = data + (size_t)i * dim;
+    const int Wm = (m + 63) / 64;
+    int cnt = 0;
+    for (int wd = 0; wd < Wm; ++wd) {
+        const int j = wd * 64 + lane;
+        bool nb = false;
+        if (j < m && j != i) {
+            const float* pj = data + (size_t)j * dim;
+            const double d0 = (double)pj[0] - (double)pi[0];
+            double d2 = d0 * d0;
+            for (int k = 1; k < dim; ++k) {
+                const double d = (double)pj[k] - (double)pi[k];
+                const double pr = d * d;
+                d2 = d2 + pr;
+            }
+            nb = d2 <= eps2;
+        }
+        const u64 word = __ballot(nb);
+        if (lane == 0) adj[(size_t)i * W + wd] = word;
+        cnt += __popcll(word);
+    }
+    if (lane == 0) {
+        const bool c = cnt >= min_points;
+        core[i] = c ? 1 : 0;
+        lab[i] = c ? i : INT_MAX;
+    }
+}
+
+// counts[1] = the noise class's size (what k_db_rank does on its way; no ranking here)
+__global__ void k_dbnd_counts(const int* __restrict__ size, int* counts) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[1] = size[0];
+}
+
+// the four launches on cap >= 1 points of dim coordinates; d_m, data, label and counts are device pointers (label: cap entries, counts: 3)
+void dbscan_nd_enqueue(nrs_ctx* c, const DbWs& w, const int* d_m, int dim, const float* d_data, double eps, int min_points, int* d_label,
+                       int* d_counts) {
+    const double eps2 = eps * eps;
+    const int cap = w.cap;
+    if (c->dbg.is_set(SW_DBND_NO_TILE)) {
+        hipLaunchKernelGGL(k_db_neigh_nd_plain, dim3((cap + 3) / 4), dim3(256), 0, c->stream, d_m, cap, w.W, dim, d_data, eps2, min_points, w.adj,
+                           w.core, w.lab);
+    } else {
+        const int R = flowc_queries_per_wave(cap), Q = 4 * R;
+        const dim3 grid((cap + Q - 1) / Q);
+        if (R == 1) hipLaunchKernelGGL(k_db_neigh_nd<1>, grid, dim3(256), 0, c->stream, d_m, cap, w.W, dim, d_data, eps2, min_points, w.adj, w.core, w.lab);
+        else if (R == 2) hipLaunchKernelGGL(k_db_neigh_nd<2>, grid, dim3(256), 0, c->stream, d_m, cap, w.W, dim, d_data, eps2, min_points, w.adj, w.core, w.lab);
+        else hipLaunchKernelGGL(k_db_neigh_nd<4>, grid, dim3(256), 0, c->stream, d_m, cap, w.W, dim, d_data, eps2, min_points, w.adj, w.core, w.lab);
+    }
+    hipLaunchKernelGGL(k_db_comp, dim3(1), dim3(DB_BLOCK), 0, c->stream, d_m, cap, w.W, w.adj, w.core, w.lab, w.coremask, w.rawid, w.size, d_counts);
+    hipLaunchKernelGGL(k_db_border, dim3((cap + 3) / 4), dim3(256), 0, c->stream, d_m, cap, w.W, w.adj, w.coremask, w.core, w.lab, w.rawid, d_label, w.size);
+    hipLaunchKernelGGL(k_dbnd_counts, dim3(1), dim3(64), 0, c->stream, w.size, d_counts);
 }
 
 struct SiPacked { unsigned xyz, status, code, raw, label, selected, sel_xyz; };          // word offsets of SinitLayout
@@ -418,4 +579,61 @@ extern "C" int nrs_init_stereo_front(nrs_ctx* c, const nrs_camera* cam, const nr
     const uint8_t *left = nullptr, *right = nullptr;
     NRS_TRY(front_resident_pair(c, "nrs_init_stereo_front", w, h, image, &left, &right));
     return sinit_run(c, "nrs_init_stereo_front", cam, opt, left, right, true, w, h, w, w, n, xy, out);
+}
+
+// Both flow-clustering entry points: ONE upload (the count and the caller's floats), the launches, ONE packed download.  length = 0: the
+// floats are n x dim points; otherwise n x length x 2 keypoints, and k_flow_build writes the points into the download's flows
+static int dbnd_run(nrs_ctx* c, const char* who, int n, int dim, int length, const float* in, double eps, int min_points, float* flows_out,
+                    int32_t* label, int32_t counts[2]) {
+    NRS_HIP(c, hipSetDevice(c->device));
+    const FlowcScratch S((size_t)n, (size_t)dim, (size_t)length);
+    DevBuf big;
+    NRS_TRY(c->ensure(big, S.bytes));
+    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
+    char* base = big.as<char>();
+    int* d_m = reinterpret_cast<int*>(base + S.m);
+    float* d_in = reinterpret_cast<float*>(base + S.in);
+    int* d_out = reinterpret_cast<int*>(base + S.out);
+    float* d_flows = reinterpret_cast<float*>(d_out + S.flows_word);
+    const DbWs w = db_carve(base + S.rows, n);
+    std::vector<char> up(S.up_bytes, 0);
+    memcpy(up.data() + S.m, &n, sizeof(int));
+    memcpy(up.data() + S.in, in, sizeof(float) * S.in_floats);
+    NRS_HIP(c, hipMemcpyAsync(base, up.data(), S.up_bytes, hipMemcpyHostToDevice, c->stream));            // the one upload
+    if (length) {
+        const size_t steps = (size_t)n * (length - 1);
+        hipLaunchKernelGGL(k_flow_build, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, c->stream, n, length, d_in, d_flows);
+    }
+    dbscan_nd_enqueue(c, w, d_m, dim, length ? d_flows : d_in, eps, min_points, d_out + 4, d_out);
+    NRS_HIP(c, hipGetLastError());
+    std::vector<int32_t> host(S.out_words);
+    NRS_HIP(c, hipMemcpyAsync(host.data(), d_out, sizeof(int) * S.out_words, hipMemcpyDeviceToHost, c->stream));   // the one download
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (host[0] < 0 || host[0] > n || host[1] < 0 || host[1] > n)
+        return c->fail(NRS_ERR_HIP, "%s: the counts came back as (%d, %d) for %d points", who, host[0], host[1], n);
+    counts[0] = host[0]; counts[1] = host[1];
+    memcpy(label, host.data() + 4, sizeof(int32_t) * (size_t)n);
+    if (length && flows_out) memcpy(flows_out, host.data() + S.flows_word, sizeof(float) * (size_t)n * dim);
+    return NRS_OK;
+}
+
+extern "C" int nrs_dbscan_nd(nrs_ctx* c, int32_t n, int32_t dim, const float* data, double eps, int32_t min_points, int32_t* label,
+                             int32_t counts[2]) {
+    if (!c) return NRS_ERR_INVALID;
+    char msg[256];
+    if (dbscan_nd_check_args(n, dim, data, eps, min_points, label, counts, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    counts[0] = counts[1] = 0;
+    if (n == 0) return NRS_OK;
+    return dbnd_run(c, "nrs_dbscan_nd", n, dim, 0, data, eps, min_points, nullptr, label, counts);
+}
+
+extern "C" int nrs_flow_tracks_cluster(nrs_ctx* c, int32_t n_tracks, int32_t length, const float* tracks_xy, float* flows_out, int32_t* label,
+                                       int32_t counts[2]) {
+    if (!c) return NRS_ERR_INVALID;
+    char msg[256];
+    if (flow_tracks_check_args(n_tracks, length, tracks_xy, label, counts, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    counts[0] = counts[1] = 0;
+    if (n_tracks == 0) return NRS_OK;
+    const int dim = flowc_dim(length);
+    return dbnd_run(c, "nrs_flow_tracks_cluster", n_tracks, dim, length, tracks_xy, flowc_eps(dim), FLOWC_MIN_POINTS, flows_out, label, counts);
 }

@@ -32,7 +32,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_rgraph_create", "nrs_rgraph_destroy", "nrs_rgraph_set_sigma", "nrs_rgraph_min_weight", "nrs_rgraph_add_edges",
            "nrs_rgraph_update", "nrs_rgraph_get_edges", "nrs_rgraph_edge", "nrs_rgraph_rows", "nrs_rgraph_resize", "nrs_triangulate_batch", "nrs_map_frame", "nrs_map_grow_graph", "nrs_track_deform_solve_rg", "nrs_dba_solve_window_rg", "nrs_dba_window_rg_stats", "nrs_dba_solve_window_rg_embedded",
            "nrs_skin_select_nodes", "nrs_dba_stats", "nrs_dba_skin_stats",
-           "nrs_init_options_init", "nrs_init_essential",
+           "nrs_init_options_init", "nrs_init_essential", "nrs_dbscan_nd", "nrs_flow_tracks_cluster",
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame",
            "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo",
            "nrs_front_process_stereo", "nrs_stereo_match_pattern_front", "nrs_init_stereo_front", "nrs_stereo_match_lk_front",
@@ -142,6 +142,8 @@ class InitStereoResult(C.Structure):
 SINIT_OK, SINIT_NOTHING_GATED = 0, 1
 SINIT_SELECTED, SINIT_MATCHER_REJECTED, SINIT_OUTSIDE_GATE, SINIT_OTHER_CLUSTER = 0, 1, 2, 3
 DBSCAN_MAX_POINTS = 16384
+DBSCAN_MAX_DIM = 64
+FLOW_MIN_LENGTH, FLOW_MAX_LENGTH, FLOW_MIN_POINTS = 2, 33, 10
 
 INIT_OK, INIT_FEW_MATCHES, INIT_FEW_LANDMARKS, INIT_LOW_PARALLAX = 0, 1, 2, 3
 INIT_COUNTERS = ("N", "n_triangulated", "n_parallax", "n_depth_1", "n_reprojection_error_1", "n_depth_2", "n_reprojection_error_2",
@@ -176,6 +178,9 @@ def load_library(path=LIB_PATH):
     lib.nrs_stereo_match_pattern_front.argtypes = [ptr, ptr, f32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]
     lib.nrs_init_stereo_front.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr]
     lib.nrs_stereo_match_lk_front.argtypes = [ptr, ptr, ptr, f32, i32, i32, i32, i32, ptr, f32, ptr, ptr, ptr, ptr]
+    # flow-track clustering (include/nrs.h "f6")
+    lib.nrs_dbscan_nd.argtypes = [ptr, i32, i32, ptr, C.c_double, i32, ptr, ptr]
+    lib.nrs_flow_tracks_cluster.argtypes = [ptr, i32, i32, ptr, ptr, ptr, ptr]
     # the resident temporal buffer (include/nrs.h "The resident TemporalBuffer")
     lib.nrs_tbuf_create.argtypes = [ptr, i32, ptr]
     lib.nrs_tbuf_destroy.restype = None
@@ -841,6 +846,33 @@ class Context:
             if samples is None:
                 r.update(labels=a["labels"], centres=a["centres"])
         return r
+
+    # ---- f6: flow-track clustering
+    def dbscan_nd(self, data, eps, min_points=FLOW_MIN_POINTS, n=None, dim=None):
+        """nrs_dbscan_nd on data [n, dim] fp32 -> (label [n], counts (clusters, noise points)).  n / dim: the values passed to the library
+        when they are not data's shape (refusal tests)"""
+        data = _f32(data)
+        if data.ndim != 2:
+            raise ValueError("dbscan_nd: data must be n x dim")
+        m, d = data.shape
+        lab, counts = np.zeros(m, np.int32), np.zeros(2, np.int32)
+        self._chk(self.lib.nrs_dbscan_nd(self.h, m if n is None else n, d if dim is None else dim, data.ctypes.data if data.size else None,
+                                         float(eps), int(min_points), lab.ctypes.data if m else None, counts.ctypes.data))
+        return lab, counts
+
+    def flow_tracks_cluster(self, tracks_xy, flows=True, n=None, length=None):
+        """nrs_flow_tracks_cluster on tracks_xy [n, length, 2] fp32 -> (label [n], counts (clusters, noise points), flows [n, 2 (length - 1)]
+        or None).  n / length: the values passed to the library when they are not the array's shape (refusal tests)"""
+        t = _f32(tracks_xy)
+        if t.ndim != 3 or t.shape[2] != 2:
+            raise ValueError("flow_tracks_cluster: tracks_xy must be n x length x 2")
+        m, ln = t.shape[0], t.shape[1]
+        lab, counts = np.zeros(m, np.int32), np.zeros(2, np.int32)
+        fl = np.zeros((m, max(2 * (ln - 1), 0)), np.float32) if flows else None
+        self._chk(self.lib.nrs_flow_tracks_cluster(self.h, m if n is None else n, ln if length is None else length, t.ctypes.data if t.size else None,
+                                                   fl.ctypes.data if fl is not None and fl.size else None, lab.ctypes.data if m else None,
+                                                   counts.ctypes.data))
+        return lab, counts, fl
 
     # ---- f8: stereo map initialisation
     def dbscan3d(self, xyz, eps=2.5, min_points=5, noise_competes=True, n=None):

@@ -228,6 +228,12 @@ class GpuBackend:
     def init_essential(self, ref_xy, cur_xy, status, n_matches, **options):
         return self.ctx.init_essential(self.cam, ref_xy, cur_xy, status, n_matches, taps=False, **options)
 
+    # MonocularMapInitializer::FeatureTracksClustering (monocular_map_initializer.cc:185-219) on the device: include/nrs.h
+    # nrs_flow_tracks_cluster.  tracks: [n, length, 2] keypoints of the full-length tracks in ascending feature index -> labels [n]
+    def flow_cluster(self, tracks):
+        label, _, _ = self.ctx.flow_tracks_cluster(tracks, flows=False)
+        return label
+
     # Tracking::StereoMapInitialization (tracking.cc:216-263) on the device: include/nrs.h nrs_init_stereo.  Without the front mode the images
     # are grey bytes from the host; in front mode they are the RAW frames, processed once as a pair (front_stereo) and matched where they
     # lie (nrs_init_stereo_front).  The result carries the selected keypoints for FrameLoop.from_stereo_initialization
@@ -374,13 +380,22 @@ class MonoInitializer:
     """MonocularMapInitializer (modules/tracking/monocular_map_initializer.cc:52-307) on flat arrays over a backend: ProcessNewImage /
     DataAssociation / ResetInitialization / AddFeatureTracks / RigidInitialization / InitializationRefinement.  A feature's id is its index in
     the arrays of the current reference (they are never reordered between two resets), so a feature track is its first keypoint, its last one
-    and its length.  Not restated: FeatureTracksClustering (its DBSCAN labels reach the visualiser only).  n_tracks_in_image_ is taken as the
+    and its length.  n_tracks_in_image_ is taken as the
     number of TRACKED statuses after the tracker's call -- what LucasKanadeTracker::Track returns.  max_features thins the extractor's list
-    evenly, mask is handed to the extractor's filter (ExtractFeatures, :135-153)."""
+    evenly, mask is handed to the extractor's filter (ExtractFeatures, :135-153).
+
+    cluster_tracks=True adds FeatureTracksClustering (:185-219): AddFeatureTracks then keeps the keypoints of every image since the reset (a
+    keypoint is appended only where the status is TRACKED), and every image that is not a reset hands the tracks of the maximal length, in
+    ascending feature index (the reference: the order of a hash map), to backend.flow_cluster.  The log entry gains `full_tracks` (their
+    indices) and `feature_labels`, a successful result `track_labels`, aligned with `index` -- a track's label is its own, where
+    InitializationRefinement (:260) indexes the labels, which are in full-length-track order, by keypoint.  Off (the default) nothing of
+    this runs and the log is what it was."""
     NO_DATA, RECENTLY_RESET, OK = 0, 1, 2
 
-    def __init__(self, backend, klt_min_ssim=0.5, min_tracks=100, max_images=30, max_features=None, **init_options):
+    def __init__(self, backend, klt_min_ssim=0.5, min_tracks=100, max_images=30, max_features=None, cluster_tracks=False, **init_options):
         self.b, self.min_ssim, self.min_tracks, self.max_images, self.max_features = backend, klt_min_ssim, min_tracks, max_images, max_features
+        self.cluster_tracks = bool(cluster_tracks)
+        self.history = []                                        # cluster_tracks: (keypoints, TRACKED mask) of every image since the reset
         self.init_options = init_options
         self.state = self.NO_DATA
         self.kp = self.ref_kp = np.zeros((0, 2), F32)
@@ -399,6 +414,7 @@ class MonoInitializer:
         self.status = np.full(len(xy), TRACKED, np.int32)
         self.track_len = np.zeros(len(xy), np.int32)
         self.max_len, self.images = 0, 0
+        self.history = []
         self.state = self.RECENTLY_RESET
 
     def data_association(self, im, mask=None):                   # (:105-133)
@@ -417,6 +433,16 @@ class MonoInitializer:
                     self.reset(im, mask)
         self.track_len[self.status == TRACKED] += 1              # AddFeatureTracks (:155-166)
         self.max_len += 1
+        if self.cluster_tracks:
+            self.history.append((self.kp.copy(), self.status == TRACKED))
+
+    def feature_tracks_clustering(self):
+        """FeatureTracksClustering (:185-219) -> (full_tracks: indices of the tracks of the maximal length, ascending; feature_labels)"""
+        full = np.nonzero(self.track_len == self.max_len)[0].astype(np.int32)
+        if len(full) == 0:
+            return full, np.zeros(0, np.int32)
+        tracks = np.stack([kp[full] for kp, _ in self.history], axis=1).astype(F32)       # [n, length, 2]; every mask is set on these rows
+        return full, np.asarray(self.b.flow_cluster(tracks), np.int32)
 
     def process_new_image(self, im, mask=None):
         """ProcessNewImage (:52-78): None ("Just reset" / "Rigid Initialization failed") or the InitializationResults as a dict"""
@@ -425,6 +451,9 @@ class MonoInitializer:
         self.log.append(entry)
         if self.state == self.RECENTLY_RESET:
             return None
+        if self.cluster_tracks:
+            full, labels = self.feature_tracks_clustering()
+            entry.update(full_tracks=full, feature_labels=labels)
         entry.update(ref_xy=self.ref_kp.copy(), cur_xy=self.kp.copy(), status=self.status.copy())
         r = self.b.init_essential(self.ref_kp, self.kp, self.status, self.n_tracks, **self.init_options)
         entry["verdict"] = int(r["verdict"])
@@ -436,6 +465,8 @@ class MonoInitializer:
         res = dict(index=keep, reference_keypoints=self.ref_kp[keep].copy(), current_keypoints=self.kp[keep].copy(),
                    reference_landmark_positions=xyz.copy(), current_landmark_positions=xyz.copy(),
                    pose_q=np.asarray(r["pose_q"], F32), pose_t=np.asarray(r["pose_t"], F32))
+        if self.cluster_tracks:                                  # keep is a subset of the full-length tracks
+            res["track_labels"] = labels[np.searchsorted(full, keep)].copy()
         entry["n_map_points"] = len(keep)
         return res
 
