@@ -225,6 +225,10 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs A) {
     // ================= optimize(10): OptimizationAlgorithmLevenberg::solve
     double lam = -1, ni = 2, chi = 0;
     int iters = 0, trials = 0;
+    // a failed solve leaves dx as it was (g2o keeps its last solution, which starts at zero): without this, a first Cholesky that fails
+    // -- no regulariser edge at all -- would add whatever the LDS held to the estimates and to rho
+    for (int i = lane; i < N; i += 64) dx[i] = 0;
+    __syncthreads();
     for (int it = 0; it < 10; ++it) {
         chi = eval_chi();
         // ---- buildSystem: H (dense, LDS), b
