@@ -269,12 +269,22 @@ class ShiTomasi:
         im = np.ascontiguousarray(im, np.uint8)
         if im.shape[1] < im.shape[0] or im.shape[0] < 5:
             raise ValueError("the reference's row passes index columns up to rows-1: width >= height >= 5 required")
+        held = None
+        if prev_xy is not None and len(prev_xy):
+            # the cells of the held keypoints, before any state changes: a cell outside the image is refused as the C ABI refuses it
+            # (NumPy would wrap a -1 to the last row or column; the reference indexes out of bounds)
+            p = np.asarray(prev_xy, np.float32).reshape(-1, 2).astype(np.float64)
+            if not np.isfinite(p).all():
+                raise ValueError("a held keypoint is not finite")
+            cell = np.sign(p) * np.floor(np.abs(p) + 0.5)
+            if ((cell < 0) | (cell > np.array([im.shape[1] - 1, im.shape[0] - 1]))).any():
+                raise ValueError("a held keypoint rounds to a cell outside the image")
+            held = (_round_half_away(p[:, 1]), _round_half_away(p[:, 0]))
         if self.shape != im.shape:
             self._resize(im.shape)
         (self.scores_literal if literal else self.scores_closed)(im)
-        if prev_xy is not None and len(prev_xy):
-            p = np.asarray(prev_xy, np.float32).reshape(-1, 2)
-            self.scores[_round_half_away(p[:, 1]), _round_half_away(p[:, 0])] = F32(-1.0)
+        if held is not None:
+            self.scores[held] = F32(-1.0)
         lm = self.local_maxima_literal() if literal else self.local_maxima()
         rr, cc = np.nonzero(lm)                                # row-major, like the r / c loops of :77-88
         ids = self.next_id + np.arange(len(rr))
