@@ -111,6 +111,35 @@ extern "C" int nrs_cpu_nd_solve(int32_t n_nodes, const double* pos, const uint8_
     return nrs::nd_host_solve(P, Dn, V.data(), bn, lambda, x) ? 0 : -6;
 }
 
+// Two taps of the plan for the designed systems of tests/nd_cases.py: which front shapes a system reaches, and where a node sits.
+// fronts: 5 ints per front (level, parent front or -1, own unknowns s, boundary unknowns b without the right-hand-side row, workgroups
+// of k_nd_level: its (I >= J) row-block pairs and the inverse one).  Returns the number of fronts (never more than nodes), -1: no plan;
+// writes only if `cap` fronts hold them all.
+extern "C" int nrs_cpu_nd_plan_fronts(int32_t n_nodes, const double* pos, const uint8_t* last, int32_t n_pairs, const int32_t* pairs, int32_t* fronts, int32_t cap) {
+    nrs::NdPlan P;
+    std::string err;
+    if (n_nodes <= 0 || n_pairs < 0 || !nrs::nd_build_plan(n_nodes, pos, last, n_pairs, pairs, P, &err)) return -1;
+    if (!fronts || cap < P.n_fronts) return P.n_fronts;
+    for (int f = 0; f < P.n_fronts; ++f) {
+        const nrs::NdFrontD& D = P.fr[f];
+        int32_t* o = fronts + 5 * (size_t)f;
+        o[0] = D.level; o[1] = D.par; o[2] = D.s; o[3] = D.b; o[4] = 0;
+    }
+    for (size_t w = 0; w < P.wg.size() / 3; ++w) fronts[5 * (size_t)P.wg[3 * w] + 4]++;
+    return P.n_fronts;
+}
+// nodes: 2 ints per node (the front that eliminates it, the column of its first unknown among that front's own columns).  Returns 0, -1: no plan.
+extern "C" int nrs_cpu_nd_plan_nodes(int32_t n_nodes, const double* pos, const uint8_t* last, int32_t n_pairs, const int32_t* pairs, int32_t* nodes) {
+    nrs::NdPlan P;
+    std::string err;
+    if (n_nodes <= 0 || n_pairs < 0 || !nodes || !nrs::nd_build_plan(n_nodes, pos, last, n_pairs, pairs, P, &err)) return -1;
+    for (int f = 0; f < P.n_fronts; ++f) {
+        const nrs::NdFrontD& D = P.fr[f];
+        for (int i = 0; i < D.s / 3; ++i) { const int u = P.own[D.own_off + i]; nodes[2 * (size_t)u] = f; nodes[2 * (size_t)u + 1] = 3 * i; }
+    }
+    return 0;
+}
+
 // Structural invariants of a plan the device kernels rely on (tests/test_nd_cpu.py): returns 0, or the number of the first
 // violated check.  (1) every node is owned by exactly one front; (2) both ends of every pair sit in the front that owns the
 // earlier-eliminated one (own or boundary): the separators separate; (3) a front's boundary is sorted by elimination position and

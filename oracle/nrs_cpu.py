@@ -266,6 +266,38 @@ def nd_plan_check(pos, last, pairs, lib=None):
     return int(lib.nrs_cpu_nd_plan_check(C.c_int32(len(pos)), _p(pos, C.c_double), _p(last, C.c_uint8), C.c_int32(len(pairs)), _p(pairs, C.c_int32)))
 
 
+def nd_plan_fronts(pos, last, pairs, lib=None):
+    """oracle/nd_host.cpp nrs_cpu_nd_plan_fronts: the fronts of the nested-dissection plan as an int array [fronts, 5] with the
+    columns FRONT_COLS: level, parent front (-1: a root), own unknowns s, boundary unknowns b (without the right-hand-side row),
+    workgroups of k_nd_level"""
+    lib = lib or load()
+    pos = np.ascontiguousarray(pos, np.float64)
+    last = None if last is None else np.ascontiguousarray(last, np.uint8)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    out = np.zeros((len(pos), 5), np.int32)                         # (every front owns a node: never more fronts than nodes)
+    nf = int(lib.nrs_cpu_nd_plan_fronts(C.c_int32(len(pos)), _p(pos, C.c_double), _p(last, C.c_uint8), C.c_int32(len(pairs)), _p(pairs, C.c_int32),
+                                        _p(out, C.c_int32), C.c_int32(len(out))))
+    if nf < 0:
+        raise RuntimeError("nrs_cpu_nd_plan_fronts: the plan could not be built")
+    return out[:nf].copy()
+
+
+FRONT_COLS = ("level", "parent", "s", "b", "workgroups")
+
+
+def nd_plan_nodes(pos, last, pairs, lib=None):
+    """oracle/nd_host.cpp nrs_cpu_nd_plan_nodes: per node (the front that eliminates it, the column of its first unknown among that
+    front's own columns) as an int array [nodes, 2]"""
+    lib = lib or load()
+    pos = np.ascontiguousarray(pos, np.float64)
+    last = None if last is None else np.ascontiguousarray(last, np.uint8)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    out = np.full((len(pos), 2), -1, np.int32)
+    if lib.nrs_cpu_nd_plan_nodes(C.c_int32(len(pos)), _p(pos, C.c_double), _p(last, C.c_uint8), C.c_int32(len(pairs)), _p(pairs, C.c_int32), _p(out, C.c_int32)) != 0:
+        raise RuntimeError("nrs_cpu_nd_plan_nodes: the plan could not be built")
+    return out
+
+
 def nd_solve(pos, last, pairs, Dn, Vp, bn, lam=0.0, lib=None):
     """oracle/nd_host.cpp: the nested-dissection plan of nr-slam_amd/csrc/nrs_nd_plan.hpp + its host reference solve of
     (A + lam I) x = b (A: diagonal blocks Dn [n,3,3], pair blocks Vp [p,3,3] with rows = pairs[:,0]'s components).
