@@ -165,7 +165,6 @@ __global__ void k_local_sum(PtrPack in, int world, double* out, size_t n) {
 struct LocalComm : Comm {
     LocalGroup* g = nullptr;
     DevBuf tmp;
-    ~LocalComm() override { if (tmp.p) (void)hipFree(tmp.p); }
     int allreduce(nrs_ctx* c, const double* send, double* recv, size_t n) override {
         g->slot[rank] = send;
         NRS_LOCAL(c, g, hip_rc(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize"));
@@ -207,13 +206,13 @@ struct LocalComm : Comm {
 
 void comm_free(nrs_ctx* c) {
     // exchanges may still be in flight on either stream: drain both before the communicator goes away
-    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
+    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream.get());
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     delete c->comm;
     c->comm = nullptr;
-    if (c->comm_stream) { (void)hipStreamDestroy(c->comm_stream); c->comm_stream = nullptr; }
-    if (c->ev_vec) { (void)hipEventDestroy(c->ev_vec); c->ev_vec = nullptr; }
-    if (c->ev_halo) { (void)hipEventDestroy(c->ev_halo); c->ev_halo = nullptr; }
+    c->comm_stream.reset();
+    c->ev_vec.reset();
+    c->ev_halo.reset();
 }
 
 // Every rank passes the status of its rank-local set-up; all of them return NRS_OK, or none does.  Without
@@ -239,9 +238,9 @@ int comm_agree(nrs_ctx* c, int rc) {
 // second stream + the two events that order it against the context's stream (hand-offs are events only)
 static int comm_streams(nrs_ctx* c) {
     NRS_HIP(c, hipSetDevice(c->device));
-    if (!c->comm_stream) NRS_HIP(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-    if (!c->ev_vec) NRS_HIP(c, hipEventCreateWithFlags(&c->ev_vec, hipEventDisableTiming));
-    if (!c->ev_halo) NRS_HIP(c, hipEventCreateWithFlags(&c->ev_halo, hipEventDisableTiming));
+    if (!c->comm_stream) NRS_HIP(c, stream_create(c->comm_stream));
+    if (!c->ev_vec) NRS_HIP(c, event_create(c->ev_vec));
+    if (!c->ev_halo) NRS_HIP(c, event_create(c->ev_halo));
     return NRS_OK;
 }
 

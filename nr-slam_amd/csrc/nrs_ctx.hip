@@ -12,6 +12,12 @@ const DebugOpts& DebugOpts::process() {
     static const DebugOpts snap = [] { DebugOpts d; d.load_environment(environ); return d; }();
     return snap;
 }
+
+// The four places the library gives a GPU resource back (nrs_own.hpp): nothing else calls these HIP functions.
+void dev_free(void* p) noexcept { if (p) (void)hipFree(p); }
+void pin_free(void* p) noexcept { if (p) (void)hipHostFree(p); }
+void stream_destroy(ihipStream_t* s) noexcept { if (s) (void)hipStreamDestroy(s); }
+void event_destroy(ihipEvent_t* e) noexcept { if (e) (void)hipEventDestroy(e); }
 }  // namespace nrs
 
 extern "C" int nrs_debug_set(nrs_ctx* c, const char* name, const char* value) {
@@ -45,11 +51,12 @@ extern "C" int nrs_create(nrs_ctx** out, const nrs_options* opt) {
     if (dev >= ndev || hipSetDevice(dev) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
     c->device = dev;
     if (hipGetDeviceProperties(&c->prop, dev) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return NRS_ERR_NO_DEVICE; }
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-        delete c;
+    if (stream_create(c->main_stream) != hipSuccess || event_create(c->ev0, hipEventDefault) != hipSuccess ||
+        event_create(c->ev1, hipEventDefault) != hipSuccess) {
+        delete c;                                                  // (what was created goes with it)
         return NRS_ERR_NO_DEVICE;
     }
+    c->stream = c->main_stream.get();
     *out = c;
     return NRS_OK;
 }
@@ -63,26 +70,9 @@ extern "C" void nrs_destroy(nrs_ctx* c) {
     nrs::shi_free(c);
     nrs::front_free(c);
     nrs::comm_free(c);
-    if (c->pin_scal) (void)hipHostFree(c->pin_scal);
-    if (c->pin_flags) (void)hipHostFree(c->pin_flags);
-    if (c->pin_spec_scal) (void)hipHostFree(c->pin_spec_scal);
-    if (c->pin_spec_flags) (void)hipHostFree(c->pin_spec_flags);
-    if (c->embwin_pin) (void)hipHostFree(c->embwin_pin);
-    for (int j = 0; j < 3; ++j) {
-        if (c->spec_stream[j]) { (void)hipStreamSynchronize(c->spec_stream[j]); (void)hipStreamDestroy(c->spec_stream[j]); }
-        if (c->spec_join[j]) (void)hipEventDestroy(c->spec_join[j]);
-    }
-    if (c->spec_fork) (void)hipEventDestroy(c->spec_fork);
-    for (int j = 0; j < 4; ++j) if (c->spec_back[j]) (void)hipEventDestroy(c->spec_back[j]);
-    if (c->arena_dba.base) (void)hipFree(c->arena_dba.base);
-    if (c->arena_trk.base) (void)hipFree(c->arena_trk.base);
-    c->release(c->po_uv); c->release(c->po_X); c->release(c->po_err);
-    c->release(c->po_level); c->release(c->po_out); c->release(c->po_trace); c->release(c->comm_flag); c->release(c->gather_ws); c->release(c->tap); c->release(c->pack_ws); c->release(c->pack_ws2); c->release(c->pack_ws3); c->release(c->pack_ws4); c->release(c->nd_skin); c->release(c->dba_skin); c->release(c->dba_kft); c->release(c->po_multi);
+    for (auto& s : c->spec_stream) if (s) (void)hipStreamSynchronize(s.get());
     nrs::nd_cache_free(c);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                      // every buffer, pinned word, event and stream it owns
 }
 
 extern "C" const char* nrs_last_error(const nrs_ctx* c) { return c ? c->err : "null context"; }

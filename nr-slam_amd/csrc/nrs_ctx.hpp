@@ -1,4 +1,5 @@
-// Context shared by the C-ABI entry points: one HIP stream, growable device buffers, last-error text.
+// Context shared by the C-ABI entry points: one HIP stream, growable device buffers, last-error text.  The buffers, the pinned words, the
+// streams and the events are owners (nrs_own.hpp): they free themselves when the context, or the state that holds them, is deleted.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -9,15 +10,10 @@
 #include <utility>
 #include <vector>
 #include "../../include/nrs.h"
+#include "nrs_own.hpp"
 #include "nrs_switches.hpp"
 
 namespace nrs {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct Engine;       // nrs_engine.hip
 struct EmbWindow;    // nrs_engine.hpp: the lists of an embedded window built in one call
@@ -25,6 +21,8 @@ struct RgWindow;     // nrs_engine.hpp: what nrs_dba_solve_window_rg leaves next
 struct KltState;     // nrs_klt.hip
 struct ShiState;     // nrs_shi.hip
 struct FrontState;   // nrs_front.hip
+struct PlanWorker;   // nrs_engine_nd.hpp
+struct NdCache;      // nrs_engine_nd.hpp
 
 // Exchange steps of a sharded solve (nrs_comm.hip): one process per GPU, every call is ordered on the
 // context's stream.  Two primitives are all the engine needs:
@@ -41,19 +39,27 @@ struct Comm {
     virtual int exchange(nrs_ctx* c, double* vec, const HaloPlan& h, hipStream_t stream) = 0;   // ordered on `stream`
     virtual int handover(nrs_ctx* c, const double* send, double* recv, size_t n, int from, int to) = 0;   // ordered on the context's stream
 };
-struct Arena { char* base = nullptr; size_t cap = 0, off = 0; };
+struct Arena { DevBuf mem; size_t off = 0; };   // one device allocation that an engine's arrays are carved from (nrs_engine_plan.hpp)
 
 }  // namespace nrs
 
 struct nrs_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // Streams and events come first: members are destroyed in reverse order, so every buffer below is freed while they still exist.
+    nrs::Stream main_stream;         // the context's own stream ...
+    hipStream_t stream = nullptr;    // ... and the stream launches are ordered on: main_stream, but for the time a shadow set's view swaps it (nrs_engine.hip)
+    nrs::Event ev0, ev1;
+    nrs::Stream comm_stream;         // boundary-row exchanges run here, next to the interior tiles on `stream`
+    nrs::Event ev_vec, ev_halo;
+    // speculative LM trials of the single-frame engines (nrs_engine_types.hpp SpecSet): streams and events of the shadow sets
+    nrs::Stream spec_stream[3];
+    nrs::Event spec_fork, spec_join[3];
+    nrs::Event spec_back[4];         // behind the back pass of the batch's k-th trial (they run one after the other: nd_solve_enqueue)
     hipDeviceProp_t prop;
     nrs_options opt;
     nrs::DebugOpts dbg;              // debug / A-B switches (nrs_switches.hpp): read once at nrs_create, changed by nrs_debug_set only
     char err[512];
     nrs_profile prof;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // scratch for a1
     nrs::DevBuf po_uv, po_X, po_err, po_level, po_out, po_trace, po_multi;   // (po_multi: state + partial slots of the multi-workgroup form)
     // resident BA problem (a3) and per-call tracking problems (a2): one reusable arena each
@@ -63,33 +69,26 @@ struct nrs_ctx {
     nrs::ShiState* shi = nullptr;
     nrs::FrontState* front = nullptr;   // image front end: configuration + the resident grey / CLAHE / Global mask of the last frame
     nrs::Comm* comm = nullptr;       // set by nrs_comm_init_*: BA problems uploaded afterwards are sharded over its ranks
-    hipStream_t comm_stream = nullptr;   // boundary-row exchanges run here, next to the interior tiles on `stream`
-    hipEvent_t ev_vec = nullptr, ev_halo = nullptr;
     nrs::DevBuf tap;                 // residual taps (edge lists by vertex + outputs) of the engine `tap_serial`: built on first use
     unsigned long long tap_serial = 0, engine_serial = 0;
     nrs::DevBuf pack_ws, pack_ws2, pack_ws3, pack_ws4;   // device-side problem construction (scratch plans: nrs_devpack_host.hpp): raw inputs + intermediates, window-edge scratch and output
     nrs::DevBuf dba_skin;            // ... and of the resident BA window (N2b)
+    nrs::DevBuf fused_snap;          // NRS_CHECK_FUSED: the state a fused iteration is launched from twice (nrs_engine_probes.hpp)
     nrs::DevBuf dba_kft;             // embedded BA window: the keyframe-block factorisation (nrs_engine_kft.hpp)
     bool kft_attr_done = false;      // ... its kernels' dynamic-LDS attributes are set on this context's device (kft_kernel_attributes)
     nrs::EmbWindow* dba_embwin = nullptr;   // lists of the resident window when nrs_dba_solve_window_embedded made it (dropped by dba_free)
     nrs::RgWindow* dba_rgwin = nullptr;     // statistics (and host-packed lists) of the resident window when nrs_dba_solve_window_rg made it (dropped by dba_free)
-    void* embwin_pin = nullptr;      // pinned host staging of the device-built lists (nrs_engine_embwin.hpp), kept for the context's lifetime
-    size_t embwin_pin_cap = 0;
+    nrs::PinBuf embwin_pin;          // pinned host staging of the device-built lists (nrs_engine_embwin.hpp), kept for the context's lifetime
     nrs::DevBuf nd_skin;             // embedded mode (nrs_engine_skin.hpp): the skinned observations of the tracking engine
-    void* plan_worker = nullptr;     // nrs_engine_nd.hpp PlanWorker: the helper thread of the direct solver's symbolic phase (one for the context's lifetime)
-    void* nd_cache = nullptr;        // direct solver of the tracking engines (nrs_engine_nd.hpp NdCache; kernels: nrs_nd_kernels.hpp): the last few plans with their device arrays
+    nrs::PlanWorker* plan_worker = nullptr;   // the helper thread of the direct solver's symbolic phase (one for the context's lifetime)
+    nrs::NdCache* nd_cache = nullptr;         // direct solver of the tracking engines (kernels: nrs_nd_kernels.hpp): the last few plans with their device arrays
     nrs::DevBuf comm_flag;           // one double: status word the ranks agree on after a sharded upload
     nrs::DevBuf gather_ws;           // sharded download / taps: two full-length row vectors for the gather (a rank holds its own rows only); released after use
     bool err_local = true;           // last set-up failure may be specific to this rank (allocation, HIP, rank-dependent checks)
-    double* pin_scal = nullptr;      // pinned host mirrors of the engine's scalars / flags
-    int* pin_flags = nullptr;
+    nrs::PinBuf pin_scal, pin_flags; // pinned host mirrors of the engine's scalars (doubles) / flags (ints)
     int seq = 0;                     // sequence number of the last publication the host waited for (pin_flags[7])
-    // speculative LM trials of the single-frame engines (nrs_engine_types.hpp SpecSet): mirrors, streams and events of the shadow sets
-    double* pin_spec_scal = nullptr; int* pin_spec_flags = nullptr;
+    nrs::PinBuf pin_spec_scal, pin_spec_flags;   // ... and of the shadow sets
     int spec_run = 4;                // rejections of the last completed run of an LM iteration (sizes the next batch)
-    hipStream_t spec_stream[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t spec_fork = nullptr, spec_join[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t spec_back[4] = {nullptr, nullptr, nullptr, nullptr};   // behind the back pass of the batch's k-th trial (they run one after the other: nd_solve_enqueue)
 
     int fail(int code, const char* fmt, ...) {
         va_list ap;
@@ -98,24 +97,37 @@ struct nrs_ctx {
         va_end(ap);
         return code;
     }
+    // exactly `bytes` of device memory in b, what it held freed first; the caller words the failure
+    hipError_t alloc(nrs::DevBuf& b, size_t bytes) {
+        b.reset();
+        const hipError_t e = hipMalloc(&b.p, bytes);
+        if (e == hipSuccess) b.cap = bytes; else b.p = nullptr;
+        return e;
+    }
     int ensure(nrs::DevBuf& b, size_t bytes) {
         if (bytes <= b.cap && b.p) return NRS_OK;
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&b.p, want);
+        const size_t want = nrs::grown_bytes(bytes);
+        const hipError_t e = alloc(b, want);
         if (e != hipSuccess) return fail(NRS_ERR_ALLOC, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        b.cap = want;
         if (dbg.is_set(nrs::SW_POISON)) { (void)hipMemset(b.p, 0xFF, want); (void)hipDeviceSynchronize(); }     // (debug: a read of memory nobody wrote shows up as NaN)
         return NRS_OK;
     }
-    void release(nrs::DevBuf& b) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
+    // pinned host memory: kept when it holds `bytes`, else freed first and allocated anew as exactly `bytes` (a site that grows in
+    // larger steps asks for its step); the caller words the failure
+    hipError_t ensure_pinned(nrs::PinBuf& b, size_t bytes, unsigned flags) {
+        if (bytes <= b.cap && b.p) return hipSuccess;
+        b.reset();
+        const hipError_t e = hipHostMalloc(&b.p, bytes, flags);
+        if (e == hipSuccess) b.cap = bytes; else b.p = nullptr;
+        return e;
     }
 };
+
+namespace nrs {
+// a non-blocking stream / an event into its owner
+inline hipError_t stream_create(Stream& s) { hipStream_t h = nullptr; const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking); s.reset(h); return e; }
+inline hipError_t event_create(Event& ev, unsigned flags = hipEventDisableTiming) { hipEvent_t h = nullptr; const hipError_t e = hipEventCreateWithFlags(&h, flags); ev.reset(h); return e; }
+}  // namespace nrs
 
 #define NRS_HIP(ctx, call)                                                                     \
     do {                                                                                       \

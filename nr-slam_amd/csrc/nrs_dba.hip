@@ -605,7 +605,7 @@ extern "C" int nrs_debug_pcg_solve(nrs_ctx* c, int32_t n_rows, const double* Hpp
     int it = 0, ok = 0;
     if (rc == NRS_OK) rc = engine_debug_solve(c, e, Hpp21, bp, D6, Hpl18, bl, lambda, x, x + 6, &it, &ok);
     if (e) engine_destroy(c, e);
-    arena_release(&arena);
+    arena.mem.reset();
     c->comm = keep;
     if (iters) *iters = it;
     if (rc == NRS_OK && !ok) return c->fail(NRS_ERR_NUMERIC, "debug solve: not positive definite or not converged after %d iterations", it);

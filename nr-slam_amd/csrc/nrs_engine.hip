@@ -160,7 +160,7 @@ static int direct_trial_enqueue(nrs_ctx* c, Engine* e, int set, double lam, int*
     const int cur = e->cur, trial = 1 - e->cur;
     const dim3 g(((d.sh_ng + 7) / 8) * 8), b(BLK);
     if (set < 0) {
-        NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam, nullptr, solve_id, nullptr, in_batch ? c->spec_back[0] : nullptr));
+        NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam, nullptr, solve_id, nullptr, in_batch ? c->spec_back[0].get() : nullptr));
         hipLaunchKernelGGL(k_apply_reproj, g, b, 0, c->stream, d, lam, d.pose[cur], d.xl[cur], d.pose[trial], d.xl[trial]);
         NRS_TRY(evaluate<false>(c, e, trial, true));
         *seq = c->seq;
@@ -175,15 +175,15 @@ static int direct_trial_enqueue(nrs_ctx* c, Engine* e, int set, double lam, int*
     d.h_scal = q.h_scal; d.h_flags = q.h_flags;
     if (d.sk_n > 0) { d.sk_part = q.sk_part; d.sk_chi = q.sk_chi; }
     d.pose[trial] = q.pose; d.xl[trial] = q.xl;
-    c->stream = c->spec_stream[set];
-    NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork, 0));
+    c->stream = c->spec_stream[set].get();
+    NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork.get(), 0));
     NdDev nd = nd_alt_dev(e->nd->S(), set);
     nd.out_rows = q.xv; nd.out_pose = q.xp; nd.flags = q.flags; nd.abort = q.abort;
-    NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam, &nd, solve_id, c->spec_back[set], c->spec_back[set + 1]));
+    NRS_TRY(nd_solve_enqueue(c, e->nd->S(), lam, &nd, solve_id, c->spec_back[set].get(), c->spec_back[set + 1].get()));
     hipLaunchKernelGGL(k_apply_reproj, g, b, 0, c->stream, d, lam, d.pose[cur], d.xl[cur], q.pose, q.xl);
     NRS_TRY(evaluate<false>(c, e, trial, true));
     *seq = c->seq;
-    NRS_HIP(c, hipEventRecord(c->spec_join[set], c->stream));
+    NRS_HIP(c, hipEventRecord(c->spec_join[set].get(), c->stream));
     return NRS_OK;
 }
 
@@ -208,7 +208,7 @@ struct PcgSetView {
         d.abort = q.abort; d.abort_id = abort_id;
         e->h_scal = q.h_scal; e->h_flags = q.h_flags;
         e->view_set = set;
-        c->stream = c->spec_stream[set];
+        c->stream = c->spec_stream[set].get();
     }
     ~PcgSetView() { if (on) { e->d = saved; c->stream = main; e->h_scal = hs; e->h_flags = hf; e->view_set = -1; } }
     PcgSetView(const PcgSetView&) = delete;
@@ -288,10 +288,10 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
         if (d.sh_on && d.sh_world > 1) {
             // sharded: the operator reads u of the neighbouring ranks' boundary keyframes (dampers).  The rows
             // travel on the second stream while the interior tiles run; the boundary tiles follow them.
-            NRS_HIP(c, hipEventRecord(c->ev_vec, c->stream));
-            NRS_HIP(c, hipStreamWaitEvent(c->comm_stream, c->ev_vec, 0));
-            NRS_TRY(c->comm->exchange(c, d.uv3, e->halo, c->comm_stream));
-            NRS_HIP(c, hipEventRecord(c->ev_halo, c->comm_stream));
+            NRS_HIP(c, hipEventRecord(c->ev_vec.get(), c->stream));
+            NRS_HIP(c, hipStreamWaitEvent(c->comm_stream.get(), c->ev_vec.get(), 0));
+            NRS_TRY(c->comm->exchange(c, d.uv3, e->halo, c->comm_stream.get()));
+            NRS_HIP(c, hipEventRecord(c->ev_halo.get(), c->comm_stream.get()));
             Dev di = d, db = d;
             for (int cls = 0; cls < 2; ++cls) {
                 di.sh_t0[cls] = d.sh_t0[cls] + d.sh_front[cls];
@@ -306,7 +306,7 @@ static int pcg_enqueue_batch(nrs_ctx* c, Engine* e, double lam, int* it_io, int 
                 hipLaunchKernelGGL(k_skin_op, dim3(d.sk_nblk), dim3(BLK), 0, c->stream, d, it);
                 skin_op_done = true;
             }
-            NRS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_halo, 0));
+            NRS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_halo.get(), 0));
             NRS_TRY(launch_spmv(c, db, lam, it, tol2));
         } else {
             const int reps = c->opt.profile ? PROFILE_REPS : 1;    // (a profiling context has no convergence look-ahead: the launch is idempotent)
@@ -422,7 +422,7 @@ struct TrialBatch {
     explicit TrialBatch(const LmRun& r_) : r(r_) {}
     // an error return with trials in flight: nothing of theirs may outlive the engine the caller is about to drop
     ~TrialBatch() {
-        if (!ok) for (int j = 0; j < std::max(r.n_spec, r.n_spec_pcg); ++j) if (r.c->spec_stream[j]) (void)hipStreamSynchronize(r.c->spec_stream[j]);
+        if (!ok) for (int j = 0; j < std::max(r.n_spec, r.n_spec_pcg); ++j) if (r.c->spec_stream[j]) (void)hipStreamSynchronize(r.c->spec_stream[j].get());
     }
     bool empty() const { return i_pend == n_pend; }
     // the context's stream continues behind every shadow trial of the batch (they read the linearisation and the state)
@@ -440,7 +440,7 @@ struct TrialBatch {
         }
         if (any) NRS_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.e->spec[0].abort), r.e->spec_gen, r.e->n_spec, c->stream));
         for (int j = 0; j < n_pend; ++j)
-            if (pend[j].set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_join[pend[j].set], 0));
+            if (pend[j].set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_join[pend[j].set].get(), 0));
         n_pend = i_pend = 0;
         return NRS_OK;
     }
@@ -464,7 +464,7 @@ struct TrialBatch {
         // of them, default n_spec; 0: none) -- C2: the rejected run 852 -> 642 us of a step, 2.62 -> 2.48 ms per step
         if (qmax == 0 && r.spec_first_pcg > 0 && it < 32 && (e->spec_run_at >> it & 1u)) nb = std::min(1 + r.n_spec_pcg, 1 + r.spec_first_pcg);
         if (nb <= 1) return NRS_OK;
-        NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
+        NRS_HIP(c, hipEventRecord(c->spec_fork.get(), c->stream));
         double l = lam, n = ni;
         for (int j = 0; j < nb; ++j) {
             if (j > 0) { l *= n; n *= 2; if (!std::isfinite(l)) break; }
@@ -474,13 +474,13 @@ struct TrialBatch {
             p.first = qmax == 0 && j > 0 && e->spec_follow_first > 0 ? e->spec_follow_first : first_batch(c, e, qmax + j);
             p.set = j - 1; p.lam = l; p.solve_id = ++e->spec_gen; p.pit = 0;
             PcgSetView v(c, e, p.set, p.solve_id);
-            if (p.set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork, 0));
+            if (p.set >= 0) NRS_HIP(c, hipStreamWaitEvent(c->stream, c->spec_fork.get(), 0));
             NRS_TRY(pcg_begin(c, e, l, &p.pit));
             NRS_TRY(pcg_enqueue_batch(c, e, l, &p.pit, p.first));
             hipLaunchKernelGGL(k_apply, dim3(d.sh_nvb), dim3(BLK), 0, c->stream, d, l, d.pose[e->cur], d.xl[e->cur], d.pose[trial], d.xl[trial]);
             NRS_TRY(evaluate<false>(c, e, trial, false));
             p.seq = c->seq;
-            if (p.set >= 0) NRS_HIP(c, hipEventRecord(c->spec_join[p.set], c->stream));
+            if (p.set >= 0) NRS_HIP(c, hipEventRecord(c->spec_join[p.set].get(), c->stream));
             ++n_pend;
             if (r.spec_dbg) fprintf(stderr, "[spec] it %d trial %d: set %d first %d enqueued\n", it, qmax + j, p.set, p.first);
         }
@@ -498,7 +498,7 @@ struct TrialBatch {
         if (qmax == 0 && r.spec_first > 0) nb = std::min(1 + r.n_spec, 1 + r.spec_first);   // (experiment: NRS_SPEC_FIRST=<n> further trials behind the first of an iteration)
         if (qmax >= 1) nb = std::min(std::min(std::max(c->spec_run - qmax + 1, 2), 1 + r.n_spec), 10 - qmax);
         if (c->dbg.is_set(SW_SPEC_FIXED) && qmax >= 1) nb = std::min(std::min(std::max(1, c->dbg.int_of(SW_SPEC_FIXED)), 1 + r.n_spec), 10 - qmax);
-        if (nb > 1) NRS_HIP(c, hipEventRecord(c->spec_fork, c->stream));
+        if (nb > 1) NRS_HIP(c, hipEventRecord(c->spec_fork.get(), c->stream));
         double l = lam, n = ni;
         const auto tq0 = std::chrono::steady_clock::now();
         for (int j = 0; j < nb; ++j) {
@@ -586,7 +586,7 @@ static int run_trial(const LmRun& r, TrialBatch& tb, int it, int qmax, double la
         NRS_TRY(tb.take(lam, &pp));
         won = pp->set;
         if (won >= 0) { hs = e->spec[won].h_scal; hf = e->spec[won].h_flags; }
-        NRS_TRY(wait_published(c, hf, pp->seq, won >= 0 ? c->spec_stream[won] : c->stream));
+        NRS_TRY(wait_published(c, hf, pp->seq, won >= 0 ? c->spec_stream[won].get() : c->stream));
         if (r.spec_dbg) fprintf(stderr, "[spec] it %d trial %d: result of set %d at +%.1f us\n", it, qmax, won, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tb.t_batch).count());
         done = true;
     } else if (direct) {
@@ -749,7 +749,7 @@ int engine_download(nrs_ctx* c, Engine* e, Pose* poses, double* x) {
     if (poses) NRS_HIP(c, hipMemcpyAsync(poses, d.pose[e->cur], sizeof(Pose) * d.K, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipMemcpyAsync(xl.data(), src, sizeof(double) * xl.size(), hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
-    c->release(c->gather_ws);
+    c->gather_ws.reset();
     if (x)
         for (int v = 0; v < d.M; ++v)
             for (int k = 0; k < 3; ++k) x[3 * (size_t)v + k] = xl[3 * (size_t)e->vrow[v] + k];
@@ -807,7 +807,7 @@ int engine_residuals(nrs_ctx* c, Engine* e, double* r_reproj, double* r_spring, 
     if (r_spring && d.n_sp) NRS_HIP(c, hipMemcpyAsync(r_spring, rs, sizeof(double) * (size_t)d.n_sp, hipMemcpyDeviceToHost, c->stream));
     if (r_damper && d.n_dm) NRS_HIP(c, hipMemcpyAsync(r_damper, rd, sizeof(double) * 3 * (size_t)d.n_dm, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
-    c->release(c->gather_ws);
+    c->gather_ws.reset();
     return NRS_OK;
 }
 

@@ -133,7 +133,6 @@ int engine_nd_debug_solve(nrs_ctx* c, int n_nodes, const double* pos, const uint
 int engine_kft_agree(nrs_ctx* c, Engine* e);   // collective (sharded windows, after the upload's agreement): the factorisation on every rank or on none
 int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const double* in_d, double* out_d, int32_t* out_i);   // include/nrs.h nrs_debug_kft
 void nd_cache_stats(nrs_ctx* c, int64_t out[2]);                   // plans reused / built by the direct solver's cache
-void arena_release(Arena* a);
 void engine_stats(const Engine* e, int64_t stats[5]);              // rows, rows packed here, spring / damper incidence slots, device bytes
 void shard_plan(int K, const int* grp_ptr, int world, int* kb);     // contiguous keyframe ranges, balanced by rows
 int engine_num_poses(const Engine* e);

@@ -325,7 +325,7 @@ int DeviceBuild::host_side() {
     NRS_HIP(c, hipMemcpy(h_fl2, d_flag, sizeof(int) * 2, hipMemcpyDeviceToHost));
     if (h_fl2[0]) return c->fail(NRS_ERR_HIP, "device pack: halo hash overflow in the second pass");
     d.tp_ok = h_fl2[1] ? 0 : 1;
-    if (c->pack_ws2.cap > ((size_t)512 << 20)) c->release(c->pack_ws2);      // intermediates of a large window: not worth keeping resident
+    if (c->pack_ws2.cap > ((size_t)512 << 20)) c->pack_ws2.reset();      // intermediates of a large window: not worth keeping resident
     mark("final arrays");
     engine_compact_headers(c, e);
     NRS_TRY(engine_reset(c, e));

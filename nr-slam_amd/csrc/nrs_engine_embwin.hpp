@@ -378,13 +378,10 @@ static int ew_finish(nrs_ctx* c, const EwBuild& B, const int* kf_rowptr, bool ow
     size_t off[EW_N];
     const size_t bytes = embwin_layout(tot[0], tot[1], tot[2], tot[3], out->sk_held, off);
     NRS_TRY(c->ensure(c->pack_ws4, bytes + 4096));
-    if (bytes > c->embwin_pin_cap) {
-        if (c->embwin_pin) (void)hipHostFree(c->embwin_pin);
-        c->embwin_pin = nullptr; c->embwin_pin_cap = 0;
+    if (bytes > c->embwin_pin.cap) {
         const size_t want = bytes + bytes / 4;
-        hipError_t he = hipHostMalloc(&c->embwin_pin, want, hipHostMallocDefault);
+        hipError_t he = c->ensure_pinned(c->embwin_pin, want, hipHostMallocDefault);
         if (he != hipSuccess) return c->fail(NRS_ERR_ALLOC, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(he));
-        c->embwin_pin_cap = want;
     }
     EmbWindow dv = *out;
     embwin_bind(&dv, c->pack_ws4.as<char>());
@@ -395,10 +392,10 @@ static int ew_finish(nrs_ctx* c, const EwBuild& B, const int* kf_rowptr, bool ow
                            dv.lm_xyz, dv.lm_uv, dv.lm_kf, dv.sk_xyz, dv.sk_uv, dv.sk_kf);
     NRS_HIP(c, hipGetLastError());
     mark("emit + gathers");
-    NRS_HIP(c, hipMemcpyAsync(c->embwin_pin, c->pack_ws4.as<char>(), bytes, hipMemcpyDeviceToHost, st));
+    NRS_HIP(c, hipMemcpyAsync(c->embwin_pin.p, c->pack_ws4.as<char>(), bytes, hipMemcpyDeviceToHost, st));
     NRS_HIP(c, hipStreamSynchronize(st));
     mark("copy back");
-    embwin_bind(out, static_cast<char*>(c->embwin_pin));
+    embwin_bind(out, c->embwin_pin.as<char>());
     out->on_device = 1;
     return NRS_OK;
 }

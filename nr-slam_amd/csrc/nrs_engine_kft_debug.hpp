@@ -88,7 +88,7 @@ int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const d
             NRS_TRY(c->comm->allreduce(c, g, g + n, n));
             NRS_HIP(c, hipMemcpyAsync(out_d, g + n, 8 * n, hipMemcpyDeviceToHost, c->stream));
             NRS_HIP(c, hipStreamSynchronize(c->stream));
-            c->release(c->gather_ws);
+            c->gather_ws.reset();
             int bad = fl[2], any = 0;                              // (a pivot failure on any rank fails every rank)
             NRS_TRY(c->ensure(c->gather_ws, 2 * sizeof(double)));
             double fv = bad ? 1.0 : 0.0, fs = 0.0;
@@ -97,7 +97,7 @@ int engine_kft_debug(nrs_ctx* c, Engine* e, double lam, int what, int k, const d
             NRS_TRY(c->comm->allreduce(c, g, g + 1, 1));
             NRS_HIP(c, hipMemcpyAsync(&fs, g + 1, 8, hipMemcpyDeviceToHost, c->stream));
             NRS_HIP(c, hipStreamSynchronize(c->stream));
-            c->release(c->gather_ws);
+            c->gather_ws.reset();
             any = fs != 0.0;
             fl[2] = any;
         }

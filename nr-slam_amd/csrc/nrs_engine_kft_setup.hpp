@@ -131,7 +131,7 @@ static int kft_setup(nrs_ctx* c, Engine* e, const EngineSpec& s, const std::vect
         c->err[0] = 0;
         fits = false;
     }
-    if (!fits) { c->release(c->dba_kft); return NRS_OK; }
+    if (!fits) { c->dba_kft.reset(); return NRS_OK; }
     mark("device buffer");
     char* base = c->dba_kft.as<char>();
     NRS_TRY(kft_upload(c, P, base));
@@ -160,7 +160,7 @@ int engine_kft_agree(nrs_ctx* c, Engine* e) {
     if (sum != 0.0) {                                              // some rank cannot hold its share: block-Jacobi PCG everywhere
         delete e->kft;
         e->kft = nullptr;
-        c->release(c->dba_kft);
+        c->dba_kft.reset();
     }
     return NRS_OK;
 }

@@ -13,13 +13,13 @@ namespace nrs {
 constexpr int PROFILE_REPS = 4;
 struct Timer {
     nrs_ctx* c; double* acc; int64_t* cnt; int reps;
-    Timer(nrs_ctx* c_, double* a, int64_t* n, int reps_ = 1) : c(c_), acc(a), cnt(n), reps(reps_) { if (c->opt.profile) (void)hipEventRecord(c->ev0, c->stream); }
+    Timer(nrs_ctx* c_, double* a, int64_t* n, int reps_ = 1) : c(c_), acc(a), cnt(n), reps(reps_) { if (c->opt.profile) (void)hipEventRecord(c->ev0.get(), c->stream); }
     ~Timer() {
         if (!c->opt.profile) return;
-        (void)hipEventRecord(c->ev1, c->stream);
-        (void)hipEventSynchronize(c->ev1);
+        (void)hipEventRecord(c->ev1.get(), c->stream);
+        (void)hipEventSynchronize(c->ev1.get());
         float ms = 0;
-        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        (void)hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get());
         *acc += ms / reps;
         *cnt += 1;
     }

@@ -45,27 +45,22 @@ struct NdEngine {
     bool on = false;
 };
 
-static void nd_slot_free(nrs_ctx* c, NdSlot* sl) {
-    if (!sl) return;
-    c->release(sl->ws); c->release(sl->vb);
-    delete sl;
-}
 static void plan_worker_free(nrs_ctx* c);
 void nd_cache_free(nrs_ctx* c) {
     plan_worker_free(c);
-    NdCache* nc = static_cast<NdCache*>(c->nd_cache);
+    NdCache* nc = c->nd_cache;
     if (!nc) return;
-    for (NdSlot* sl : nc->slots) nd_slot_free(c, sl);
+    for (NdSlot* sl : nc->slots) delete sl;
     delete nc;
     c->nd_cache = nullptr;
 }
 void nd_cache_stats(nrs_ctx* c, int64_t out[2]) {
-    const NdCache* nc = static_cast<const NdCache*>(c->nd_cache);
+    const NdCache* nc = c->nd_cache;
     out[0] = nc ? (int64_t)nc->hits : 0; out[1] = nc ? (int64_t)nc->misses : 0;
 }
 static void nd_slot_release(nrs_ctx* c, NdEngine* nd) {            // the engine lets go of its slot: cached ones stay for later frames
     if (!nd || !nd->slot) return;
-    if (nd->slot->cached) nd->slot->busy = false; else nd_slot_free(c, nd->slot);
+    if (nd->slot->cached) nd->slot->busy = false; else delete nd->slot;
     nd->slot = nullptr; nd->on = false;
 }
 
@@ -139,12 +134,7 @@ struct PlanWorker {
     }
 };
 inline void NdPrep::wait() { if (worker) { worker->wait(); worker = nullptr; } }
-static void plan_worker_free(nrs_ctx* c) {                         // (idle: every NdPrep waits for it before it goes away)
-    delete static_cast<PlanWorker*>(c->plan_worker);
-    c->plan_worker = nullptr;
-}
-
-
+static void plan_worker_free(nrs_ctx* c) { delete c->plan_worker; c->plan_worker = nullptr; }   // (idle: every NdPrep waits for it before it goes away)
 
 static void nd_prep_run_body(nrs_ctx* c, const NdIn& in, NdPrep& P);
 // (runs on a helper thread of engine_create: nothing may escape it -- an exception there would end the process)
@@ -161,7 +151,7 @@ static int nd_plan_par_min(const nrs_ctx* c) {
 }
 // the cache (read only here: nobody changes it while an engine is being set up): the free slot an earlier frame left with this key
 static NdSlot* nd_cache_lookup(nrs_ctx* c, const NdPrep& P) {
-    const NdCache* nc = static_cast<const NdCache*>(c->nd_cache);
+    const NdCache* nc = c->nd_cache;
     if (!nc || c->dbg.is_set(SW_ND_NO_CACHE)) return nullptr;
     for (NdSlot* sl : nc->slots)
         if (!sl->busy && sl->st && sl->hash == P.hash && sl->key == P.key) return sl;
@@ -321,16 +311,16 @@ static int nd_engine_finish(nrs_ctx* c, Engine* e, NdEngine* nd, NdPrep& P) {
     StageTimer lapf{c, "direct solve finish:", false};
     nd_slot_release(c, nd);                                        // (a rebuild after the fixed set changed: the old plan goes back to the cache)
     if (!P.wanted || !nd_wanted(c, e->d, P.n_free)) return NRS_OK;
-    NdCache* nc = static_cast<NdCache*>(c->nd_cache);
+    NdCache* nc = c->nd_cache;
     if (!nc) { nc = new (std::nothrow) NdCache(); if (!nc) return c->fail(NRS_ERR_ALLOC, "out of host memory"); c->nd_cache = nc; }
     bool hit = false;
     int rc = NRS_OK;
     NdSlot* sl = nd_slot_acquire(c, nc, P, &hit, &rc);
     if (!sl) return rc;
     struct SlotGuard {                                             // a slot whose set-up fails holds nothing valid
-        nrs_ctx* c; NdSlot* sl; bool keep = false;
-        ~SlotGuard() { if (keep) return; if (sl->cached) { sl->hash = 0; sl->key.clear(); sl->key.push_back(0xFF); sl->used = 0; } else nd_slot_free(c, sl); }
-    } sguard{c, sl};
+        NdSlot* sl; bool keep = false;
+        ~SlotGuard() { if (keep) return; if (sl->cached) { sl->hash = 0; sl->key.clear(); sl->key.push_back(0xFF); sl->used = 0; } else delete sl; }
+    } sguard{sl};
     if (!hit) {
         bool fits = true;
         NRS_TRY(nd_slot_upload_plan(c, sl, P, e->n_spec, &fits));

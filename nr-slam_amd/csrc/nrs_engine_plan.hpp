@@ -203,12 +203,6 @@ static int shard_window(nrs_ctx* c, Dev& d, HaloPlan& h, const EngineSpec& s, co
 }
 
 // ---- device memory: one arena allocation, reused across calls when large enough
-void arena_release(Arena* a) {
-    if (a->base) (void)hipFree(a->base);
-    a->base = nullptr;
-    a->cap = a->off = 0;
-}
-
 struct ArenaPlan {                   // two passes: size, then carve
     Arena* a;
     bool dry;
@@ -216,7 +210,7 @@ struct ArenaPlan {                   // two passes: size, then carve
     size_t row_lo = 0, row_n = 0;    // the rows this engine holds of every per-row array (a rank of a sharded window: its keyframes and one ghost keyframe either side)
     template <class Tp> Tp* get(size_t n) {
         const size_t bytes = ((n * sizeof(Tp) + 255) / 256) * 256 + 256;
-        Tp* p = dry ? nullptr : reinterpret_cast<Tp*>(a->base + off);
+        Tp* p = dry ? nullptr : reinterpret_cast<Tp*>(a->mem.as<char>() + off);
         off += bytes;
         return p;
     }
@@ -347,14 +341,12 @@ static int arena_fit(nrs_ctx* c, Arena* arena, Engine* e, Dev& d, bool has_X0, s
         te.n_spec = e->n_spec; te.spec_pcg = e->spec_pcg;
         carve(dry, tmp, has_X0, nnz_s, nnz_d, n_slices, n_halo, &te);
     }
-    if (dry.off > arena->cap) {
+    if (dry.off > arena->mem.cap) {
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        arena_release(arena);
         const size_t want = dry.off + dry.off / 8;
-        hipError_t he = hipMalloc((void**)&arena->base, want);
+        hipError_t he = c->alloc(arena->mem, want);                // (the old arena is freed first)
         if (he != hipSuccess) return c->fail(NRS_ERR_ALLOC, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(he));
-        arena->cap = want;
-        if (c->dbg.is_set(SW_POISON)) { (void)hipMemset(arena->base, 0xFF, want); (void)hipDeviceSynchronize(); }    // (debug: a read of memory nobody wrote shows up as NaN)
+        if (c->dbg.is_set(SW_POISON)) { (void)hipMemset(arena->mem.p, 0xFF, want); (void)hipDeviceSynchronize(); }    // (debug: a read of memory nobody wrote shows up as NaN)
     }
     ArenaPlan real{arena, false};
     carve(real, d, has_X0, nnz_s, nnz_d, n_slices, n_halo, e);
@@ -397,18 +389,17 @@ static int zero_work_arrays(nrs_ctx* c, Dev& d) {
 }
 
 // host words the kernels publish into (mapped: the same pointer on the device)
-template <class Tp>
-static hipError_t pinned_words(Tp** p, size_t n) { return hipHostMalloc((void**)p, sizeof(Tp) * n, hipHostMallocMapped | hipHostMallocCoherent); }
+constexpr unsigned PIN_PUBLISHED = hipHostMallocMapped | hipHostMallocCoherent;
 
 // the engine's scalar and status mirrors live in the context (reused by every engine)
 static int pin_host_words(nrs_ctx* c, Engine* e) {
-    if (!c->pin_scal) NRS_HIP(c, pinned_words(&c->pin_scal, SC_N));
-    if (!c->pin_flags) {
-        NRS_HIP(c, pinned_words(&c->pin_flags, 8));
-        memset(c->pin_flags, 0, sizeof(int) * 8);                  // [7] is the publication sequence word the host polls
+    NRS_HIP(c, c->ensure_pinned(c->pin_scal, sizeof(double) * SC_N, PIN_PUBLISHED));
+    if (!c->pin_flags.p) {
+        NRS_HIP(c, c->ensure_pinned(c->pin_flags, sizeof(int) * 8, PIN_PUBLISHED));
+        memset(c->pin_flags.p, 0, sizeof(int) * 8);                // [7] is the publication sequence word the host polls
     }
-    e->h_scal = e->d.h_scal = c->pin_scal;
-    e->h_flags = e->d.h_flags = c->pin_flags;
+    e->h_scal = e->d.h_scal = c->pin_scal.as<double>();
+    e->h_flags = e->d.h_flags = c->pin_flags.as<int>();
     return NRS_OK;
 }
 

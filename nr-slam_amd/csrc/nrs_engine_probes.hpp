@@ -15,13 +15,14 @@ namespace nrs {
 // Phase clocks of ONE launch (100 MHz wall clock): the kernel's waves / tiles stamp Dev::dbg_clk, 8 words per record; the constructor
 // hands a zeroed buffer to a Dev copy, the destructor waits for the stream and prints the mean length of each phase
 struct PhaseClocks {
-    nrs_ctx* c; long long* buf = nullptr; size_t n_rec;
+    nrs_ctx* c; DevBuf mem; long long* buf = nullptr; size_t n_rec;
     const char *kernel, *unit;                                     // the printed line's kernel name and what a record is ("wave", "tile")
     std::vector<const char*> phases;                               // record words k .. k + 1 bound phase k
     // (on: the probe's condition; the buffer goes to d, a Dev copy of the launch to be timed)
     PhaseClocks(nrs_ctx* c_, bool on, Dev& d, size_t n_rec_, const char* kernel_, const char* unit_, std::vector<const char*> phases_)
         : c(c_), n_rec(n_rec_), kernel(kernel_), unit(unit_), phases(std::move(phases_)) {
-        if (!on || hipMalloc((void**)&buf, sizeof(long long) * 8 * n_rec) != hipSuccess) { buf = nullptr; return; }
+        if (!on || c->ensure(mem, sizeof(long long) * 8 * n_rec) != NRS_OK) return;
+        buf = mem.as<long long>();
         (void)hipMemsetAsync(buf, 0, sizeof(long long) * 8 * n_rec, c->stream);
         d.dbg_clk = buf;
     }
@@ -31,7 +32,7 @@ struct PhaseClocks {
         (void)hipStreamSynchronize(c->stream);
         std::vector<long long> h(8 * n_rec);
         (void)hipMemcpy(h.data(), buf, sizeof(long long) * 8 * n_rec, hipMemcpyDeviceToHost);
-        (void)hipFree(buf);
+        mem.reset();
         const size_t np = phases.size();
         std::vector<double> acc(np, 0.0);
         long long t_min = LLONG_MAX, t_max = 0;
@@ -118,8 +119,8 @@ static int check_fused_launch(nrs_ctx* c, const Dev& d, dim3 g, size_t shm, doub
                        {d.part_spmv2, npart, "part1"}, {d.scal, sizeof(double) * SC_N, "scal"}, {d.flags, sizeof(int) * 8, "flags"}};
     size_t total = 0;
     for (const Arr& a : arr) total += (a.bytes + 255) & ~(size_t)255;
-    static char* snap = nullptr; static size_t snap_cap = 0;
-    if (snap_cap < total) { if (snap) (void)hipFree(snap); NRS_HIP(c, hipMalloc((void**)&snap, total)); snap_cap = total; }
+    NRS_TRY(c->ensure(c->fused_snap, total));                      // (kept in the context: an owner with static storage would free after the runtime is gone)
+    char* snap = c->fused_snap.as<char>();
     std::vector<char> h1(total), h2(total);
     auto gather = [&](char* dst, hipMemcpyKind kind) -> int {
         size_t o = 0;

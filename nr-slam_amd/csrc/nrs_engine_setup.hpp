@@ -15,22 +15,22 @@ void engine_edge_counts(const Engine* e, int* n_sp, int* n_dm) { *n_sp = e->d.n_
 // context's streams and events for them (created on first use)
 static int spec_prepare(nrs_ctx* c, Engine* e) {
     const Dev& d = e->d;
-    if (!c->pin_spec_scal) {
-        NRS_HIP(c, pinned_words(&c->pin_spec_scal, SC_N * SPEC_MAX));
-        NRS_HIP(c, pinned_words(&c->pin_spec_flags, 8 * SPEC_MAX));
-        memset(c->pin_spec_flags, 0, sizeof(int) * 8 * SPEC_MAX);
+    if (!c->pin_spec_scal.p) {
+        NRS_HIP(c, c->ensure_pinned(c->pin_spec_scal, sizeof(double) * SC_N * SPEC_MAX, PIN_PUBLISHED));
+        NRS_HIP(c, c->ensure_pinned(c->pin_spec_flags, sizeof(int) * 8 * SPEC_MAX, PIN_PUBLISHED));
+        memset(c->pin_spec_flags.p, 0, sizeof(int) * 8 * SPEC_MAX);
         // (measured and dropped: shadow streams at the lowest priority so that they yield to the context's stream -- a level of the
         // factorisation on such a stream takes 57 us instead of 28 even with the device to itself)
         for (int j = 0; j < SPEC_MAX; ++j) {
-            NRS_HIP(c, hipStreamCreateWithFlags(&c->spec_stream[j], hipStreamNonBlocking));
-            NRS_HIP(c, hipEventCreateWithFlags(&c->spec_join[j], hipEventDisableTiming));
+            NRS_HIP(c, stream_create(c->spec_stream[j]));
+            NRS_HIP(c, event_create(c->spec_join[j]));
         }
-        NRS_HIP(c, hipEventCreateWithFlags(&c->spec_fork, hipEventDisableTiming));
-        for (int j = 0; j < 1 + SPEC_MAX; ++j) NRS_HIP(c, hipEventCreateWithFlags(&c->spec_back[j], hipEventDisableTiming));
+        NRS_HIP(c, event_create(c->spec_fork));
+        for (int j = 0; j < 1 + SPEC_MAX; ++j) NRS_HIP(c, event_create(c->spec_back[j]));
     }
     for (int j = 0; j < e->n_spec; ++j) {
         SpecSet& q = e->spec[j];
-        q.h_scal = c->pin_spec_scal + SC_N * j; q.h_flags = c->pin_spec_flags + 8 * j;
+        q.h_scal = c->pin_spec_scal.as<double>() + SC_N * j; q.h_flags = c->pin_spec_flags.as<int>() + 8 * j;
         NRS_HIP(c, hipMemsetAsync(q.part_apply, 0, sizeof(double) * (size_t)d.n_vecblk, c->stream));
         NRS_HIP(c, hipMemsetAsync(q.part_rchi, 0, sizeof(double) * (size_t)d.n_groups, c->stream));
         NRS_HIP(c, hipMemsetAsync(q.part_reg, 0, sizeof(double) * 2 * (size_t)d.n_regblk, c->stream));
@@ -234,7 +234,7 @@ static int nd_plan_start(nrs_ctx* c, const EngineSpec& s, Engine* e, NdIn& nd_in
     nd_in.vpos = e->nd->pos.data();
     bool inline_run = c->dbg.is_set(SW_HOST_THREADS) && c->dbg.int_of(SW_HOST_THREADS) <= 1;
     if (!inline_run) {
-        PlanWorker* pw = static_cast<PlanWorker*>(c->plan_worker);
+        PlanWorker* pw = c->plan_worker;
         if (!pw) {
             pw = new (std::nothrow) PlanWorker();
             if (pw && !pw->start()) { delete pw; pw = nullptr; }
@@ -1000,7 +1000,7 @@ int engine_skin_positions(nrs_ctx* c, Engine* e, double* xyz) {
     if (d.sh_on) { NRS_TRY(c->comm->allreduce(c, in, in + m, m)); res = in + m; }
     NRS_HIP(c, hipMemcpyAsync(xyz, res, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
-    c->release(c->gather_ws);
+    c->gather_ws.reset();
     return NRS_OK;
 }
 int engine_skin_stats(const Engine* e, int64_t out[3]) {

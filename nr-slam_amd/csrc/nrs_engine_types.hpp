@@ -1,6 +1,7 @@
 // Types, constants and device helpers of the graph-LM engine (included by nrs_engine.hip only).
 // Part of nrs_engine.hip (one translation unit); see that file's header for the design.
 #pragma once
+#include <type_traits>
 
 namespace nrs {
 
@@ -201,6 +202,7 @@ struct Dev {
                                      // share k_skin_rows adds to D for the preconditioner -- k_spmv applies these (k_skin_op / the row pass apply A_o whole); null: D
     double* pk; double* pk_loc;      // evaluation packet: [0] chi2 [1] scale [2..2+world) max diag per rank, then K x 27 (H_pp, b_p)
 };
+static_assert(std::is_trivially_copyable_v<Dev>, "passed to kernels by value: plain pointers, never an owner");
 
 // factor recomputation of a tile class (Dev::rc): with the damper part on, the operator stages the positions of the whole halo,
 // which has to fit a workgroup's 64 KB -- a class of outlier halos keeps its dampers' factors stored

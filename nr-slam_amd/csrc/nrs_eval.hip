@@ -410,9 +410,8 @@ static int stereo_match_shell(nrs_ctx* c, const char* who, const nrs_camera* cam
     const size_t img = on_device ? 0 : (size_t)w * h, ws_bytes = stereo_match_ws_bytes(c, w, h, n);
     const size_t bytes = 2 * padded(img) + padded(sizeof(float) * 2 * n) + ws_bytes + padded(sizeof(float) * 3 * n) + padded(sizeof(int) * n) +
                          padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n);
-    DevBuf big;
+    DevBuf big;                                                    // (freed when the call returns)
     NRS_TRY(c->ensure(big, bytes));
-    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
     Carver cv(big.as<char>());
     const uint8_t *d_left = left, *d_right = right;
     if (!on_device) {
@@ -463,9 +462,8 @@ extern "C" int nrs_eval_depth_ground_truth(nrs_ctx* c, const nrs_camera* cam, co
     if (n == 0) return NRS_OK;
     NRS_HIP(c, hipSetDevice(c->device));
     const size_t img = (size_t)w * h;
-    DevBuf big;
+    DevBuf big;                                                    // (freed when the call returns)
     NRS_TRY(c->ensure(big, padded(sizeof(float) * img) + padded(sizeof(float) * 2 * n) + padded(sizeof(float) * 3 * n) + padded(sizeof(int) * n)));
-    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
     Carver cv(big.as<char>());
     float* d_m = cv.take<float>(img);
     float* d_xy = cv.take<float>(2 * (size_t)n);

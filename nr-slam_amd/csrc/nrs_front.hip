@@ -245,16 +245,8 @@ __global__ void k_front_mask_at(const uint8_t* __restrict__ mask, int w, int h, 
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-static void front_release(nrs_ctx* c, FrontState* f) {
-    DevBuf* bufs[] = {&f->raw, &f->gray, &f->clahe, &f->global, &f->tmp_a, &f->tmp_f, &f->lut, &f->at, &f->raw_r, &f->gray_r, &f->clahe_r, &f->lut_r};
-    for (auto b : bufs) c->release(*b);
-    for (auto& b : f->fmask) c->release(b);
-    delete f;
-}
-
 void front_free(nrs_ctx* c) {
-    if (!c->front) return;
-    front_release(c, c->front);
+    delete c->front;
     c->front = nullptr;
 }
 

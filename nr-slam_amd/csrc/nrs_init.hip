@@ -8,6 +8,7 @@
 //   k_init_reconstruct  one workgroup: arg-max (highest score, lowest h), the inlier flags of the winner, DecomposeEssentialMatrix /
 //                       ReconstructCameras (:284-318) and ReconstructPoints (:320-410) with the counters and the verdict
 // The fp32 steps run with contraction off in the operation order of tests/init_oracle.py; no atomics (every count is a reduction).
+#include <type_traits>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -33,6 +34,7 @@ struct InitArgs {
     // packed result (one download): header words, then the arrays
     int* hdr; float* xyz; int* code; float* hyp_E; int* hyp_score; int* samples; int* labels; float* centres; uint8_t* inlier;
 };
+static_assert(std::is_trivially_copyable_v<InitArgs>, "passed to kernels by value: plain pointers, never an owner");
 
 // ---- workgroup helpers (IN_T threads)
 __device__ inline int block_excl_scan(int v, int* sm, int& total) {
@@ -510,9 +512,8 @@ extern "C" int nrs_init_essential(nrs_ctx* c, const nrs_camera* cam, const nrs_i
     const size_t ws_bytes = al(4 * NC) + al(8 * NC) + al(12 * NC) * 2 + al(4 * NC) * 2 + al(64);
     const size_t o_hdr = 0, o_xyz = o_hdr + al(4 * IN_HDR), o_code = o_xyz + al(12 * N), o_hE = o_code + al(4 * N), o_hs = o_hE + al(36 * NH),
                  o_smp = o_hs + al(4 * NH), o_lab = o_smp + al(32 * NH), o_cen = o_lab + al(4 * NC), o_inl = o_cen + al(64), out_bytes = o_inl + al((size_t)n_matches);
-    DevBuf big;
+    DevBuf big;                                                    // (freed when the call returns)
     NRS_TRY(c->ensure(big, in_bytes + ws_bytes + out_bytes + 256));
-    struct Free1 { nrs_ctx* c; DevBuf* b; ~Free1() { c->release(*b); } } fr1{c, &big};
     char* p = big.as<char>();
     InitArgs A;
     A.cam.model = cam->model;

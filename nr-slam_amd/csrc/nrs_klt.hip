@@ -15,6 +15,7 @@
 //     are row-major float loops (LK:377-407) and float addition does not commute, so bit-identical
 //     status codes need the same order.  Exact-integer sums (window mean) use wave reductions.
 //   * the fp32 arithmetic is compiled with contraction off (separate mul/add, like the oracle).
+#include <type_traits>
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -38,12 +39,14 @@ struct Pyr {
     PyrLevel L[KMAXL];
     int n_levels;
 };
+static_assert(std::is_trivially_copyable_v<Pyr>, "passed to kernels by value: plain pointers, never an owner");
 
 // What a kernel is handed of a set of templates: entry e, level l is item e * levels + l of every array (sizes: nrs_klt_host.hpp)
 struct TemplateView {
     short* I; short2* D; float* mean; uint8_t* valid;
     int levels;
 };
+static_assert(std::is_trivially_copyable_v<TemplateView>, "passed to kernels by value: plain pointers, never an owner");
 
 // A set of templates in HBM: the four arrays, `levels` levels an entry, room for `cap` entries, and one side array of side_bytes per
 // entry -- the tracker's reference points, or the archive's "has" bytes (side_zero: they read zero wherever the set has grown)
@@ -55,11 +58,7 @@ struct TemplateSet {
     const char* what;                        // names the set in an error text
     TemplateSet(int levels_, size_t side_bytes_, bool side_zero_, const char* what_) : levels(levels_), side_bytes(side_bytes_), side_zero(side_zero_), what(what_) {}
     TemplateView view() const { return TemplateView{arr[0].as<short>(), arr[1].as<short2>(), arr[2].as<float>(), arr[3].as<uint8_t>(), levels}; }
-    void release(nrs_ctx* c) {
-        for (DevBuf& b : arr) c->release(b);
-        c->release(side);
-        cap = 0;
-    }
+    void clear() { *this = TemplateSet(levels, side_bytes, side_zero, what); }   // holds nothing again: the old buffers are freed here
     // Room for `want` entries, the first `keep` of them carried over.  All or nothing: after a failure the set is what it was, nothing
     // new is left allocated and the context's error is set.  Waits for the stream once, behind the copies
     int reserve(nrs_ctx* c, int want, int keep) {
@@ -71,10 +70,10 @@ struct TemplateSet {
         int rc = NRS_OK;
         for (int a = 0; a < KLT_ARRAYS && rc == NRS_OK; ++a) rc = c->ensure(g.arr[a], klt_entry_bytes(a, levels) * g.cap);
         if (rc == NRS_OK) rc = c->ensure(g.side, side_bytes * g.cap);
-        if (rc != NRS_OK) { g.release(c); return rc; }             // nothing of a half-made set is kept
+        if (rc != NRS_OK) return rc;                               // nothing of a half-made set is kept: g frees what it got
         if (side_zero) {
             he = hipMemsetAsync(g.side.p, 0, side_bytes * g.cap, c->stream);
-            if (he != hipSuccess) { g.release(c); return c->fail(NRS_ERR_HIP, "%s: clearing the grown buffers failed: %s", what, hipGetErrorString(he)); }
+            if (he != hipSuccess) return c->fail(NRS_ERR_HIP, "%s: clearing the grown buffers failed: %s", what, hipGetErrorString(he));
         }
         if (keep > 0) {
             const size_t m = (size_t)keep;
@@ -82,16 +81,10 @@ struct TemplateSet {
                 he = hipMemcpyAsync(g.arr[a].p, arr[a].p, klt_entry_bytes(a, levels) * m, hipMemcpyDeviceToDevice, c->stream);
             if (he == hipSuccess) he = hipMemcpyAsync(g.side.p, side.p, side_bytes * m, hipMemcpyDeviceToDevice, c->stream);
             if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-            if (he != hipSuccess) {                                // (the new buffers do not outlive a failed copy; the set stays as it was)
-                g.release(c);
-                return c->fail(NRS_ERR_HIP, "%s: copy to the grown buffers failed: %s", what, hipGetErrorString(he));
-            }
+            // (the new buffers do not outlive a failed copy; the set stays as it was)
+            if (he != hipSuccess) return c->fail(NRS_ERR_HIP, "%s: copy to the grown buffers failed: %s", what, hipGetErrorString(he));
         }
-        const int grown = g.cap;
-        release(c);
-        for (int a = 0; a < KLT_ARRAYS; ++a) arr[a] = g.arr[a];
-        side = g.side;
-        cap = grown;
+        *this = std::move(g);                                      // the old buffers are freed here, the grown ones move in
         return NRS_OK;
     }
 };
@@ -261,6 +254,7 @@ struct TrackArgs {
     int* status;           // in/out
     TemplateView t;        // read only
 };
+static_assert(std::is_trivially_copyable_v<TrackArgs>, "passed to kernels by value: plain pointers, never an owner");
 
 __device__ inline bool usable(int s) { return s == NRS_TRACKED_WITH_3D || s == NRS_TRACKED || s == NRS_JUST_TRIANGULATED; }
 
@@ -495,13 +489,7 @@ static KltState* klt(nrs_ctx* c) {
 }
 
 void klt_free(nrs_ctx* c) {
-    if (!c->klt) return;
-    KltState* k = c->klt;
-    DevBuf* bufs[] = {&k->pyr_buf, &k->img_in, &k->mask_in, &k->pts, &k->status, &k->misc, &k->a_idx, &k->reuse_in, &k->reuse_ws, &k->reuse_out};
-    for (auto b : bufs) c->release(*b);
-    k->tmpl.release(c);
-    k->arch.release(c);
-    delete k;
+    delete c->klt;
     c->klt = nullptr;
 }
 
@@ -558,7 +546,7 @@ extern "C" int nrs_klt_configure(nrs_ctx* c, const nrs_klt_config* cfg) {
     if (cfg->max_level + 1 != k->tmpl.levels && k->tmpl.cap > 0) {
         // the template buffers are sized cap x levels: another level count invalidates them (k->n == 0 here)
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        k->tmpl.release(c);
+        k->tmpl.clear();
     }
     k->max_level = cfg->max_level; k->tmpl.levels = cfg->max_level + 1;          // max_level + 1 slots per point
     k->max_iters = cfg->max_iters; k->eps = cfg->epsilon; k->min_eig = cfg->min_eig_threshold;
@@ -776,7 +764,7 @@ extern "C" int nrs_klt_archive_templates(nrs_ctx* c, int32_t n, const int32_t* s
     NRS_HIP(c, hipSetDevice(c->device));
     if (k->arch.levels != k->tmpl.levels && k->arch.cap > 0) {     // (another level count: the archive starts over)
         NRS_HIP(c, hipStreamSynchronize(c->stream));
-        k->arch.release(c);
+        k->arch.clear();
         k->a_has.clear();
     }
     k->arch.levels = k->tmpl.levels;

@@ -231,8 +231,7 @@ extern "C" int nrs_map_frame(nrs_ctx* c, const nrs_camera* cam, int32_t n_frames
         return NRS_OK;
     }
     const size_t fbytes = (sizeof(float) * (size_t)n_frames + 255) / 256 * 256;
-    DevBuf big;
-    struct Free2 { nrs_ctx* c; DevBuf* b; ~Free2() { c->release(*b); } } fr2{c, &big};
+    DevBuf big;                                                    // (freed when the call returns)
     TriArgs T;
     char* p = nullptr;
     StageTimer tm{c, "nrs_map_frame", true};

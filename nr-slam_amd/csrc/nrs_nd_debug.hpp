@@ -44,8 +44,9 @@ static void nd_debug_report_clocks(nrs_ctx* c, const NdPlan& P, const std::vecto
 // ... taken from one more solve, every level in a launch of its own
 static int nd_debug_phase_clocks(nrs_ctx* c, NdSolver& S, double lam) {
     const size_t nw = S.plan.wg.size() / 3 + (size_t)S.plan.n_fronts;
-    long long* clk = nullptr;
-    NRS_HIP(c, hipMalloc((void**)&clk, sizeof(long long) * 8 * nw));
+    DevBuf buf;
+    NRS_TRY(c->ensure(buf, sizeof(long long) * 8 * nw));
+    long long* clk = buf.as<long long>();
     NRS_HIP(c, hipMemsetAsync(clk, 0, sizeof(long long) * 8 * nw, c->stream));
     S.dev.clk = clk;
     NRS_TRY(nd_solve_enqueue(c, S, lam));
@@ -53,7 +54,7 @@ static int nd_debug_phase_clocks(nrs_ctx* c, NdSolver& S, double lam) {
     std::vector<long long> h(8 * nw);
     NRS_HIP(c, hipMemcpyAsync(h.data(), clk, sizeof(long long) * 8 * nw, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(clk);
+    buf.reset();
     nd_debug_report_clocks(c, S.plan, h);
     return NRS_OK;
 }
@@ -66,7 +67,7 @@ int engine_nd_debug_solve(nrs_ctx* c, int n_nodes, const double* pos, const uint
     std::string err;
     if (!nd_build_plan(n_nodes, pos, last, n_pairs, pairs, S.plan, &err, nd_leaf_n(c), ND_SMAXN, true, 0, !c->dbg.is_set(SW_ND_NO_COVER))) return c->fail(NRS_ERR_INVALID, "direct solve: %s", err.c_str());
     nd_stats(S.plan, stats);
-    struct Rel { nrs_ctx* c; NdSolver* s; ~Rel() { (void)hipStreamSynchronize(c->stream); c->release(s->own); } } rel{c, &S};
+    struct Sync { nrs_ctx* c; ~Sync() { (void)hipStreamSynchronize(c->stream); } } sync{c};   // (S.own is freed right after it, when S goes)
     NRS_TRY(nd_upload(c, S));
     std::vector<double> V, ev(9 * S.plan.ent.size(), 0.0);
     nd_orient_pairs(S.plan, pairs, Vp, V);
@@ -79,12 +80,12 @@ int engine_nd_debug_solve(nrs_ctx* c, int n_nodes, const double* pos, const uint
     NRS_TRY(nd_solve_enqueue(c, S, lam));                          // (warm-up and the result)
     NRS_HIP(c, hipStreamSynchronize(c->stream));
     if (repeats > 0) {
-        NRS_HIP(c, hipEventRecord(c->ev0, c->stream));
+        NRS_HIP(c, hipEventRecord(c->ev0.get(), c->stream));
         for (int r = 0; r < repeats; ++r) NRS_TRY(nd_solve_enqueue(c, S, lam));
-        NRS_HIP(c, hipEventRecord(c->ev1, c->stream));
-        NRS_HIP(c, hipEventSynchronize(c->ev1));
+        NRS_HIP(c, hipEventRecord(c->ev1.get(), c->stream));
+        NRS_HIP(c, hipEventSynchronize(c->ev1.get()));
         float ms = 0;
-        NRS_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        NRS_HIP(c, hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()));
         if (ms_per_solve) *ms_per_solve = ms / repeats;
     }
     if (c->dbg.is_set(SW_ND_DBG)) NRS_TRY(nd_debug_phase_clocks(c, S, lam));

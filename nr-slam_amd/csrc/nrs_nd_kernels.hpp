@@ -21,6 +21,7 @@
 // This file is the device code; around it: nrs_nd_solver.hpp (upload and launches), nrs_nd_debug.hpp (the solver on its own),
 // nrs_nd_prep_host.hpp (the set-up's host stages, no HIP) and nrs_engine_nd.hpp (plan cache, plan thread, the two set-up phases).
 #pragma once
+#include <type_traits>
 #include "nrs_nd_plan.hpp"
 
 namespace nrs {
@@ -48,6 +49,7 @@ struct NdDev {
                                      // remaining workgroups of its FACTORISATION return at once (null: never); they wait for nobody, so a stale read only costs time
     long long* clk;                  // NRS_ND_DBG: 8 phase clocks (100 MHz) per workgroup of the factorisation, then per front of the back substitution; else null
 };
+static_assert(std::is_trivially_copyable_v<NdDev>, "passed to kernels by value: plain pointers, never an owner");
 
 // value of lane K of the caller's 16-lane row, in every lane of the row: DPP row_newbcast (a plain VALU move, no SGPR round trip)
 template <int K>
@@ -878,6 +880,7 @@ struct NdVals {                      // (NdPairD: nrs_nd_plan.hpp, next to NdEnt
     // embedded mode: per entry the skinned observations that add to it (fixed order) with their weight products
     const int* ske_ptr; const int* ske_pt; const double* ske_coef;
 };
+static_assert(std::is_trivially_copyable_v<NdVals>, "passed to kernels by value: plain pointers, never an owner");
 
 __device__ inline int nd_hpp_idx(int r, int cc) { return r * 6 - (r * (r - 1)) / 2 + (cc - r); }   // H_pp packed upper-triangular (r <= cc)
 

@@ -18,6 +18,9 @@ struct NdStage {
 };
 
 struct NdSolver {
+    NdSolver() = default;
+    NdSolver(NdSolver&&) = delete;   // `buf` may point at `own`: a solver stays where it was made (cache slots are held by pointer)
+    NdSolver& operator=(NdSolver&&) = delete;
     NdPlan plan;
     NdDev dev;
     DevBuf own;                      // everything the kernels read: plan arrays, entry values, assembly areas, L, x ...

@@ -8,6 +8,7 @@
 // loads that stay in L1/L2: 20 B/point), reduce with wave butterflies + LDS, and lane 0 runs
 // the LM control flow, the Cholesky of H+lambda*I and the SE(3) retraction.  No host round trips,
 // no inter-workgroup hand-offs; latency per trial is a few microseconds.
+#include <type_traits>
 #include <algorithm>
 #include <cstddef>
 #include <cstdlib>
@@ -39,6 +40,7 @@ struct PoseOnlyArgs {
     int* counters;      // [0] trials, [1] iterations
     int cache_pts;      // 1: uv/X of all points are cached in LDS (n * 20 B of dynamic LDS)
 };
+static_assert(std::is_trivially_copyable_v<PoseOnlyArgs>, "passed to kernels by value: plain pointers, never an owner");
 
 __device__ inline bool chol6_solve(const double* Hu /*21 upper, row-major packed*/, double lam,
                                    const double* b, double* x) {

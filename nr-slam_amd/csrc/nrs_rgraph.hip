@@ -29,28 +29,27 @@ __global__ void k_rg_fill(uint8_t* st, size_t n);
 
 // The dense state: four capacity x capacity arrays, held all or not at all
 struct RgDense {
-    float *maxd = nullptr, *mind = nullptr, *d0 = nullptr;
-    uint8_t* st = nullptr;
-    // the four arrays and, enqueued on `s`, the "no edge" fill of the status.  On failure nothing is held; *filling: the arrays were
-    // there and the fill's launch failed
-    hipError_t alloc(int cap, hipStream_t s, bool* filling) {
+    DevBuf b_maxd, b_mind, b_d0, b_st;
+    float* maxd() const { return b_maxd.as<float>(); }
+    float* mind() const { return b_mind.as<float>(); }
+    float* d0() const { return b_d0.as<float>(); }
+    uint8_t* st() const { return b_st.as<uint8_t>(); }
+    // the four arrays and, enqueued on the context's stream, the "no edge" fill of the status.  On failure nothing is held; *filling:
+    // the arrays were there and the fill's launch failed
+    hipError_t alloc(nrs_ctx* c, int cap, bool* filling) {
         const size_t n2 = (size_t)cap * cap;
         *filling = false;
-        hipError_t e = hipMalloc((void**)&maxd, n2 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&mind, n2 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&d0, n2 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&st, n2);
+        hipError_t e = c->alloc(b_maxd, n2 * sizeof(float));
+        if (e == hipSuccess) e = c->alloc(b_mind, n2 * sizeof(float));
+        if (e == hipSuccess) e = c->alloc(b_d0, n2 * sizeof(float));
+        if (e == hipSuccess) e = c->alloc(b_st, n2);
         if (e == hipSuccess) {
             *filling = true;
-            hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, st, n2);
+            hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, c->stream, st(), n2);
             e = hipGetLastError();
         }
-        if (e != hipSuccess) free();
+        if (e != hipSuccess) *this = RgDense();
         return e;
-    }
-    void free() {
-        for (void* p : {(void*)maxd, (void*)mind, (void*)d0, (void*)st}) if (p) (void)hipFree(p);
-        *this = RgDense();
     }
 };
 }  // namespace nrs
@@ -61,11 +60,9 @@ struct nrs_rgraph : nrs::RgDense {
     float sigma = 1.f, stretch_th = 1.1f, min_w = 0.f;
     nrs::DevBuf pos, ids_a, ids_b, out_i, good, skip, slot, walk;   // (walk: the device-side neighbour walk of a2, rg_walk)
     nrs::DevBuf mir;                 // status + longest distance once more as FULL matrices (k_rg_mirror), for GetEdges over many rows
-    void release_bufs() { for (nrs::DevBuf* b : {&pos, &ids_a, &ids_b, &out_i, &good, &skip, &slot, &walk, &mir}) c->release(*b); }
     int last_n_ids = 0, last_cap = 0;  // shape of the lists out_i holds (the last GetEdges)
     std::vector<int> h_slot;
-    char* pin = nullptr;             // pinned staging area of the GetEdges results (page-faulting pageable targets cost more than the kernel)
-    size_t pin_cap = 0;
+    nrs::PinBuf pin;                 // pinned staging area of the GetEdges results (page-faulting pageable targets cost more than the kernel)
     void set_sigma(float s) { sigma = s; min_w = nrs::rg_min_weight(s); }
     nrs::RgDense& dense() { return *this; }
 };
@@ -355,7 +352,7 @@ static int rg_refused(nrs_ctx* c, int rc, const char* msg) { return rc == 0 ? NR
 // the four arrays of a graph of `cap` points with the fill enqueued, or the failure in the name of `who` with nothing held
 static int rg_alloc_dense(nrs_ctx* c, RgDense* d, int cap, const char* who) {
     bool filling = false;
-    const hipError_t e = d->alloc(cap, c->stream, &filling);
+    const hipError_t e = d->alloc(c, cap, &filling);
     if (e == hipSuccess) return NRS_OK;
     if (filling) return c->fail(NRS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     const int rc = c->fail(NRS_ERR_ALLOC, "%s: %zu bytes for %d points: %s", who, (size_t)cap * cap * 13, cap, hipGetErrorString(e));
@@ -380,7 +377,7 @@ extern "C" int nrs_rgraph_create(nrs_ctx* c, int32_t capacity, float sigma, floa
     int rc = rg_alloc_dense(c, g, capacity, "nrs_rgraph_create");
     if (rc == NRS_OK) {
         const hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { rc = c->fail(NRS_ERR_HIP, "nrs_rgraph_create: %s", hipGetErrorString(e)); g->free(); }
+        if (e != hipSuccess) rc = c->fail(NRS_ERR_HIP, "nrs_rgraph_create: %s", hipGetErrorString(e));
     }
     if (rc != NRS_OK) { delete g; return rc; }                     // (nothing is held: neither the arrays nor the object)
     *out = g;
@@ -392,9 +389,6 @@ extern "C" void nrs_rgraph_destroy(nrs_rgraph* g) {
     nrs_ctx* c = g->c;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    g->free();
-    if (g->pin) (void)hipHostFree(g->pin);
-    g->release_bufs();
     delete g;
 }
 
@@ -426,7 +420,7 @@ extern "C" int nrs_rgraph_add_edges(nrs_rgraph* g, const float* pos, int32_t n_n
     for (int a0 = 0; a0 < n_new; a0 += 32768) {                   // grid.y limit
         const int na = std::min(32768, n_new - a0);
         hipLaunchKernelGGL(k_rg_add, dim3((n_other + 255) / 256, na), dim3(256), 0, c->stream, na, g->ids_a.as<int>() + a0, n_other,
-                           g->ids_b.as<int>(), g->pos.as<float>(), g->cap, g->maxd, g->mind, g->d0, g->st);
+                           g->ids_b.as<int>(), g->pos.as<float>(), g->cap, g->maxd(), g->mind(), g->d0(), g->st());
     }
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipStreamSynchronize(c->stream));
@@ -452,13 +446,13 @@ extern "C" int nrs_rgraph_update(nrs_rgraph* g, const float* pos, int32_t n_ids,
         NRS_TRY(c->ensure(g->slot, sizeof(int) * (size_t)g->cap));
         NRS_HIP(c, hipMemcpyAsync(g->slot.p, g->h_slot.data(), sizeof(int) * (size_t)g->cap, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_rg_update_tri, dim3((g->cap + RG_TC - 1) / RG_TC, (g->cap + RG_TR - 1) / RG_TR), dim3(RG_TC), 0, c->stream,
-                           g->slot.as<int>(), g->pos.as<float>(), g->cap, g->maxd, g->mind, g->st, g->stretch_th, g->good.as<int>());
+                           g->slot.as<int>(), g->pos.as<float>(), g->cap, g->maxd(), g->mind(), g->st(), g->stretch_th, g->good.as<int>());
     }
     const int bx = std::max(1, std::min(8, (g->cap + 1023) / 1024));
     for (int a0 = 0; a0 < n_ids && !tri; a0 += 32768) {
         const int na = std::min(32768, n_ids - a0);
         hipLaunchKernelGGL(k_rg_update, dim3(bx, na), dim3(256), 0, c->stream, na, g->ids_a.as<int>() + a0, g->pos.as<float>(), g->cap,
-                           g->maxd, g->mind, g->st, g->stretch_th, g->good.as<int>() + a0);
+                           g->maxd(), g->mind(), g->st(), g->stretch_th, g->good.as<int>() + a0);
     }
     NRS_HIP(c, hipGetLastError());
     NRS_HIP(c, hipMemcpyAsync(good_count, g->good.p, sizeof(int) * (size_t)n_ids, hipMemcpyDeviceToHost, c->stream));
@@ -609,12 +603,9 @@ static int rg_ge_staging(nrs_rgraph* g, const RgListLayout& L) {
     nrs_ctx* c = g->c;
     NRS_TRY(c->ensure(g->ids_a, sizeof(int) * (size_t)L.n_ids));
     NRS_TRY(c->ensure(g->out_i, L.bytes()));
-    if (L.bytes() > g->pin_cap) {
-        if (g->pin) (void)hipHostFree(g->pin);
-        g->pin = nullptr; g->pin_cap = 0;
+    if (L.bytes() > g->pin.cap) {
         const size_t want = L.bytes() + L.bytes() / 4;
-        if (hipHostMalloc((void**)&g->pin, want, hipHostMallocDefault) != hipSuccess) return c->fail(NRS_ERR_ALLOC, "nrs_rgraph_get_edges: %zu bytes of pinned host memory", want);
-        g->pin_cap = want;
+        if (c->ensure_pinned(g->pin, want, hipHostMallocDefault) != hipSuccess) return c->fail(NRS_ERR_ALLOC, "nrs_rgraph_get_edges: %zu bytes of pinned host memory", want);
     }
     return NRS_OK;
 }
@@ -643,7 +634,7 @@ static int rg_ge_mirror(nrs_rgraph* g, int n_ids, const uint8_t** st_f, const fl
     const int nt = (g->cap + 63) / 64;
     uint8_t* s = g->mir.as<uint8_t>();
     float* m = reinterpret_cast<float*>(g->mir.as<char>() + o_m);
-    hipLaunchKernelGGL(k_rg_mirror, dim3(nt, nt), dim3(256), 0, c->stream, g->cap, g->st, g->maxd, s, m);
+    hipLaunchKernelGGL(k_rg_mirror, dim3(nt, nt), dim3(256), 0, c->stream, g->cap, g->st(), g->maxd(), s, m);
     NRS_HIP(c, hipGetLastError());
     *st_f = s; *maxd_f = m;
     return NRS_OK;
@@ -654,14 +645,14 @@ static int rg_ge_mirror(nrs_rgraph* g, int n_ids, const uint8_t** st_f, const fl
 static int rg_ge_passes(nrs_rgraph* g, const RgGetEdges& a, const RgListLayout& L, size_t cand_limit, const uint8_t* st_f, const float* maxd_f) {
     nrs_ctx* c = g->c;
     int* d = g->out_i.as<int>();
-    int* h = reinterpret_cast<int*>(g->pin);
+    int* h = g->pin.as<int>();
     const float d_hi = rg_far_distance(g->sigma);
     g->last_n_ids = 0; g->last_cap = 0;                            // (the lists out_i held are overwritten from here on)
     for (int pass = 0; pass < 2; ++pass) {
         const RgPass p = rg_pass_plan(pass, g->cap, a.cap_per_point, cand_limit);
         NRS_HIP(c, hipMemsetAsync(d + L.overflow, 0, sizeof(int), c->stream));
         NRS_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rg_get_edges), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-        hipLaunchKernelGGL(k_rg_get_edges, dim3(a.n_ids), dim3(64), p.lds_bytes, c->stream, a.n_ids, g->ids_a.as<int>(), g->cap, g->maxd, g->d0, g->st, g->sigma,
+        hipLaunchKernelGGL(k_rg_get_edges, dim3(a.n_ids), dim3(64), p.lds_bytes, c->stream, a.n_ids, g->ids_a.as<int>(), g->cap, g->maxd(), g->d0(), g->st(), g->sigma,
                            g->min_w, d_hi, p.cand_cap, a.cap_per_point, pass, a.pass_over ? g->skip.as<uint8_t>() : nullptr, d, d + L.col,
                            reinterpret_cast<float*>(d + L.w), reinterpret_cast<float*>(d + L.d0), d + L.status, d + L.overflow, st_f, maxd_f);
         NRS_HIP(c, hipGetLastError());
@@ -691,7 +682,7 @@ static int rg_get_edges_impl(nrs_rgraph* g, const RgGetEdges& a, RgDeviceLists* 
     const float* maxd_f = nullptr;
     NRS_TRY(rg_ge_mirror(g, a.n_ids, &st_f, &maxd_f));
     NRS_TRY(rg_ge_passes(g, a, L, cand_limit, st_f, maxd_f));
-    *host = L.view(g->pin);
+    *host = L.view(g->pin.as<char>());
     return NRS_OK;
 }
 int rg_get_edges_staged(nrs_rgraph* g, int32_t n_ids, const int32_t* ids, int32_t cap_per_point, RgDeviceLists* host, const uint8_t* pass_over, bool lists_to_host) {
@@ -732,10 +723,10 @@ extern "C" int nrs_rgraph_edge(nrs_rgraph* g, int32_t i, int32_t j, float out[4]
     NRS_HIP(c, hipSetDevice(c->device));
     const size_t k = i < j ? (size_t)i * g->cap + j : (size_t)j * g->cap + i;
     uint8_t s = 0;
-    NRS_HIP(c, hipMemcpy(&s, g->st + k, 1, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(&out[2], g->maxd + k, 4, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(&out[3], g->mind + k, 4, hipMemcpyDeviceToHost));
-    NRS_HIP(c, hipMemcpy(&out[1], g->d0 + k, 4, hipMemcpyDeviceToHost));
+    NRS_HIP(c, hipMemcpy(&s, g->st() + k, 1, hipMemcpyDeviceToHost));
+    NRS_HIP(c, hipMemcpy(&out[2], g->maxd() + k, 4, hipMemcpyDeviceToHost));
+    NRS_HIP(c, hipMemcpy(&out[3], g->mind() + k, 4, hipMemcpyDeviceToHost));
+    NRS_HIP(c, hipMemcpy(&out[1], g->d0() + k, 4, hipMemcpyDeviceToHost));
     out[0] = rg_weight(out[2], g->sigma);
     *status = s == RG_NONE ? -1 : (int32_t)s;
     return NRS_OK;
@@ -761,10 +752,10 @@ extern "C" int nrs_rgraph_rows(nrs_rgraph* g, int32_t n_ids, const int32_t* ids,
             if (i > 0) NRS_HIP(c, hipMemcpy2D(dst + (size_t)r * cap, sizeof(float), src + i, sizeof(float) * (size_t)cap, sizeof(float), (size_t)i, hipMemcpyDeviceToHost));
             return NRS_OK;
         };
-        NRS_TRY(fetch(g->maxd, maxd)); NRS_TRY(fetch(g->mind, mind)); NRS_TRY(fetch(g->d0, d0));
+        NRS_TRY(fetch(g->maxd(), maxd)); NRS_TRY(fetch(g->mind(), mind)); NRS_TRY(fetch(g->d0(), d0));
         if (status) {
-            NRS_HIP(c, hipMemcpy(status + (size_t)r * cap + i, g->st + (size_t)i * cap + i, (size_t)(cap - i), hipMemcpyDeviceToHost));
-            if (i > 0) NRS_HIP(c, hipMemcpy2D(status + (size_t)r * cap, 1, g->st + i, (size_t)cap, 1, (size_t)i, hipMemcpyDeviceToHost));
+            NRS_HIP(c, hipMemcpy(status + (size_t)r * cap + i, g->st() + (size_t)i * cap + i, (size_t)(cap - i), hipMemcpyDeviceToHost));
+            if (i > 0) NRS_HIP(c, hipMemcpy2D(status + (size_t)r * cap, 1, g->st() + i, (size_t)cap, 1, (size_t)i, hipMemcpyDeviceToHost));
             status[(size_t)r * cap + i] = RG_NONE;
         }
     }
@@ -785,26 +776,21 @@ extern "C" int nrs_rgraph_resize(nrs_rgraph* g, int32_t new_capacity) {
     RgDense n;
     NRS_TRY(rg_alloc_dense(c, &n, new_capacity, "nrs_rgraph_resize (as nrs_rgraph_create)"));
     // (the float arrays are read only where the status says there is an edge; zeroed all the same so that no cell is undefined)
-    hipError_t e = hipMemsetAsync(n.maxd, 0, n2 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(n.mind, 0, n2 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(n.d0, 0, n2 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(n.maxd, ncap * 4, g->maxd, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(n.mind, ncap * 4, g->mind, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(n.d0, ncap * 4, g->d0, oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(n.st, ncap, g->st, oc, oc, oc, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = hipMemsetAsync(n.maxd(), 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(n.mind(), 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(n.d0(), 0, n2 * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.maxd(), ncap * 4, g->maxd(), oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.mind(), ncap * 4, g->mind(), oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.d0(), ncap * 4, g->d0(), oc * 4, oc * 4, oc, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(n.st(), ncap, g->st(), oc, oc, oc, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        const int rc = c->fail(NRS_ERR_HIP, "nrs_rgraph_resize: %s", hipGetErrorString(e));
-        n.free();
-        return rc;
-    }
-    g->free();
-    g->dense() = n;
+    if (e != hipSuccess) return c->fail(NRS_ERR_HIP, "nrs_rgraph_resize: %s", hipGetErrorString(e));   // (n frees the new arrays)
+    g->dense() = std::move(n);                                     // the old arrays are freed here
     g->cap = new_capacity;
     // what was sized or filled for the old capacity: the GetEdges lists on the device (rg_walk refuses to read them), the full-matrix
     // mirrors (rebuilt by the next GetEdges) and the position / flag buffers (re-ensured by every call)
     g->last_n_ids = 0; g->last_cap = 0;
-    c->release(g->mir);
+    g->mir.reset();
     g->h_slot.clear();
     return NRS_OK;
 }

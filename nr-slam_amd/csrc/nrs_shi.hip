@@ -225,11 +225,7 @@ __global__ void k_shi_emit(const uint8_t* __restrict__ flags, int w, const int* 
 }
 
 void shi_free(nrs_ctx* c) {
-    if (!c->shi) return;
-    ShiState* s = c->shi;
-    DevBuf* bufs[] = {&s->img, &s->xg, &s->yg, &s->scores, &s->flags, &s->rowcnt, &s->rowoff, &s->prev, &s->out_xy, &s->out_id};
-    for (auto b : bufs) c->release(*b);
-    delete s;
+    delete c->shi;
     c->shi = nullptr;
 }
 

@@ -485,9 +485,8 @@ extern "C" int nrs_dbscan3d(nrs_ctx* c, int32_t n, const float* xyz, double eps,
     // in: m | xyz[3n];  out: counts[4] | raw[n] | label[n], one download
     const size_t in_bytes = padded(sizeof(int)) + padded(sizeof(float) * 3 * (size_t)n), out_words = 4 + 2 * (size_t)n;
     const size_t bytes = in_bytes + padded(sizeof(int) * out_words) + db_ws_bytes(n);
-    DevBuf big;
+    DevBuf big;                                                    // (freed when the call returns)
     NRS_TRY(c->ensure(big, bytes));
-    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
     Carver cv(big.as<char>());
     int* d_m = cv.take<int>(1);
     float* d_xyz = cv.take<float>(3 * (size_t)n);
@@ -527,9 +526,8 @@ static int sinit_run(nrs_ctx* c, const char* who, const nrs_camera* cam, const n
     const size_t ws_bytes = stereo_match_ws_bytes(c, w, h, n);
     const size_t bytes = padded(U.bytes) + ws_bytes + padded(sizeof(double) * n) + padded(sizeof(int) * 2 * n) + padded(sizeof(int) * L.words) +
                          padded(sizeof(int) * n) + padded(sizeof(float) * 3 * n) + 2 * padded(sizeof(int) * n) + padded(sizeof(int) * 4) + db_ws_bytes(n);
-    DevBuf big;
+    DevBuf big;                                                    // (freed when the call returns)
     NRS_TRY(c->ensure(big, bytes));
-    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
     Carver cv(big.as<char>());
     char* d_in = cv.take<char>(U.bytes);
     char* d_ws = cv.take<char>(ws_bytes);
@@ -587,9 +585,8 @@ static int dbnd_run(nrs_ctx* c, const char* who, int n, int dim, int length, con
                     int32_t* label, int32_t counts[2]) {
     NRS_HIP(c, hipSetDevice(c->device));
     const FlowcScratch S((size_t)n, (size_t)dim, (size_t)length);
-    DevBuf big;
+    DevBuf big;                                                    // (freed when the call returns)
     NRS_TRY(c->ensure(big, S.bytes));
-    struct Free { nrs_ctx* c; DevBuf* b; ~Free() { c->release(*b); } } fr{c, &big};
     char* base = big.as<char>();
     int* d_m = reinterpret_cast<int*>(base + S.m);
     float* d_in = reinterpret_cast<float*>(base + S.in);

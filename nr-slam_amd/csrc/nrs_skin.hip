@@ -93,8 +93,7 @@ extern "C" int nrs_skin_select_nodes(nrs_ctx* c, int32_t n_points, const float* 
     if (!c) return NRS_ERR_INVALID;
     if (!pos || !node_ids || n_points <= 0 || n_nodes <= 0 || n_nodes > n_points) return c->fail(NRS_ERR_INVALID, "nrs_skin_select_nodes: bad argument");
     NRS_HIP(c, hipSetDevice(c->device));
-    DevBuf d_pos, d_el, d_mind, d_out;
-    struct Rel { nrs_ctx* c; DevBuf *a, *b, *d, *e; ~Rel() { c->release(*a); c->release(*b); c->release(*d); c->release(*e); } } rel{c, &d_pos, &d_el, &d_mind, &d_out};
+    DevBuf d_out, d_mind, d_el, d_pos;                             // (freed when the call returns, d_pos first)
     NRS_TRY(c->ensure(d_pos, sizeof(float) * 3 * (size_t)n_points));
     NRS_TRY(c->ensure(d_mind, sizeof(float) * (size_t)n_points));
     NRS_TRY(c->ensure(d_out, sizeof(int) * ((size_t)n_nodes + 1)));

@@ -10,6 +10,7 @@
 //                   [snapshot][row]; for the last snapshot the status and the row -> id table
 // and then the launches of nrs_map_frame, unchanged (map_run, nrs_map.hip), whose two id lists leave as keypoint ids.
 // The host knows the number of distinct ids (reference counts), the span and the candidate count: nothing is read back before the result.
+#include <type_traits>
 #include <new>
 #include <vector>
 #include "nrs_ctx.hpp"
@@ -23,9 +24,8 @@ struct nrs_tbuf {
     nrs::TbufHost h;
     nrs::DevBuf slots;               // n_slots x tb_slot_words(h.cap) words
     nrs::DevBuf ws;                  // the dense tables (TbLayout) + the mapping call's work area
-    uint32_t* pin = nullptr;         // pinned staging of one snapshot
-    size_t pin_words = 0;
-    hipEvent_t ev_up = nullptr;      // behind the last upload from `pin`
+    nrs::PinBuf pin;                 // pinned staging of one snapshot
+    nrs::Event ev_up;                // behind the last upload from `pin`
     bool up_pending = false;
     std::vector<uint64_t> seen;      // scratch of the duplicate check
 };
@@ -42,6 +42,7 @@ struct TbFlat {
     int id_lo, span, n;
     int* row; uint8_t* has_kp; float* kp_xy; uint8_t* has_lm; float* lm_xyz; int* status; int* row_id; float* poses; float* mag;
 };
+static_assert(std::is_trivially_copyable_v<TbFlat>, "passed to kernels by value: plain pointers, never an owner");
 
 // entry e of the concatenated snapshots -> (snapshot f, entry j); false past the end
 __device__ inline bool tb_entry(const TbSnaps& S, int e, int& f, int& j) {
@@ -115,15 +116,11 @@ __global__ __launch_bounds__(256) void k_tb_scatter(TbFlat A) {
 // the pinned staging area holds a snapshot of `words` words; an upload still reading it is waited for first
 static int tb_stage(nrs_tbuf* tb, size_t words) {
     nrs_ctx* c = tb->c;
-    if (tb->up_pending) { NRS_HIP(c, hipEventSynchronize(tb->ev_up)); tb->up_pending = false; }
-    if (words <= tb->pin_words) return NRS_OK;
-    if (tb->pin) (void)hipHostFree(tb->pin);
-    tb->pin = nullptr; tb->pin_words = 0;
-    if (hipHostMalloc((void**)&tb->pin, 4 * words, hipHostMallocDefault) != hipSuccess) {
+    if (tb->up_pending) { NRS_HIP(c, hipEventSynchronize(tb->ev_up.get())); tb->up_pending = false; }
+    if (c->ensure_pinned(tb->pin, 4 * words, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         return c->fail(NRS_ERR_ALLOC, "nrs_tbuf: %zu bytes of pinned host memory", 4 * words);
     }
-    tb->pin_words = words;
     return NRS_OK;
 }
 
@@ -137,9 +134,8 @@ static int tb_grow_slots(nrs_tbuf* tb, int new_cap) {
     if (tb->slots.p && !tb->h.snaps.empty())
         e = hipMemcpy2DAsync(nb.p, 4 * nw, tb->slots.p, 4 * ow, 4 * ow, (size_t)tb->h.n_slots(), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { c->release(nb); return c->fail(NRS_ERR_HIP, "nrs_tbuf: moving the slots: %s", hipGetErrorString(e)); }
-    c->release(tb->slots);
-    tb->slots = nb;
+    if (e != hipSuccess) return c->fail(NRS_ERR_HIP, "nrs_tbuf: moving the slots: %s", hipGetErrorString(e));   // (nb frees the new slots)
+    tb->slots = std::move(nb);                                     // the old slots are freed here
     return NRS_OK;
 }
 
@@ -197,7 +193,7 @@ extern "C" int nrs_tbuf_create(nrs_ctx* c, int32_t max_buffer_size, nrs_tbuf** o
     tb_reset(tb->h, max_buffer_size);
     int rc = tb_grow_slots(tb, tb->h.cap);
     if (rc == NRS_OK) rc = tb_stage(tb, tb_slot_words(tb->h.cap));
-    if (rc == NRS_OK && hipEventCreateWithFlags(&tb->ev_up, hipEventDisableTiming) != hipSuccess) rc = c->fail(NRS_ERR_HIP, "nrs_tbuf_create: hipEventCreate failed");
+    if (rc == NRS_OK && event_create(tb->ev_up) != hipSuccess) rc = c->fail(NRS_ERR_HIP, "nrs_tbuf_create: hipEventCreate failed");
     if (rc != NRS_OK) { nrs_tbuf_destroy(tb); return rc; }
     *out = tb;
     return NRS_OK;
@@ -208,9 +204,6 @@ extern "C" void nrs_tbuf_destroy(nrs_tbuf* tb) {
     nrs_ctx* c = tb->c;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (tb->ev_up) (void)hipEventDestroy(tb->ev_up);
-    if (tb->pin) (void)hipHostFree(tb->pin);
-    c->release(tb->slots); c->release(tb->ws);
     delete tb;
 }
 
@@ -232,9 +225,9 @@ extern "C" int nrs_tbuf_insert(nrs_tbuf* tb, int32_t n, const int32_t* kp_id, co
     if (plan.new_cap > tb->h.cap) { NRS_TRY(tb_grow_slots(tb, plan.new_cap)); tb->h.cap = plan.new_cap; }
     const size_t words = (size_t)TBUF_HEAD + (size_t)TBUF_ENTRY * (size_t)plan.m;
     NRS_TRY(tb_stage(tb, tb_slot_words(tb->h.cap)));
-    tb_pack(in, plan, tb->pin);
-    NRS_HIP(c, hipMemcpyAsync(tb->slots.as<uint32_t>() + (size_t)plan.slot * tb_slot_words(tb->h.cap), tb->pin, 4 * words, hipMemcpyHostToDevice, c->stream));
-    NRS_HIP(c, hipEventRecord(tb->ev_up, c->stream));
+    tb_pack(in, plan, tb->pin.as<uint32_t>());
+    NRS_HIP(c, hipMemcpyAsync(tb->slots.as<uint32_t>() + (size_t)plan.slot * tb_slot_words(tb->h.cap), tb->pin.p, 4 * words, hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipEventRecord(tb->ev_up.get(), c->stream));
     tb->up_pending = true;
     tb_commit(tb->h, in, plan);
     return NRS_OK;

@@ -112,16 +112,17 @@ __global__ void k_graph_update(int n_ids, const int* __restrict__ ids, const int
 
 struct GraphDevice {            // device mirror of an nrs_graph for the duration of one call
     nrs_ctx* c;
-    std::vector<void*> allocs;
+    std::vector<DevBuf> allocs;
     int *rowptr = nullptr, *col = nullptr, *eid = nullptr, *status = nullptr, *rank = nullptr, *count = nullptr;
     int *o_rowptr = nullptr, *o_col = nullptr, *o_eid = nullptr, *ids = nullptr, *good = nullptr;
     float *w = nullptr, *mx = nullptr, *mn = nullptr, *pos = nullptr;
     int n = 0, nnz = 0, ne = 0;
-    ~GraphDevice() { for (void* p : allocs) (void)hipFree(p); }
     template <class Tp> int alloc(Tp** p, size_t n_) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(16, n_ * sizeof(Tp)));
+        DevBuf b;
+        hipError_t e = c->alloc(b, std::max<size_t>(16, n_ * sizeof(Tp)));
         if (e != hipSuccess) return c->fail(NRS_ERR_ALLOC, "hipMalloc failed: %s", hipGetErrorString(e));
-        allocs.push_back(*p);
+        *p = b.as<Tp>();
+        allocs.push_back(std::move(b));
         return NRS_OK;
     }
 };

@@ -453,8 +453,7 @@ extern "C" int nrs_triangulate_batch(nrs_ctx* c, const nrs_camera* cam, int32_t 
     }
     if (n_cand == 0) return NRS_OK;
     const size_t extra = sizeof(int) * 2 * (size_t)n_cand + sizeof(float) * 3 * (size_t)n_cand + sizeof(double) * 4 * (size_t)n_cand + 256 * 5;
-    DevBuf big;
-    struct Free2 { nrs_ctx* c; DevBuf* b; ~Free2() { c->release(*b); } } fr2{c, &big};
+    DevBuf big;                                                    // (freed when the call returns)
     TriArgs A;
     char* p = nullptr;
     NRS_TRY(tri_upload(c, big, extra, cam, n_frames, poses, n_ids, has_kp, kp_xy, has_lm, lm_xyz, last_status, min_track, A, &p));

@@ -1,6 +1,7 @@
 // What nrs_triang.hip (f2: DeformableTriangulation) and nrs_map.hip (Mapping::LandmarkTriangulation) share: the device-side flat
 // TemporalBuffer, the keypoint distance of GetClosestMapPointsToFeature, and the upload + launch of k_triangulate.
 #pragma once
+#include <type_traits>
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
 
@@ -25,6 +26,7 @@ struct TriArgs {
     double* o_dbg;               // n_cand x 4 or null: final chi2, LM iterations, trials, regulariser edges
     const uint8_t* close_bits;   // n_cand or null: tb_scan_close of every candidate, computed by an earlier launch (nrs_map.hip)
 };
+static_assert(std::is_trivially_copyable_v<TriArgs>, "passed to kernels by value: plain pointers, never an owner");
 
 // GetClosestMapPointsToFeature (temporal_buffer.cc:97-141) on the last snapshot: which ids are looked at, and their distance
 __device__ inline bool tb_eligible(const TriArgs& A, int cand, int j) {

@@ -1,4 +1,4 @@
-// Stand-alone check of the context's host logic (csrc/nrs_switches.hpp) for a sanitizer build: `make ctx_check && ./ctx_check`.
+// Stand-alone check of the context's host logic (csrc/nrs_switches.hpp, csrc/nrs_own.hpp) for a sanitizer build: `make ctx_check && ./ctx_check`.
 // No HIP, no library.  `./ctx_check --list` prints the table, "name kind group" per row (tests/test_switch_table_cpu.py reads it).
 //   table        names unique, "NRS_" + capitals / digits / underscores, identifiers dense and in row order, a group and a description in
 //                every row, the rows that force the host packer against the twelve names written out
@@ -8,12 +8,29 @@
 //   kinds        presence "0" is on, integer "abc" reads 0, the defaults when unset, the shared clamps at their edges
 //   options      struct_size 0 / 7 / 4097 / this build's / larger, every solver field out of range, the pcg defaults and the NRS_PCG_RTOL
 //                override; the input is not written to
+//   owners       csrc/nrs_own.hpp against counting versions of the four free functions (the library's are in nrs_ctx.hip): a new
+//                owner is empty; reset and the destructor free once each and an empty one frees nothing; move construction and move
+//                assignment free the old target once and leave the source empty; self-move; a std::vector<DevBuf> that reallocates frees
+//                nothing until it is cleared; the growth rule at 0, 1, 1023 and 1 << 32; stream and event owners destroy once; a
+//                struct ordered like nrs_ctx frees its buffers before it destroys its stream
+// Seeded faults, each tried once in a scratch copy; each one aborts check_owners at the CHECK named:
+//   ~DevBuf() without reset()                            "freed(A) == 2 ..." behind the first scope
+//   the move constructor leaves the source set           "!a.p && !a.cap && b.p == A ..."
+//   the move assignment without its reset()              "freed(B) == 1 && freed(A) == 0 ..."
+//   the move assignment without `this != &o`             the self-move: "a.p == A && a.cap == 64 ..."
+//   reset() that leaves cap                              "!a.p && !a.cap && freed(A) == 1"
+//   PinBuf::reset calling dev_free                       "... order() == std::string(2, kind)"
+//   grown_bytes without its 256                          "grown_bytes(0) == 256 ..."
+//   CtxLike's stream declared behind its buffers         "order() == \"pddes\"" (the stream goes first)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <set>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
+#include "../csrc/nrs_own.hpp"
 #include "../csrc/nrs_switches.hpp"
 
 using namespace nrs;
@@ -197,6 +214,96 @@ static void check_options() {
       CHECK(resolve_options(nullptr, o, &out) == NRS_OK && out.pcg_rtol == 1e-10); }
 }
 
+// ---- the owners: counting versions of the four free functions; every release is logged in order
+static std::vector<std::pair<char, const void*>> free_log;         // ('d' | 'p' | 's' | 'e', what)
+namespace nrs {
+void dev_free(void* p) noexcept { if (p) free_log.push_back({'d', p}); }
+void pin_free(void* p) noexcept { if (p) free_log.push_back({'p', p}); }
+void stream_destroy(ihipStream_t* s) noexcept { if (s) free_log.push_back({'s', s}); }
+void event_destroy(ihipEvent_t* e) noexcept { if (e) free_log.push_back({'e', e}); }
+}
+static int freed(const void* p) { int n = 0; for (const auto& f : free_log) n += f.second == p; return n; }
+static std::string order() { std::string s; for (const auto& f : free_log) s += f.first; return s; }
+
+template <class Buf>
+static void check_buffer_owner(char kind) {
+    static_assert(!std::is_copy_constructible_v<Buf> && !std::is_copy_assignable_v<Buf>, "an owner is move-only");
+    static_assert(std::is_nothrow_move_constructible_v<Buf> && std::is_nothrow_move_assignable_v<Buf>, "a vector of owners moves them when it grows");
+    char mem[8];
+    void *A = mem, *B = mem + 1, *C = mem + 2;
+    free_log.clear();
+    { Buf a; CHECK(!a.p && !a.cap && a.template as<int>() == nullptr); a.reset(); }
+    CHECK(free_log.empty());                                       // an empty owner frees nothing, neither by reset nor when it goes
+    {
+        Buf a; a.p = A; a.cap = 64;
+        CHECK(a.template as<char>() == mem);
+        a.reset();
+        CHECK(!a.p && !a.cap && freed(A) == 1);
+        a.reset();
+        CHECK(freed(A) == 1);
+        a.p = A; a.cap = 64;
+    }
+    CHECK(freed(A) == 2 && free_log.size() == 2 && order() == std::string(2, kind));   // (once by reset, once by the destructor)
+    free_log.clear();
+    {
+        Buf a; a.p = A; a.cap = 64;
+        Buf b(std::move(a));
+        CHECK(!a.p && !a.cap && b.p == A && b.cap == 64 && free_log.empty());
+        a.p = B; a.cap = 32;
+        a = std::move(b);                                          // the old target is freed once, the source is empty
+        CHECK(freed(B) == 1 && freed(A) == 0 && a.p == A && a.cap == 64 && !b.p && !b.cap);
+        Buf& self = a;
+        a = std::move(self);                                       // self-move: nothing freed, nothing lost
+        CHECK(a.p == A && a.cap == 64 && free_log.size() == 1);
+        Buf c; c.p = C; c.cap = 8;
+        c = Buf();                                                 // (how a holder empties itself)
+        CHECK(freed(C) == 1 && !c.p && !c.cap);
+    }
+    CHECK(freed(A) == 1 && freed(B) == 1 && freed(C) == 1 && free_log.size() == 3);
+}
+
+static void check_owners() {
+    check_buffer_owner<DevBuf>('d');
+    check_buffer_owner<PinBuf>('p');
+    // a growing vector of buffers (GraphDevice): reallocation moves them, nothing is freed until the vector lets go
+    static char cells[100];
+    free_log.clear();
+    {
+        std::vector<DevBuf> v;
+        for (int i = 0; i < 100; ++i) { DevBuf b; b.p = &cells[i]; b.cap = 16; v.push_back(std::move(b)); }
+        CHECK(free_log.empty());
+        for (int i = 0; i < 100; ++i) CHECK(v[i].p == &cells[i] && v[i].cap == 16);
+        v.clear();
+        CHECK(free_log.size() == 100);
+        for (int i = 0; i < 100; ++i) CHECK(freed(&cells[i]) == 1);
+    }
+    CHECK(free_log.size() == 100);
+    // the growth rule of nrs_ctx::ensure
+    CHECK(grown_bytes(0) == 256 && grown_bytes(1) == 257 && grown_bytes(1023) == 1023 + 255 + 256);
+    CHECK(grown_bytes((size_t)1 << 32) == ((size_t)1 << 32) + ((size_t)1 << 30) + 256);
+    // streams and events: destroyed once, by the right function; release() hands the handle on without destroying it
+    ihipStream_t* S = reinterpret_cast<ihipStream_t*>(&cells[0]);
+    ihipEvent_t* E = reinterpret_cast<ihipEvent_t*>(&cells[1]);
+    free_log.clear();
+    { Stream s; Event e; CHECK(!s && !e); }
+    CHECK(free_log.empty());
+    { Stream s(S); Stream t(std::move(s)); CHECK(!s && t.get() == S); }
+    CHECK(order() == "s" && freed(S) == 1);
+    { Event e(E); e.reset(); CHECK(!e && freed(E) == 1); }
+    CHECK(order() == "se" && freed(E) == 1);
+    // the order of nrs_ctx: the streams and events are declared before the buffers, so the buffers go first -- also when nrs_create
+    // deletes a context whose set-up stopped half way (here: no second event yet)
+    struct CtxLike { Stream stream; Event ev0, ev1; DevBuf buf; struct { DevBuf b; } arena; PinBuf pin; };
+    free_log.clear();
+    {
+        CtxLike* c = new CtxLike();
+        c->stream.reset(S); c->ev0.reset(E);
+        c->buf.p = &cells[2]; c->arena.b.p = &cells[3]; c->pin.p = &cells[4];
+        delete c;
+    }
+    CHECK(order() == "pddes");
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "--list")) {
         for (const SwitchRow& r : SWITCHES) std::printf("%s %s %s\n", r.name, kind_name(r.kind), r.group);
@@ -206,7 +313,9 @@ int main(int argc, char** argv) {
     check_environment();
     check_kinds();
     check_options();
+    check_owners();
     std::printf("ctx_check OK: %d switches (names, identifiers, groups, the host packer's twelve), made-up environments and NRS_DEBUG lists, set / change / "
-                "unset of every row by name, the three kinds with their defaults and shared clamps, nrs_create's option handling at every field boundary\n", (int)SW_COUNT);
+                "unset of every row by name, the three kinds with their defaults and shared clamps, nrs_create's option handling at every field boundary, the owners of device buffers, pinned memory, "
+                "streams and events\n", (int)SW_COUNT);
     return 0;
 }

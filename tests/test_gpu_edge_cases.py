@@ -170,9 +170,7 @@ def test_ba_trial_chi2_paths_agree(exact, monkeypatch):
     assert np.allclose(a[0], b[0], atol=1e-9, rtol=0) and np.allclose(a[1], b[1], atol=1e-6, rtol=0)
 
 
-def test_contexts_and_engines_do_not_leak_device_memory(lib_built):
-    """create / solve / destroy many times: device memory in use must not grow (arena reuse inside a
-    context, full release on nrs_destroy)."""
+def _free_bytes_reader():
     import ctypes
     hip = ctypes.CDLL("libamdhip64.so")          # the runtime instance libnrs_hip.so itself is linked to
 
@@ -181,7 +179,13 @@ def test_contexts_and_engines_do_not_leak_device_memory(lib_built):
         free, total = ctypes.c_size_t(), ctypes.c_size_t()
         assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
         return free.value
+    return free_bytes
 
+
+def test_contexts_and_engines_do_not_leak_device_memory(lib_built):
+    """create / solve / destroy many times: device memory in use must not grow (arena reuse inside a
+    context, full release on nrs_destroy)."""
+    free_bytes = _free_bytes_reader()
     p = S.make_dba_problem(400, 3, 77)
     e = nrs.dba_build_edges(p["kf_points"], p["nbr"])
     cam = nrs.make_camera(p["model"], p["prm"])
@@ -213,6 +217,92 @@ def test_contexts_and_engines_do_not_leak_device_memory(lib_built):
         cycle()
     free1 = free_bytes()
     assert free0 - free1 < 8 << 20, "device memory in use grew by %d bytes over 25 create/solve/destroy cycles" % (free0 - free1)
+
+
+def test_image_path_and_one_call_stages_do_not_leak_device_memory(lib_built):
+    """The sibling of the test above for everything it does not reach: per cycle a fresh context runs the front end (one image and a
+    pair), the tracker with its archive and a template store grown past its first capacity, PointReuse, the extractor, a temporal buffer
+    with frame mapping, triangulation, both initialisers, the pattern matcher, the evaluation, pose-only optimisation in its one- and
+    many-workgroup forms, a one-call embedded BA window and a tracking solve with its shadow streams; then everything is closed.  The
+    images are 1024 x 768, so every image-holding subsystem allocates at least one buffer of 512 KiB or more and 25 leaked copies exceed
+    the bound; a leaked buffer of a few KB is below what hipMemGetInfo shows (host/ctx_check.cpp covers the owners themselves)."""
+    import time
+    import embedded_window_cases as W
+    import init_cases as IC
+    import stereo_cases as SC
+    import tbuf_cases as TC
+    free_bytes = _free_bytes_reader()
+    F32 = np.float32
+    w, h = 1024, 768
+    sp = S.make_stereo_pair((w, h), 3, (0, 8), 40)
+    left, right = sp["left"], sp["right"]
+    st_opts = dict(bf=SC.BF_INIT, z_min=float(F32(SC.BF_INIT) / F32(8.5)), z_max=60.0, eps=1.0, min_points=1)
+    cam_st = nrs.make_camera(0, SC.PRM)
+    prm = np.array([700.0, 700.0, w / 2.0, h / 2.0], F32)
+    cam = nrs.make_camera(S.PINHOLE, prm)
+    gx, gy = np.meshgrid(np.linspace(60, w - 60, 15), np.linspace(60, h - 60, 10))
+    kp = np.stack([gx.ravel(), gy.ravel()], 1).astype(F32)          # 150 keypoints: the template store starts with room for 256
+    n = len(kp)
+    rng = np.random.default_rng(5)
+    z = rng.uniform(2.0, 4.0, n)
+    map_pos = np.stack([(kp[:, 0] - prm[2]) / prm[0] * z, (kp[:, 1] - prm[3]) / prm[1] * z, z], 1).astype(F32)
+    frame_slot = np.where(np.arange(n) % 2 == 0, np.arange(n), -1).astype(np.int32)
+    slot_status = np.zeros(n, np.int32)
+    lost = np.arange(1, n, 9)
+    eye_q, zero_t = np.array([0, 0, 0, 1], F32), np.zeros(3, F32)
+    tbd = S.make_temporal_buffer(8, 9)
+    cam_tb = nrs.make_camera(tbd["model"], tbd["prm"])
+    _, snaps = TC.snapshots_of(dict(tb=tbd, deform_mag=np.zeros(tbd["has_kp"].shape[0], F32)), "identity")
+    ip = IC.case("pinhole300")
+    depth = np.full((h, w), 1.3, F32)
+    ev_X = np.stack([(kp[:, 0] - prm[2]) / prm[0], (kp[:, 1] - prm[3]) / prm[1], np.ones(n)], 1).astype(F32)
+    tp = S.make_tracking_problem(300, 78)
+    camt = nrs.make_camera(tp["model"], tp["prm"])
+    fm = np.arange(300, dtype=np.int32)
+    ok = tp["status"] == 0
+    wp, wflag, wnb = W.window(W.CASES[0], "nodes")
+    wcam = nrs.make_camera(wp["model"], wp["prm"])
+    wqt = np.concatenate([wp["poses_q"], wp["poses_t"]], 1)
+
+    def cycle():
+        c = nrs.Context()
+        c.front_configure([("bright", 200)])
+        c.front_process(left, outputs=False)
+        c.front_process_stereo(left, right, outputs=False)
+        c.klt_configure(win=21, max_level=4, max_iters=10, epsilon=1e-4, min_eig=1e-4)
+        c.klt_set_reference(left, kp)
+        c.klt_track(right, kp, np.zeros(n, np.int32))
+        c.klt_archive_templates(np.arange(n), np.arange(n))
+        c.klt_insert_archived(c, np.arange(n), kp)                  # 300 templates: past the 256 the store began with
+        assert c.klt_num_points() == 2 * n > 256
+        c.point_reuse(cam, eye_q, zero_t, (w, h), map_pos, frame_slot, slot_status, lost)
+        c.shi_extract(left, capacity=4096)
+        tb = nrs.TBuf(c, 20)
+        for s in snaps:
+            tb.insert(s["ids"], s["xy"], s["pos"], s["status"], s["pose"], s["mag"], has_lm=s["has_lm"])
+        tb.map_frame(cam_tb, float(1.0 / tbd["prm"][0]))
+        c.triangulate_batch(cam_tb, tbd, tbd["cand"])
+        c.init_essential(nrs.make_camera(ip["model"], ip["prm"]), ip["ref_xy"], ip["cur_xy"], ip["status"], ip["n_matches"],
+                         radians_per_pixel=float(ip["rpp"]))
+        c.init_stereo(cam_st, left, right, sp["xy"], **st_opts)
+        c.stereo_match_pattern(cam_st, SC.BF_PATTERN, left, right, sp["xy"])
+        c.eval_frame(cam, eye_q, zero_t, ev_X, kp, depth=depth)
+        c.pose_only_solve(camt, tp["uv"][ok], tp["X_prev"][ok], tp["pose_q"], tp["pose_t"])
+        c.debug_set("NRS_PO_MULTI_MIN", "1")                        # the many-workgroup form at this size
+        c.pose_only_solve(camt, tp["uv"][ok], tp["X_prev"][ok], tp["pose_q"], tp["pose_t"])
+        c.dba_solve_window_embedded(wcam, wqt, wp["kf_points"], wp["lm_xyz"], wp["lm_uv"], wflag, wnb, wp["scale"], 1)
+        c.track_deform_solve(camt, tp["graph"], tp["X_prev"], fm, tp["status"], tp["uv"], tp["X_prev"], tp["pose_q"], tp["pose_t"], tp["scale"])
+        tb.close()
+        c.close()
+
+    cycle()                                   # warm-up: runtime / code-object allocations happen once
+    free0 = free_bytes()
+    t0 = time.time()
+    for _ in range(25):
+        cycle()
+    free1 = free_bytes()
+    print("25 cycles: %.2f s, device memory in use grew by %d bytes" % (time.time() - t0, free0 - free1))
+    assert free0 - free1 < 8 << 20, "device memory in use grew by %d bytes over 25 create/run/destroy cycles" % (free0 - free1)
 
 
 def test_non_finite_inputs_fail_fast_with_a_numeric_error(ctx):
