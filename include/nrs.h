@@ -181,7 +181,8 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *                 prefix a call may ask for: the "ran off at the limit" refusals)
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
  *   front end     NRS_FRONT_PER_EYE (nrs_front_process_stereo: grey and CLAHE issued per eye with the single-frame kernels instead of the
- *                 pair launches; the same bytes)
+ *                 pair launches; the same bytes), NRS_RECT_OWN_LAUNCH (nrs_front_process_stereo_raw: the remap into a rectified colour
+ *                 buffer and the pair's grey kernel after it, two launches instead of the fused one; the same bytes)
  *   initialisation NRS_DBND_NO_TILE (nrs_dbscan_nd and nrs_flow_tracks_cluster: the neighbour stage as a wave per point with candidates
  *                 from global memory instead of the LDS tiles; the same bits)
  *   probes      (read by a `make PROBES=1` build only) NRS_LIN_DBG / NRS_SPMV_DBG / NRS_PCG_DBG (phase clocks of one lineariser /
@@ -864,6 +865,40 @@ int nrs_shi_extract_front(nrs_ctx* ctx, int32_t w, int32_t h, int32_t image, int
 int nrs_front_process_stereo(nrs_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t w, int32_t h, int32_t stride_l, int32_t stride_r,
                              int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out,
                              uint8_t* gray_right_out, uint8_t* clahe_right_out);
+/* Stereo rectification: what the reference's Hamlyn loader does to every pair before System::TrackImageWithStereo sees it
+ * (modules/datasets/hamlyn.cc:194-198: stereoRectify + one initUndistortRectifyMap per eye, once; :226-229: cv::remap(INTER_LINEAR) of
+ * both eyes, every frame), on the device, so that the RAW pair crosses the bus and the rectified one never does.  cv::stereoRectify
+ * stays with the caller (a one-off on 3 x 3 matrices): an eye record takes its outputs.  The arithmetic is this project's definition
+ * (DESIGN.md 4 "Stereo rectification"; parity with OpenCV unpinned: no OpenCV in the build, none of its source in the reference tree),
+ * restated in tests/rect_oracle.py, to which the device is held bit for bit (maps) and byte for byte (images):
+ *   map     per destination pixel, fp64: (X, Y, W) = (P R)^-1 (u, v, 1), the rational distortion model on (X/W, Y/W), K's focal lengths and
+ *           centre; stored as fp32.  dist = k1 k2 p1 p2 k3 k4 k5 k6, unused entries 0 (the reference passes four, hamlyn.cc:194-198)
+ *   remap   OpenCV's 8-bit INTER_LINEAR convention: the map times 32 rounded half to even, integer part saturated to int16, 5-bit fractions,
+ *           integer tap weights that sum to 2^15, (sum + 2^14) >> 15; a tap outside the source is 0 (BORDER_CONSTANT 0, the default
+ *           hamlyn.cc:226-229 takes); a non-finite map entry gives 0
+ * row-major 3 x 3 matrices; of K only K[0], K[4], K[2], K[5] are used; P: the left 3 x 3 of stereoRectify's P1 / P2. */
+typedef struct { double K[9], dist[8], R[9], P[9]; } nrs_rect_eye;
+/* hamlyn.cc:194-198: builds both eyes' maps on the device (src_w x src_h raw eyes, dst_w x dst_h rectified ones) and drops the
+ * resident frame.  nrs_front_configure keeps the maps (filters and rectification are independent); nrs_destroy frees them.
+ * NRS_ERR_INVALID: a null eye, a size that is not in 1 .. 16384, a non-finite parameter, det(P R) == 0. */
+int nrs_front_rectify_configure(nrs_ctx* ctx, int32_t src_w, int32_t src_h, int32_t dst_w, int32_t dst_h, const nrs_rect_eye* left,
+                                const nrs_rect_eye* right);
+/* The fp32 maps of eye 0 (left) or 1 (right), as initUndistortRectifyMap(CV_32FC1) would hand them over (hamlyn.cc:194-198):
+ * dst_w x dst_h floats each, rows packed; either pointer may be NULL.  NRS_ERR_STATE before any nrs_front_rectify_configure. */
+int nrs_front_rectify_maps(nrs_ctx* ctx, int32_t eye, float* map_x, float* map_y);
+/* hamlyn.cc:226-229 followed by nrs_front_process_stereo: the raw eyes (src_w x src_h, 1 / 3 / 4 interleaved channels, a row stride in
+ * bytes each) are uploaded once, remapped channel by channel and converted to grey in one launch over both eyes; from the CLAHE LUTs on
+ * everything is nrs_front_process_stereo.  Outputs: exactly those of nrs_front_process_stereo, all dst_w x dst_h, and the rectified
+ * images themselves, dst_w x dst_h x channels, rows packed (the colour pixel is written only when one of the two is asked for).  Every
+ * output may be NULL.
+ * State: afterwards the context is exactly what nrs_front_process_stereo leaves when fed the two rectified images: w x h is
+ * dst_w x dst_h, every nrs_*_front call works on it unchanged, a PREDEFINED mask must have the rectified size.
+ * NRS_ERR_STATE before any nrs_front_rectify_configure; NRS_ERR_INVALID: a raw size other than the configured src_w x src_h, and the
+ * refusals of nrs_front_process_stereo. */
+int nrs_front_process_stereo_raw(nrs_ctx* ctx, const uint8_t* left, const uint8_t* right, int32_t src_w, int32_t src_h, int32_t stride_l,
+                                 int32_t stride_r, int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out,
+                                 uint8_t* const* filter_masks_out, uint8_t* gray_right_out, uint8_t* clahe_right_out, uint8_t* rect_left_out,
+                                 uint8_t* rect_right_out);
 
 /* ---- N2: the skinned mode ("5k points x 500 graph nodes") --------------------------------------------------------
  * The reference has no separate node set; its skinning is stage 2 of CameraPoseAndDeformationOptimization

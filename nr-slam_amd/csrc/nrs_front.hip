@@ -10,6 +10,10 @@
 //   k_front_clahe_lut      one workgroup per tile: LDS histogram (integer atomics), clip, redistribution, scan, LUT
 //   k_front_clahe_apply    bilinear blend of the four neighbouring LUTs, fp32, contraction off
 //   k_front_*_pair         the three above over a stereo pair in one launch each, the eye in grid.z (nrs_front_process_stereo)
+//   k_front_rect_map       stereo rectification (reference modules/datasets/hamlyn.cc:194-198): both eyes' undistort-rectify maps, once
+//                          per configuration, fp64; stored as fp32 and as the fixed-point taps the remap reads
+//   k_front_rect_gray_pair hamlyn.cc:226-229 + grey: the raw pair remapped (8-bit INTER_LINEAR, BORDER_CONSTANT 0) and converted in one
+//                          launch (nrs_front_process_stereo_raw); DESIGN.md 4 "Stereo rectification", held to tests/rect_oracle.py
 //   k_front_erode_ellipse  union of the element's row spans over a tile staged in LDS (the threshold of BrightFilter is
 //                          applied while the tile is loaded)
 //   k_front_rowmin/colmin  the rectangles, separably; the row pass reads its source through a functor: a plain image, the
@@ -19,9 +23,11 @@
 #include <algorithm>
 #include <cmath>
 #include <new>
+#include <utility>
 #include <vector>
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
+#include "nrs_rect_host.hpp"
 
 namespace nrs {
 
@@ -40,6 +46,16 @@ struct FrontFilter {
     int mw = 0, mh = 0;                        // PREDEFINED: size of the caller's mask
 };
 
+// Stereo rectification: the maps of nrs_front_rectify_configure.  They belong to the context, not to a filter configuration:
+// nrs_front_configure carries them over into the state it builds
+struct RectState {
+    bool on = false;                           // maps have been built
+    int sw = 0, sh = 0, dw = 0, dh = 0;        // raw and rectified size of an eye
+    DevBuf taps;                               // [eye][dh x dw] fixed-point taps, 8 bytes each: what the remap reads
+    DevBuf maps;                               // [eye][x | y][dh x dw] floats: what nrs_front_rectify_maps hands out
+    DevBuf colour, colour_r;                   // the rectified eyes, dw x dh x channels (a rect_*_out pointer, or NRS_RECT_OWN_LAUNCH)
+};
+
 struct FrontState {
     std::vector<FrontFilter> filters;
     float clip = 3.f;
@@ -52,6 +68,7 @@ struct FrontState {
     DevBuf fmask[NRS_FRONT_MAX_FILTERS];       // BRIGHT / BORDER: the last frame's mask; PREDEFINED: the eroded mask (made once)
     EllSpans e11, e20;
     GaussW gw;
+    RectState rect;
 };
 
 // ---- the three stages both eyes take: one body each, entered by the single-frame kernel and by the pair kernel -----------------------
@@ -153,6 +170,51 @@ __global__ __launch_bounds__(256) void k_front_clahe_lut_pair(Eyes grays, int w,
 }
 __global__ void k_front_clahe_apply_pair(Eyes grays, int w, int h, int tw, int th, int tiles_x, int tiles_y, Eyes luts, Eyes dsts) {
     front_clahe_blend_px(grays.mine(), w, h, tw, th, tiles_x, tiles_y, luts.mine(), dsts.mine());
+}
+
+// ---- stereo rectification (nrs_rect_host.hpp holds the per-pixel bodies: the stand-alone check runs the same ones) ----------------------
+struct RectEyes { RectEye e[2]; };
+
+__device__ inline uint2 rect_pack(RectTap t) { uint2 v; __builtin_memcpy(&v, &t, 8); return v; }
+__device__ inline RectTap rect_unpack(uint2 v) { RectTap t; __builtin_memcpy(&t, &v, 8); return t; }
+
+// once per configuration: one thread per destination pixel, rows of 256, the eye in grid.z
+__global__ __launch_bounds__(256) void k_front_rect_map(RectEyes eyes, int dw, int dh, uint2* __restrict__ taps, float* __restrict__ maps) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, eye = blockIdx.z;
+    if (x >= dw) return;
+    const size_t n = (size_t)dw * dh, i = (size_t)y * dw + x;
+    float mx, my;
+    rect_map_px(eye ? eyes.e[1] : eyes.e[0], x, y, &mx, &my);
+    maps[(size_t)(2 * eye) * n + i] = mx;
+    maps[(size_t)(2 * eye + 1) * n + i] = my;
+    taps[(size_t)eye * n + i] = rect_pack(rect_fix(mx, my));
+}
+
+// The hot path of a raw pair: one output pixel per thread, rows of 256, the eye in grid.z.  The tap is read coalesced (8 bytes a thread), the
+// four source pixels of every channel are gathered from the raw upload (packed rows; at the workload's size an eye lies in L2), the grey byte
+// is computed from the ROUNDED channel bytes -- remap first, then front_gray_px's formula: the reference's order -- and written directly.
+// COLOUR: the rectified pixel is written too (a rect_*_out pointer was given, or NRS_RECT_OWN_LAUNCH); GRAY = false leaves the grey to
+// k_front_gray_pair (NRS_RECT_OWN_LAUNCH).  No LDS staging: neighbouring threads' taps are neighbours in the source, the gather already
+// hits the lines its wave has just fetched, and a tile's source footprint is not known before the map is read
+template <int CH, bool COLOUR, bool GRAY>
+__global__ __launch_bounds__(256) void k_front_rect_gray_pair(Eyes raw, int sw, int sh, const uint2* __restrict__ taps, int dw, int dh, Eyes gray,
+                                                              Eyes colour) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= dw) return;
+    const size_t n = (size_t)dw * dh, i = (size_t)y * dw + x;
+    const RectTap t = rect_unpack(taps[(size_t)blockIdx.z * n + i]);
+    int v[CH];
+    rect_sample_px<CH>(raw.mine(), sw * CH, sw, sh, t, v);
+    if (COLOUR) {
+        uint8_t* d = colour.mine() + i * CH;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) d[c] = (uint8_t)v[c];
+    }
+    if (GRAY) {
+        int g = v[0];
+        if constexpr (CH > 1) g = (v[0] * 9798 + v[1] * 19235 + v[2] * 3735 + (1 << 14)) >> 15;
+        gray.mine()[i] = (uint8_t)g;
+    }
 }
 
 // ---- morphology -------------------------------------------------------------------------------------------------------------
@@ -349,6 +411,16 @@ extern "C" int nrs_front_configure(nrs_ctx* c, int32_t n_filters, const nrs_fron
     }
     NRS_HIP(c, hipSetDevice(c->device));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
+    // the rectification maps are no part of the filter configuration: they move into whatever state this call leaves (a refusal below
+    // leaves the default one)
+    struct KeepMaps {
+        nrs_ctx* c;
+        RectState r;
+        ~KeepMaps() {
+            if (!r.on) return;
+            if (FrontState* s = front_default(c)) s->rect = std::move(r);
+        }
+    } keep{c, c->front ? std::move(c->front->rect) : RectState()};
     front_free(c);                                                 // a fresh Masker: nothing of the old configuration or its frame is kept
     FrontState* f = front_default(c);
     if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
@@ -378,11 +450,26 @@ extern "C" int nrs_front_configure(nrs_ctx* c, int32_t n_filters, const nrs_fron
     return NRS_OK;
 }
 
+// what a raw pair adds to a pair's arguments: where the rectified eyes go (nullable)
+struct RawPair { uint8_t* rect_left_out; uint8_t* rect_right_out; };
+
+// the remap of both eyes: with the grey and, where `colour`, the rectified pixel too; or (gray false) the rectified pixel alone
+template <int CH>
+static void front_rect_launch(nrs_ctx* c, const RectState& r, bool colour, bool gray, Eyes raws, Eyes grays, Eyes colours) {
+    const dim3 grid((r.dw + 255) / 256, r.dh, 2), blk(256);
+    const uint2* taps = r.taps.as<uint2>();
+    if (colour && gray) hipLaunchKernelGGL((k_front_rect_gray_pair<CH, true, true>), grid, blk, 0, c->stream, raws, r.sw, r.sh, taps, r.dw, r.dh, grays, colours);
+    else if (gray) hipLaunchKernelGGL((k_front_rect_gray_pair<CH, false, true>), grid, blk, 0, c->stream, raws, r.sw, r.sh, taps, r.dw, r.dh, grays, colours);
+    else hipLaunchKernelGGL((k_front_rect_gray_pair<CH, true, false>), grid, blk, 0, c->stream, raws, r.sw, r.sh, taps, r.dw, r.dh, grays, colours);
+}
+
 // One frame (right == nullptr: nrs_front_process, the single-frame kernels) or a stereo pair (nrs_front_process_stereo: the right eye is
 // uploaded next to the left one and takes grey + CLAHE in the same launches; the masks are the left eye's).  Everything else is shared.
+// raw != nullptr (nrs_front_process_stereo_raw): img / right are the RAW eyes of w x h; the first stage rectifies them into the configured
+// dst_w x dst_h, which is the size of everything after it -- from the CLAHE LUTs onward nothing knows the difference.
 static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint8_t* right, int32_t w, int32_t h, int32_t stride, int32_t stride_r,
                      int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out,
-                     uint8_t* gray_right_out, uint8_t* clahe_right_out) {
+                     uint8_t* gray_right_out, uint8_t* clahe_right_out, const RawPair* raw = nullptr) {
     if (!img || w <= 0 || h <= 0) return c->fail(NRS_ERR_INVALID, "%s: empty image", who);
     if (channels != 1 && channels != 3 && channels != 4) return c->fail(NRS_ERR_INVALID, "%s: %d channels (1, 3 or 4)", who, channels);
     if ((int64_t)stride < (int64_t)w * channels || (right && (int64_t)stride_r < (int64_t)w * channels))
@@ -390,6 +477,13 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
     NRS_HIP(c, hipSetDevice(c->device));
     FrontState* f = front_default(c);                              // (never configured: no filters, clip 3.0, 8x8)
     if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
+    const int sw = w, sh = h;                                      // what is uploaded
+    if (raw) {
+        char msg[256];
+        const int bad = rect_check_raw(f->rect.on, f->rect.sw, f->rect.sh, w, h, msg, sizeof msg);
+        if (bad) return c->fail(bad == -2 ? NRS_ERR_STATE : NRS_ERR_INVALID, "%s", msg);
+        w = f->rect.dw; h = f->rect.dh;                            // ... and what is processed
+    }
     const int nf = (int)f->filters.size();
     BorderSrc bsrc[NRS_FRONT_MAX_FILTERS];
     for (int i = 0; i < nf; ++i) {
@@ -405,12 +499,18 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
         }
     }
     f->valid = false; f->valid_right = false;
-    const size_t n = (size_t)w * h, row = (size_t)w * channels;
-    NRS_TRY(c->ensure(f->raw, row * h));
+    const size_t n = (size_t)w * h, row = (size_t)sw * channels;
+    // a raw pair: the rectified colour eyes exist only where somebody reads them
+    const bool rect_own = raw && c->dbg.is_set(SW_RECT_OWN_LAUNCH), rect_colour = raw && (rect_own || raw->rect_left_out || raw->rect_right_out);
+    NRS_TRY(c->ensure(f->raw, row * sh));
     NRS_TRY(c->ensure(f->gray, n));
     NRS_TRY(c->ensure(f->clahe, n));
+    if (rect_colour) {
+        NRS_TRY(c->ensure(f->rect.colour, n * channels));
+        NRS_TRY(c->ensure(f->rect.colour_r, n * channels));
+    }
     if (right) {
-        NRS_TRY(c->ensure(f->raw_r, row * h));
+        NRS_TRY(c->ensure(f->raw_r, row * sh));
         NRS_TRY(c->ensure(f->gray_r, n));
         NRS_TRY(c->ensure(f->clahe_r, n));
         NRS_TRY(c->ensure(f->lut_r, (size_t)f->tiles_x * f->tiles_y * 256));
@@ -422,8 +522,8 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
         if (f->filters[i].kind != NRS_FRONT_PREDEFINED) NRS_TRY(c->ensure(f->fmask[i], n));
         if (f->filters[i].kind == NRS_FRONT_BRIGHT) NRS_TRY(c->ensure(f->tmp_f, sizeof(float) * n));
     }
-    NRS_HIP(c, hipMemcpy2DAsync(f->raw.p, row, img, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
-    if (right) NRS_HIP(c, hipMemcpy2DAsync(f->raw_r.p, row, right, (size_t)stride_r, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipMemcpy2DAsync(f->raw.p, row, img, (size_t)stride, row, (size_t)sh, hipMemcpyHostToDevice, c->stream));
+    if (right) NRS_HIP(c, hipMemcpy2DAsync(f->raw_r.p, row, right, (size_t)stride_r, row, (size_t)sh, hipMemcpyHostToDevice, c->stream));
     const dim3 blk(256), grid = front_grid(w, h);
     uint8_t* gray = f->gray.as<uint8_t>();
     uint8_t* tmp = f->tmp_a.as<uint8_t>();
@@ -434,13 +534,21 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
     const int clip = std::max(1, (int)(f->clip * (float)(tw * th) / 256.f));
     const Eyes raws{{f->raw.as<uint8_t>(), f->raw_r.as<uint8_t>()}}, grays{{gray, f->gray_r.as<uint8_t>()}};
     const Eyes luts{{f->lut.as<uint8_t>(), f->lut_r.as<uint8_t>()}}, clahes{{f->clahe.as<uint8_t>(), f->clahe_r.as<uint8_t>()}};
+    if (raw) {                                                     // the first stage of a raw pair: remap + grey, always over both eyes
+        const Eyes colours{{f->rect.colour.as<uint8_t>(), f->rect.colour_r.as<uint8_t>()}};
+        if (channels == 1) front_rect_launch<1>(c, f->rect, rect_colour, !rect_own, raws, grays, colours);
+        else if (channels == 3) front_rect_launch<3>(c, f->rect, rect_colour, !rect_own, raws, grays, colours);
+        else front_rect_launch<4>(c, f->rect, rect_colour, !rect_own, raws, grays, colours);
+        if (rect_own)                                              // NRS_RECT_OWN_LAUNCH: the grey of the rectified colour eyes, as of any pair
+            hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, colours, (int)(w * channels), channels, w, h, grays);
+    }
     if (right && !c->dbg.is_set(SW_FRONT_PER_EYE)) {               // the pair: one launch per shared stage, the eye in grid.z
-        hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, raws, (int)row, channels, w, h, grays);
+        if (!raw) hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, raws, (int)row, channels, w, h, grays);
         hipLaunchKernelGGL(k_front_clahe_lut_pair, dim3(f->tiles_x, f->tiles_y, 2), blk, 0, c->stream, grays, w, h, tw, th, clip, luts);
         hipLaunchKernelGGL(k_front_clahe_apply_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, grays, w, h, tw, th, f->tiles_x, f->tiles_y, luts, clahes);
     } else {
         for (int e = 0; e < (right ? 2 : 1); ++e) {                // a single frame, or NRS_FRONT_PER_EYE: the right eye through the same three kernels
-            hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, raws.p[e], (int)row, channels, w, h, grays.p[e]);
+            if (!raw) hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, raws.p[e], (int)row, channels, w, h, grays.p[e]);
             hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, grays.p[e], w, h, tw, th, clip, luts.p[e]);
             hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, grays.p[e], w, h, tw, th, f->tiles_x, f->tiles_y, luts.p[e], clahes.p[e]);
         }
@@ -474,7 +582,9 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
             if (filter_masks_out[i]) NRS_HIP(c, hipMemcpyAsync(filter_masks_out[i], f->fmask[i].p, n, hipMemcpyDeviceToHost, c->stream));
     if (right && gray_right_out) NRS_HIP(c, hipMemcpyAsync(gray_right_out, f->gray_r.p, n, hipMemcpyDeviceToHost, c->stream));
     if (right && clahe_right_out) NRS_HIP(c, hipMemcpyAsync(clahe_right_out, f->clahe_r.p, n, hipMemcpyDeviceToHost, c->stream));
-    NRS_HIP(c, hipStreamSynchronize(c->stream));                   // (also what lets another context read the resident images afterwards)
+    if (raw && raw->rect_left_out) NRS_HIP(c, hipMemcpyAsync(raw->rect_left_out, f->rect.colour.p, n * channels, hipMemcpyDeviceToHost, c->stream));
+    if (raw && raw->rect_right_out) NRS_HIP(c, hipMemcpyAsync(raw->rect_right_out, f->rect.colour_r.p, n * channels, hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));                  // (also what lets another context read the resident images afterwards)
     f->w = w; f->h = h; f->valid = true; f->valid_right = right != nullptr;
     return NRS_OK;
 }
@@ -492,4 +602,55 @@ extern "C" int nrs_front_process_stereo(nrs_ctx* c, const uint8_t* left, const u
     if (!right) return c->fail(NRS_ERR_INVALID, "nrs_front_process_stereo: empty image");
     return front_run(c, "nrs_front_process_stereo", left, right, w, h, stride_l, stride_r, channels, gray_out, clahe_out, global_out, filter_masks_out,
                      gray_right_out, clahe_right_out);
+}
+
+// hamlyn.cc:194-198 (initUndistortRectifyMap per eye, once): both maps in one launch
+extern "C" int nrs_front_rectify_configure(nrs_ctx* c, int32_t src_w, int32_t src_h, int32_t dst_w, int32_t dst_h, const nrs_rect_eye* left,
+                                           const nrs_rect_eye* right) {
+    if (!c) return NRS_ERR_INVALID;
+    RectEyes eyes;
+    char msg[256];
+    if (rect_check_configure(src_w, src_h, dst_w, dst_h, left, right, eyes.e, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    NRS_HIP(c, hipSetDevice(c->device));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    FrontState* f = front_default(c);
+    if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
+    f->valid = false; f->valid_right = false;                      // the resident frame is dropped; the filters stay
+    RectState& r = f->rect;
+    r.on = false;
+    const size_t n = (size_t)dst_w * dst_h;
+    NRS_TRY(c->ensure(r.taps, 2 * n * sizeof(uint2)));
+    NRS_TRY(c->ensure(r.maps, 4 * n * sizeof(float)));
+    hipLaunchKernelGGL(k_front_rect_map, dim3((dst_w + 255) / 256, dst_h, 2), dim3(256), 0, c->stream, eyes, dst_w, dst_h, r.taps.as<uint2>(), r.maps.as<float>());
+    NRS_HIP(c, hipGetLastError());
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    r.sw = src_w; r.sh = src_h; r.dw = dst_w; r.dh = dst_h; r.on = true;
+    return NRS_OK;
+}
+
+extern "C" int nrs_front_rectify_maps(nrs_ctx* c, int32_t eye, float* map_x, float* map_y) {
+    if (!c) return NRS_ERR_INVALID;
+    const char* who = "nrs_front_rectify_maps";
+    if (eye != 0 && eye != 1) return c->fail(NRS_ERR_INVALID, RECT_MSG_EYE, who, eye);
+    const FrontState* f = c->front;
+    if (!f || !f->rect.on) return c->fail(NRS_ERR_STATE, RECT_MSG_NONE, who);
+    NRS_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)f->rect.dw * f->rect.dh;
+    const float* m = f->rect.maps.as<float>() + (size_t)(2 * eye) * n;
+    if (map_x) NRS_HIP(c, hipMemcpyAsync(map_x, m, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (map_y) NRS_HIP(c, hipMemcpyAsync(map_y, m + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    return NRS_OK;
+}
+
+// hamlyn.cc:226-229 (cv::remap of both eyes) in front of nrs_front_process_stereo
+extern "C" int nrs_front_process_stereo_raw(nrs_ctx* c, const uint8_t* left, const uint8_t* right, int32_t src_w, int32_t src_h, int32_t stride_l,
+                                            int32_t stride_r, int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out,
+                                            uint8_t* const* filter_masks_out, uint8_t* gray_right_out, uint8_t* clahe_right_out,
+                                            uint8_t* rect_left_out, uint8_t* rect_right_out) {
+    if (!c) return NRS_ERR_INVALID;
+    if (!right) return c->fail(NRS_ERR_INVALID, "nrs_front_process_stereo_raw: empty image");
+    const RawPair raw{rect_left_out, rect_right_out};
+    return front_run(c, "nrs_front_process_stereo_raw", left, right, src_w, src_h, stride_l, stride_r, channels, gray_out, clahe_out, global_out,
+                     filter_masks_out, gray_right_out, clahe_right_out, &raw);
 }

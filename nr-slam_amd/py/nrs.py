@@ -36,6 +36,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_stereo_match_pattern", "nrs_eval_depth_ground_truth", "nrs_stereo_from_tracks", "nrs_eval_rmse", "nrs_eval_frame",
            "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo",
            "nrs_front_process_stereo", "nrs_stereo_match_pattern_front", "nrs_init_stereo_front", "nrs_stereo_match_lk_front",
+           "nrs_front_rectify_configure", "nrs_front_rectify_maps", "nrs_front_process_stereo_raw",
            "nrs_tbuf_create", "nrs_tbuf_destroy", "nrs_tbuf_clear", "nrs_tbuf_insert", "nrs_tbuf_info", "nrs_tbuf_flat", "nrs_map_frame_tbuf"]
 
 
@@ -112,6 +113,25 @@ FRONT_BRIGHT, FRONT_BORDER, FRONT_PREDEFINED = 0, 1, 2
 FRONT_GRAY, FRONT_CLAHE = 0, 1
 
 
+class RectEye(C.Structure):
+    """nrs_rect_eye: K, dist (k1 k2 p1 p2 k3 k4 k5 k6), R, P -- doubles, the matrices row-major"""
+    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 9)]
+
+
+def make_rect_eye(eye):
+    """a RectEye, or a dict(K=3x3, dist=up to 8 numbers, R=3x3, P=3x3) (the form of tests/rect_oracle.py) -> RectEye; None stays None"""
+    if eye is None or isinstance(eye, RectEye):
+        return eye
+    r = RectEye()
+    for name in ("K", "R", "P"):
+        getattr(r, name)[:] = [float(v) for v in np.asarray(eye[name], np.float64).reshape(9)]
+    dist = [float(v) for v in np.asarray(eye.get("dist", ()), np.float64).ravel()]
+    if len(dist) > 8:
+        raise ValueError("at most 8 distortion coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+    r.dist[:] = dist + [0.0] * (8 - len(dist))
+    return r
+
+
 class InitOptions(C.Structure):
     """nrs_init_options (f6)"""
     _fields_ = [("struct_size", C.c_uint32), ("n_hypotheses", C.c_int32), ("epipolar_threshold", C.c_float), ("radians_per_pixel", C.c_float),
@@ -178,6 +198,10 @@ def load_library(path=LIB_PATH):
     lib.nrs_stereo_match_pattern_front.argtypes = [ptr, ptr, f32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]
     lib.nrs_init_stereo_front.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr]
     lib.nrs_stereo_match_lk_front.argtypes = [ptr, ptr, ptr, f32, i32, i32, i32, i32, ptr, f32, ptr, ptr, ptr, ptr]
+    # stereo rectification (include/nrs.h "Stereo rectification")
+    lib.nrs_front_rectify_configure.argtypes = [ptr, i32, i32, i32, i32, ptr, ptr]
+    lib.nrs_front_rectify_maps.argtypes = [ptr, i32, ptr, ptr]
+    lib.nrs_front_process_stereo_raw.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
     # flow-track clustering (include/nrs.h "f6")
     lib.nrs_dbscan_nd.argtypes = [ptr, i32, i32, ptr, C.c_double, i32, ptr, ptr]
     lib.nrs_flow_tracks_cluster.argtypes = [ptr, i32, i32, ptr, ptr, ptr, ptr]
@@ -692,6 +716,62 @@ class Context:
                                                     _p(out.get("gray"), C.c_uint8), _p(out.get("clahe"), C.c_uint8), _p(out.get("global"), C.c_uint8),
                                                     ptrs, _p(out.get("gray_right"), C.c_uint8), _p(out.get("clahe_right"), C.c_uint8)))
         self._front_shape = (hh, ww)                                # (after the call: a refused pair leaves the resident size as it was)
+        return out
+
+    # ---- stereo rectification: the maps once, then raw pairs into the resident pair
+    def front_rectify_configure(self, src_wh, dst_wh, left, right):
+        """nrs_front_rectify_configure: src_wh / dst_wh = (w, h) of a raw / a rectified eye; left / right: eye records (make_rect_eye)"""
+        l, r = make_rect_eye(left), make_rect_eye(right)
+        self._chk(self.lib.nrs_front_rectify_configure(self.h, int(src_wh[0]), int(src_wh[1]), int(dst_wh[0]), int(dst_wh[1]),
+                                                       None if l is None else C.addressof(l), None if r is None else C.addressof(r)))
+        self._rect_src, self._rect_dst = (int(src_wh[0]), int(src_wh[1])), (int(dst_wh[0]), int(dst_wh[1]))
+
+    def front_rectify_maps(self, eye, shape=None):
+        """nrs_front_rectify_maps -> (map_x, map_y), dst_h x dst_w float32, of eye 0 (left) or 1 (right)"""
+        ww, hh = (shape[1], shape[0]) if shape else getattr(self, "_rect_dst", (1, 1))      # (never configured: the library refuses)
+        mx, my = np.zeros((hh, ww), np.float32), np.zeros((hh, ww), np.float32)
+        self._chk(self.lib.nrs_front_rectify_maps(self.h, int(eye), _p(mx, C.c_float), _p(my, C.c_float)))
+        return mx, my
+
+    def front_process_stereo_raw(self, left, right, outputs=True, stride_l=None, stride_r=None, width=None, channels=1):
+        """nrs_front_process_stereo_raw: the RAW eyes of a pair, rectified on the device by the maps of front_rectify_configure, then as
+        front_process_stereo.  The arguments are those of front_process_stereo, at the raw size; outputs: True, False or the names wanted of
+        "gray", "clahe", "global", "masks", "gray_right", "clahe_right", "rect_left", "rect_right" (the rectified images, dst_h x dst_w or
+        dst_h x dst_w x channels).  -> dict of those, all of the rectified size"""
+        left = np.asarray(left, np.uint8)
+        none_right = right is None
+        right = left if none_right else np.asarray(right, np.uint8)
+        if (stride_l is None) != (stride_r is None):
+            raise ValueError("front_process_stereo_raw: give both strides or neither")
+        if stride_l is None:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+            if left.shape != right.shape:
+                raise NrsError(-1, "front_process_stereo_raw: the eyes differ in size or channel count: %s and %s" % (left.shape, right.shape))
+            hh, ww = left.shape[:2]
+            ch = 1 if left.ndim == 2 else left.shape[2]
+            stride_l = stride_r = left.strides[0] if hh else ww * ch
+        else:
+            if left.shape[0] != right.shape[0]:
+                raise NrsError(-1, "front_process_stereo_raw: the eyes differ in height: %d and %d" % (left.shape[0], right.shape[0]))
+            hh, ww, ch = left.shape[0], int(width), int(channels)
+        dw, dh = getattr(self, "_rect_dst", (ww, hh))                # (never configured: the library refuses)
+        nf = getattr(self, "_front_n", 0)
+        names = ("gray", "clahe", "global", "gray_right", "clahe_right")
+        want = names + ("masks", "rect_left", "rect_right") if outputs is True else tuple(outputs or ())
+        out = {k: np.zeros((dh, dw), np.uint8) for k in names if k in want}
+        for k in ("rect_left", "rect_right"):
+            if k in want:
+                out[k] = np.zeros((dh, dw) if ch == 1 else (dh, dw, ch), np.uint8)
+        ptrs = None
+        if "masks" in want:
+            out["masks"] = [np.zeros((dh, dw), np.uint8) for _ in range(nf)]
+            if nf:
+                ptrs = (C.c_void_p * nf)(*[m.ctypes.data for m in out["masks"]])
+        self._chk(self.lib.nrs_front_process_stereo_raw(self.h, left.ctypes.data, None if none_right else right.ctypes.data, ww, hh, int(stride_l), int(stride_r),
+                                                        ch, _p(out.get("gray"), C.c_uint8), _p(out.get("clahe"), C.c_uint8), _p(out.get("global"), C.c_uint8),
+                                                        ptrs, _p(out.get("gray_right"), C.c_uint8), _p(out.get("clahe_right"), C.c_uint8),
+                                                        _p(out.get("rect_left"), C.c_uint8), _p(out.get("rect_right"), C.c_uint8)))
+        self._front_shape = (dh, dw)
         return out
 
     def klt_set_reference_front(self, xy, image=FRONT_GRAY, use_global_mask=True, shape=None):

@@ -90,7 +90,7 @@ class GpuBackend:
     device_reuse=True PointReuse is one call on the main context and the second one is never made)."""
 
     def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None, device_reuse=False,
-                 device_tbuf=False):
+                 device_tbuf=False, rectify=None):
         """n_nodes > 0: EMBEDDED-DEFORMATION mode (include/nrs.h nrs_track_deform_solve_embedded; needs the dense graph): n_nodes map points
         (farthest-point sampling on the initial map, nrs_skin_select_nodes) carry the deformation vertices for the whole sequence, every
         other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call).  Mapping
@@ -105,7 +105,10 @@ class GpuBackend:
         False (the default) = the two-context path: host projection, reuse_track_archived on ctx_reuse, insert_archived.
         device_tbuf: True = the loop's TemporalBuffer is the resident one of the main context (include/nrs.h nrs_tbuf): a frame enters
         with one upload (tbuf_insert) and frame mapping reads it in place (map_frame_resident), which hands keypoint ids back.
-        False (the default) = nrs_frame_loop.TemporalBuffer on the host, flattened and uploaded whole by every map_frame."""
+        False (the default) = nrs_frame_loop.TemporalBuffer on the host, flattened and uploaded whole by every map_frame.
+        rectify: None (the default) = a stereo pair handed to front_stereo is rectified already.  dict(src_wh=(w, h), dst_wh=(w, h), left=eye
+        record, right=eye record) (nrs.Context.front_rectify_configure; needs the front mode) = front_stereo is handed the RAW eyes, as the
+        camera gives them, and rectifies them on the device (nrs_front_process_stereo_raw): every later step sees the rectified pair."""
         self.nrs = nrs
         self.device_tbuf, self.tb = bool(device_tbuf), None
         self.dense, self.cap, self.rg = dense_graph or n_nodes > 0, cap_per_point, None
@@ -121,6 +124,11 @@ class GpuBackend:
         self._front_right, self._front_fresh, self.n_front_calls = None, None, 0      # (n_front_calls: front-end calls made, one or two eyes each)
         if self.front:
             self.ctx.front_configure(front if isinstance(front, (list, tuple)) else ())
+        self.rectify = rectify is not None
+        if self.rectify:
+            if not self.front:
+                raise ValueError("rectify needs the front mode (front=True or a list of filters)")
+            self.ctx.front_rectify_configure(rectify["src_wh"], rectify["dst_wh"], rectify["left"], rectify["right"])
 
     @property
     def ctx_reuse(self):
@@ -140,12 +148,14 @@ class GpuBackend:
     # front mode, stereo: one nrs_front_process_stereo per pair -- the same identity rule on (left, right).  Afterwards the left eye is the
     # resident frame of every step above (they see the same `left` array and do not process again) and both eyes are there for init_stereo /
     # stereo_pattern / stereo_lk.  force: the start of a frame (FrameLoop.track_image_with_stereo); the klt_track that follows on the same
-    # left array then tracks on the resident eye instead of processing it a second time
+    # left array then tracks on the resident eye instead of processing it a second time.  With rectify the eyes are the raw ones and the
+    # call is nrs_front_process_stereo_raw: what is resident afterwards, and the grey handed back, is the rectified pair
     def front_stereo(self, left, right, force=False):
         if not self.front:
             raise ValueError("front_stereo needs the front mode (front=True or a list of filters)")
         if force or left is not self._front_im or right is not self._front_right:
-            self._front_gray = self.ctx.front_process_stereo(left, right, outputs=("gray",))["gray"]
+            process = self.ctx.front_process_stereo_raw if self.rectify else self.ctx.front_process_stereo
+            self._front_gray = process(left, right, outputs=("gray",))["gray"]
             self._front_im, self._front_right = left, right
             self.n_front_calls += 1
             if force:
