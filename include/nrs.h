@@ -182,7 +182,9 @@ int nrs_create(nrs_ctx** out, const nrs_options* opt);
  *   evaluation    NRS_STEREO_NO_MFMA (nrs_stereo_match_pattern: plain integer correlation instead of the int8 matrix-core form)
  *   front end     NRS_FRONT_PER_EYE (nrs_front_process_stereo: grey and CLAHE issued per eye with the single-frame kernels instead of the
  *                 pair launches; the same bytes), NRS_RECT_OWN_LAUNCH (nrs_front_process_stereo_raw: the remap into a rectified colour
- *                 buffer and the pair's grey kernel after it, two launches instead of the fused one; the same bytes)
+ *                 buffer and the pair's grey kernel after it, two launches instead of the fused one; the same bytes), NRS_RESIZE_OWN_LAUNCH
+ *                 (nrs_front_process_raw: the resize into a colour buffer and the ordinary grey kernel after it, two launches instead of
+ *                 the fused one; the same bytes)
  *   initialisation NRS_DBND_NO_TILE (nrs_dbscan_nd and nrs_flow_tracks_cluster: the neighbour stage as a wave per point with candidates
  *                 from global memory instead of the LDS tiles; the same bits)
  *   probes      (read by a `make PROBES=1` build only) NRS_LIN_DBG / NRS_SPMV_DBG / NRS_PCG_DBG (phase clocks of one lineariser /
@@ -899,6 +901,36 @@ int nrs_front_process_stereo_raw(nrs_ctx* ctx, const uint8_t* left, const uint8_
                                  int32_t stride_r, int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out,
                                  uint8_t* const* filter_masks_out, uint8_t* gray_right_out, uint8_t* clahe_right_out, uint8_t* rect_left_out,
                                  uint8_t* rect_right_out);
+/* Frame resize: what the reference's Endomapper app does to every frame before System::TrackImage sees it (apps/endomapper.cc:65-69:
+ * cv::resize(image, image, Size(cols / 2.0f, rows / 2.0f)), INTER_LINEAR), on the device, so that the frame crosses the bus as the video
+ * decoder hands it over.  The arithmetic is this project's definition (DESIGN.md 4 "Frame resize"; parity with OpenCV unpinned: no OpenCV
+ * in the build, none of its source in the reference tree), restated in tests/resize_oracle.py, to which the device is held byte for byte.
+ * It follows OpenCV's 8-bit INTER_LINEAR conventions:
+ *   box      iff src_w == 2 dst_w and src_h == 2 dst_h: per channel (s00 + s01 + s10 + s11 + 2) >> 2 over the 2 x 2 block
+ *   general  every other size, up-scaling included.  scale = 1.0 / ((double)dst / src); f = (float)((d + 0.5) * scale - 0.5), s = floor(f),
+ *            f -= s in fp32; weights sat_i16(rne((1.f - f) * 2048.f)), sat_i16(rne(f * 2048.f)), rne = round half to even.
+ *            Columns: s < 0 -> s = 0, f = 0; s >= src_w - 1 -> s = src_w - 1, f = 0 (the second tap is not read).  Rows: the fraction
+ *            stays, rows s and s + 1 are each clamped to [0, src_h - 1].  Per channel D_r = S[r][sx] a0 + S[r][sx + 1] a1 (int32),
+ *            dst = sat_u8((((b0 (D_0 >> 4)) >> 16) + ((b1 (D_1 >> 4)) >> 16) + 2) >> 2)
+ * The resize comes first, channel by channel; the grey conversion of nrs_front_process reads the resized pixel (the reference's order).
+ *
+ * nrs_front_resize_configure builds the tap tables (on the host, uploaded) and drops the resident frame.  nrs_front_configure and
+ * nrs_front_rectify_configure leave the tables alone, and this call leaves the filters and the maps alone; nrs_destroy frees them.
+ * NRS_ERR_INVALID: a size that is not in 1 .. 16384. */
+int nrs_front_resize_configure(nrs_ctx* ctx, int32_t src_w, int32_t src_h, int32_t dst_w, int32_t dst_h);
+/* The tables: sx [dst_w], ax [dst_w][2], sy [dst_h][2] (clamped), by [dst_h][2]; *box = 1 when the box branch applies (the tables are built
+ * all the same), else 0.  Every pointer may be NULL.  NRS_ERR_STATE before any nrs_front_resize_configure. */
+int nrs_front_resize_taps(nrs_ctx* ctx, int32_t* sx, int16_t* ax, int32_t* sy, int16_t* by, int32_t* box);
+/* endomapper.cc:65-69 followed by nrs_front_process: the raw frame (src_w x src_h, 1 / 3 / 4 interleaved channels, a row stride in bytes)
+ * is uploaded once, resized and converted to grey in one launch; from the CLAHE LUTs on everything is nrs_front_process.  Outputs: those
+ * of nrs_front_process, all dst_w x dst_h, and the resized frame itself, dst_w x dst_h x channels, rows packed (the colour pixel is written
+ * only when it is asked for).  Every output may be NULL.
+ * State: afterwards the context is exactly what nrs_front_process leaves when fed the resized image: w x h is dst_w x dst_h, every
+ * nrs_*_front call works on it unchanged, a PREDEFINED mask must have the resized size, no right eye is resident.
+ * NRS_ERR_STATE before any nrs_front_resize_configure; NRS_ERR_INVALID: a raw size other than the configured src_w x src_h, and the
+ * refusals of nrs_front_process. */
+int nrs_front_process_raw(nrs_ctx* ctx, const uint8_t* img, int32_t src_w, int32_t src_h, int32_t stride, int32_t channels, uint8_t* gray_out,
+                          uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out, uint8_t* resized_out);
 
 /* ---- N2: the skinned mode ("5k points x 500 graph nodes") --------------------------------------------------------
  * The reference has no separate node set; its skinning is stage 2 of CameraPoseAndDeformationOptimization

@@ -14,6 +14,9 @@
 //                          per configuration, fp64; stored as fp32 and as the fixed-point taps the remap reads
 //   k_front_rect_gray_pair hamlyn.cc:226-229 + grey: the raw pair remapped (8-bit INTER_LINEAR, BORDER_CONSTANT 0) and converted in one
 //                          launch (nrs_front_process_stereo_raw); DESIGN.md 4 "Stereo rectification", held to tests/rect_oracle.py
+//   k_front_resize_gray    the resize of the Endomapper app (reference apps/endomapper.cc:65-69, cv::resize INTER_LINEAR) + grey: the raw frame
+//                          resized (2 x 2 box when exactly halved, else 11-bit fixed-point taps) and converted in one launch
+//                          (nrs_front_process_raw); DESIGN.md 4 "Frame resize", held to tests/resize_oracle.py
 //   k_front_erode_ellipse  union of the element's row spans over a tile staged in LDS (the threshold of BrightFilter is
 //                          applied while the tile is loaded)
 //   k_front_rowmin/colmin  the rectangles, separably; the row pass reads its source through a functor: a plain image, the
@@ -28,6 +31,7 @@
 #include "nrs_ctx.hpp"
 #include "nrs_device.hpp"
 #include "nrs_rect_host.hpp"
+#include "nrs_resize_host.hpp"
 
 namespace nrs {
 
@@ -56,6 +60,15 @@ struct RectState {
     DevBuf colour, colour_r;                   // the rectified eyes, dw x dh x channels (a rect_*_out pointer, or NRS_RECT_OWN_LAUNCH)
 };
 
+// Frame resize: the tap tables of nrs_front_resize_configure.  Like the maps they belong to the context, not to a filter configuration
+struct ResizeState {
+    bool on = false;                           // tables have been built
+    bool box = false;                          // exactly halved: the 2 x 2 box branch (the tables are built all the same)
+    int sw = 0, sh = 0, dw = 0, dh = 0;        // raw and resized size of a frame
+    DevBuf tabs;                               // sx [dw] | sy [dh][2] (int32), then ax [dw][2] | by [dh][2] (int16): what nrs_front_resize_taps hands out
+    DevBuf colour;                             // the resized frame, dw x dh x channels (resized_out, or NRS_RESIZE_OWN_LAUNCH)
+};
+
 struct FrontState {
     std::vector<FrontFilter> filters;
     float clip = 3.f;
@@ -69,6 +82,7 @@ struct FrontState {
     EllSpans e11, e20;
     GaussW gw;
     RectState rect;
+    ResizeState resize;
 };
 
 // ---- the three stages both eyes take: one body each, entered by the single-frame kernel and by the pair kernel -----------------------
@@ -214,6 +228,48 @@ __global__ __launch_bounds__(256) void k_front_rect_gray_pair(Eyes raw, int sw, 
         int g = v[0];
         if constexpr (CH > 1) g = (v[0] * 9798 + v[1] * 19235 + v[2] * 3735 + (1 << 14)) >> 15;
         gray.mine()[i] = (uint8_t)g;
+    }
+}
+
+// ---- frame resize (nrs_resize_host.hpp holds the tables' rule and the pixel bodies: the stand-alone check runs the same ones) ------------
+struct ResizeTabs {
+    const int32_t* sx; const int32_t* sy;      // [dw], [dh][2]
+    const short2* ax; const short2* by;        // [dw], [dh]: the two weights of a tap, one 4-byte load
+};
+
+// The hot path of a raw frame: one output pixel per thread, a workgroup is 256 consecutive pixels of one output row.  Lane-to-pixel mapping:
+// the frame is interleaved bytes (1, 3 or 4 a pixel) and the kernel is memory-bound (1440 x 1080 x 3: 4.7 MB in, 0.4 MB grey out).
+// Consecutive lanes take consecutive output pixels, so in the box branch a wave reads two contiguous runs of 64 * 2 * CH bytes (one per
+// source row) and the workgroup's runs follow each other without a gap: every fetched line is used whole, by this wave or the next.
+// The per-lane loads stay byte loads -- a pixel pair is 6 bytes at CH = 3 and a row may begin at any byte, so nothing wider is aligned --
+// and what the lanes of a wave do not merge, L2 absorbs: a line is touched by at most two neighbouring waves of one workgroup.  The general
+// branch reads the column tap coalesced (4 + 4 bytes a lane), the row tap is the same for the whole workgroup (scalar loads), and the
+// source runs are contiguous up to the scale.  The grey byte is computed from the ROUNDED channel bytes -- resize first, then
+// front_gray_px's formula: the reference's order.  COLOUR: the resized pixel is written too (resized_out, or NRS_RESIZE_OWN_LAUNCH);
+// GRAY = false leaves the grey to k_front_gray (NRS_RESIZE_OWN_LAUNCH).  No LDS: no byte is read twice by one workgroup in the box
+// branch, and in the general branch only the shared tap of two neighbouring lanes is
+template <int CH, bool BOX, bool COLOUR, bool GRAY>
+__global__ __launch_bounds__(256) void k_front_resize_gray(const uint8_t* __restrict__ raw, int stride, ResizeTabs t, int dw, int dh,
+                                                           uint8_t* __restrict__ gray, uint8_t* __restrict__ colour) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= dw || y >= dh) return;
+    const size_t i = (size_t)y * dw + x;
+    int v[CH];
+    if constexpr (BOX) {
+        resize_box_px<CH>(raw, stride, x, y, v);
+    } else {
+        const short2 a = t.ax[x], b = t.by[y];
+        resize_sample_px<CH>(raw, stride, t.sx[x], a.x, a.y, t.sy[2 * y], t.sy[2 * y + 1], b.x, b.y, v);
+    }
+    if (COLOUR) {
+        uint8_t* d = colour + i * CH;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) d[c] = (uint8_t)v[c];
+    }
+    if (GRAY) {
+        int g = v[0];
+        if constexpr (CH > 1) g = (v[0] * 9798 + v[1] * 19235 + v[2] * 3735 + (1 << 14)) >> 15;
+        gray[i] = (uint8_t)g;
     }
 }
 
@@ -411,16 +467,19 @@ extern "C" int nrs_front_configure(nrs_ctx* c, int32_t n_filters, const nrs_fron
     }
     NRS_HIP(c, hipSetDevice(c->device));
     NRS_HIP(c, hipStreamSynchronize(c->stream));
-    // the rectification maps are no part of the filter configuration: they move into whatever state this call leaves (a refusal below
-    // leaves the default one)
+    // the rectification maps and the resize tables are no part of the filter configuration: they move into whatever state this call
+    // leaves (a refusal below leaves the default one)
     struct KeepMaps {
         nrs_ctx* c;
         RectState r;
+        ResizeState z;
         ~KeepMaps() {
-            if (!r.on) return;
-            if (FrontState* s = front_default(c)) s->rect = std::move(r);
+            if (!r.on && !z.on) return;
+            FrontState* s = front_default(c);
+            if (s && r.on) s->rect = std::move(r);
+            if (s && z.on) s->resize = std::move(z);
         }
-    } keep{c, c->front ? std::move(c->front->rect) : RectState()};
+    } keep{c, c->front ? std::move(c->front->rect) : RectState(), c->front ? std::move(c->front->resize) : ResizeState()};
     front_free(c);                                                 // a fresh Masker: nothing of the old configuration or its frame is kept
     FrontState* f = front_default(c);
     if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
@@ -463,13 +522,36 @@ static void front_rect_launch(nrs_ctx* c, const RectState& r, bool colour, bool 
     else hipLaunchKernelGGL((k_front_rect_gray_pair<CH, true, false>), grid, blk, 0, c->stream, raws, r.sw, r.sh, taps, r.dw, r.dh, grays, colours);
 }
 
+// what a raw frame adds to a frame's arguments: where the resized frame goes (nullable)
+struct RawFrame { uint8_t* resized_out; };
+
+// the resize of a frame: with the grey and, where `colour`, the resized pixel too; or (gray false) the resized pixel alone
+template <int CH, bool BOX>
+static void front_resize_launch_b(nrs_ctx* c, const ResizeState& z, bool colour, bool gray, const uint8_t* raw, uint8_t* grays, uint8_t* colours) {
+    const dim3 grid((z.dw + 255) / 256, z.dh), blk(256);
+    const int32_t* i32 = z.tabs.as<int32_t>();
+    const short2* i16 = reinterpret_cast<const short2*>(i32 + z.dw + 2 * (size_t)z.dh);
+    const ResizeTabs t{i32, i32 + z.dw, i16, i16 + z.dw};
+    const int stride = z.sw * CH;
+    if (colour && gray) hipLaunchKernelGGL((k_front_resize_gray<CH, BOX, true, true>), grid, blk, 0, c->stream, raw, stride, t, z.dw, z.dh, grays, colours);
+    else if (gray) hipLaunchKernelGGL((k_front_resize_gray<CH, BOX, false, true>), grid, blk, 0, c->stream, raw, stride, t, z.dw, z.dh, grays, colours);
+    else hipLaunchKernelGGL((k_front_resize_gray<CH, BOX, true, false>), grid, blk, 0, c->stream, raw, stride, t, z.dw, z.dh, grays, colours);
+}
+template <int CH>
+static void front_resize_launch(nrs_ctx* c, const ResizeState& z, bool colour, bool gray, const uint8_t* raw, uint8_t* grays, uint8_t* colours) {
+    if (z.box) front_resize_launch_b<CH, true>(c, z, colour, gray, raw, grays, colours);
+    else front_resize_launch_b<CH, false>(c, z, colour, gray, raw, grays, colours);
+}
+
 // One frame (right == nullptr: nrs_front_process, the single-frame kernels) or a stereo pair (nrs_front_process_stereo: the right eye is
 // uploaded next to the left one and takes grey + CLAHE in the same launches; the masks are the left eye's).  Everything else is shared.
 // raw != nullptr (nrs_front_process_stereo_raw): img / right are the RAW eyes of w x h; the first stage rectifies them into the configured
 // dst_w x dst_h, which is the size of everything after it -- from the CLAHE LUTs onward nothing knows the difference.
+// rawf != nullptr (nrs_front_process_raw): img is the RAW frame of w x h; the first stage resizes it into the configured dst_w x dst_h, in the
+// same way.
 static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint8_t* right, int32_t w, int32_t h, int32_t stride, int32_t stride_r,
                      int32_t channels, uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out,
-                     uint8_t* gray_right_out, uint8_t* clahe_right_out, const RawPair* raw = nullptr) {
+                     uint8_t* gray_right_out, uint8_t* clahe_right_out, const RawPair* raw = nullptr, const RawFrame* rawf = nullptr) {
     if (!img || w <= 0 || h <= 0) return c->fail(NRS_ERR_INVALID, "%s: empty image", who);
     if (channels != 1 && channels != 3 && channels != 4) return c->fail(NRS_ERR_INVALID, "%s: %d channels (1, 3 or 4)", who, channels);
     if ((int64_t)stride < (int64_t)w * channels || (right && (int64_t)stride_r < (int64_t)w * channels))
@@ -483,6 +565,12 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
         const int bad = rect_check_raw(f->rect.on, f->rect.sw, f->rect.sh, w, h, msg, sizeof msg);
         if (bad) return c->fail(bad == -2 ? NRS_ERR_STATE : NRS_ERR_INVALID, "%s", msg);
         w = f->rect.dw; h = f->rect.dh;                            // ... and what is processed
+    }
+    if (rawf) {
+        char msg[256];
+        const int bad = resize_check_raw(f->resize.on, f->resize.sw, f->resize.sh, w, h, msg, sizeof msg);
+        if (bad) return c->fail(bad == -2 ? NRS_ERR_STATE : NRS_ERR_INVALID, "%s", msg);
+        w = f->resize.dw; h = f->resize.dh;
     }
     const int nf = (int)f->filters.size();
     BorderSrc bsrc[NRS_FRONT_MAX_FILTERS];
@@ -502,8 +590,11 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
     const size_t n = (size_t)w * h, row = (size_t)sw * channels;
     // a raw pair: the rectified colour eyes exist only where somebody reads them
     const bool rect_own = raw && c->dbg.is_set(SW_RECT_OWN_LAUNCH), rect_colour = raw && (rect_own || raw->rect_left_out || raw->rect_right_out);
+    // a raw frame: the resized colour frame likewise
+    const bool resize_own = rawf && c->dbg.is_set(SW_RESIZE_OWN_LAUNCH), resize_colour = rawf && (resize_own || rawf->resized_out);
     NRS_TRY(c->ensure(f->raw, row * sh));
     NRS_TRY(c->ensure(f->gray, n));
+    if (resize_colour) NRS_TRY(c->ensure(f->resize.colour, n * channels));
     NRS_TRY(c->ensure(f->clahe, n));
     if (rect_colour) {
         NRS_TRY(c->ensure(f->rect.colour, n * channels));
@@ -522,8 +613,11 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
         if (f->filters[i].kind != NRS_FRONT_PREDEFINED) NRS_TRY(c->ensure(f->fmask[i], n));
         if (f->filters[i].kind == NRS_FRONT_BRIGHT) NRS_TRY(c->ensure(f->tmp_f, sizeof(float) * n));
     }
-    NRS_HIP(c, hipMemcpy2DAsync(f->raw.p, row, img, (size_t)stride, row, (size_t)sh, hipMemcpyHostToDevice, c->stream));
-    if (right) NRS_HIP(c, hipMemcpy2DAsync(f->raw_r.p, row, right, (size_t)stride_r, row, (size_t)sh, hipMemcpyHostToDevice, c->stream));
+    // (packed rows go up as one run of bytes: a 2-D copy of 1081 rows of 4323 bytes was measured at 8 ms against 0.06 ms, DESIGN.md 4 "Frame resize")
+    if ((size_t)stride == row) NRS_HIP(c, hipMemcpyAsync(f->raw.p, img, row * sh, hipMemcpyHostToDevice, c->stream));
+    else NRS_HIP(c, hipMemcpy2DAsync(f->raw.p, row, img, (size_t)stride, row, (size_t)sh, hipMemcpyHostToDevice, c->stream));
+    if (right && (size_t)stride_r == row) NRS_HIP(c, hipMemcpyAsync(f->raw_r.p, right, row * sh, hipMemcpyHostToDevice, c->stream));
+    else if (right) NRS_HIP(c, hipMemcpy2DAsync(f->raw_r.p, row, right, (size_t)stride_r, row, (size_t)sh, hipMemcpyHostToDevice, c->stream));
     const dim3 blk(256), grid = front_grid(w, h);
     uint8_t* gray = f->gray.as<uint8_t>();
     uint8_t* tmp = f->tmp_a.as<uint8_t>();
@@ -542,13 +636,21 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
         if (rect_own)                                              // NRS_RECT_OWN_LAUNCH: the grey of the rectified colour eyes, as of any pair
             hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, colours, (int)(w * channels), channels, w, h, grays);
     }
+    if (rawf) {                                                    // the first stage of a raw frame: resize + grey
+        uint8_t* col = f->resize.colour.as<uint8_t>();
+        if (channels == 1) front_resize_launch<1>(c, f->resize, resize_colour, !resize_own, raws.p[0], gray, col);
+        else if (channels == 3) front_resize_launch<3>(c, f->resize, resize_colour, !resize_own, raws.p[0], gray, col);
+        else front_resize_launch<4>(c, f->resize, resize_colour, !resize_own, raws.p[0], gray, col);
+        if (resize_own)                                            // NRS_RESIZE_OWN_LAUNCH: the grey of the resized colour frame, as of any frame
+            hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, col, (int)(w * channels), channels, w, h, gray);
+    }
     if (right && !c->dbg.is_set(SW_FRONT_PER_EYE)) {               // the pair: one launch per shared stage, the eye in grid.z
         if (!raw) hipLaunchKernelGGL(k_front_gray_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, raws, (int)row, channels, w, h, grays);
         hipLaunchKernelGGL(k_front_clahe_lut_pair, dim3(f->tiles_x, f->tiles_y, 2), blk, 0, c->stream, grays, w, h, tw, th, clip, luts);
         hipLaunchKernelGGL(k_front_clahe_apply_pair, dim3(grid.x, grid.y, 2), blk, 0, c->stream, grays, w, h, tw, th, f->tiles_x, f->tiles_y, luts, clahes);
     } else {
         for (int e = 0; e < (right ? 2 : 1); ++e) {                // a single frame, or NRS_FRONT_PER_EYE: the right eye through the same three kernels
-            if (!raw) hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, raws.p[e], (int)row, channels, w, h, grays.p[e]);
+            if (!raw && !rawf) hipLaunchKernelGGL(k_front_gray, grid, blk, 0, c->stream, raws.p[e], (int)row, channels, w, h, grays.p[e]);
             hipLaunchKernelGGL(k_front_clahe_lut, dim3(f->tiles_x, f->tiles_y), blk, 0, c->stream, grays.p[e], w, h, tw, th, clip, luts.p[e]);
             hipLaunchKernelGGL(k_front_clahe_apply, grid, blk, 0, c->stream, grays.p[e], w, h, tw, th, f->tiles_x, f->tiles_y, luts.p[e], clahes.p[e]);
         }
@@ -584,6 +686,7 @@ static int front_run(nrs_ctx* c, const char* who, const uint8_t* img, const uint
     if (right && clahe_right_out) NRS_HIP(c, hipMemcpyAsync(clahe_right_out, f->clahe_r.p, n, hipMemcpyDeviceToHost, c->stream));
     if (raw && raw->rect_left_out) NRS_HIP(c, hipMemcpyAsync(raw->rect_left_out, f->rect.colour.p, n * channels, hipMemcpyDeviceToHost, c->stream));
     if (raw && raw->rect_right_out) NRS_HIP(c, hipMemcpyAsync(raw->rect_right_out, f->rect.colour_r.p, n * channels, hipMemcpyDeviceToHost, c->stream));
+    if (rawf && rawf->resized_out) NRS_HIP(c, hipMemcpyAsync(rawf->resized_out, f->resize.colour.p, n * channels, hipMemcpyDeviceToHost, c->stream));
     NRS_HIP(c, hipStreamSynchronize(c->stream));                  // (also what lets another context read the resident images afterwards)
     f->w = w; f->h = h; f->valid = true; f->valid_right = right != nullptr;
     return NRS_OK;
@@ -653,4 +756,57 @@ extern "C" int nrs_front_process_stereo_raw(nrs_ctx* c, const uint8_t* left, con
     const RawPair raw{rect_left_out, rect_right_out};
     return front_run(c, "nrs_front_process_stereo_raw", left, right, src_w, src_h, stride_l, stride_r, channels, gray_out, clahe_out, global_out,
                      filter_masks_out, gray_right_out, clahe_right_out, &raw);
+}
+
+// apps/endomapper.cc:65-69 (cv::resize to the configured size, once per frame): the tap tables, computed on the host and uploaded
+extern "C" int nrs_front_resize_configure(nrs_ctx* c, int32_t src_w, int32_t src_h, int32_t dst_w, int32_t dst_h) {
+    if (!c) return NRS_ERR_INVALID;
+    char msg[256];
+    if (resize_check_configure(src_w, src_h, dst_w, dst_h, msg, sizeof msg) != 0) return c->fail(NRS_ERR_INVALID, "%s", msg);
+    NRS_HIP(c, hipSetDevice(c->device));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    FrontState* f = front_default(c);
+    if (!f) return c->fail(NRS_ERR_ALLOC, "out of host memory");
+    f->valid = false; f->valid_right = false;                      // the resident frame is dropped; the filters and the maps stay
+    ResizeState& z = f->resize;
+    z.on = false;
+    const size_t n32 = (size_t)dst_w + 2 * (size_t)dst_h, n16 = 2 * ((size_t)dst_w + (size_t)dst_h);
+    std::vector<int32_t> i32;
+    std::vector<int16_t> i16;
+    try { i32.resize(n32); i16.resize(n16); } catch (const std::bad_alloc&) { return c->fail(NRS_ERR_ALLOC, "out of host memory"); }
+    resize_build_taps(src_w, src_h, dst_w, dst_h, i32.data(), i16.data(), i32.data() + dst_w, i16.data() + 2 * (size_t)dst_w);
+    NRS_TRY(c->ensure(z.tabs, n32 * sizeof(int32_t) + n16 * sizeof(int16_t)));
+    NRS_HIP(c, hipMemcpyAsync(z.tabs.p, i32.data(), n32 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipMemcpyAsync(z.tabs.as<int32_t>() + n32, i16.data(), n16 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));                   // (the vectors go when this returns)
+    z.sw = src_w; z.sh = src_h; z.dw = dst_w; z.dh = dst_h; z.box = resize_is_box(src_w, src_h, dst_w, dst_h); z.on = true;
+    return NRS_OK;
+}
+
+extern "C" int nrs_front_resize_taps(nrs_ctx* c, int32_t* sx, int16_t* ax, int32_t* sy, int16_t* by, int32_t* box) {
+    if (!c) return NRS_ERR_INVALID;
+    const FrontState* f = c->front;
+    if (!f || !f->resize.on) return c->fail(NRS_ERR_STATE, RESIZE_MSG_NONE, "nrs_front_resize_taps");
+    NRS_HIP(c, hipSetDevice(c->device));
+    const ResizeState& z = f->resize;
+    const size_t dw = (size_t)z.dw, dh = (size_t)z.dh;
+    const int32_t* i32 = z.tabs.as<int32_t>();
+    const int16_t* i16 = reinterpret_cast<const int16_t*>(i32 + dw + 2 * dh);
+    if (sx) NRS_HIP(c, hipMemcpyAsync(sx, i32, dw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (sy) NRS_HIP(c, hipMemcpyAsync(sy, i32 + dw, 2 * dh * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (ax) NRS_HIP(c, hipMemcpyAsync(ax, i16, 2 * dw * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    if (by) NRS_HIP(c, hipMemcpyAsync(by, i16 + 2 * dw, 2 * dh * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    NRS_HIP(c, hipStreamSynchronize(c->stream));
+    if (box) *box = z.box ? 1 : 0;
+    return NRS_OK;
+}
+
+// apps/endomapper.cc:65-69 (cv::resize of the frame) in front of nrs_front_process
+extern "C" int nrs_front_process_raw(nrs_ctx* c, const uint8_t* img, int32_t src_w, int32_t src_h, int32_t stride, int32_t channels,
+                                     uint8_t* gray_out, uint8_t* clahe_out, uint8_t* global_out, uint8_t* const* filter_masks_out,
+                                     uint8_t* resized_out) {
+    if (!c) return NRS_ERR_INVALID;
+    const RawFrame rawf{resized_out};
+    return front_run(c, "nrs_front_process_raw", img, nullptr, src_w, src_h, stride, 0, channels, gray_out, clahe_out, global_out, filter_masks_out,
+                     nullptr, nullptr, nullptr, &rawf);
 }

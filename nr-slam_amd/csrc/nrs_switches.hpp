@@ -99,6 +99,7 @@ constexpr bool HOST_PACK = true;     // (the row's mark "forces the host packer"
     X(STEREO_NO_MFMA,       SW_PRESENCE, 0,       "evaluation",    false,     "stereo pattern matcher: plain integer correlation") \
     X(FRONT_PER_EYE,        SW_PRESENCE, 0,       "front end",     false,     "nrs_front_process_stereo: grey and CLAHE issued per eye with the single-frame kernels, not as pair launches") \
     X(RECT_OWN_LAUNCH,      SW_PRESENCE, 0,       "front end",     false,     "nrs_front_process_stereo_raw: the remap into a rectified colour buffer, then the pair's grey kernel, not the fused launch") \
+    X(RESIZE_OWN_LAUNCH,    SW_PRESENCE, 0,       "front end",     false,     "nrs_front_process_raw: the resize into a colour buffer, then the ordinary grey kernel, not the fused launch") \
     X(DBND_NO_TILE,         SW_PRESENCE, 0,       "initialisation", false,    "nrs_dbscan_nd / nrs_flow_tracks_cluster: a wave per point with candidates from global memory, not the LDS tiles") \
     X(LIN_DBG,              SW_PRESENCE, 0,       "probes",       false,     "make PROBES=1: phase clocks of one lineariser launch") \
     X(SPMV_DBG,             SW_PRESENCE, 0,       "probes",        false,     "make PROBES=1: phase clocks of one operator launch") \

@@ -37,6 +37,7 @@ SYMBOLS = ["nrs_create", "nrs_options_init", "nrs_destroy", "nrs_last_error", "n
            "nrs_dbscan3d", "nrs_init_stereo_options_init", "nrs_init_stereo",
            "nrs_front_process_stereo", "nrs_stereo_match_pattern_front", "nrs_init_stereo_front", "nrs_stereo_match_lk_front",
            "nrs_front_rectify_configure", "nrs_front_rectify_maps", "nrs_front_process_stereo_raw",
+           "nrs_front_resize_configure", "nrs_front_resize_taps", "nrs_front_process_raw",
            "nrs_tbuf_create", "nrs_tbuf_destroy", "nrs_tbuf_clear", "nrs_tbuf_insert", "nrs_tbuf_info", "nrs_tbuf_flat", "nrs_map_frame_tbuf"]
 
 
@@ -132,6 +133,11 @@ def make_rect_eye(eye):
     return r
 
 
+def half_size(w, h):
+    """the newSize of the reference's Endomapper app (apps/endomapper.cc:65-69: cv::Size(cols / 2.0f, rows / 2.0f), truncated) -> (w, h)"""
+    return int(np.float32(w) / np.float32(2)), int(np.float32(h) / np.float32(2))
+
+
 class InitOptions(C.Structure):
     """nrs_init_options (f6)"""
     _fields_ = [("struct_size", C.c_uint32), ("n_hypotheses", C.c_int32), ("epipolar_threshold", C.c_float), ("radians_per_pixel", C.c_float),
@@ -202,6 +208,10 @@ def load_library(path=LIB_PATH):
     lib.nrs_front_rectify_configure.argtypes = [ptr, i32, i32, i32, i32, ptr, ptr]
     lib.nrs_front_rectify_maps.argtypes = [ptr, i32, ptr, ptr]
     lib.nrs_front_process_stereo_raw.argtypes = [ptr, ptr, ptr, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+    # frame resize (include/nrs.h "Frame resize")
+    lib.nrs_front_resize_configure.argtypes = [ptr, i32, i32, i32, i32]
+    lib.nrs_front_resize_taps.argtypes = [ptr, ptr, ptr, ptr, ptr, ptr]
+    lib.nrs_front_process_raw.argtypes = [ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]
     # flow-track clustering (include/nrs.h "f6")
     lib.nrs_dbscan_nd.argtypes = [ptr, i32, i32, ptr, C.c_double, i32, ptr, ptr]
     lib.nrs_flow_tracks_cluster.argtypes = [ptr, i32, i32, ptr, ptr, ptr, ptr]
@@ -772,6 +782,51 @@ class Context:
                                                         ptrs, _p(out.get("gray_right"), C.c_uint8), _p(out.get("clahe_right"), C.c_uint8),
                                                         _p(out.get("rect_left"), C.c_uint8), _p(out.get("rect_right"), C.c_uint8)))
         self._front_shape = (dh, dw)
+        return out
+
+    # ---- frame resize: the tables once, then raw frames into the resident frame
+    def front_resize_configure(self, src_wh, dst_wh):
+        """nrs_front_resize_configure: src_wh / dst_wh = (w, h) of a raw / a resized frame (half_size gives the Endomapper app's)"""
+        self._chk(self.lib.nrs_front_resize_configure(self.h, int(src_wh[0]), int(src_wh[1]), int(dst_wh[0]), int(dst_wh[1])))
+        self._resize_src, self._resize_dst = (int(src_wh[0]), int(src_wh[1])), (int(dst_wh[0]), int(dst_wh[1]))
+
+    def front_resize_taps(self):
+        """nrs_front_resize_taps -> dict(sx int32 [dst_w], ax int16 [dst_w, 2], sy int32 [dst_h, 2], by int16 [dst_h, 2], box 0 / 1)"""
+        dw, dh = getattr(self, "_resize_dst", (1, 1))                # (never configured: the library refuses)
+        out = dict(sx=np.zeros(dw, np.int32), ax=np.zeros((dw, 2), np.int16), sy=np.zeros((dh, 2), np.int32), by=np.zeros((dh, 2), np.int16))
+        box = C.c_int32(-1)
+        self._chk(self.lib.nrs_front_resize_taps(self.h, out["sx"].ctypes.data, out["ax"].ctypes.data, out["sy"].ctypes.data, out["by"].ctypes.data,
+                                                 C.addressof(box)))
+        out["box"] = int(box.value)
+        return out
+
+    def front_process_raw(self, img, outputs=True, stride=None, width=None, channels=1):
+        """nrs_front_process_raw: the RAW frame, resized on the device by the tables of front_resize_configure, then as front_process.  The
+        arguments are those of front_process, at the raw size; outputs: True, False or the names wanted of "gray", "clahe", "global", "masks",
+        "resized" (the resized frame, dst_h x dst_w or dst_h x dst_w x channels).  -> dict of those, all of the resized size"""
+        img = np.asarray(img, np.uint8)
+        if stride is None:
+            img = np.ascontiguousarray(img)
+            hh, ww = img.shape[:2]
+            ch = 1 if img.ndim == 2 else img.shape[2]
+            stride = img.strides[0] if hh else ww * ch
+        else:
+            hh, ww, ch = img.shape[0], int(width), int(channels)
+        dw, dh = getattr(self, "_resize_dst", (ww, hh))              # (never configured: the library refuses)
+        nf = getattr(self, "_front_n", 0)
+        want = ("gray", "clahe", "global", "masks", "resized") if outputs is True else tuple(outputs or ())
+        out = {k: np.zeros((dh, dw), np.uint8) for k in ("gray", "clahe", "global") if k in want}
+        if "resized" in want:
+            out["resized"] = np.zeros((dh, dw) if ch == 1 else (dh, dw, ch), np.uint8)
+        ptrs = None
+        if "masks" in want:
+            out["masks"] = [np.zeros((dh, dw), np.uint8) for _ in range(nf)]
+            if nf:
+                ptrs = (C.c_void_p * nf)(*[m.ctypes.data for m in out["masks"]])
+        self._chk(self.lib.nrs_front_process_raw(self.h, img.ctypes.data, ww, hh, int(stride), ch, _p(out.get("gray"), C.c_uint8),
+                                                 _p(out.get("clahe"), C.c_uint8), _p(out.get("global"), C.c_uint8), ptrs,
+                                                 _p(out.get("resized"), C.c_uint8)))
+        self._front_shape = (dh, dw)                                 # (after the call: a refused frame leaves the resident size as it was)
         return out
 
     def klt_set_reference_front(self, xy, image=FRONT_GRAY, use_global_mask=True, shape=None):

@@ -90,7 +90,7 @@ class GpuBackend:
     device_reuse=True PointReuse is one call on the main context and the second one is never made)."""
 
     def __init__(self, nrs, model, prm, klt_opts, dense_graph=False, cap_per_point=64, direct_solve=0, n_nodes=0, front=None, device_reuse=False,
-                 device_tbuf=False, rectify=None):
+                 device_tbuf=False, rectify=None, resize=None):
         """n_nodes > 0: EMBEDDED-DEFORMATION mode (include/nrs.h nrs_track_deform_solve_embedded; needs the dense graph): n_nodes map points
         (farthest-point sampling on the initial map, nrs_skin_select_nodes) carry the deformation vertices for the whole sequence, every
         other tracked point is skinned to <= 11 of them in the pose-and-deformation solve of each frame (tracking.cc:321-333's call).  Mapping
@@ -108,7 +108,11 @@ class GpuBackend:
         False (the default) = nrs_frame_loop.TemporalBuffer on the host, flattened and uploaded whole by every map_frame.
         rectify: None (the default) = a stereo pair handed to front_stereo is rectified already.  dict(src_wh=(w, h), dst_wh=(w, h), left=eye
         record, right=eye record) (nrs.Context.front_rectify_configure; needs the front mode) = front_stereo is handed the RAW eyes, as the
-        camera gives them, and rectifies them on the device (nrs_front_process_stereo_raw): every later step sees the rectified pair."""
+        camera gives them, and rectifies them on the device (nrs_front_process_stereo_raw): every later step sees the rectified pair.
+        resize: None (the default) = a frame handed to the loop has the size it is tracked at.  dict(src_wh=(w, h), dst_wh=(w, h))
+        (nrs.Context.front_resize_configure; needs the front mode; nrs.half_size gives the dst_wh of apps/endomapper.cc:65-69) = every
+        single-frame step is handed the RAW frame, as the video decoder gives it, and resizes it on the device (nrs_front_process_raw):
+        every later step sees the resized frame.  front_stereo is unaffected: no loader resizes a pair."""
         self.nrs = nrs
         self.device_tbuf, self.tb = bool(device_tbuf), None
         self.dense, self.cap, self.rg = dense_graph or n_nodes > 0, cap_per_point, None
@@ -129,6 +133,11 @@ class GpuBackend:
             if not self.front:
                 raise ValueError("rectify needs the front mode (front=True or a list of filters)")
             self.ctx.front_rectify_configure(rectify["src_wh"], rectify["dst_wh"], rectify["left"], rectify["right"])
+        self.resize = resize is not None
+        if self.resize:
+            if not self.front:
+                raise ValueError("resize needs the front mode (front=True or a list of filters)")
+            self.ctx.front_resize_configure(resize["src_wh"], resize["dst_wh"])
 
     @property
     def ctx_reuse(self):
@@ -137,10 +146,12 @@ class GpuBackend:
         return self._ctx_reuse
 
     # front mode: one nrs_front_process per frame.  The loop hands the SAME array to every step of a frame and starts each frame with
-    # klt_track, which therefore always processes; the later steps process only when they see another array
+    # klt_track, which therefore always processes; the later steps process only when they see another array.  With resize the frame is
+    # the raw one and the call is nrs_front_process_raw: what is resident afterwards, and the grey handed back, is the resized frame
     def _front_frame(self, im, force=False):
         if force or im is not self._front_im:
-            self._front_gray = self.ctx.front_process(im, outputs=("gray",))["gray"]
+            process = self.ctx.front_process_raw if self.resize else self.ctx.front_process
+            self._front_gray = process(im, outputs=("gray",))["gray"]
             self._front_im, self._front_right, self._front_fresh = im, None, None      # (a single frame invalidates the resident right eye)
             self.n_front_calls += 1
         return self._front_gray
