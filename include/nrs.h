@@ -943,7 +943,9 @@ int nrs_front_process_raw(nrs_ctx* ctx, const uint8_t* img, int32_t src_w, int32
  * not in `lost`, keeps its old position and its NRS_TRACKED status: callers find them as "status NRS_TRACKED and not listed
  * in lost" (farthest point sampling with n_nodes >= n_points / 10 leaves < 10 % of them on the synthetic frames).  This call chooses the nodes: farthest point
  * sampling over the eligible points (eligible == NULL: all), first pick = lowest eligible index, fp32 squared distances,
- * ties to the lowest index.  node_ids[n_nodes] in pick order.  NRS_ERR_INVALID if fewer points are eligible. */
+ * ties to the lowest index.  node_ids[n_nodes] in pick order.  NRS_ERR_INVALID if fewer points are eligible.
+ * An eligible point with a NaN or +-inf coordinate is refused (NRS_ERR_INVALID, the message names the first one; host scan, nothing is
+ * uploaded); a point that is not eligible may hold anything and cannot influence a pick. */
 int nrs_skin_select_nodes(nrs_ctx* ctx, int32_t n_points, const float* pos /* n_points x 3 */, const uint8_t* eligible /* nullable */,
                           int32_t n_nodes, int32_t* node_ids);
 

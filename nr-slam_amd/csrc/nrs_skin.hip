@@ -92,8 +92,13 @@ extern "C" int nrs_skin_select_nodes(nrs_ctx* c, int32_t n_points, const float* 
                                      int32_t* node_ids) {
     if (!c) return NRS_ERR_INVALID;
     if (!pos || !node_ids || n_points <= 0 || n_nodes <= 0 || n_nodes > n_points) return c->fail(NRS_ERR_INVALID, "nrs_skin_select_nodes: bad argument");
+    // an eligible point with a NaN or +-inf coordinate is refused: k_fps's `d2 < d` would skip a NaN distance and hand the point to
+    // stage 1 as a node.  A point that is not eligible (a lost one) may hold anything: no distance is computed for it
+    for (int32_t j = 0; j < n_points; ++j)
+        if ((!eligible || eligible[j]) && !(std::isfinite(pos[3 * (size_t)j]) && std::isfinite(pos[3 * (size_t)j + 1]) && std::isfinite(pos[3 * (size_t)j + 2])))
+            return c->fail(NRS_ERR_INVALID, "nrs_skin_select_nodes: eligible point %d has a non-finite position", j);
     NRS_HIP(c, hipSetDevice(c->device));
-    DevBuf d_out, d_mind, d_el, d_pos;                             // (freed when the call returns, d_pos first)
+    DevBuf d_out, d_mind, d_el, d_pos;                            // (freed when the call returns, d_pos first)
     NRS_TRY(c->ensure(d_pos, sizeof(float) * 3 * (size_t)n_points));
     NRS_TRY(c->ensure(d_mind, sizeof(float) * (size_t)n_points));
     NRS_TRY(c->ensure(d_out, sizeof(int) * ((size_t)n_nodes + 1)));

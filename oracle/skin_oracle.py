@@ -11,24 +11,32 @@ F32 = np.float32
 
 def select_nodes(pos, n_nodes, eligible=None):
     """pick 0 = lowest eligible index; pick k = eligible point with the largest fp32 squared distance
-    ((dx*dx + dy*dy) + dz*dz) to the picks so far, ties to the lowest index"""
+    ((dx*dx + dy*dy) + dz*dz) to the picks so far, ties to the lowest index.  A squared distance that overflows is +inf and ties
+    with every other +inf.  An eligible point with a NaN or +-inf coordinate is refused (ValueError naming the first one); a point
+    that is not eligible may hold anything: no distance is computed for it"""
     pos = np.asarray(pos, F32).reshape(-1, 3)
     n = len(pos)
     ok = np.ones(n, bool) if eligible is None else np.asarray(eligible).astype(bool)
+    bad = ok & ~np.isfinite(pos).all(1)
+    if bad.any():
+        raise ValueError("eligible point %d has a non-finite position" % int(np.argmax(bad)))
     if ok.sum() < n_nodes:
         raise ValueError("fewer eligible points than nodes")
-    mind = np.where(ok, F32(np.inf), F32(-1)).astype(F32)
-    pick = int(np.argmax(ok))
+    rows = np.nonzero(ok)[0]                                         # ascending: the first maximum below is the lowest index
+    p = pos[rows]
+    mind = np.full(len(rows), np.inf, F32)
+    at = 0
     out = []
     for k in range(n_nodes):
-        out.append(pick)
+        out.append(int(rows[at]))
         if k + 1 == n_nodes:
             break
-        d = pos - pos[pick]
-        d2 = ((d[:, 0] * d[:, 0]).astype(F32) + (d[:, 1] * d[:, 1]).astype(F32)).astype(F32)
-        d2 = (d2 + (d[:, 2] * d[:, 2]).astype(F32)).astype(F32)
+        with np.errstate(over="ignore"):
+            d = p - p[at]
+            d2 = ((d[:, 0] * d[:, 0]).astype(F32) + (d[:, 1] * d[:, 1]).astype(F32)).astype(F32)
+            d2 = (d2 + (d[:, 2] * d[:, 2]).astype(F32)).astype(F32)
         upd = mind >= 0
         mind[upd] = np.minimum(mind[upd], d2[upd])
-        mind[pick] = F32(-1)
-        pick = int(np.argmax(mind))                                  # first maximum = lowest index
+        mind[at] = F32(-1)
+        at = int(np.argmax(mind))                                    # first maximum = lowest index
     return np.asarray(out, np.int32)

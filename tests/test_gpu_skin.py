@@ -24,9 +24,10 @@ def test_node_selection_is_exact(ctx, n, m, seed):
     assert np.array_equal(ids, K.select_nodes(pos, m, el)) and el[ids].all() and len(set(ids.tolist())) == m
     with pytest.raises(nrs.NrsError):
         ctx.skin_select_nodes(pos, int(el.sum()) + 1, el)
-    # every point a node: all of them, each once
+    # every point a node: all of them, each once, in the oracle's pick order
     small = pos[:300]
-    assert sorted(ctx.skin_select_nodes(small, 300).tolist()) == list(range(300))
+    ids = ctx.skin_select_nodes(small, 300)
+    assert np.array_equal(ids, K.select_nodes(small, 300)) and sorted(ids.tolist()) == list(range(300))
 
 
 @pytest.mark.parametrize("n,m,seed,model", [(600, 120, 31, 0), (900, 150, 32, 1)])

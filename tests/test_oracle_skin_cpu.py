@@ -3,25 +3,7 @@ that define the sampling (distinct picks, non-increasing cover radius, eligibili
 import numpy as np
 
 import skin_oracle as K
-
-
-def _literal(pos, m, ok):
-    pos = pos.astype(np.float32)
-    sel = [int(np.argmax(ok))]
-    while len(sel) < m:
-        best, bi = np.float32(-1), -1
-        for j in range(len(pos)):
-            if not ok[j] or j in sel:
-                continue
-            dmin = np.float32(np.inf)
-            for s in sel:
-                d = pos[j] - pos[s]
-                d2 = np.float32(np.float32(d[0] * d[0]) + np.float32(d[1] * d[1])) + np.float32(d[2] * d[2])
-                dmin = min(dmin, np.float32(d2))
-            if dmin > best:
-                best, bi = dmin, j
-        sel.append(bi)
-    return np.asarray(sel, np.int32)
+from skin_cases import literal as _literal                          # (shared with tests/test_skin_cases_cpu.py)
 
 
 def test_matches_a_literal_loop_and_the_defining_properties():
